@@ -42,6 +42,10 @@ Secondary legs of the default workload, all in the same JSON line (never ``value
   ``engine_api``  the same models behind ``MarieHipOcrEngine.extract`` (host frames in, dictionaries out).
   ``det_passes_3``, ``pcie_inclusive``, ``parity`` (GPU vs oracle on the cpu_baseline sample).
 
+``--dump-outputs DIR`` (dit_trocr) writes the results of the last timed step as DIR/<name>.npy: det_boxes, det_scores and
+det_boxes_per_page of the detector, and rec_tokens (padded with -1), rec_lengths and rec_scores of the recognizer.  Inputs
+and weights are seeded, so two builds run with the same arguments can be compared array by array.
+
 Rank 0 prints ONE JSON line.  ``roofline`` covers the dominant kernel (conv_igemm, MFMA-bound): algorithmic FLOPs of all
 its launches in a step (2*MAC, real channel counts, accumulated by the launcher: mhip_profile_flops) divided by their
 summed device time, measured live with HIP events on the launch streams in one more step run exactly like the timed ones
@@ -313,6 +317,40 @@ def _checksum(records):
     return acc
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dit_trocr_step_arrays(per_page, hyps, width):
+    """What a caller of the dit_trocr step receives, as arrays: the detector's (boxes (n, 4) xyxy, scores (n,)) of every page
+    concatenated in page order with the count per page, and the recognizer's hypotheses (token ids padded with -1 to `width`,
+    lengths, length-normalised log-probabilities) in crop order."""
+    toks = np.full((len(hyps), width), -1, np.int64)
+    for i, (t, _) in enumerate(hyps):
+        toks[i, :len(t)] = t
+    return {"det_boxes": np.concatenate([b for b, _ in per_page]),
+            "det_scores": np.concatenate([s for _, s in per_page]),
+            "det_boxes_per_page": np.array([len(b) for b, _ in per_page]),
+            "rec_tokens": toks,
+            "rec_lengths": np.array([len(t) for t, _ in hyps]),
+            "rec_scores": np.array([s for _, s in hyps], np.float32)}
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """out_dir/<name>.npy for every array: floating values as float32, integer values (ids, counts) as float64, which holds
+    them exactly.  Above `limit` bytes in all, every array keeps the same share of its rows, chosen by a fixed seed, and
+    out_dir/<name>_rows.npy lists the rows kept."""
+    arrays = {k: np.asarray(v, np.float32 if np.issubdtype(np.asarray(v).dtype, np.floating) else np.float64)
+              for k, v in arrays.items()}
+    total = sum(a.nbytes + 8 * len(a) for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        if total > limit:
+            rows = np.sort(np.random.default_rng(0).choice(len(a), int(len(a) * limit / total), replace=False))
+            np.save(os.path.join(out_dir, f"{k}_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+
+
 def run_dit_trocr(args, torch, dist, rank, local_rank, world, prec):
     """BASELINE configs[2] (default), configs[3] (--stream-pages) and configs[4] (mixed-DPI leg): DiT-base detector +
     TrOCR-base recognizer, full pages, one GPU per rank."""
@@ -388,10 +426,10 @@ def run_dit_trocr(args, torch, dist, rank, local_rank, world, prec):
         for pz in range(det_passes[0]):
             for s0 in range(0, len(slots), DB):
                 ptrs = [cur["base"] + sl * page_bytes for sl in slots[s0:s0 + DB]]
-                for boxes, _scores in det.detect_device(ptrs, PAGE_H, PAGE_W):
+                for boxes, scores in det.detect_device(ptrs, PAGE_H, PAGE_W):
                     nb += len(boxes)
                     if pz == 0:
-                        per_page.append(len(boxes))
+                        per_page.append((boxes, scores))
         stats["boxes"] += nb // det_passes[0]
         last_det[0] = per_page
 
@@ -436,6 +474,8 @@ def run_dit_trocr(args, torch, dist, rank, local_rank, world, prec):
     fence()
     dt = time.perf_counter() - t0
     boxes_pp = stats["boxes"] / (args.steps * P)
+    if args.dump_outputs and rank == 0:      # before the legs below overwrite the last step's results
+        dump_outputs(args.dump_outputs, dit_trocr_step_arrays(last_det[0], last[0], rec.max_len + 1))
 
     def profiled(serial):
         for c in ctxs:
@@ -527,7 +567,7 @@ def run_dit_trocr(args, torch, dist, rank, local_rank, world, prec):
             hyps = last[0]
             for j, pi in enumerate(ids):
                 toks = [hyps[j * LINES_PER_PAGE + c][0].tolist() for c in range(LINES_PER_PAGE)]
-                local.append((pi, int(last_det[0][j]), toks))
+                local.append((pi, len(last_det[0][j][0]), toks))
         cur.update(saved)
         allrec = gather_in_order(local, total, dist)       # all_gather_object: variable-length records, page order
         fence()
@@ -921,9 +961,16 @@ def main():
                     help="extra steps with the pages fed from pinned host memory (dit_trocr, N=1; reported as pcie_inclusive)")
     ap.add_argument("--no-kernel-timing", action="store_true", help="no per-kernel HIP events in the timed region")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="dit_trocr: after the timed steps, write what the last timed step returned (rank 0's pages) as "
+                         "DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.workload == "pages":
         args.workload = "craft_crnn"
+    if args.dump_outputs and args.workload != "dit_trocr":
+        raise SystemExit("--dump-outputs is implemented for the dit_trocr workload only")
     if args.pages <= 0:
         args.pages = 64 if args.workload == "dit_trocr" else 12       # BASELINE configs[2]: 64 pages
     if args.gpus < 1:

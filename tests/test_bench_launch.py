@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -117,13 +118,84 @@ def test_all_legs_run_and_the_process_exits_cleanly():
     assert line["overlay"]["value"] > 0
 
 
-def test_symbol_error_rate_is_levenshtein_over_reference_length():
+def _bench_module():
     import importlib.util
 
     spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
     bench = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(bench)
+    return bench
+
+
+def test_symbol_error_rate_is_levenshtein_over_reference_length():
+    bench = _bench_module()
     assert bench._edit_rate([[1, 2, 3, 4]], [[1, 2, 4]]) == 0.25                 # one deletion
     assert bench._edit_rate([[1, 2], [3]], [[1, 2], [3]]) == 0.0
     assert bench._edit_rate([[1, 2, 3]], [[9, 9, 9, 9]]) == pytest.approx(4 / 3)  # three substitutions + one insertion
     assert bench._edit_rate([[5, 6]], [[]]) == 1.0
+
+
+def test_steps_below_one_are_refused():
+    r = _run(["--steps", "0"], timeout=120)
+    assert r.returncode != 0 and "--steps must be >= 1" in (r.stderr + r.stdout)
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    bench = _bench_module()
+    per_page = [(np.array([[1, 2, 3, 4], [5, 6, 7, 8.5]], np.float32), np.array([0.9, 0.8], np.float32)),
+                (np.zeros((0, 4), np.float32), np.zeros((0,), np.float32))]
+    hyps = [(np.array([7, 50264, 2], np.int32), -0.5), (np.array([2], np.int32), -1.25)]
+    bench.dump_outputs(str(tmp_path / "all"), bench.dit_trocr_step_arrays(per_page, hyps, 4))
+    got = {f[:-4]: np.load(tmp_path / "all" / f) for f in os.listdir(tmp_path / "all")}
+    assert sorted(got) == ["det_boxes", "det_boxes_per_page", "det_scores", "rec_lengths", "rec_scores", "rec_tokens"]
+    for k in ("det_boxes", "det_scores", "rec_scores"):
+        assert got[k].dtype == np.float32, k
+    for k in ("det_boxes_per_page", "rec_lengths", "rec_tokens"):
+        assert got[k].dtype == np.float64, k
+    np.testing.assert_array_equal(got["det_boxes"], per_page[0][0])
+    np.testing.assert_array_equal(got["det_scores"], per_page[0][1])
+    assert got["det_boxes_per_page"].tolist() == [2, 0]
+    np.testing.assert_array_equal(got["rec_tokens"], [[7, 50264, 2, -1], [2, -1, -1, -1]])
+    assert got["rec_lengths"].tolist() == [3, 1] and got["rec_scores"].tolist() == [-0.5, -1.25]
+
+    # over the limit: every array keeps the same seeded rows, listed beside it, and the whole stays within the limit
+    big = {"a": np.arange(4000, dtype=np.float32).reshape(1000, 4), "b": np.arange(1000)}
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), big, limit=8000)
+    out = [{f[:-4]: np.load(tmp_path / d / f) for f in os.listdir(tmp_path / d)} for d in ("s1", "s2")]
+    assert sorted(out[0]) == ["a", "a_rows", "b", "b_rows"]
+    for k in out[0]:
+        np.testing.assert_array_equal(out[0][k], out[1][k])
+    rows = out[0]["a_rows"].astype(np.int64)
+    assert 0 < len(rows) < 1000 and (np.diff(rows) > 0).all()
+    np.testing.assert_array_equal(out[0]["a"], big["a"][rows])
+    np.testing.assert_array_equal(out[0]["b"], big["b"][out[0]["b_rows"].astype(np.int64)])
+    assert sum(a.nbytes for a in out[0].values()) <= 8000
+
+
+DUMPED = ("det_boxes", "det_scores", "det_boxes_per_page", "rec_tokens", "rec_lengths", "rec_scores")
+
+
+@pytest.mark.gpu
+def test_dump_outputs_is_the_last_timed_step(tmp_path):
+    """With every leg after the timed region off, the line's sample_output and box count are the timed step's: the dump holds
+    them.  The inputs are seeded, so a run of three timed steps dumps the same results as a run of one."""
+    common = ["--gpus", "1", "--warmup", "1", "--pages", "4", "--det-batch", "4", "--decode-len", "3", "--stream-pages", "0",
+              "--no-mixed-dpi", "--no-cpu-baseline", "--no-kernel-timing", "--no-secondary", "--host-steps", "0"]
+    dumps = []
+    for steps in (1, 3):
+        r = _run(common + ["--steps", str(steps), "--dump-outputs", str(tmp_path / str(steps))])
+        assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
+        line = _json_line(r.stdout)
+        assert line["steps"] == steps and line["ms_per_step"] > 0
+        d = {k: np.load(tmp_path / str(steps) / f"{k}.npy") for k in DUMPED}
+        assert sorted(os.listdir(tmp_path / str(steps))) == sorted(f"{k}.npy" for k in DUMPED)
+        toks, score = line["sample_output"]
+        assert d["rec_tokens"].shape == (4 * 40, 3 + 1) and d["rec_lengths"].shape == d["rec_scores"].shape == (4 * 40,)
+        assert d["rec_tokens"][0, :len(toks)].tolist() == toks and (d["rec_tokens"][0, len(toks):] == -1).all()
+        assert d["rec_lengths"][0] == len(toks) and d["rec_scores"][0] == np.float32(score)
+        assert d["det_boxes_per_page"].shape == (4,) and d["det_boxes"].shape == (len(d["det_scores"]), 4)
+        assert d["det_boxes_per_page"].sum() == len(d["det_boxes"]) == round(line["config"]["detector_boxes_per_page"] * 4)
+        dumps.append(d)
+    for k in DUMPED:
+        np.testing.assert_array_equal(dumps[0][k], dumps[1][k], err_msg=k)
