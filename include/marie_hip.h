@@ -419,6 +419,17 @@ int mhip_trocr_generate_trace_host(mhip_trocr* m, const uint8_t* crops_host, int
  * (projected, scaled), enc [crops][n_tok][enc_dim], wk / wv [heads*64][enc_dim], bv [heads*64] -> out [crops*beam][heads*64]. */
 int mhip_cross_attention_host(mhip_ctx* ctx, const float* q, const float* enc, const float* wk, const float* wv,
                               const float* bv, int crops, int beam, int heads, int n_tok, int enc_dim, float* out);
+/* The decoder's decode attention alone (one layer, one step) on host inputs, through the kernels trocr_decode launches: the
+ * self-attention over a hypothesis' history and the encoder-attention over projected keys / values (fp32, and f16 without the
+ * absorbed path).  replaces: fairseq MultiheadAttention (self_attn with incremental state / encoder_attn) as
+ * TextRecognitionGenerator drives it, marie/models/unilm/trocr/generator.py:127-362.  Operands are rounded to the precision's
+ * element type and laid out with the production pitches.  q [rows][heads*64] (projected, scaled), rows = groups * nq.
+ *   anc != NULL (self-attention, nq = 1): k / v [n_keys][slots][heads*64], key s of row r at step s, slot anc[r*anc_ld + s];
+ *   anc == NULL (encoder-attention, nq queries per group): k / v [groups][kv_rows][heads*64], the first n_keys rows attended.
+ * force_generic: the generic kernel even where the f16 short-history kernel would run.  -> out [rows][heads*64].          */
+int mhip_decode_attention_host(mhip_ctx* ctx, int precision, int heads, int n_keys, int nq, int rows, int slots, int kv_rows,
+                               const float* q, const float* k, const float* v, const int32_t* anc, int anc_ld,
+                               int force_generic, float* out);
 
 /* ---- word-box / line geometry of the DiT box processor (host, pure functions; no ctx) --------------------------------- */
 /* replaces: merge_boxes, marie/utils/overlap.py:268-330 (find_overlap_horizontal(center_y_overlap=0.5) :106-183,

@@ -311,6 +311,7 @@ int mhip_launch_layernorm2(mhip_ctx* ctx, int precision, const float* x, const f
                            void* y_t, int rows, int D, float eps);
 int mhip_launch_embed_step(mhip_ctx* ctx, int precision, const int* tokens, const void* emb, const float* pos_row, float scale,
                            const float* g, const float* b, float* x, void* xt, int rows, int D, float eps);
+constexpr int DEC_ATTN_MAX_KEYS = 640;   // longest history / encoder sequence decode attention runs (its (4, 640) instantiation)
 struct DecAttnDesc {
   const void* q = nullptr;   // [groups*nq][ldq] T, pre-scaled
   const void* k = nullptr;
@@ -321,6 +322,7 @@ struct DecAttnDesc {
   int kv_rows = 0;           // cross-attention: k/v rows per group
   int ldq = 0, ldk = 0, ldo = 0;
   int heads = 0, groups = 0, nq = 1, n_keys = 0;
+  int force_generic = 0;     // skip the f16 short-history self-attention kernel (what MARIE_HIP_GENERIC_SELF_ATTN does per process)
 };
 int mhip_launch_decode_attention(mhip_ctx* ctx, int precision, const DecAttnDesc& d);
 // Encoder-attention of one decoder layer with the key / value projections absorbed (cross_attn.hip; f16 only):

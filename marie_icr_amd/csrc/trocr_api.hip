@@ -64,6 +64,8 @@ extern "C" int mhip_trocr_default_config(int model, mhip_trocr_config* c) {
   return MHIP_OK;
 }
 
+static int trocr_max_len(const mhip_trocr_config& c) { return std::min(c.max_len_b, c.max_positions - 1); }
+
 extern "C" int mhip_trocr_create(mhip_ctx* ctx, int precision, const mhip_trocr_config* cfg, mhip_trocr** out) {
   if (!ctx || !cfg || !out) return MHIP_EINVAL;
   *out = nullptr;
@@ -73,6 +75,10 @@ extern "C" int mhip_trocr_create(mhip_ctx* ctx, int precision, const mhip_trocr_
       c.vocab < 8 || c.beam < 1 || c.beam > 4 || c.img_size % 16 || c.max_len_b < 1 || c.max_positions < 2 ||
       c.pad < 0 || c.eos < 0 || c.pad >= c.vocab || c.eos >= c.vocab)
     return mhip_fail(ctx, MHIP_EINVAL, "trocr: unsupported configuration");
+  // the last step of a search attends over max_len + 1 keys of history: refuse here what would fail halfway through a search
+  if (trocr_max_len(c) + 1 > DEC_ATTN_MAX_KEYS)
+    return mhip_fail(ctx, MHIP_EINVAL, "trocr: max_len %d needs %d keys of self-attention history, decode attention runs at most %d",
+                     trocr_max_len(c), trocr_max_len(c) + 1, DEC_ATTN_MAX_KEYS);
   mhip_vit_config vc{};
   vc.dim = c.enc_dim; vc.depth = c.enc_depth; vc.heads = c.enc_heads; vc.patch = 16;
   vc.pos_h = vc.pos_w = c.img_size / 16;
@@ -244,8 +250,6 @@ extern "C" int mhip_trocr_set_decode_gate(mhip_trocr* m, mhip_gate* gate) {
   m->decode_gate = gate;
   return MHIP_OK;
 }
-
-static int trocr_max_len(const mhip_trocr_config& c) { return std::min(c.max_len_b, c.max_positions - 1); }
 
 extern "C" int mhip_trocr_max_len(const mhip_trocr_config* c) { return c ? trocr_max_len(*c) : MHIP_EINVAL; }
 
@@ -654,5 +658,88 @@ extern "C" int mhip_cross_attention_host(mhip_ctx* ctx, const float* q, const fl
   MHIP_HIP(ctx, hipMemcpyAsync(ho.data(), ao, ho.size() * 2, hipMemcpyDeviceToHost, ctx->stream));
   MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
   for (size_t i = 0; i < ho.size(); ++i) out[i] = (float)ho[i];
+  return MHIP_OK;
+}
+
+// The decoder's decode attention on caller-supplied host inputs, through mhip_launch_decode_attention as trocr_decode drives it
+// (operands rounded to the precision's element type, the production pitches): what the kernel-level tests compare with softmax
+// attention in fp64.  See include/marie_hip.h for the two layouts.
+template <typename T>
+static void to_elems(const float* src, size_t n, std::vector<char>& dst, size_t off, size_t count, size_t src_ld, size_t dst_ld) {
+  // count rows of n elements: src row i at src + i * src_ld -> dst element offset off + i * dst_ld
+  T* d = (T*)dst.data();
+  for (size_t i = 0; i < count; ++i)
+    for (size_t j = 0; j < n; ++j) d[off + i * dst_ld + j] = (T)src[i * src_ld + j];
+}
+
+extern "C" int mhip_decode_attention_host(mhip_ctx* ctx, int precision, int heads, int n_keys, int nq, int rows, int slots,
+                                          int kv_rows, const float* q, const float* k, const float* v, const int32_t* anc,
+                                          int anc_ld, int force_generic, float* out) {
+  if (!ctx || !q || !k || !v || !out) return MHIP_EINVAL;
+  if (precision != MHIP_PREC_F16 && precision != MHIP_PREC_F32) return mhip_fail(ctx, MHIP_EINVAL, "unknown precision %d", precision);
+  if (heads < 1 || heads > 16 || n_keys < 1 || nq < 1 || rows < 1 || rows % nq)
+    return mhip_fail(ctx, MHIP_EINVAL, "decode_attention_host: heads %d n_keys %d nq %d rows %d", heads, n_keys, nq, rows);
+  // the launcher judges n_keys and nq; here only what the host layout needs to stay inside its buffers
+  const bool self = anc != nullptr;
+  if (self && (nq != 1 || slots < 1 || anc_ld < std::min(n_keys, DEC_ATTN_MAX_KEYS + 1)))
+    return mhip_fail(ctx, MHIP_EINVAL, "decode_attention_host: self-attention needs nq 1, slots >= 1, anc_ld >= n_keys");
+  if (!self && kv_rows < n_keys) return mhip_fail(ctx, MHIP_EINVAL, "decode_attention_host: kv_rows %d < n_keys %d", kv_rows, n_keys);
+  const int hist = std::min(n_keys, DEC_ATTN_MAX_KEYS + 1);     // rows of history laid out (a rejected n_keys reads none)
+  if (self)
+    for (int r = 0; r < rows; ++r)
+      for (int s = 0; s < hist; ++s)
+        if (anc[(size_t)r * anc_ld + s] < 0 || anc[(size_t)r * anc_ld + s] >= slots)
+          return mhip_fail(ctx, MHIP_EINVAL, "decode_attention_host: ancestry slot out of range at row %d step %d", r, s);
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  const int D = heads * 64, groups = rows / nq;
+  const size_t es = precision == MHIP_PREC_F16 ? 2 : 4;
+  // self-attention: one [hist][slots][3 D] buffer, q | k | v of a step side by side (the q columns of the history are never read by
+  // the attention: NaN), the queries in a [rows][3 D] buffer of the same pitch.  cross: q [rows][D], k / v [groups][kv_rows][D].
+  const int ldq = self ? 3 * D : D, ldk = self ? 3 * D : D;
+  const size_t nq_el = (size_t)rows * ldq;
+  const size_t nk_el = self ? (size_t)hist * slots * ldk : (size_t)groups * kv_rows * D;
+  std::vector<char> hq(nq_el * es), hk(nk_el * es), hv(self ? 0 : nk_el * es);
+  auto fill_nan = [&](std::vector<char>& b) {
+    if (es == 2) std::fill((_Float16*)b.data(), (_Float16*)(b.data() + b.size()), (_Float16)NAN);
+    else std::fill((float*)b.data(), (float*)(b.data() + b.size()), NAN);
+  };
+  fill_nan(hq);
+  if (self) fill_nan(hk);
+  auto conv = [&](const float* src, std::vector<char>& dst, size_t off, size_t count, size_t dst_ld) {
+    if (es == 2) to_elems<_Float16>(src, D, dst, off, count, D, dst_ld);
+    else to_elems<float>(src, D, dst, off, count, D, dst_ld);
+  };
+  conv(q, hq, 0, rows, ldq);
+  if (self) {
+    conv(k, hk, D, (size_t)hist * slots, ldk);
+    conv(v, hk, 2 * D, (size_t)hist * slots, ldk);
+  } else {
+    conv(k, hk, 0, (size_t)groups * kv_rows, D);
+    conv(v, hv, 0, (size_t)groups * kv_rows, D);
+  }
+  const size_t anc_bytes = self ? (size_t)rows * anc_ld * 4 : 0, out_bytes = (size_t)rows * D * es;
+  int rc = mhip_ensure_workspace(ctx, hq.size() + hk.size() + hv.size() + anc_bytes + out_bytes + 5 * 256 + 4096);
+  if (rc) return rc;
+  Carver ws(ctx->ws);
+  char* dq = ws.take(hq.size());
+  char* dk = ws.take(hk.size());
+  char* dv = self ? dk : ws.take(hv.size());
+  int* danc = self ? ws.take<int>(anc_bytes) : nullptr;
+  char* dout = ws.take(out_bytes);
+  MHIP_HIP(ctx, hipMemcpyAsync(dq, hq.data(), hq.size(), hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(dk, hk.data(), hk.size(), hipMemcpyHostToDevice, ctx->stream));
+  if (!self) MHIP_HIP(ctx, hipMemcpyAsync(dv, hv.data(), hv.size(), hipMemcpyHostToDevice, ctx->stream));
+  if (self) MHIP_HIP(ctx, hipMemcpyAsync(danc, anc, anc_bytes, hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemsetAsync(dout, 0xff, out_bytes, ctx->stream));      // all-ones: NaN in f16 and fp32, a cell left unwritten shows
+  DecAttnDesc d;
+  d.q = dq; d.k = self ? dk + (size_t)D * es : dk; d.v = self ? dk + (size_t)2 * D * es : dv; d.out = dout;
+  d.anc = danc; d.anc_ld = anc_ld; d.slots = slots; d.kv_rows = kv_rows;
+  d.ldq = ldq; d.ldk = ldk; d.ldo = D; d.heads = heads; d.groups = groups; d.nq = nq; d.n_keys = n_keys;
+  d.force_generic = force_generic;
+  if ((rc = mhip_launch_decode_attention(ctx, precision, d))) return rc;
+  std::vector<char> ho(out_bytes);
+  MHIP_HIP(ctx, hipMemcpyAsync(ho.data(), dout, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (size_t i = 0; i < (size_t)rows * D; ++i) out[i] = es == 2 ? (float)((const _Float16*)ho.data())[i] : ((const float*)ho.data())[i];
   return MHIP_OK;
 }

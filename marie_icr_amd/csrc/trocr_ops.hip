@@ -518,14 +518,14 @@ int mhip_launch_embed_step(mhip_ctx* ctx, int precision, const int* tokens, cons
 }
 
 int mhip_launch_decode_attention(mhip_ctx* ctx, int precision, const DecAttnDesc& d) {
-  if (d.n_keys < 1 || d.n_keys > 640 || d.nq < 1 || d.nq > 4 || d.heads < 1 || d.groups < 1)
+  if (d.n_keys < 1 || d.n_keys > DEC_ATTN_MAX_KEYS || d.nq < 1 || d.nq > 4 || d.heads < 1 || d.groups < 1)
     return mhip_fail(ctx, MHIP_EINVAL, "decode_attention: n_keys %d nq %d", d.n_keys, d.nq);
   const bool small = d.nq == 1 && d.n_keys <= 256;   // self-attention over a short history: 4 KB of LDS, full occupancy
   DecAttnArgs a;
   a.q = d.q; a.k = d.k; a.v = d.v; a.out = d.out; a.anc = d.anc; a.anc_ld = d.anc_ld; a.slots = d.slots;
   a.kv_rows = d.kv_rows; a.ldq = d.ldq; a.ldk = d.ldk; a.ldo = d.ldo; a.n_keys = d.n_keys; a.nq = d.nq;
   static const bool generic_only = getenv("MARIE_HIP_GENERIC_SELF_ATTN") != nullptr;      // A/B aid
-  if (precision == MHIP_PREC_F16 && d.anc && d.nq == 1 && d.n_keys <= 64 && d.heads % 8 == 0 && !generic_only &&
+  if (precision == MHIP_PREC_F16 && d.anc && d.nq == 1 && d.n_keys <= 64 && d.heads % 8 == 0 && !generic_only && !d.force_generic &&
       d.ldq % 8 == 0 && d.ldk % 8 == 0 && d.ldo % 8 == 0) {
     PROF_LAUNCH(ctx, MHIP_K_DEC_OPS, hipLaunchKernelGGL(decode_self_attn_f16_kernel, dim3((d.groups + 3) / 4), dim3(256), 0, ctx->stream, a, d.heads, d.groups));
     CHECK_LAUNCH(ctx, "decode_self_attention");

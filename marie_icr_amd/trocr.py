@@ -283,7 +283,24 @@ class TrOcrProcessor(OcrProcessor):
         return out
 
     # ---- several page batches, one beam search (OcrEngine's batched path) ---------------------------------------------------
-    decode_batch = 4096      # crops per beam search: more than this many pending crops are decoded before the next batch is added
+    decode_batch = 4096      # upper limit of crops per beam search: more pending crops are decoded before the next batch is added
+    decode_budget_bytes: Optional[int] = None   # device memory one search's workspace may take; None: a quarter of the device's
+
+    def effective_decode_batch(self) -> int:
+        """Crops per beam search of the batched path: at most ``decode_batch``, and no more than a search whose workspace — with
+        the 1/8 headroom ``mhip_ensure_workspace`` adds — fits ``decode_budget_bytes``.  The q | k | v history is reserved for
+        max_len + 1 steps up front, so the bound follows the model's own max_len: ~56 MB per crop for TrOCR-base at the default
+        max_len 200 (1224 crops in a quarter of an MI355X's 309 GB), ~17 MB at max_len 15."""
+        lib, h = self.model.lib, self.model.h
+        budget = self.decode_budget_bytes
+        if budget is None:
+            budget = self.ctx.device_info()["hbm_bytes"] // 4
+        fits = lambda n: lib.mhip_trocr_workspace_bytes(h, n) * 9 // 8 <= budget
+        lo, hi = 1, max(1, int(self.decode_batch))          # workspace grows with n: the largest n that fits, by bisection
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            lo, hi = (mid, hi) if fits(mid) else (lo, mid - 1)
+        return lo
 
     def recognize_pages_begin(self, expected_pages: int = 0):
         """Start a call whose pages arrive in batches (``recognize_pages_add``) and are finished together
@@ -293,6 +310,7 @@ class TrOcrProcessor(OcrProcessor):
         self._pending = []          # (img shape, boxes, lines, n fragments) in arrival order
         self._done = []             # results of the pages already decoded
         self._pending_results = []  # fragment results of the pages in _pending that have been decoded (always empty or complete)
+        self._decode_limit = self.effective_decode_batch()
         self.model.encode_begin(0)
 
     def recognize_pages_add(self, pages):
@@ -304,7 +322,8 @@ class TrOcrProcessor(OcrProcessor):
         for img, boxes, fragments, lines in pages:
             img = self._check_inputs(img, boxes, fragments, lines)
             n = len(fragments) if len(boxes) else 0
-            if n and self.model.encoded() + n > self.decode_batch and self.model.encoded():
+            # known limit: a page whose own crop count exceeds the bound is still searched in one piece
+            if n and self.model.encoded() + n > self._decode_limit and self.model.encoded():
                 self._flush()
             if n:
                 frl = fragments if isinstance(fragments, FragmentList) else FragmentList(list(fragments))
