@@ -10,6 +10,8 @@ import ctypes as C
 import os
 import weakref
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MARIE_HIP_LIB selects another build of the same library (kernel A/B experiments); never a fallback
 LIB_PATH = os.environ.get("MARIE_HIP_LIB") or os.path.join(_HERE, "libmarie_hip.so")
@@ -291,6 +293,68 @@ class Context:
             for child in list(getattr(self, "_children", ())):
                 child.close()
             self.lib.mhip_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ModelHandle:
+    """Base of the model handles: one ``mhip_<stem>_*`` object of the library on a :class:`Context`.  It owns create +
+    ``ctx.adopt``, the state_dict upload (``set_tensor`` per tensor, then ``finalize``, which packs the device weight
+    arena), the arena entries of the RCCL start-up broadcast (marie_icr_amd/dist.py) and destroy."""
+
+    def __init__(self, ctx: Context, stem: str, *create_args):
+        self.ctx, self.lib, self._stem = ctx, ctx.lib, stem
+        h = C.c_void_p()
+        check(ctx.h, self._fn("create")(ctx.h, *create_args, C.byref(h)), f"mhip_{stem}_create")
+        self.h = h
+        ctx.adopt(self)
+
+    def _fn(self, what: str):
+        return getattr(self.lib, f"mhip_{self._stem}_{what}")
+
+    def _call(self, what: str, *args):
+        check(self.ctx.h, self._fn(what)(self.h, *args), f"mhip_{self._stem}_{what}")
+
+    def load_state(self, state):
+        """Every tensor of ``state`` (name -> array) to the library, then pack the arena (reference:
+        ``model.load_state_dict``).  The library strips a DataParallel ``module.`` prefix where the checkpoints carry one."""
+        set_tensor = self._fn("set_tensor")
+        for key, val in state.items():
+            arr = np.ascontiguousarray(np.asarray(val), dtype=np.float32)
+            shape = (C.c_int64 * max(arr.ndim, 1))(*arr.shape)
+            check(self.ctx.h, set_tensor(self.h, key.encode(), arr.ctypes.data_as(C.c_void_p), shape, arr.ndim),
+                  f"mhip_{self._stem}_set_tensor({key})")
+        self._call("finalize")
+
+    def alloc_arena(self):
+        """Allocate the arena(s) unfilled: the receiving ranks of the broadcast."""
+        self._call("alloc_arena")
+
+    def arena(self):
+        """(device pointer, bytes) of the packed weight arena of the single-arena models (CRAFT, CRNN, ICR, ViT): the
+        RCCL broadcast unit.  The overlay generator exposes no arena."""
+        p, n = C.c_void_p(), C.c_size_t()
+        self._call("arena", C.byref(p), C.byref(n))
+        return p.value, n.value
+
+    def arenas(self):
+        """[(device pointer, bytes), ...] of the models that keep two arenas (DiT, TrOCR: the ViT encoder, then the
+        heads / decoder)."""
+        out = []
+        for which in (0, 1):
+            p, n = C.c_void_p(), C.c_size_t()
+            self._call("arena", which, C.byref(p), C.byref(n))
+            out.append((p.value, n.value))
+        return out
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h.value:
+            self._fn("destroy")(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):

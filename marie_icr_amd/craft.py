@@ -22,46 +22,22 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-from ._lib import PREC_F16, PREC_F32, Context, MarieHipError, check
+from ._lib import PREC_F16, PREC_F32, Context, MarieHipError, ModelHandle, check
 from .box_processor import PSMode, find_line_number
-from .weights import strip_module_prefix
 
 
-class CraftModel:
-    """Device-resident CRAFT weights + forward/detect.  Thin handle over ``mhip_craft``."""
+class CraftModel(ModelHandle):
+    """Device-resident CRAFT weights + forward/detect.  Thin handle over ``mhip_craft``; ``load_state`` is the
+    reference's net.load_state_dict(copyStateDict(torch.load(...))), craft_box_processor.py:272-278."""
 
     def __init__(self, ctx: Context, state: Optional[Dict[str, np.ndarray]], precision: int = PREC_F16,
                  max_boxes: int = 65536):
-        self.ctx = ctx
-        self.lib = ctx.lib
         self.precision = int(precision)
         self.max_boxes = int(max_boxes)
-        h = C.c_void_p()
-        check(ctx.h, self.lib.mhip_craft_create(ctx.h, self.precision, C.byref(h)), "mhip_craft_create")
-        self.h = h
-        ctx.adopt(self)
+        super().__init__(ctx, "craft", self.precision)
         self._boxes = np.empty((self.max_boxes, 4, 2), np.float32)
         if state is not None:
             self.load_state(state)
-
-    def load_state(self, state: Dict[str, np.ndarray]):
-        """reference: net.load_state_dict(copyStateDict(torch.load(...))), craft_box_processor.py:272-278."""
-        for key, val in strip_module_prefix(state).items():
-            arr = np.ascontiguousarray(np.asarray(val), dtype=np.float32)
-            shape = (C.c_int64 * max(arr.ndim, 1))(*arr.shape)
-            check(self.ctx.h,
-                  self.lib.mhip_craft_set_tensor(self.h, key.encode(), arr.ctypes.data_as(C.c_void_p), shape, arr.ndim),
-                  f"mhip_craft_set_tensor({key})")
-        check(self.ctx.h, self.lib.mhip_craft_finalize(self.h), "mhip_craft_finalize")
-
-    def alloc_arena(self):
-        check(self.ctx.h, self.lib.mhip_craft_alloc_arena(self.h), "mhip_craft_alloc_arena")
-
-    def arena(self):
-        p = C.c_void_p()
-        n = C.c_size_t()
-        check(self.ctx.h, self.lib.mhip_craft_arena(self.h, C.byref(p), C.byref(n)), "mhip_craft_arena")
-        return p.value, n.value
 
     def geometry(self, h: int, w: int, canvas_size: int, mag_ratio: float = 1.0):
         r = C.c_double()
@@ -113,17 +89,6 @@ class CraftModel:
         return {self.lib.mhip_kernel_name(k).decode():
                 self.lib.mhip_craft_kernel_flops(self.h, k, int(h), int(w), canvas, float(mag_ratio))
                 for k in range(self.lib.mhip_kernel_count())}
-
-    def close(self):
-        if getattr(self, "h", None) is not None and self.h.value:
-            self.lib.mhip_craft_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def adjust_result_coordinates(polys: np.ndarray, ratio_w: float, ratio_h: float, ratio_net: int = 2) -> np.ndarray:

@@ -17,49 +17,24 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import PREC_F16, PREC_F32, Context, MarieHipError, check
+from ._lib import PREC_F16, PREC_F32, Context, MarieHipError, ModelHandle, check
 from .ocr_processor import OcrProcessor
-from .weights import CRNN_CHARSET, strip_module_prefix
+from .weights import CRNN_CHARSET
 
 IMG_H = 32
 
 
-class CrnnModel:
-    """Device-resident recognizer weights + forward.  Thin handle over ``mhip_crnn``."""
+class CrnnModel(ModelHandle):
+    """Device-resident recognizer weights + forward.  Thin handle over ``mhip_crnn``; ``load_state`` is
+    the reference's ``model.load_state_dict(torch.load(...))`` (craft_ocr_processor.py:146)."""
 
     def __init__(self, ctx: Context, state: Optional[Dict[str, np.ndarray]], num_class: int,
                  precision: int = PREC_F16):
-        self.ctx = ctx
-        self.lib = ctx.lib
         self.num_class = int(num_class)
         self.precision = int(precision)
-        h = C.c_void_p()
-        check(ctx.h, self.lib.mhip_crnn_create(ctx.h, self.precision, self.num_class, C.byref(h)), "mhip_crnn_create")
-        self.h = h
-        ctx.adopt(self)
+        super().__init__(ctx, "crnn", self.precision, self.num_class)
         if state is not None:
             self.load_state(state)
-
-    # -- weights ------------------------------------------------------------------------
-    def load_state(self, state: Dict[str, np.ndarray]):
-        """reference: ``model.load_state_dict(torch.load(...))`` craft_ocr_processor.py:146."""
-        for key, val in strip_module_prefix(state).items():
-            arr = np.ascontiguousarray(np.asarray(val), dtype=np.float32)
-            shape = (C.c_int64 * max(arr.ndim, 1))(*arr.shape)
-            check(self.ctx.h,
-                  self.lib.mhip_crnn_set_tensor(self.h, key.encode(), arr.ctypes.data_as(C.c_void_p), shape, arr.ndim),
-                  f"mhip_crnn_set_tensor({key})")
-        check(self.ctx.h, self.lib.mhip_crnn_finalize(self.h), "mhip_crnn_finalize")
-
-    def alloc_arena(self):
-        check(self.ctx.h, self.lib.mhip_crnn_alloc_arena(self.h), "mhip_crnn_alloc_arena")
-
-    def arena(self):
-        """(device pointer, bytes) of the single packed weight arena (RCCL broadcast unit)."""
-        p = C.c_void_p()
-        n = C.c_size_t()
-        check(self.ctx.h, self.lib.mhip_crnn_arena(self.h, C.byref(p), C.byref(n)), "mhip_crnn_arena")
-        return p.value, n.value
 
     # -- forward --------------------------------------------------------------------------
     def seq_len(self, w: int) -> int:
@@ -147,17 +122,6 @@ class CrnnModel:
 
     def workspace_bytes(self, n: int, w: int) -> int:
         return int(self.lib.mhip_crnn_workspace_bytes(self.h, int(n), int(w)))
-
-    def close(self):
-        if getattr(self, "h", None) is not None and self.h.value:
-            self.lib.mhip_crnn_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def tokens_to_text(tokens: np.ndarray, lengths: np.ndarray, charset: str) -> List[str]:

@@ -167,6 +167,12 @@ size_t mhip_lstm_wpack_bytes(int precision);
 int mhip_lstm_xproj_row(int col);
 // host-side packing of W_hh (fwd, bwd: [1024][256] fp32, gate order i,f,g,o) into fragment order
 void mhip_lstm_pack_whh(int precision, const float* whh_fwd, const float* whh_bwd, void* dst);
+// host-side packing of one bidirectional BidirectionalLSTM block (`prefix` "SequenceModeling.<j>."; CRNN and ICR):
+// W_ih rows permuted to the xproj column order at `precision` [2][1024][in], b_ih + b_hh fp32 [2][1024], W_hh via
+// mhip_lstm_pack_whh, and the linear layer ([256][512] at `precision`, bias fp32 [256])
+struct TensorStore;
+int mhip_lstm_pack_bilstm(mhip_ctx* ctx, const TensorStore& st, const std::string& prefix, int in, int precision,
+                          char* ih_w, float* ih_b, char* hh_pack, char* lin_w, float* lin_b);
 
 // greedy CTC decode
 int mhip_launch_ctc_decode(mhip_ctx* ctx, const float* logits, int n, int T, int C, int32_t* argmax,

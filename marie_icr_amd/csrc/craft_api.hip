@@ -6,16 +6,10 @@
 #include <math.h>
 
 #include <algorithm>
-#include <map>
 
-#include "common.h"
+#include "weights_util.h"
 
 namespace {
-
-struct HostTensor {
-  std::vector<int64_t> shape;
-  std::vector<float> data;
-};
 
 // forward-order conv table; `cinp`/`coutp` are the channel counts the kernels see (thin layers are zero-padded
 // to 64 so every layer is a multiple of the MFMA K slice and of the 16-byte lane vector).
@@ -56,18 +50,15 @@ const CLayer kL[27] = {
 };
 constexpr int NL = 27;
 
-size_t al256(size_t v) { return (v + 255) / 256 * 256; }
-
 }  // namespace
 
 struct mhip_craft {
   mhip_ctx* ctx = nullptr;
   int precision = MHIP_PREC_F16;
-  std::map<std::string, HostTensor> tensors;
+  TensorStore store;
   size_t w_off[NL] = {0}, s_off[NL] = {0}, b_off[NL] = {0};
   size_t head_off = 0;   // fp32 [w1 16x16][b1 16][w2 2x16][b2 2] of conv_cls.6 / conv_cls.8 for the fused score head
-  size_t arena_bytes = 0;
-  char* arena = nullptr;
+  Arena arena;
   bool ready = false;
   // pinned host staging for the post-processing read-back
   void* hpin = nullptr;
@@ -78,33 +69,15 @@ struct mhip_craft {
 namespace {
 
 void craft_layout(mhip_craft* m) {
-  size_t o = 0;
+  Arena& a = m->arena;
   for (int i = 0; i < NL; ++i) {
     const CLayer& L = kL[i];
-    const size_t wbytes = (i == 0) ? (size_t)27 * 64 * 4 : (size_t)L.coutp * L.k * L.k * L.cinp * m->esz();
-    m->w_off[i] = o;
-    o = al256(o + wbytes);
-    m->s_off[i] = o;
-    o = al256(o + (size_t)std::max(L.coutp, 64) * 4);
-    m->b_off[i] = o;
-    o = al256(o + (size_t)std::max(L.coutp, 64) * 4);
+    const std::string k = L.key;
+    m->w_off[i] = a.take(k + ".w", i == 0 ? (size_t)27 * 64 * 4 : (size_t)L.coutp * L.k * L.k * L.cinp * m->esz());
+    m->s_off[i] = a.take(k + ".s", (size_t)std::max(L.coutp, 64) * 4);
+    m->b_off[i] = a.take(k + ".b", (size_t)std::max(L.coutp, 64) * 4);
   }
-  m->head_off = o;
-  o = al256(o + (256 + 16 + 32 + 2) * 4);
-  m->arena_bytes = o;
-}
-
-const HostTensor* cfind(const mhip_craft* m, const std::string& k, std::initializer_list<int64_t> shape) {
-  auto it = m->tensors.find(k);
-  if (it == m->tensors.end()) {
-    mhip_fail(m->ctx, MHIP_ESTATE, "missing tensor %s", k.c_str());
-    return nullptr;
-  }
-  if (it->second.shape != std::vector<int64_t>(shape)) {
-    mhip_fail(m->ctx, MHIP_EINVAL, "tensor %s has the wrong shape", k.c_str());
-    return nullptr;
-  }
-  return &it->second;
+  m->head_off = a.take("score_head", (256 + 16 + 32 + 2) * 4);
 }
 
 }  // namespace
@@ -125,7 +98,7 @@ extern "C" int mhip_craft_create(mhip_ctx* ctx, int precision, mhip_craft** out)
 extern "C" int mhip_craft_destroy(mhip_craft* m) {
   if (!m) return MHIP_OK;
   mhip_quiesce(m->ctx);
-  if (m->arena) (void)hipFree(m->arena);
+  m->arena.release();
   if (m->hpin) (void)hipHostFree(m->hpin);
   delete m;
   return MHIP_OK;
@@ -134,97 +107,45 @@ extern "C" int mhip_craft_destroy(mhip_craft* m) {
 extern "C" int mhip_craft_set_tensor(mhip_craft* m, const char* key, const float* data, const int64_t* shape,
                                      int ndim) {
   if (!m || !key) return MHIP_EINVAL;
-  std::string k(key);
-  if (k.rfind("module.", 0) == 0) k = k.substr(7);   // copyStateDict (marie/boxes/box_processor.py) strips it too
-  if (k.size() > 19 && k.compare(k.size() - 19, 19, "num_batches_tracked") == 0) return MHIP_OK;
-  bool known = k.rfind("basenet.", 0) == 0 || k.rfind("upconv", 0) == 0 || k.rfind("conv_cls.", 0) == 0;
-  if (!known) return mhip_fail(m->ctx, MHIP_EINVAL, "unknown state_dict key %s", key);
-  if (!data || ndim < 0 || ndim > 4 || (ndim > 0 && !shape)) return mhip_fail(m->ctx, MHIP_EINVAL, "bad tensor %s", key);
-  HostTensor t;
-  size_t n = 1;
-  for (int i = 0; i < ndim; ++i) {
-    if (shape[i] <= 0) return mhip_fail(m->ctx, MHIP_EINVAL, "bad shape for %s", key);
-    t.shape.push_back(shape[i]);
-    n *= (size_t)shape[i];
-  }
-  t.data.assign(data, data + n);
-  m->tensors[k] = std::move(t);
-  m->ready = false;
-  return MHIP_OK;
+  // copyStateDict (marie/boxes/box_processor.py) strips `module.` too
+  return set_conv_model_tensor(m->ctx, m->store, m->ready, key, {"basenet.", "upconv", "conv_cls."}, data, shape, ndim);
 }
 
 extern "C" int mhip_craft_alloc_arena(mhip_craft* m) {
   if (!m) return MHIP_EINVAL;
-  if (!m->arena && hipMalloc((void**)&m->arena, m->arena_bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return mhip_fail(m->ctx, MHIP_ENOMEM, "arena allocation of %zu bytes failed", m->arena_bytes);
-  }
+  int rc = m->arena.alloc(m->ctx);
+  if (rc) return rc;
   m->ready = true;
   return MHIP_OK;
 }
 
 extern "C" int mhip_craft_arena(mhip_craft* m, void** dev, size_t* bytes) {
   if (!m) return MHIP_EINVAL;
-  if (dev) *dev = m->arena;
-  if (bytes) *bytes = m->arena_bytes;
+  if (dev) *dev = m->arena.dev;
+  if (bytes) *bytes = m->arena.bytes;
   return MHIP_OK;
 }
 
 extern "C" int mhip_craft_finalize(mhip_craft* m) {
   if (!m) return MHIP_EINVAL;
   mhip_ctx* ctx = m->ctx;
-  std::vector<char> host(m->arena_bytes, 0);
-  char* h = host.data();
+  const TensorStore& st = m->store;
+  m->arena.begin_fill();
+  char* h = m->arena.host.data();
   for (int i = 0; i < NL; ++i) {
     const CLayer& L = kL[i];
-    const HostTensor* w = cfind(m, std::string(L.key) + ".weight", {L.co, L.ci, L.k, L.k});
-    const HostTensor* b = cfind(m, std::string(L.key) + ".bias", {L.co});
-    if (!w || !b) return MHIP_ESTATE;
-    const int taps = L.k * L.k;
-    if (i == 0) {  // [64][3][3][3] -> [(tap*3 + c)][64] fp32 for the VALU first layer
-      float* dw = (float*)(h + m->w_off[0]);
-      for (int o = 0; o < 64; ++o)
-        for (int c = 0; c < 3; ++c)
-          for (int t = 0; t < 9; ++t) dw[(t * 3 + c) * 64 + o] = w->data[((size_t)o * 3 + c) * 9 + t];
-    } else {       // [Co][Ci][k][k] -> [Cop][k][k][Cip], zero padded
-      std::vector<float> tmp((size_t)L.coutp * taps * L.cinp, 0.f);
-      for (int o = 0; o < L.co; ++o)
-        for (int c = 0; c < L.ci; ++c)
-          for (int t = 0; t < taps; ++t)
-            tmp[((size_t)o * taps + t) * L.cinp + c] = w->data[((size_t)o * L.ci + c) * taps + t];
-      if (m->precision == MHIP_PREC_F16) {
-        _Float16* d = (_Float16*)(h + m->w_off[i]);
-        for (size_t q = 0; q < tmp.size(); ++q) d[q] = (_Float16)tmp[q];
-      } else {
-        memcpy(h + m->w_off[i], tmp.data(), tmp.size() * 4);
-      }
-    }
-    float* sc = (float*)(h + m->s_off[i]);
-    float* bi = (float*)(h + m->b_off[i]);
-    const int np = std::max(L.coutp, 64);
-    for (int o = 0; o < np; ++o) {
-      sc[o] = 1.f;
-      bi[o] = 0.f;      // padded output channels: 0 * x + 0 -> ReLU -> 0
-    }
-    for (int o = 0; o < L.co; ++o) bi[o] = b->data[o];
-    if (L.bn) {
-      const HostTensor* g = cfind(m, std::string(L.bn) + ".weight", {L.co});
-      const HostTensor* be = cfind(m, std::string(L.bn) + ".bias", {L.co});
-      const HostTensor* mu = cfind(m, std::string(L.bn) + ".running_mean", {L.co});
-      const HostTensor* va = cfind(m, std::string(L.bn) + ".running_var", {L.co});
-      if (!g || !be || !mu || !va) return MHIP_ESTATE;
-      for (int o = 0; o < L.co; ++o) {
-        const float s = g->data[o] / sqrtf(va->data[o] + 1e-5f);
-        sc[o] = s;
-        bi[o] = be->data[o] + (bi[o] - mu->data[o]) * s;
-      }
-    }
+    const HostTensor* w = st.find(ctx, std::string(L.key) + ".weight", {L.co, L.ci, L.k, L.k});
+    if (!w) return MHIP_ESTATE;
+    if (i == 0) pack_first_conv_weight((float*)(h + m->w_off[0]), *w, 64, 3, 9);   // fp32 for the VALU first layer
+    else pack_conv_weight(m->precision, h + m->w_off[i], *w, L.co, L.ci, L.k * L.k, L.coutp, L.cinp);
+    if (fold_conv_bn(ctx, st, L.key, true, L.bn, L.co, L.coutp, (float*)(h + m->s_off[i]), (float*)(h + m->b_off[i])))
+      return MHIP_ESTATE;
   }
   {
-    const HostTensor* w1 = cfind(m, "conv_cls.6.weight", {16, 16, 1, 1});
-    const HostTensor* b1 = cfind(m, "conv_cls.6.bias", {16});
-    const HostTensor* w2 = cfind(m, "conv_cls.8.weight", {2, 16, 1, 1});
-    const HostTensor* b2 = cfind(m, "conv_cls.8.bias", {2});
+    const HostTensor* w1 = st.find(ctx, "conv_cls.6.weight", {16, 16, 1, 1});
+    const HostTensor* b1 = st.find(ctx, "conv_cls.6.bias", {16});
+    const HostTensor* w2 = st.find(ctx, "conv_cls.8.weight", {2, 16, 1, 1});
+    const HostTensor* b2 = st.find(ctx, "conv_cls.8.bias", {2});
     if (!w1 || !b1 || !w2 || !b2) return MHIP_ESTATE;
     float* hd = (float*)(h + m->head_off);
     for (int i = 0; i < 256; ++i) {
@@ -238,12 +159,11 @@ extern "C" int mhip_craft_finalize(mhip_craft* m) {
     }
     memcpy(hd + 304, b2->data.data(), 2 * 4);
   }
-  int rc = mhip_craft_alloc_arena(m);
-  if (rc) return rc;
   m->ready = false;
-  MHIP_HIP(ctx, hipMemcpy(m->arena, h, m->arena_bytes, hipMemcpyHostToDevice));
+  int rc = m->arena.upload(ctx);
+  if (rc) return rc;
   m->ready = true;
-  m->tensors.clear();
+  m->store.t.clear();
   return MHIP_OK;
 }
 
@@ -333,7 +253,7 @@ extern "C" int mhip_craft_forward(mhip_craft* m, const uint8_t* page_dev, int h,
                                   double mag_ratio, float* scores_dev) {
   if (!m) return MHIP_EINVAL;
   mhip_ctx* ctx = m->ctx;
-  if (!m->ready || !m->arena) return mhip_fail(ctx, MHIP_ESTATE, "craft: weights not finalized");
+  if (!m->ready || !m->arena.dev) return mhip_fail(ctx, MHIP_ESTATE, "craft: weights not finalized");
   if (!page_dev || !scores_dev) return mhip_fail(ctx, MHIP_EINVAL, "craft: null buffer");
   CPlan p;
   if (make_cplan(m, h, w, canvas_size, mag_ratio, &p)) return mhip_fail(ctx, MHIP_EINVAL, "craft: bad page %dx%d", h, w);
@@ -342,7 +262,7 @@ extern "C" int mhip_craft_forward(mhip_craft* m, const uint8_t* page_dev, int h,
   int rc = mhip_ensure_workspace(ctx, p.total);
   if (rc) return rc;
   char* ws = (char*)ctx->ws;
-  const char* A = m->arena;
+  const char* A = m->arena.dev;
   const int prec = m->precision;
   const int H = p.H, W = p.W;
 

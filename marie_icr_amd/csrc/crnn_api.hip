@@ -5,10 +5,9 @@
 #include <math.h>
 #include <stdarg.h>
 
-#include <map>
 #include <memory>
 
-#include "common.h"
+#include "weights_util.h"
 
 // ======================================================================= context
 int mhip_fail(mhip_ctx* ctx, int code, const char* fmt, ...) {
@@ -229,11 +228,6 @@ extern "C" int mhip_conv2d_nhwc(mhip_ctx* ctx, int precision, const mhip_conv_de
 // ======================================================================= CRNN model
 namespace {
 
-struct HostTensor {
-  std::vector<int64_t> shape;
-  std::vector<float> data;
-};
-
 struct ConvSpec {
   const char* key;
   int co, ci, kh, kw;
@@ -251,16 +245,15 @@ const ConvSpec kConvs[7] = {
     {"FeatureExtraction.ConvNet.18", 512, 512, 2, 2, true, nullptr},
 };
 
-struct Arena {
-  // byte offsets into the device arena
+// byte offsets of the weight blocks in the device arena
+struct Layout {
   size_t conv0_w = 0, conv0_b = 0;
   size_t conv_w[7] = {0}, conv_scale[7] = {0}, conv_bias[7] = {0};
   size_t ih_w[2] = {0}, ih_b[2] = {0}, hh_pack[2] = {0}, lin_w[2] = {0}, lin_b[2] = {0};
   size_t pred_w = 0, pred_b = 0;
-  size_t bytes = 0;
 };
 
-size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
+size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 }  // namespace
 
@@ -268,9 +261,9 @@ struct mhip_crnn {
   mhip_ctx* ctx = nullptr;
   int precision = MHIP_PREC_F16;
   int num_class = 0;
-  std::map<std::string, HostTensor> tensors;
-  Arena lay;
-  char* arena = nullptr;
+  TensorStore store;
+  Layout lay;
+  Arena arena;
   bool ready = false;
   size_t esz() const { return precision == MHIP_PREC_F16 ? 2 : 4; }
 };
@@ -278,55 +271,29 @@ struct mhip_crnn {
 namespace {
 
 void build_layout(mhip_crnn* m) {
-  Arena& L = m->lay;
+  Layout& L = m->lay;
+  Arena& a = m->arena;
   const size_t es = m->esz();
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    size_t at = o;
-    o = align_up(o + bytes);
-    return at;
-  };
-  L.conv0_w = take(9 * 64 * 4);
-  L.conv0_b = take(64 * 4);
+  L.conv0_w = a.take("conv0_w", 9 * 64 * 4);
+  L.conv0_b = a.take("conv0_b", 64 * 4);
   for (int i = 1; i < 7; ++i) {
     const ConvSpec& c = kConvs[i];
-    L.conv_w[i] = take((size_t)c.co * c.ci * c.kh * c.kw * es);
-    L.conv_scale[i] = take((size_t)c.co * 4);
-    L.conv_bias[i] = take((size_t)c.co * 4);
+    const std::string k = c.key;
+    L.conv_w[i] = a.take(k + ".w", (size_t)c.co * c.ci * c.kh * c.kw * es);
+    L.conv_scale[i] = a.take(k + ".s", (size_t)c.co * 4);
+    L.conv_bias[i] = a.take(k + ".b", (size_t)c.co * 4);
   }
   for (int j = 0; j < 2; ++j) {
-    int in = j == 0 ? 512 : 256;
-    L.ih_w[j] = take((size_t)2048 * in * es);
-    L.ih_b[j] = take(2048 * 4);
-    L.hh_pack[j] = take(mhip_lstm_wpack_bytes(m->precision));
-    L.lin_w[j] = take((size_t)256 * 512 * es);
-    L.lin_b[j] = take(256 * 4);
+    const int in = j == 0 ? 512 : 256;
+    const std::string p = "lstm" + std::to_string(j);
+    L.ih_w[j] = a.take(p + ".ih_w", (size_t)2048 * in * es);
+    L.ih_b[j] = a.take(p + ".ih_b", 2048 * 4);
+    L.hh_pack[j] = a.take(p + ".hh_pack", mhip_lstm_wpack_bytes(m->precision));
+    L.lin_w[j] = a.take(p + ".lin_w", (size_t)256 * 512 * es);
+    L.lin_b[j] = a.take(p + ".lin_b", 256 * 4);
   }
-  L.pred_w = take((size_t)m->num_class * 256 * es);
-  L.pred_b = take((size_t)m->num_class * 4);
-  L.bytes = o;
-}
-
-void put(const mhip_crnn* m, char* dst, const float* src, size_t n) {
-  if (m->precision == MHIP_PREC_F16) {
-    _Float16* d = (_Float16*)dst;
-    for (size_t i = 0; i < n; ++i) d[i] = (_Float16)src[i];
-  } else {
-    memcpy(dst, src, n * 4);
-  }
-}
-
-const HostTensor* find(const mhip_crnn* m, const std::string& k, std::initializer_list<int64_t> shape) {
-  auto it = m->tensors.find(k);
-  if (it == m->tensors.end()) {
-    mhip_fail(m->ctx, MHIP_ESTATE, "missing tensor %s", k.c_str());
-    return nullptr;
-  }
-  if (it->second.shape != std::vector<int64_t>(shape)) {
-    mhip_fail(m->ctx, MHIP_EINVAL, "tensor %s has the wrong shape", k.c_str());
-    return nullptr;
-  }
-  return &it->second;
+  L.pred_w = a.take("pred_w", (size_t)m->num_class * 256 * es);
+  L.pred_b = a.take("pred_b", (size_t)m->num_class * 4);
 }
 
 }  // namespace
@@ -348,10 +315,8 @@ extern "C" int mhip_crnn_create(mhip_ctx* ctx, int precision, int num_class, mhi
 
 extern "C" int mhip_crnn_destroy(mhip_crnn* m) {
   if (!m) return MHIP_OK;
-  if (m->arena) {
-    mhip_quiesce(m->ctx);
-    (void)hipFree(m->arena);
-  }
+  if (m->arena.dev) mhip_quiesce(m->ctx);
+  m->arena.release();
   delete m;
   return MHIP_OK;
 }
@@ -359,141 +324,69 @@ extern "C" int mhip_crnn_destroy(mhip_crnn* m) {
 extern "C" int mhip_crnn_set_tensor(mhip_crnn* m, const char* key, const float* data, const int64_t* shape,
                                     int ndim) {
   if (!m || !key) return MHIP_EINVAL;
-  std::string k(key);
-  if (k.rfind("module.", 0) == 0) k = k.substr(7);
-  if (k.size() > 19 && k.compare(k.size() - 19, 19, "num_batches_tracked") == 0) return MHIP_OK;
-  bool known = k.rfind("FeatureExtraction.ConvNet.", 0) == 0 || k.rfind("SequenceModeling.", 0) == 0 ||
-               k.rfind("Prediction.", 0) == 0;
-  if (!known) return mhip_fail(m->ctx, MHIP_EINVAL, "unknown state_dict key %s", key);
-  if (!data || ndim < 0 || ndim > 4 || (ndim > 0 && !shape))
-    return mhip_fail(m->ctx, MHIP_EINVAL, "bad tensor %s", key);
-  HostTensor t;
-  size_t n = 1;
-  for (int i = 0; i < ndim; ++i) {
-    if (shape[i] <= 0) return mhip_fail(m->ctx, MHIP_EINVAL, "bad shape for %s", key);
-    t.shape.push_back(shape[i]);
-    n *= (size_t)shape[i];
-  }
-  t.data.assign(data, data + n);
-  m->tensors[k] = std::move(t);
-  m->ready = false;
-  return MHIP_OK;
+  return set_conv_model_tensor(m->ctx, m->store, m->ready, key,
+                               {"FeatureExtraction.ConvNet.", "SequenceModeling.", "Prediction."}, data, shape, ndim);
 }
 
 extern "C" int mhip_crnn_alloc_arena(mhip_crnn* m) {
   if (!m) return MHIP_EINVAL;
-  if (!m->arena) {
-    if (hipMalloc((void**)&m->arena, m->lay.bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      return mhip_fail(m->ctx, MHIP_ENOMEM, "arena allocation of %zu bytes failed", m->lay.bytes);
-    }
-  }
+  int rc = m->arena.alloc(m->ctx);
+  if (rc) return rc;
   m->ready = true;  // contents are the caller's responsibility (RCCL broadcast)
   return MHIP_OK;
 }
 
 extern "C" int mhip_crnn_arena(mhip_crnn* m, void** dev, size_t* bytes) {
   if (!m) return MHIP_EINVAL;
-  if (dev) *dev = m->arena;
-  if (bytes) *bytes = m->lay.bytes;
+  if (dev) *dev = m->arena.dev;
+  if (bytes) *bytes = m->arena.bytes;
   return MHIP_OK;
 }
 
 extern "C" int mhip_crnn_finalize(mhip_crnn* m) {
   if (!m) return MHIP_EINVAL;
   mhip_ctx* ctx = m->ctx;
-  const Arena& L = m->lay;
-  const size_t es = m->esz();
-  std::vector<char> host(L.bytes, 0);
-  char* h = host.data();
+  const TensorStore& st = m->store;
+  const Layout& L = m->lay;
+  const int prec = m->precision;
+  m->arena.begin_fill();
+  char* h = m->arena.host.data();
 
   // conv0: [64][1][3][3] -> tap-major [9][64] fp32
   {
-    const HostTensor* w = find(m, std::string(kConvs[0].key) + ".weight", {64, 1, 3, 3});
-    const HostTensor* b = find(m, std::string(kConvs[0].key) + ".bias", {64});
+    const HostTensor* w = st.find(ctx, std::string(kConvs[0].key) + ".weight", {64, 1, 3, 3});
+    const HostTensor* b = st.find(ctx, std::string(kConvs[0].key) + ".bias", {64});
     if (!w || !b) return MHIP_ESTATE;
-    float* dw = (float*)(h + L.conv0_w);
-    for (int c = 0; c < 64; ++c)
-      for (int k = 0; k < 9; ++k) dw[k * 64 + c] = w->data[c * 9 + k];
+    pack_first_conv_weight((float*)(h + L.conv0_w), *w, 64, 1, 9);
     memcpy(h + L.conv0_b, b->data.data(), 64 * 4);
   }
   // conv1..6: [Co][Ci][kh][kw] -> [Co][kh][kw][Ci]; BN folded to per-channel scale/shift (fp32 epilogue)
   for (int i = 1; i < 7; ++i) {
     const ConvSpec& c = kConvs[i];
-    const HostTensor* w = find(m, std::string(c.key) + ".weight", {c.co, c.ci, c.kh, c.kw});
+    const HostTensor* w = st.find(ctx, std::string(c.key) + ".weight", {c.co, c.ci, c.kh, c.kw});
     if (!w) return MHIP_ESTATE;
-    std::vector<float> tmp((size_t)c.co * c.ci * c.kh * c.kw);
-    const int taps = c.kh * c.kw;
-    for (int o = 0; o < c.co; ++o)
-      for (int ci = 0; ci < c.ci; ++ci)
-        for (int t = 0; t < taps; ++t)
-          tmp[((size_t)o * taps + t) * c.ci + ci] = w->data[((size_t)o * c.ci + ci) * taps + t];
-    put(m, h + L.conv_w[i], tmp.data(), tmp.size());
-    float* sc = (float*)(h + L.conv_scale[i]);
-    float* bi = (float*)(h + L.conv_bias[i]);
-    for (int o = 0; o < c.co; ++o) {
-      sc[o] = 1.f;
-      bi[o] = 0.f;
-    }
-    if (c.has_bias) {
-      const HostTensor* b = find(m, std::string(c.key) + ".bias", {c.co});
-      if (!b) return MHIP_ESTATE;
-      memcpy(bi, b->data.data(), (size_t)c.co * 4);
-    }
-    if (c.bn) {
-      const HostTensor* g = find(m, std::string(c.bn) + ".weight", {c.co});
-      const HostTensor* be = find(m, std::string(c.bn) + ".bias", {c.co});
-      const HostTensor* mu = find(m, std::string(c.bn) + ".running_mean", {c.co});
-      const HostTensor* va = find(m, std::string(c.bn) + ".running_var", {c.co});
-      if (!g || !be || !mu || !va) return MHIP_ESTATE;
-      for (int o = 0; o < c.co; ++o) {
-        float s = g->data[o] / sqrtf(va->data[o] + 1e-5f);  // nn.BatchNorm2d eps
-        sc[o] = s;
-        bi[o] = be->data[o] + (bi[o] - mu->data[o]) * s;
-      }
-    }
+    pack_conv_weight(prec, h + L.conv_w[i], *w, c.co, c.ci, c.kh * c.kw, c.co, c.ci);
+    if (fold_conv_bn(ctx, st, c.key, c.has_bias, c.bn, c.co, c.co, (float*)(h + L.conv_scale[i]),
+                     (float*)(h + L.conv_bias[i])))
+      return MHIP_ESTATE;
   }
-  // BiLSTM layers
-  for (int j = 0; j < 2; ++j) {
-    const int in = j == 0 ? 512 : 256;
-    const std::string p = "SequenceModeling." + std::to_string(j) + ".";
-    const HostTensor* wih[2] = {find(m, p + "rnn.weight_ih_l0", {1024, in}),
-                                find(m, p + "rnn.weight_ih_l0_reverse", {1024, in})};
-    const HostTensor* whh[2] = {find(m, p + "rnn.weight_hh_l0", {1024, 256}),
-                                find(m, p + "rnn.weight_hh_l0_reverse", {1024, 256})};
-    const HostTensor* bih[2] = {find(m, p + "rnn.bias_ih_l0", {1024}), find(m, p + "rnn.bias_ih_l0_reverse", {1024})};
-    const HostTensor* bhh[2] = {find(m, p + "rnn.bias_hh_l0", {1024}), find(m, p + "rnn.bias_hh_l0_reverse", {1024})};
-    const HostTensor* lw = find(m, p + "linear.weight", {256, 512});
-    const HostTensor* lb = find(m, p + "linear.bias", {256});
-    for (int d = 0; d < 2; ++d)
-      if (!wih[d] || !whh[d] || !bih[d] || !bhh[d]) return MHIP_ESTATE;
-    if (!lw || !lb) return MHIP_ESTATE;
-    // rows permuted so the GEMM writes xproj gate-interleaved, the order lstm.hip consumes
-    for (int d = 0; d < 2; ++d) {
-      float* bb = (float*)(h + L.ih_b[j]) + d * 1024;
-      for (int col = 0; col < 1024; ++col) {
-        const int n = mhip_lstm_xproj_row(col);
-        put(m, h + L.ih_w[j] + ((size_t)d * 1024 + col) * in * es, wih[d]->data.data() + (size_t)n * in, (size_t)in);
-        bb[col] = bih[d]->data[n] + bhh[d]->data[n];
-      }
-    }
-    mhip_lstm_pack_whh(m->precision, whh[0]->data.data(), whh[1]->data.data(), h + L.hh_pack[j]);
-    put(m, h + L.lin_w[j], lw->data.data(), (size_t)256 * 512);
-    memcpy(h + L.lin_b[j], lb->data.data(), 256 * 4);
-  }
+  for (int j = 0; j < 2; ++j)
+    if (mhip_lstm_pack_bilstm(ctx, st, "SequenceModeling." + std::to_string(j) + ".", j == 0 ? 512 : 256, prec,
+                              h + L.ih_w[j], (float*)(h + L.ih_b[j]), h + L.hh_pack[j], h + L.lin_w[j],
+                              (float*)(h + L.lin_b[j])))
+      return MHIP_ESTATE;
   {
-    const HostTensor* w = find(m, "Prediction.weight", {m->num_class, 256});
-    const HostTensor* b = find(m, "Prediction.bias", {m->num_class});
+    const HostTensor* w = st.find(ctx, "Prediction.weight", {m->num_class, 256});
+    const HostTensor* b = st.find(ctx, "Prediction.bias", {m->num_class});
     if (!w || !b) return MHIP_ESTATE;
-    put(m, h + L.pred_w, w->data.data(), (size_t)m->num_class * 256);
+    Arena::put(prec, h + L.pred_w, w->data.data(), (size_t)m->num_class * 256);
     memcpy(h + L.pred_b, b->data.data(), (size_t)m->num_class * 4);
   }
-  int rc = mhip_crnn_alloc_arena(m);
-  if (rc) return rc;
   m->ready = false;
-  MHIP_HIP(ctx, hipMemcpy(m->arena, h, L.bytes, hipMemcpyHostToDevice));
+  int rc = m->arena.upload(ctx);
+  if (rc) return rc;
   m->ready = true;
-  m->tensors.clear();  // host copies are no longer needed
+  m->store.t.clear();  // host copies are no longer needed
   return MHIP_OK;
 }
 
@@ -581,15 +474,15 @@ extern "C" int mhip_crnn_forward(mhip_crnn* m, const uint8_t* crops, int n, int 
   int rc = check_shape(m, n, w);
   if (rc) return rc;
   mhip_ctx* ctx = m->ctx;
-  if (!m->ready || !m->arena) return mhip_fail(ctx, MHIP_ESTATE, "crnn: weights not finalized");
+  if (!m->ready || !m->arena.dev) return mhip_fail(ctx, MHIP_ESTATE, "crnn: weights not finalized");
   if (!crops || !argmax || !tokens || !lengths || !conf) return mhip_fail(ctx, MHIP_EINVAL, "crnn: null buffer");
   MHIP_HIP(ctx, hipSetDevice(ctx->device));
   const Plan p = make_plan(m, n, w);
   rc = mhip_ensure_workspace(ctx, p.total);
   if (rc) return rc;
   char* ws = (char*)ctx->ws;
-  const Arena& L = m->lay;
-  const char* A = m->arena;
+  const Layout& L = m->lay;
+  const char* A = m->arena.dev;
   const int prec = m->precision;
   const int w2 = w / 2, w4 = w / 4, T = p.T;
 

@@ -6,14 +6,9 @@
 
 #include <map>
 
-#include "common.h"
+#include "weights_util.h"
 
 namespace {
-
-struct HostTensor {
-  std::vector<int64_t> shape;
-  std::vector<float> data;
-};
 
 // conv + BatchNorm pairs in forward/state_dict order (marie_icr_amd/weights.py::icr_conv_table mirrors this)
 struct CB {
@@ -49,8 +44,6 @@ std::vector<CB> build_table() {
   return t;
 }
 
-size_t al256(size_t v) { return (v + 255) / 256 * 256; }
-
 }  // namespace
 
 struct mhip_icr {
@@ -59,14 +52,13 @@ struct mhip_icr {
   int num_class = 96;
   std::vector<CB> tab;
   std::map<std::string, int> tab_index;
-  std::map<std::string, HostTensor> tensors;
+  TensorStore store;
   // arena offsets
   std::vector<size_t> w_off, s_off, b_off;
   size_t fc1_w = 0, fc1_b = 0, fc2_w = 0, fc2_b = 0, idc = 0, phat = 0;
   size_t ih_w[2] = {0}, ih_b[2] = {0}, hh_pack[2] = {0}, lin_w[2] = {0}, lin_b[2] = {0};
   size_t i2h_w = 0, hg_w = 0, hg_b = 0, score_w = 0, ihc_w = 0, onehot_w = 0, gen_w = 0, gen_b = 0;
-  size_t arena_bytes = 0;
-  char* arena = nullptr;
+  Arena arena;
   bool ready = false;
   size_t esz() const { return precision == MHIP_PREC_F16 ? 2 : 4; }
 };
@@ -76,13 +68,8 @@ namespace {
 constexpr int IMG_H = 32, IMG_W = 100, NFID = 20, MAXLEN = 48, STEPS = MAXLEN + 1;
 
 void icr_layout(mhip_icr* m) {
-  size_t o = 0;
+  Arena& a = m->arena;
   const size_t es = m->esz();
-  auto take = [&](size_t bytes) {
-    size_t at = o;
-    o = al256(o + bytes);
-    return at;
-  };
   const size_t n = m->tab.size();
   m->w_off.resize(n);
   m->s_off.resize(n);
@@ -90,55 +77,33 @@ void icr_layout(mhip_icr* m) {
   for (size_t i = 0; i < n; ++i) {
     const CB& c = m->tab[i];
     const bool gray = c.ci == 1;
-    m->w_off[i] = take(gray ? (size_t)9 * c.co * 4 : (size_t)c.cop * c.k * c.k * c.cip * es);
-    m->s_off[i] = take((size_t)std::max(c.cop, 64) * 4);
-    m->b_off[i] = take((size_t)std::max(c.cop, 64) * 4);
+    m->w_off[i] = a.take(c.conv + ".w", gray ? (size_t)9 * c.co * 4 : (size_t)c.cop * c.k * c.k * c.cip * es);
+    m->s_off[i] = a.take(c.conv + ".s", (size_t)std::max(c.cop, 64) * 4);
+    m->b_off[i] = a.take(c.conv + ".b", (size_t)std::max(c.cop, 64) * 4);
   }
-  m->fc1_w = take((size_t)256 * 512 * es);
-  m->fc1_b = take(256 * 4);
-  m->fc2_w = take((size_t)2 * NFID * 256 * es);
-  m->fc2_b = take(2 * NFID * 4);
-  m->idc = take((size_t)(NFID + 3) * (NFID + 3) * 4);
-  m->phat = take((size_t)IMG_H * IMG_W * (NFID + 3) * 4);
+  m->fc1_w = a.take("fc1_w", (size_t)256 * 512 * es);
+  m->fc1_b = a.take("fc1_b", 256 * 4);
+  m->fc2_w = a.take("fc2_w", (size_t)2 * NFID * 256 * es);
+  m->fc2_b = a.take("fc2_b", 2 * NFID * 4);
+  m->idc = a.take("inv_delta_C", (size_t)(NFID + 3) * (NFID + 3) * 4);
+  m->phat = a.take("P_hat", (size_t)IMG_H * IMG_W * (NFID + 3) * 4);
   for (int j = 0; j < 2; ++j) {
     const int in = j == 0 ? 512 : 256;
-    m->ih_w[j] = take((size_t)2048 * in * es);
-    m->ih_b[j] = take(2048 * 4);
-    m->hh_pack[j] = take(mhip_lstm_wpack_bytes(m->precision));
-    m->lin_w[j] = take((size_t)256 * 512 * es);
-    m->lin_b[j] = take(256 * 4);
+    const std::string p = "lstm" + std::to_string(j);
+    m->ih_w[j] = a.take(p + ".ih_w", (size_t)2048 * in * es);
+    m->ih_b[j] = a.take(p + ".ih_b", 2048 * 4);
+    m->hh_pack[j] = a.take(p + ".hh_pack", mhip_lstm_wpack_bytes(m->precision));
+    m->lin_w[j] = a.take(p + ".lin_w", (size_t)256 * 512 * es);
+    m->lin_b[j] = a.take(p + ".lin_b", 256 * 4);
   }
-  m->i2h_w = take((size_t)256 * 256 * es);
-  m->hg_w = take((size_t)1280 * 256 * es);
-  m->hg_b = take(1280 * 4);
-  m->score_w = take(256 * 4);
-  m->ihc_w = take((size_t)1024 * 256 * es);
-  m->onehot_w = take((size_t)m->num_class * 1024 * 4);
-  m->gen_w = take((size_t)m->num_class * 256 * es);
-  m->gen_b = take((size_t)m->num_class * 4);
-  m->arena_bytes = o;
-}
-
-const HostTensor* ifind(const mhip_icr* m, const std::string& k, std::vector<int64_t> shape) {
-  auto it = m->tensors.find(k);
-  if (it == m->tensors.end()) {
-    mhip_fail(m->ctx, MHIP_ESTATE, "missing tensor %s", k.c_str());
-    return nullptr;
-  }
-  if (it->second.shape != shape) {
-    mhip_fail(m->ctx, MHIP_EINVAL, "tensor %s has the wrong shape", k.c_str());
-    return nullptr;
-  }
-  return &it->second;
-}
-
-void putT(const mhip_icr* m, char* dst, const float* src, size_t n) {
-  if (m->precision == MHIP_PREC_F16) {
-    _Float16* d = (_Float16*)dst;
-    for (size_t i = 0; i < n; ++i) d[i] = (_Float16)src[i];
-  } else {
-    memcpy(dst, src, n * 4);
-  }
+  m->i2h_w = a.take("i2h_w", (size_t)256 * 256 * es);
+  m->hg_w = a.take("hg_w", (size_t)1280 * 256 * es);
+  m->hg_b = a.take("hg_b", 1280 * 4);
+  m->score_w = a.take("score_w", 256 * 4);
+  m->ihc_w = a.take("ihc_w", (size_t)1024 * 256 * es);
+  m->onehot_w = a.take("onehot_w", (size_t)m->num_class * 1024 * 4);
+  m->gen_w = a.take("gen_w", (size_t)m->num_class * 256 * es);
+  m->gen_b = a.take("gen_b", (size_t)m->num_class * 4);
 }
 
 }  // namespace
@@ -164,148 +129,89 @@ extern "C" int mhip_icr_create(mhip_ctx* ctx, int precision, int num_class, mhip
 extern "C" int mhip_icr_destroy(mhip_icr* m) {
   if (!m) return MHIP_OK;
   mhip_quiesce(m->ctx);
-  if (m->arena) (void)hipFree(m->arena);
+  m->arena.release();
   delete m;
   return MHIP_OK;
 }
 
 extern "C" int mhip_icr_set_tensor(mhip_icr* m, const char* key, const float* data, const int64_t* shape, int ndim) {
   if (!m || !key) return MHIP_EINVAL;
-  std::string k(key);
-  if (k.rfind("module.", 0) == 0) k = k.substr(7);
-  if (k.size() > 19 && k.compare(k.size() - 19, 19, "num_batches_tracked") == 0) return MHIP_OK;
-  bool known = k.rfind("Transformation.", 0) == 0 || k.rfind("FeatureExtraction.ConvNet.", 0) == 0 ||
-               k.rfind("SequenceModeling.", 0) == 0 || k.rfind("Prediction.", 0) == 0;
-  if (!known) return mhip_fail(m->ctx, MHIP_EINVAL, "unknown state_dict key %s", key);
-  if (!data || ndim < 0 || ndim > 4 || (ndim > 0 && !shape)) return mhip_fail(m->ctx, MHIP_EINVAL, "bad tensor %s", key);
-  HostTensor t;
-  size_t n = 1;
-  for (int i = 0; i < ndim; ++i) {
-    if (shape[i] <= 0) return mhip_fail(m->ctx, MHIP_EINVAL, "bad shape for %s", key);
-    t.shape.push_back(shape[i]);
-    n *= (size_t)shape[i];
-  }
-  t.data.assign(data, data + n);
-  m->tensors[k] = std::move(t);
-  m->ready = false;
-  return MHIP_OK;
+  return set_conv_model_tensor(m->ctx, m->store, m->ready, key,
+                               {"Transformation.", "FeatureExtraction.ConvNet.", "SequenceModeling.", "Prediction."},
+                               data, shape, ndim);
 }
 
 extern "C" int mhip_icr_alloc_arena(mhip_icr* m) {
   if (!m) return MHIP_EINVAL;
-  if (!m->arena && hipMalloc((void**)&m->arena, m->arena_bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return mhip_fail(m->ctx, MHIP_ENOMEM, "arena allocation of %zu bytes failed", m->arena_bytes);
-  }
+  int rc = m->arena.alloc(m->ctx);
+  if (rc) return rc;
   m->ready = true;
   return MHIP_OK;
 }
 
 extern "C" int mhip_icr_arena(mhip_icr* m, void** dev, size_t* bytes) {
   if (!m) return MHIP_EINVAL;
-  if (dev) *dev = m->arena;
-  if (bytes) *bytes = m->arena_bytes;
+  if (dev) *dev = m->arena.dev;
+  if (bytes) *bytes = m->arena.bytes;
   return MHIP_OK;
 }
 
 extern "C" int mhip_icr_finalize(mhip_icr* m) {
   if (!m) return MHIP_EINVAL;
   mhip_ctx* ctx = m->ctx;
+  const TensorStore& st = m->store;
   const size_t es = m->esz();
-  const int C = m->num_class;
-  std::vector<char> host(m->arena_bytes, 0);
-  char* h = host.data();
+  const int C = m->num_class, prec = m->precision;
+  m->arena.begin_fill();
+  char* h = m->arena.host.data();
   for (size_t i = 0; i < m->tab.size(); ++i) {
     const CB& c = m->tab[i];
-    const HostTensor* w = ifind(m, c.conv + ".weight", {c.co, c.ci, c.k, c.k});
+    const HostTensor* w = st.find(ctx, c.conv + ".weight", {c.co, c.ci, c.k, c.k});
     if (!w) return MHIP_ESTATE;
-    const int taps = c.k * c.k;
-    if (c.ci == 1) {   // [Co][1][3][3] -> [9][Co] fp32 for the VALU first-layer kernel
-      float* dw = (float*)(h + m->w_off[i]);
-      for (int o = 0; o < c.co; ++o)
-        for (int t = 0; t < 9; ++t) dw[t * c.co + o] = w->data[(size_t)o * 9 + t];
-    } else {
-      std::vector<float> tmp((size_t)c.cop * taps * c.cip, 0.f);
-      for (int o = 0; o < c.co; ++o)
-        for (int ci = 0; ci < c.ci; ++ci)
-          for (int t = 0; t < taps; ++t) tmp[((size_t)o * taps + t) * c.cip + ci] = w->data[((size_t)o * c.ci + ci) * taps + t];
-      putT(m, h + m->w_off[i], tmp.data(), tmp.size());
-    }
-    const HostTensor* g = ifind(m, c.bn + ".weight", {c.co});
-    const HostTensor* be = ifind(m, c.bn + ".bias", {c.co});
-    const HostTensor* mu = ifind(m, c.bn + ".running_mean", {c.co});
-    const HostTensor* va = ifind(m, c.bn + ".running_var", {c.co});
-    if (!g || !be || !mu || !va) return MHIP_ESTATE;
-    float* sc = (float*)(h + m->s_off[i]);
-    float* bi = (float*)(h + m->b_off[i]);
-    const int np = std::max(c.cop, 64);
-    for (int o = 0; o < np; ++o) {
-      sc[o] = 1.f;
-      bi[o] = 0.f;
-    }
-    for (int o = 0; o < c.co; ++o) {
-      const float s = g->data[o] / sqrtf(va->data[o] + 1e-5f);
-      sc[o] = s;
-      bi[o] = be->data[o] - mu->data[o] * s;
-    }
+    if (c.ci == 1) pack_first_conv_weight((float*)(h + m->w_off[i]), *w, c.co, 1, 9);   // fp32 for the VALU first layer
+    else pack_conv_weight(prec, h + m->w_off[i], *w, c.co, c.ci, c.k * c.k, c.cop, c.cip);
+    if (fold_conv_bn(ctx, st, c.conv, false, c.bn.c_str(), c.co, c.cop, (float*)(h + m->s_off[i]),
+                     (float*)(h + m->b_off[i])))
+      return MHIP_ESTATE;
   }
   const std::string loc = "Transformation.LocalizationNetwork.";
   {
-    const HostTensor* w1 = ifind(m, loc + "localization_fc1.0.weight", {256, 512});
-    const HostTensor* b1 = ifind(m, loc + "localization_fc1.0.bias", {256});
-    const HostTensor* w2 = ifind(m, loc + "localization_fc2.weight", {2 * NFID, 256});
-    const HostTensor* b2 = ifind(m, loc + "localization_fc2.bias", {2 * NFID});
-    const HostTensor* idc = ifind(m, "Transformation.GridGenerator.inv_delta_C", {NFID + 3, NFID + 3});
-    const HostTensor* ph = ifind(m, "Transformation.GridGenerator.P_hat", {IMG_H * IMG_W, NFID + 3});
+    const HostTensor* w1 = st.find(ctx, loc + "localization_fc1.0.weight", {256, 512});
+    const HostTensor* b1 = st.find(ctx, loc + "localization_fc1.0.bias", {256});
+    const HostTensor* w2 = st.find(ctx, loc + "localization_fc2.weight", {2 * NFID, 256});
+    const HostTensor* b2 = st.find(ctx, loc + "localization_fc2.bias", {2 * NFID});
+    const HostTensor* idc = st.find(ctx, "Transformation.GridGenerator.inv_delta_C", {NFID + 3, NFID + 3});
+    const HostTensor* ph = st.find(ctx, "Transformation.GridGenerator.P_hat", {IMG_H * IMG_W, NFID + 3});
     if (!w1 || !b1 || !w2 || !b2 || !idc || !ph) return MHIP_ESTATE;
-    putT(m, h + m->fc1_w, w1->data.data(), w1->data.size());
+    Arena::put(prec, h + m->fc1_w, w1->data.data(), w1->data.size());
     memcpy(h + m->fc1_b, b1->data.data(), 256 * 4);
-    putT(m, h + m->fc2_w, w2->data.data(), w2->data.size());
+    Arena::put(prec, h + m->fc2_w, w2->data.data(), w2->data.size());
     memcpy(h + m->fc2_b, b2->data.data(), 2 * NFID * 4);
     memcpy(h + m->idc, idc->data.data(), idc->data.size() * 4);
     memcpy(h + m->phat, ph->data.data(), ph->data.size() * 4);
   }
-  for (int j = 0; j < 2; ++j) {
-    const int in = j == 0 ? 512 : 256;
-    const std::string p = "SequenceModeling." + std::to_string(j) + ".";
-    const HostTensor* wih[2] = {ifind(m, p + "rnn.weight_ih_l0", {1024, in}), ifind(m, p + "rnn.weight_ih_l0_reverse", {1024, in})};
-    const HostTensor* whh[2] = {ifind(m, p + "rnn.weight_hh_l0", {1024, 256}), ifind(m, p + "rnn.weight_hh_l0_reverse", {1024, 256})};
-    const HostTensor* bih[2] = {ifind(m, p + "rnn.bias_ih_l0", {1024}), ifind(m, p + "rnn.bias_ih_l0_reverse", {1024})};
-    const HostTensor* bhh[2] = {ifind(m, p + "rnn.bias_hh_l0", {1024}), ifind(m, p + "rnn.bias_hh_l0_reverse", {1024})};
-    const HostTensor* lw = ifind(m, p + "linear.weight", {256, 512});
-    const HostTensor* lb = ifind(m, p + "linear.bias", {256});
-    for (int d = 0; d < 2; ++d)
-      if (!wih[d] || !whh[d] || !bih[d] || !bhh[d]) return MHIP_ESTATE;
-    if (!lw || !lb) return MHIP_ESTATE;
-    for (int d = 0; d < 2; ++d) {
-      float* bb = (float*)(h + m->ih_b[j]) + d * 1024;
-      for (int col = 0; col < 1024; ++col) {
-        const int n = mhip_lstm_xproj_row(col);
-        putT(m, h + m->ih_w[j] + ((size_t)d * 1024 + col) * in * es, wih[d]->data.data() + (size_t)n * in, (size_t)in);
-        bb[col] = bih[d]->data[n] + bhh[d]->data[n];
-      }
-    }
-    mhip_lstm_pack_whh(m->precision, whh[0]->data.data(), whh[1]->data.data(), h + m->hh_pack[j]);
-    putT(m, h + m->lin_w[j], lw->data.data(), (size_t)256 * 512);
-    memcpy(h + m->lin_b[j], lb->data.data(), 256 * 4);
-  }
+  for (int j = 0; j < 2; ++j)
+    if (mhip_lstm_pack_bilstm(ctx, st, "SequenceModeling." + std::to_string(j) + ".", j == 0 ? 512 : 256, prec,
+                              h + m->ih_w[j], (float*)(h + m->ih_b[j]), h + m->hh_pack[j], h + m->lin_w[j],
+                              (float*)(h + m->lin_b[j])))
+      return MHIP_ESTATE;
   {
     const std::string a = "Prediction.attention_cell.";
-    const HostTensor* i2h = ifind(m, a + "i2h.weight", {256, 256});
-    const HostTensor* h2h = ifind(m, a + "h2h.weight", {256, 256});
-    const HostTensor* h2hb = ifind(m, a + "h2h.bias", {256});
-    const HostTensor* sw = ifind(m, a + "score.weight", {1, 256});
-    const HostTensor* wih = ifind(m, a + "rnn.weight_ih", {1024, 256 + C});
-    const HostTensor* whh = ifind(m, a + "rnn.weight_hh", {1024, 256});
-    const HostTensor* bih = ifind(m, a + "rnn.bias_ih", {1024});
-    const HostTensor* bhh = ifind(m, a + "rnn.bias_hh", {1024});
-    const HostTensor* gw = ifind(m, "Prediction.generator.weight", {C, 256});
-    const HostTensor* gb = ifind(m, "Prediction.generator.bias", {C});
+    const HostTensor* i2h = st.find(ctx, a + "i2h.weight", {256, 256});
+    const HostTensor* h2h = st.find(ctx, a + "h2h.weight", {256, 256});
+    const HostTensor* h2hb = st.find(ctx, a + "h2h.bias", {256});
+    const HostTensor* sw = st.find(ctx, a + "score.weight", {1, 256});
+    const HostTensor* wih = st.find(ctx, a + "rnn.weight_ih", {1024, 256 + C});
+    const HostTensor* whh = st.find(ctx, a + "rnn.weight_hh", {1024, 256});
+    const HostTensor* bih = st.find(ctx, a + "rnn.bias_ih", {1024});
+    const HostTensor* bhh = st.find(ctx, a + "rnn.bias_hh", {1024});
+    const HostTensor* gw = st.find(ctx, "Prediction.generator.weight", {C, 256});
+    const HostTensor* gb = st.find(ctx, "Prediction.generator.bias", {C});
     if (!i2h || !h2h || !h2hb || !sw || !wih || !whh || !bih || !bhh || !gw || !gb) return MHIP_ESTATE;
-    putT(m, h + m->i2h_w, i2h->data.data(), (size_t)256 * 256);
+    Arena::put(prec, h + m->i2h_w, i2h->data.data(), (size_t)256 * 256);
     // one GEMM per step over h: rows 0..255 = h2h, rows 256..1279 = W_hh (gate order i,f,g,o kept)
-    putT(m, h + m->hg_w, h2h->data.data(), (size_t)256 * 256);
-    putT(m, h + m->hg_w + (size_t)256 * 256 * es, whh->data.data(), (size_t)1024 * 256);
+    Arena::put(prec, h + m->hg_w, h2h->data.data(), (size_t)256 * 256);
+    Arena::put(prec, h + m->hg_w + (size_t)256 * 256 * es, whh->data.data(), (size_t)1024 * 256);
     float* hb = (float*)(h + m->hg_b);
     for (int i = 0; i < 256; ++i) hb[i] = h2hb->data[i];
     for (int i = 0; i < 1024; ++i) hb[256 + i] = bih->data[i] + bhh->data[i];
@@ -316,16 +222,15 @@ extern "C" int mhip_icr_finalize(mhip_icr* m) {
       for (int k = 0; k < 256; ++k) ctxw[(size_t)r * 256 + k] = wih->data[(size_t)r * (256 + C) + k];
       for (int ch = 0; ch < C; ++ch) oh[(size_t)ch * 1024 + r] = wih->data[(size_t)r * (256 + C) + 256 + ch];
     }
-    putT(m, h + m->ihc_w, ctxw.data(), ctxw.size());
-    putT(m, h + m->gen_w, gw->data.data(), (size_t)C * 256);
+    Arena::put(prec, h + m->ihc_w, ctxw.data(), ctxw.size());
+    Arena::put(prec, h + m->gen_w, gw->data.data(), (size_t)C * 256);
     memcpy(h + m->gen_b, gb->data.data(), (size_t)C * 4);
   }
-  int rc = mhip_icr_alloc_arena(m);
-  if (rc) return rc;
   m->ready = false;
-  MHIP_HIP(ctx, hipMemcpy(m->arena, h, m->arena_bytes, hipMemcpyHostToDevice));
+  int rc = m->arena.upload(ctx);
+  if (rc) return rc;
   m->ready = true;
-  m->tensors.clear();
+  m->store.t.clear();
   return MHIP_OK;
 }
 
@@ -337,7 +242,7 @@ extern "C" int mhip_icr_forward(mhip_icr* m, const uint8_t* crops, int n, float*
                                 float* pmax, float* rectified_out) {
   if (!m) return MHIP_EINVAL;
   mhip_ctx* ctx = m->ctx;
-  if (!m->ready || !m->arena) return mhip_fail(ctx, MHIP_ESTATE, "icr: weights not finalized");
+  if (!m->ready || !m->arena.dev) return mhip_fail(ctx, MHIP_ESTATE, "icr: weights not finalized");
   if (!crops || !logits || !argmax || !pmax || n < 1 || n > 65535)
     return mhip_fail(ctx, MHIP_EINVAL, "icr: bad arguments (n=%d)", n);
   MHIP_HIP(ctx, hipSetDevice(ctx->device));
@@ -363,7 +268,7 @@ extern "C" int mhip_icr_forward(mhip_icr* m, const uint8_t* crops, int n, float*
   int rc = mhip_ensure_workspace(ctx, o);
   if (rc) return rc;
   char* ws = (char*)ctx->ws;
-  const char* A = m->arena;
+  const char* A = m->arena.dev;
 #define CK(x) do { rc = (x); if (rc) return rc; } while (0)
   auto conv = [&](const std::string& key, const void* in, int hh, int ww, void* out, int pool, int relu,
                   const void* res = nullptr, int sy = 1, int pad_y = -1, int pad_x = -1) {

@@ -23,7 +23,7 @@
 //
 // f32 parity mode (`lstm_rec_stream<float>`): W_hh is 1 MB per direction and cannot be resident;
 // it is streamed from L2 in fragment order (1 KiB coalesced loads) every step.
-#include "common.h"
+#include "weights_util.h"
 
 namespace {
 
@@ -315,6 +315,33 @@ void mhip_lstm_pack_whh(int precision, const float* whh_fwd, const float* whh_bw
             }
           }
   }
+}
+
+int mhip_lstm_pack_bilstm(mhip_ctx* ctx, const TensorStore& st, const std::string& p, int in, int precision,
+                          char* ih_w, float* ih_b, char* hh_pack, char* lin_w, float* lin_b) {
+  const HostTensor* wih[2] = {st.find(ctx, p + "rnn.weight_ih_l0", {1024, in}),
+                              st.find(ctx, p + "rnn.weight_ih_l0_reverse", {1024, in})};
+  const HostTensor* whh[2] = {st.find(ctx, p + "rnn.weight_hh_l0", {1024, 256}),
+                              st.find(ctx, p + "rnn.weight_hh_l0_reverse", {1024, 256})};
+  const HostTensor* bih[2] = {st.find(ctx, p + "rnn.bias_ih_l0", {1024}), st.find(ctx, p + "rnn.bias_ih_l0_reverse", {1024})};
+  const HostTensor* bhh[2] = {st.find(ctx, p + "rnn.bias_hh_l0", {1024}), st.find(ctx, p + "rnn.bias_hh_l0_reverse", {1024})};
+  const HostTensor* lw = st.find(ctx, p + "linear.weight", {256, 512});
+  const HostTensor* lb = st.find(ctx, p + "linear.bias", {256});
+  for (int d = 0; d < 2; ++d)
+    if (!wih[d] || !whh[d] || !bih[d] || !bhh[d]) return MHIP_ESTATE;
+  if (!lw || !lb) return MHIP_ESTATE;
+  const size_t es = precision == MHIP_PREC_F16 ? 2 : 4;
+  // rows permuted so the GEMM writes xproj gate-interleaved, the order the recurrence consumes
+  for (int d = 0; d < 2; ++d)
+    for (int col = 0; col < 1024; ++col) {
+      const int n = mhip_lstm_xproj_row(col);
+      Arena::put(precision, ih_w + ((size_t)d * 1024 + col) * in * es, wih[d]->data.data() + (size_t)n * in, (size_t)in);
+      ih_b[d * 1024 + col] = bih[d]->data[n] + bhh[d]->data[n];
+    }
+  mhip_lstm_pack_whh(precision, whh[0]->data.data(), whh[1]->data.data(), hh_pack);
+  Arena::put(precision, lin_w, lw->data.data(), (size_t)256 * 512);
+  memcpy(lin_b, lb->data.data(), 256 * 4);
+  return MHIP_OK;
 }
 
 int mhip_launch_lstm_rec(mhip_ctx* ctx, int precision, const float* xproj, const void* wpack, void* hseq, int B,

@@ -1,6 +1,11 @@
-// weights_util.h — host-side weight staging shared by the ViT / DiT / TrOCR model files: a state_dict-like tensor store,
-// and an arena builder that lays named blocks out once (256-byte aligned) and fills them in the kernels' layouts.
+// weights_util.h — host-side weight staging shared by every model file (CRAFT, CRNN, ICR, ViT, DiT, TrOCR, overlay): a
+// state_dict-like tensor store, an arena builder that lays named blocks out once (256-byte aligned) and fills them in the
+// kernels' layouts, and the conv packers the conv models have in common.
 #pragma once
+#include <math.h>
+
+#include <algorithm>
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <vector>
@@ -42,6 +47,22 @@ struct TensorStore {
   }
   bool has(const std::string& k) const { return t.count(k) != 0; }
 };
+
+// set_tensor of the conv models (CRAFT, CRNN, ICR): a DataParallel `module.` prefix is stripped, BatchNorm's
+// num_batches_tracked is dropped, a key under none of `prefixes` is refused, and tensors are at most 4-d
+inline int set_conv_model_tensor(mhip_ctx* ctx, TensorStore& st, bool& ready, const char* key,
+                                 std::initializer_list<const char*> prefixes, const float* data, const int64_t* shape,
+                                 int ndim) {
+  std::string k(key);
+  if (k.rfind("module.", 0) == 0) k = k.substr(7);
+  if (k.size() > 19 && k.compare(k.size() - 19, 19, "num_batches_tracked") == 0) return MHIP_OK;
+  if (std::none_of(prefixes.begin(), prefixes.end(), [&](const char* p) { return k.rfind(p, 0) == 0; }))
+    return mhip_fail(ctx, MHIP_EINVAL, "unknown state_dict key %s", key);
+  if (ndim > 4) return mhip_fail(ctx, MHIP_EINVAL, "bad tensor %s", key);
+  int rc = st.set(ctx, k, data, shape, ndim);
+  if (!rc) ready = false;
+  return rc;
+}
 
 struct Arena {
   std::map<std::string, size_t> off;
@@ -88,6 +109,50 @@ struct Arena {
     dev = nullptr;
   }
 };
+
+// conv weight [Co][Ci][k][k] -> [Cop][taps][Cip] at `precision`, zero padded to the channel counts the kernels see
+inline void pack_conv_weight(int precision, char* dst, const HostTensor& w, int co, int ci, int taps, int cop, int cip) {
+  std::vector<float> tmp((size_t)cop * taps * cip, 0.f);
+  for (int o = 0; o < co; ++o)
+    for (int c = 0; c < ci; ++c)
+      for (int t = 0; t < taps; ++t) tmp[((size_t)o * taps + t) * cip + c] = w.data[((size_t)o * ci + c) * taps + t];
+  Arena::put(precision, dst, tmp.data(), tmp.size());
+}
+
+// first-layer conv weight [Co][Cin][k][k] -> [tap*Cin + c][Co] fp32 for the VALU first-layer kernels
+inline void pack_first_conv_weight(float* dst, const HostTensor& w, int co, int cin, int taps) {
+  for (int o = 0; o < co; ++o)
+    for (int c = 0; c < cin; ++c)
+      for (int t = 0; t < taps; ++t) dst[(t * cin + c) * co + o] = w.data[((size_t)o * cin + c) * taps + t];
+}
+
+// fp32 per-channel epilogue of a conv: the conv's bias (none: 0) with an eval-mode BatchNorm (`bn` prefix, or nullptr)
+// folded in, scale = gamma / sqrt(var + 1e-5), shift = beta + (bias - mean) * scale.  Both arrays hold max(cop, 64)
+// channels; padded output channels get 1 / 0 (0 * x + 0 -> ReLU -> 0).
+inline int fold_conv_bn(mhip_ctx* ctx, const TensorStore& st, const std::string& conv, bool has_bias, const char* bn,
+                        int co, int cop, float* scale, float* shift) {
+  const int np = std::max(cop, 64);
+  std::fill(scale, scale + np, 1.f);
+  std::fill(shift, shift + np, 0.f);
+  if (has_bias) {
+    const HostTensor* b = st.find(ctx, conv + ".bias", {co});
+    if (!b) return MHIP_ESTATE;
+    std::copy(b->data.begin(), b->data.end(), shift);
+  }
+  if (!bn) return MHIP_OK;
+  const std::string p(bn);
+  const HostTensor* g = st.find(ctx, p + ".weight", {co});
+  const HostTensor* be = st.find(ctx, p + ".bias", {co});
+  const HostTensor* mu = st.find(ctx, p + ".running_mean", {co});
+  const HostTensor* va = st.find(ctx, p + ".running_var", {co});
+  if (!g || !be || !mu || !va) return MHIP_ESTATE;
+  for (int o = 0; o < co; ++o) {
+    const float s = g->data[o] / sqrtf(va->data[o] + 1e-5f);   // nn.BatchNorm2d eps
+    scale[o] = s;
+    shift[o] = be->data[o] + (shift[o] - mu->data[o]) * s;
+  }
+  return MHIP_OK;
+}
 
 // bump allocator over the context workspace for one forward
 struct Carver {

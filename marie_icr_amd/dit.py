@@ -10,8 +10,7 @@ from typing import Dict, Optional, Sequence
 
 import numpy as np
 
-from ._lib import PREC_F16, Context, DitConfig, check
-from .vit import load_tensors
+from ._lib import PREC_F16, Context, DitConfig, ModelHandle, check
 
 MAX_ROIS = 1000
 ANCHOR_SIZES = (4.0, 8.0, 16.0, 32.0, 64.0)
@@ -30,34 +29,19 @@ def default_config(lib, model: str = "base") -> DitConfig:
     return cfg
 
 
-class DitModel:
+class DitModel(ModelHandle):
     def __init__(self, ctx: Context, state: Optional[Dict[str, np.ndarray]] = None, model: str = "base",
                  precision: int = PREC_F16, config: Optional[DitConfig] = None):
-        self.ctx, self.lib, self.precision = ctx, ctx.lib, int(precision)
+        self.precision = int(precision)
         self.cfg = config or default_config(ctx.lib, model)
-        h = C.c_void_p()
-        check(ctx.h, self.lib.mhip_dit_create(ctx.h, self.precision, C.byref(self.cfg), C.byref(h)), "mhip_dit_create")
-        self.h = h
-        ctx.adopt(self)
+        super().__init__(ctx, "dit", self.precision, C.byref(self.cfg))
         if state is not None:
-            load_tensors(ctx, self.lib.mhip_dit_set_tensor, self.h, state, "mhip_dit_set_tensor")
-            check(ctx.h, self.lib.mhip_dit_finalize(self.h), "mhip_dit_finalize")
+            self.load_state(state)
 
     def resized_shape(self, h: int, w: int):
         nh, nw, H32, W32 = C.c_int(), C.c_int(), C.c_int(), C.c_int()
         self.lib.mhip_dit_resized_shape(C.byref(self.cfg), h, w, C.byref(nh), C.byref(nw), C.byref(H32), C.byref(W32))
         return nh.value, nw.value, H32.value, W32.value
-
-    def arenas(self):
-        out = []
-        for which in (0, 1):
-            p, n = C.c_void_p(), C.c_size_t()
-            check(self.ctx.h, self.lib.mhip_dit_arena(self.h, which, C.byref(p), C.byref(n)), "mhip_dit_arena")
-            out.append((p.value, n.value))
-        return out
-
-    def alloc_arena(self):
-        check(self.ctx.h, self.lib.mhip_dit_alloc_arena(self.h), "mhip_dit_alloc_arena")
 
     def _unpack(self, boxes, scores, counts):
         return [(boxes[b, : counts[b]].copy(), scores[b, : counts[b]].copy()) for b in range(len(counts))]
@@ -108,17 +92,6 @@ class DitModel:
         return {"boxes": boxes[: n.value], "scores": scores[: n.value], "fpn": fpn, "proposals": pb[: pn.value],
                 "proposal_scores": ps[: pn.value], "resized_hw": (nh, nw), "sizes": sizes,
                 "rpn_heads": [r[:, :15].copy() for r in rpn], "head": head[: pn.value, :6].copy()}
-
-    def close(self):
-        if getattr(self, "h", None) is not None and self.h.value:
-            self.lib.mhip_dit_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---------------------------------------------------------------------------------------------------- stage entries

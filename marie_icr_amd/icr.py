@@ -17,46 +17,23 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-from ._lib import PREC_F16, PREC_F32, Context, MarieHipError, check
+from ._lib import PREC_F16, PREC_F32, Context, MarieHipError, ModelHandle, check
 from .crnn import IMG_H, pack_fragments
 from .ocr_processor import OcrProcessor
-from .weights import CRNN_CHARSET, ICR_IMG_W, strip_module_prefix
+from .weights import CRNN_CHARSET, ICR_IMG_W
 
 
-class IcrModel:
+class IcrModel(ModelHandle):
     """Device-resident TPS-ResNet-BiLSTM-Attn weights + forward.  Thin handle over ``mhip_icr``."""
 
     def __init__(self, ctx: Context, state: Optional[Dict[str, np.ndarray]], num_class: int = 96,
                  precision: int = PREC_F16):
-        self.ctx = ctx
-        self.lib = ctx.lib
         self.num_class = int(num_class)
         self.precision = int(precision)
-        self.steps = self.lib.mhip_icr_steps()
-        h = C.c_void_p()
-        check(ctx.h, self.lib.mhip_icr_create(ctx.h, self.precision, self.num_class, C.byref(h)), "mhip_icr_create")
-        self.h = h
-        ctx.adopt(self)
+        self.steps = ctx.lib.mhip_icr_steps()
+        super().__init__(ctx, "icr", self.precision, self.num_class)
         if state is not None:
             self.load_state(state)
-
-    def load_state(self, state: Dict[str, np.ndarray]):
-        for key, val in strip_module_prefix(state).items():
-            arr = np.ascontiguousarray(np.asarray(val), dtype=np.float32)
-            shape = (C.c_int64 * max(arr.ndim, 1))(*arr.shape)
-            check(self.ctx.h,
-                  self.lib.mhip_icr_set_tensor(self.h, key.encode(), arr.ctypes.data_as(C.c_void_p), shape, arr.ndim),
-                  f"mhip_icr_set_tensor({key})")
-        check(self.ctx.h, self.lib.mhip_icr_finalize(self.h), "mhip_icr_finalize")
-
-    def alloc_arena(self):
-        check(self.ctx.h, self.lib.mhip_icr_alloc_arena(self.h), "mhip_icr_alloc_arena")
-
-    def arena(self):
-        p = C.c_void_p()
-        n = C.c_size_t()
-        check(self.ctx.h, self.lib.mhip_icr_arena(self.h, C.byref(p), C.byref(n)), "mhip_icr_arena")
-        return p.value, n.value
 
     def forward_host(self, crops_u8: np.ndarray, want_logits: bool = False, want_rectified: bool = False):
         """crops_u8: (n, 32, 100) uint8.  Returns dict of host arrays: argmax (n,49), pmax (n,49) [, logits, rectified]."""
@@ -74,17 +51,6 @@ class IcrModel:
             check(self.ctx.h, self.lib.mhip_icr_forward_host(self.h, vp(crops), n, vp(logits), vp(argmax), vp(pmax),
                                                              vp(rect)), "mhip_icr_forward_host")
         return {"logits": logits, "argmax": argmax, "pmax": pmax, "rectified": rect}
-
-    def close(self):
-        if getattr(self, "h", None) is not None and self.h.value:
-            self.lib.mhip_icr_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def attn_texts(argmax: np.ndarray, pmax: np.ndarray, charset: str):

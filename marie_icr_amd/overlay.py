@@ -17,25 +17,20 @@ from typing import Dict, Optional, Tuple
 
 import numpy as np
 
-from ._lib import PREC_F16, PREC_F32, Context, MarieHipError, check
-from .vit import load_tensors
+from ._lib import PREC_F16, PREC_F32, Context, MarieHipError, ModelHandle, check
 
 
 def _vp(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else C.c_void_p(0)
 
 
-class OverlayModel:
+class OverlayModel(ModelHandle):
     """Thin handle over ``mhip_overlay``."""
 
     def __init__(self, ctx: Context, state: Dict[str, np.ndarray], ngf: int = 64, precision: int = PREC_F16):
-        self.ctx, self.lib, self.ngf, self.precision = ctx, ctx.lib, int(ngf), int(precision)
-        h = C.c_void_p()
-        check(ctx.h, self.lib.mhip_overlay_create(ctx.h, self.precision, self.ngf, C.byref(h)), "mhip_overlay_create")
-        self.h = h
-        ctx.adopt(self)
-        load_tensors(ctx, self.lib.mhip_overlay_set_tensor, self.h, state, "mhip_overlay_set_tensor")
-        check(ctx.h, self.lib.mhip_overlay_finalize(self.h), "mhip_overlay_finalize")
+        self.ngf, self.precision = int(ngf), int(precision)
+        super().__init__(ctx, "overlay", self.precision, self.ngf)
+        self.load_state(state)
 
     def padded_shape(self, h: int, w: int) -> Tuple[int, int]:
         H, W = C.c_int(), C.c_int()
@@ -54,17 +49,6 @@ class OverlayModel:
 
     def forward_device(self, page_ptr: int, h: int, w: int, fake_ptr: int):
         check(self.ctx.h, self.lib.mhip_overlay_forward(self.h, C.c_void_p(page_ptr), h, w, C.c_void_p(fake_ptr)), "mhip_overlay_forward")
-
-    def close(self):
-        if getattr(self, "h", None) is not None and self.h.value:
-            self.lib.mhip_overlay_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class OverlayProcessor:

@@ -20,10 +20,9 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-from ._lib import PREC_F16, PREC_F32, Context, MarieHipError, TrocrConfig, check
+from ._lib import PREC_F16, PREC_F32, Context, MarieHipError, ModelHandle, TrocrConfig, check
 from .crnn import pack_fragments
 from .ocr_processor import OcrProcessor
-from .vit import load_tensors
 
 
 def default_config(lib, model: str = "base") -> TrocrConfig:
@@ -38,28 +37,13 @@ def _vp(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else C.c_void_p(0)
 
 
-class TrocrModel:
+class TrocrModel(ModelHandle):
     def __init__(self, ctx: Context, state: Optional[Dict[str, np.ndarray]], config: TrocrConfig, precision: int = PREC_F16):
-        self.ctx, self.lib, self.cfg, self.precision = ctx, ctx.lib, config, int(precision)
-        h = C.c_void_p()
-        check(ctx.h, self.lib.mhip_trocr_create(ctx.h, self.precision, C.byref(config), C.byref(h)), "mhip_trocr_create")
-        self.h = h
-        ctx.adopt(self)
+        self.cfg, self.precision = config, int(precision)
+        super().__init__(ctx, "trocr", self.precision, C.byref(config))
         self.max_len = self.lib.mhip_trocr_max_len(C.byref(config))
         if state is not None:
-            load_tensors(ctx, self.lib.mhip_trocr_set_tensor, self.h, state, "mhip_trocr_set_tensor")
-            check(ctx.h, self.lib.mhip_trocr_finalize(self.h), "mhip_trocr_finalize")
-
-    def arenas(self):
-        out = []
-        for which in (0, 1):
-            p, n = C.c_void_p(), C.c_size_t()
-            check(self.ctx.h, self.lib.mhip_trocr_arena(self.h, which, C.byref(p), C.byref(n)), "mhip_trocr_arena")
-            out.append((p.value, n.value))
-        return out
-
-    def alloc_arena(self):
-        check(self.ctx.h, self.lib.mhip_trocr_alloc_arena(self.h), "mhip_trocr_alloc_arena")
+            self.load_state(state)
 
     def _outputs(self, n):
         return (np.empty((n, self.max_len + 1), np.int32), np.empty((n,), np.int32), np.empty((n,), np.float32))
@@ -136,14 +120,7 @@ class TrocrModel:
     def close(self):
         if getattr(self, "h", None) is not None and self.h.value:
             self.lib.mhip_trocr_set_decode_gate(self.h, None)
-            self.lib.mhip_trocr_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
 
 
 # ---------------------------------------------------------------------------------------------------- text side

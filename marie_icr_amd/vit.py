@@ -10,7 +10,7 @@ from typing import Dict, Optional, Sequence
 
 import numpy as np
 
-from ._lib import PREC_F16, Context, VitConfig, check
+from ._lib import PREC_F16, Context, ModelHandle, VitConfig, check
 
 
 def dit_config(name: str = "base") -> VitConfig:
@@ -40,24 +40,13 @@ def make_config(dim, depth, heads, taps=(0, 0, 0, 0), pos_hw=(14, 14), layer_sca
     return cfg
 
 
-def load_tensors(ctx: Context, setter, handle, state: Dict[str, np.ndarray], what: str):
-    for key, val in state.items():
-        arr = np.ascontiguousarray(np.asarray(val), dtype=np.float32)
-        shape = (C.c_int64 * max(arr.ndim, 1))(*arr.shape)
-        check(ctx.h, setter(handle, key.encode(), arr.ctypes.data_as(C.c_void_p), shape, arr.ndim), f"{what}({key})")
-
-
-class VitModel:
+class VitModel(ModelHandle):
     def __init__(self, ctx: Context, cfg: VitConfig, state: Optional[Dict[str, np.ndarray]] = None,
                  precision: int = PREC_F16):
-        self.ctx, self.lib, self.cfg, self.precision = ctx, ctx.lib, cfg, int(precision)
-        h = C.c_void_p()
-        check(ctx.h, self.lib.mhip_vit_create(ctx.h, self.precision, C.byref(cfg), C.byref(h)), "mhip_vit_create")
-        self.h = h
-        ctx.adopt(self)
+        self.cfg, self.precision = cfg, int(precision)
+        super().__init__(ctx, "vit", self.precision, C.byref(cfg))
         if state is not None:
-            load_tensors(ctx, self.lib.mhip_vit_set_tensor, self.h, state, "mhip_vit_set_tensor")
-            check(ctx.h, self.lib.mhip_vit_finalize(self.h), "mhip_vit_finalize")
+            self.load_state(state)
 
     def forward_host(self, imgs_u8: np.ndarray, canvas_hw: Sequence[int], swap_rb: bool = True, want_tokens=False,
                      want_fpn=True):
@@ -76,14 +65,3 @@ class VitModel:
         check(self.ctx.h, self.lib.mhip_vit_forward_host(self.h, vp(imgs), B, th, tw, H32, W32, int(swap_rb), vp(tokens),
                                                          vp(f[0]), vp(f[1]), vp(f[2]), vp(f[3])), "mhip_vit_forward_host")
         return {"tokens": tokens, "fpn": fpn}
-
-    def close(self):
-        if getattr(self, "h", None) is not None and self.h.value:
-            self.lib.mhip_vit_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -41,11 +41,6 @@ VGG_BNS = ("FeatureExtraction.ConvNet.12", "FeatureExtraction.ConvNet.15")
 HIDDEN = 256
 
 
-def strip_module_prefix(state: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
-    """Drop the DataParallel ``module.`` prefix if present."""
-    return {(k[7:] if k.startswith("module.") else k): v for k, v in state.items()}
-
-
 def make_crnn_state(seed: int = 0, num_class: int = 95, logit_gain: float = 24.0) -> Dict[str, np.ndarray]:
     """Seeded None-VGG-BiLSTM-CTC weights with O(1) activations.
 
