@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the MI355X OCR hot path on synthetic data.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -33,14 +33,18 @@ collective.  ``python bench.py --gpus N`` (N > 1) with no launcher around it sta
 exits non-zero.  Rank 0 packs the weights and the packed arenas are broadcast once over RCCL/xGMI at start-up; the timed
 region is bracketed by barrier + synchronize and the maximum over ranks is reported.
 
-Secondary legs of the default workload, all in the same JSON line (never ``value``):
+A plain run does what the headline needs and nothing more: it sets up, warms up, times ``--steps`` steps, writes
+``--dump-outputs`` if asked and prints the JSON line.  ``--full`` adds every other leg after the timed steps, all in the same
+JSON line (never ``value``); the ``--no-*`` switches drop single legs from it.  Legs of ``--full`` for the default workload:
   ``stream``      BASELINE configs[3] — a fixed stream (2048 pages when N > 1) sharded round-robin over the ranks
                   (``marie_icr_amd.dist.shard_indices``), boxes-per-page and token ids gathered in page order
                   (``gather_in_order``); strong scaling; ``result_checksum`` is the same for every N.
   ``mixed_dpi``   BASELINE configs[4] — 150/200/300-DPI pages interleaved, chunks pulled from a host work queue, pages
                   bucketed by size, crops pooled.
   ``engine_api``  the same models behind ``MarieHipOcrEngine.extract`` (host frames in, dictionaries out).
-  ``det_passes_3``, ``pcie_inclusive``, ``parity`` (GPU vs oracle on the cpu_baseline sample).
+  ``overlay``     the overlay cleaner's generator on the same resident pages.
+  ``det_passes_3``, ``pcie_inclusive``, ``parity`` (GPU vs oracle on the cpu_baseline sample), and the ``roofline`` and
+  ``cpu_baseline`` figures below, which every workload reports under ``--full``.
 
 ``--dump-outputs DIR`` (dit_trocr) writes the results of the last timed step as DIR/<name>.npy: det_boxes, det_scores and
 det_boxes_per_page of the detector, and rec_tokens (padded with -1), rec_lengths and rec_scores of the recognizer.  Inputs
@@ -924,8 +928,13 @@ def launch_ranks(n: int) -> int:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--engine-page-batch", type=int, default=32, help="pages per detector / recognizer batch of the engine_api leg")
-    ap.add_argument("--engine-first-batch", type=int, default=0, help="pages of the first batch of the engine_api leg (0 = the engine's default)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other leg (per-kernel timing and roofline, cpu_baseline and "
+                         "parity, det_passes_3, pcie_inclusive, stream, mixed_dpi, engine_api, overlay); off: the headline only")
+    ap.add_argument("--engine-page-batch", type=int, help="pages per detector / recognizer batch of the engine_api leg "
+                                                          "(--full; default 32)")
+    ap.add_argument("--engine-first-batch", type=int, help="pages of the first batch of the engine_api leg (--full; default 0 = "
+                                                           "the engine's default)")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", choices=["dit_trocr", "craft_crnn", "pages", "crnn"], default="dit_trocr")
@@ -943,13 +952,15 @@ def main():
     ap.add_argument("--no-phase-align", action="store_true",
                     help="dit_trocr: let the detector and the recognizer streams race from the start of a step instead of "
                          "starting the detector where the recognizer begins to decode")
-    ap.add_argument("--stream-pages", type=int, default=-1,
-                    help="dit_trocr, BASELINE configs[3]: also time a fixed stream of this many pages sharded over the ranks "
-                         "with the results gathered in page order (default: 2048 when N > 1, two steps' worth at N = 1; 0 = off)")
-    ap.add_argument("--mixed-pages", type=int, default=48,
-                    help="dit_trocr, BASELINE configs[4]: pages per GPU of the mixed-DPI stream leg (multiple of 24)")
-    ap.add_argument("--no-mixed-dpi", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip det_passes_3 and the engine_api legs (N = 1)")
+    ap.add_argument("--stream-pages", type=int,
+                    help="dit_trocr --full, BASELINE configs[3]: also time a fixed stream of this many pages sharded over the "
+                         "ranks with the results gathered in page order (default: 2048 when N > 1, two steps' worth at N = 1; "
+                         "0 = off)")
+    ap.add_argument("--mixed-pages", type=int,
+                    help="dit_trocr --full, BASELINE configs[4]: pages per GPU of the mixed-DPI stream leg (multiple of 24; "
+                         "default 48)")
+    ap.add_argument("--no-mixed-dpi", action="store_true", help="--full without the mixed_dpi leg")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the det_passes_3, engine_api and overlay legs (N = 1)")
     ap.add_argument("--crops", choices=["lines", "detector"], default="lines")
     ap.add_argument("--inflight", type=int, default=6,
                     help="page pipelines per GPU (one context + stream + host thread each): the host-side box "
@@ -957,16 +968,28 @@ def main():
     ap.add_argument("--lines", type=int, default=1024, help="lines per GPU per step (workload crnn)")
     ap.add_argument("--width", type=int, default=256)
     ap.add_argument("--precision", choices=["f16", "f32"], default="f16")
-    ap.add_argument("--host-steps", type=int, default=2,
-                    help="extra steps with the pages fed from pinned host memory (dit_trocr, N=1; reported as pcie_inclusive)")
-    ap.add_argument("--no-kernel-timing", action="store_true", help="no per-kernel HIP events in the timed region")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--host-steps", type=int,
+                    help="extra steps with the pages fed from pinned host memory (dit_trocr --full, N=1; reported as "
+                         "pcie_inclusive; default 2)")
+    ap.add_argument("--no-kernel-timing", action="store_true",
+                    help="--full without the steps timed kernel by kernel with HIP events (roofline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline and parity")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="dit_trocr: after the timed steps, write what the last timed step returned (rank 0's pages) as "
                          "DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     args = ap.parse_args()
     if args.steps < 1:
         raise SystemExit("--steps must be >= 1")
+    # the sizes of the legs of --full: a plain run refuses one that would switch a leg on instead of ignoring it
+    for name, default in (("stream_pages", -1), ("mixed_pages", 48), ("host_steps", 2), ("engine_page_batch", 32),
+                          ("engine_first_batch", 0)):
+        v = getattr(args, name)
+        if v and not args.full:
+            raise SystemExit(f"--{name.replace('_', '-')} sizes a leg of --full; a plain run has none")
+        setattr(args, name, default if v is None else v)
+    if not args.full:      # the headline only: no leg after the timed steps
+        args.no_kernel_timing = args.no_cpu_baseline = args.no_secondary = args.no_mixed_dpi = True
+        args.host_steps = args.stream_pages = 0
     if args.workload == "pages":
         args.workload = "craft_crnn"
     if args.dump_outputs and args.workload != "dit_trocr":

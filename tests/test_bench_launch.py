@@ -51,8 +51,8 @@ def test_two_rank_rehearsal_matches_one_rank():
     """MARIE_BENCH_REHEARSE=1 python bench.py --gpus 2 on one GPU (gloo for the start-up broadcast / gathers, both ranks on
     device 0): n_gpus is 2, the weight broadcast checksum passed, and the stream / mixed-DPI results gathered from two ranks
     equal the one-rank results (order-sensitive checksums)."""
-    common = ["--steps", "1", "--warmup", "1", "--pages", "4", "--det-batch", "4", "--decode-len", "3", "--stream-pages", "12",
-              "--mixed-pages", "24", "--no-cpu-baseline", "--no-kernel-timing", "--no-secondary", "--host-steps", "0"]
+    common = ["--full", "--steps", "1", "--warmup", "1", "--pages", "4", "--det-batch", "4", "--decode-len", "3", "--stream-pages",
+              "12", "--mixed-pages", "24", "--no-cpu-baseline", "--no-kernel-timing", "--no-secondary", "--host-steps", "0"]
     one = _json_line(_run(["--gpus", "1"] + common).stdout)
     r = _run(["--gpus", "2"] + common, {"MARIE_BENCH_REHEARSE": "1"})
     assert r.returncode == 0, r.stderr[-3000:]
@@ -77,8 +77,8 @@ def test_rccl_path_with_one_rank_under_the_launcher():
     (order-sensitive checksums) equal the launcher-less run's."""
     import socket
 
-    common = ["--gpus", "1", "--steps", "1", "--warmup", "1", "--pages", "4", "--det-batch", "4", "--decode-len", "3", "--stream-pages", "12",
-              "--mixed-pages", "24", "--no-cpu-baseline", "--no-kernel-timing", "--no-secondary", "--host-steps", "0"]
+    common = ["--gpus", "1", "--full", "--steps", "1", "--warmup", "1", "--pages", "4", "--det-batch", "4", "--decode-len", "3",
+              "--stream-pages", "12", "--mixed-pages", "24", "--no-cpu-baseline", "--no-kernel-timing", "--no-secondary", "--host-steps", "0"]
     plain = _json_line(_run(common).stdout)
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
@@ -100,12 +100,12 @@ def test_rccl_path_with_one_rank_under_the_launcher():
 
 @pytest.mark.gpu
 def test_all_legs_run_and_the_process_exits_cleanly():
-    """The default command's shape at a reduced size with every secondary leg on (engine_api, overlay, det_passes_3, mixed DPI,
+    """The --full command's shape at a reduced size with every secondary leg on (engine_api, overlay, det_passes_3, mixed DPI,
     cpu parity sample off): one JSON line with the contract's fields, exit code 0.  Regression: the engine leg's detector thread
     used to leave its (dead) torch stream in the detector's context, and the teardown's hipStreamSynchronize on it aborted the
     interpreter AFTER the line was printed (exit 134)."""
-    r = _run(["--gpus", "1", "--steps", "1", "--warmup", "1", "--pages", "8", "--det-batch", "4", "--decode-len", "3", "--mixed-pages", "6",
-              "--no-cpu-baseline", "--host-steps", "0", "--engine-page-batch", "4"])
+    r = _run(["--gpus", "1", "--full", "--steps", "1", "--warmup", "1", "--pages", "8", "--det-batch", "4", "--decode-len", "3",
+              "--mixed-pages", "6", "--no-cpu-baseline", "--host-steps", "0", "--engine-page-batch", "4"])
     assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
     line = _json_line(r.stdout)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
@@ -138,6 +138,25 @@ def test_symbol_error_rate_is_levenshtein_over_reference_length():
 def test_steps_below_one_are_refused():
     r = _run(["--steps", "0"], timeout=120)
     assert r.returncode != 0 and "--steps must be >= 1" in (r.stderr + r.stdout)
+
+
+@pytest.mark.parametrize("opt", [["--stream-pages", "12"], ["--stream-pages", "-1"], ["--mixed-pages", "24"],
+                                 ["--host-steps", "2"], ["--engine-page-batch", "4"], ["--engine-first-batch", "8"]])
+def test_plain_run_refuses_the_sizes_of_full_legs(opt):
+    """An option that would switch on a leg of --full is refused by a plain run instead of being ignored (before any GPU call)."""
+    r = _run(["--steps", "1"] + opt, timeout=120)
+    assert r.returncode != 0 and f"{opt[0]} sizes a leg of --full" in (r.stderr + r.stdout)
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_only():
+    """Without --full the line holds the headline and its configuration, and no leg run after the timed steps."""
+    r = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--pages", "4", "--det-batch", "4", "--decode-len", "3"])
+    assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
+    line = _json_line(r.stdout)
+    assert sorted(line) == sorted(["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+                                   "scaling", "vs_baseline", "dtype", "data", "config", "sample_output"])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["value"] > 0 and line["dtype"] == "f16"
 
 
 def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
