@@ -91,6 +91,25 @@ def _plain(v):
     return v
 
 
+def register_frames(args, frames):
+    """ExtractPipeline.boundary (marie/pipe/extract_pipeline.py:184-233): each frame is replaced by its aligned page where the
+    document was found.  Without --models-dir the detector carries seeded weights."""
+    from marie_icr_amd._lib import Context
+    from marie_icr_amd.document_registration import UnilmDocumentBoundaryRegistration
+    from marie_icr_amd.weights import make_dit_boundary_state
+
+    ctx = Context(args.device)
+    kw = {"models_dir": args.models_dir} if args.models_dir else {"state": make_dit_boundary_state(0)}
+    reg = UnilmDocumentBoundaryRegistration("unilm/dit/object_detection/document_boundary", precision=args.precision, ctx=ctx,
+                                            **kw)
+    preds = reg.run(frames, args.boundary)
+    out = [p.aligned_image if p.detected else f for f, p in zip(frames, preds)]
+    print(f"boundary registration ({args.boundary}): {sum(p.detected for p in preds)} of {len(frames)} frames aligned")
+    reg.close()
+    ctx.close()
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("files", nargs="*", help="images or multi-page TIFFs")
@@ -105,6 +124,8 @@ def main(argv=None):
     ap.add_argument("--no-refinement", action="store_true", help="one detector pass instead of the reference's three")
     ap.add_argument("--crop-to-content", action="store_true")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--boundary", choices=("absolute", "fit_to_page"), default=None,
+                    help="document boundary registration of the frames before the engine, as ExtractPipeline does")
     args = ap.parse_args(argv)
 
     from marie_icr_amd.box_processor import PSMode
@@ -113,6 +134,8 @@ def main(argv=None):
 
     os.makedirs(args.out, exist_ok=True)
     frames = load_frames(args)
+    if args.boundary:
+        frames = register_frames(args, frames)
     engine = build_engine(args)
     t0 = time.perf_counter()
     results = engine.extract(frames, PSMode.SPARSE, CoordinateFormat.XYWH, crop_to_content=args.crop_to_content)

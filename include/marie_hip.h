@@ -285,6 +285,8 @@ typedef struct mhip_dit_config {
   float rpn_nms_thresh;      /* RPN.NMS_THRESH 0.7                                                                  */
   float score_thresh;        /* ROI_HEADS.SCORE_THRESH_TEST 0.05                                                    */
   float nms_thresh;          /* ROI_HEADS.NMS_THRESH_TEST 0.5                                                       */
+  int num_classes;           /* ROI_HEADS.NUM_CLASSES: 1 (text detector), 5 (document boundary model); 1..16;
+                              * more than 1 needs detections_per_image <= 1000                                         */
 } mhip_dit_config;
 int mhip_dit_default_config(int model, mhip_dit_config* cfg);
 /* ResizeShortestEdge output (nh, nw) and the /32 canvas for an h x w page */
@@ -304,6 +306,12 @@ int mhip_dit_detect(mhip_dit* m, const uint8_t* const* pages_dev, int B, int h, 
                     float* scores_host, int* counts_host);
 int mhip_dit_detect_host(mhip_dit* m, const uint8_t* pages_host, int B, int h, int w, float* boxes_host,
                          float* scores_host, int* counts_host);
+/* the same with the predicted class of every box (detectron2 pred_classes, 0-based; all 0 when num_classes is 1):
+ * classes_host [B][1000] int32, may be NULL                                                                          */
+int mhip_dit_detect_ex(mhip_dit* m, const uint8_t* const* pages_dev, int B, int h, int w, float* boxes_host,
+                       float* scores_host, int32_t* classes_host, int* counts_host);
+int mhip_dit_detect_ex_host(mhip_dit* m, const uint8_t* pages_host, int B, int h, int w, float* boxes_host,
+                            float* scores_host, int32_t* classes_host, int* counts_host);
 /* one page plus the intermediates the parity tests compare: FPN maps p2..p6 fp32 NHWC and the RPN proposals (any NULL) */
 int mhip_dit_debug_host(mhip_dit* m, const uint8_t* page_host, int h, int w, float* boxes_host, float* scores_host,
                         int* count_host, float* p2, float* p3, float* p4, float* p5, float* p6, float* prop_boxes,
@@ -327,6 +335,39 @@ int mhip_roi_align_host(mhip_ctx* ctx, const float* const* feats_host, const int
 int mhip_det_final_host(mhip_ctx* ctx, const float* head_host, const float* rois_host, int n, int img_h, int img_w,
                         int page_h, int page_w, float score_thresh, float nms_thresh, int max_det, float* boxes_out,
                         float* scores_out, int* count_out);
+/* The K-class FastRCNNOutputLayers.inference + detector_postprocess (K = num_classes > 1): head_host [n][ld] fp32 with
+ * the K + 1 class logits (background last) in columns 0..K and the class-specific deltas [4K] in columns K+1..5K;
+ * softmax, decode (10, 10, 5, 5), drop non-finite rows, clip, (row, class) pairs with score > score_thresh, torchvision
+ * batched_nms with the class-offset coordinates, top max_det (<= 1000), rescale to the page, clip, drop empty.
+ * -> boxes [1000][4], scores [1000], classes [1000] int32, *count.                                                       */
+int mhip_det_final_multi_host(mhip_ctx* ctx, const float* head_host, int ld, const float* rois_host, int n, int num_classes,
+                              int img_h, int img_w, int page_h, int page_w, float score_thresh, float nms_thresh,
+                              int max_det, float* boxes_out, float* scores_out, int32_t* classes_out, int* count_out);
+/* ---- document boundary registration (UnilmDocumentBoundaryRegistration.predict_document_image, the warp) ----------------- */
+/* replaces: the crop / cv2.resize(INTER_AREA) / cv2.copyMakeBorder / cv2.circle / cv2.resize(INTER_CUBIC) chain of
+ * marie/components/document_registration/unilm_dit.py:416-508 on a device page.  The crop window of the page is resized
+ * to out_w x out_h (INTER_AREA semantics: area shrink, or OpenCV's linear resampler with area coefficients when either axis
+ * enlarges; a plain copy when the sizes agree) and placed at (left, top) of a white canvas_w x canvas_h canvas, every
+ * canvas pixel written once; filled Circle()s of marker_radius at the marker centres (clipped to the canvas) in
+ * marker_color (array channel order).  When the canvas differs from final_w x final_h it is then resized to it with
+ * INTER_CUBIC.                                                                                                              */
+typedef struct mhip_register_desc {
+  int crop_x, crop_y, crop_w, crop_h;   /* window of the page (inside it); crop_w or crop_h 0: nothing is pasted       */
+  int out_w, out_h;                     /* resized window size                                                         */
+  int left, top;                        /* where the resized window lands on the canvas                                */
+  int canvas_w, canvas_h;               /* the aligned page before the shape restore                                   */
+  int n_markers;                        /* 0..4                                                                        */
+  int marker_x[4], marker_y[4];
+  int marker_radius;                    /* 0..64                                                                       */
+  int marker_color[3];
+  int final_w, final_h;                 /* the returned page                                                           */
+} mhip_register_desc;
+/* page_dev u8 [h][w][3] with rows page_pitch bytes apart -> out_dev u8 [final_h][final_w][3] packed.  scratch_dev holds
+ * the canvas when a restore is needed (canvas_w * canvas_h * 3 bytes; may be NULL otherwise).  Enqueued on the ctx stream. */
+int mhip_register_warp(mhip_ctx* ctx, const uint8_t* page_dev, int h, int w, size_t page_pitch, const mhip_register_desc* d,
+                       uint8_t* scratch_dev, uint8_t* out_dev);
+int mhip_register_warp_host(mhip_ctx* ctx, const uint8_t* page_host, int h, int w, const mhip_register_desc* d,
+                            uint8_t* out_host);
 /* ---- overlay cleaner: pix2pixHD LocalEnhancer generator + blend -------------------------------- */
 /* replaces: OverlayProcessor.__extract_segmentation_mask / model.test() (marie/overlay/overlay.py:165-189;
  * marie/models/pix2pix/models/networks_hd.py:24-213, netG "local", instance norm, spectral-normed convolutions) — page in HBM

@@ -86,11 +86,17 @@ _SIGNATURES = (
     ("mhip_dit_workspace_bytes", _sz, [_vp, _i, _i, _i]),
     ("mhip_dit_detect", _i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     ("mhip_dit_detect_host", _i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    ("mhip_dit_detect_ex", _i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    ("mhip_dit_detect_ex_host", _i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     ("mhip_dit_debug_host", _i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("mhip_dit_debug_taps_host", _i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("mhip_rpn_proposals_host", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_float, _vp, _vp, _vp]),
     ("mhip_roi_align_host", _i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     ("mhip_det_final_host", _i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_float, C.c_float, _i, _vp, _vp, _vp]),
+    ("mhip_det_final_multi_host", _i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, C.c_float, C.c_float, _i, _vp, _vp,
+                                       _vp, _vp]),
+    ("mhip_register_warp", _i, [_vp, _vp, _i, _i, C.c_size_t, _vp, _vp, _vp]),
+    ("mhip_register_warp_host", _i, [_vp, _vp, _i, _i, _vp, _vp]),
     ("mhip_blackout_bboxes", _i, [_vp, _vp, _i, _i, _vp, _i, C.POINTER(_i)]),
     ("mhip_content_extents", _i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp]),
     ("mhip_overlay_create", _i, [_vp, _i, _i, C.POINTER(_vp)]),
@@ -165,7 +171,16 @@ class DitConfig(C.Structure):
     """mirror of mhip_dit_config (include/marie_hip.h)"""
     _fields_ = [("model", C.c_int), ("min_size_test", C.c_int), ("max_size_test", C.c_int),
                 ("detections_per_image", C.c_int), ("anchor_sizes", C.c_float * 5), ("aspect_ratios", C.c_float * 3),
-                ("rpn_nms_thresh", C.c_float), ("score_thresh", C.c_float), ("nms_thresh", C.c_float)]
+                ("rpn_nms_thresh", C.c_float), ("score_thresh", C.c_float), ("nms_thresh", C.c_float),
+                ("num_classes", C.c_int)]
+
+
+class RegisterDesc(C.Structure):
+    """mirror of mhip_register_desc (include/marie_hip.h)"""
+    _fields_ = [("crop_x", C.c_int), ("crop_y", C.c_int), ("crop_w", C.c_int), ("crop_h", C.c_int), ("out_w", C.c_int),
+                ("out_h", C.c_int), ("left", C.c_int), ("top", C.c_int), ("canvas_w", C.c_int), ("canvas_h", C.c_int),
+                ("n_markers", C.c_int), ("marker_x", C.c_int * 4), ("marker_y", C.c_int * 4), ("marker_radius", C.c_int),
+                ("marker_color", C.c_int * 3), ("final_w", C.c_int), ("final_h", C.c_int)]
 
 
 class TrocrConfig(C.Structure):

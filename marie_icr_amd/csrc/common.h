@@ -309,6 +309,27 @@ struct DetFinalDesc {
   int* out_count = nullptr;      // [images]
 };
 int mhip_launch_det_final(mhip_ctx* ctx, const DetFinalDesc& d);
+// the K-class final stage (K = num_classes > 1): head [images][max_rois][ld] = K + 1 logits (background last), 4K deltas
+constexpr int DET_MAX_CLASSES = 16;
+struct DetFinalMultiDesc {
+  const float* head = nullptr;
+  int ld = 0, num_classes = 2;
+  const float* rois = nullptr;
+  const int* counts = nullptr;
+  int images = 1, max_rois = 1000;
+  int img_h = 0, img_w = 0, out_h = 0, out_w = 0;
+  float score_thr = 0.05f, nms_thr = 0.5f;
+  int max_det = 100;             // <= 1000
+  unsigned long long* cls_keys = nullptr;   // scratch [images][K][1000]
+  float* cls_boxes = nullptr;               // scratch [images][K][1000][4]
+  int* cls_counts = nullptr;                // scratch [images][K]
+  float* out_boxes = nullptr;    // [images][max_rois][4]
+  float* out_scores = nullptr;   // [images][max_rois]
+  int* out_classes = nullptr;    // [images][max_rois]
+  int* out_count = nullptr;      // [images]
+};
+size_t mhip_det_final_multi_scratch_bytes(int images, int num_classes);
+int mhip_launch_det_final_multi(mhip_ctx* ctx, const DetFinalMultiDesc& d);
 int mhip_launch_blackout(mhip_ctx* ctx, uint8_t* page, int H, int W, const int* boxes_dev, int n, int* changed_dev);
 int mhip_launch_subsample2(mhip_ctx* ctx, int precision, const void* in, void* out, int B, int H, int W, int C);
 

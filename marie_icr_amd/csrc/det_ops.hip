@@ -466,6 +466,215 @@ __global__ __launch_bounds__(1024) void det_final_kernel(FinalArgs p) {
   }
 }
 
+// ---- the K-class final stage (ROI_HEADS.NUM_CLASSES > 1: the document boundary model) ---------------------------------------
+// detectron2 fast_rcnn_inference_single_image for K classes: softmax over K + 1 logits (background last), class-specific
+// deltas decoded with weights (10, 10, 5, 5), rows with any non-finite box or score dropped, clip, (row, class) pairs with
+// score > 0.05 in row-major order, torchvision batched_nms (for <= 20 000 box coordinates: the coordinate-offset trick, every
+// box shifted by class * (max coordinate + 1) before one NMS), top-k, then detector_postprocess.
+// The shift keeps boxes of different classes at least 1 apart, so the single NMS is exactly one NMS per class on the shifted
+// boxes (same fp32 IoU roundings), merged in (score, pair index) order: one workgroup per (class, image) with the LDS sort
+// and bit-mask NMS of det_final_kernel, then one merge workgroup per image.
+// exp is evaluated in double and rounded (a correctly rounded expf), so a host restatement reproduces every bit; the
+// clamp of dw / dh propagates NaN as torch.clamp does (fminf would not).
+struct FinalMultiArgs {
+  const float* head;      // [B][max_rois][ld]
+  int ld, K;
+  const float* rois;      // [B][max_rois][4]
+  const int* counts;      // [B]
+  int max_rois;
+  int img_h, img_w;
+  float score_thr, nms_thr;
+  u64* cls_keys;          // [B][K][TOPK]: kept pairs of the class, score-ordered
+  float* cls_boxes;       // [B][K][TOPK][4]: by row
+  int* cls_counts;        // [B][K]
+};
+
+__device__ __forceinline__ float exp_cr(float x) { return (float)exp((double)x); }
+
+__device__ __forceinline__ void decode_cls(const float a[4], const float* d, float out[4]) {
+  const float clampv = 4.135166556742356f;   // log(1000 / 16)
+  const float widths = a[2] - a[0], heights = a[3] - a[1];
+  const float ctr_x = a[0] + 0.5f * widths, ctr_y = a[1] + 0.5f * heights;
+  const float dx = d[0] / 10.f, dy = d[1] / 10.f;
+  float dw = d[2] / 5.f, dh = d[3] / 5.f;
+  dw = dw > clampv ? clampv : dw;
+  dh = dh > clampv ? clampv : dh;
+  const float pcx = dx * widths + ctr_x, pcy = dy * heights + ctr_y;
+  const float pw = exp_cr(dw) * widths, ph = exp_cr(dh) * heights;
+  out[0] = pcx - 0.5f * pw; out[1] = pcy - 0.5f * ph;
+  out[2] = pcx + 0.5f * pw; out[3] = pcy + 0.5f * ph;
+}
+
+__device__ __forceinline__ bool finite4(const float b[4]) {
+  return isfinite(b[0]) && isfinite(b[1]) && isfinite(b[2]) && isfinite(b[3]);
+}
+
+__device__ __forceinline__ void clip4(float b[4], int img_h, int img_w) {
+  b[0] = fminf(fmaxf(b[0], 0.f), (float)img_w); b[2] = fminf(fmaxf(b[2], 0.f), (float)img_w);
+  b[1] = fminf(fmaxf(b[1], 0.f), (float)img_h); b[3] = fminf(fmaxf(b[3], 0.f), (float)img_h);
+}
+
+// softmax probability of class j of a row: max left to right, exp(x - max), sum left to right, divide
+__device__ __forceinline__ float row_prob(const float* h, float mx, float sum, int j) {
+  return exp_cr(h[j] - mx) / sum;
+}
+
+__global__ __launch_bounds__(1024) void det_final_cls_kernel(FinalMultiArgs p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  u64* keys = (u64*)smem;                               // 1024 * 8
+  float* sbox = (float*)(smem + 8192);                  // 1024 * 16
+  unsigned char* keep = (unsigned char*)(smem + 8192 + 16384 + 4096);
+  u64* mask = (u64*)(smem + 8192 + 16384 + 4096 + 1024);   // [1000][16]
+  __shared__ int wave_cnt[16], wave_off[16];
+  __shared__ int s_m;
+  __shared__ unsigned s_max;
+  const int cls = blockIdx.x, img = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int K = p.K, n = p.counts[img];
+  if (tid == 0) s_max = 0u;
+  __syncthreads();
+  float bx[4] = {0, 0, 0, 0}, prob = 0.f;
+  bool ok = false;
+  if (tid < n) {
+    const float* h = p.head + ((size_t)img * p.max_rois + tid) * p.ld;
+    const float* a = p.rois + ((size_t)img * p.max_rois + tid) * 4;
+    const float an[4] = {a[0], a[1], a[2], a[3]};
+    float mx = h[0];
+    for (int j = 1; j <= K; ++j) mx = fmaxf(mx, h[j]);
+    float sum = 0.f;
+    for (int j = 0; j <= K; ++j) sum = sum + exp_cr(h[j] - mx);
+    bool valid = isfinite(row_prob(h, mx, sum, K));   // background
+    float local_max = 0.f;
+    for (int j = 0; j < K; ++j) {
+      const float pj = row_prob(h, mx, sum, j);
+      float b[4];
+      decode_cls(an, h + K + 1 + 4 * j, b);
+      valid = valid && isfinite(pj) && finite4(b);
+      clip4(b, p.img_h, p.img_w);
+      if (pj > p.score_thr) local_max = fmaxf(local_max, fmaxf(fmaxf(b[0], b[1]), fmaxf(b[2], b[3])));
+      if (j == cls) { prob = pj; bx[0] = b[0]; bx[1] = b[1]; bx[2] = b[2]; bx[3] = b[3]; }
+    }
+    ok = valid && prob > p.score_thr;
+    if (valid && local_max > 0.f) atomicMax(&s_max, __float_as_uint(local_max));   // non-negative: uint order = float order
+  }
+  keys[tid] = ok ? (((u64)ordered_key(prob) << 32) | (u64)(0xffffffffu - (unsigned)tid)) : 0ull;
+  const u64 bal = __ballot(ok);
+  if (lane == 0) wave_cnt[wv] = __popcll(bal);
+  __syncthreads();
+  if (tid == 0) {
+    int acc = 0;
+    for (int w = 0; w < 16; ++w) acc += wave_cnt[w];
+    s_m = acc;
+  }
+  // batched_nms: offsets = idxs * (boxes.max() + 1), boxes_for_nms = boxes + offsets
+  const float off = (float)cls * (__uint_as_float(s_max) + 1.f);
+  sbox[4 * tid] = bx[0] + off; sbox[4 * tid + 1] = bx[1] + off; sbox[4 * tid + 2] = bx[2] + off; sbox[4 * tid + 3] = bx[3] + off;
+  bitonic_desc(keys, 1024);
+  const int m = s_m;
+  float gb[4] = {0, 0, 0, 0};
+  unsigned src = 0;
+  if (tid < m) {
+    src = 0xffffffffu - (unsigned)(keys[tid] & 0xffffffffu);
+    gb[0] = sbox[4 * src]; gb[1] = sbox[4 * src + 1]; gb[2] = sbox[4 * src + 2]; gb[3] = sbox[4 * src + 3];
+  }
+  __syncthreads();
+  sbox[4 * tid] = gb[0]; sbox[4 * tid + 1] = gb[1]; sbox[4 * tid + 2] = gb[2]; sbox[4 * tid + 3] = gb[3];
+  __syncthreads();
+  nms_sorted(sbox, m, p.nms_thr, mask, keep);
+  const bool kv = tid < m && keep[tid];
+  const u64 b1 = __ballot(kv);
+  if (lane == 0) wave_cnt[wv] = __popcll(b1);
+  __syncthreads();
+  if (tid == 0) {
+    int acc = 0;
+    for (int w = 0; w < 16; ++w) { wave_off[w] = acc; acc += wave_cnt[w]; }
+    p.cls_counts[img * K + cls] = acc;
+  }
+  __syncthreads();
+  if (kv) {
+    const int rank = wave_off[wv] + __popcll(b1 & ((1ull << lane) - 1ull));
+    const unsigned pair = src * (unsigned)K + (unsigned)cls;   // index of the (row, class) pair in row-major order
+    p.cls_keys[((size_t)img * K + cls) * TOPK + rank] = (keys[tid] & 0xffffffff00000000ull) | (u64)(0xffffffffu - pair);
+    // the unshifted clipped box of (src, cls), recomputed from the inputs (the same arithmetic as above)
+    const float* h = p.head + ((size_t)img * p.max_rois + src) * p.ld;
+    const float* a = p.rois + ((size_t)img * p.max_rois + src) * 4;
+    const float an[4] = {a[0], a[1], a[2], a[3]};
+    float b[4];
+    decode_cls(an, h + K + 1 + 4 * cls, b);
+    clip4(b, p.img_h, p.img_w);
+    float* o = p.cls_boxes + (((size_t)img * K + cls) * TOPK + src) * 4;
+    o[0] = b[0]; o[1] = b[1]; o[2] = b[2]; o[3] = b[3];
+  }
+}
+
+// merge the per-class kept lists of an image in (score desc, pair index asc) order = the order of the single NMS's keep,
+// top max_det, then detector_postprocess (scale to the page, clip, drop empty), order preserved
+struct MergeMultiArgs {
+  const u64* cls_keys;
+  const float* cls_boxes;
+  const int* cls_counts;
+  int K, max_rois, max_det;
+  int out_h, out_w;
+  float fx, fy;           // page / resized, rounded to fp32 once
+  float* out_boxes;
+  float* out_scores;
+  int* out_classes;
+  int* out_count;
+};
+
+__global__ __launch_bounds__(1024) void det_merge_cls_kernel(MergeMultiArgs p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  u64* keys = (u64*)smem;
+  __shared__ int wave_cnt[16], wave_off[16];
+  const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, K = p.K;
+  int total = 0;
+  for (int c = 0; c < K; ++c) total += p.cls_counts[img * K + c];
+  int sort_n = 1024;
+  while (sort_n < total) sort_n <<= 1;
+  for (int i = tid; i < sort_n; i += 1024) keys[i] = 0ull;
+  __syncthreads();
+  int base = 0;
+  for (int c = 0; c < K; ++c) {
+    const int cnt = p.cls_counts[img * K + c];
+    for (int i = tid; i < cnt; i += 1024) keys[base + i] = p.cls_keys[((size_t)img * K + c) * TOPK + i];
+    base += cnt;
+  }
+  __syncthreads();
+  bitonic_desc(keys, sort_n);
+  const int m = total < p.max_det ? total : p.max_det;
+  bool kv = tid < m;
+  float ob[4] = {0, 0, 0, 0}, sc = 0.f;
+  int cls = 0;
+  if (kv) {
+    const u64 k = keys[tid];
+    const unsigned pair = 0xffffffffu - (unsigned)(k & 0xffffffffu);
+    const int row = (int)(pair / (unsigned)K);
+    cls = (int)(pair % (unsigned)K);
+    sc = key_to_float((unsigned)(k >> 32));
+    const float* b = p.cls_boxes + (((size_t)img * K + cls) * TOPK + row) * 4;
+    ob[0] = fminf(fmaxf(b[0] * p.fx, 0.f), (float)p.out_w);
+    ob[2] = fminf(fmaxf(b[2] * p.fx, 0.f), (float)p.out_w);
+    ob[1] = fminf(fmaxf(b[1] * p.fy, 0.f), (float)p.out_h);
+    ob[3] = fminf(fmaxf(b[3] * p.fy, 0.f), (float)p.out_h);
+    kv = (ob[2] - ob[0] > 0.f) && (ob[3] - ob[1] > 0.f);
+  }
+  const u64 b2 = __ballot(kv);
+  if (lane == 0) wave_cnt[wv] = __popcll(b2);
+  __syncthreads();
+  if (tid == 0) {
+    int acc = 0;
+    for (int w = 0; w < 16; ++w) { wave_off[w] = acc; acc += wave_cnt[w]; }
+    p.out_count[img] = acc;
+  }
+  __syncthreads();
+  if (kv) {
+    const int at = wave_off[wv] + __popcll(b2 & ((1ull << lane) - 1ull));
+    float* o = p.out_boxes + ((size_t)img * p.max_rois + at) * 4;
+    o[0] = ob[0]; o[1] = ob[1]; o[2] = ob[2]; o[3] = ob[3];
+    p.out_scores[(size_t)img * p.max_rois + at] = sc;
+    p.out_classes[(size_t)img * p.max_rois + at] = cls;
+  }
+}
+
 // ---- blackout_bboxes: white-fill each box unless its snippet is framed by black or mostly black ------------------------------
 // gray = cv2.COLOR_BGR2GRAY: (B*1868 + G*9617 + R*4899 + 8192) >> 14.  One block per box; phase 1 decides, phase 2 fills.
 __global__ __launch_bounds__(256) void blackout_kernel(uint8_t* __restrict__ page, int H, int W, const int* __restrict__ boxes,
@@ -589,6 +798,43 @@ int mhip_launch_det_final(mhip_ctx* ctx, const DetFinalDesc& d) {
   });
   PROF_LAUNCH(ctx, MHIP_K_DET_OPS, hipLaunchKernelGGL(det_final_kernel, dim3(d.images), dim3(1024), lds, ctx->stream, a));
   CHECK_LAUNCH(ctx, "det_final");
+  return 0;
+}
+
+size_t mhip_det_final_multi_scratch_bytes(int images, int num_classes) {
+  const size_t per = (size_t)images * num_classes;
+  return per * TOPK * 8 + 256 + per * TOPK * 16 + 256 + per * 4 + 256;
+}
+
+int mhip_launch_det_final_multi(mhip_ctx* ctx, const DetFinalMultiDesc& d) {
+  if (d.max_rois > 1000) return mhip_fail(ctx, MHIP_EINVAL, "det_final_multi: at most 1000 proposals per image");
+  if (d.num_classes < 2 || d.num_classes > DET_MAX_CLASSES) return mhip_fail(ctx, MHIP_EINVAL, "det_final_multi: %d classes", d.num_classes);
+  if (d.max_det < 0 || d.max_det > 1000) return mhip_fail(ctx, MHIP_EINVAL, "det_final_multi: max_det %d above 1000", d.max_det);
+  if (d.ld < 5 * d.num_classes + 1) return mhip_fail(ctx, MHIP_EINVAL, "det_final_multi: head row of %d floats", d.ld);
+  FinalMultiArgs a;
+  a.head = d.head; a.ld = d.ld; a.K = d.num_classes; a.rois = d.rois; a.counts = d.counts; a.max_rois = d.max_rois;
+  a.img_h = d.img_h; a.img_w = d.img_w; a.score_thr = d.score_thr; a.nms_thr = d.nms_thr;
+  a.cls_keys = d.cls_keys; a.cls_boxes = d.cls_boxes; a.cls_counts = d.cls_counts;
+  MergeMultiArgs g;
+  g.cls_keys = d.cls_keys; g.cls_boxes = d.cls_boxes; g.cls_counts = d.cls_counts;
+  g.K = d.num_classes; g.max_rois = d.max_rois; g.max_det = d.max_det; g.out_h = d.out_h; g.out_w = d.out_w;
+  g.fx = (float)((double)d.out_w / (double)d.img_w);
+  g.fy = (float)((double)d.out_h / (double)d.img_h);
+  g.out_boxes = d.out_boxes; g.out_scores = d.out_scores; g.out_classes = d.out_classes; g.out_count = d.out_count;
+  const int lds1 = 8192 + 16384 + 4096 + 1024 + 1000 * 16 * 8;
+  int sort_n = 1024;
+  while (sort_n < d.num_classes * TOPK) sort_n <<= 1;
+  const int lds2 = sort_n * 8;
+  static std::once_flag attr;
+  std::call_once(attr, [&] {
+    (void)hipFuncSetAttribute((const void*)det_final_cls_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds1);
+    (void)hipFuncSetAttribute((const void*)det_merge_cls_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 8);
+  });
+  PROF_LAUNCH(ctx, MHIP_K_DET_OPS, {
+    hipLaunchKernelGGL(det_final_cls_kernel, dim3(d.num_classes, d.images), dim3(1024), lds1, ctx->stream, a);
+    hipLaunchKernelGGL(det_merge_cls_kernel, dim3(d.images), dim3(1024), lds2, ctx->stream, g);
+  });
+  CHECK_LAUNCH(ctx, "det_final_multi");
   return 0;
 }
 

@@ -29,6 +29,11 @@ namespace {
 constexpr int FPN_C = 256, FC_DIM = 1024, POOL = 7, MAX_ROIS = 1000;
 const char* kVitPrefix = "backbone.bottom_up.backbone.";
 
+// box predictor rows (cls_score K + 1, then bbox_pred 4K; padded for the GEMM's weight tiles) and the head row pitch in floats:
+// the single-class text detector keeps its 64 rows and rows of 8
+int pred_rows(int K) { return std::max(64, (5 * K + 1 + 63) / 64 * 64); }
+int head_ld(int K) { return K == 1 ? 8 : (5 * K + 1 + 7) / 8 * 8; }
+
 struct DitGeom {
   int nh, nw, H32, W32;
   int lh[5], lw[5];   // p2..p6
@@ -77,6 +82,7 @@ extern "C" int mhip_dit_default_config(int model, mhip_dit_config* c) {
   c->rpn_nms_thresh = 0.7f;
   c->score_thresh = 0.05f;
   c->nms_thresh = 0.5f;
+  c->num_classes = 1;
   return MHIP_OK;
 }
 
@@ -96,6 +102,10 @@ extern "C" int mhip_dit_create(mhip_ctx* ctx, int precision, const mhip_dit_conf
   *out = nullptr;
   if (precision != MHIP_PREC_F16 && precision != MHIP_PREC_F32) return mhip_fail(ctx, MHIP_EINVAL, "unknown precision %d", precision);
   if (cfg->min_size_test < 32 || cfg->max_size_test < cfg->min_size_test) return mhip_fail(ctx, MHIP_EINVAL, "dit: bad test sizes");
+  if (cfg->num_classes < 1 || cfg->num_classes > DET_MAX_CLASSES)
+    return mhip_fail(ctx, MHIP_EINVAL, "dit: num_classes %d (1..%d)", cfg->num_classes, DET_MAX_CLASSES);
+  if (cfg->num_classes > 1 && (cfg->detections_per_image < 0 || cfg->detections_per_image > MAX_ROIS))
+    return mhip_fail(ctx, MHIP_EINVAL, "dit: %d classes need detections_per_image <= %d", cfg->num_classes, MAX_ROIS);
   mhip_vit_config vc{};
   vc.dim = cfg->model ? 1024 : 768;
   vc.depth = cfg->model ? 24 : 12;
@@ -120,7 +130,8 @@ extern "C" int mhip_dit_create(mhip_ctx* ctx, int precision, const mhip_dit_conf
   a.take("rpn_head_w", (size_t)16 * FPN_C * es); a.take("rpn_head_b", 64 * 4);
   a.take("fc1_w", (size_t)FC_DIM * POOL * POOL * FPN_C * es); a.take("fc1_b", FC_DIM * 4);
   a.take("fc2_w", (size_t)FC_DIM * FC_DIM * es); a.take("fc2_b", FC_DIM * 4);
-  a.take("pred_w", (size_t)64 * FC_DIM * es); a.take("pred_b", 64 * 4);
+  const int PR = pred_rows(cfg->num_classes);
+  a.take("pred_w", (size_t)PR * FC_DIM * es); a.take("pred_b", (size_t)PR * 4);
   *out = m;
   return MHIP_OK;
 }
@@ -221,10 +232,11 @@ extern "C" int mhip_dit_finalize(mhip_dit* m) {
     const HostTensor* b1 = st.find(ctx, "roi_heads.box_head.fc1.bias", {FC_DIM});
     const HostTensor* w2 = st.find(ctx, "roi_heads.box_head.fc2.weight", {FC_DIM, FC_DIM});
     const HostTensor* b2 = st.find(ctx, "roi_heads.box_head.fc2.bias", {FC_DIM});
-    const HostTensor* cw = st.find(ctx, "roi_heads.box_predictor.cls_score.weight", {2, FC_DIM});
-    const HostTensor* cb = st.find(ctx, "roi_heads.box_predictor.cls_score.bias", {2});
-    const HostTensor* bw = st.find(ctx, "roi_heads.box_predictor.bbox_pred.weight", {4, FC_DIM});
-    const HostTensor* bb = st.find(ctx, "roi_heads.box_predictor.bbox_pred.bias", {4});
+    const int NC = m->cfg.num_classes;
+    const HostTensor* cw = st.find(ctx, "roi_heads.box_predictor.cls_score.weight", {NC + 1, FC_DIM});
+    const HostTensor* cb = st.find(ctx, "roi_heads.box_predictor.cls_score.bias", {NC + 1});
+    const HostTensor* bw = st.find(ctx, "roi_heads.box_predictor.bbox_pred.weight", {4 * NC, FC_DIM});
+    const HostTensor* bb = st.find(ctx, "roi_heads.box_predictor.bbox_pred.bias", {4 * NC});
     if (!w1 || !b1 || !w2 || !b2 || !cw || !cb || !bw || !bb) return MHIP_ESTATE;
     // torch flattens the pooled (C, 7, 7) as k = c*49 + bin; ROIAlign here writes k' = bin*C + c
     std::vector<float> tmp(w1->numel());
@@ -236,11 +248,11 @@ extern "C" int mhip_dit_finalize(mhip_dit* m) {
     memcpy(a.h("fc1_b"), b1->data.data(), FC_DIM * 4);
     Arena::put(prec, a.h("fc2_w"), w2->data.data(), w2->numel());
     memcpy(a.h("fc2_b"), b2->data.data(), FC_DIM * 4);
-    Arena::put(prec, a.h("pred_w"), cw->data.data(), (size_t)2 * FC_DIM);
-    Arena::put(prec, a.h("pred_w") + (size_t)2 * FC_DIM * es, bw->data.data(), (size_t)4 * FC_DIM);
+    Arena::put(prec, a.h("pred_w"), cw->data.data(), (size_t)(NC + 1) * FC_DIM);
+    Arena::put(prec, a.h("pred_w") + (size_t)(NC + 1) * FC_DIM * es, bw->data.data(), (size_t)4 * NC * FC_DIM);
     float* pb = (float*)a.h("pred_b");
-    pb[0] = cb->data[0]; pb[1] = cb->data[1];
-    for (int i = 0; i < 4; ++i) pb[2 + i] = bb->data[i];
+    for (int i = 0; i <= NC; ++i) pb[i] = cb->data[i];
+    for (int i = 0; i < 4 * NC; ++i) pb[NC + 1 + i] = bb->data[i];
   }
   if ((rc = a.upload(ctx))) return rc;
   m->ready = true;
@@ -259,7 +271,9 @@ static size_t dit_ws_bytes(const mhip_dit* m, int B, int h, int w, const DitGeom
   b += 4 * ((size_t)B * px * FPN_C * es + 5 * 256);            // lateral, merged, p-levels, rpn conv
   b += (size_t)B * px * 16 * 4 + 5 * 256;                      // rpn head
   b += (size_t)B * (5 * MAX_ROIS * 5 * 4 + MAX_ROIS * 5 * 4 * 2 + 64) + 4096;
-  b += (size_t)B * MAX_ROIS * (POOL * POOL * FPN_C + 2 * FC_DIM) * es + (size_t)B * MAX_ROIS * 8 * 4 + 4096;
+  const int K = m->cfg.num_classes;
+  b += (size_t)B * MAX_ROIS * (POOL * POOL * FPN_C + 2 * FC_DIM) * es + (size_t)B * MAX_ROIS * head_ld(K) * 4 + 4096;
+  if (K > 1) b += mhip_det_final_multi_scratch_bytes(B, K) + (size_t)B * MAX_ROIS * 4 + 4096;
   return b + (1 << 16);
 }
 
@@ -276,11 +290,11 @@ struct DitDebug {
   float* prop_scores = nullptr;  // host [1000]
   int* prop_count = nullptr;
   float* rpn_head[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // host fp32 [H*W][16] per level (3 logits, 12 deltas, pad)
-  float* box_head = nullptr;     // host fp32 [1000][8] (2 class scores, 4 deltas, 2 pad), rows past prop_count undefined
+  float* box_head = nullptr;     // host fp32 [1000][head_ld] (K + 1 class scores, 4K deltas, pad), rows past prop_count undefined
 };
 
 static int dit_run(mhip_dit* m, const uint8_t* const* pages_dev, int B, int h, int w, float* boxes_host, float* scores_host,
-                   int* counts_host, const DitDebug* dbg) {
+                   int32_t* classes_host, int* counts_host, const DitDebug* dbg) {
   mhip_ctx* ctx = m->ctx;
   if (!m->ready) return mhip_fail(ctx, MHIP_ESTATE, "dit: weights not finalized");
   if (B < 1 || h < 1 || w < 1) return mhip_fail(ctx, MHIP_EINVAL, "dit: bad page geometry");
@@ -356,11 +370,12 @@ static int dit_run(mhip_dit* m, const uint8_t* const* pages_dev, int B, int h, i
   if ((rc = mhip_launch_roi_align(ctx, prec, ro))) return rc;
   char* f1 = ws.take((size_t)B * MAX_ROIS * FC_DIM * es);
   char* f2 = ws.take((size_t)B * MAX_ROIS * FC_DIM * es);
-  float* hd = ws.take<float>((size_t)B * MAX_ROIS * 8 * 4);
+  const int K = m->cfg.num_classes, LD = head_ld(K);
+  float* hd = ws.take<float>((size_t)B * MAX_ROIS * LD * 4);
   const long long R = (long long)B * MAX_ROIS;
   if ((rc = mhip_gemm(ctx, prec, pooled, a.d("fc1_w"), R, FC_DIM, K1, nullptr, a.d<float>("fc1_b"), f1, ACT_RELU, 0))) return rc;
   if ((rc = mhip_gemm(ctx, prec, f1, a.d("fc2_w"), R, FC_DIM, FC_DIM, nullptr, a.d<float>("fc2_b"), f2, ACT_RELU, 0))) return rc;
-  if ((rc = mhip_gemm(ctx, prec, f2, a.d("pred_w"), R, 6, FC_DIM, nullptr, a.d<float>("pred_b"), hd, ACT_NONE, 1, nullptr, 8, 1))) return rc;
+  if ((rc = mhip_gemm(ctx, prec, f2, a.d("pred_w"), R, 5 * K + 1, FC_DIM, nullptr, a.d<float>("pred_b"), hd, ACT_NONE, 1, nullptr, LD, 1))) return rc;
   DetFinalDesc fd;
   fd.head = hd; fd.rois = rd.out_boxes; fd.counts = rd.out_counts; fd.images = B; fd.max_rois = MAX_ROIS;
   fd.img_h = g.nh; fd.img_w = g.nw; fd.out_h = h; fd.out_w = w;
@@ -368,10 +383,28 @@ static int dit_run(mhip_dit* m, const uint8_t* const* pages_dev, int B, int h, i
   fd.out_boxes = ws.take<float>((size_t)B * MAX_ROIS * 4 * 4);
   fd.out_scores = ws.take<float>((size_t)B * MAX_ROIS * 4);
   fd.out_count = ws.take<int>((size_t)B * 4);
-  if ((rc = mhip_launch_det_final(ctx, fd))) return rc;
+  int* out_classes = nullptr;
+  if (K == 1) {
+    if ((rc = mhip_launch_det_final(ctx, fd))) return rc;
+  } else {
+    DetFinalMultiDesc md;
+    md.head = hd; md.ld = LD; md.num_classes = K; md.rois = rd.out_boxes; md.counts = rd.out_counts; md.images = B;
+    md.max_rois = MAX_ROIS; md.img_h = g.nh; md.img_w = g.nw; md.out_h = h; md.out_w = w;
+    md.score_thr = m->cfg.score_thresh; md.nms_thr = m->cfg.nms_thresh; md.max_det = m->cfg.detections_per_image;
+    md.cls_keys = ws.take<unsigned long long>((size_t)B * K * MAX_ROIS * 8);
+    md.cls_boxes = ws.take<float>((size_t)B * K * MAX_ROIS * 16);
+    md.cls_counts = ws.take<int>((size_t)B * K * 4);
+    md.out_boxes = fd.out_boxes; md.out_scores = fd.out_scores; md.out_count = fd.out_count;
+    md.out_classes = out_classes = ws.take<int>((size_t)B * MAX_ROIS * 4);
+    if ((rc = mhip_launch_det_final_multi(ctx, md))) return rc;
+  }
   MHIP_HIP(ctx, hipMemcpyAsync(counts_host, fd.out_count, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
   MHIP_HIP(ctx, hipMemcpyAsync(boxes_host, fd.out_boxes, (size_t)B * MAX_ROIS * 16, hipMemcpyDeviceToHost, ctx->stream));
   if (scores_host) MHIP_HIP(ctx, hipMemcpyAsync(scores_host, fd.out_scores, (size_t)B * MAX_ROIS * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (classes_host) {
+    if (out_classes) MHIP_HIP(ctx, hipMemcpyAsync(classes_host, out_classes, (size_t)B * MAX_ROIS * 4, hipMemcpyDeviceToHost, ctx->stream));
+    else memset(classes_host, 0, (size_t)B * MAX_ROIS * 4);
+  }
   if (dbg) {
     float* stage = ws.take<float>((size_t)g.lh[0] * g.lw[0] * FPN_C * 4);
     for (int l = 0; l < 5; ++l)
@@ -384,7 +417,7 @@ static int dit_run(mhip_dit* m, const uint8_t* const* pages_dev, int B, int h, i
     for (int l = 0; l < 5; ++l)
       if (dbg->rpn_head[l])
         MHIP_HIP(ctx, hipMemcpyAsync(dbg->rpn_head[l], rd.head[l], (size_t)g.lh[l] * g.lw[l] * 64, hipMemcpyDeviceToHost, ctx->stream));
-    if (dbg->box_head) MHIP_HIP(ctx, hipMemcpyAsync(dbg->box_head, hd, (size_t)MAX_ROIS * 32, hipMemcpyDeviceToHost, ctx->stream));
+    if (dbg->box_head) MHIP_HIP(ctx, hipMemcpyAsync(dbg->box_head, hd, (size_t)MAX_ROIS * LD * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (dbg->prop_boxes) MHIP_HIP(ctx, hipMemcpyAsync(dbg->prop_boxes, rd.out_boxes, MAX_ROIS * 16, hipMemcpyDeviceToHost, ctx->stream));
     if (dbg->prop_scores) MHIP_HIP(ctx, hipMemcpyAsync(dbg->prop_scores, rd.out_scores, MAX_ROIS * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (dbg->prop_count) MHIP_HIP(ctx, hipMemcpyAsync(dbg->prop_count, rd.out_counts, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -396,11 +429,17 @@ static int dit_run(mhip_dit* m, const uint8_t* const* pages_dev, int B, int h, i
 extern "C" int mhip_dit_detect(mhip_dit* m, const uint8_t* const* pages_dev, int B, int h, int w, float* boxes_host,
                                float* scores_host, int* counts_host) {
   if (!m || !pages_dev || !boxes_host || !counts_host) return MHIP_EINVAL;
-  return dit_run(m, pages_dev, B, h, w, boxes_host, scores_host, counts_host, nullptr);
+  return dit_run(m, pages_dev, B, h, w, boxes_host, scores_host, nullptr, counts_host, nullptr);
 }
 
-extern "C" int mhip_dit_detect_host(mhip_dit* m, const uint8_t* pages_host, int B, int h, int w, float* boxes_host,
-                                    float* scores_host, int* counts_host) {
+extern "C" int mhip_dit_detect_ex(mhip_dit* m, const uint8_t* const* pages_dev, int B, int h, int w, float* boxes_host,
+                                  float* scores_host, int32_t* classes_host, int* counts_host) {
+  if (!m || !pages_dev || !boxes_host || !counts_host) return MHIP_EINVAL;
+  return dit_run(m, pages_dev, B, h, w, boxes_host, scores_host, classes_host, counts_host, nullptr);
+}
+
+static int dit_detect_host(mhip_dit* m, const uint8_t* pages_host, int B, int h, int w, float* boxes_host, float* scores_host,
+                           int32_t* classes_host, int* counts_host) {
   if (!m || !pages_host || !boxes_host || !counts_host) return MHIP_EINVAL;
   mhip_ctx* ctx = m->ctx;
   MHIP_HIP(ctx, hipSetDevice(ctx->device));
@@ -413,11 +452,21 @@ extern "C" int mhip_dit_detect_host(mhip_dit* m, const uint8_t* pages_host, int 
   if (!rc) {
     std::vector<const uint8_t*> ptrs(B);
     for (int b = 0; b < B; ++b) ptrs[b] = dev + pb * b;
-    rc = dit_run(m, ptrs.data(), B, h, w, boxes_host, scores_host, counts_host, nullptr);
+    rc = dit_run(m, ptrs.data(), B, h, w, boxes_host, scores_host, classes_host, counts_host, nullptr);
   }
   (void)hipStreamSynchronize(ctx->stream);
   (void)hipFree(dev);
   return rc;
+}
+
+extern "C" int mhip_dit_detect_host(mhip_dit* m, const uint8_t* pages_host, int B, int h, int w, float* boxes_host,
+                                    float* scores_host, int* counts_host) {
+  return dit_detect_host(m, pages_host, B, h, w, boxes_host, scores_host, nullptr, counts_host);
+}
+
+extern "C" int mhip_dit_detect_ex_host(mhip_dit* m, const uint8_t* pages_host, int B, int h, int w, float* boxes_host,
+                                       float* scores_host, int32_t* classes_host, int* counts_host) {
+  return dit_detect_host(m, pages_host, B, h, w, boxes_host, scores_host, classes_host, counts_host);
 }
 
 // one page, with the intermediate maps the parity tests look at
@@ -437,7 +486,7 @@ extern "C" int mhip_dit_debug_host(mhip_dit* m, const uint8_t* page_host, int h,
     d.fpn[0] = p2; d.fpn[1] = p3; d.fpn[2] = p4; d.fpn[3] = p5; d.fpn[4] = p6;
     d.prop_boxes = prop_boxes; d.prop_scores = prop_scores; d.prop_count = prop_count;
     const uint8_t* ptr = dev;
-    rc = dit_run(m, &ptr, 1, h, w, boxes_host, scores_host, count_host, &d);
+    rc = dit_run(m, &ptr, 1, h, w, boxes_host, scores_host, nullptr, count_host, &d);
   }
   (void)hipStreamSynchronize(ctx->stream);
   (void)hipFree(dev);
@@ -465,7 +514,7 @@ extern "C" int mhip_dit_debug_taps_host(mhip_dit* m, const uint8_t* page_host, i
     }
     d.prop_boxes = prop_boxes; d.prop_scores = prop_scores; d.prop_count = prop_count; d.box_head = box_head;
     const uint8_t* ptr = dev;
-    rc = dit_run(m, &ptr, 1, h, w, boxes_host, scores_host, count_host, &d);
+    rc = dit_run(m, &ptr, 1, h, w, boxes_host, scores_host, nullptr, count_host, &d);
   }
   (void)hipStreamSynchronize(ctx->stream);
   (void)hipFree(dev);
@@ -583,6 +632,45 @@ extern "C" int mhip_det_final_host(mhip_ctx* ctx, const float* head_host, const 
   MHIP_HIP(ctx, hipMemcpyAsync(boxes_out, fd.out_boxes, MAX_ROIS * 16, hipMemcpyDeviceToHost, ctx->stream));
   MHIP_HIP(ctx, hipMemcpyAsync(scores_out, fd.out_scores, MAX_ROIS * 4, hipMemcpyDeviceToHost, ctx->stream));
   MHIP_HIP(ctx, hipMemcpyAsync(count_out, fd.out_count, 4, hipMemcpyDeviceToHost, ctx->stream));
+  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return MHIP_OK;
+}
+
+// head_host [n][ld] (K + 1 class logits, background last, then 4K class-specific deltas), rois_host [n][4] -> detections in page
+// coordinates with their classes
+extern "C" int mhip_det_final_multi_host(mhip_ctx* ctx, const float* head_host, int ld, const float* rois_host, int n,
+                                         int num_classes, int img_h, int img_w, int page_h, int page_w, float score_thresh,
+                                         float nms_thresh, int max_det, float* boxes_out, float* scores_out,
+                                         int32_t* classes_out, int* count_out) {
+  if (!ctx || !head_host || !rois_host || !boxes_out || !scores_out || !classes_out || !count_out || n < 0 || n > MAX_ROIS ||
+      num_classes < 2 || num_classes > DET_MAX_CLASSES || ld < 5 * num_classes + 1)
+    return MHIP_EINVAL;
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  int rc = mhip_ensure_workspace(ctx, (size_t)MAX_ROIS * (ld * 4 + 48) + mhip_det_final_multi_scratch_bytes(1, num_classes) + 8192);
+  if (rc) return rc;
+  Carver ws(ctx->ws);
+  float* head = ws.take<float>((size_t)MAX_ROIS * ld * 4);
+  float* rois = ws.take<float>(MAX_ROIS * 16);
+  int* cnt = ws.take<int>(4);
+  DetFinalMultiDesc md;
+  md.cls_keys = ws.take<unsigned long long>((size_t)num_classes * MAX_ROIS * 8);
+  md.cls_boxes = ws.take<float>((size_t)num_classes * MAX_ROIS * 16);
+  md.cls_counts = ws.take<int>((size_t)num_classes * 4);
+  md.out_boxes = ws.take<float>(MAX_ROIS * 16);
+  md.out_scores = ws.take<float>(MAX_ROIS * 4);
+  md.out_classes = ws.take<int>(MAX_ROIS * 4);
+  md.out_count = ws.take<int>(4);
+  MHIP_HIP(ctx, hipMemcpyAsync(head, head_host, (size_t)n * ld * 4, hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(rois, rois_host, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(cnt, &n, 4, hipMemcpyHostToDevice, ctx->stream));
+  md.head = head; md.ld = ld; md.num_classes = num_classes; md.rois = rois; md.counts = cnt; md.images = 1;
+  md.max_rois = MAX_ROIS; md.img_h = img_h; md.img_w = img_w; md.out_h = page_h; md.out_w = page_w;
+  md.score_thr = score_thresh; md.nms_thr = nms_thresh; md.max_det = max_det;
+  if ((rc = mhip_launch_det_final_multi(ctx, md))) return rc;
+  MHIP_HIP(ctx, hipMemcpyAsync(boxes_out, md.out_boxes, MAX_ROIS * 16, hipMemcpyDeviceToHost, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(scores_out, md.out_scores, MAX_ROIS * 4, hipMemcpyDeviceToHost, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(classes_out, md.out_classes, MAX_ROIS * 4, hipMemcpyDeviceToHost, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(count_out, md.out_count, 4, hipMemcpyDeviceToHost, ctx->stream));
   MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return MHIP_OK;
 }

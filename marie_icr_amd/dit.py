@@ -15,6 +15,8 @@ from ._lib import PREC_F16, Context, DitConfig, ModelHandle, check
 MAX_ROIS = 1000
 ANCHOR_SIZES = (4.0, 8.0, 16.0, 32.0, 64.0)
 ASPECT_RATIOS = (1.5, 3.5, 6.5)
+BOUNDARY_ANCHOR_SIZES = (32.0, 64.0, 128.0, 256.0, 512.0)
+BOUNDARY_ASPECT_RATIOS = (0.5, 1.0, 2.0)
 
 
 def _vp(a):
@@ -26,6 +28,21 @@ def default_config(lib, model: str = "base") -> DitConfig:
     rc = lib.mhip_dit_default_config(0 if model == "base" else 1, C.byref(cfg))
     if rc:
         raise ValueError(f"mhip_dit_default_config({model}) -> {rc}")
+    return cfg
+
+
+def boundary_config(lib) -> DitConfig:
+    """The document boundary model (UnilmDocumentBoundaryRegistration): config/zoo/unilm/dit/object_detection/
+    document_boundary/prod.yaml over its Base-RCNN-FPN.yaml and the detectron2 defaults — dit_base_patch16,
+    MAX_SIZE_TEST 1000, anchors 32..512 x ratios 0.5 / 1 / 2, NUM_CLASSES 5, DETECTIONS_PER_IMAGE 100."""
+    cfg = default_config(lib, "base")
+    cfg.max_size_test = 1000
+    cfg.detections_per_image = 100
+    for i, v in enumerate(BOUNDARY_ANCHOR_SIZES):
+        cfg.anchor_sizes[i] = v
+    for i, v in enumerate(BOUNDARY_ASPECT_RATIOS):
+        cfg.aspect_ratios[i] = v
+    cfg.num_classes = 5
     return cfg
 
 
@@ -70,6 +87,38 @@ class DitModel(ModelHandle):
               "mhip_dit_detect")
         return self._unpack(boxes, scores, counts)
 
+    def detect_ex_host(self, pages_bgr: np.ndarray):
+        """As :meth:`detect_host`, plus the class of every box: list of (boxes, scores, classes int32)."""
+        pages = np.ascontiguousarray(pages_bgr, np.uint8)
+        if pages.ndim == 3:
+            pages = pages[None]
+        B, h, w, _ = pages.shape
+        boxes, scores, classes, counts = self._outputs(B)
+        check(self.ctx.h, self.lib.mhip_dit_detect_ex_host(self.h, _vp(pages), B, h, w, _vp(boxes), _vp(scores), _vp(classes),
+                                                           _vp(counts)), "mhip_dit_detect_ex_host")
+        return [(boxes[b, : counts[b]].copy(), scores[b, : counts[b]].copy(), classes[b, : counts[b]].copy())
+                for b in range(B)]
+
+    def detect_ex_device(self, page_ptrs: Sequence[int], h: int, w: int):
+        """device pages of one size -> list of (boxes, scores, classes int32)."""
+        B = len(page_ptrs)
+        ptrs = (C.c_void_p * B)(*page_ptrs)
+        boxes, scores, classes, counts = self._outputs(B)
+        check(self.ctx.h, self.lib.mhip_dit_detect_ex(self.h, ptrs, B, h, w, _vp(boxes), _vp(scores), _vp(classes), _vp(counts)),
+              "mhip_dit_detect_ex")
+        return [(boxes[b, : counts[b]].copy(), scores[b, : counts[b]].copy(), classes[b, : counts[b]].copy())
+                for b in range(B)]
+
+    @staticmethod
+    def _outputs(B: int):
+        return (np.empty((B, MAX_ROIS, 4), np.float32), np.empty((B, MAX_ROIS), np.float32),
+                np.zeros((B, MAX_ROIS), np.int32), np.zeros((B,), np.int32))
+
+    def head_ld(self) -> int:
+        """floats per row of the box-head output: 8 for one class, 5K + 1 rounded up to 8 otherwise"""
+        k = int(self.cfg.num_classes)
+        return 8 if k == 1 else (5 * k + 1 + 7) // 8 * 8
+
     def debug_host(self, page_bgr: np.ndarray):
         """One page plus what the parity tests look at: FPN maps, the RPN head outputs and the box-head outputs (the inputs
         of the two discrete stages as this run computed them), proposals and detections."""
@@ -82,7 +131,8 @@ class DitModel(ModelHandle):
         rpn = [np.empty((s[0] * s[1], 16), np.float32) for s in sizes]
         boxes, scores = np.empty((MAX_ROIS, 4), np.float32), np.empty((MAX_ROIS,), np.float32)
         pb, ps = np.empty((MAX_ROIS, 4), np.float32), np.empty((MAX_ROIS,), np.float32)
-        head = np.empty((MAX_ROIS, 8), np.float32)
+        ld = self.head_ld()
+        head = np.empty((MAX_ROIS, ld), np.float32)
         n, pn = C.c_int(0), C.c_int(0)
         fp = (C.c_void_p * 5)(*[f.ctypes.data for f in fpn])
         rp = (C.c_void_p * 5)(*[r.ctypes.data for r in rpn])
@@ -91,7 +141,8 @@ class DitModel(ModelHandle):
               "mhip_dit_debug_taps_host")
         return {"boxes": boxes[: n.value], "scores": scores[: n.value], "fpn": fpn, "proposals": pb[: pn.value],
                 "proposal_scores": ps[: pn.value], "resized_hw": (nh, nw), "sizes": sizes,
-                "rpn_heads": [r[:, :15].copy() for r in rpn], "head": head[: pn.value, :6].copy()}
+                "rpn_heads": [r[:, :15].copy() for r in rpn],
+                "head": head[: pn.value, : 5 * int(self.cfg.num_classes) + 1].copy()}
 
 
 # ---------------------------------------------------------------------------------------------------- stage entries
@@ -147,3 +198,22 @@ def pil_resize_rgb(ctx: Context, img: np.ndarray, out_hw, bicubic: bool = False)
     check(ctx.h, ctx.lib.mhip_pil_resize_rgb_host(ctx.h, _vp(img), img.shape[0], img.shape[1], _vp(out), out.shape[0],
                                                   out.shape[1], 3 if bicubic else 2), "mhip_pil_resize_rgb_host")
     return out
+
+
+def det_final_multi(ctx: Context, head: np.ndarray, rois: np.ndarray, num_classes: int, img_hw, page_hw, score_thresh=0.05,
+                    nms_thresh=0.5, max_det=100):
+    """The K-class final stage: head (n, 5K + 1) fp32 = K + 1 logits (background last) then 4K deltas ->
+    (boxes (m, 4), scores (m,), classes (m,) int32) in page coordinates."""
+    n, K = len(rois), int(num_classes)
+    ld = (5 * K + 1 + 7) // 8 * 8
+    hd = np.zeros((n, ld), np.float32)
+    hd[:, : 5 * K + 1] = head
+    rois = np.ascontiguousarray(rois, np.float32)
+    boxes, scores = np.empty((MAX_ROIS, 4), np.float32), np.empty((MAX_ROIS,), np.float32)
+    classes = np.empty((MAX_ROIS,), np.int32)
+    cnt = C.c_int(0)
+    check(ctx.h, ctx.lib.mhip_det_final_multi_host(ctx.h, _vp(hd), ld, _vp(rois), n, K, int(img_hw[0]), int(img_hw[1]),
+                                                   int(page_hw[0]), int(page_hw[1]), score_thresh, nms_thresh, max_det,
+                                                   _vp(boxes), _vp(scores), _vp(classes), C.byref(cnt)),
+          "mhip_det_final_multi_host")
+    return boxes[: cnt.value], scores[: cnt.value], classes[: cnt.value]

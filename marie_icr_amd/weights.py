@@ -435,6 +435,26 @@ def make_dit_state(seed: int = 0, model: str = "base") -> Dict[str, np.ndarray]:
     return st
 
 
+def make_dit_boundary_state(seed: int = 0, num_classes: int = 5) -> Dict[str, np.ndarray]:
+    """Seeded weights for the document boundary model (a DiT-base Mask R-CNN with ``num_classes`` box classes): the text
+    detector's seeded backbone, FPN, RPN and box head of :func:`make_dit_state`, and a K-class box predictor
+    (cls_score [K + 1, 1024], background last; bbox_pred [4K, 1024]) from a generator of its own."""
+    st = make_dit_state(seed, "base")
+    rng = np.random.Generator(np.random.PCG64(seed + 70001))
+
+    def uni(shape, bound):
+        return rng.uniform(-bound, bound, size=shape).astype(np.float32)
+
+    K = int(num_classes)
+    p = "roi_heads.box_predictor."
+    st[p + "cls_score.weight"] = uni((K + 1, 1024), 0.5 * np.sqrt(3.0 / 1024))
+    st[p + "cls_score.bias"] = uni((K + 1,), 0.2)
+    st[p + "cls_score.bias"][0] += 2.5          # class 0 (the document) clears 0.7 on some proposals
+    st[p + "bbox_pred.weight"] = uni((4 * K, 1024), 2.0 * np.sqrt(3.0 / 1024))
+    st[p + "bbox_pred.bias"] = uni((4 * K,), 0.2)
+    return st
+
+
 # ------------------------------------------------------------------------------------------------ TrOCR
 def make_trocr_state(seed: int = 0, enc=(768, 12, 12), dec=(1024, 12, 16, 4096), vocab: int = 50265, max_positions: int = 512,
                      pad: int = 1, img: int = 384, logit_gain: float = 6.0, eos: int = 2, eos_gain: float = 18.0
