@@ -169,7 +169,7 @@ int mhip_crnn_forward_fragments_host(mhip_crnn* m, const uint8_t* packed_host, s
                                      const mhip_crop_desc* descs_host, int n, int img_w, float* logits_host,
                                      int32_t* argmax_host, int32_t* tokens_host, int32_t* lengths_host,
                                      float* conf_host);
-/* Bytes of ctx workspace one forward of n lines of width w needs (activations, gate buffers). */
+/* Bytes of ctx workspace mhip_crnn_forward of n lines of width w carves: exactly its layout's sizing pass. */
 size_t mhip_crnn_workspace_bytes(mhip_crnn* m, int n, int w);
 /* Algorithmic FLOPs (2*MAC) of one forward of n lines of width w, per kernel id — what
  * bench.py divides by the measured kernel time for the roofline line.                    */
@@ -216,6 +216,7 @@ int mhip_craft_arena(mhip_craft* m, void** arena_dev, size_t* bytes);
  * (h, w) page -> ratio, resized (th, tw), /32 canvas (H32, W32); the score maps are H32/2 x W32/2.          */
 int mhip_craft_geometry(int h, int w, int canvas_size, double mag_ratio, double* ratio, int* th, int* tw,
                         int* H32, int* W32);
+/* Bytes of ctx workspace mhip_craft_forward of an h x w page carves: exactly its layout's sizing pass. */
 size_t mhip_craft_workspace_bytes(mhip_craft* m, int h, int w, int canvas_size, double mag_ratio);
 /* Algorithmic FLOPs (2*MAC over the checkpoint's real channel counts) of one forward of an h x w page, per kernel id. */
 double mhip_craft_kernel_flops(mhip_craft* m, int kernel_id, int h, int w, int canvas_size, double mag_ratio);
@@ -299,6 +300,7 @@ int mhip_dit_set_tensor(mhip_dit* m, const char* key, const float* data, const i
 int mhip_dit_finalize(mhip_dit* m);
 int mhip_dit_alloc_arena(mhip_dit* m);
 int mhip_dit_arena(mhip_dit* m, int which /* 0 backbone, 1 heads */, void** arena_dev, size_t* bytes);
+/* Bytes of ctx workspace mhip_dit_detect of B h x w pages carves: exactly its layout's sizing pass. */
 size_t mhip_dit_workspace_bytes(mhip_dit* m, int B, int h, int w);
 /* B device pages u8 BGR [h][w][3] of one size -> per page up to 1000 boxes xyxy fp32 in page coordinates, score-ordered.
  * boxes_host [B][1000][4], scores_host [B][1000] (may be NULL), counts_host [B].                                      */
@@ -425,6 +427,7 @@ int mhip_trocr_set_tensor(mhip_trocr* m, const char* key, const float* data, con
 int mhip_trocr_finalize(mhip_trocr* m);
 int mhip_trocr_alloc_arena(mhip_trocr* m);
 int mhip_trocr_arena(mhip_trocr* m, int which /* 0 encoder, 1 decoder */, void** arena_dev, size_t* bytes);
+/* Bytes of ctx workspace mhip_trocr_generate of n crops carves (encoder + beam search): exactly its layout's sizing pass. */
 size_t mhip_trocr_workspace_bytes(mhip_trocr* m, int n);
 /* `gate` (may be NULL) is signalled inside every generate call at the point of the stream where the image encoder ends and
  * the autoregressive decode begins (TextRecognitionGenerator._generate's step loop, generator.py:182-362).  The caller owns it. */

@@ -113,46 +113,23 @@ __global__ void beam_best_kernel(BeamState st, int* tokens_out, int* lengths_out
   scores_out[s] = st.fin_score[s * beam + best];
 }
 
-struct Layout {
-  size_t tok0, tok1, last_tok, parent, cum, ignore, finished, fin_count, fin_tokens, fin_len, fin_score, remaining, end;
-};
-
-Layout layout(int bsz, int beam, int max_len) {
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  const size_t M = (size_t)bsz * beam;
-  Layout l;
-  size_t o = 0;
-  l.tok0 = o; o = up(o + M * (max_len + 2) * 4);
-  l.tok1 = o; o = up(o + M * (max_len + 2) * 4);
-  l.last_tok = o; o = up(o + M * 4);
-  l.parent = o; o = up(o + M * 4);
-  l.cum = o; o = up(o + M * 4);
-  l.ignore = o; o = up(o + M);
-  l.finished = o; o = up(o + bsz);
-  l.fin_count = o; o = up(o + (size_t)bsz * 4);
-  l.fin_tokens = o; o = up(o + M * (max_len + 1) * 4);
-  l.fin_len = o; o = up(o + M * 4);
-  l.fin_score = o; o = up(o + M * 4);
-  l.remaining = o; o = up(o + 4);
-  l.end = o;
-  return l;
-}
-
 }  // namespace
 
-size_t mhip_beam_state_bytes(int bsz, int beam, int max_len) { return layout(bsz, beam, max_len).end; }
-
-int mhip_beam_state_carve(void* base, int bsz, int beam, int max_len, int pad, int eos, BeamState* st) {
-  if (!base || !st || bsz < 1 || beam < 1 || beam > 4 || max_len < 1) return MHIP_EINVAL;
-  const Layout l = layout(bsz, beam, max_len);
-  char* b = (char*)base;
+void mhip_beam_state_carve(Carver& ws, int bsz, int beam, int max_len, int pad, int eos, BeamState* st) {
+  const size_t M = (size_t)bsz * beam;
   st->bsz = bsz; st->beam = beam; st->max_len = max_len; st->pad = pad; st->eos = eos;
-  st->tokens[0] = (int*)(b + l.tok0); st->tokens[1] = (int*)(b + l.tok1);
-  st->last_tok = (int*)(b + l.last_tok); st->parent = (int*)(b + l.parent); st->cum = (float*)(b + l.cum);
-  st->ignore = (unsigned char*)(b + l.ignore); st->finished = (unsigned char*)(b + l.finished);
-  st->fin_count = (int*)(b + l.fin_count); st->fin_tokens = (int*)(b + l.fin_tokens); st->fin_len = (int*)(b + l.fin_len);
-  st->fin_score = (float*)(b + l.fin_score); st->remaining = (int*)(b + l.remaining);
-  return MHIP_OK;
+  st->tokens[0] = ws.take<int>(M * (max_len + 2) * 4);
+  st->tokens[1] = ws.take<int>(M * (max_len + 2) * 4);
+  st->last_tok = ws.take<int>(M * 4);
+  st->parent = ws.take<int>(M * 4);
+  st->cum = ws.take<float>(M * 4);
+  st->ignore = ws.take<unsigned char>(M);
+  st->finished = ws.take<unsigned char>(bsz);
+  st->fin_count = ws.take<int>((size_t)bsz * 4);
+  st->fin_tokens = ws.take<int>(M * (max_len + 1) * 4);
+  st->fin_len = ws.take<int>(M * 4);
+  st->fin_score = ws.take<float>(M * 4);
+  st->remaining = ws.take<int>(4);
 }
 
 int mhip_launch_beam_init(mhip_ctx* ctx, const BeamState& st, int* anc0, int anc_ld) {

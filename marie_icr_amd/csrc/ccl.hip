@@ -255,23 +255,17 @@ float mhip_ordered_bits_to_float(int bits) {
   return f;
 }
 
-static size_t al(size_t v) { return (v + 255) / 256 * 256; }
-
-size_t mhip_ccl_workspace_bytes(int H, int W) {
+void mhip_ccl_carve(Carver& ws, int H, int W, CclBuffers* o) {
   const size_t n = (size_t)H * W;
   const size_t nb = (n + SCAN_ITEMS - 1) / SCAN_ITEMS + 1;
-  return al(n) + al(n * 4) + al(n * 4) + al(nb * 4) + al((n / 2 + 2) * 6 * 4) + al(4);
-}
-
-void mhip_ccl_carve(char* base, int H, int W, CclBuffers* o) {
-  const size_t n = (size_t)H * W;
-  const size_t nb = (n + SCAN_ITEMS - 1) / SCAN_ITEMS + 1;
-  o->flags = (uint8_t*)base;  base += al(n);
-  o->parent = (int*)base;     base += al(n * 4);
-  o->labels = (int*)base;     base += al(n * 4);
-  o->blocksum = (int*)base;   base += al(nb * 4);
-  o->stats = (int*)base;      base += al((n / 2 + 2) * 6 * 4);
-  o->n_labels = (int*)base;
+  Carver c = ws.sub(256);   // 256-byte pieces, one block of the caller's layout
+  o->flags = c.take<uint8_t>(n);
+  o->parent = c.take<int>(n * 4);
+  o->labels = c.take<int>(n * 4);
+  o->blocksum = c.take<int>(nb * 4);
+  o->stats = c.take<int>((n / 2 + 2) * 6 * 4);
+  o->n_labels = c.take<int>(4);
+  ws.take(c.off);
 }
 
 int mhip_launch_ccl(mhip_ctx* ctx, const float* scores, int H, int W, float low_text, float link_thr,

@@ -78,6 +78,44 @@ inline void mhip_quiesce(const mhip_ctx* ctx) {
   (void)hipDeviceSynchronize();
 }
 int mhip_ensure_workspace(mhip_ctx* ctx, size_t bytes);
+
+// Bump allocator that lays out one call's buffers: every take starts at a multiple of `align`.  With a null base it only
+// counts: take() returns nullptr and `off` ends as the bytes the same takes need on a real base.
+struct Carver {
+  char* base;
+  size_t align;
+  size_t off = 0;
+  explicit Carver(void* b, size_t a = 256) : base((char*)b), align(a) {}
+  template <typename P = char>
+  P* take(size_t bytes) {
+    const size_t at = off;
+    off = (off + bytes + align - 1) / align * align;
+    return base ? (P*)(base + at) : nullptr;
+  }
+  // a nested layout with its own alignment, starting here; the caller then takes sub.off bytes
+  Carver sub(size_t a) const { return Carver(base ? base + off : nullptr, a); }
+};
+
+// bytes of the layout `layout(Carver&)` carves
+template <typename F>
+size_t mhip_layout_bytes(F&& layout, size_t align = 256) {
+  Carver c(nullptr, align);
+  layout(c);
+  return c.off;
+}
+// The one way a call gets its workspace: `layout` runs on a sizing Carver, the workspace grows to that size, and `layout` runs
+// again on ctx->ws to place the buffers.  Called once per exported entry, before its first launch: a nested ensure could move
+// the workspace under pointers the caller holds.
+template <typename F>
+int mhip_carve_workspace(mhip_ctx* ctx, F&& layout, size_t align = 256) {
+  const size_t need = mhip_layout_bytes(layout, align);
+  int rc = mhip_ensure_workspace(ctx, need);
+  if (rc) return rc;
+  Carver ws(ctx->ws, align);
+  layout(ws);
+  if (ws.off != need) return mhip_fail(ctx, MHIP_ESTATE, "workspace layout carved %zu bytes, sized %zu", ws.off, need);
+  return MHIP_OK;
+}
 extern "C" int mhip_gate_signal(mhip_gate* g, mhip_ctx* ctx);   // phase_gate.hip
 void mhip_prof_begin(mhip_ctx* ctx, int kid, hipEvent_t* e0);
 void mhip_prof_end(mhip_ctx* ctx, int kid, hipEvent_t e0);
@@ -202,8 +240,7 @@ struct CclBuffers {
   int* stats;       // [max_labels][6]
   int* n_labels;    // [1]
 };
-size_t mhip_ccl_workspace_bytes(int H, int W);
-void mhip_ccl_carve(char* base, int H, int W, CclBuffers* out);
+void mhip_ccl_carve(Carver& ws, int H, int W, CclBuffers* out);
 int mhip_launch_ccl(mhip_ctx* ctx, const float* scores, int H, int W, float low_text, float link_thr,
                     const CclBuffers& b);
 float mhip_ordered_bits_to_float(int bits);
@@ -328,7 +365,6 @@ struct DetFinalMultiDesc {
   int* out_classes = nullptr;    // [images][max_rois]
   int* out_count = nullptr;      // [images]
 };
-size_t mhip_det_final_multi_scratch_bytes(int images, int num_classes);
 int mhip_launch_det_final_multi(mhip_ctx* ctx, const DetFinalMultiDesc& d);
 int mhip_launch_blackout(mhip_ctx* ctx, uint8_t* page, int H, int W, const int* boxes_dev, int n, int* changed_dev);
 int mhip_launch_subsample2(mhip_ctx* ctx, int precision, const void* in, void* out, int B, int H, int W, int C);
@@ -402,8 +438,8 @@ struct BeamState {
   float* fin_score = nullptr;           // [bsz][beam] normalised scores, in finalisation order
   int* remaining = nullptr;             // [1] crops not finished yet
 };
-size_t mhip_beam_state_bytes(int bsz, int beam, int max_len);
-int mhip_beam_state_carve(void* base, int bsz, int beam, int max_len, int pad, int eos, BeamState* st);   // pointers into `base`
+// the state's arrays from `ws` (beam <= 4: the generator's limit, checked when the model is created)
+void mhip_beam_state_carve(Carver& ws, int bsz, int beam, int max_len, int pad, int eos, BeamState* st);
 int mhip_launch_beam_init(mhip_ctx* ctx, const BeamState& st, int* anc0, int anc_ld);
 int mhip_launch_beam_select(mhip_ctx* ctx, const BeamState& st, int cur, int step);
 // best hypothesis per crop -> tokens_out [bsz][max_len + 1] (padded), lengths_out [bsz], scores_out [bsz] (device arrays)

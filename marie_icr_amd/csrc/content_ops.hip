@@ -203,18 +203,21 @@ extern "C" int mhip_content_extents(mhip_ctx* ctx, const uint8_t* page_dev, int 
     for (int i = 0; i < n; ++i) { int32_t* e = ext_host + 5 * i; e[0] = e[1] = e[2] = e[3] = e[4] = 0; }
     return MHIP_OK;
   }
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  const size_t o_rect = 0, o_hist = up(o_rect + (size_t)n * sizeof(ContentRect)), o_thr = up(o_hist + (size_t)n * 1024),
-               o_ext = up(o_thr + (size_t)n * 4), o_g = up(o_ext + (size_t)n * 20), o_d = up(o_g + total), o_end = up(o_d + total);
-  int rc = mhip_ensure_workspace(ctx, o_end);
+  ContentRect* d_rects = nullptr;
+  unsigned* d_hist = nullptr;
+  int* d_thr = nullptr;
+  int* d_ext = nullptr;
+  uint8_t* G = nullptr;
+  uint8_t* D = nullptr;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
+    d_rects = ws.take<ContentRect>((size_t)n * sizeof(ContentRect));
+    d_hist = ws.take<unsigned>((size_t)n * 1024);
+    d_thr = ws.take<int>((size_t)n * 4);
+    d_ext = ws.take<int>((size_t)n * 20);
+    G = ws.take<uint8_t>(total);
+    D = ws.take<uint8_t>(total);
+  });
   if (rc) return rc;
-  char* ws = (char*)ctx->ws;
-  ContentRect* d_rects = (ContentRect*)(ws + o_rect);
-  unsigned* d_hist = (unsigned*)(ws + o_hist);
-  int* d_thr = (int*)(ws + o_thr);
-  int* d_ext = (int*)(ws + o_ext);
-  uint8_t* G = (uint8_t*)(ws + o_g);
-  uint8_t* D = (uint8_t*)(ws + o_d);
   MHIP_HIP(ctx, hipMemcpyAsync(d_rects, rects.data(), (size_t)n * sizeof(ContentRect), hipMemcpyHostToDevice, ctx->stream));
   MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));      // `rects` is pageable and dies with this call
   MHIP_HIP(ctx, hipMemsetAsync(d_hist, 0, (size_t)n * 1024, ctx->stream));

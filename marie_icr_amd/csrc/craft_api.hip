@@ -190,35 +190,45 @@ namespace {
 struct CPlan {
   int th, tw, H, W;   // resized image, /32 canvas
   double ratio;
-  size_t resized, tabs, act[32], total;
-  size_t ccl;
 };
 
-// activation slots (byte offsets); all NHWC with the padded channel counts
+// activation slots; all NHWC with the padded channel counts
 enum Slot { A1_1, P1, A2_1, A2_2, P2, A3_1, A3_2, A3_3P, A4_1, A4_2, A4_3P, A5_1, A5_2, P5, A6, FC7, U1A, U1B, UP1,
             U2A, U2B, UP2, U3A, U3B, UP3, U4A, U4B, C0, C1, C2, C3, NSLOT };
 
-int make_cplan(const mhip_craft* m, int h, int w, int canvas, double mag, CPlan* p) {
-  int rc = mhip_craft_geometry(h, w, canvas, mag, &p->ratio, &p->th, &p->tw, &p->H, &p->W);
-  if (rc) return rc;
+constexpr size_t CRAFT_ALIGN = 4096;   // every CRAFT layout: buffers on 4 KiB boundaries
+
+// the forward's buffers (and the CCL scratch of detect), in layout order
+struct CraftBufs {
+  uint8_t* resized;
+  char* tabs;
+  char* act[NSLOT];
+  CclBuffers ccl;
+};
+
+int make_cplan(int h, int w, int canvas, double mag, CPlan* p) {
+  return mhip_craft_geometry(h, w, canvas, mag, &p->ratio, &p->th, &p->tw, &p->H, &p->W);
+}
+
+void craft_carve(const mhip_craft* m, Carver& ws, const CPlan& p, CraftBufs* b) {
   const size_t es = m->esz();
-  const size_t H = p->H, W = p->W;
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    size_t at = o;
-    o = (o + bytes + 4095) / 4096 * 4096;
-    return at;
-  };
-  p->resized = take((size_t)p->th * p->tw * 3);
-  p->tabs = take(((size_t)p->th + p->tw) * 8 + 64);
+  const size_t H = p.H, W = p.W;
+  b->resized = ws.take<uint8_t>((size_t)p.th * p.tw * 3);
+  b->tabs = ws.take(((size_t)p.th + p.tw) * 8 + 64);
   const size_t px1 = H * W, px2 = px1 / 4, px4 = px1 / 16, px8 = px1 / 64, px16 = px1 / 256;
   const size_t ch[NSLOT] = {64, 64, 128, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512, 1024, 1024, 512, 256,
                             256, 256, 128, 128, 128, 64, 64, 64, 64, 64, 64, 64, 64};
   const size_t px[NSLOT] = {px1, px2, px2, px2, px4, px4, px4, px8, px8, px8, px16, px16, px16, px16, px16, px16, px16,
                             px16, px8, px8, px8, px4, px4, px4, px2, px2, px2, px2, px2, px2, px2};
-  for (int s = 0; s < NSLOT; ++s) p->act[s] = take(px[s] * ch[s] * es);
-  p->ccl = take(mhip_ccl_workspace_bytes((int)(H / 2), (int)(W / 2)));
-  p->total = o;
+  for (int s = 0; s < NSLOT; ++s) b->act[s] = ws.take(px[s] * ch[s] * es);
+  mhip_ccl_carve(ws, (int)(H / 2), (int)(W / 2), &b->ccl);
+}
+
+// the checked geometry of one call
+int craft_plan(mhip_craft* m, int h, int w, int canvas, double mag, CPlan* p) {
+  if (!m->ready || !m->arena.dev) return mhip_fail(m->ctx, MHIP_ESTATE, "craft: weights not finalized");
+  if (make_cplan(h, w, canvas, mag, p)) return mhip_fail(m->ctx, MHIP_EINVAL, "craft: bad page %dx%d", h, w);
+  if ((long long)p->H * p->W > 0x7fffff00LL / 4) return mhip_fail(m->ctx, MHIP_EINVAL, "craft: canvas too large");
   return MHIP_OK;
 }
 
@@ -226,13 +236,14 @@ int make_cplan(const mhip_craft* m, int h, int w, int canvas, double mag, CPlan*
 
 extern "C" size_t mhip_craft_workspace_bytes(mhip_craft* m, int h, int w, int canvas_size, double mag_ratio) {
   CPlan p;
-  if (!m || make_cplan(m, h, w, canvas_size, mag_ratio, &p)) return 0;
-  return p.total;
+  if (!m || make_cplan(h, w, canvas_size, mag_ratio, &p)) return 0;
+  CraftBufs b;
+  return mhip_layout_bytes([&](Carver& ws) { craft_carve(m, ws, p, &b); }, CRAFT_ALIGN);
 }
 
 extern "C" double mhip_craft_kernel_flops(mhip_craft* m, int kid, int h, int w, int canvas_size, double mag_ratio) {
   CPlan p;
-  if (!m || make_cplan(m, h, w, canvas_size, mag_ratio, &p)) return 0.0;
+  if (!m || make_cplan(h, w, canvas_size, mag_ratio, &p)) return 0.0;
   const double px1 = (double)p.H * p.W;
   // resolution divisor (pixels = px1 / div) of every layer of kL, in table order
   static const int div[NL] = {1, 1, 4, 4, 16, 16, 16, 64, 64, 64, 256, 256, 256, 256, 256, 256, 64, 64, 16, 16, 4, 4,
@@ -248,23 +259,14 @@ extern "C" double mhip_craft_kernel_flops(mhip_craft* m, int kid, int h, int w, 
   return 0.0;
 }
 
-// Network forward: page uint8 [h][w][3] (device) -> scores fp32 [H32/2][W32/2][2] (device).
-extern "C" int mhip_craft_forward(mhip_craft* m, const uint8_t* page_dev, int h, int w, int canvas_size,
-                                  double mag_ratio, float* scores_dev) {
-  if (!m) return MHIP_EINVAL;
+// Network forward on carved buffers: page uint8 [h][w][3] (device) -> scores fp32 [H32/2][W32/2][2] (device).
+static int craft_forward(mhip_craft* m, const CraftBufs& b, const CPlan& p, const uint8_t* page_dev, int h, int w,
+                         float* scores_dev) {
   mhip_ctx* ctx = m->ctx;
-  if (!m->ready || !m->arena.dev) return mhip_fail(ctx, MHIP_ESTATE, "craft: weights not finalized");
-  if (!page_dev || !scores_dev) return mhip_fail(ctx, MHIP_EINVAL, "craft: null buffer");
-  CPlan p;
-  if (make_cplan(m, h, w, canvas_size, mag_ratio, &p)) return mhip_fail(ctx, MHIP_EINVAL, "craft: bad page %dx%d", h, w);
-  if ((long long)p.H * p.W > 0x7fffff00LL / 4) return mhip_fail(ctx, MHIP_EINVAL, "craft: canvas too large");
-  MHIP_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = mhip_ensure_workspace(ctx, p.total);
-  if (rc) return rc;
-  char* ws = (char*)ctx->ws;
   const char* A = m->arena.dev;
   const int prec = m->precision;
   const int H = p.H, W = p.W;
+  int rc;
 
   // ---- resize (cv2 INTER_LINEAR, 8-bit fixed point); identity when the size is unchanged ----
   const uint8_t* img = page_dev;
@@ -273,8 +275,7 @@ extern "C" int mhip_craft_forward(mhip_craft* m, const uint8_t* page_dev, int h,
     std::vector<short> xa, yb;
     mhip_resize_linear_tables(w, p.tw, xo, xa);
     mhip_resize_linear_tables(h, p.th, yo, yb);
-    char* t = ws + p.tabs;
-    int* d_xo = (int*)t;
+    int* d_xo = (int*)b.tabs;
     int* d_yo = d_xo + p.tw;
     short* d_xa = (short*)(d_yo + p.th);
     short* d_yb = d_xa + 2 * p.tw;
@@ -283,16 +284,15 @@ extern "C" int mhip_craft_forward(mhip_craft* m, const uint8_t* page_dev, int h,
     MHIP_HIP(ctx, hipMemcpyAsync(d_xa, xa.data(), (size_t)p.tw * 4, hipMemcpyHostToDevice, ctx->stream));
     MHIP_HIP(ctx, hipMemcpyAsync(d_yb, yb.data(), (size_t)p.th * 4, hipMemcpyHostToDevice, ctx->stream));
     MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the host tables die with this scope
-    rc = mhip_launch_resize_linear_u8(ctx, page_dev, h, w, (uint8_t*)(ws + p.resized), p.th, p.tw, d_xo, d_xa, d_yo,
-                                      d_yb);
+    rc = mhip_launch_resize_linear_u8(ctx, page_dev, h, w, b.resized, p.th, p.tw, d_xo, d_xa, d_yo, d_yb);
     if (rc) return rc;
-    img = (const uint8_t*)(ws + p.resized);
+    img = b.resized;
   }
 
   auto W_ = [&](int i) { return (const void*)(A + m->w_off[i]); };
   auto S_ = [&](int i) { return kL[i].bn ? (const float*)(A + m->s_off[i]) : nullptr; };
   auto B_ = [&](int i) { return (const float*)(A + m->b_off[i]); };
-  auto act = [&](int s) { return (void*)(ws + p.act[s]); };
+  auto act = [&](int s) { return (void*)b.act[s]; };
 
   auto conv = [&](int li, const void* in, int hh, int ww, void* out, int pool, int relu, int dil = 1, int pad = -1,
                   const void* in2 = nullptr, int cin1 = 0, int out_f32 = 0) {
@@ -349,6 +349,20 @@ extern "C" int mhip_craft_forward(mhip_craft* m, const uint8_t* page_dev, int h,
   }
 #undef CK
   return MHIP_OK;
+}
+
+extern "C" int mhip_craft_forward(mhip_craft* m, const uint8_t* page_dev, int h, int w, int canvas_size,
+                                  double mag_ratio, float* scores_dev) {
+  if (!m) return MHIP_EINVAL;
+  mhip_ctx* ctx = m->ctx;
+  CPlan p;
+  int rc = craft_plan(m, h, w, canvas_size, mag_ratio, &p);
+  if (rc) return rc;
+  if (!page_dev || !scores_dev) return mhip_fail(ctx, MHIP_EINVAL, "craft: null buffer");
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  CraftBufs b;
+  if ((rc = mhip_carve_workspace(ctx, [&](Carver& ws) { craft_carve(m, ws, p, &b); }, CRAFT_ALIGN))) return rc;
+  return craft_forward(m, b, p, page_dev, h, w, scores_dev);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -437,25 +451,16 @@ float norm2(float ax, float ay) {
 
 }  // namespace
 
-// Full detector: forward + post-processing.  boxes_host receives up to max_boxes x 8 floats (4 corners x,y in
-// score-map coordinates, clockwise from the top-left-most corner) in OpenCV label order.
-extern "C" int mhip_craft_detect(mhip_craft* m, const uint8_t* page_dev, int h, int w, int canvas_size,
-                                 double mag_ratio, float text_threshold, float link_threshold, float low_text,
-                                 float* boxes_host, int max_boxes, int* n_boxes, float* scores_host,
-                                 double* ratio_out) {
-  if (!m || !n_boxes || (max_boxes > 0 && !boxes_host)) return MHIP_EINVAL;
+// Full detector on carved buffers: forward + post-processing.  boxes_host receives up to max_boxes x 8 floats (4 corners x,y
+// in score-map coordinates, clockwise from the top-left-most corner) in OpenCV label order.
+static int craft_detect(mhip_craft* m, const CraftBufs& b, const CPlan& p, float* scores_dev, const uint8_t* page_dev, int h,
+                        int w, float text_threshold, float link_threshold, float low_text, float* boxes_host, int max_boxes,
+                        int* n_boxes, float* scores_host, double* ratio_out) {
   mhip_ctx* ctx = m->ctx;
-  CPlan p;
-  if (make_cplan(m, h, w, canvas_size, mag_ratio, &p)) return mhip_fail(ctx, MHIP_EINVAL, "craft: bad page %dx%d", h, w);
   const int H2 = p.H / 2, W2 = p.W / 2, npx = H2 * W2;
-  int rc = mhip_ensure_workspace(ctx, p.total + (size_t)npx * 8 + 4096);
+  int rc = craft_forward(m, b, p, page_dev, h, w, scores_dev);
   if (rc) return rc;
-  float* scores_dev = (float*)((char*)ctx->ws + p.total);
-  rc = mhip_craft_forward(m, page_dev, h, w, canvas_size, mag_ratio, scores_dev);
-  if (rc) return rc;
-  char* ws = (char*)ctx->ws;
-  CclBuffers cb;
-  mhip_ccl_carve(ws + p.ccl, H2, W2, &cb);
+  const CclBuffers& cb = b.ccl;
   rc = mhip_launch_ccl(ctx, scores_dev, H2, W2, low_text, link_threshold, cb);
   if (rc) return rc;
 
@@ -584,20 +589,47 @@ extern "C" int mhip_craft_detect(mhip_craft* m, const uint8_t* page_dev, int h, 
   return MHIP_OK;
 }
 
+extern "C" int mhip_craft_detect(mhip_craft* m, const uint8_t* page_dev, int h, int w, int canvas_size,
+                                 double mag_ratio, float text_threshold, float link_threshold, float low_text,
+                                 float* boxes_host, int max_boxes, int* n_boxes, float* scores_host,
+                                 double* ratio_out) {
+  if (!m || !page_dev || !n_boxes || (max_boxes > 0 && !boxes_host)) return MHIP_EINVAL;
+  mhip_ctx* ctx = m->ctx;
+  CPlan p;
+  int rc = craft_plan(m, h, w, canvas_size, mag_ratio, &p);
+  if (rc) return rc;
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  CraftBufs b;
+  float* scores = nullptr;
+  rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
+    craft_carve(m, ws, p, &b);
+    scores = ws.take<float>((size_t)(p.H / 2) * (p.W / 2) * 8);
+  }, CRAFT_ALIGN);
+  if (rc) return rc;
+  return craft_detect(m, b, p, scores, page_dev, h, w, text_threshold, link_threshold, low_text, boxes_host, max_boxes, n_boxes,
+                      scores_host, ratio_out);
+}
+
 extern "C" int mhip_craft_detect_host(mhip_craft* m, const uint8_t* page_host, int h, int w, int canvas_size,
                                       double mag_ratio, float text_threshold, float link_threshold, float low_text,
                                       float* boxes_host, int max_boxes, int* n_boxes, float* scores_host,
                                       double* ratio_out) {
-  if (!m || !page_host) return MHIP_EINVAL;
+  if (!m || !page_host || !n_boxes || (max_boxes > 0 && !boxes_host)) return MHIP_EINVAL;
   mhip_ctx* ctx = m->ctx;
   CPlan p;
-  if (make_cplan(m, h, w, canvas_size, mag_ratio, &p)) return mhip_fail(ctx, MHIP_EINVAL, "craft: bad page %dx%d", h, w);
-  const size_t npx = (size_t)(p.H / 2) * (p.W / 2);
-  const size_t page_off = p.total + npx * 8 + 8192;
-  int rc = mhip_ensure_workspace(ctx, page_off + (size_t)h * w * 3 + 4096);
+  int rc = craft_plan(m, h, w, canvas_size, mag_ratio, &p);
   if (rc) return rc;
-  uint8_t* page_dev = (uint8_t*)ctx->ws + page_off;
-  MHIP_HIP(ctx, hipMemcpyAsync(page_dev, page_host, (size_t)h * w * 3, hipMemcpyHostToDevice, ctx->stream));
-  return mhip_craft_detect(m, page_dev, h, w, canvas_size, mag_ratio, text_threshold, link_threshold, low_text,
-                           boxes_host, max_boxes, n_boxes, scores_host, ratio_out);
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  CraftBufs b;
+  float* scores = nullptr;
+  uint8_t* page = nullptr;
+  rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
+    craft_carve(m, ws, p, &b);
+    scores = ws.take<float>((size_t)(p.H / 2) * (p.W / 2) * 8);
+    page = ws.take<uint8_t>((size_t)h * w * 3);
+  }, CRAFT_ALIGN);
+  if (rc) return rc;
+  MHIP_HIP(ctx, hipMemcpyAsync(page, page_host, (size_t)h * w * 3, hipMemcpyHostToDevice, ctx->stream));
+  return craft_detect(m, b, p, scores, page, h, w, text_threshold, link_threshold, low_text, boxes_host, max_boxes, n_boxes,
+                      scores_host, ratio_out);
 }

@@ -801,11 +801,6 @@ int mhip_launch_det_final(mhip_ctx* ctx, const DetFinalDesc& d) {
   return 0;
 }
 
-size_t mhip_det_final_multi_scratch_bytes(int images, int num_classes) {
-  const size_t per = (size_t)images * num_classes;
-  return per * TOPK * 8 + 256 + per * TOPK * 16 + 256 + per * 4 + 256;
-}
-
 int mhip_launch_det_final_multi(mhip_ctx* ctx, const DetFinalMultiDesc& d) {
   if (d.max_rois > 1000) return mhip_fail(ctx, MHIP_EINVAL, "det_final_multi: at most 1000 proposals per image");
   if (d.num_classes < 2 || d.num_classes > DET_MAX_CLASSES) return mhip_fail(ctx, MHIP_EINVAL, "det_final_multi: %d classes", d.num_classes);

@@ -260,30 +260,6 @@ extern "C" int mhip_dit_finalize(mhip_dit* m) {
   return MHIP_OK;
 }
 
-static size_t dit_ws_bytes(const mhip_dit* m, int B, int h, int w, const DitGeom& g) {
-  const size_t es = m->esz();
-  VitGeom vg;
-  vit_geometry(m->vit, g.H32, g.W32, &vg);
-  size_t b = (size_t)B * g.nh * g.nw * 3 + 256 + mhip_pil_resize_scratch_bytes(h, w, g.nh, g.nw, MHIP_PIL_BILINEAR) + 256;
-  b += vit_workspace_bytes(m->vit, B, vg) + vit_fpn_workspace_bytes(m->vit, B, vg);
-  size_t px = 0;
-  for (int l = 0; l < 5; ++l) px += (size_t)g.lh[l] * g.lw[l];
-  b += 4 * ((size_t)B * px * FPN_C * es + 5 * 256);            // lateral, merged, p-levels, rpn conv
-  b += (size_t)B * px * 16 * 4 + 5 * 256;                      // rpn head
-  b += (size_t)B * (5 * MAX_ROIS * 5 * 4 + MAX_ROIS * 5 * 4 * 2 + 64) + 4096;
-  const int K = m->cfg.num_classes;
-  b += (size_t)B * MAX_ROIS * (POOL * POOL * FPN_C + 2 * FC_DIM) * es + (size_t)B * MAX_ROIS * head_ld(K) * 4 + 4096;
-  if (K > 1) b += mhip_det_final_multi_scratch_bytes(B, K) + (size_t)B * MAX_ROIS * 4 + 4096;
-  return b + (1 << 16);
-}
-
-extern "C" size_t mhip_dit_workspace_bytes(mhip_dit* m, int B, int h, int w) {
-  if (!m || B < 1 || h < 1 || w < 1) return 0;
-  DitGeom g;
-  dit_geometry(m->cfg, h, w, &g);
-  return dit_ws_bytes(m, B, h, w, g);
-}
-
 struct DitDebug {
   float* fpn[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // host fp32 NHWC p2..p6 (B = 1)
   float* prop_boxes = nullptr;   // host [1000][4]
@@ -292,6 +268,71 @@ struct DitDebug {
   float* rpn_head[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // host fp32 [H*W][16] per level (3 logits, 12 deltas, pad)
   float* box_head = nullptr;     // host fp32 [1000][head_ld] (K + 1 class scores, 4K deltas, pad), rows past prop_count undefined
 };
+
+// the buffers of one detector call, in layout order
+struct DitBufs {
+  uint8_t* imgs;
+  void* rscratch;
+  VitRun run;
+  VitFpnOut fo;
+  char *lat[4], *merged[4], *pl[5], *rt;
+  float* rpn_head[5];
+  RpnDesc rd;
+  char *pooled, *f1, *f2;
+  float* hd;
+  DetFinalDesc fd;
+  DetFinalMultiDesc md;
+  float* stage = nullptr;   // debug entries: one FPN map in fp32
+};
+
+static void dit_carve(const mhip_dit* m, Carver& ws, int B, int h, int w, const DitGeom& g, bool dbg, DitBufs* b) {
+  const size_t es = m->esz();
+  const int K = m->cfg.num_classes;
+  VitGeom vg;
+  vit_geometry(m->vit, g.H32, g.W32, &vg);
+  b->imgs = ws.take<uint8_t>((size_t)B * g.nh * g.nw * 3);
+  b->rscratch = ws.take(mhip_pil_resize_scratch_bytes(h, w, g.nh, g.nw, MHIP_PIL_BILINEAR));
+  vit_carve(m->vit, ws, B, vg, &b->run);
+  vit_fpn_carve(m->vit, ws, B, vg, &b->fo);
+  for (int l = 0; l < 4; ++l) {
+    const size_t n = (size_t)B * g.lh[l] * g.lw[l] * FPN_C * es;
+    b->lat[l] = ws.take(n);
+    b->merged[l] = ws.take(n);
+    b->pl[l] = ws.take(n);
+  }
+  b->pl[4] = ws.take((size_t)B * g.lh[4] * g.lw[4] * FPN_C * es);
+  b->rt = ws.take((size_t)B * g.lh[0] * g.lw[0] * FPN_C * es);
+  for (int l = 0; l < 5; ++l) b->rpn_head[l] = ws.take<float>((size_t)B * g.lh[l] * g.lw[l] * 16 * 4);
+  RpnDesc& rd = b->rd;
+  rd.lvl_boxes = ws.take<float>((size_t)B * 5 * MAX_ROIS * 4 * 4);
+  rd.lvl_scores = ws.take<float>((size_t)B * 5 * MAX_ROIS * 4);
+  rd.lvl_counts = ws.take<int>((size_t)B * 5 * 4);
+  rd.out_boxes = ws.take<float>((size_t)B * MAX_ROIS * 4 * 4);
+  rd.out_scores = ws.take<float>((size_t)B * MAX_ROIS * 4);
+  rd.out_counts = ws.take<int>((size_t)B * 4);
+  b->pooled = ws.take((size_t)B * MAX_ROIS * POOL * POOL * FPN_C * es);
+  b->f1 = ws.take((size_t)B * MAX_ROIS * FC_DIM * es);
+  b->f2 = ws.take((size_t)B * MAX_ROIS * FC_DIM * es);
+  b->hd = ws.take<float>((size_t)B * MAX_ROIS * head_ld(K) * 4);
+  b->fd.out_boxes = ws.take<float>((size_t)B * MAX_ROIS * 4 * 4);
+  b->fd.out_scores = ws.take<float>((size_t)B * MAX_ROIS * 4);
+  b->fd.out_count = ws.take<int>((size_t)B * 4);
+  if (K > 1) {
+    b->md.cls_keys = ws.take<unsigned long long>((size_t)B * K * MAX_ROIS * 8);
+    b->md.cls_boxes = ws.take<float>((size_t)B * K * MAX_ROIS * 16);
+    b->md.cls_counts = ws.take<int>((size_t)B * K * 4);
+    b->md.out_classes = ws.take<int>((size_t)B * MAX_ROIS * 4);
+  }
+  if (dbg) b->stage = ws.take<float>((size_t)g.lh[0] * g.lw[0] * FPN_C * 4);
+}
+
+extern "C" size_t mhip_dit_workspace_bytes(mhip_dit* m, int B, int h, int w) {
+  if (!m || B < 1 || h < 1 || w < 1) return 0;
+  DitGeom g;
+  dit_geometry(m->cfg, h, w, &g);
+  DitBufs b;
+  return mhip_layout_bytes([&](Carver& ws) { dit_carve(m, ws, B, h, w, g, false, &b); });
+}
 
 static int dit_run(mhip_dit* m, const uint8_t* const* pages_dev, int B, int h, int w, float* boxes_host, float* scores_host,
                    int32_t* classes_host, int* counts_host, const DitDebug* dbg) {
@@ -303,30 +344,22 @@ static int dit_run(mhip_dit* m, const uint8_t* const* pages_dev, int B, int h, i
   const size_t es = m->esz();
   DitGeom g;
   dit_geometry(m->cfg, h, w, &g);
-  int rc = mhip_ensure_workspace(ctx, dit_ws_bytes(m, B, h, w, g) + (dbg ? (size_t)g.lh[0] * g.lw[0] * FPN_C * 4 + 256 : 0));
+  DitBufs bf;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) { dit_carve(m, ws, B, h, w, g, dbg != nullptr, &bf); });
   if (rc) return rc;
-  Carver ws(ctx->ws);
   const Arena& a = m->arena;
   // 1. resize (PIL bilinear, channel order irrelevant) into B x [nh][nw][3]
-  uint8_t* imgs = ws.take<uint8_t>((size_t)B * g.nh * g.nw * 3);
-  void* rscratch = ws.take(mhip_pil_resize_scratch_bytes(h, w, g.nh, g.nw, MHIP_PIL_BILINEAR));
   for (int b = 0; b < B; ++b)
-    if ((rc = mhip_launch_pil_resize_rgb(ctx, pages_dev[b], h, w, (size_t)w * 3, imgs + (size_t)b * g.nh * g.nw * 3, g.nh, g.nw, MHIP_PIL_BILINEAR, rscratch))) return rc;
+    if ((rc = mhip_launch_pil_resize_rgb(ctx, pages_dev[b], h, w, (size_t)w * 3, bf.imgs + (size_t)b * g.nh * g.nw * 3, g.nh, g.nw, MHIP_PIL_BILINEAR, bf.rscratch))) return rc;
   // 2. backbone (pages arrive BGR, INPUT.FORMAT is RGB)
-  VitRun run;
-  if ((rc = vit_encode(m->vit, ws, imgs, B, g.nh, g.nw, g.H32, g.W32, 1, &run))) return rc;
-  VitFpnOut fo;
-  if ((rc = vit_fpn(m->vit, ws, B, run, &fo))) return rc;
+  if ((rc = vit_encode(m->vit, bf.imgs, B, g.nh, g.nw, g.H32, g.W32, 1, &bf.run))) return rc;
+  if ((rc = vit_fpn(m->vit, B, bf.run, &bf.fo))) return rc;
+  const VitFpnOut& fo = bf.fo;
   const int D = m->vit->cfg.dim;
   // 3. FPN: laterals (per-pixel, any row order), top-down merge restores raster order, 3x3 output convs
-  char* lat[4];
-  char* merged[4];
-  char* pl[5];
-  for (int l = 0; l < 4; ++l) {
-    const size_t n = (size_t)B * g.lh[l] * g.lw[l] * FPN_C * es;
-    lat[l] = ws.take(n); merged[l] = ws.take(n); pl[l] = ws.take(n);
-  }
-  pl[4] = ws.take((size_t)B * g.lh[4] * g.lw[4] * FPN_C * es);
+  char** lat = bf.lat;
+  char** merged = bf.merged;
+  char** pl = bf.pl;
   for (int l = 3; l >= 0; --l) {
     const std::string s = std::to_string(l + 2);
     const long long rows = (long long)B * g.lh[l] * g.lw[l];
@@ -342,60 +375,48 @@ static int dit_run(mhip_dit* m, const uint8_t* const* pages_dev, int B, int h, i
   }
   if ((rc = mhip_launch_subsample2(ctx, prec, pl[3], pl[4], B, g.lh[3], g.lw[3], FPN_C))) return rc;
   // 4. RPN head on p2..p6
-  RpnDesc rd;
-  char* rt = ws.take((size_t)B * g.lh[0] * g.lw[0] * FPN_C * es);
+  RpnDesc& rd = bf.rd;
+  char* rt = bf.rt;
   for (int l = 0; l < 5; ++l) {
-    float* ho = ws.take<float>((size_t)B * g.lh[l] * g.lw[l] * 16 * 4);
+    float* ho = bf.rpn_head[l];
     if ((rc = conv(ctx, prec, pl[l], a.d("rpn_conv_w"), a.d<float>("rpn_conv_b"), rt, B, g.lh[l], g.lw[l], FPN_C, FPN_C, 3, ACT_RELU))) return rc;
     if ((rc = conv(ctx, prec, rt, a.d("rpn_head_w"), a.d<float>("rpn_head_b"), ho, B, g.lh[l], g.lw[l], FPN_C, 15, 1, ACT_NONE, 1, 16))) return rc;
     rd.head[l] = ho; rd.H[l] = g.lh[l]; rd.W[l] = g.lw[l]; rd.stride[l] = 4 << l;
   }
   mhip_rpn_cell_anchors(m->cfg.anchor_sizes, m->cfg.aspect_ratios, rd.cell);
   rd.images = B; rd.img_h = g.nh; rd.img_w = g.nw; rd.nms_thr = m->cfg.rpn_nms_thresh; rd.post_topk = MAX_ROIS;
-  rd.lvl_boxes = ws.take<float>((size_t)B * 5 * MAX_ROIS * 4 * 4);
-  rd.lvl_scores = ws.take<float>((size_t)B * 5 * MAX_ROIS * 4);
-  rd.lvl_counts = ws.take<int>((size_t)B * 5 * 4);
-  rd.out_boxes = ws.take<float>((size_t)B * MAX_ROIS * 4 * 4);
-  rd.out_scores = ws.take<float>((size_t)B * MAX_ROIS * 4);
-  rd.out_counts = ws.take<int>((size_t)B * 4);
   if ((rc = mhip_launch_rpn_proposals(ctx, rd))) return rc;
   // 5. box head
   RoiDesc ro;
   for (int l = 0; l < 4; ++l) { ro.feat[l] = pl[l]; ro.H[l] = g.lh[l]; ro.W[l] = g.lw[l]; ro.scale[l] = 1.f / (float)(4 << l); }
   ro.rois = rd.out_boxes; ro.counts = rd.out_counts; ro.images = B; ro.max_rois = MAX_ROIS; ro.C = FPN_C;
   const int K1 = POOL * POOL * FPN_C;
-  char* pooled = ws.take((size_t)B * MAX_ROIS * K1 * es);
+  char* pooled = bf.pooled;
   MHIP_HIP(ctx, hipMemsetAsync(pooled, 0, (size_t)B * MAX_ROIS * K1 * es, ctx->stream));   // rows past the proposal count
   ro.out = pooled;
   if ((rc = mhip_launch_roi_align(ctx, prec, ro))) return rc;
-  char* f1 = ws.take((size_t)B * MAX_ROIS * FC_DIM * es);
-  char* f2 = ws.take((size_t)B * MAX_ROIS * FC_DIM * es);
+  char* f1 = bf.f1;
+  char* f2 = bf.f2;
   const int K = m->cfg.num_classes, LD = head_ld(K);
-  float* hd = ws.take<float>((size_t)B * MAX_ROIS * LD * 4);
+  float* hd = bf.hd;
   const long long R = (long long)B * MAX_ROIS;
   if ((rc = mhip_gemm(ctx, prec, pooled, a.d("fc1_w"), R, FC_DIM, K1, nullptr, a.d<float>("fc1_b"), f1, ACT_RELU, 0))) return rc;
   if ((rc = mhip_gemm(ctx, prec, f1, a.d("fc2_w"), R, FC_DIM, FC_DIM, nullptr, a.d<float>("fc2_b"), f2, ACT_RELU, 0))) return rc;
   if ((rc = mhip_gemm(ctx, prec, f2, a.d("pred_w"), R, 5 * K + 1, FC_DIM, nullptr, a.d<float>("pred_b"), hd, ACT_NONE, 1, nullptr, LD, 1))) return rc;
-  DetFinalDesc fd;
+  DetFinalDesc& fd = bf.fd;
   fd.head = hd; fd.rois = rd.out_boxes; fd.counts = rd.out_counts; fd.images = B; fd.max_rois = MAX_ROIS;
   fd.img_h = g.nh; fd.img_w = g.nw; fd.out_h = h; fd.out_w = w;
   fd.score_thr = m->cfg.score_thresh; fd.nms_thr = m->cfg.nms_thresh; fd.max_det = m->cfg.detections_per_image;
-  fd.out_boxes = ws.take<float>((size_t)B * MAX_ROIS * 4 * 4);
-  fd.out_scores = ws.take<float>((size_t)B * MAX_ROIS * 4);
-  fd.out_count = ws.take<int>((size_t)B * 4);
   int* out_classes = nullptr;
   if (K == 1) {
     if ((rc = mhip_launch_det_final(ctx, fd))) return rc;
   } else {
-    DetFinalMultiDesc md;
+    DetFinalMultiDesc& md = bf.md;
     md.head = hd; md.ld = LD; md.num_classes = K; md.rois = rd.out_boxes; md.counts = rd.out_counts; md.images = B;
     md.max_rois = MAX_ROIS; md.img_h = g.nh; md.img_w = g.nw; md.out_h = h; md.out_w = w;
     md.score_thr = m->cfg.score_thresh; md.nms_thr = m->cfg.nms_thresh; md.max_det = m->cfg.detections_per_image;
-    md.cls_keys = ws.take<unsigned long long>((size_t)B * K * MAX_ROIS * 8);
-    md.cls_boxes = ws.take<float>((size_t)B * K * MAX_ROIS * 16);
-    md.cls_counts = ws.take<int>((size_t)B * K * 4);
     md.out_boxes = fd.out_boxes; md.out_scores = fd.out_scores; md.out_count = fd.out_count;
-    md.out_classes = out_classes = ws.take<int>((size_t)B * MAX_ROIS * 4);
+    out_classes = md.out_classes;
     if ((rc = mhip_launch_det_final_multi(ctx, md))) return rc;
   }
   MHIP_HIP(ctx, hipMemcpyAsync(counts_host, fd.out_count, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -406,7 +427,7 @@ static int dit_run(mhip_dit* m, const uint8_t* const* pages_dev, int B, int h, i
     else memset(classes_host, 0, (size_t)B * MAX_ROIS * 4);
   }
   if (dbg) {
-    float* stage = ws.take<float>((size_t)g.lh[0] * g.lw[0] * FPN_C * 4);
+    float* stage = bf.stage;
     for (int l = 0; l < 5; ++l)
       if (dbg->fpn[l]) {
         const int rows = g.lh[l] * g.lw[l];
@@ -529,10 +550,10 @@ extern "C" int mhip_blackout_bboxes(mhip_ctx* ctx, uint8_t* page_dev, int h, int
   *changed = 0;
   if (n <= 0) return MHIP_OK;
   MHIP_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = mhip_ensure_workspace(ctx, (size_t)n * 16 + 256);
+  int* flag = nullptr;
+  int* boxes = nullptr;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) { flag = ws.take<int>(4); boxes = ws.take<int>((size_t)n * 16); });
   if (rc) return rc;
-  int* flag = (int*)ctx->ws;
-  int* boxes = flag + 64;
   MHIP_HIP(ctx, hipMemsetAsync(flag, 0, 4, ctx->stream));
   MHIP_HIP(ctx, hipMemcpyAsync(boxes, boxes_xyxy_host, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
   if ((rc = mhip_launch_blackout(ctx, page_dev, h, w, boxes, n, flag))) return rc;
@@ -550,26 +571,24 @@ extern "C" int mhip_rpn_proposals_host(mhip_ctx* ctx, const float* const* heads_
   if (!ctx || !heads_host || !H || !W || !strides || !anchor_sizes || !aspect_ratios || !boxes_out || !scores_out || !count_out)
     return MHIP_EINVAL;
   MHIP_HIP(ctx, hipSetDevice(ctx->device));
-  size_t need = 1 << 16;
-  for (int l = 0; l < 5; ++l) need += (size_t)H[l] * W[l] * 64 + 256;
-  need += (size_t)5 * MAX_ROIS * 20 + MAX_ROIS * 20 + 4096;
-  int rc = mhip_ensure_workspace(ctx, need);
-  if (rc) return rc;
-  Carver ws(ctx->ws);
   RpnDesc rd;
+  float* heads[5];
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
+    for (int l = 0; l < 5; ++l) heads[l] = ws.take<float>((size_t)H[l] * W[l] * 64);
+    rd.lvl_boxes = ws.take<float>((size_t)5 * MAX_ROIS * 16);
+    rd.lvl_scores = ws.take<float>((size_t)5 * MAX_ROIS * 4);
+    rd.lvl_counts = ws.take<int>(5 * 4);
+    rd.out_boxes = ws.take<float>((size_t)MAX_ROIS * 16);
+    rd.out_scores = ws.take<float>((size_t)MAX_ROIS * 4);
+    rd.out_counts = ws.take<int>(4);
+  });
+  if (rc) return rc;
   for (int l = 0; l < 5; ++l) {
-    float* d = ws.take<float>((size_t)H[l] * W[l] * 64);
-    MHIP_HIP(ctx, hipMemcpyAsync(d, heads_host[l], (size_t)H[l] * W[l] * 64, hipMemcpyHostToDevice, ctx->stream));
-    rd.head[l] = d; rd.H[l] = H[l]; rd.W[l] = W[l]; rd.stride[l] = strides[l];
+    MHIP_HIP(ctx, hipMemcpyAsync(heads[l], heads_host[l], (size_t)H[l] * W[l] * 64, hipMemcpyHostToDevice, ctx->stream));
+    rd.head[l] = heads[l]; rd.H[l] = H[l]; rd.W[l] = W[l]; rd.stride[l] = strides[l];
   }
   mhip_rpn_cell_anchors(anchor_sizes, aspect_ratios, rd.cell);
   rd.images = 1; rd.img_h = img_h; rd.img_w = img_w; rd.nms_thr = nms_thresh; rd.post_topk = MAX_ROIS;
-  rd.lvl_boxes = ws.take<float>((size_t)5 * MAX_ROIS * 16);
-  rd.lvl_scores = ws.take<float>((size_t)5 * MAX_ROIS * 4);
-  rd.lvl_counts = ws.take<int>(5 * 4);
-  rd.out_boxes = ws.take<float>((size_t)MAX_ROIS * 16);
-  rd.out_scores = ws.take<float>((size_t)MAX_ROIS * 4);
-  rd.out_counts = ws.take<int>(4);
   if ((rc = mhip_launch_rpn_proposals(ctx, rd))) return rc;
   MHIP_HIP(ctx, hipMemcpyAsync(boxes_out, rd.out_boxes, MAX_ROIS * 16, hipMemcpyDeviceToHost, ctx->stream));
   MHIP_HIP(ctx, hipMemcpyAsync(scores_out, rd.out_scores, MAX_ROIS * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -583,20 +602,22 @@ extern "C" int mhip_roi_align_host(mhip_ctx* ctx, const float* const* feats_host
                                    const float* rois_host, int n, float* pooled_out) {
   if (!ctx || !feats_host || !H || !W || !rois_host || !pooled_out || n < 0 || n > MAX_ROIS || C < 1) return MHIP_EINVAL;
   MHIP_HIP(ctx, hipSetDevice(ctx->device));
-  size_t need = (size_t)n * 49 * C * 4 + MAX_ROIS * 16 + 8192;
-  for (int l = 0; l < 4; ++l) need += (size_t)H[l] * W[l] * C * 4 + 256;
-  int rc = mhip_ensure_workspace(ctx, need);
+  float* feats[4];
+  float* rois = nullptr;
+  int* cnt = nullptr;
+  float* out = nullptr;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
+    for (int l = 0; l < 4; ++l) feats[l] = ws.take<float>((size_t)H[l] * W[l] * C * 4);
+    rois = ws.take<float>(MAX_ROIS * 16);
+    cnt = ws.take<int>(4);
+    out = ws.take<float>((size_t)std::max(n, 1) * 49 * C * 4);
+  });
   if (rc) return rc;
-  Carver ws(ctx->ws);
   RoiDesc ro;
   for (int l = 0; l < 4; ++l) {
-    float* d = ws.take<float>((size_t)H[l] * W[l] * C * 4);
-    MHIP_HIP(ctx, hipMemcpyAsync(d, feats_host[l], (size_t)H[l] * W[l] * C * 4, hipMemcpyHostToDevice, ctx->stream));
-    ro.feat[l] = d; ro.H[l] = H[l]; ro.W[l] = W[l]; ro.scale[l] = 1.f / (float)(4 << l);
+    MHIP_HIP(ctx, hipMemcpyAsync(feats[l], feats_host[l], (size_t)H[l] * W[l] * C * 4, hipMemcpyHostToDevice, ctx->stream));
+    ro.feat[l] = feats[l]; ro.H[l] = H[l]; ro.W[l] = W[l]; ro.scale[l] = 1.f / (float)(4 << l);
   }
-  float* rois = ws.take<float>(MAX_ROIS * 16);
-  int* cnt = ws.take<int>(4);
-  float* out = ws.take<float>((size_t)std::max(n, 1) * 49 * C * 4);
   MHIP_HIP(ctx, hipMemcpyAsync(rois, rois_host, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
   MHIP_HIP(ctx, hipMemcpyAsync(cnt, &n, 4, hipMemcpyHostToDevice, ctx->stream));
   ro.rois = rois; ro.counts = cnt; ro.images = 1; ro.max_rois = std::max(n, 1); ro.C = C; ro.out = out;
@@ -612,16 +633,19 @@ extern "C" int mhip_det_final_host(mhip_ctx* ctx, const float* head_host, const 
                                    float* boxes_out, float* scores_out, int* count_out) {
   if (!ctx || !head_host || !rois_host || !boxes_out || !scores_out || !count_out || n < 0 || n > MAX_ROIS) return MHIP_EINVAL;
   MHIP_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = mhip_ensure_workspace(ctx, (size_t)MAX_ROIS * 80 + 8192);
-  if (rc) return rc;
-  Carver ws(ctx->ws);
-  float* head = ws.take<float>(MAX_ROIS * 32);
-  float* rois = ws.take<float>(MAX_ROIS * 16);
-  int* cnt = ws.take<int>(4);
+  float* head = nullptr;
+  float* rois = nullptr;
+  int* cnt = nullptr;
   DetFinalDesc fd;
-  fd.out_boxes = ws.take<float>(MAX_ROIS * 16);
-  fd.out_scores = ws.take<float>(MAX_ROIS * 4);
-  fd.out_count = ws.take<int>(4);
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
+    head = ws.take<float>(MAX_ROIS * 32);
+    rois = ws.take<float>(MAX_ROIS * 16);
+    cnt = ws.take<int>(4);
+    fd.out_boxes = ws.take<float>(MAX_ROIS * 16);
+    fd.out_scores = ws.take<float>(MAX_ROIS * 4);
+    fd.out_count = ws.take<int>(4);
+  });
+  if (rc) return rc;
   MHIP_HIP(ctx, hipMemcpyAsync(head, head_host, (size_t)n * 32, hipMemcpyHostToDevice, ctx->stream));
   MHIP_HIP(ctx, hipMemcpyAsync(rois, rois_host, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
   MHIP_HIP(ctx, hipMemcpyAsync(cnt, &n, 4, hipMemcpyHostToDevice, ctx->stream));
@@ -646,20 +670,23 @@ extern "C" int mhip_det_final_multi_host(mhip_ctx* ctx, const float* head_host, 
       num_classes < 2 || num_classes > DET_MAX_CLASSES || ld < 5 * num_classes + 1)
     return MHIP_EINVAL;
   MHIP_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = mhip_ensure_workspace(ctx, (size_t)MAX_ROIS * (ld * 4 + 48) + mhip_det_final_multi_scratch_bytes(1, num_classes) + 8192);
-  if (rc) return rc;
-  Carver ws(ctx->ws);
-  float* head = ws.take<float>((size_t)MAX_ROIS * ld * 4);
-  float* rois = ws.take<float>(MAX_ROIS * 16);
-  int* cnt = ws.take<int>(4);
+  float* head = nullptr;
+  float* rois = nullptr;
+  int* cnt = nullptr;
   DetFinalMultiDesc md;
-  md.cls_keys = ws.take<unsigned long long>((size_t)num_classes * MAX_ROIS * 8);
-  md.cls_boxes = ws.take<float>((size_t)num_classes * MAX_ROIS * 16);
-  md.cls_counts = ws.take<int>((size_t)num_classes * 4);
-  md.out_boxes = ws.take<float>(MAX_ROIS * 16);
-  md.out_scores = ws.take<float>(MAX_ROIS * 4);
-  md.out_classes = ws.take<int>(MAX_ROIS * 4);
-  md.out_count = ws.take<int>(4);
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
+    head = ws.take<float>((size_t)MAX_ROIS * ld * 4);
+    rois = ws.take<float>(MAX_ROIS * 16);
+    cnt = ws.take<int>(4);
+    md.cls_keys = ws.take<unsigned long long>((size_t)num_classes * MAX_ROIS * 8);
+    md.cls_boxes = ws.take<float>((size_t)num_classes * MAX_ROIS * 16);
+    md.cls_counts = ws.take<int>((size_t)num_classes * 4);
+    md.out_boxes = ws.take<float>(MAX_ROIS * 16);
+    md.out_scores = ws.take<float>(MAX_ROIS * 4);
+    md.out_classes = ws.take<int>(MAX_ROIS * 4);
+    md.out_count = ws.take<int>(4);
+  });
+  if (rc) return rc;
   MHIP_HIP(ctx, hipMemcpyAsync(head, head_host, (size_t)n * ld * 4, hipMemcpyHostToDevice, ctx->stream));
   MHIP_HIP(ctx, hipMemcpyAsync(rois, rois_host, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
   MHIP_HIP(ctx, hipMemcpyAsync(cnt, &n, 4, hipMemcpyHostToDevice, ctx->stream));

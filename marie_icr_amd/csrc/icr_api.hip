@@ -249,25 +249,22 @@ extern "C" int mhip_icr_forward(mhip_icr* m, const uint8_t* crops, int n, float*
   const size_t es = m->esz();
   const int prec = m->precision, C = m->num_class;
   const int H = IMG_H, W = IMG_W;
-  // ---- workspace: two ping-pong activation buffers + named scratch -------------------------------------
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    size_t at = o;
-    o = (o + bytes + 4095) / 4096 * 4096;
-    return at;
-  };
+  // ---- workspace: two ping-pong activation buffers + named scratch, on 4 KiB boundaries -----------------
   const size_t big = (size_t)n * H * W * 64 * es;          // largest activation ([n][32][100][64])
-  const size_t bufA = take(big), bufB = take(big), bufC = take(big / 2), bufD = take(big / 2);
   const int T = 26;
-  const size_t o_cprime = take((size_t)n * 2 * NFID * 4), o_rect = take((size_t)n * H * W * 4);
-  const size_t o_xproj = take((size_t)n * T * 2048 * 4), o_hseq = take((size_t)n * T * 512 * es);
-  const size_t o_lin0 = take((size_t)n * T * 256 * es), o_lin1 = take((size_t)n * T * 256 * es);
-  const size_t o_hproj = take((size_t)n * T * 256 * 4), o_hg = take((size_t)n * 1280 * 4);
-  const size_t o_ctx = take((size_t)n * 256 * es), o_gctx = take((size_t)n * 1024 * 4);
-  const size_t o_h = take((size_t)n * 256 * es), o_c = take((size_t)n * 256 * 4), o_chars = take((size_t)n * 4);
-  int rc = mhip_ensure_workspace(ctx, o);
+  char *bufA = nullptr, *bufB = nullptr, *bufC = nullptr, *bufD = nullptr, *o_cprime = nullptr, *o_rect = nullptr;
+  char *o_xproj = nullptr, *o_hseq = nullptr, *o_lin0 = nullptr, *o_lin1 = nullptr, *o_hproj = nullptr, *o_hg = nullptr;
+  char *o_ctx = nullptr, *o_gctx = nullptr, *o_h = nullptr, *o_c = nullptr, *o_chars = nullptr;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
+    bufA = ws.take(big); bufB = ws.take(big); bufC = ws.take(big / 2); bufD = ws.take(big / 2);
+    o_cprime = ws.take((size_t)n * 2 * NFID * 4); o_rect = ws.take((size_t)n * H * W * 4);
+    o_xproj = ws.take((size_t)n * T * 2048 * 4); o_hseq = ws.take((size_t)n * T * 512 * es);
+    o_lin0 = ws.take((size_t)n * T * 256 * es); o_lin1 = ws.take((size_t)n * T * 256 * es);
+    o_hproj = ws.take((size_t)n * T * 256 * 4); o_hg = ws.take((size_t)n * 1280 * 4);
+    o_ctx = ws.take((size_t)n * 256 * es); o_gctx = ws.take((size_t)n * 1024 * 4);
+    o_h = ws.take((size_t)n * 256 * es); o_c = ws.take((size_t)n * 256 * 4); o_chars = ws.take((size_t)n * 4);
+  }, 4096);
   if (rc) return rc;
-  char* ws = (char*)ctx->ws;
   const char* A = m->arena.dev;
 #define CK(x) do { rc = (x); if (rc) return rc; } while (0)
   auto conv = [&](const std::string& key, const void* in, int hh, int ww, void* out, int pool, int relu,
@@ -295,7 +292,7 @@ extern "C" int mhip_icr_forward(mhip_icr* m, const uint8_t* crops, int n, float*
     return mhip_launch_conv_gray_first(ctx, prec, in_is_u8, img, n, H, W, c.co, (const float*)(A + m->w_off[i]),
                                        (const float*)(A + m->s_off[i]), (const float*)(A + m->b_off[i]), out);
   };
-  void *a = ws + bufA, *b = ws + bufB, *c2 = ws + bufC, *d2 = ws + bufD;
+  void *a = bufA, *b = bufB, *c2 = bufC, *d2 = bufD;
 
   // ---- TPS: localization network -> fiducials -> rectified crop ------------------------------------------
   const std::string loc = "Transformation.LocalizationNetwork.conv.";
@@ -306,9 +303,9 @@ extern "C" int mhip_icr_forward(mhip_icr* m, const uint8_t* crops, int n, float*
   CK(conv(loc + "12", b, 4, 12, a, POOL_NONE, 1));                             // [n][4][12][512]
   CK(mhip_launch_avgpool_hw(ctx, prec, a, b, n, 48, 512));                     // [n][512]
   CK(gemm(b, n, 512, m->fc1_w, m->fc1_b, 256, a, 1, 0));                       // fc1 + ReLU
-  CK(gemm(a, n, 256, m->fc2_w, m->fc2_b, 2 * NFID, ws + o_cprime, 0, 1));      // C' fp32 [n][40]
-  float* rect = rectified_out ? rectified_out : (float*)(ws + o_rect);
-  CK(mhip_launch_tps_sample(ctx, crops, (const float*)(ws + o_cprime), (const float*)(A + m->idc),
+  CK(gemm(a, n, 256, m->fc2_w, m->fc2_b, 2 * NFID, o_cprime, 0, 1));      // C' fp32 [n][40]
+  float* rect = rectified_out ? rectified_out : (float*)(o_rect);
+  CK(mhip_launch_tps_sample(ctx, crops, (const float*)(o_cprime), (const float*)(A + m->idc),
                             (const float*)(A + m->phat), rect, n, H, W, NFID));
 
   // ---- ResNet-45 -------------------------------------------------------------------------------------------
@@ -351,31 +348,31 @@ extern "C" int mhip_icr_forward(mhip_icr* m, const uint8_t* crops, int n, float*
   // ---- BiLSTM x 2 (AdaptiveAvgPool over H is the identity: H = 1) ----------------------------------------------
   const void* seq_in = cur;
   int seq_ch = 512;
-  const size_t lin_off[2] = {o_lin0, o_lin1};
+  char* const lin_off[2] = {o_lin0, o_lin1};
   for (int j = 0; j < 2; ++j) {
-    CK(gemm(seq_in, n * T, seq_ch, m->ih_w[j], m->ih_b[j], 2048, ws + o_xproj, 0, 1));
-    CK(mhip_launch_lstm_rec(ctx, prec, (const float*)(ws + o_xproj), A + m->hh_pack[j], ws + o_hseq, n, T));
-    CK(gemm(ws + o_hseq, n * T, 512, m->lin_w[j], m->lin_b[j], 256, ws + lin_off[j], 0, 0));
-    seq_in = ws + lin_off[j];
+    CK(gemm(seq_in, n * T, seq_ch, m->ih_w[j], m->ih_b[j], 2048, o_xproj, 0, 1));
+    CK(mhip_launch_lstm_rec(ctx, prec, (const float*)(o_xproj), A + m->hh_pack[j], o_hseq, n, T));
+    CK(gemm(o_hseq, n * T, 512, m->lin_w[j], m->lin_b[j], 256, lin_off[j], 0, 0));
+    seq_in = lin_off[j];
     seq_ch = 256;
   }
-  const void* batch_h = ws + o_lin1;
+  const void* batch_h = o_lin1;
 
   // ---- attention decoder: 49 greedy steps ---------------------------------------------------------------------
-  CK(gemm(batch_h, n * T, 256, m->i2h_w, 0, 256, ws + o_hproj, 0, 1));         // i2h(batch_H), loop-invariant
-  MHIP_HIP(ctx, hipMemsetAsync(ws + o_h, 0, (size_t)n * 256 * es, ctx->stream));
-  MHIP_HIP(ctx, hipMemsetAsync(ws + o_c, 0, (size_t)n * 256 * 4, ctx->stream));
-  MHIP_HIP(ctx, hipMemsetAsync(ws + o_chars, 0, (size_t)n * 4, ctx->stream));  // [GO] = 0
+  CK(gemm(batch_h, n * T, 256, m->i2h_w, 0, 256, o_hproj, 0, 1));         // i2h(batch_H), loop-invariant
+  MHIP_HIP(ctx, hipMemsetAsync(o_h, 0, (size_t)n * 256 * es, ctx->stream));
+  MHIP_HIP(ctx, hipMemsetAsync(o_c, 0, (size_t)n * 256 * 4, ctx->stream));
+  MHIP_HIP(ctx, hipMemsetAsync(o_chars, 0, (size_t)n * 4, ctx->stream));  // [GO] = 0
   for (int s = 0; s < STEPS; ++s) {
-    CK(gemm(ws + o_h, n, 256, m->hg_w, m->hg_b, 1280, ws + o_hg, 0, 1));       // [h2h(h)+b | W_hh h + b_ih + b_hh]
-    CK(mhip_launch_attn_context(ctx, prec, (const float*)(ws + o_hproj), (const float*)(ws + o_hg), 1280,
-                                (const float*)(A + m->score_w), batch_h, ws + o_ctx, n, T));
-    CK(gemm(ws + o_ctx, n, 256, m->ihc_w, 0, 1024, ws + o_gctx, 0, 1));        // W_ih[:, :256] context
-    CK(mhip_launch_attn_cell(ctx, prec, (const float*)(ws + o_gctx), (const float*)(ws + o_hg), 1280,
-                             (const float*)(A + m->onehot_w), (const int*)(ws + o_chars), (float*)(ws + o_c),
-                             ws + o_h, n));
-    CK(gemm(ws + o_h, n, 256, m->gen_w, m->gen_b, C, logits + (size_t)s * C, 0, 1, STEPS * C));   // probs[:, s, :]
-    CK(mhip_launch_argmax_rows(ctx, logits + (size_t)s * C, STEPS * C, C, (int*)(ws + o_chars), n));
+    CK(gemm(o_h, n, 256, m->hg_w, m->hg_b, 1280, o_hg, 0, 1));       // [h2h(h)+b | W_hh h + b_ih + b_hh]
+    CK(mhip_launch_attn_context(ctx, prec, (const float*)(o_hproj), (const float*)(o_hg), 1280,
+                                (const float*)(A + m->score_w), batch_h, o_ctx, n, T));
+    CK(gemm(o_ctx, n, 256, m->ihc_w, 0, 1024, o_gctx, 0, 1));        // W_ih[:, :256] context
+    CK(mhip_launch_attn_cell(ctx, prec, (const float*)(o_gctx), (const float*)(o_hg), 1280,
+                             (const float*)(A + m->onehot_w), (const int*)(o_chars), (float*)(o_c),
+                             o_h, n));
+    CK(gemm(o_h, n, 256, m->gen_w, m->gen_b, C, logits + (size_t)s * C, 0, 1, STEPS * C));   // probs[:, s, :]
+    CK(mhip_launch_argmax_rows(ctx, logits + (size_t)s * C, STEPS * C, C, (int*)(o_chars), n));
   }
   CK(mhip_launch_rowmax_softmax(ctx, logits, n * STEPS, C, argmax, pmax));
 #undef CK
@@ -390,19 +387,19 @@ extern "C" int mhip_icr_forward_host(mhip_icr* m, const uint8_t* crops_h, int n,
   const int C = m->num_class;
   const size_t in_b = (size_t)n * IMG_H * IMG_W, lg_b = (size_t)n * STEPS * C * 4, it_b = (size_t)n * STEPS * 4,
                rc_b = (size_t)n * IMG_H * IMG_W * 4;
-  // I/O staging in its own allocation so the forward's workspace planning stays independent
+  // I/O staging in its own allocation so the forward's workspace layout stays independent
+  char *d_in = nullptr, *d_lg = nullptr, *d_am = nullptr, *d_pm = nullptr, *d_rc = nullptr;
+  auto layout = [&](Carver& c) {
+    d_in = c.take(in_b); d_lg = c.take(lg_b); d_am = c.take(it_b); d_pm = c.take(it_b); d_rc = c.take(rc_b);
+  };
   char* io = nullptr;
-  const size_t total = in_b + lg_b + 2 * it_b + rc_b + 4096 * 5;
+  const size_t total = mhip_layout_bytes(layout, 4096);
   if (hipMalloc((void**)&io, total) != hipSuccess) {
     (void)hipGetLastError();
     return mhip_fail(ctx, MHIP_ENOMEM, "icr: I/O staging of %zu bytes failed", total);
   }
-  auto al = [](size_t v) { return (v + 4095) / 4096 * 4096; };
-  char* d_in = io;
-  char* d_lg = d_in + al(in_b);
-  char* d_am = d_lg + al(lg_b);
-  char* d_pm = d_am + al(it_b);
-  char* d_rc = d_pm + al(it_b);
+  Carver c(io, 4096);
+  layout(c);
   int rc = MHIP_OK;
   hipError_t e = hipMemcpyAsync(d_in, crops_h, in_b, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) {

@@ -324,10 +324,10 @@ extern "C" int mhip_resize_area_u8_host(mhip_ctx* ctx, const uint8_t* src_host, 
   if (sh <= 0 || sw <= 0 || dh <= 0 || dw <= 0 || (cn != 1 && cn != 3)) return mhip_fail(ctx, MHIP_EINVAL, "resize_area: bad shape");
   MHIP_HIP(ctx, hipSetDevice(ctx->device));
   const size_t sb = (size_t)sh * sw * cn, db = (size_t)dh * dw * cn;
-  int rc = mhip_ensure_workspace(ctx, sb + db + 1024);
+  uint8_t* s = nullptr;
+  uint8_t* d = nullptr;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) { s = ws.take<uint8_t>(sb); d = ws.take<uint8_t>(db); });
   if (rc) return rc;
-  uint8_t* s = (uint8_t*)ctx->ws;
-  uint8_t* d = s + (sb + 255) / 256 * 256;
   MHIP_HIP(ctx, hipMemcpyAsync(s, src_host, sb, hipMemcpyHostToDevice, ctx->stream));
   if ((rc = mhip_resize_area_u8(ctx, s, sh, sw, cn, (size_t)sw * cn, d, dh, dw))) return rc;
   MHIP_HIP(ctx, hipMemcpyAsync(dst_host, d, db, hipMemcpyDeviceToHost, ctx->stream));
@@ -363,10 +363,10 @@ extern "C" int mhip_resize_cubic_u8_host(mhip_ctx* ctx, const uint8_t* src_host,
   if (sh <= 0 || sw <= 0 || dh <= 0 || dw <= 0 || (cn != 1 && cn != 3)) return mhip_fail(ctx, MHIP_EINVAL, "resize_cubic: bad shape");
   MHIP_HIP(ctx, hipSetDevice(ctx->device));
   const size_t sb = (size_t)sh * sw * cn, db = (size_t)dh * dw * cn;
-  int rc = mhip_ensure_workspace(ctx, sb + db + 1024);
+  uint8_t* s = nullptr;
+  uint8_t* d = nullptr;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) { s = ws.take<uint8_t>(sb); d = ws.take<uint8_t>(db); });
   if (rc) return rc;
-  uint8_t* s = (uint8_t*)ctx->ws;
-  uint8_t* d = s + (sb + 255) / 256 * 256;
   MHIP_HIP(ctx, hipMemcpyAsync(s, src_host, sb, hipMemcpyHostToDevice, ctx->stream));
   if ((rc = mhip_resize_cubic_u8(ctx, s, sh, sw, cn, (size_t)sw * cn, d, dh, dw))) return rc;
   MHIP_HIP(ctx, hipMemcpyAsync(dst_host, d, db, hipMemcpyDeviceToHost, ctx->stream));
@@ -479,11 +479,11 @@ extern "C" int mhip_register_warp_host(mhip_ctx* ctx, const uint8_t* page_host, 
     return mhip_fail(ctx, MHIP_EINVAL, "register_warp: bad shape");
   MHIP_HIP(ctx, hipSetDevice(ctx->device));
   const size_t sb = (size_t)h * w * 3, cb = (size_t)d->canvas_w * d->canvas_h * 3, ob = (size_t)d->final_w * d->final_h * 3;
-  int rc = mhip_ensure_workspace(ctx, sb + cb + ob + 1024);
+  uint8_t* s = nullptr;
+  uint8_t* c = nullptr;
+  uint8_t* o = nullptr;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) { s = ws.take<uint8_t>(sb); c = ws.take<uint8_t>(cb); o = ws.take<uint8_t>(ob); });
   if (rc) return rc;
-  uint8_t* s = (uint8_t*)ctx->ws;
-  uint8_t* c = s + (sb + 255) / 256 * 256;
-  uint8_t* o = c + (cb + 255) / 256 * 256;
   MHIP_HIP(ctx, hipMemcpyAsync(s, page_host, sb, hipMemcpyHostToDevice, ctx->stream));
   if ((rc = mhip_register_warp(ctx, s, h, w, (size_t)w * 3, d, c, o))) return rc;
   MHIP_HIP(ctx, hipMemcpyAsync(out_host, o, ob, hipMemcpyDeviceToHost, ctx->stream));

@@ -188,18 +188,29 @@ extern "C" int mhip_overlay_padded_shape(int h, int w, int* H, int* W) {
   return MHIP_OK;
 }
 
-static size_t overlay_ws_bytes(const mhip_overlay* m, int H, int W) {
-  // exactly what overlay_run carves, in its order (every take is rounded up to 256 bytes)
+// the generator's buffers, in layout order
+struct OverlayBufs {
+  float* stats;
+  char *x4, *half4, *g, *t1, *t2, *patches, *l1, *l2, *zi, *y8;
+};
+
+static void overlay_carve(const mhip_overlay* m, Carver& ws, int H, int W, OverlayBufs* b) {
   const size_t es = m->esz(), P = (size_t)H * W, ngf = m->ngf, G = 2 * ngf, Hh = H / 2, Wh = W / 2;
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  size_t b = up(3 * 2048 * 4);                              // stats
-  b += up(P * 4 * es) + up(Hh * Wh * 4 * es);               // x4, half4
-  b += 3 * up((Hh + 2) * (Wh + 2) * 2 * G * es);            // g, t1, t2
-  b += up(P * 192 * es);                                    // patches of the 7x7 stems
-  b += 2 * up((size_t)(H + 6) * (W + 6) * ngf * es);        // l1, l2
-  b += up((size_t)(H + 2) * (W + 2) * G * es);              // zero-inserted canvas
-  b += up(P * 8 * es);                                      // y8
-  return b + 4096;
+  b->stats = ws.take<float>(3 * 2048 * 4);
+  b->x4 = ws.take(P * 4 * es);
+  b->half4 = ws.take(Hh * Wh * 4 * es);
+  // big enough for any map of the global branch incl. frames (the largest: 2 G channels at half resolution, the up-sampled
+  // input of the last 3x3 convolution)
+  const size_t gmax = (Hh + 2) * (Wh + 2) * 2 * G * es;
+  b->g = ws.take(gmax);
+  b->t1 = ws.take(gmax);
+  b->t2 = ws.take(gmax);
+  b->patches = ws.take(P * 192 * es);                       // patch matrix of the 7x7 stems
+  const size_t lmax = (size_t)(H + 6) * (W + 6) * ngf * es;
+  b->l1 = ws.take(lmax);
+  b->l2 = ws.take(lmax);
+  b->zi = ws.take((size_t)(H + 2) * (W + 2) * G * es);    // zero-inserted canvas
+  b->y8 = ws.take(P * 8 * es);
 }
 
 // page_dev u8 BGR [h][w][3] -> fake_rgb_dev u8 RGB [H][W][3] on the padded canvas (mhip_overlay_padded_shape); raw_dev (optional)
@@ -211,24 +222,20 @@ static int overlay_run(mhip_overlay* m, const uint8_t* page_dev, int h, int w, u
   int H, W;
   mhip_overlay_padded_shape(h, w, &H, &W);
   const int prec = m->precision, ngf = m->ngf, G = 2 * ngf;
-  const size_t es = m->esz();
-  int rc = mhip_ensure_workspace(ctx, overlay_ws_bytes(m, H, W));
+  OverlayBufs bf;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) { overlay_carve(m, ws, H, W, &bf); });
   if (rc) return rc;
-  Carver ws(ctx->ws);
   const Arena& a = m->arena;
-  float* stats = ws.take<float>(3 * 2048 * 4);
+  float* stats = bf.stats;
   const int Hh = H / 2, Wh = W / 2;
   // ---- input
-  char* x4 = ws.take((size_t)H * W * 4 * es);
+  char* x4 = bf.x4;
   if ((rc = mhip_ov_preprocess(ctx, prec, page_dev, h, w, x4, H, W))) return rc;
-  char* half4 = ws.take((size_t)Hh * Wh * 4 * es);
+  char* half4 = bf.half4;
   if ((rc = mhip_ov_conv_c3(ctx, prec, x4, a.d<float>("downsample_w"), a.d<float>("downsample_b"), half4, H, W, 3, 3, 2, 1, 0))) return rc;
-  // scratch big enough for any map of the global branch incl. frames (the largest: 2 G channels at half resolution, the
-  // up-sampled input of the last 3x3 convolution)
-  const size_t gmax = (size_t)(Hh + 2) * (Wh + 2) * 2 * G * es;
-  char* g = ws.take(gmax);
-  char* t1 = ws.take(gmax);
-  char* t2 = ws.take(gmax);
+  char* g = bf.g;
+  char* t1 = bf.t1;
+  char* t2 = bf.t2;
   // ---- global branch
   auto stem = [&](const void* img4, const char* name, void* out, int hs, int wsz, int cout, void* patches) -> int {
     int r = mhip_ov_im2col7(ctx, prec, img4, patches, hs, wsz);
@@ -238,7 +245,7 @@ static int overlay_run(mhip_overlay* m, const uint8_t* page_dev, int h, int w, u
     c.B = 1; c.H = hs; c.W = wsz; c.Cin = 192; c.KH = c.KW = 1; c.pad = 0; c.N = cout;
     return mhip_launch_conv_igemm(ctx, prec, c);
   };
-  char* patches = ws.take((size_t)H * W * 192 * es);
+  char* patches = bf.patches;
   if ((rc = stem(half4, "model.1", t1, Hh, Wh, G, patches))) return rc;
   if ((rc = mhip_ov_instance_norm(ctx, prec, t1, Hh, Wh, 1, G, IN_EPS, 1, nullptr, g, stats))) return rc;
   int ch = G, hh = Hh, wh = Wh;
@@ -269,9 +276,8 @@ static int overlay_run(mhip_overlay* m, const uint8_t* page_dev, int h, int w, u
   }
   // g: [Hh][Wh][G] before its swish
   // ---- local branch
-  const size_t lmax = (size_t)(H + 6) * (W + 6) * ngf * es;
-  char* l1 = ws.take(lmax);
-  char* l2 = ws.take(lmax);
+  char* l1 = bf.l1;
+  char* l2 = bf.l2;
   if ((rc = stem(x4, "model1_1.1", l1, H, W, ngf, patches))) return rc;
   if ((rc = mhip_ov_instance_norm(ctx, prec, l1, H, W, 1, ngf, IN_EPS, 1, nullptr, l1, stats))) return rc;
   if ((rc = conv(m, l1, "model1_1.4", l2, H, W, ngf, G, 3, 1, 2))) return rc;                                 // [Hh][W][G]
@@ -287,12 +293,12 @@ static int overlay_run(mhip_overlay* m, const uint8_t* page_dev, int h, int w, u
     if ((rc = mhip_ov_instance_norm(ctx, prec, t2, Hh, Wh, 1, G, IN_EPS, 0, g, g, stats))) return rc;
   }
   // ConvTranspose2d(G -> ngf, k 3, s 2, p 1, output_padding 1): zero-inserted canvas [H + 2][W + 2][G], 3x3 convolution, no padding
-  char* zi = ws.take((size_t)(H + 2) * (W + 2) * G * es);
+  char* zi = bf.zi;
   if ((rc = mhip_ov_zero_insert(ctx, prec, g, zi, Hh, Wh, G))) return rc;
   if ((rc = conv(m, zi, "model1_2.3", l1, H + 2, W + 2, G, ngf, 3, 0, 1))) return rc;
   if ((rc = mhip_ov_instance_norm(ctx, prec, l1, H, W, 1, ngf, IN_EPS, 1, nullptr, l1, stats))) return rc;
   if ((rc = mhip_ov_reflect_pad(ctx, prec, l1, l2, H, W, ngf, 3))) return rc;
-  char* y8 = ws.take((size_t)H * W * 8 * es);
+  char* y8 = bf.y8;
   if ((rc = conv(m, l2, "model1_2.7", y8, H + 6, W + 6, ngf, 3, 7, 0, 1, 8))) return rc;
   return mhip_ov_final(ctx, prec, y8, fake_rgb_dev, raw_dev, (size_t)H * W);
 }

@@ -199,12 +199,41 @@ int ksize_of(int in_size, int out_size, int filter) {
   return (int)ceil(support) * 2 + 1;
 }
 
+// the coefficient tables and the intermediate image of n resizes (tmp_bytes of horizontal-pass output) in `c`
+struct PilScratch {
+  uint8_t* tmp;
+  int *bx, *kx, *by, *ky;
+};
+void pil_carve(Carver& c, int n, size_t tmp_bytes, int dh, int dw, int kx, int ky, PilScratch* s) {
+  s->tmp = c.take<uint8_t>(tmp_bytes);
+  s->bx = c.take<int>((size_t)n * dw * 8);
+  s->kx = c.take<int>((size_t)n * dw * kx * 4);
+  s->by = c.take<int>((size_t)n * dh * 8);
+  s->ky = c.take<int>((size_t)n * dh * ky * 4);
+}
+
+// the scratch of mhip_pil_resize_fragments: sized with a null base, placed on the caller's scratch otherwise
+struct FragScratch {
+  FragDev* fr;
+  PilScratch p;
+  int kx = 1, ky = 1;
+};
+void frag_carve(Carver& c, const mhip_crop_desc* descs, int n, int dh, int dw, int filter, FragScratch* s) {
+  size_t tmp_total = 0;
+  for (int i = 0; i < n; ++i) {
+    tmp_total += ((size_t)std::max(descs[i].h, 1) * dw * 3 + 255) / 256 * 256;
+    s->kx = std::max(s->kx, ksize_of(std::max(descs[i].w, 1), dw, filter));
+    s->ky = std::max(s->ky, ksize_of(std::max(descs[i].h, 1), dh, filter));
+  }
+  s->fr = c.take<FragDev>(n * sizeof(FragDev));
+  pil_carve(c, n, tmp_total, dh, dw, s->kx, s->ky, &s->p);
+}
+
 }  // namespace
 
 size_t mhip_pil_resize_scratch_bytes(int sh, int sw, int dh, int dw, int filter) {
-  const size_t kx = ksize_of(sw, dw, filter), ky = ksize_of(sh, dh, filter);
-  auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-  return al((size_t)sh * dw * 3) + al((size_t)dw * 8) + al((size_t)dw * kx * 4) + al((size_t)dh * 8) + al((size_t)dh * ky * 4);
+  PilScratch s;
+  return mhip_layout_bytes([&](Carver& c) { pil_carve(c, 1, (size_t)sh * dw * 3, dh, dw, ksize_of(sw, dw, filter), ksize_of(sh, dh, filter), &s); });
 }
 
 // src: u8 RGB rows of `src_stride` bytes; dst [dh][dw][3]; scratch from mhip_pil_resize_scratch_bytes
@@ -213,64 +242,52 @@ int mhip_launch_pil_resize_rgb(mhip_ctx* ctx, const uint8_t* src, int sh, int sw
   if (sh < 1 || sw < 1 || dh < 1 || dw < 1 || (filter != MHIP_PIL_BILINEAR && filter != MHIP_PIL_BICUBIC))
     return mhip_fail(ctx, MHIP_EINVAL, "pil_resize: bad arguments");
   const int kx = ksize_of(sw, dw, filter), ky = ksize_of(sh, dh, filter);
-  auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-  char* p = (char*)scratch;
-  uint8_t* tmp = (uint8_t*)p; p += al((size_t)sh * dw * 3);
-  int* bx = (int*)p; p += al((size_t)dw * 8);
-  int* kkx = (int*)p; p += al((size_t)dw * kx * 4);
-  int* by = (int*)p; p += al((size_t)dh * 8);
-  int* kky = (int*)p;
+  Carver c(scratch);
+  PilScratch s;
+  pil_carve(c, 1, (size_t)sh * dw * 3, dh, dw, kx, ky, &s);
   PROF_LAUNCH(ctx, MHIP_K_IMAGE_OPS, {
-    hipLaunchKernelGGL(pil_coeffs_kernel, dim3((dw + 255) / 256), dim3(256), 0, ctx->stream, sw, dw, filter, kx, bx, kkx);
-    hipLaunchKernelGGL(pil_coeffs_kernel, dim3((dh + 255) / 256), dim3(256), 0, ctx->stream, sh, dh, filter, ky, by, kky);
+    hipLaunchKernelGGL(pil_coeffs_kernel, dim3((dw + 255) / 256), dim3(256), 0, ctx->stream, sw, dw, filter, kx, s.bx, s.kx);
+    hipLaunchKernelGGL(pil_coeffs_kernel, dim3((dh + 255) / 256), dim3(256), 0, ctx->stream, sh, dh, filter, ky, s.by, s.ky);
     const long long t1 = (long long)sh * dw, t2 = (long long)dh * dw;
-    hipLaunchKernelGGL(pil_hpass_kernel, dim3((unsigned)std::min<long long>((t1 + 255) / 256, 1 << 20)), dim3(256), 0, ctx->stream, src, sh, src_stride, dw, kx, bx, kkx, tmp);
-    hipLaunchKernelGGL(pil_vpass_kernel, dim3((unsigned)std::min<long long>((t2 + 255) / 256, 1 << 20)), dim3(256), 0, ctx->stream, tmp, dw, dh, ky, by, kky, dst);
+    hipLaunchKernelGGL(pil_hpass_kernel, dim3((unsigned)std::min<long long>((t1 + 255) / 256, 1 << 20)), dim3(256), 0, ctx->stream, src, sh, src_stride, dw, kx, s.bx, s.kx, s.tmp);
+    hipLaunchKernelGGL(pil_vpass_kernel, dim3((unsigned)std::min<long long>((t2 + 255) / 256, 1 << 20)), dim3(256), 0, ctx->stream, s.tmp, dw, dh, ky, s.by, s.ky, dst);
   });
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return mhip_fail(ctx, MHIP_EHIP, "pil_resize launch: %s", hipGetErrorString(e));
   return 0;
 }
 
-// n fragments (3-channel u8, descs on the host) -> dst [n][dh][dw][3].  Allocates its scratch from the context workspace
-// TAIL (offset ws_off onwards), so callers that carve the head of the workspace are not disturbed.
+// n fragments (3-channel u8, descs on the host) -> dst [n][dh][dw][3], through the caller's scratch of scratch_bytes
+// (mhip_pil_resize_fragments_scratch)
 int mhip_pil_resize_fragments(mhip_ctx* ctx, const uint8_t* base_dev, const mhip_crop_desc* descs, int n, uint8_t* dst, int dh,
                               int dw, int filter, void* scratch, size_t scratch_bytes) {
   if (n < 1) return 0;
   std::vector<FragDev> fr(n);
-  size_t tmp_total = 0;
-  int kx = 1, ky = 1, hmax = 1;
+  size_t tmp_off = 0;
+  int hmax = 1;
   for (int i = 0; i < n; ++i) {
     if (descs[i].channels != 3 || descs[i].h < 1 || descs[i].w < 1) return mhip_fail(ctx, MHIP_EINVAL, "pil_resize: fragment %d must be h x w x 3", i);
-    fr[i].src_off = descs[i].src_offset; fr[i].tmp_off = tmp_total;
+    fr[i].src_off = descs[i].src_offset; fr[i].tmp_off = tmp_off;
     fr[i].h = descs[i].h; fr[i].w = descs[i].w; fr[i].row_stride = descs[i].row_stride;
-    tmp_total += ((size_t)descs[i].h * dw * 3 + 255) / 256 * 256;
-    kx = std::max(kx, ksize_of(descs[i].w, dw, filter));
-    ky = std::max(ky, ksize_of(descs[i].h, dh, filter));
+    tmp_off += ((size_t)descs[i].h * dw * 3 + 255) / 256 * 256;
     hmax = std::max(hmax, descs[i].h);
   }
-  auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-  const size_t need = al(n * sizeof(FragDev)) + al(tmp_total) + al((size_t)n * dw * 8) + al((size_t)n * dw * kx * 4) +
-                      al((size_t)n * dh * 8) + al((size_t)n * dh * ky * 4);
-  if (need > scratch_bytes) return mhip_fail(ctx, MHIP_ENOMEM, "pil_resize: scratch %zu < %zu", scratch_bytes, need);
-  char* p = (char*)scratch;
-  FragDev* dfr = (FragDev*)p; p += al(n * sizeof(FragDev));
-  uint8_t* tmp = (uint8_t*)p; p += al(tmp_total);
-  int* bx = (int*)p; p += al((size_t)n * dw * 8);
-  int* kkx = (int*)p; p += al((size_t)n * dw * kx * 4);
-  int* by = (int*)p; p += al((size_t)n * dh * 8);
-  int* kky = (int*)p;
+  Carver c(scratch);
+  FragScratch s;
+  frag_carve(c, descs, n, dh, dw, filter, &s);
+  if (c.off > scratch_bytes) return mhip_fail(ctx, MHIP_ENOMEM, "pil_resize: scratch %zu < %zu", scratch_bytes, c.off);
+  const int kx = s.kx, ky = s.ky;
   // fr is a host temporary: through pinned staging, without draining the stream (the engine encodes page batches back to back;
   // a drain here left the GPU idle while the host prepared the next batch: ~12 ms per 8 pages)
   {
-    const int rc = mhip_stage_h2d(ctx, dfr, fr.data(), n * sizeof(FragDev));
+    const int rc = mhip_stage_h2d(ctx, s.fr, fr.data(), n * sizeof(FragDev));
     if (rc) return rc;
   }
   PROF_LAUNCH(ctx, MHIP_K_IMAGE_OPS, {
-    hipLaunchKernelGGL(pil_coeffs_batch_kernel, dim3((dw + 255) / 256, n), dim3(256), 0, ctx->stream, dfr, 0, dw, filter, kx, bx, kkx);
-    hipLaunchKernelGGL(pil_coeffs_batch_kernel, dim3((dh + 255) / 256, n), dim3(256), 0, ctx->stream, dfr, 1, dh, filter, ky, by, kky);
-    hipLaunchKernelGGL(pil_hpass_batch_kernel, dim3((hmax * dw + 255) / 256, n), dim3(256), 0, ctx->stream, base_dev, dfr, dw, kx, bx, kkx, tmp);
-    hipLaunchKernelGGL(pil_vpass_batch_kernel, dim3((dh * dw + 255) / 256, n), dim3(256), 0, ctx->stream, tmp, dfr, dw, dh, ky, by, kky, dst);
+    hipLaunchKernelGGL(pil_coeffs_batch_kernel, dim3((dw + 255) / 256, n), dim3(256), 0, ctx->stream, s.fr, 0, dw, filter, kx, s.p.bx, s.p.kx);
+    hipLaunchKernelGGL(pil_coeffs_batch_kernel, dim3((dh + 255) / 256, n), dim3(256), 0, ctx->stream, s.fr, 1, dh, filter, ky, s.p.by, s.p.ky);
+    hipLaunchKernelGGL(pil_hpass_batch_kernel, dim3((hmax * dw + 255) / 256, n), dim3(256), 0, ctx->stream, base_dev, s.fr, dw, kx, s.p.bx, s.p.kx, s.p.tmp);
+    hipLaunchKernelGGL(pil_vpass_batch_kernel, dim3((dh * dw + 255) / 256, n), dim3(256), 0, ctx->stream, s.p.tmp, s.fr, dw, dh, ky, s.p.by, s.p.ky, dst);
   });
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return mhip_fail(ctx, MHIP_EHIP, "pil_resize_fragments launch: %s", hipGetErrorString(e));
@@ -278,16 +295,8 @@ int mhip_pil_resize_fragments(mhip_ctx* ctx, const uint8_t* base_dev, const mhip
 }
 
 size_t mhip_pil_resize_fragments_scratch(const mhip_crop_desc* descs, int n, int dh, int dw, int filter) {
-  auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-  size_t tmp_total = 0;
-  int kx = 1, ky = 1;
-  for (int i = 0; i < n; ++i) {
-    tmp_total += ((size_t)std::max(descs[i].h, 1) * dw * 3 + 255) / 256 * 256;
-    kx = std::max(kx, ksize_of(std::max(descs[i].w, 1), dw, filter));
-    ky = std::max(ky, ksize_of(std::max(descs[i].h, 1), dh, filter));
-  }
-  return al(n * sizeof(FragDev)) + al(tmp_total) + al((size_t)n * dw * 8) + al((size_t)n * dw * kx * 4) + al((size_t)n * dh * 8) +
-         al((size_t)n * dh * ky * 4) + 4096;
+  FragScratch s;
+  return mhip_layout_bytes([&](Carver& c) { frag_carve(c, descs, n, dh, dw, filter, &s); });
 }
 
 // replaces: Image.fromarray(rgb).resize((dw, dh), BILINEAR | BICUBIC) on host buffers (test / standalone entry)
@@ -296,12 +305,15 @@ extern "C" int mhip_pil_resize_rgb_host(mhip_ctx* ctx, const uint8_t* src_host, 
   if (!ctx || !src_host || !dst_host) return MHIP_EINVAL;
   MHIP_HIP(ctx, hipSetDevice(ctx->device));
   const size_t sb = (size_t)sh * sw * 3, db = (size_t)dh * dw * 3;
-  const size_t need = sb + db + mhip_pil_resize_scratch_bytes(sh, sw, dh, dw, filter) + 1024;
-  int rc = mhip_ensure_workspace(ctx, need);
+  uint8_t* s = nullptr;
+  uint8_t* d = nullptr;
+  void* scratch = nullptr;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
+    s = ws.take<uint8_t>(sb);
+    d = ws.take<uint8_t>(db);
+    scratch = ws.take(mhip_pil_resize_scratch_bytes(sh, sw, dh, dw, filter));
+  });
   if (rc) return rc;
-  uint8_t* s = (uint8_t*)ctx->ws;
-  uint8_t* d = s + (sb + 255) / 256 * 256;
-  void* scratch = d + (db + 255) / 256 * 256;
   MHIP_HIP(ctx, hipMemcpyAsync(s, src_host, sb, hipMemcpyHostToDevice, ctx->stream));
   if ((rc = mhip_launch_pil_resize_rgb(ctx, s, sh, sw, (size_t)sw * 3, d, dh, dw, filter, scratch))) return rc;
   MHIP_HIP(ctx, hipMemcpyAsync(dst_host, d, db, hipMemcpyDeviceToHost, ctx->stream));

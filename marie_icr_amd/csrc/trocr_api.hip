@@ -253,23 +253,74 @@ extern "C" int mhip_trocr_set_decode_gate(mhip_trocr* m, mhip_gate* gate) {
 
 extern "C" int mhip_trocr_max_len(const mhip_trocr_config* c) { return c ? trocr_max_len(*c) : MHIP_EINVAL; }
 
-static size_t trocr_ws_bytes(const mhip_trocr* m, int n) {
+// the decoder's buffers, in layout order
+struct TrocrDecodeBufs {
+  char *ck = nullptr, *cv = nullptr;   // projected path: encoder keys / values of every decoder layer
+  char *qt = nullptr, *ct = nullptr;   // absorbed path: absorbed queries / contexts
+  char* hqkv;                          // self-attention history [layer][step][slot][q | k | v]
+  float* x;
+  char *xt, *qb, *ao, *hid;
+  char* logits;                        // element type T: f16 logits in the f16 mode, fp32 in the parity mode
+  int* anc[2];
+  float* cand_scores;
+  int *cand_tokens, *cand_beams;
+  BeamState bs;                        // generator state
+  int *out_tok, *out_len;              // device copies of the outputs
+  float* out_score;
+  float* step0_stage = nullptr;        // parity entries: step-0 logits in fp32
+};
+
+static void trocr_decode_carve(const mhip_trocr* m, Carver& ws, int n, const VitGeom& vg, bool step0_stage, TrocrDecodeBufs* b) {
   const mhip_trocr_config& c = m->cfg;
-  const size_t es = m->esz(), D = c.dec_dim, M = (size_t)n * c.beam, ML = trocr_max_len(c);
-  VitGeom vg;
-  vit_geometry(m->vit, c.img_size, c.img_size, &vg);
-  const size_t ldv = (c.vocab + 7) / 8 * 8;
-  size_t b = vit_workspace_bytes(m->vit, n, vg);
-  if (m->absorb) b += 2 * M * 16 * (size_t)c.enc_dim * 2 + 512;      // absorbed queries / contexts
-  else b += 2 * (size_t)c.dec_layers * n * vg.npad * D * es;          // cross K / V
-  b += 3 * (size_t)c.dec_layers * (ML + 1) * M * D * es;              // self q | k | v history
-  b += M * D * 4 + 3 * M * D * es + M * c.dec_ffn * es + M * ldv * 4; // x, xt, q, ao, hidden, logits
-  b += 2 * M * (ML + 2) * 4 + (size_t)n * 2 * c.beam * 12 + (size_t)vg.n_tok * c.enc_dim * 4 + (size_t)c.vocab * 4 + 4096;
-  b += mhip_beam_state_bytes(n, c.beam, (int)ML) + (size_t)n * (ML + 3) * 4 + 1024;   // generator state + device copies of the outputs
-  return b + (1 << 16);
+  const size_t es = m->esz(), D = c.dec_dim, M = (size_t)n * c.beam;
+  const int ML = trocr_max_len(c), ldv = (c.vocab + 7) / 8 * 8, K2 = 2 * c.beam;
+  if (m->absorb) {
+    b->qt = ws.take(M * 16 * c.enc_dim * 2);
+    b->ct = ws.take(M * 16 * c.enc_dim * 2);
+  } else {
+    const size_t cross = (size_t)c.dec_layers * n * vg.npad * D * es;
+    b->ck = ws.take(cross);
+    b->cv = ws.take(cross);
+  }
+  b->hqkv = ws.take((size_t)c.dec_layers * (ML + 1) * M * 3 * D * es);
+  b->x = ws.take<float>(M * D * 4);
+  b->xt = ws.take(M * D * es);
+  b->qb = ws.take(M * D * es);
+  b->ao = ws.take(M * D * es);
+  b->hid = ws.take(M * c.dec_ffn * es);
+  b->logits = ws.take(M * ldv * 4);
+  for (int i = 0; i < 2; ++i) b->anc[i] = ws.take<int>(M * (ML + 2) * 4);
+  b->cand_scores = ws.take<float>((size_t)n * K2 * 4);
+  b->cand_tokens = ws.take<int>((size_t)n * K2 * 4);
+  b->cand_beams = ws.take<int>((size_t)n * K2 * 4);
+  mhip_beam_state_carve(ws, n, c.beam, ML, c.pad, c.eos, &b->bs);
+  b->bs.cand_scores = b->cand_scores; b->bs.cand_tokens = b->cand_tokens; b->bs.cand_beams = b->cand_beams;
+  b->out_tok = ws.take<int>((size_t)n * (ML + 1) * 4);
+  b->out_len = ws.take<int>((size_t)n * 4);
+  b->out_score = ws.take<float>((size_t)n * 4);
+  if (step0_stage) b->step0_stage = ws.take<float>((size_t)c.vocab * 4);
 }
 
-extern "C" size_t mhip_trocr_workspace_bytes(mhip_trocr* m, int n) { return (m && n > 0) ? trocr_ws_bytes(m, n) : 0; }
+// the layout of one generate call over n crops: encoder, the parity entries' staging on request, decoder
+struct TrocrBufs {
+  VitRun run;
+  float* enc_stage = nullptr;
+  TrocrDecodeBufs dec;
+};
+
+static void trocr_carve(const mhip_trocr* m, Carver& ws, int n, bool enc_stage, bool step0_stage, TrocrBufs* b) {
+  VitGeom vg;
+  vit_geometry(m->vit, m->cfg.img_size, m->cfg.img_size, &vg);
+  vit_carve(m->vit, ws, n, vg, &b->run);
+  if (enc_stage) b->enc_stage = ws.take<float>((size_t)vg.n_tok * m->cfg.enc_dim * 4);
+  trocr_decode_carve(m, ws, n, vg, step0_stage, &b->dec);
+}
+
+extern "C" size_t mhip_trocr_workspace_bytes(mhip_trocr* m, int n) {
+  if (!m || n < 1) return 0;
+  TrocrBufs b;
+  return mhip_layout_bytes([&](Carver& ws) { trocr_carve(m, ws, n, false, false, &b); });
+}
 
 // crops_dev: n images u8 [img][img][3].  tokens_out [n][max_len + 1] (the hypothesis without the leading eos, eos included,
 // padded with `pad`), lengths_out [n], scores_out [n] (length-normalised log-probability of the best hypothesis).
@@ -280,8 +331,8 @@ struct TrocrTrace {          // host arrays [max_len + 1][n][2 * beam], filled f
   int steps;
 };
 
-static int trocr_decode(mhip_trocr* m, Carver& ws, const char* enc_tokens, const VitGeom& vg, int n, int32_t* tokens_out,
-                        int32_t* lengths_out, float* scores_out, float* step0_logits_host, TrocrTrace* trace);
+static int trocr_decode(mhip_trocr* m, const TrocrDecodeBufs& b, const char* enc_tokens, const VitGeom& vg, int n,
+                        int32_t* tokens_out, int32_t* lengths_out, float* scores_out, float* step0_logits_host, TrocrTrace* trace);
 
 static int trocr_generate(mhip_trocr* m, const uint8_t* crops_dev, int n, int swap_rb, int32_t* tokens_out,
                           int32_t* lengths_out, float* scores_out, float* enc_tokens_host, float* step0_logits_host,
@@ -293,28 +344,26 @@ static int trocr_generate(mhip_trocr* m, const uint8_t* crops_dev, int n, int sw
   const mhip_trocr_config& c = m->cfg;
   const int prec = m->precision, E = c.enc_dim;
   const size_t es = m->esz();
-  int rc = mhip_ensure_workspace(ctx, trocr_ws_bytes(m, n));
+  TrocrBufs b;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) { trocr_carve(m, ws, n, enc_tokens_host, step0_logits_host, &b); });
   if (rc) return rc;
-  Carver ws(ctx->ws);
   // ---- encoder --------------------------------------------------------------------------------------------------
-  VitRun run;
-  if ((rc = vit_encode(m->vit, ws, crops_dev, n, c.img_size, c.img_size, c.img_size, c.img_size, swap_rb, &run))) return rc;
-  const VitGeom& vg = run.g;
+  if ((rc = vit_encode(m->vit, crops_dev, n, c.img_size, c.img_size, c.img_size, c.img_size, swap_rb, &b.run))) return rc;
+  const VitGeom& vg = b.run.g;
   if (enc_tokens_host) {
-    float* stage = ws.take<float>((size_t)vg.n_tok * E * 4);
     for (int i = 0; i < n; ++i) {
-      if ((rc = mhip_launch_convert_rows(ctx, prec, run.tokens + (size_t)i * vg.npad * E * es, stage, vg.n_tok, E))) return rc;
-      MHIP_HIP(ctx, hipMemcpyAsync(enc_tokens_host + (size_t)i * vg.n_tok * E, stage, (size_t)vg.n_tok * E * 4, hipMemcpyDeviceToHost, ctx->stream));
+      if ((rc = mhip_launch_convert_rows(ctx, prec, b.run.tokens + (size_t)i * vg.npad * E * es, b.enc_stage, vg.n_tok, E))) return rc;
+      MHIP_HIP(ctx, hipMemcpyAsync(enc_tokens_host + (size_t)i * vg.n_tok * E, b.enc_stage, (size_t)vg.n_tok * E * 4, hipMemcpyDeviceToHost, ctx->stream));
       MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
   }
-  return trocr_decode(m, ws, run.tokens, vg, n, tokens_out, lengths_out, scores_out, step0_logits_host, trace);
+  return trocr_decode(m, b.dec, b.run.tokens, vg, n, tokens_out, lengths_out, scores_out, step0_logits_host, trace);
 }
 
 // The autoregressive part (TextRecognitionGenerator._generate, generator.py:127-362) over the encoder tokens of n crops:
 // enc_tokens T [n * vg.npad + 64 slack rows][enc_dim].
-static int trocr_decode(mhip_trocr* m, Carver& ws, const char* enc_tokens, const VitGeom& vg, int n, int32_t* tokens_out,
-                        int32_t* lengths_out, float* scores_out, float* step0_logits_host, TrocrTrace* trace) {
+static int trocr_decode(mhip_trocr* m, const TrocrDecodeBufs& b, const char* enc_tokens, const VitGeom& vg, int n,
+                        int32_t* tokens_out, int32_t* lengths_out, float* scores_out, float* step0_logits_host, TrocrTrace* trace) {
   mhip_ctx* ctx = m->ctx;
   const mhip_trocr_config& c = m->cfg;
   const int prec = m->precision, D = c.dec_dim, E = c.enc_dim, F = c.dec_ffn, beam = c.beam, L = c.dec_layers;
@@ -326,10 +375,8 @@ static int trocr_decode(mhip_trocr* m, Carver& ws, const char* enc_tokens, const
   struct { const char* tokens; } run{enc_tokens};
   // ---- encoder keys / values of every decoder layer (static over the steps) -----------------------------------------
   const size_t cross_l = (size_t)n * vg.npad * D * es;
-  char* ck = m->absorb ? nullptr : ws.take(L * cross_l);
-  char* cv = m->absorb ? nullptr : ws.take(L * cross_l);
-  char* qt = m->absorb ? ws.take((size_t)M * 16 * E * 2) : nullptr;
-  char* ct = m->absorb ? ws.take((size_t)M * 16 * E * 2) : nullptr;
+  char* ck = b.ck;
+  char* cv = b.cv;
   for (int l = 0; l < L && !m->absorb; ++l) {
     if ((rc = mhip_gemm(ctx, prec, run.tokens, a.d(lay(l, "ca_k") + "_w"), (long long)n * vg.npad, D, E, nullptr, a.d<float>(lay(l, "ca_k") + "_b"), ck + l * cross_l, ACT_NONE, 0))) return rc;
     if ((rc = mhip_gemm(ctx, prec, run.tokens, a.d(lay(l, "ca_v") + "_w"), (long long)n * vg.npad, D, E, nullptr, a.d<float>(lay(l, "ca_v") + "_b"), cv + l * cross_l, ACT_NONE, 0))) return rc;
@@ -339,25 +386,23 @@ static int trocr_decode(mhip_trocr* m, Carver& ws, const char* enc_tokens, const
   if (m->decode_gate && (rc = mhip_gate_signal(m->decode_gate, ctx))) return rc;
   // ---- decoder state ------------------------------------------------------------------------------------------------
   const size_t hist_s = (size_t)M * 3 * D * es;              // one step of one layer: rows of q | k | v
-  char* hqkv = ws.take((size_t)L * (ML + 1) * hist_s);
-  float* x = ws.take<float>((size_t)M * D * 4);
-  char* xt = ws.take((size_t)M * D * es);
-  char* qb = ws.take((size_t)M * D * es);
-  char* ao = ws.take((size_t)M * D * es);
-  char* hid = ws.take((size_t)M * F * es);
-  char* logits = ws.take((size_t)M * ldv * 4);      // element type T: f16 logits in the f16 mode, fp32 in the parity mode
+  char* hqkv = b.hqkv;
+  float* x = b.x;
+  char* xt = b.xt;
+  char* qb = b.qb;
+  char* ao = b.ao;
+  char* hid = b.hid;
+  char* logits = b.logits;
   const int anc_ld = ML + 2;
-  int* anc[2] = {ws.take<int>((size_t)M * anc_ld * 4), ws.take<int>((size_t)M * anc_ld * 4)};
-  float* d_cs = ws.take<float>((size_t)n * K2 * 4);
-  int* d_ct = ws.take<int>((size_t)n * K2 * 4);
-  int* d_cb = ws.take<int>((size_t)n * K2 * 4);
+  int* const* anc = b.anc;
+  float* d_cs = b.cand_scores;
+  int* d_ct = b.cand_tokens;
+  int* d_cb = b.cand_beams;
+  const BeamState& bs = b.bs;
   // generator state (TextRecognitionGenerator._generate without batch compaction: finished crops keep their rows), all in HBM
-  BeamState bs;
-  if ((rc = mhip_beam_state_carve(ws.take(mhip_beam_state_bytes(n, beam, ML)), n, beam, ML, c.pad, c.eos, &bs))) return rc;
-  bs.cand_scores = d_cs; bs.cand_tokens = d_ct; bs.cand_beams = d_cb;
-  int* d_out_tok = ws.take<int>((size_t)n * (ML + 1) * 4);
-  int* d_out_len = ws.take<int>((size_t)n * 4);
-  float* d_out_score = ws.take<float>((size_t)n * 4);
+  int* d_out_tok = b.out_tok;
+  int* d_out_len = b.out_len;
+  float* d_out_score = b.out_score;
   if ((rc = mhip_launch_beam_init(ctx, bs, anc[0], anc_ld))) return rc;
   int cur = 0, tcur = 0;
   for (int step = 0; step <= ML; ++step) {
@@ -392,7 +437,7 @@ static int trocr_decode(mhip_trocr* m, Carver& ws, const char* enc_tokens, const
         CrossAbsorbDesc cd;
         cd.q = qb; cd.ldq = D; cd.E = run.tokens; cd.kv_rows = vg.npad; cd.n_keys = vg.n_tok; cd.enc_dim = E;
         cd.wkt = a.d(lay(l, "ca_kt")); cd.wv = a.d(lay(l, "ca_v") + "_w"); cd.bv = a.d<float>(lay(l, "ca_v") + "_b");
-        cd.qt = qt; cd.ct = ct; cd.ao = ao; cd.ldo = D; cd.crops = n; cd.beam = beam; cd.heads = c.dec_heads;
+        cd.qt = b.qt; cd.ct = b.ct; cd.ao = ao; cd.ldo = D; cd.crops = n; cd.beam = beam; cd.heads = c.dec_heads;
         if ((rc = mhip_launch_cross_absorbed(ctx, cd))) return rc;
       } else {
         DecAttnDesc ca;
@@ -409,7 +454,7 @@ static int trocr_decode(mhip_trocr* m, Carver& ws, const char* enc_tokens, const
     }
     if ((rc = mhip_gemm(ctx, prec, xt, a.d("out_w"), M, c.vocab, D, nullptr, nullptr, logits, ACT_NONE, 0, nullptr, ldv, 1))) return rc;
     if (step == 0 && step0_logits_host) {
-      float* stage = ws.take<float>((size_t)c.vocab * 4);
+      float* stage = b.step0_stage;
       for (int i = 0; i < n; ++i) {
         if ((rc = mhip_launch_convert_rows(ctx, prec, logits + (size_t)i * beam * ldv * es, stage, 1, c.vocab))) return rc;
         MHIP_HIP(ctx, hipMemcpyAsync(step0_logits_host + (size_t)i * c.vocab, stage, (size_t)c.vocab * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -523,12 +568,6 @@ extern "C" int mhip_trocr_generate_fragments(mhip_trocr* m, const uint8_t* base_
 // (OcrEngine's batched path: page batches leave the detector one after the other; their crops are encoded as they come — the
 // encoder's GEMMs are as efficient on 300 crops as on 3000 — while the decoder, whose 16 steps are latency-bound on small
 // batches (~5 ms per step whatever the batch), runs once.)
-static size_t trocr_decode_ws_bytes(const mhip_trocr* m, int n) {
-  VitGeom vg;
-  vit_geometry(m->vit, m->cfg.img_size, m->cfg.img_size, &vg);
-  return trocr_ws_bytes(m, n) - vit_workspace_bytes(m->vit, n, vg);
-}
-
 extern "C" int mhip_trocr_encode_begin(mhip_trocr* m, int max_crops) {
   if (!m || max_crops < 0) return MHIP_EINVAL;
   mhip_ctx* ctx = m->ctx;
@@ -586,13 +625,13 @@ extern "C" int mhip_trocr_encode_fragments(mhip_trocr* m, const uint8_t* base_de
       m->frag_scratch_bytes = scratch;
     }
   }
-  int rc = mhip_pil_resize_fragments(ctx, base_dev, descs_host, n, m->frag_crops, S, S, MHIP_PIL_BICUBIC, m->frag_scratch, m->frag_scratch_bytes);
-  if (rc) return rc;
-  if ((rc = mhip_ensure_workspace(ctx, vit_workspace_bytes(m->vit, n, vg) + (1 << 16)))) return rc;
-  Carver ws(ctx->ws);
   VitRun run;
   run.tokens_dst = m->enc_store + (size_t)m->enc_count * vg.npad * c.enc_dim * es;
-  if ((rc = vit_encode(m->vit, ws, m->frag_crops, n, S, S, S, S, swap_rb, &run))) return rc;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) { vit_carve(m->vit, ws, n, vg, &run); });
+  if (rc) return rc;
+  rc = mhip_pil_resize_fragments(ctx, base_dev, descs_host, n, m->frag_crops, S, S, MHIP_PIL_BICUBIC, m->frag_scratch, m->frag_scratch_bytes);
+  if (rc) return rc;
+  if ((rc = vit_encode(m->vit, m->frag_crops, n, S, S, S, S, swap_rb, &run))) return rc;
   m->enc_count += n;
   return MHIP_OK;
 }
@@ -605,12 +644,12 @@ extern "C" int mhip_trocr_decode(mhip_trocr* m, int32_t* tokens_out, int32_t* le
   const int n = m->enc_count;
   VitGeom vg;
   vit_geometry(m->vit, m->cfg.img_size, m->cfg.img_size, &vg);
+  TrocrDecodeBufs b;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) { trocr_decode_carve(m, ws, n, vg, false, &b); });
+  if (rc) return rc;
   // the 64 rows behind the last crop are read (masked) by its final key tiles: keep them finite
   MHIP_HIP(ctx, hipMemsetAsync(m->enc_store + (size_t)n * vg.npad * m->cfg.enc_dim * m->esz(), 0, (size_t)64 * m->cfg.enc_dim * m->esz(), ctx->stream));
-  int rc = mhip_ensure_workspace(ctx, trocr_decode_ws_bytes(m, n) + (1 << 16));
-  if (rc) return rc;
-  Carver ws(ctx->ws);
-  rc = trocr_decode(m, ws, m->enc_store, vg, n, tokens_out, lengths_out, scores_out, nullptr, nullptr);
+  rc = trocr_decode(m, b, m->enc_store, vg, n, tokens_out, lengths_out, scores_out, nullptr, nullptr);
   m->enc_count = 0;
   return rc;
 }
@@ -637,13 +676,14 @@ extern "C" int mhip_cross_attention_host(mhip_ctx* ctx, const float* q, const fl
       for (int j = 0; j < 64; ++j) hkt[((size_t)h * enc_dim + d) * 64 + j] = (_Float16)(wk[(size_t)(h * 64 + j) * enc_dim + d] * log2e);
   for (size_t i = 0; i < hwv.size(); ++i) hwv[i] = (_Float16)wv[i];
   const size_t scr = (size_t)M * 16 * enc_dim * 2;
-  size_t need = hq.size() * 2 + hE.size() * 2 + hkt.size() * 2 + hwv.size() * 2 + (size_t)D * 4 + 2 * scr + (size_t)M * D * 2 + 4096;
-  int rc = mhip_ensure_workspace(ctx, need);
+  char *dq = nullptr, *dE = nullptr, *dkt = nullptr, *dwv = nullptr, *qt = nullptr, *ct = nullptr, *ao = nullptr;
+  float* dbv = nullptr;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
+    dq = ws.take(hq.size() * 2); dE = ws.take(hE.size() * 2); dkt = ws.take(hkt.size() * 2);
+    dwv = ws.take(hwv.size() * 2); dbv = ws.take<float>((size_t)D * 4);
+    qt = ws.take(scr); ct = ws.take(scr); ao = ws.take((size_t)M * D * 2);
+  });
   if (rc) return rc;
-  Carver ws(ctx->ws);
-  char* dq = ws.take(hq.size() * 2); char* dE = ws.take(hE.size() * 2); char* dkt = ws.take(hkt.size() * 2);
-  char* dwv = ws.take(hwv.size() * 2); float* dbv = ws.take<float>((size_t)D * 4);
-  char* qt = ws.take(scr); char* ct = ws.take(scr); char* ao = ws.take((size_t)M * D * 2);
   MHIP_HIP(ctx, hipMemcpyAsync(dq, hq.data(), hq.size() * 2, hipMemcpyHostToDevice, ctx->stream));
   MHIP_HIP(ctx, hipMemcpyAsync(dE, hE.data(), hE.size() * 2, hipMemcpyHostToDevice, ctx->stream));
   MHIP_HIP(ctx, hipMemcpyAsync(dkt, hkt.data(), hkt.size() * 2, hipMemcpyHostToDevice, ctx->stream));
@@ -718,14 +758,16 @@ extern "C" int mhip_decode_attention_host(mhip_ctx* ctx, int precision, int head
     conv(v, hv, 0, (size_t)groups * kv_rows, D);
   }
   const size_t anc_bytes = self ? (size_t)rows * anc_ld * 4 : 0, out_bytes = (size_t)rows * D * es;
-  int rc = mhip_ensure_workspace(ctx, hq.size() + hk.size() + hv.size() + anc_bytes + out_bytes + 5 * 256 + 4096);
+  char *dq = nullptr, *dk = nullptr, *dv = nullptr, *dout = nullptr;
+  int* danc = nullptr;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
+    dq = ws.take(hq.size());
+    dk = ws.take(hk.size());
+    dv = self ? dk : ws.take(hv.size());
+    danc = self ? ws.take<int>(anc_bytes) : nullptr;
+    dout = ws.take(out_bytes);
+  });
   if (rc) return rc;
-  Carver ws(ctx->ws);
-  char* dq = ws.take(hq.size());
-  char* dk = ws.take(hk.size());
-  char* dv = self ? dk : ws.take(hv.size());
-  int* danc = self ? ws.take<int>(anc_bytes) : nullptr;
-  char* dout = ws.take(out_bytes);
   MHIP_HIP(ctx, hipMemcpyAsync(dq, hq.data(), hq.size(), hipMemcpyHostToDevice, ctx->stream));
   MHIP_HIP(ctx, hipMemcpyAsync(dk, hk.data(), hk.size(), hipMemcpyHostToDevice, ctx->stream));
   if (!self) MHIP_HIP(ctx, hipMemcpyAsync(dv, hv.data(), hv.size(), hipMemcpyHostToDevice, ctx->stream));

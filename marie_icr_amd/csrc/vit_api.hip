@@ -304,24 +304,28 @@ void vit_geometry(const mhip_vit* m, int H32, int W32, VitGeom* g) {
   g->npad = (g->n_tok + 7) / 8 * 8;      // 16-byte aligned V^T columns per image; tiles may run into the next image's rows
 }
 
-size_t vit_workspace_bytes(const mhip_vit* m, int B, const VitGeom& g) {
+void vit_carve(const mhip_vit* m, Carver& ws, int B, const VitGeom& g, VitRun* run) {
   const size_t es = m->esz(), D = m->cfg.dim, R = (size_t)B * g.npad;
-  size_t b = 0;
-  auto add = [&](size_t n) { b += (n + 255) / 256 * 256; };
-  add(R * D * 4);              // x
-  add(R * D * es);             // ln / attention output
-  add((R + 128) * 2 * D * es); // q | k (+ slack: the last image's final query block / key tile reads past its rows)
-  add((D * R + 128) * es);     // v^T (+ slack)
-  add(R * D * es);             // attention output
-  add(R * 4 * D * es);         // mlp hidden; also the patch matrix
-  if (m->cfg.fpn) add(4 * (size_t)B * g.np * D * es);
-  else add((R + 64) * D * es); // final tokens (+ slack rows)
-  if (m->fold) { add(D / 64 * R * 8); add(R * 4); add(R * 4); }   // row statistics per chunk, rstd, mean * rstd
-  return b;
+  run->x = ws.take(R * D * 4);                  // fp32 stream, or f16 / the two f16 planes in its bytes
+  run->ln = ws.take(R * D * es);
+  run->qk = ws.take((R + 128) * 2 * D * es);    // + slack: the last image's final query block / key tile reads past its rows
+  run->vt = ws.take((D * R + 128) * es);        // + slack, likewise
+  run->ao = ws.take(R * D * es);
+  run->hid = ws.take(R * 4 * D * es);
+  if (m->fold) {
+    run->stats = ws.take<float>(D / 64 * R * 8);
+    run->rstd = ws.take<float>(R * 4);
+    run->mur = ws.take<float>(R * 4);
+  }
+  if (m->cfg.fpn)
+    for (int j = 0; j < 4; ++j) run->tap[j] = ws.take((size_t)B * g.np * D * es);
+  // + 64 finite rows: the decoder's encoder-attention walks every image's tokens in 32-row tiles and so reads (masked) rows
+  // past the last image
+  run->tokens = nullptr;
+  if (m->cfg.final_norm) run->tokens = run->tokens_dst ? run->tokens_dst : ws.take((R + 64) * D * es);
 }
 
-int vit_encode(mhip_vit* m, Carver& ws, const uint8_t* imgs, int B, int th, int tw, int H32, int W32, int swap_rb,
-               VitRun* run) {
+int vit_encode(mhip_vit* m, const uint8_t* imgs, int B, int th, int tw, int H32, int W32, int swap_rb, VitRun* run) {
   mhip_ctx* ctx = m->ctx;
   if (!m->ready) return mhip_fail(ctx, MHIP_ESTATE, "vit: weights not finalized");
   const mhip_vit_config& c = m->cfg;
@@ -352,26 +356,22 @@ int vit_encode(mhip_vit* m, Carver& ws, const uint8_t* imgs, int B, int th, int 
     m->pos_tables.push_back({g.hp, g.wp, pos_dev, pos16});
   }
   const size_t R = (size_t)B * g.npad;
-  void* x = ws.take<float>(R * D * 4);      // fp32 stream, or f16 in the first half of it
-  char* ln = ws.take(R * D * es);
-  char* qk = ws.take((R + 128) * 2 * D * es);
-  char* vt = ws.take((D * R + 128) * es);
+  void* x = run->x;
+  char* ln = run->ln;
+  char* qk = run->qk;
+  char* vt = run->vt;
   // rows / columns past the last image are read by its final tiles (and masked): keep them finite
   MHIP_HIP(ctx, hipMemsetAsync(qk + R * 2 * D * es, 0, (size_t)128 * 2 * D * es, ctx->stream));
   MHIP_HIP(ctx, hipMemsetAsync(vt + (size_t)D * R * es, 0, 128 * es, ctx->stream));
-  char* ao = ws.take(R * D * es);
-  char* hid = ws.take(R * 4 * D * es);
-  run->x = x;
-  const bool fold = m->fold && prec == MHIP_PREC_F16 && !x16;
+  char* ao = run->ao;
+  char* hid = run->hid;
+  const bool fold = m->fold;     // implies the f16 mode without an f16 stream (mhip_vit_create)
   const int chunks = D / 64;
   char* xlo = fold ? (char*)x + R * D * 2 : nullptr;          // the split stream: two f16 planes in the bytes of the fp32 one
   run->x_lo = xlo;
-  float* stats = nullptr; float* rstd = nullptr; float* mur = nullptr;
-  if (fold) {
-    stats = ws.take<float>((size_t)chunks * R * 8);
-    rstd = ws.take<float>(R * 4);
-    mur = ws.take<float>(R * 4);
-  }
+  float* stats = run->stats;
+  float* rstd = run->rstd;
+  float* mur = run->mur;
   int rc;
   // patches -> hid (as the [B*np][768] patch matrix) -> x rows 1.. with bias + resized position table
   const int K0 = 3 * P * P;
@@ -404,7 +404,6 @@ int vit_encode(mhip_vit* m, Carver& ws, const uint8_t* imgs, int B, int th, int 
     return mhip_launch_conv_igemm(ctx, prec, c);
   };
   int tap_at = 0;
-  if (c.fpn) for (int j = 0; j < 4; ++j) run->tap[j] = ws.take((size_t)B * g.np * D * es);
   for (int i = 0; i < c.depth; ++i) {
     if (fold) {
       if ((rc = mhip_launch_ln_finalize(ctx, stats, chunks, (int)R, rstd, mur, (int)R, D, c.ln_eps))) return rc;
@@ -443,51 +442,44 @@ int vit_encode(mhip_vit* m, Carver& ws, const uint8_t* imgs, int B, int th, int 
           ++tap_at;
         }
   }
-  run->tokens = nullptr;
   if (c.final_norm) {
-    // + 64 finite rows: the decoder's encoder-attention walks every image's tokens in 32-row tiles and so reads (masked) rows
-    // past the last image
-    if (run->tokens_dst) {
-      run->tokens = run->tokens_dst;
-    } else {
-      run->tokens = ws.take((R + 64) * D * es);
-      MHIP_HIP(ctx, hipMemsetAsync(run->tokens + R * D * es, 0, (size_t)64 * D * es, ctx->stream));
-    }
+    if (!run->tokens_dst) MHIP_HIP(ctx, hipMemsetAsync(run->tokens + R * D * es, 0, (size_t)64 * D * es, ctx->stream));
     if ((rc = mhip_launch_layernorm(ctx, prec, x, a.d<float>("norm_g"), a.d<float>("norm_b"), run->tokens, (int)R, D, c.ln_eps, x16 || fold, xlo))) return rc;
   }
   (void)tap_at;
   return MHIP_OK;
 }
 
-size_t vit_fpn_workspace_bytes(const mhip_vit* m, int B, const VitGeom& g) {
+void vit_fpn_carve(const mhip_vit* m, Carver& ws, int B, const VitGeom& g, VitFpnOut* out) {
   const size_t es = m->esz(), D = m->cfg.dim, M = (size_t)B * g.np;
-  return (4 * M * D * es + 256) + (16 * M * D * es + 256) + (4 * M * D * es + 256) + (M / 4 * D * es + 256) + 4096;
+  out->t1 = ws.take(4 * M * D * es);
+  out->level[0] = ws.take(16 * M * D * es);
+  out->level[1] = ws.take(4 * M * D * es);
+  out->level[3] = ws.take((size_t)B * (g.hp / 2) * (g.wp / 2) * D * es);   // MaxPool2d(2, 2) floors odd sizes
 }
 
 // fpn1..fpn4 on the four taps.  ConvTranspose2d(2, 2) is per-pixel: a GEMM to 4*D columns whose output, read as
 // [4*rows][D], is the 2x-upsampled map in NESTED order (row = parent*4 + dy*2 + dx).  Consumers that are per-pixel
 // themselves (the FPN lateral 1x1) take it as is; mhip_launch_unnest restores raster order.
-int vit_fpn(mhip_vit* m, Carver& ws, int B, const VitRun& run, VitFpnOut* out) {
+int vit_fpn(mhip_vit* m, int B, const VitRun& run, VitFpnOut* out) {
   mhip_ctx* ctx = m->ctx;
   const int D = m->cfg.dim, prec = m->precision;
-  const size_t es = m->esz();
   const VitGeom& g = run.g;
   const long long M = (long long)B * g.np;
   const Arena& a = m->arena;
-  char* t1 = ws.take(4 * M * D * es);
-  char* o1 = ws.take(16 * M * D * es);
-  char* o2 = ws.take(4 * M * D * es);
+  char* t1 = out->t1;
+  char* o1 = out->level[0];
+  char* o2 = out->level[1];
   int rc;
   if ((rc = gemm(ctx, prec, run.tap[0], a.d("f1a_w"), M, 4 * D, D, a.d<float>("f1a_s"), a.d<float>("f1a_b"), t1, ACT_GELU, 0))) return rc;
   if ((rc = gemm(ctx, prec, t1, a.d("f1b_w"), 4 * M, 4 * D, D, a.d<float>("f1b_s"), a.d<float>("f1b_b"), o1, ACT_NONE, 0))) return rc;
   if ((rc = gemm(ctx, prec, run.tap[1], a.d("f2_w"), M, 4 * D, D, a.d<float>("f2_s"), a.d<float>("f2_b"), o2, ACT_NONE, 0))) return rc;
-  out->level[0] = o1; out->nest[0] = 2;
-  out->level[1] = o2; out->nest[1] = 1;
+  out->nest[0] = 2;
+  out->nest[1] = 1;
   out->level[2] = run.tap[2]; out->nest[2] = 0;
-  const int h4 = g.hp / 2, w4 = g.wp / 2;   // MaxPool2d(2, 2) floors odd sizes
-  char* o4 = ws.take((size_t)B * h4 * w4 * D * es);
-  if ((rc = mhip_launch_maxpool(ctx, prec, 2, run.tap[3], o4, B, g.hp, g.wp, D))) return rc;
-  out->level[3] = o4; out->nest[3] = 0;
+  const int h4 = g.hp / 2, w4 = g.wp / 2;
+  if ((rc = mhip_launch_maxpool(ctx, prec, 2, run.tap[3], out->level[3], B, g.hp, g.wp, D))) return rc;
+  out->nest[3] = 0;
   out->h[0] = 4 * g.hp; out->w[0] = 4 * g.wp;
   out->h[1] = 2 * g.hp; out->w[1] = 2 * g.wp;
   out->h[2] = g.hp; out->w[2] = g.wp;
@@ -506,15 +498,19 @@ extern "C" int mhip_vit_forward_host(mhip_vit* m, const uint8_t* imgs_host, int 
   const size_t D = m->cfg.dim;
   const size_t img_bytes = (size_t)B * th * tw * 3;
   const size_t out_f32 = m->cfg.fpn ? (size_t)B * 16 * g.np * D * 4 : (size_t)B * g.npad * D * 4;
-  const size_t need = vit_workspace_bytes(m, B, g) + (m->cfg.fpn ? vit_fpn_workspace_bytes(m, B, g) : 0) + img_bytes + out_f32 + 4096;
-  int rc = mhip_ensure_workspace(ctx, need);
-  if (rc) return rc;
-  Carver ws(ctx->ws);
-  uint8_t* imgs = ws.take<uint8_t>(img_bytes);
-  float* stage = ws.take<float>(out_f32);
-  MHIP_HIP(ctx, hipMemcpyAsync(imgs, imgs_host, img_bytes, hipMemcpyHostToDevice, ctx->stream));
+  uint8_t* imgs = nullptr;
+  float* stage = nullptr;
   VitRun run;
-  if ((rc = vit_encode(m, ws, imgs, B, th, tw, H32, W32, swap_rb, &run))) return rc;
+  VitFpnOut fo;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
+    imgs = ws.take<uint8_t>(img_bytes);
+    stage = ws.take<float>(out_f32);
+    vit_carve(m, ws, B, g, &run);
+    if (m->cfg.fpn) vit_fpn_carve(m, ws, B, g, &fo);
+  });
+  if (rc) return rc;
+  MHIP_HIP(ctx, hipMemcpyAsync(imgs, imgs_host, img_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = vit_encode(m, imgs, B, th, tw, H32, W32, swap_rb, &run))) return rc;
   if (tokens_out) {
     // final tokens (after the last norm if configured, else the residual stream), valid rows only
     for (int b = 0; b < B; ++b) {
@@ -539,8 +535,7 @@ extern "C" int mhip_vit_forward_host(mhip_vit* m, const uint8_t* imgs_host, int 
     }
   }
   if (m->cfg.fpn) {
-    VitFpnOut fo;
-    if ((rc = vit_fpn(m, ws, B, run, &fo))) return rc;
+    if ((rc = vit_fpn(m, B, run, &fo))) return rc;
     float* outs[4] = {fpn0, fpn1, fpn2, fpn3};
     for (int j = 0; j < 4; ++j) {
       if (!outs[j]) continue;

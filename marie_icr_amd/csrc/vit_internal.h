@@ -28,28 +28,39 @@ struct VitGeom {
   int npad;         // rows per image (multiple of 8)
 };
 
+// the encoder's buffers (vit_carve) and what a forward leaves in them
 struct VitRun {
   VitGeom g;
   void* x = nullptr;          // residual stream [B*npad][D]: fp32, or f16 when the model keeps an f16 stream, or (split) the high plane
   void* x_lo = nullptr;       // split stream: the low plane
+  char* ln = nullptr;         // LayerNorm output
+  char* qk = nullptr;         // q | k rows
+  char* vt = nullptr;         // V^T
+  char* ao = nullptr;         // attention output
+  char* hid = nullptr;        // mlp hidden; also the patch matrix
+  float* stats = nullptr;     // split stream: row statistics per 64-column chunk, rstd, mean * rstd
+  float* rstd = nullptr;
+  float* mur = nullptr;
   char* tap[4] = {nullptr};   // T [B*np][D] patch tokens after blocks cfg.taps[j]
   char* tokens = nullptr;     // T [B*npad][D] after the final norm (final_norm models)
-  char* tokens_dst = nullptr; // set by the caller: the final norm writes here instead of into the workspace (its own slack rows)
+  char* tokens_dst = nullptr; // set by the caller before vit_carve: the final norm writes here instead of into the workspace
+                              // (its own slack rows)
 };
 
 struct VitFpnOut {
   char* level[4];   // T, D channels: strides 4, 8, 16, 32
   int nest[4];      // 2 / 1 / 0: nested 2x2 row order depth (see vit_fpn)
   int h[4], w[4];
+  char* t1;         // scratch of fpn1
 };
 
 void vit_geometry(const mhip_vit* m, int H32, int W32, VitGeom* g);
-size_t vit_workspace_bytes(const mhip_vit* m, int B, const VitGeom& g);
-size_t vit_fpn_workspace_bytes(const mhip_vit* m, int B, const VitGeom& g);
-// imgs: B device images u8 [th][tw][3] placed on a zero canvas H32 x W32 (after normalisation)
-int vit_encode(mhip_vit* m, Carver& ws, const uint8_t* imgs, int B, int th, int tw, int H32, int W32, int swap_rb,
-               VitRun* run);
-int vit_fpn(mhip_vit* m, Carver& ws, int B, const VitRun& run, VitFpnOut* out);
+// the buffers of one forward of B images of geometry g (vit_fpn_carve: of its fpn1..fpn4)
+void vit_carve(const mhip_vit* m, Carver& ws, int B, const VitGeom& g, VitRun* run);
+void vit_fpn_carve(const mhip_vit* m, Carver& ws, int B, const VitGeom& g, VitFpnOut* out);
+// imgs: B device images u8 [th][tw][3] placed on a zero canvas H32 x W32 (after normalisation); run carved by vit_carve
+int vit_encode(mhip_vit* m, const uint8_t* imgs, int B, int th, int tw, int H32, int W32, int swap_rb, VitRun* run);
+int vit_fpn(mhip_vit* m, int B, const VitRun& run, VitFpnOut* out);
 
 int mhip_gemm(mhip_ctx* ctx, int prec, const void* in, const void* w, long long M, int N, int K, const float* scale,
               const float* bias, void* out, int act, int out_f32, const void* res = nullptr, int ldc = 0, int pad_cols_writable = 0);

@@ -153,16 +153,3 @@ inline int fold_conv_bn(mhip_ctx* ctx, const TensorStore& st, const std::string&
   }
   return MHIP_OK;
 }
-
-// bump allocator over the context workspace for one forward
-struct Carver {
-  char* base;
-  size_t off = 0;
-  explicit Carver(void* b) : base((char*)b) {}
-  template <typename P = char>
-  P* take(size_t bytes) {
-    P* p = (P*)(base + off);
-    off = (off + bytes + 255) / 256 * 256;
-    return p;
-  }
-};
