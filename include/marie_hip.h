@@ -272,6 +272,48 @@ int mhip_vit_arena(mhip_vit* m, void** arena_dev, size_t* bytes);
 int mhip_vit_forward_host(mhip_vit* m, const uint8_t* imgs_host, int B, int th, int tw, int H32, int W32, int swap_rb,
                           float* tokens_out, float* fpn0, float* fpn1, float* fpn2, float* fpn3);
 
+/* One GEMM of a ViT block in the f16 mode, alone, on device operands: the products vit_encode launches around the split residual
+ * stream (x = hi + lo, two f16 planes) with LayerNorm folded into the epilogue, through the same launcher and descriptor.
+ * replaces: the norm1 / attn.qkv / attn.proj / norm2 / mlp.fc1 / mlp.fc2 modules of a BEiT / DeiT Block and PatchEmbed.proj
+ * (marie/boxes/dit/ditod/beit.py, marie/models/unilm/trocr/deit.py), one product at a time.  For parity tests of each epilogue.
+ *   MHIP_EPI_SPLIT    out (hi), out2 (lo) [rows][N] f16 = scale[n] * in[m] . w[n] + bias[n] + res[m][n] + res2[m][n] (res == out and
+ *                     res2 == out2 allowed: in place); stats[(c * stats_ld + row) * 2] = (sum, centred sum of squares) of the row
+ *                     over columns [64 c, 64 c + 64).  row_period > 0: GEMM row q is written to row
+ *                     (q / row_period) * row_stride + row_offset + q % row_period and takes residual row q % row_period
+ *   MHIP_EPI_LN_ROWS  out [M][N] f16 = act(ln_a[m] * in[m] . w[n] - ln_b[m] * ln_cs[n] + bias[n]);  ln_a = rstd, ln_b = mean * rstd
+ *   MHIP_EPI_LN_COLS  out [M][N] f16 = ln_a[n] * in[m] . w[n] - ln_b[n] * ln_cs[m] + row_bias[m]
+ * in [M][K], w [N][K] f16; act: 0 none, 2 erf GELU.  Every pointer is a device address; unused ones are NULL.  Enqueued on the
+ * ctx stream.  Shapes and operands the kernel cannot take return MHIP_EINVAL.                                                   */
+#define MHIP_EPI_LN_ROWS 1
+#define MHIP_EPI_LN_COLS 2
+#define MHIP_EPI_SPLIT 3
+typedef struct mhip_gemm_fold_desc {
+  const void* in_dev;
+  const void* w_dev;
+  const float* scale_dev;
+  const float* bias_dev;
+  void* out_dev;
+  const float* ln_a_dev;
+  const float* ln_b_dev;
+  const float* ln_cs_dev;
+  const float* row_bias_dev;
+  void* out2_dev;
+  const void* res_dev;
+  const void* res2_dev;
+  float* stats_dev;
+  int32_t epi, M, N, K, act, stats_ld;
+  int32_t row_period, row_stride, row_offset;
+} mhip_gemm_fold_desc;
+int mhip_gemm_ln_fold(mhip_ctx* ctx, int precision, const mhip_gemm_fold_desc* d);
+/* The row statistics of MHIP_EPI_SPLIT (chunks = D / 64 of them per row, ld rows apart) -> rstd [rows] = (var + eps)^-1/2 and
+ * mur [rows] = mean * rstd.  replaces: the mean / variance pass of nn.LayerNorm (norm1, norm2 of a Block).                      */
+int mhip_ln_finalize(mhip_ctx* ctx, const float* stats_dev, int chunks, int ld, float* rstd_dev, float* mur_dev, int rows, int D,
+                     float eps);
+/* cls row (row 0) and pad rows (n_tok .. npad - 1) of each of B images of the split stream hi / lo [B * npad][D] f16, and their row
+ * statistics (cls_stats fp32 [D / 64][2], zero for the pad rows).  replaces: torch.cat((cls_tokens, x), dim=1) of the forward.    */
+int mhip_token_init_split(mhip_ctx* ctx, void* hi_dev, void* lo_dev, const float* cls_row_dev, const float* cls_stats_dev,
+                          float* stats_dev, int stats_ld, int B, int npad, int n_tok, int D);
+
 /* ---- DiT Mask R-CNN text detector (BoxProcessorUlimDit's model) ------------------------------------------------------- */
 /* replaces: OptimizedDetectronPredictor.invoke_model, marie/detectron/detector.py:83-147 (model built by
  * build_vit_fpn_backbone, marie/boxes/dit/ditod/backbone.py:131-153; config/zoo/unilm/dit/text_detection/ YAMLs).       */

@@ -127,6 +127,9 @@ _SIGNATURES = (
     ("mhip_trocr_generate_trace_host", _i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i)]),
     ("mhip_cross_attention_host", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     ("mhip_decode_attention_host", _i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    ("mhip_gemm_ln_fold", _i, [_vp, _i, _vp]),
+    ("mhip_ln_finalize", _i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, C.c_float]),
+    ("mhip_token_init_split", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     ("mhip_max_page_size", _i, [_i, _i, _i, _i, C.c_double, C.POINTER(_i), C.POINTER(_i)]),
     ("mhip_resize_area_u8", _i, [_vp, _vp, _i, _i, _i, C.c_size_t, _vp, _i, _i]),
     ("mhip_resize_area_u8_host", _i, [_vp, _vp, _i, _i, _i, _vp, _i, _i]),
@@ -158,6 +161,16 @@ class ConvDesc(C.Structure):
     """mirror of ``mhip_conv_desc`` (include/marie_hip.h)"""
     _fields_ = [(n, C.c_int32) for n in ("B", "H", "W", "Cin", "KH", "KW", "pad", "N", "pool", "relu", "out_f32",
                                          "dil", "Cin1", "ldc", "pad_cols_writable")]
+
+
+EPI_LN_ROWS, EPI_LN_COLS, EPI_SPLIT = 1, 2, 3
+
+
+class GemmFoldDesc(C.Structure):
+    """mirror of ``mhip_gemm_fold_desc`` (include/marie_hip.h); the pointers are HBM addresses"""
+    _fields_ = ([(n, C.c_void_p) for n in ("in_dev", "w_dev", "scale_dev", "bias_dev", "out_dev", "ln_a_dev", "ln_b_dev",
+                                           "ln_cs_dev", "row_bias_dev", "out2_dev", "res_dev", "res2_dev", "stats_dev")] +
+                [(n, C.c_int32) for n in ("epi", "M", "N", "K", "act", "stats_ld", "row_period", "row_stride", "row_offset")])
 
 
 class VitConfig(C.Structure):
@@ -281,6 +294,22 @@ class Context:
                                                 C.c_void_p(in2_ptr or 0), C.c_void_p(w_ptr), C.c_void_p(scale_ptr or 0),
                                                 C.c_void_p(bias_ptr or 0), C.c_void_p(out_ptr)),
               "mhip_conv2d_nhwc")
+
+    def gemm_ln_fold(self, precision: int, desc: "GemmFoldDesc"):
+        """Enqueue one LayerNorm-folded GEMM of a ViT block (EPI_SPLIT / EPI_LN_ROWS / EPI_LN_COLS) on the ctx stream."""
+        check(self.h, self.lib.mhip_gemm_ln_fold(self.h, int(precision), C.byref(desc)), "mhip_gemm_ln_fold")
+
+    def ln_finalize(self, stats_ptr: int, chunks: int, ld: int, rstd_ptr: int, mur_ptr: int, rows: int, D: int, eps: float):
+        """Enqueue the merge of EPI_SPLIT's row statistics into rstd and mean * rstd."""
+        check(self.h, self.lib.mhip_ln_finalize(self.h, C.c_void_p(stats_ptr), int(chunks), int(ld), C.c_void_p(rstd_ptr),
+                                                C.c_void_p(mur_ptr), int(rows), int(D), float(eps)), "mhip_ln_finalize")
+
+    def token_init_split(self, hi_ptr: int, lo_ptr: int, cls_row_ptr: int, cls_stats_ptr: int, stats_ptr: int, stats_ld: int,
+                         B: int, npad: int, n_tok: int, D: int):
+        """Enqueue the cls / pad rows of the split stream and their row statistics."""
+        check(self.h, self.lib.mhip_token_init_split(self.h, C.c_void_p(hi_ptr), C.c_void_p(lo_ptr), C.c_void_p(cls_row_ptr),
+                                                     C.c_void_p(cls_stats_ptr), C.c_void_p(stats_ptr), int(stats_ld), int(B),
+                                                     int(npad), int(n_tok), int(D)), "mhip_token_init_split")
 
     def profile_enable(self, on: bool):
         check(self.h, self.lib.mhip_profile_enable(self.h, 1 if on else 0), "mhip_profile_enable")

@@ -547,3 +547,30 @@ extern "C" int mhip_vit_forward_host(mhip_vit* m, const uint8_t* imgs_host, int 
   MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return MHIP_OK;
 }
+
+// ======================================================================= single stages of the f16 block, for parity tests
+extern "C" int mhip_gemm_ln_fold(mhip_ctx* ctx, int precision, const mhip_gemm_fold_desc* d) {
+  if (!ctx || !d) return MHIP_EINVAL;
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  ConvDesc c;      // filled as produce / consume_rows / cv of vit_encode fill theirs
+  c.in = d->in_dev; c.w = d->w_dev; c.scale = d->scale_dev; c.bias = d->bias_dev; c.out = d->out_dev;
+  c.B = 1; c.H = 1; c.W = d->M; c.Cin = d->K; c.N = d->N; c.relu = d->act;
+  c.epi = d->epi; c.ln_a = d->ln_a_dev; c.ln_b = d->ln_b_dev; c.ln_cs = d->ln_cs_dev; c.row_bias = d->row_bias_dev;
+  c.out2 = d->out2_dev; c.res = d->res_dev; c.res2 = d->res2_dev; c.stats = d->stats_dev; c.stats_ld = d->stats_ld;
+  c.row_period = d->row_period; c.row_stride = d->row_stride; c.row_offset = d->row_offset;
+  return mhip_launch_conv_igemm(ctx, precision, c);
+}
+
+extern "C" int mhip_ln_finalize(mhip_ctx* ctx, const float* stats, int chunks, int ld, float* rstd, float* mur, int rows, int D,
+                                float eps) {
+  if (!ctx) return MHIP_EINVAL;
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  return mhip_launch_ln_finalize(ctx, stats, chunks, ld, rstd, mur, rows, D, eps);
+}
+
+extern "C" int mhip_token_init_split(mhip_ctx* ctx, void* hi, void* lo, const float* cls_row, const float* cls_stats, float* stats,
+                                     int stats_ld, int B, int npad, int n_tok, int D) {
+  if (!ctx) return MHIP_EINVAL;
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  return mhip_launch_token_init_split(ctx, hi, lo, cls_row, cls_stats, stats, stats_ld, B, npad, n_tok, D);
+}

@@ -10,7 +10,7 @@ Bars (written next to each assertion):
         within 2e-3 px, scores exact / 1e-6); end to end every box the interval analysis (oracle/dit_trace.py) marks KEPT has
         a partner at IoU >= 0.999 (boxes of a few pixels, whose IoU moves by 0.3 % under a 0.004 px shift: every coordinate
         within the measured error, < 0.01 px) and every extra / missing box is a proven near-tie; TrOCR tokens exact, score
-        within 1e-3.  Measured (profiles/r02/a_fullsize_parity.json): 911 / 911 boxes, 0 unstable, max |d coordinate| 0.004 px.
+        within 1e-3.  Measured (profiles/r03/b_fullsize_parity.json): 911 / 911 boxes, 876 KEPT and all matched, max |d coordinate| 0.004 px.
   f16   (the bench dtype) maps within 0.5 % of range; the same interval analysis with f16's measured error: every KEPT box
         matched, every f16 box a KEPT or UNSTABLE candidate, matched pairs within the predicted coordinate error; box-set match
         fractions reported and bounded; TrOCR: every divergence of the beam search a proven near-tie (40 lines), and on the
@@ -29,12 +29,13 @@ PAGE_H, PAGE_W, LINES = 3300, 2550, 40
 REPORT = {}
 
 
-def _report(key, val):
-    REPORT[key] = val
+def _report(key, val, report=REPORT, name="fullsize_parity.json"):
+    """also the writer of the other parity reports (tests/test_gemm_fold_gpu.py): `report` into the file `name`"""
+    report[key] = val
     d = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
     if os.path.isdir(d):
-        with open(os.path.join(d, "fullsize_parity.json"), "w") as f:
-            json.dump(REPORT, f, indent=1, default=float)
+        with open(os.path.join(d, name), "w") as f:
+            json.dump(report, f, indent=1, default=float)
 
 
 @pytest.fixture(scope="module")

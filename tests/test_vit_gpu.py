@@ -1,5 +1,7 @@
 """GPU parity of the ViT encoder stack (LayerNorm, MFMA attention, GEMM epilogues, patch embed, fpn heads) through the
-C ABI: fp32 mode against goldens from the reference's beit.py; f16 (production) mode against the oracle."""
+C ABI: fp32 mode against goldens from the reference's beit.py; f16 (production) mode against the oracle.  These are end-to-end
+bars over whole stacks; the parity of each LayerNorm-folded GEMM epilogue of the f16 mode, element by element, lives in
+tests/test_gemm_fold_gpu.py."""
 import os
 
 import numpy as np
