@@ -126,6 +126,8 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--boundary", choices=("absolute", "fit_to_page"), default=None,
                     help="document boundary registration of the frames before the engine, as ExtractPipeline does")
+    ap.add_argument("--classifier", default=None, metavar="DIR",
+                    help="classify every page with the LayoutLMv3 checkpoint in DIR (config.json, weights, vocab.json, merges.txt)")
     args = ap.parse_args(argv)
 
     from marie_icr_amd.box_processor import PSMode
@@ -146,6 +148,15 @@ def main(argv=None):
     for sub, renderer in (("blobs", BlobRenderer()), ("adlib", AdlibRenderer())):
         os.makedirs(os.path.join(args.out, sub), exist_ok=True)
         renderer.render(frames, results, os.path.join(args.out, sub))
+    if args.classifier:
+        from marie_icr_amd.document_classifier import TransformersDocumentClassifier
+        from marie_icr_amd.renderer import get_words_and_boxes
+
+        wb = [get_words_and_boxes(results, i) for i in range(len(frames))]
+        classes = TransformersDocumentClassifier(args.classifier, precision=args.precision).predict(
+            frames, [w for w, _ in wb], [b for _, b in wb])
+        with open(os.path.join(args.out, "classification.json"), "w", encoding="utf-8") as f:
+            json.dump(classes, f)
     words = sum(len(r["words"]) for r in results)
     print(json.dumps({"pages": len(frames), "words": words, "seconds": round(dt, 3), "pages_per_s": round(len(frames) / dt, 2),
                       "out": args.out}))

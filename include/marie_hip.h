@@ -517,6 +517,63 @@ int mhip_decode_attention_host(mhip_ctx* ctx, int precision, int heads, int n_ke
                                const float* q, const float* k, const float* v, const int32_t* anc, int anc_ld,
                                int force_generic, float* out);
 
+/* ---- LayoutLMv3 page classifier (OCR words + boxes + page image -> class logits) ------------------------------------------ */
+/* replaces: the model path of TransformersDocumentClassifier with task="text-classification-multimodal",
+ * marie/components/document_classifier/transformers.py (LayoutLMv3ForSequenceClassification of the transformers library:
+ * text + layout embeddings, 16 x 16 patch embeddings of the page resized to input_size, twelve post-LN layers whose attention
+ * carries a learned relative-position bias (1-d bucket of the token index, 2-d buckets of x0 and y1) and a padding mask, and
+ * the classification head on row 0).                                                                                        */
+typedef struct mhip_layoutlmv3 mhip_layoutlmv3;
+typedef struct mhip_layoutlmv3_config {
+  int hidden, layers, heads, ffn;                 /* 768 / 12 / 12 / 3072                                                    */
+  int vocab, type_vocab;                          /* 50265 / 1                                                               */
+  int max_position_embeddings;                    /* 514: position ids of max_text unpadded tokens reach pad + max_text      */
+  int max_2d_position_embeddings;                 /* 1024                                                                    */
+  int coordinate_size, shape_size;                /* 128 / 128: 4 * coordinate_size + 2 * shape_size == hidden               */
+  int input_size, patch;                          /* 224 / 16                                                                */
+  int rel_pos_bins, max_rel_pos;                  /* 32 / 128                                                                */
+  int rel_2d_pos_bins, max_rel_2d_pos;            /* 64 / 256                                                                */
+  float layer_norm_eps;                           /* 1e-5 (the visual `norm` keeps the library's fixed 1e-6)                 */
+  int pad_id;                                     /* 1                                                                       */
+  int num_labels;
+  int max_text;                                   /* text rows per page (512)                                                */
+} mhip_layoutlmv3_config;
+int mhip_layoutlmv3_default_config(mhip_layoutlmv3_config* cfg);
+/* MHIP_EINVAL for what the kernels do not cover: hidden != heads * 64, hidden % 256, hidden > 1024, ffn % 64, patch != 16,
+ * input_size % 16, 4 * coordinate_size + 2 * shape_size != hidden, max_2d_position_embeddings > 1024, max_text > 1024 or
+ * max_text % 8, max_position_embeddings < max_text + pad_id + 1, odd bucket counts.                                        */
+int mhip_layoutlmv3_create(mhip_ctx* ctx, int precision, const mhip_layoutlmv3_config* cfg, mhip_layoutlmv3** out);
+int mhip_layoutlmv3_destroy(mhip_layoutlmv3* m);
+/* Hugging Face state-dict keys: "layoutlmv3.embeddings.word_embeddings.weight" ... "classifier.out_proj.bias"              */
+int mhip_layoutlmv3_set_tensor(mhip_layoutlmv3* m, const char* key, const float* data, const int64_t* shape, int ndim);
+int mhip_layoutlmv3_finalize(mhip_layoutlmv3* m);
+int mhip_layoutlmv3_alloc_arena(mhip_layoutlmv3* m);
+int mhip_layoutlmv3_arena(mhip_layoutlmv3* m, void** arena_dev, size_t* bytes);
+/* rows per page of the hidden states: max_text + (input_size / patch)^2 + 1 (709)                                          */
+int mhip_layoutlmv3_seq_len(const mhip_layoutlmv3_config* cfg);
+/* LayoutLMv3Encoder.relative_position_bucket (bidirectional) of one difference, evaluated in float32 as the library does.
+ * Host only, no ctx: the attention tables are folded from it at finalize.                                                  */
+int mhip_layoutlmv3_bucket(int relative_position, int num_buckets, int max_distance);
+/* n pages (3-channel u8 fragments of any size inside one device buffer, channel order as stored) with their token ids
+ * [n][max_text], boxes [n][max_text][4] on the 0..1000 grid and attention mask [n][max_text] (host int32 arrays)
+ * -> logits_out fp32 [n][num_labels] (host).  One call runs all n pages through one launch sequence.  A box coordinate
+ * outside [0, max_2d_position_embeddings) or an id outside the vocabulary is MHIP_EINVAL.                                  */
+int mhip_layoutlmv3_classify(mhip_layoutlmv3* m, const uint8_t* base_dev, const mhip_crop_desc* pages_host, int n,
+                             const int32_t* ids, const int32_t* bbox, const int32_t* attention_mask, float* logits_out);
+/* the same on one packed host buffer of pages; optional parity taps: hidden_out fp32 [n][seq_len][hidden] (the last hidden
+ * states, all rows: padded text rows hold what the library computes for them), resized_out u8 [n][input_size][input_size][3] */
+int mhip_layoutlmv3_hidden_host(mhip_layoutlmv3* m, const uint8_t* pages_host, size_t pages_bytes,
+                                const mhip_crop_desc* pages_desc, int n, const int32_t* ids, const int32_t* bbox,
+                                const int32_t* attention_mask, float* logits_out, float* hidden_out, uint8_t* resized_out);
+/* The biased attention kernel alone on host inputs (parity tests): softmax(q k^T / 8 + (B1[h][b(pj - pi)] + Bx[h][b(xj - xi)]
+ * + By[h][b(yj - yi)]) / 8 + mask) v for `heads` heads of 64.  q, k, v fp32 [n_tok][heads*64] (rounded to the precision's
+ * element type), pos / x / y int32 [n_tok], valid int32 [n_tok] (0: masked as a key), w1 [heads][bins_1d], wx / wy
+ * [heads][bins_2d] -> out fp32 [n_tok][heads*64].                                                                          */
+int mhip_attention_bias_host(mhip_ctx* ctx, int precision, int heads, int n_tok, const float* q, const float* k,
+                             const float* v, const int32_t* pos, const int32_t* x, const int32_t* y, const int32_t* valid,
+                             const float* w1, const float* wx, const float* wy, int bins_1d, int max_1d, int bins_2d,
+                             int max_2d, float* out);
+
 /* ---- word-box / line geometry of the DiT box processor (host, pure functions; no ctx) --------------------------------- */
 /* replaces: merge_boxes, marie/utils/overlap.py:268-330 (find_overlap_horizontal(center_y_overlap=0.5) :106-183,
  * merge_bboxes_as_block :186-204).  xyxy fp32 [n][4] -> out_xyxy fp32 (capacity n rows), *n_out rows.       */

@@ -130,6 +130,18 @@ _SIGNATURES = (
     ("mhip_gemm_ln_fold", _i, [_vp, _i, _vp]),
     ("mhip_ln_finalize", _i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, C.c_float]),
     ("mhip_token_init_split", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    ("mhip_layoutlmv3_default_config", _i, [_vp]),
+    ("mhip_layoutlmv3_create", _i, [_vp, _i, _vp, C.POINTER(_vp)]),
+    ("mhip_layoutlmv3_destroy", _i, [_vp]),
+    ("mhip_layoutlmv3_set_tensor", _i, [_vp, C.c_char_p, _vp, C.POINTER(C.c_int64), _i]),
+    ("mhip_layoutlmv3_finalize", _i, [_vp]),
+    ("mhip_layoutlmv3_alloc_arena", _i, [_vp]),
+    ("mhip_layoutlmv3_arena", _i, [_vp, C.POINTER(_vp), C.POINTER(_sz)]),
+    ("mhip_layoutlmv3_seq_len", _i, [_vp]),
+    ("mhip_layoutlmv3_bucket", _i, [_i, _i, _i]),
+    ("mhip_layoutlmv3_classify", _i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    ("mhip_layoutlmv3_hidden_host", _i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("mhip_attention_bias_host", _i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     ("mhip_max_page_size", _i, [_i, _i, _i, _i, C.c_double, C.POINTER(_i), C.POINTER(_i)]),
     ("mhip_resize_area_u8", _i, [_vp, _vp, _i, _i, _i, C.c_size_t, _vp, _i, _i]),
     ("mhip_resize_area_u8_host", _i, [_vp, _vp, _i, _i, _i, _vp, _i, _i]),
@@ -202,6 +214,16 @@ class TrocrConfig(C.Structure):
                 ("dec_layers", C.c_int), ("dec_heads", C.c_int), ("dec_ffn", C.c_int), ("vocab", C.c_int),
                 ("max_positions", C.c_int), ("beam", C.c_int), ("max_len_b", C.c_int), ("min_len", C.c_int),
                 ("pad", C.c_int), ("eos", C.c_int), ("embed_scale", C.c_float), ("img_size", C.c_int)]
+
+
+class LayoutLMv3Config(C.Structure):
+    """mirror of mhip_layoutlmv3_config (include/marie_hip.h)"""
+    _fields_ = [("hidden", C.c_int), ("layers", C.c_int), ("heads", C.c_int), ("ffn", C.c_int), ("vocab", C.c_int),
+                ("type_vocab", C.c_int), ("max_position_embeddings", C.c_int), ("max_2d_position_embeddings", C.c_int),
+                ("coordinate_size", C.c_int), ("shape_size", C.c_int), ("input_size", C.c_int), ("patch", C.c_int),
+                ("rel_pos_bins", C.c_int), ("max_rel_pos", C.c_int), ("rel_2d_pos_bins", C.c_int),
+                ("max_rel_2d_pos", C.c_int), ("layer_norm_eps", C.c_float), ("pad_id", C.c_int), ("num_labels", C.c_int),
+                ("max_text", C.c_int)]
 
 
 class CropDesc(C.Structure):

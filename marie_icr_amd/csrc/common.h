@@ -33,7 +33,8 @@ enum MhipKernelId {
   MHIP_K_IGEMM_S128 = 15,   // conv_igemm_kernel<.., 1128, ..> 128 x 128 tile (few-row GEMMs)
   MHIP_K_IGEMM_PATCH = 16,  // conv3x3_patch_kernel            3x3 / pad 1 convolutions
   MHIP_K_CROSS_ATTN = 17,   // decoder encoder-attention over the encoder tokens themselves (absorbed K / V projections)
-  MHIP_K_COUNT = 18
+  MHIP_K_ATTN_BIAS = 18,    // attn_bias_f16_kernel / attn_bias_simple_f32_kernel: attention with a relative-position bias and a key mask
+  MHIP_K_COUNT = 19
 };
 
 constexpr int MHIP_ZERO_BYTES = 65536;
@@ -444,6 +445,43 @@ int mhip_launch_beam_init(mhip_ctx* ctx, const BeamState& st, int* anc0, int anc
 int mhip_launch_beam_select(mhip_ctx* ctx, const BeamState& st, int cur, int step);
 // best hypothesis per crop -> tokens_out [bsz][max_len + 1] (padded), lengths_out [bsz], scores_out [bsz] (device arrays)
 int mhip_launch_beam_best(mhip_ctx* ctx, const BeamState& st, int* tokens_out, int* lengths_out, float* scores_out);
+// ------------------------------------------------------------------ LayoutLMv3 ops (layoutlmv3_ops.hip)
+// Attention with a learned relative-position bias and a key mask.  Every token carries a code p | x << 12 | y << 22 (p: 1-d
+// position, x: x0, y: y1 of its box); a score takes tab[h][kp + dp - qp] + tab[h][off_x + kx + dx - qx] + tab[h][off_y + ky + dx - qy]
+// (already scaled as the pre-scaled q is).  A masked key carries p = 2 dp + 1 in kcode: entries [2 dp + 1, 3 dp + 1] of the 1-d
+// table hold MHIP_ATTN_MASKED, so the mask costs no instruction of its own.
+constexpr float MHIP_ATTN_MASKED = -1024.f;    // log2 units: exp2 of it is 0 in fp32 beside any score a LayerNormed model produces
+struct AttnBiasDesc {
+  AttnDesc a;
+  const uint32_t* qcode = nullptr;   // [images*npad_q (+ 128 of slack)]
+  const uint32_t* kcode = nullptr;   // [images*npad_k (+ 128 of slack)]
+  const float* tab = nullptr;        // [heads][mhip_attn_bias_table_len(dp, dx)] fp32
+  int dp = 0, dx = 0;                // largest |p_j - p_i| (<= 1023) and |x_j - x_i|, |y_j - y_i| (<= 1023)
+};
+inline int mhip_attn_bias_table_len(int dp, int dx) { return 3 * dp + 2 + 2 * (2 * dx + 1); }
+int mhip_launch_attention_bias(mhip_ctx* ctx, int precision, const AttnBiasDesc& d);
+// tab[h] from the three head-major bias matrices (w1 [heads][bins_1d], wx / wy [heads][bins_2d]), scaled by `scale`
+void mhip_attn_bias_fold(const float* w1, const float* wx, const float* wy, int heads, int bins_1d, int max_1d, int bins_2d,
+                         int max_2d, int dp, int dx, float scale, float* tab);
+int mhip_relative_position_bucket(int relative_position, int num_buckets, int max_distance);
+struct Lmv3EmbedDesc {
+  const int* tok = nullptr;          // [pages*max_text][8]: id, position id, x0, y0, x1, y1, h, w (clipped)
+  const void* word = nullptr;        // [vocab][D] T
+  const float *type0 = nullptr, *pos = nullptr, *xe = nullptr, *ye = nullptr, *he = nullptr, *we = nullptr;
+  const float *g_text = nullptr, *b_text = nullptr;      // embeddings.LayerNorm
+  const float* patches = nullptr;    // [pages*(n_vis - 1)][D] fp32: patch projection + bias + position rows 1..
+  const float* cls = nullptr;        // [D]: cls_token + position row 0
+  const float *g_vis = nullptr, *b_vis = nullptr;        // norm (eps_vis)
+  const float *g_all = nullptr, *b_all = nullptr;        // LayoutLMv3Model.LayerNorm
+  float* h = nullptr;                // [pages*npad][D] fp32
+  void* ht = nullptr;                // the same rows as T
+  int pages = 0, max_text = 0, n_vis = 0, npad = 0, D = 0, coord = 0, shape = 0;
+  float eps = 1e-5f, eps_vis = 1e-6f;
+};
+int mhip_launch_lmv3_embed(mhip_ctx* ctx, int precision, const Lmv3EmbedDesc& d);
+// logits[page] = out_proj(tanh(dense(h[page*npad]))), fp32 weights
+int mhip_launch_lmv3_head(mhip_ctx* ctx, const float* h, int pages, int npad, int D, const float* dw, const float* db,
+                          const float* ow, const float* ob, int labels, float* logits);
 size_t mhip_pil_resize_fragments_scratch(const mhip_crop_desc* descs, int n, int dh, int dw, int filter);
 int mhip_pil_resize_fragments(mhip_ctx* ctx, const uint8_t* base_dev, const mhip_crop_desc* descs, int n, uint8_t* dst, int dh,
                               int dw, int filter, void* scratch, size_t scratch_bytes);

@@ -1,0 +1,523 @@
+// layoutlmv3_api.hip — the LayoutLMv3 page classifier behind the C ABI.
+//
+// Host-side counterpart of LayoutLMv3ForSequenceClassification.forward (transformers/models/layoutlmv3/modeling_layoutlmv3.py:
+// LayoutLMv3Model.forward, LayoutLMv3Encoder.forward, LayoutLMv3Layer, LayoutLMv3ClassificationHead) as
+// TransformersDocumentClassifier drives it (marie/components/document_classifier/transformers.py, task
+// "text-classification-multimodal").  One object = one weight arena + the launch sequence.
+//
+// Row layout: every page owns `npad` rows (seq_len rounded up to 8): max_text text rows, then cls + patches, then zeros.
+// Padded text rows stay in the sequence and are masked as keys, as the library does.
+// The hidden states h are fp32 (every LayerNorm writes them, and their copy in the GEMM element type); a post-LN layer is
+//   q|k = ht Wqk^T + b        V^T = Wv ht^T            (the value bias moves into the output projection: soft-max rows sum to 1)
+//   ao = attention_bias(q, k, V^T)     y = ao Wo^T + (bo + Wo bv) + h     h, ht = LN(y)
+//   hid = gelu(ht Wi^T + bi)           y = hid Wd^T + bd + h              h, ht = LN(y)
+#include <math.h>
+
+#include "vit_internal.h"
+
+struct mhip_layoutlmv3 {
+  mhip_ctx* ctx = nullptr;
+  int precision = MHIP_PREC_F16;
+  mhip_layoutlmv3_config cfg{};
+  TensorStore store;
+  Arena arena;
+  bool ready = false;
+  size_t esz() const { return precision == MHIP_PREC_F16 ? 2 : 4; }
+  int grid() const { return cfg.input_size / cfg.patch; }
+  int n_vis() const { return grid() * grid() + 1; }
+  int seq() const { return cfg.max_text + n_vis(); }
+  int npad() const { return (seq() + 7) / 8 * 8; }
+  int dp() const { return std::max(cfg.max_text, n_vis()) - 1; }
+  int dx() const { return cfg.max_2d_position_embeddings - 1; }
+};
+
+namespace {
+
+constexpr float LOG2E = 1.4426950408889634f;
+const char* PFX = "layoutlmv3.";
+
+std::string lyr(int i, const char* s) { return "layoutlmv3.encoder.layer." + std::to_string(i) + "." + s; }
+std::string blk(int i, const char* s) { return "l" + std::to_string(i) + "." + s; }
+
+// the buffers of one call of n pages
+struct Lmv3Run {
+  uint8_t* resized = nullptr;
+  void* frag_scratch = nullptr;
+  size_t frag_bytes = 0;
+  int* tok = nullptr;
+  uint32_t *qcode = nullptr, *kcode = nullptr;
+  float *pe = nullptr, *h = nullptr, *y = nullptr, *logits = nullptr;
+  char *ht = nullptr, *qk = nullptr, *vt = nullptr, *ao = nullptr, *hid = nullptr;
+};
+
+void lmv3_carve(const mhip_layoutlmv3* m, Carver& ws, const mhip_crop_desc* pages, int n, Lmv3Run* r) {
+  const mhip_layoutlmv3_config& c = m->cfg;
+  const size_t es = m->esz(), D = c.hidden, R = (size_t)n * m->npad(), S = c.input_size;
+  r->resized = ws.take<uint8_t>((size_t)n * S * S * 3);
+  r->frag_bytes = mhip_pil_resize_fragments_scratch(pages, n, c.input_size, c.input_size, MHIP_PIL_BILINEAR);
+  r->frag_scratch = ws.take(r->frag_bytes);
+  r->tok = ws.take<int>((size_t)n * c.max_text * 8 * 4);
+  r->qcode = ws.take<uint32_t>((R + 128) * 4);     // + slack: the last page's final query block / key tile reads past its rows
+  r->kcode = ws.take<uint32_t>((R + 128) * 4);
+  r->pe = ws.take<float>((size_t)n * (m->n_vis() - 1) * D * 4);
+  r->h = ws.take<float>(R * D * 4);
+  r->y = ws.take<float>(R * D * 4);
+  r->logits = ws.take<float>((size_t)n * c.num_labels * 4);
+  r->ht = ws.take(R * D * es);
+  r->qk = ws.take((R + 128) * 2 * D * es);
+  r->vt = ws.take((D * R + 128) * es);
+  r->ao = ws.take(R * D * es);
+  r->hid = ws.take(R * std::max<size_t>(c.ffn, 3 * c.patch * c.patch) * es);     // mlp hidden; also the patch matrix
+}
+
+// token ids / boxes / mask of n pages -> the embedding kernel's gather rows and the attention codes (host)
+int lmv3_prepare(mhip_layoutlmv3* m, int n, const int32_t* ids, const int32_t* bbox, const int32_t* mask, std::vector<int>& tok,
+                 std::vector<uint32_t>& qcode, std::vector<uint32_t>& kcode) {
+  const mhip_layoutlmv3_config& c = m->cfg;
+  const int T = c.max_text, NP = m->npad(), G = m->grid(), NV = m->n_vis(), M2 = c.max_2d_position_embeddings;
+  const uint32_t masked = (uint32_t)(2 * m->dp() + 1);
+  tok.assign((size_t)n * T * 8, 0);
+  qcode.assign((size_t)n * NP + 128, 0);
+  kcode.assign((size_t)n * NP + 128, masked);
+  for (int p = 0; p < n; ++p) {
+    int seen = 0;
+    for (int t = 0; t < T; ++t) {
+      const size_t e = (size_t)p * T + t;
+      const int id = ids[e];
+      const int32_t* b = bbox + e * 4;
+      if (id < 0 || id >= c.vocab) return mhip_fail(m->ctx, MHIP_EINVAL, "layoutlmv3: token id %d outside the vocabulary (page %d, token %d)", id, p, t);
+      for (int j = 0; j < 4; ++j)
+        if (b[j] < 0 || b[j] >= M2)
+          return mhip_fail(m->ctx, MHIP_EINVAL, "layoutlmv3: box coordinate %d outside [0, %d) (page %d, token %d)", b[j], M2, p, t);
+      int pid = c.pad_id;
+      if (id != c.pad_id) pid += ++seen;
+      if (pid >= c.max_position_embeddings) return mhip_fail(m->ctx, MHIP_EINVAL, "layoutlmv3: position id %d beyond the table", pid);
+      int* tk = &tok[e * 8];
+      tk[0] = id; tk[1] = pid; tk[2] = b[0]; tk[3] = b[1]; tk[4] = b[2]; tk[5] = b[3];
+      tk[6] = std::min(std::max(b[3] - b[1], 0), M2 - 1);
+      tk[7] = std::min(std::max(b[2] - b[0], 0), M2 - 1);
+      const uint32_t xy = ((uint32_t)b[0] << 12) | ((uint32_t)b[3] << 22);
+      qcode[(size_t)p * NP + t] = (uint32_t)t | xy;
+      kcode[(size_t)p * NP + t] = (mask[e] ? (uint32_t)t : masked) | xy;
+    }
+    // LayoutLMv3Model.create_visual_bbox: cls box [1, 1, 999, 999], then the G x G grid on 0..1000 (x0, y1 matter here)
+    for (int v = 0; v < NV; ++v) {
+      int x0 = 1, y1 = 999;
+      if (v > 0) { x0 = 1000 * ((v - 1) % G) / G; y1 = 1000 * ((v - 1) / G + 1) / G; }
+      const uint32_t code = (uint32_t)v | ((uint32_t)x0 << 12) | ((uint32_t)y1 << 22);
+      qcode[(size_t)p * NP + T + v] = code;
+      kcode[(size_t)p * NP + T + v] = code;
+    }
+  }
+  return MHIP_OK;
+}
+
+// pages already resized in run.resized; codes staged -> hidden states in run.h / run.ht and logits in run.logits
+int lmv3_forward(mhip_layoutlmv3* m, int n, const Lmv3Run& run) {
+  mhip_ctx* ctx = m->ctx;
+  const mhip_layoutlmv3_config& c = m->cfg;
+  const int D = c.hidden, F = c.ffn, prec = m->precision, NP = m->npad(), G = m->grid(), P = c.patch, S = c.input_size;
+  const size_t es = m->esz(), R = (size_t)n * NP;
+  const Arena& a = m->arena;
+  int rc;
+  // rows / columns past the last page are read by its final tiles (and masked): keep them finite
+  MHIP_HIP(ctx, hipMemsetAsync(run.qk + R * 2 * D * es, 0, (size_t)128 * 2 * D * es, ctx->stream));
+  MHIP_HIP(ctx, hipMemsetAsync(run.vt + (size_t)D * R * es, 0, 128 * es, ctx->stream));
+  // (x / 255 - 0.5) / 0.5 -> 16 x 16 patches -> projection + bias + position rows 1.. (row q takes position row q % G^2)
+  const int K0 = 3 * P * P, np = G * G;
+  if ((rc = mhip_launch_patchify(ctx, prec, run.resized, n, S, S, G, G, P, 0, 127.5f, 127.5f, run.hid, K0))) return rc;
+  {
+    ConvDesc cd;
+    cd.in = run.hid; cd.w = a.d("pe_w"); cd.bias = a.d<float>("pe_b"); cd.out = run.pe; cd.res = a.d<float>("pos_vis");
+    cd.B = 1; cd.H = 1; cd.W = n * np; cd.Cin = K0; cd.N = D; cd.out_f32 = 1;
+    cd.row_period = np; cd.row_stride = np; cd.row_offset = 0;
+    if ((rc = mhip_launch_conv_igemm(ctx, prec, cd))) return rc;
+  }
+  Lmv3EmbedDesc e;
+  e.tok = run.tok; e.word = a.d("word"); e.type0 = a.d<float>("type0"); e.pos = a.d<float>("pos");
+  e.xe = a.d<float>("xe"); e.ye = a.d<float>("ye"); e.he = a.d<float>("he"); e.we = a.d<float>("we");
+  e.g_text = a.d<float>("ln_text_g"); e.b_text = a.d<float>("ln_text_b");
+  e.patches = run.pe; e.cls = a.d<float>("cls");
+  e.g_vis = a.d<float>("ln_vis_g"); e.b_vis = a.d<float>("ln_vis_b");
+  e.g_all = a.d<float>("ln_all_g"); e.b_all = a.d<float>("ln_all_b");
+  e.h = run.h; e.ht = run.ht;
+  e.pages = n; e.max_text = c.max_text; e.n_vis = m->n_vis(); e.npad = NP; e.D = D; e.coord = c.coordinate_size; e.shape = c.shape_size;
+  e.eps = c.layer_norm_eps; e.eps_vis = 1e-6f;      // LayoutLMv3Model.norm = nn.LayerNorm(hidden, eps=1e-6)
+  if ((rc = mhip_launch_lmv3_embed(ctx, prec, e))) return rc;
+
+  AttnBiasDesc ad;
+  ad.a.q = run.qk; ad.a.k = run.qk + (size_t)D * es; ad.a.vt = run.vt; ad.a.out = run.ao;
+  ad.a.ldq = ad.a.ldk = 2 * D; ad.a.ldv = (int)R; ad.a.ldo = D;
+  ad.a.images = n; ad.a.heads = c.heads; ad.a.npad_q = ad.a.npad_k = NP; ad.a.n_queries = ad.a.n_keys = m->seq();
+  ad.qcode = run.qcode; ad.kcode = run.kcode; ad.tab = a.d<float>("bias_tab"); ad.dp = m->dp(); ad.dx = m->dx();
+  for (int i = 0; i < c.layers; ++i) {
+    if ((rc = mhip_gemm(ctx, prec, run.ht, a.d(blk(i, "qk_w")), (long long)R, 2 * D, D, nullptr, a.d<float>(blk(i, "qk_b")), run.qk, ACT_NONE, 0))) return rc;
+    if ((rc = mhip_gemm(ctx, prec, a.d(blk(i, "v_w")), run.ht, D, (int)R, D, nullptr, nullptr, run.vt, ACT_NONE, 0))) return rc;   // V^T = W_v X^T
+    if ((rc = mhip_launch_attention_bias(ctx, prec, ad))) return rc;
+    if ((rc = mhip_gemm(ctx, prec, run.ao, a.d(blk(i, "ao_w")), (long long)R, D, D, nullptr, a.d<float>(blk(i, "ao_b")), run.y, ACT_NONE, 1, run.h))) return rc;
+    if ((rc = mhip_launch_layernorm2(ctx, prec, run.y, a.d<float>(blk(i, "ln1_g")), a.d<float>(blk(i, "ln1_b")), run.h, run.ht, (int)R, D, c.layer_norm_eps))) return rc;
+    if ((rc = mhip_gemm(ctx, prec, run.ht, a.d(blk(i, "fc1_w")), (long long)R, F, D, nullptr, a.d<float>(blk(i, "fc1_b")), run.hid, ACT_GELU, 0))) return rc;
+    if ((rc = mhip_gemm(ctx, prec, run.hid, a.d(blk(i, "fc2_w")), (long long)R, D, F, nullptr, a.d<float>(blk(i, "fc2_b")), run.y, ACT_NONE, 1, run.h))) return rc;
+    if ((rc = mhip_launch_layernorm2(ctx, prec, run.y, a.d<float>(blk(i, "ln2_g")), a.d<float>(blk(i, "ln2_b")), run.h, run.ht, (int)R, D, c.layer_norm_eps))) return rc;
+  }
+  return mhip_launch_lmv3_head(ctx, run.h, n, NP, D, a.d<float>("cd_w"), a.d<float>("cd_b"), a.d<float>("co_w"), a.d<float>("co_b"),
+                               c.num_labels, run.logits);
+}
+
+int lmv3_check_call(mhip_layoutlmv3* m, const mhip_crop_desc* pages, int n, const int32_t* ids, const int32_t* bbox,
+                    const int32_t* mask) {
+  if (!m->ready) return mhip_fail(m->ctx, MHIP_ESTATE, "layoutlmv3: weights not finalized");
+  if (!pages || !ids || !bbox || !mask || n < 1 || n > 4096) return mhip_fail(m->ctx, MHIP_EINVAL, "layoutlmv3: bad arguments (n = %d)", n);
+  return MHIP_OK;
+}
+
+// resize + stage the host tables + forward; the caller has carved `run`
+int lmv3_run(mhip_layoutlmv3* m, const uint8_t* base_dev, const mhip_crop_desc* pages, int n, const std::vector<int>& tok,
+             const std::vector<uint32_t>& qcode, const std::vector<uint32_t>& kcode, const Lmv3Run& run) {
+  mhip_ctx* ctx = m->ctx;
+  const int S = m->cfg.input_size;
+  int rc = mhip_pil_resize_fragments(ctx, base_dev, pages, n, run.resized, S, S, MHIP_PIL_BILINEAR, run.frag_scratch, run.frag_bytes);
+  if (rc) return rc;
+  if ((rc = mhip_stage_h2d(ctx, run.tok, tok.data(), tok.size() * 4))) return rc;
+  if ((rc = mhip_stage_h2d(ctx, run.qcode, qcode.data(), qcode.size() * 4))) return rc;
+  if ((rc = mhip_stage_h2d(ctx, run.kcode, kcode.data(), kcode.size() * 4))) return rc;
+  return lmv3_forward(m, n, run);
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------- lifecycle
+extern "C" int mhip_layoutlmv3_default_config(mhip_layoutlmv3_config* cfg) {
+  if (!cfg) return MHIP_EINVAL;
+  mhip_layoutlmv3_config c{};
+  c.hidden = 768; c.layers = 12; c.heads = 12; c.ffn = 3072;
+  c.vocab = 50265; c.type_vocab = 1;
+  c.max_position_embeddings = 514; c.max_2d_position_embeddings = 1024;
+  c.coordinate_size = 128; c.shape_size = 128;
+  c.input_size = 224; c.patch = 16;
+  c.rel_pos_bins = 32; c.max_rel_pos = 128; c.rel_2d_pos_bins = 64; c.max_rel_2d_pos = 256;
+  c.layer_norm_eps = 1e-5f; c.pad_id = 1; c.num_labels = 2; c.max_text = 512;
+  *cfg = c;
+  return MHIP_OK;
+}
+
+extern "C" int mhip_layoutlmv3_seq_len(const mhip_layoutlmv3_config* cfg) {
+  if (!cfg || cfg->patch < 1) return MHIP_EINVAL;
+  const int g = cfg->input_size / cfg->patch;
+  return cfg->max_text + g * g + 1;
+}
+
+extern "C" int mhip_layoutlmv3_bucket(int relative_position, int num_buckets, int max_distance) {
+  return mhip_relative_position_bucket(relative_position, num_buckets, max_distance);
+}
+
+extern "C" int mhip_layoutlmv3_create(mhip_ctx* ctx, int precision, const mhip_layoutlmv3_config* cfg, mhip_layoutlmv3** out) {
+  if (!ctx || !out || !cfg) return MHIP_EINVAL;
+  *out = nullptr;
+  if (precision != MHIP_PREC_F16 && precision != MHIP_PREC_F32) return mhip_fail(ctx, MHIP_EINVAL, "unknown precision %d", precision);
+  const mhip_layoutlmv3_config& c = *cfg;
+  if (c.hidden != c.heads * 64 || c.hidden % 256 || c.hidden > 1024 || c.layers < 1 || c.ffn < 64 || c.ffn % 64)
+    return mhip_fail(ctx, MHIP_EINVAL, "layoutlmv3: unsupported width (hidden %d, heads %d, ffn %d: heads of 64, hidden a multiple of 256 up to 1024)", c.hidden, c.heads, c.ffn);
+  if (c.patch != 16 || c.input_size < 16 || c.input_size % 16)
+    return mhip_fail(ctx, MHIP_EINVAL, "layoutlmv3: unsupported image geometry (input %d, patch %d)", c.input_size, c.patch);
+  if (c.coordinate_size < 4 || c.shape_size < 4 || c.coordinate_size % 4 || c.shape_size % 4 || 4 * c.coordinate_size + 2 * c.shape_size != c.hidden)
+    return mhip_fail(ctx, MHIP_EINVAL, "layoutlmv3: 4 * coordinate_size + 2 * shape_size must equal hidden");
+  if (c.max_2d_position_embeddings < 1001 || c.max_2d_position_embeddings > 1024)
+    return mhip_fail(ctx, MHIP_EINVAL, "layoutlmv3: max_2d_position_embeddings %d (1001 .. 1024)", c.max_2d_position_embeddings);
+  if (c.max_text < 8 || c.max_text > 1024 || c.max_text % 8 || c.pad_id < 0 || c.vocab <= c.pad_id || c.type_vocab < 1 || c.num_labels < 1)
+    return mhip_fail(ctx, MHIP_EINVAL, "layoutlmv3: unsupported text geometry (max_text %d, vocab %d, pad %d, labels %d)", c.max_text, c.vocab, c.pad_id, c.num_labels);
+  if (c.max_position_embeddings < c.max_text + c.pad_id + 1)
+    return mhip_fail(ctx, MHIP_EINVAL, "layoutlmv3: max_position_embeddings %d cannot hold %d unpadded tokens (needs %d)",
+                     c.max_position_embeddings, c.max_text, c.max_text + c.pad_id + 1);
+  if (c.rel_pos_bins < 4 || c.rel_pos_bins % 4 || c.rel_2d_pos_bins < 4 || c.rel_2d_pos_bins % 4 || c.max_rel_pos <= c.rel_pos_bins / 4 ||
+      c.max_rel_2d_pos <= c.rel_2d_pos_bins / 4)
+    return mhip_fail(ctx, MHIP_EINVAL, "layoutlmv3: unsupported relative-position buckets");
+  if (!(c.layer_norm_eps > 0.f)) return mhip_fail(ctx, MHIP_EINVAL, "layoutlmv3: layer_norm_eps");
+  mhip_layoutlmv3* m = new mhip_layoutlmv3();
+  m->ctx = ctx;
+  m->precision = precision;
+  m->cfg = c;
+  if (m->dp() > 1023) { delete m; return mhip_fail(ctx, MHIP_EINVAL, "layoutlmv3: more than 1024 positions"); }
+  const size_t es = m->esz(), D = c.hidden, F = c.ffn, M2 = c.max_2d_position_embeddings;
+  Arena& a = m->arena;
+  a.take("word", (size_t)c.vocab * D * es);
+  a.take("type0", D * 4);
+  a.take("pos", (size_t)c.max_position_embeddings * D * 4);
+  a.take("xe", M2 * c.coordinate_size * 4); a.take("ye", M2 * c.coordinate_size * 4);
+  a.take("he", M2 * c.shape_size * 4); a.take("we", M2 * c.shape_size * 4);
+  a.take("ln_text_g", D * 4); a.take("ln_text_b", D * 4);
+  a.take("ln_vis_g", D * 4); a.take("ln_vis_b", D * 4);
+  a.take("ln_all_g", D * 4); a.take("ln_all_b", D * 4);
+  a.take("pe_w", D * 3 * 16 * 16 * es); a.take("pe_b", D * 4);
+  a.take("pos_vis", (size_t)(m->n_vis() - 1) * D * 4);
+  a.take("cls", D * 4);
+  a.take("bias_tab", (size_t)c.heads * mhip_attn_bias_table_len(m->dp(), m->dx()) * 4);
+  for (int i = 0; i < c.layers; ++i) {
+    a.take(blk(i, "qk_w"), 2 * D * D * es); a.take(blk(i, "qk_b"), 2 * D * 4);
+    a.take(blk(i, "v_w"), D * D * es);
+    a.take(blk(i, "ao_w"), D * D * es); a.take(blk(i, "ao_b"), D * 4);
+    a.take(blk(i, "ln1_g"), D * 4); a.take(blk(i, "ln1_b"), D * 4);
+    a.take(blk(i, "fc1_w"), F * D * es); a.take(blk(i, "fc1_b"), F * 4);
+    a.take(blk(i, "fc2_w"), D * F * es); a.take(blk(i, "fc2_b"), D * 4);
+    a.take(blk(i, "ln2_g"), D * 4); a.take(blk(i, "ln2_b"), D * 4);
+  }
+  a.take("cd_w", D * D * 4); a.take("cd_b", D * 4);
+  a.take("co_w", (size_t)c.num_labels * D * 4); a.take("co_b", (size_t)c.num_labels * 4);
+  *out = m;
+  return MHIP_OK;
+}
+
+extern "C" int mhip_layoutlmv3_destroy(mhip_layoutlmv3* m) {
+  if (!m) return MHIP_OK;
+  mhip_quiesce(m->ctx);
+  m->arena.release();
+  delete m;
+  return MHIP_OK;
+}
+
+extern "C" int mhip_layoutlmv3_set_tensor(mhip_layoutlmv3* m, const char* key, const float* data, const int64_t* shape, int ndim) {
+  if (!m || !key) return MHIP_EINVAL;
+  std::string k(key);
+  auto ends = [&](const char* s) { const size_t n = strlen(s); return k.size() >= n && k.compare(k.size() - n, n, s) == 0; };
+  if (ends("position_ids") || ends("visual_bbox")) return MHIP_OK;      // buffers older checkpoints carry; rebuilt from the config
+  if (k.rfind(PFX, 0) != 0 && k.rfind("classifier.", 0) != 0) return mhip_fail(m->ctx, MHIP_EINVAL, "unknown state_dict key %s", key);
+  m->ready = false;
+  return m->store.set(m->ctx, k, data, shape, ndim);
+}
+
+extern "C" int mhip_layoutlmv3_alloc_arena(mhip_layoutlmv3* m) {
+  if (!m) return MHIP_EINVAL;
+  int rc = m->arena.alloc(m->ctx);
+  if (rc) return rc;
+  m->ready = true;
+  return MHIP_OK;
+}
+
+extern "C" int mhip_layoutlmv3_arena(mhip_layoutlmv3* m, void** dev, size_t* bytes) {
+  if (!m) return MHIP_EINVAL;
+  if (dev) *dev = m->arena.dev;
+  if (bytes) *bytes = m->arena.bytes;
+  return MHIP_OK;
+}
+
+extern "C" int mhip_layoutlmv3_finalize(mhip_layoutlmv3* m) {
+  if (!m) return MHIP_EINVAL;
+  mhip_ctx* ctx = m->ctx;
+  const mhip_layoutlmv3_config& c = m->cfg;
+  const int D = c.hidden, F = c.ffn, prec = m->precision, M2 = c.max_2d_position_embeddings, NV = m->n_vis();
+  const size_t es = m->esz();
+  Arena& a = m->arena;
+  const TensorStore& st = m->store;
+  a.begin_fill();
+  const std::string E = std::string(PFX) + "embeddings.";
+  const HostTensor* word = st.find(ctx, E + "word_embeddings.weight", {c.vocab, D});
+  const HostTensor* type = st.find(ctx, E + "token_type_embeddings.weight", {c.type_vocab, D});
+  const HostTensor* pos = st.find(ctx, E + "position_embeddings.weight", {c.max_position_embeddings, D});
+  const HostTensor* xe = st.find(ctx, E + "x_position_embeddings.weight", {M2, c.coordinate_size});
+  const HostTensor* ye = st.find(ctx, E + "y_position_embeddings.weight", {M2, c.coordinate_size});
+  const HostTensor* he = st.find(ctx, E + "h_position_embeddings.weight", {M2, c.shape_size});
+  const HostTensor* we = st.find(ctx, E + "w_position_embeddings.weight", {M2, c.shape_size});
+  const HostTensor* ltg = st.find(ctx, E + "LayerNorm.weight", {D});
+  const HostTensor* ltb = st.find(ctx, E + "LayerNorm.bias", {D});
+  const HostTensor* lag = st.find(ctx, std::string(PFX) + "LayerNorm.weight", {D});
+  const HostTensor* lab = st.find(ctx, std::string(PFX) + "LayerNorm.bias", {D});
+  const HostTensor* lvg = st.find(ctx, std::string(PFX) + "norm.weight", {D});
+  const HostTensor* lvb = st.find(ctx, std::string(PFX) + "norm.bias", {D});
+  const HostTensor* pw = st.find(ctx, std::string(PFX) + "patch_embed.proj.weight", {D, 3, 16, 16});
+  const HostTensor* pb = st.find(ctx, std::string(PFX) + "patch_embed.proj.bias", {D});
+  const HostTensor* cls = st.find(ctx, std::string(PFX) + "cls_token", {1, 1, D});
+  const HostTensor* pv = st.find(ctx, std::string(PFX) + "pos_embed", {1, NV, D});
+  const HostTensor* r1 = st.find(ctx, std::string(PFX) + "encoder.rel_pos_bias.weight", {c.heads, c.rel_pos_bins});
+  const HostTensor* rx = st.find(ctx, std::string(PFX) + "encoder.rel_pos_x_bias.weight", {c.heads, c.rel_2d_pos_bins});
+  const HostTensor* ry = st.find(ctx, std::string(PFX) + "encoder.rel_pos_y_bias.weight", {c.heads, c.rel_2d_pos_bins});
+  const HostTensor* cdw = st.find(ctx, "classifier.dense.weight", {D, D});
+  const HostTensor* cdb = st.find(ctx, "classifier.dense.bias", {D});
+  const HostTensor* cow = st.find(ctx, "classifier.out_proj.weight", {c.num_labels, D});
+  const HostTensor* cob = st.find(ctx, "classifier.out_proj.bias", {c.num_labels});
+  if (!word || !type || !pos || !xe || !ye || !he || !we || !ltg || !ltb || !lag || !lab || !lvg || !lvb || !pw || !pb || !cls ||
+      !pv || !r1 || !rx || !ry || !cdw || !cdb || !cow || !cob)
+    return MHIP_ESTATE;
+  Arena::put(prec, a.h("word"), word->data.data(), word->numel());
+  memcpy(a.h("type0"), type->data.data(), D * 4);                  // token_type_ids are zeros on this path
+  memcpy(a.h("pos"), pos->data.data(), pos->numel() * 4);
+  memcpy(a.h("xe"), xe->data.data(), xe->numel() * 4);
+  memcpy(a.h("ye"), ye->data.data(), ye->numel() * 4);
+  memcpy(a.h("he"), he->data.data(), he->numel() * 4);
+  memcpy(a.h("we"), we->data.data(), we->numel() * 4);
+  memcpy(a.h("ln_text_g"), ltg->data.data(), D * 4); memcpy(a.h("ln_text_b"), ltb->data.data(), D * 4);
+  memcpy(a.h("ln_all_g"), lag->data.data(), D * 4); memcpy(a.h("ln_all_b"), lab->data.data(), D * 4);
+  memcpy(a.h("ln_vis_g"), lvg->data.data(), D * 4); memcpy(a.h("ln_vis_b"), lvb->data.data(), D * 4);
+  Arena::put(prec, a.h("pe_w"), pw->data.data(), pw->numel());
+  memcpy(a.h("pe_b"), pb->data.data(), D * 4);
+  memcpy(a.h("pos_vis"), pv->data.data() + D, (size_t)(NV - 1) * D * 4);
+  for (int d = 0; d < D; ++d) ((float*)a.h("cls"))[d] = cls->data[d] + pv->data[d];
+  // the three bias matrices folded into difference-indexed tables, in the units of the scores (1 / sqrt(64), base-2 exponent)
+  const float qs = 0.125f * LOG2E;
+  mhip_attn_bias_fold(r1->data.data(), rx->data.data(), ry->data.data(), c.heads, c.rel_pos_bins, c.max_rel_pos, c.rel_2d_pos_bins,
+                      c.max_rel_2d_pos, m->dp(), m->dx(), qs, (float*)a.h("bias_tab"));
+  for (int i = 0; i < c.layers; ++i) {
+    const HostTensor* qw = st.find(ctx, lyr(i, "attention.self.query.weight"), {D, D});
+    const HostTensor* qb = st.find(ctx, lyr(i, "attention.self.query.bias"), {D});
+    const HostTensor* kw = st.find(ctx, lyr(i, "attention.self.key.weight"), {D, D});
+    const HostTensor* kb = st.find(ctx, lyr(i, "attention.self.key.bias"), {D});
+    const HostTensor* vw = st.find(ctx, lyr(i, "attention.self.value.weight"), {D, D});
+    const HostTensor* vb = st.find(ctx, lyr(i, "attention.self.value.bias"), {D});
+    const HostTensor* ow = st.find(ctx, lyr(i, "attention.output.dense.weight"), {D, D});
+    const HostTensor* ob = st.find(ctx, lyr(i, "attention.output.dense.bias"), {D});
+    const HostTensor* g1 = st.find(ctx, lyr(i, "attention.output.LayerNorm.weight"), {D});
+    const HostTensor* b1 = st.find(ctx, lyr(i, "attention.output.LayerNorm.bias"), {D});
+    const HostTensor* iw = st.find(ctx, lyr(i, "intermediate.dense.weight"), {F, D});
+    const HostTensor* ib = st.find(ctx, lyr(i, "intermediate.dense.bias"), {F});
+    const HostTensor* dw = st.find(ctx, lyr(i, "output.dense.weight"), {D, F});
+    const HostTensor* db = st.find(ctx, lyr(i, "output.dense.bias"), {D});
+    const HostTensor* g2 = st.find(ctx, lyr(i, "output.LayerNorm.weight"), {D});
+    const HostTensor* b2 = st.find(ctx, lyr(i, "output.LayerNorm.bias"), {D});
+    if (!qw || !qb || !kw || !kb || !vw || !vb || !ow || !ob || !g1 || !b1 || !iw || !ib || !dw || !db || !g2 || !b2) return MHIP_ESTATE;
+    std::vector<float> wq((size_t)D * D);
+    for (size_t e = 0; e < wq.size(); ++e) wq[e] = qw->data[e] * qs;
+    Arena::put(prec, a.h(blk(i, "qk_w")), wq.data(), wq.size());
+    Arena::put(prec, a.h(blk(i, "qk_w")) + (size_t)D * D * es, kw->data.data(), kw->numel());
+    float* qkb = (float*)a.h(blk(i, "qk_b"));
+    for (int d = 0; d < D; ++d) { qkb[d] = qb->data[d] * qs; qkb[D + d] = kb->data[d]; }
+    Arena::put(prec, a.h(blk(i, "v_w")), vw->data.data(), vw->numel());
+    Arena::put(prec, a.h(blk(i, "ao_w")), ow->data.data(), ow->numel());
+    float* aob = (float*)a.h(blk(i, "ao_b"));
+    for (int o = 0; o < D; ++o) {      // dense(ctx + b_v) = dense(ctx) + W_o b_v
+      double acc = ob->data[o];
+      for (int k = 0; k < D; ++k) acc += (double)ow->data[(size_t)o * D + k] * vb->data[k];
+      aob[o] = (float)acc;
+    }
+    memcpy(a.h(blk(i, "ln1_g")), g1->data.data(), D * 4); memcpy(a.h(blk(i, "ln1_b")), b1->data.data(), D * 4);
+    Arena::put(prec, a.h(blk(i, "fc1_w")), iw->data.data(), iw->numel());
+    memcpy(a.h(blk(i, "fc1_b")), ib->data.data(), (size_t)F * 4);
+    Arena::put(prec, a.h(blk(i, "fc2_w")), dw->data.data(), dw->numel());
+    memcpy(a.h(blk(i, "fc2_b")), db->data.data(), D * 4);
+    memcpy(a.h(blk(i, "ln2_g")), g2->data.data(), D * 4); memcpy(a.h(blk(i, "ln2_b")), b2->data.data(), D * 4);
+  }
+  memcpy(a.h("cd_w"), cdw->data.data(), cdw->numel() * 4); memcpy(a.h("cd_b"), cdb->data.data(), D * 4);
+  memcpy(a.h("co_w"), cow->data.data(), cow->numel() * 4); memcpy(a.h("co_b"), cob->data.data(), (size_t)c.num_labels * 4);
+  int rc = a.upload(ctx);
+  if (rc) return rc;
+  m->ready = true;
+  m->store.t.clear();
+  return MHIP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------- forward
+extern "C" int mhip_layoutlmv3_classify(mhip_layoutlmv3* m, const uint8_t* base_dev, const mhip_crop_desc* pages, int n,
+                                        const int32_t* ids, const int32_t* bbox, const int32_t* mask, float* logits_out) {
+  if (!m || !base_dev || !logits_out) return MHIP_EINVAL;
+  mhip_ctx* ctx = m->ctx;
+  int rc = lmv3_check_call(m, pages, n, ids, bbox, mask);
+  if (rc) return rc;
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  std::vector<int> tok;
+  std::vector<uint32_t> qcode, kcode;
+  if ((rc = lmv3_prepare(m, n, ids, bbox, mask, tok, qcode, kcode))) return rc;
+  Lmv3Run run;
+  if ((rc = mhip_carve_workspace(ctx, [&](Carver& ws) { lmv3_carve(m, ws, pages, n, &run); }))) return rc;
+  if ((rc = lmv3_run(m, base_dev, pages, n, tok, qcode, kcode, run))) return rc;
+  MHIP_HIP(ctx, hipMemcpyAsync(logits_out, run.logits, (size_t)n * m->cfg.num_labels * 4, hipMemcpyDeviceToHost, ctx->stream));
+  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return MHIP_OK;
+}
+
+extern "C" int mhip_layoutlmv3_hidden_host(mhip_layoutlmv3* m, const uint8_t* pages_host, size_t pages_bytes,
+                                           const mhip_crop_desc* pages, int n, const int32_t* ids, const int32_t* bbox,
+                                           const int32_t* mask, float* logits_out, float* hidden_out, uint8_t* resized_out) {
+  if (!m || !pages_host || !pages_bytes) return MHIP_EINVAL;
+  mhip_ctx* ctx = m->ctx;
+  int rc = lmv3_check_call(m, pages, n, ids, bbox, mask);
+  if (rc) return rc;
+  for (int i = 0; i < n; ++i)
+    if (pages[i].h < 1 || pages[i].w < 1 || pages[i].row_stride < pages[i].w * 3 ||
+        pages[i].src_offset + (size_t)(pages[i].h - 1) * pages[i].row_stride + (size_t)pages[i].w * 3 > pages_bytes)
+      return mhip_fail(ctx, MHIP_EINVAL, "layoutlmv3: page %d lies outside the buffer", i);
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  std::vector<int> tok;
+  std::vector<uint32_t> qcode, kcode;
+  if ((rc = lmv3_prepare(m, n, ids, bbox, mask, tok, qcode, kcode))) return rc;
+  Lmv3Run run;
+  uint8_t* base = nullptr;
+  if ((rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
+         base = ws.take<uint8_t>(pages_bytes);
+         lmv3_carve(m, ws, pages, n, &run);
+       })))
+    return rc;
+  MHIP_HIP(ctx, hipMemcpyAsync(base, pages_host, pages_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = lmv3_run(m, base, pages, n, tok, qcode, kcode, run))) return rc;
+  const size_t D = m->cfg.hidden, S = m->cfg.input_size, seq = m->seq(), NP = m->npad();
+  if (logits_out) MHIP_HIP(ctx, hipMemcpyAsync(logits_out, run.logits, (size_t)n * m->cfg.num_labels * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (hidden_out)
+    MHIP_HIP(ctx, hipMemcpy2DAsync(hidden_out, seq * D * 4, run.h, NP * D * 4, seq * D * 4, n, hipMemcpyDeviceToHost, ctx->stream));
+  if (resized_out) MHIP_HIP(ctx, hipMemcpyAsync(resized_out, run.resized, (size_t)n * S * S * 3, hipMemcpyDeviceToHost, ctx->stream));
+  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return MHIP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------- the attention kernel alone
+extern "C" int mhip_attention_bias_host(mhip_ctx* ctx, int precision, int heads, int n_tok, const float* q, const float* k,
+                                        const float* v, const int32_t* pos, const int32_t* x, const int32_t* y,
+                                        const int32_t* valid, const float* w1, const float* wx, const float* wy, int bins_1d,
+                                        int max_1d, int bins_2d, int max_2d, float* out) {
+  if (!ctx || !q || !k || !v || !pos || !x || !y || !valid || !w1 || !wx || !wy || !out) return MHIP_EINVAL;
+  if (precision != MHIP_PREC_F16 && precision != MHIP_PREC_F32) return mhip_fail(ctx, MHIP_EINVAL, "unknown precision %d", precision);
+  if (heads < 1 || heads > 64 || n_tok < 1 || n_tok > 65536 || bins_1d < 4 || bins_1d % 4 || bins_2d < 4 || bins_2d % 4 ||
+      max_1d <= bins_1d / 4 || max_2d <= bins_2d / 4)
+    return mhip_fail(ctx, MHIP_EINVAL, "attention_bias: bad arguments");
+  int dp = 0, dx = 0;
+  for (int i = 0; i < n_tok; ++i) {
+    if (pos[i] < 0 || pos[i] > 1023 || x[i] < 0 || x[i] > 1023 || y[i] < 0 || y[i] > 1023)
+      return mhip_fail(ctx, MHIP_EINVAL, "attention_bias: position / coordinate of token %d outside [0, 1023]", i);
+    dp = std::max(dp, pos[i]);
+    dx = std::max(dx, std::max(x[i], y[i]));
+  }
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t es = precision == MHIP_PREC_F16 ? 2 : 4, D = (size_t)heads * 64, NP = ((size_t)n_tok + 7) / 8 * 8;
+  const int tl = mhip_attn_bias_table_len(dp, dx);
+  // operands in the element type and with the pitches the model uses: q | k rows, V^T, zero slack
+  std::vector<char> qk((NP + 128) * 2 * D * es, 0), vt((D * NP + 128) * es, 0);
+  const float qs = 0.125f * LOG2E;
+  auto put = [&](char* dst, size_t at, float val) {
+    if (es == 2) ((_Float16*)dst)[at] = (_Float16)val; else ((float*)dst)[at] = val;
+  };
+  for (size_t t = 0; t < (size_t)n_tok; ++t)
+    for (size_t d = 0; d < D; ++d) {
+      put(qk.data(), t * 2 * D + d, q[t * D + d] * qs);
+      put(qk.data(), t * 2 * D + D + d, k[t * D + d]);
+      put(vt.data(), d * NP + t, v[t * D + d]);
+    }
+  std::vector<uint32_t> qcode(NP + 128, 0), kcode(NP + 128, (uint32_t)(2 * dp + 1));
+  for (int t = 0; t < n_tok; ++t) {
+    const uint32_t xy = ((uint32_t)x[t] << 12) | ((uint32_t)y[t] << 22);
+    qcode[t] = (uint32_t)pos[t] | xy;
+    kcode[t] = (valid[t] ? (uint32_t)pos[t] : (uint32_t)(2 * dp + 1)) | xy;
+  }
+  std::vector<float> tab((size_t)heads * tl);
+  mhip_attn_bias_fold(w1, wx, wy, heads, bins_1d, max_1d, bins_2d, max_2d, dp, dx, qs, tab.data());
+  char *dqk = nullptr, *dvt = nullptr, *dao = nullptr;
+  uint32_t *dqc = nullptr, *dkc = nullptr;
+  float *dtab = nullptr, *dout = nullptr;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
+    dqk = ws.take(qk.size()); dvt = ws.take(vt.size()); dao = ws.take(NP * D * es);
+    dqc = ws.take<uint32_t>(qcode.size() * 4); dkc = ws.take<uint32_t>(kcode.size() * 4);
+    dtab = ws.take<float>(tab.size() * 4); dout = ws.take<float>((size_t)n_tok * D * 4);
+  });
+  if (rc) return rc;
+  MHIP_HIP(ctx, hipMemcpyAsync(dqk, qk.data(), qk.size(), hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(dvt, vt.data(), vt.size(), hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(dqc, qcode.data(), qcode.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(dkc, kcode.data(), kcode.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(dtab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the sources are host temporaries in pageable memory
+  AttnBiasDesc ad;
+  ad.a.q = dqk; ad.a.k = dqk + D * es; ad.a.vt = dvt; ad.a.out = dao;
+  ad.a.ldq = ad.a.ldk = (int)(2 * D); ad.a.ldv = (int)NP; ad.a.ldo = (int)D;
+  ad.a.images = 1; ad.a.heads = heads; ad.a.npad_q = ad.a.npad_k = (int)NP; ad.a.n_queries = ad.a.n_keys = n_tok;
+  ad.qcode = dqc; ad.kcode = dkc; ad.tab = dtab; ad.dp = dp; ad.dx = dx;
+  if ((rc = mhip_launch_attention_bias(ctx, precision, ad))) return rc;
+  if ((rc = mhip_launch_convert_rows(ctx, precision, dao, dout, n_tok, (int)D))) return rc;
+  MHIP_HIP(ctx, hipMemcpyAsync(out, dout, (size_t)n_tok * D * 4, hipMemcpyDeviceToHost, ctx->stream));
+  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return MHIP_OK;
+}

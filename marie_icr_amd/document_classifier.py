@@ -1,0 +1,334 @@
+"""The page classifier that runs directly on the OCR result: LayoutLMv3 over the page image, the OCR words and their boxes.
+
+reference: ``TransformersDocumentClassifier`` with ``task="text-classification-multimodal"``
+(marie/components/document_classifier/transformers.py:41-361), ``scale_bounding_box`` (marie/components/util.py:4-29) and, for
+what the reference delegates to the transformers library, ``LayoutLMv3Processor`` / ``LayoutLMv3TokenizerFast`` (words + boxes
+-> ids, token boxes, mask) and ``LayoutLMv3ImageProcessor(apply_ocr=False, do_resize=True, resample=BILINEAR)``.
+
+The model runs in HIP (``layoutlmv3.py``; the image resize and normalisation are part of the model call).  The tokeniser runs on
+the host, here, without the transformers library: RoBERTa byte-level BPE from ``vocab.json`` / ``merges.txt``.  ``words`` and
+``boxes`` are what ``get_words_and_boxes`` (renderer.py) returns for a page.
+
+Unlike the reference, whose "batch" loops page by page, the pages of a batch go through one model call.  There is no CPU path:
+``use_gpu=False`` raises.  The ``text-classification`` and ``zero-shot-classification`` tasks (text-only pipelines of other
+model families) are not part of this project.
+"""
+from __future__ import annotations
+
+import json
+import os
+import unicodedata
+from functools import lru_cache
+from typing import Any, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from ._lib import PREC_F16, PREC_F32, Context, MarieHipError
+
+MAX_LENGTH = 512          # predict_document_image: max_length=512, padding="max_length", truncation=True
+
+
+# ------------------------------------------------------------------------------------------------ tokeniser
+@lru_cache()
+def bytes_to_unicode() -> Dict[int, str]:
+    """GPT-2's byte -> printable unicode character table (the alphabet of byte-level BPE vocabularies)."""
+    bs = list(range(ord("!"), ord("~") + 1)) + list(range(ord("¡"), ord("¬") + 1)) + list(range(ord("®"), ord("ÿ") + 1))
+    cs = bs[:]
+    n = 0
+    for b in range(256):
+        if b not in bs:
+            bs.append(b)
+            cs.append(256 + n)
+            n += 1
+    return dict(zip(bs, (chr(c) for c in cs)))
+
+
+_GPT2_PATTERN = r"'s|'t|'re|'ve|'m|'ll|'d| ?\p{L}+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|\s+(?!\S)|\s+"
+_CONTRACTIONS = ("'s", "'t", "'re", "'ve", "'m", "'ll", "'d")
+
+
+def _split_gpt2_plain(text: str) -> List[str]:
+    """The GPT-2 pre-tokenisation pattern on ``str`` predicates (for interpreters without the ``regex`` module): the same
+    alternation, tried in the same order at every position."""
+    def cls(c):
+        if c.isspace():
+            return "s"
+        k = unicodedata.category(c)[0]
+        return "L" if k == "L" else ("N" if k == "N" else "o")
+
+    out, i, n = [], 0, len(text)
+    while i < n:
+        for c in _CONTRACTIONS:
+            if text.startswith(c, i):
+                out.append(c)
+                i += len(c)
+                break
+        else:
+            j = i + 1 if text[i] == " " and i + 1 < n and cls(text[i + 1]) != "s" else i
+            k = cls(text[j])
+            if k != "s":                      # " ?" + a run of one class
+                e = j
+                while e < n and cls(text[e]) == k:
+                    e += 1
+            else:                             # \s+(?!\S) | \s+
+                e = i
+                while e < n and cls(text[e]) == "s":
+                    e += 1
+                if e < n and e - i > 1:
+                    e -= 1
+            out.append(text[i:e])
+            i = e
+    return out
+
+
+try:
+    import regex as _regex
+
+    _GPT2_RE = _regex.compile(_GPT2_PATTERN)
+
+    def split_gpt2(text: str) -> List[str]:
+        return _GPT2_RE.findall(text)
+except ImportError:      # pragma: no cover
+    split_gpt2 = _split_gpt2_plain
+
+
+class ByteLevelBPE:
+    """RoBERTa / LayoutLMv3 byte-level BPE as ``LayoutLMv3Tokenizer`` applies it to OCR words: every word is encoded on its own
+    with the leading-space marker (``add_prefix_space=True``), and every sub-token carries its word's box."""
+
+    def __init__(self, vocab_file: str, merges_file: str, bos: str = "<s>", eos: str = "</s>", pad: str = "<pad>",
+                 unk: str = "<unk>"):
+        with open(vocab_file, encoding="utf-8") as f:
+            self.vocab: Dict[str, int] = json.load(f)
+        with open(merges_file, encoding="utf-8") as f:
+            lines = f.read().split("\n")
+        if lines and lines[0].startswith("#version"):
+            lines = lines[1:]
+        self.ranks: Dict[Tuple[str, str], int] = {}
+        for ln in lines:
+            parts = ln.split()
+            if len(parts) == 2:
+                self.ranks.setdefault((parts[0], parts[1]), len(self.ranks))
+        for name in (bos, eos, pad, unk):
+            if name not in self.vocab:
+                raise ValueError(f"vocab.json lacks the special token {name}")
+        self.bos_id, self.eos_id, self.pad_id, self.unk_id = (self.vocab[t] for t in (bos, eos, pad, unk))
+        self._b2u = bytes_to_unicode()
+        self._cache: Dict[str, List[int]] = {}
+
+    def _bpe(self, token: str) -> List[str]:
+        word = list(token)
+        while len(word) > 1:
+            best, best_rank = None, None
+            for pair in zip(word[:-1], word[1:]):
+                r = self.ranks.get(pair)
+                if r is not None and (best_rank is None or r < best_rank):
+                    best, best_rank = pair, r
+            if best is None:
+                break
+            a, b = best
+            merged, i = [], 0
+            while i < len(word):
+                if i + 1 < len(word) and word[i] == a and word[i + 1] == b:
+                    merged.append(a + b)
+                    i += 2
+                else:
+                    merged.append(word[i])
+                    i += 1
+            word = merged
+        return word
+
+    def encode_word(self, word: str) -> List[int]:
+        """Sub-token ids of one OCR word (no special tokens)."""
+        ids = self._cache.get(word)
+        if ids is None:
+            text = word if word.startswith(" ") else " " + word
+            ids = []
+            for piece in split_gpt2(text):
+                sym = "".join(self._b2u[b] for b in piece.encode("utf-8"))
+                ids.extend(self.vocab.get(t, self.unk_id) for t in self._bpe(sym))
+            if len(self._cache) < 65536:
+                self._cache[word] = ids
+        return ids
+
+    def encode_page(self, words: Sequence[str], boxes: Sequence[Sequence[int]], max_length: int = MAX_LENGTH):
+        """``LayoutLMv3Tokenizer(words, boxes=boxes, max_length=512, padding="max_length", truncation=True)``:
+        (input_ids, bbox, attention_mask) as int32 arrays of max_length (x 4).  ``<s>``, ``</s>`` and ``<pad>`` carry
+        [0, 0, 0, 0]; truncation keeps the first max_length - 2 sub-tokens."""
+        if len(words) != len(boxes):
+            raise ValueError("words and boxes must have the same length")
+        ids, bbs = [self.bos_id], [[0, 0, 0, 0]]
+        room = max_length - 2
+        for w, b in zip(words, boxes):
+            if room <= 0:
+                break
+            sub = self.encode_word(str(w))[:room]
+            ids.extend(sub)
+            bbs.extend([list(b)] * len(sub))
+            room -= len(sub)
+        ids.append(self.eos_id)
+        bbs.append([0, 0, 0, 0])
+        n = len(ids)
+        input_ids = np.full((max_length,), self.pad_id, np.int32)
+        bbox = np.zeros((max_length, 4), np.int32)
+        mask = np.zeros((max_length,), np.int32)
+        input_ids[:n] = ids
+        bbox[:n] = np.asarray(bbs, np.int64).reshape(n, 4)
+        mask[:n] = 1
+        return input_ids, bbox, mask
+
+
+def scale_bounding_box(box: Sequence[int], width_scale: float = 1.0, height_scale: float = 1.0) -> List[int]:
+    """marie/components/util.py:24-29."""
+    return [int(box[0] * width_scale), int(box[1] * height_scale), int(box[2] * width_scale), int(box[3] * height_scale)]
+
+
+# ------------------------------------------------------------------------------------------------ classifier
+def _load_state(model_dir: str) -> Dict[str, np.ndarray]:
+    bin_path = os.path.join(model_dir, "pytorch_model.bin")
+    st_path = os.path.join(model_dir, "model.safetensors")
+    if os.path.exists(bin_path):
+        import torch
+
+        ck = torch.load(bin_path, map_location="cpu", weights_only=True)
+        return {k: v.detach().to(torch.float32).numpy() for k, v in ck.items()}
+    if os.path.exists(st_path):
+        try:
+            from safetensors.numpy import load_file
+        except ImportError as e:
+            raise MarieHipError(f"{st_path} needs the safetensors module, which is not installed") from e
+        return {k: np.asarray(v, np.float32) for k, v in load_file(st_path).items()}
+    raise FileNotFoundError(f"no pytorch_model.bin or model.safetensors in {model_dir}")
+
+
+class TransformersDocumentClassifier:
+    """marie/components/document_classifier/transformers.py:41-361 for ``task="text-classification-multimodal"``.
+
+    ``model_name_or_path`` is a local directory with ``config.json``, the weights (``pytorch_model.bin`` or
+    ``model.safetensors``) and, unless ``tokenizer`` names another directory, ``vocab.json`` + ``merges.txt``.  ``state`` /
+    ``config`` (a state dict under the Hugging Face key names, a ``config.json`` dictionary) replace the files of the same
+    content."""
+
+    def __init__(self, model_name_or_path: str, tokenizer: Optional[str] = None, use_gpu: bool = True, top_k: int = 1,
+                 task: str = "text-classification-multimodal", batch_size: int = 16, id2label: Optional[dict] = None, *,
+                 state: Optional[Dict[str, np.ndarray]] = None, config: Optional[dict] = None, precision: str = "f16",
+                 ctx: Optional[Context] = None, **kwargs):
+        if task in ("text-classification", "zero-shot-classification"):
+            raise NotImplementedError(f"task {task!r}: only 'text-classification-multimodal' (LayoutLMv3) is built")
+        if task != "text-classification-multimodal":
+            raise ValueError(f"unknown task {task!r}")
+        if not use_gpu:
+            raise MarieHipError("TransformersDocumentClassifier runs on the GPU only: there is no CPU path in this project")
+        if precision not in ("f16", "f32"):
+            raise ValueError(f"precision {precision!r}: 'f16' or 'f32'")
+        if not os.path.isdir(model_name_or_path):
+            raise FileNotFoundError(f"model directory {model_name_or_path!r} does not exist (models are local directories)")
+        self.task, self.top_k, self.batch_size = task, int(top_k), int(batch_size)
+        self.model_dir = model_name_or_path
+        tok_dir = tokenizer if tokenizer is not None else model_name_or_path
+        self.tokenizer = ByteLevelBPE(os.path.join(tok_dir, "vocab.json"), os.path.join(tok_dir, "merges.txt"))
+        if config is None:
+            with open(os.path.join(model_name_or_path, "config.json"), encoding="utf-8") as f:
+                config = json.load(f)
+        self.hf_config = dict(config)
+        if id2label is None:
+            id2label = self.hf_config.get("id2label")
+        if id2label is None:
+            id2label = {i: f"LABEL_{i}" for i in range(int(self.hf_config.get("num_labels", 2)))}
+        self.id2label = {int(k): v for k, v in id2label.items()}
+        self.precision = PREC_F16 if precision == "f16" else PREC_F32
+        self._open_model(state, ctx)
+
+    def _open_model(self, state, ctx):
+        from .layoutlmv3 import LayoutLMv3Model, config_from_hf
+
+        self.ctx = ctx if ctx is not None else Context(0)
+        cfg = config_from_hf(self.hf_config, self.ctx.lib)
+        if "id2label" not in self.hf_config and "num_labels" not in self.hf_config:
+            cfg.num_labels = len(self.id2label)
+        if cfg.pad_id != self.tokenizer.pad_id:
+            raise ValueError(f"config.json pad_token_id {cfg.pad_id} differs from the tokeniser's <pad> id {self.tokenizer.pad_id}")
+        if state is None:
+            state = _load_state(self.model_dir)
+        self.model = LayoutLMv3Model(self.ctx, state, cfg, self.precision)
+
+    def _logits(self, pages: List[np.ndarray], ids: np.ndarray, bbox: np.ndarray, mask: np.ndarray) -> np.ndarray:
+        """One model call over all pages -> (n, num_labels) fp32."""
+        import torch
+
+        from .layoutlmv3 import pack_pages
+
+        packed, descs = pack_pages(pages)
+        self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+        d_in = torch.from_numpy(packed).cuda()
+        logits = self.model.classify_device(d_in.data_ptr(), descs, len(pages), ids, bbox, mask)   # returns after the stream drained
+        return logits
+
+    # ---- encoding of one page -------------------------------------------------------------------------------
+    def encode(self, image: np.ndarray, words: Sequence[str], boxes: Sequence[Sequence[int]]):
+        """Boxes scaled to the 0..1000 grid with int(v * 1000 / size), tokenised, truncated / padded to 512."""
+        width, height = image.shape[1], image.shape[0]
+        ws, hs = 1000 / width, 1000 / height
+        norm = [scale_bounding_box(b, ws, hs) for b in boxes]
+        for b in norm:
+            if min(b) < 0 or max(b) > 1000:
+                raise IndexError("The `bbox` coordinate values should be within 0-1000 range.")
+        return self.tokenizer.encode_page(list(words), norm, MAX_LENGTH)
+
+    @staticmethod
+    def _frame(image) -> np.ndarray:
+        a = np.asarray(image)
+        if a.ndim == 2:
+            a = np.repeat(a[:, :, None], 3, axis=2)
+        if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8:
+            raise ValueError(f"page image must be H x W x 3 uint8, got {a.shape} {a.dtype}")
+        return np.ascontiguousarray(a)
+
+    def _predict_pages(self, images, words, boxes) -> List[List[Dict[str, Any]]]:
+        pages = [self._frame(im) for im in images]
+        enc = [self.encode(p, w, b) for p, w, b in zip(pages, words, boxes)]
+        ids = np.stack([e[0] for e in enc])
+        bbox = np.stack([e[1] for e in enc])
+        mask = np.stack([e[2] for e in enc])
+        logits = np.asarray(self._logits(pages, ids, bbox, mask), np.float32)
+        out = []
+        for row in logits:
+            z = row.astype(np.float64) - float(row.max())
+            p = np.exp(z) / np.exp(z).sum()
+            k = int(row.argmax())
+            out.append([{"label": self.id2label[k], "score": float(p[k])}])
+        return out
+
+    def predict_document_image(self, image: np.ndarray, words: Sequence[str], boxes: Sequence[Sequence[int]],
+                               top_k: int = 1) -> List[Dict[str, Any]]:
+        """transformers.py:300-361: [{"label", "score"}] of one page (as there, one entry whatever ``top_k``)."""
+        return self._predict_pages([image], [words], [boxes])[0]
+
+    def predict(self, documents, words: Optional[List[List[str]]] = None, boxes: Optional[List[List[List[int]]]] = None,
+                batch_size: Optional[int] = None):
+        """transformers.py:174-298.  ``documents``: objects with ``.tensor`` and a ``.tags`` dict — their
+        ``tags["classification"]`` is set and they are returned — or plain frames, for which the predictions are returned."""
+        if batch_size is None:
+            batch_size = self.batch_size
+        if len(documents) == 0:
+            return documents
+        assert words is not None and boxes is not None, "words and boxes must be provided for sequence classification"
+        assert len(documents) == len(words) == len(boxes), "documents, words and boxes must have the same length"
+        plain = not hasattr(documents[0], "tensor")
+        frames = [d if plain else d.tensor for d in documents]
+        predictions: List[List[Dict[str, Any]]] = []
+        for s in range(0, len(frames), max(int(batch_size), 1)):
+            e = s + max(int(batch_size), 1)
+            predictions.extend(self._predict_pages(frames[s:e], words[s:e], boxes[s:e]))
+        formatted = [{"label": p[0]["label"], "score": p[0]["score"], "details": {el["label"]: el["score"] for el in p}}
+                     for p in predictions]
+        if plain:
+            return formatted
+        for document, f in zip(documents, formatted):
+            document.tags["classification"] = f
+        return documents
+
+    def close(self):
+        m = getattr(self, "model", None)
+        if m is not None and hasattr(m, "close"):
+            m.close()

@@ -1,0 +1,140 @@
+"""LayoutLMv3 page classifier model: binding of the ``mhip_layoutlmv3_*`` entry points (include/marie_hip.h).
+
+reference: ``LayoutLMv3ForSequenceClassification`` of the transformers library as ``TransformersDocumentClassifier`` drives it
+(marie/components/document_classifier/transformers.py:159-172, :300-361).  The tokeniser and the classifier surface are in
+``document_classifier.py``; this file is the model handle: pages + token ids + boxes + mask in, logits (and, for tests, the
+last hidden states and the resized pages) out.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Optional, Sequence
+
+import numpy as np
+
+from ._lib import PREC_F16, Context, CropDesc, LayoutLMv3Config, ModelHandle, check, load
+
+# config.json keys that map one to one onto mhip_layoutlmv3_config fields
+_CONFIG_KEYS = {"hidden_size": "hidden", "num_hidden_layers": "layers", "num_attention_heads": "heads",
+                "intermediate_size": "ffn", "vocab_size": "vocab", "type_vocab_size": "type_vocab",
+                "max_position_embeddings": "max_position_embeddings",
+                "max_2d_position_embeddings": "max_2d_position_embeddings", "coordinate_size": "coordinate_size",
+                "shape_size": "shape_size", "input_size": "input_size", "patch_size": "patch", "rel_pos_bins": "rel_pos_bins",
+                "max_rel_pos": "max_rel_pos", "rel_2d_pos_bins": "rel_2d_pos_bins", "max_rel_2d_pos": "max_rel_2d_pos",
+                "layer_norm_eps": "layer_norm_eps", "pad_token_id": "pad_id"}
+
+
+def default_config(lib=None, **overrides) -> LayoutLMv3Config:
+    """The base checkpoint's configuration (``mhip_layoutlmv3_default_config``), fields overridden by keyword."""
+    cfg = LayoutLMv3Config()
+    rc = (lib or load()).mhip_layoutlmv3_default_config(C.byref(cfg))
+    if rc:
+        raise ValueError(f"mhip_layoutlmv3_default_config -> {rc}")
+    for k, v in overrides.items():
+        if not hasattr(cfg, k):
+            raise ValueError(f"unknown LayoutLMv3 config field {k}")
+        setattr(cfg, k, v)
+    return cfg
+
+
+def config_from_hf(hf: dict, lib=None) -> LayoutLMv3Config:
+    """``config.json`` of a LayoutLMv3 checkpoint -> ``LayoutLMv3Config``.  What the kernels do not cover is refused here or at
+    create: no text-only / image-only variants, no attention without both relative biases."""
+    for flag in ("visual_embed", "text_embed", "has_relative_attention_bias", "has_spatial_attention_bias"):
+        if not hf.get(flag, True):
+            raise ValueError(f"LayoutLMv3 config with {flag}=false is not supported")
+    if hf.get("hidden_act", "gelu") != "gelu":
+        raise ValueError(f"LayoutLMv3 hidden_act {hf.get('hidden_act')!r} is not supported")
+    if hf.get("num_channels", 3) != 3:
+        raise ValueError("LayoutLMv3 num_channels must be 3")
+    cfg = default_config(lib)
+    for k, f in _CONFIG_KEYS.items():
+        if k in hf:
+            setattr(cfg, f, hf[k])
+    if "id2label" in hf:
+        cfg.num_labels = len(hf["id2label"])
+    elif "num_labels" in hf:
+        cfg.num_labels = int(hf["num_labels"])
+    return cfg
+
+
+def _vp(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None else C.c_void_p(0)
+
+
+def pack_pages(pages: Sequence[np.ndarray]):
+    """Pages (H x W x 3 uint8, any sizes) -> one packed buffer and its ``CropDesc`` array."""
+    descs = (CropDesc * len(pages))()
+    total = 0
+    for i, p in enumerate(pages):
+        if p.ndim != 3 or p.shape[2] != 3 or p.dtype != np.uint8:
+            raise ValueError(f"page {i}: expected an H x W x 3 uint8 array, got {p.shape} {p.dtype}")
+        h, w = p.shape[:2]
+        descs[i] = CropDesc(total, h, w, w * 3, 3)
+        total += (h * w * 3 + 255) // 256 * 256
+    packed = np.zeros((total,), np.uint8)
+    for i, p in enumerate(pages):
+        packed[descs[i].src_offset: descs[i].src_offset + p.size] = np.ascontiguousarray(p).reshape(-1)
+    return packed, descs
+
+
+class LayoutLMv3Model(ModelHandle):
+    def __init__(self, ctx: Context, state: Optional[Dict[str, np.ndarray]], config: LayoutLMv3Config,
+                 precision: int = PREC_F16):
+        self.cfg, self.precision = config, int(precision)
+        super().__init__(ctx, "layoutlmv3", self.precision, C.byref(config))
+        self.seq_len = self.lib.mhip_layoutlmv3_seq_len(C.byref(config))
+        if state is not None:
+            self.load_state(state)
+
+    def _inputs(self, n, ids, bbox, mask):
+        T = self.cfg.max_text
+        ids = np.ascontiguousarray(ids, np.int32).reshape(n, T)
+        bbox = np.ascontiguousarray(bbox, np.int32).reshape(n, T, 4)
+        mask = np.ascontiguousarray(mask, np.int32).reshape(n, T)
+        return ids, bbox, mask
+
+    def classify_device(self, base_ptr: int, descs, n: int, ids, bbox, mask) -> np.ndarray:
+        """n pages inside one device buffer -> logits (n, num_labels), one model call."""
+        ids, bbox, mask = self._inputs(n, ids, bbox, mask)
+        logits = np.empty((n, self.cfg.num_labels), np.float32)
+        check(self.ctx.h, self.lib.mhip_layoutlmv3_classify(self.h, C.c_void_p(base_ptr), descs, n, _vp(ids), _vp(bbox),
+                                                            _vp(mask), _vp(logits)), "mhip_layoutlmv3_classify")
+        return logits
+
+    def forward_host(self, pages: Sequence[np.ndarray], ids, bbox, mask, want_hidden: bool = False,
+                     want_resized: bool = False) -> dict:
+        """Host pages -> {"logits"} (+ "hidden" (n, seq_len, hidden) fp32: the last hidden states, every row;
+        + "resized" (n, input_size, input_size, 3) uint8)."""
+        n = len(pages)
+        packed, descs = pack_pages(pages)
+        ids, bbox, mask = self._inputs(n, ids, bbox, mask)
+        S = self.cfg.input_size
+        logits = np.empty((n, self.cfg.num_labels), np.float32)
+        hidden = np.empty((n, self.seq_len, self.cfg.hidden), np.float32) if want_hidden else None
+        resized = np.empty((n, S, S, 3), np.uint8) if want_resized else None
+        check(self.ctx.h, self.lib.mhip_layoutlmv3_hidden_host(self.h, _vp(packed), packed.size, descs, n, _vp(ids), _vp(bbox),
+                                                               _vp(mask), _vp(logits), _vp(hidden), _vp(resized)),
+              "mhip_layoutlmv3_hidden_host")
+        out = {"logits": logits}
+        if want_hidden:
+            out["hidden"] = hidden
+        if want_resized:
+            out["resized"] = resized
+        return out
+
+
+def attention_bias_host(ctx: Context, precision: int, q, k, v, pos, x, y, valid, w1, wx, wy, max_1d: int = 128,
+                        max_2d: int = 256) -> np.ndarray:
+    """The biased attention kernel alone (``mhip_attention_bias_host``): q / k / v (n_tok, heads * 64) fp32, per-token
+    position / x / y / valid, the three head-major bias matrices -> (n_tok, heads * 64) fp32."""
+    q, k, v = (np.ascontiguousarray(a, np.float32) for a in (q, k, v))
+    n_tok, D = q.shape
+    pos, x, y, valid = (np.ascontiguousarray(a, np.int32) for a in (pos, x, y, valid))
+    w1, wx, wy = (np.ascontiguousarray(a, np.float32) for a in (w1, wx, wy))
+    out = np.empty((n_tok, D), np.float32)
+    check(ctx.h, ctx.lib.mhip_attention_bias_host(ctx.h, int(precision), D // 64, n_tok, _vp(q), _vp(k), _vp(v), _vp(pos),
+                                                  _vp(x), _vp(y), _vp(valid), _vp(w1), _vp(wx), _vp(wy), w1.shape[1],
+                                                  int(max_1d), wx.shape[1], int(max_2d), _vp(out)),
+          "mhip_attention_bias_host")
+    return out

@@ -710,3 +710,107 @@ def make_overlay_state(seed: int = 0, ngf: int = 64) -> Dict[str, np.ndarray]:
         st[name + ".weight_orig"], st[name + ".bias"] = w, b
         st[name + ".weight_u"], st[name + ".weight_v"] = u.astype(np.float32), v.astype(np.float32)
     return st
+
+
+# ------------------------------------------------------------------------------------------------ LayoutLMv3
+def make_layoutlmv3_state(seed: int = 0, hidden: int = 768, layers: int = 12, heads: int = 12, ffn: int = 3072,
+                          vocab: int = 50265, type_vocab: int = 1, max_position_embeddings: int = 514,
+                          max_2d_position_embeddings: int = 1024, coordinate_size: int = 128, shape_size: int = 128,
+                          input_size: int = 224, rel_pos_bins: int = 32, rel_2d_pos_bins: int = 64, num_labels: int = 7,
+                          logit_gain: float = 24.0) -> Dict[str, np.ndarray]:
+    """Seeded LayoutLMv3ForSequenceClassification weights under the Hugging Face state-dict key names
+    (``layoutlmv3.embeddings.word_embeddings.weight`` ... ``classifier.out_proj.bias``), with trained-like magnitudes: unit-scale
+    projections, LayerNorm gains around one, relative-position biases of a few units (they are divided by 8 with the scores).
+    ``logit_gain`` scales ``classifier.out_proj`` so that the class decision of a page has a margin a reduced-precision run
+    keeps (the pooled vector after tanh has entries of order one: logits spread over about ``logit_gain``)."""
+    D, F, H = hidden, ffn, heads
+    rng = np.random.Generator(np.random.PCG64(seed + 15485863))
+
+    def uni(shape, bound):
+        return rng.uniform(-bound, bound, size=shape).astype(np.float32)
+
+    def ln(prefix):
+        st[prefix + ".weight"] = rng.uniform(0.7, 1.3, size=(D,)).astype(np.float32)
+        st[prefix + ".bias"] = uni((D,), 0.1)
+
+    st: Dict[str, np.ndarray] = {}
+    e = "layoutlmv3.embeddings."
+    st[e + "word_embeddings.weight"] = uni((vocab, D), 1.0)
+    st[e + "token_type_embeddings.weight"] = uni((type_vocab, D), 0.2)
+    st[e + "position_embeddings.weight"] = uni((max_position_embeddings, D), 0.5)
+    st[e + "x_position_embeddings.weight"] = uni((max_2d_position_embeddings, coordinate_size), 0.5)
+    st[e + "y_position_embeddings.weight"] = uni((max_2d_position_embeddings, coordinate_size), 0.5)
+    st[e + "h_position_embeddings.weight"] = uni((max_2d_position_embeddings, shape_size), 0.5)
+    st[e + "w_position_embeddings.weight"] = uni((max_2d_position_embeddings, shape_size), 0.5)
+    ln(e + "LayerNorm")
+    g = input_size // 16
+    st["layoutlmv3.patch_embed.proj.weight"] = uni((D, 3, 16, 16), np.sqrt(3.0 / 768))
+    st["layoutlmv3.patch_embed.proj.bias"] = uni((D,), 0.1)
+    st["layoutlmv3.cls_token"] = uni((1, 1, D), 0.5)
+    st["layoutlmv3.pos_embed"] = uni((1, g * g + 1, D), 0.5)
+    ln("layoutlmv3.LayerNorm")
+    ln("layoutlmv3.norm")
+    st["layoutlmv3.encoder.rel_pos_bias.weight"] = uni((H, rel_pos_bins), 4.0)
+    st["layoutlmv3.encoder.rel_pos_x_bias.weight"] = uni((H, rel_2d_pos_bins), 4.0)
+    st["layoutlmv3.encoder.rel_pos_y_bias.weight"] = uni((H, rel_2d_pos_bins), 4.0)
+    for l in range(layers):
+        p = f"layoutlmv3.encoder.layer.{l}."
+        st[p + "attention.self.query.weight"] = uni((D, D), 2.0 * np.sqrt(3.0 / D))
+        st[p + "attention.self.key.weight"] = uni((D, D), 2.0 * np.sqrt(3.0 / D))
+        st[p + "attention.self.value.weight"] = uni((D, D), np.sqrt(3.0 / D))
+        st[p + "attention.output.dense.weight"] = uni((D, D), np.sqrt(3.0 / D))
+        for n in ("attention.self.query", "attention.self.key", "attention.self.value", "attention.output.dense"):
+            st[p + n + ".bias"] = uni((D,), 0.1)
+        ln(p + "attention.output.LayerNorm")
+        st[p + "intermediate.dense.weight"] = uni((F, D), np.sqrt(3.0 / D))
+        st[p + "intermediate.dense.bias"] = uni((F,), 0.1)
+        st[p + "output.dense.weight"] = uni((D, F), np.sqrt(3.0 / F))
+        st[p + "output.dense.bias"] = uni((D,), 0.1)
+        ln(p + "output.LayerNorm")
+    st["classifier.dense.weight"] = uni((D, D), np.sqrt(3.0 / D))
+    st["classifier.dense.bias"] = uni((D,), 0.1)
+    st["classifier.out_proj.weight"] = uni((num_labels, D), logit_gain * np.sqrt(3.0 / D))
+    st["classifier.out_proj.bias"] = uni((num_labels,), 0.1)
+    return st
+
+
+def write_synthetic_bpe(directory: str, seed: int = 0, n_merges: int = 2500) -> Dict[str, int]:
+    """A small RoBERTa-style byte-level BPE vocabulary in ``directory`` (``vocab.json`` + ``merges.txt``): the four special
+    tokens at ids 0..3 (``<s>``, ``<pad>``, ``</s>``, ``<unk>``), the 256 byte symbols, then ``n_merges`` seeded merges of
+    symbols that exist (pairs drawn among letters, digits and the leading-space marker, so OCR-like words do merge).
+    Returns the vocabulary."""
+    import json
+    import os
+
+    from .document_classifier import bytes_to_unicode
+
+    rng = np.random.Generator(np.random.PCG64(seed + 32452843))
+    b2u = bytes_to_unicode()
+    vocab = {"<s>": 0, "<pad>": 1, "</s>": 2, "<unk>": 3}
+    for b in range(256):
+        vocab[b2u[b]] = len(vocab)
+    common = [b2u[ord(c)] for c in "abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789.,$-'/"] + [b2u[ord(" ")]]
+    symbols = list(common)
+    merges = []
+    seen = set()
+    while len(merges) < n_merges:
+        # mostly pairs of single characters (they occur in any word), some pairs with earlier merges (multi-level merges)
+        pool_a = common if rng.random() < 0.7 else symbols
+        pool_b = common if rng.random() < 0.7 else symbols
+        a = pool_a[int(rng.integers(len(pool_a)))]
+        b = pool_b[int(rng.integers(len(pool_b)))]
+        if b.startswith(b2u[ord(" ")]) or (a, b) in seen or (a + b) in vocab:
+            continue
+        seen.add((a, b))
+        merges.append((a, b))
+        vocab[a + b] = len(vocab)
+        if len(a + b) <= 6:
+            symbols.append(a + b)
+    os.makedirs(directory, exist_ok=True)
+    with open(os.path.join(directory, "vocab.json"), "w", encoding="utf-8") as f:
+        json.dump(vocab, f, ensure_ascii=False)
+    with open(os.path.join(directory, "merges.txt"), "w", encoding="utf-8") as f:
+        f.write("#version: 0.2\n")
+        for a, b in merges:
+            f.write(f"{a} {b}\n")
+    return vocab
