@@ -10,12 +10,6 @@
 
 #include "common.h"
 
-#define CHECK_LAUNCH(ctx, what)                                                                              \
-  do {                                                                                                       \
-    hipError_t _e = hipGetLastError();                                                                       \
-    if (_e != hipSuccess) return mhip_fail((ctx), MHIP_EHIP, what " launch: %s", hipGetErrorString(_e));    \
-  } while (0)
-
 namespace {
 
 __global__ void beam_init_kernel(BeamState st, int* anc0, int anc_ld) {

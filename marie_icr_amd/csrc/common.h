@@ -33,7 +33,7 @@ enum MhipKernelId {
   MHIP_K_IGEMM_S128 = 15,   // conv_igemm_kernel<.., 1128, ..> 128 x 128 tile (few-row GEMMs)
   MHIP_K_IGEMM_PATCH = 16,  // conv3x3_patch_kernel            3x3 / pad 1 convolutions
   MHIP_K_CROSS_ATTN = 17,   // decoder encoder-attention over the encoder tokens themselves (absorbed K / V projections)
-  MHIP_K_ATTN_BIAS = 18,    // attn_bias_f16_kernel / attn_bias_simple_f32_kernel: attention with a relative-position bias and a key mask
+  MHIP_K_ATTN_BIAS = 18,    // the biased instances of the MHIP_K_ATTN_FLASH kernels (attn_flash.hip): relative-position bias and key mask
   MHIP_K_COUNT = 19
 };
 
@@ -136,6 +136,13 @@ void mhip_prof_end(mhip_ctx* ctx, int kid, hipEvent_t e0);
     if ((ctx)->profiling) mhip_prof_begin((ctx), (kid), &_e0); \
     __VA_ARGS__;                                      \
     if ((ctx)->profiling) mhip_prof_end((ctx), (kid), _e0);    \
+  } while (0)
+
+// after the launch(es) of a launcher: CHECK_LAUNCH(ctx, "name");
+#define CHECK_LAUNCH(ctx, what)                                                                              \
+  do {                                                                                                       \
+    hipError_t _e = hipGetLastError();                                                                       \
+    if (_e != hipSuccess) return mhip_fail((ctx), MHIP_EHIP, what " launch: %s", hipGetErrorString(_e));    \
   } while (0)
 
 // ------------------------------------------------------------------ conv / GEMM launcher
@@ -277,7 +284,7 @@ int mhip_launch_token_init_split(mhip_ctx* ctx, void* hi, void* lo, const float*
 int mhip_launch_ln_finalize(mhip_ctx* ctx, const float* stats, int chunks, int ld, float* rstd, float* mur, int rows, int D, float eps);
 int mhip_launch_split_f16(mhip_ctx* ctx, const float* in, void* hi, void* lo, long long n);
 int mhip_launch_join_f16(mhip_ctx* ctx, const void* hi, const void* lo, float* out, long long n);
-// softmax(Q K^T) V for `images` x `heads` independent (head_dim 64) problems; q is pre-scaled by head_dim^-0.5 * log2(e).
+// (attn_flash.hip) softmax(Q K^T) V for `images` x `heads` independent (head_dim 64) problems; q is pre-scaled by head_dim^-0.5 * log2(e).
 struct AttnDesc {
   const void* q = nullptr;    // [images*npad_q][ldq] T, head h at column h*64
   const void* k = nullptr;    // [images*npad_k][ldk] T
@@ -446,7 +453,7 @@ int mhip_launch_beam_select(mhip_ctx* ctx, const BeamState& st, int cur, int ste
 // best hypothesis per crop -> tokens_out [bsz][max_len + 1] (padded), lengths_out [bsz], scores_out [bsz] (device arrays)
 int mhip_launch_beam_best(mhip_ctx* ctx, const BeamState& st, int* tokens_out, int* lengths_out, float* scores_out);
 // ------------------------------------------------------------------ LayoutLMv3 ops (layoutlmv3_ops.hip)
-// Attention with a learned relative-position bias and a key mask.  Every token carries a code p | x << 12 | y << 22 (p: 1-d
+// Attention with a learned relative-position bias and a key mask (attn_flash.hip).  Every token carries a code p | x << 12 | y << 22 (p: 1-d
 // position, x: x0, y: y1 of its box); a score takes tab[h][kp + dp - qp] + tab[h][off_x + kx + dx - qx] + tab[h][off_y + ky + dx - qy]
 // (already scaled as the pre-scaled q is).  A masked key carries p = 2 dp + 1 in kcode: entries [2 dp + 1, 3 dp + 1] of the 1-d
 // table hold MHIP_ATTN_MASKED, so the mask costs no instruction of its own.

@@ -730,12 +730,6 @@ __global__ void subsample2_kernel(const T* __restrict__ in, T* __restrict__ out,
 
 }  // namespace
 
-#define CHECK_LAUNCH(ctx, what)                                                                              \
-  do {                                                                                                       \
-    hipError_t _e = hipGetLastError();                                                                       \
-    if (_e != hipSuccess) return mhip_fail((ctx), MHIP_EHIP, what " launch: %s", hipGetErrorString(_e));    \
-  } while (0)
-
 void mhip_rpn_cell_anchors(const float sizes[5], const float ratios[3], float out[5][3][4]) {
   for (int l = 0; l < 5; ++l)
     for (int a = 0; a < 3; ++a) {

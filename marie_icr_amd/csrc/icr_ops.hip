@@ -314,12 +314,6 @@ unsigned grid_for(long long total) {
 
 }  // namespace
 
-#define CHECK_LAUNCH(what)                                                                          \
-  do {                                                                                              \
-    hipError_t e_ = hipGetLastError();                                                              \
-    if (e_ != hipSuccess) return mhip_fail(ctx, MHIP_EHIP, what " launch: %s", hipGetErrorString(e_)); \
-  } while (0)
-
 int mhip_launch_conv_gray_first(mhip_ctx* ctx, int precision, int in_is_u8, const void* img, int B, int H, int W,
                                 int C, const float* w9xC, const float* scale, const float* bias, void* out) {
   if (B < 1 || H < 1 || W < 1 || C < 1 || C > 64) return mhip_fail(ctx, MHIP_EINVAL, "conv_gray_first: bad shape");
@@ -334,7 +328,7 @@ int mhip_launch_conv_gray_first(mhip_ctx* ctx, int precision, int in_is_u8, cons
     if (in_is_u8) L(float, uint8_t); else L(float, float);
   }
 #undef L
-  CHECK_LAUNCH("conv_gray_first");
+  CHECK_LAUNCH(ctx, "conv_gray_first");
   return 0;
 }
 
@@ -348,7 +342,7 @@ int mhip_launch_maxpool_s21_p01(mhip_ctx* ctx, int precision, const void* in, vo
   else
     PROF_LAUNCH(ctx, MHIP_K_IMAGE_OPS, hipLaunchKernelGGL((maxpool_s21_p01_kernel<float>), dim3(grid), dim3(256), 0,
                                                           ctx->stream, (const float*)in, (float*)out, B, H, W, C));
-  CHECK_LAUNCH("maxpool_s21");
+  CHECK_LAUNCH(ctx, "maxpool_s21");
   return 0;
 }
 
@@ -361,7 +355,7 @@ int mhip_launch_avgpool_hw(mhip_ctx* ctx, int precision, const void* in, void* o
   else
     PROF_LAUNCH(ctx, MHIP_K_IMAGE_OPS, hipLaunchKernelGGL((avgpool_hw_kernel<float>), dim3(grid), dim3(256), 0,
                                                           ctx->stream, (const float*)in, (float*)out, B, HW, C));
-  CHECK_LAUNCH("avgpool");
+  CHECK_LAUNCH(ctx, "avgpool");
   return 0;
 }
 
@@ -370,7 +364,7 @@ int mhip_launch_tps_sample(mhip_ctx* ctx, const uint8_t* crops, const float* cpr
   if (B < 1 || H < 2 || W < 2 || F < 2 || F + 3 > 64) return mhip_fail(ctx, MHIP_EINVAL, "tps_sample: bad shape");
   PROF_LAUNCH(ctx, MHIP_K_IMAGE_OPS, hipLaunchKernelGGL(tps_sample_kernel, dim3(B), dim3(256), 0, ctx->stream, crops,
                                                         cprime, inv_delta_c, p_hat, out, H, W, F));
-  CHECK_LAUNCH("tps_sample");
+  CHECK_LAUNCH(ctx, "tps_sample");
   return 0;
 }
 
@@ -384,7 +378,7 @@ int mhip_launch_attn_context(mhip_ctx* ctx, int precision, const float* hproj, c
   else
     PROF_LAUNCH(ctx, MHIP_K_ATTN, hipLaunchKernelGGL((attn_context_kernel<float>), dim3(B), dim3(256), 0, ctx->stream,
                                                      hproj, hp, ld_hp, score_w, (const float*)H, (float*)ctx_out, Tn));
-  CHECK_LAUNCH("attn_context");
+  CHECK_LAUNCH(ctx, "attn_context");
   return 0;
 }
 
@@ -397,7 +391,7 @@ int mhip_launch_attn_cell(mhip_ctx* ctx, int precision, const float* gctx, const
   else
     PROF_LAUNCH(ctx, MHIP_K_ATTN, hipLaunchKernelGGL((attn_cell_kernel<float>), dim3(B), dim3(256), 0, ctx->stream,
                                                      gctx, ghid, ld_hp, w_onehot, chars, c, (float*)h));
-  CHECK_LAUNCH("attn_cell");
+  CHECK_LAUNCH(ctx, "attn_cell");
   return 0;
 }
 
@@ -405,7 +399,7 @@ int mhip_launch_argmax_rows(mhip_ctx* ctx, const float* logits, int ld, int C, i
   if (B < 1 || C < 1 || ld < C) return mhip_fail(ctx, MHIP_EINVAL, "argmax_rows: bad shape");
   PROF_LAUNCH(ctx, MHIP_K_ATTN,
               hipLaunchKernelGGL(argmax_rows_kernel, dim3(B), dim3(64), 0, ctx->stream, logits, ld, C, idx));
-  CHECK_LAUNCH("argmax_rows");
+  CHECK_LAUNCH(ctx, "argmax_rows");
   return 0;
 }
 
@@ -413,6 +407,6 @@ int mhip_launch_rowmax_softmax(mhip_ctx* ctx, const float* logits, int rows, int
   if (rows < 1 || C < 1) return mhip_fail(ctx, MHIP_EINVAL, "rowmax_softmax: bad shape");
   PROF_LAUNCH(ctx, MHIP_K_ATTN, hipLaunchKernelGGL(rowmax_softmax_kernel, dim3(rows), dim3(64), 0, ctx->stream, logits,
                                                    rows, C, idx, pmax));
-  CHECK_LAUNCH("rowmax_softmax");
+  CHECK_LAUNCH(ctx, "rowmax_softmax");
   return 0;
 }

@@ -491,12 +491,6 @@ __global__ void ancestry_kernel(const int* __restrict__ anc_old, int* __restrict
 
 }  // namespace
 
-#define CHECK_LAUNCH(ctx, what)                                                                              \
-  do {                                                                                                       \
-    hipError_t _e = hipGetLastError();                                                                       \
-    if (_e != hipSuccess) return mhip_fail((ctx), MHIP_EHIP, what " launch: %s", hipGetErrorString(_e));    \
-  } while (0)
-
 int mhip_launch_layernorm2(mhip_ctx* ctx, int precision, const float* x, const float* g, const float* b, float* y_f32,
                            void* y_t, int rows, int D, float eps) {
   if (D % 256 != 0 || D > 1024 || rows <= 0) return mhip_fail(ctx, MHIP_EINVAL, "layernorm2: D=%d rows=%d", D, rows);

@@ -11,7 +11,8 @@ import json
 import sys
 from collections import defaultdict
 
-FAMILIES = (("conv_igemm", "conv_igemm_kernel"), ("conv3x3_patch", "conv3x3_patch"), ("attn_flash", "attn_flash"),
+# first match wins: the biased attention kernels are the attn_flash kernels instantiated with their BiasArgs argument
+FAMILIES = (("conv_igemm", "conv_igemm_kernel"), ("conv3x3_patch", "conv3x3_patch"), ("attn_bias", "BiasArgs"), ("attn_flash", "attn_flash"),
             ("cross_attn", "cross_attn_kernel"), ("absorb_q", "absorb_q_kernel"), ("absorb_v", "absorb_v_kernel"),
             ("decode_attn", "decode_attn"), ("layernorm", "layernorm"), ("beam_candidates", "beam_candidates"))
 
