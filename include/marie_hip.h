@@ -565,6 +565,38 @@ int mhip_layoutlmv3_classify(mhip_layoutlmv3* m, const uint8_t* base_dev, const 
 int mhip_layoutlmv3_hidden_host(mhip_layoutlmv3* m, const uint8_t* pages_host, size_t pages_bytes,
                                 const mhip_crop_desc* pages_desc, int n, const int32_t* ids, const int32_t* bbox,
                                 const int32_t* attention_mask, float* logits_out, float* hidden_out, uint8_t* resized_out);
+/* ---- LayoutLMv3 token tagging (the model call of the document indexer) ---------------------------------------------------- */
+/* replaces: the model call of TransformersDocumentIndexer.inference, marie/components/document_indexer/transformers.py:519-568
+ * (LayoutLMv3ForTokenClassification of the transformers library on the windows of a page, logits.argmax(-1) and
+ * logits.softmax(-1) at the arg-max).  The same object serves it: finalize reads the head kind from the state dict,
+ *   classifier.weight [num_labels][hidden] + classifier.bias                -> the linear head (the library's for num_labels < 10);
+ *   classifier.dense.* + classifier.out_proj.*                              -> dense, tanh, out_proj (num_labels >= 10; the shapes
+ *                                                                              of the sequence-classification head).
+ * A model with the linear head answers mhip_layoutlmv3_classify / _hidden_host with MHIP_ESTATE; one with the dense head
+ * serves both tasks.  The token head covers mhip_layoutlmv3_max_token_labels(hidden) labels (64, or what fits the LDS beside
+ * W_o: 48 at hidden 768, 35 at hidden 1024); more are MHIP_EINVAL from tag / tag_host, and from finalize for the linear head,
+ * which serves no other task.  The classifier entry points have no such limit.
+ * n_win windows of text (ids / bbox / attention_mask [n_win][max_text], as for classify) over n_pages page images: window w
+ * belongs to page window_page[w] (0 <= window_page[w] < n_pages <= n_win); resize, patch matrix and patch projection run
+ * once per page.  -> label_out int32 [n_win][max_text] (lowest index of the largest logit), score_out fp32 [n_win][max_text]
+ * (its soft-max probability, 1 / sum exp(z - z_max)), and, only when logits_out != NULL, the logits fp32
+ * [n_win][max_text][num_labels] (host arrays).  Rows of padding carry what the library computes for them.                  */
+int mhip_layoutlmv3_tag(mhip_layoutlmv3* m, const uint8_t* base_dev, const mhip_crop_desc* pages_host, int n_pages,
+                        const int32_t* window_page, int n_win, const int32_t* ids, const int32_t* bbox,
+                        const int32_t* attention_mask, int32_t* label_out, float* score_out, float* logits_out);
+/* the same on one packed host buffer of pages                                                                               */
+int mhip_layoutlmv3_tag_host(mhip_layoutlmv3* m, const uint8_t* pages_host, size_t pages_bytes, const mhip_crop_desc* pages_desc,
+                             int n_pages, const int32_t* window_page, int n_win, const int32_t* ids, const int32_t* bbox,
+                             const int32_t* attention_mask, int32_t* label_out, float* score_out, float* logits_out);
+/* labels the token head covers at this hidden width (host only, no ctx)                                                      */
+int mhip_layoutlmv3_max_token_labels(int hidden);
+/* The token head alone on host inputs (parity tests): hidden fp32 [rows][D] (D a multiple of 256 up to 1024).  dense_w [D][D] +
+ * dense_b [D] non-NULL: the dense head (hidden and dense_w rounded to the precision's element type, the product through the
+ * GEMM the model uses, then tanh); NULL: the linear head.  out_w [L][D], out_b [L] -> label_out int32 [rows], score_out fp32
+ * [rows], logits_out fp32 [rows][L] or NULL.  Everything after the dense product is fp32 in both precisions.               */
+int mhip_token_head_host(mhip_ctx* ctx, int precision, int rows, int D, int L, const float* hidden, const float* dense_w,
+                         const float* dense_b, const float* out_w, const float* out_b, int32_t* label_out, float* score_out,
+                         float* logits_out);
 /* The biased attention kernel alone on host inputs (parity tests): softmax(q k^T / 8 + (B1[h][b(pj - pi)] + Bx[h][b(xj - xi)]
  * + By[h][b(yj - yi)]) / 8 + mask) v for `heads` heads of 64.  q, k, v fp32 [n_tok][heads*64] (rounded to the precision's
  * element type), pos / x / y int32 [n_tok], valid int32 [n_tok] (0: masked as a key), w1 [heads][bins_1d], wx / wy

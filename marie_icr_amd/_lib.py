@@ -139,8 +139,12 @@ _SIGNATURES = (
     ("mhip_layoutlmv3_arena", _i, [_vp, C.POINTER(_vp), C.POINTER(_sz)]),
     ("mhip_layoutlmv3_seq_len", _i, [_vp]),
     ("mhip_layoutlmv3_bucket", _i, [_i, _i, _i]),
+    ("mhip_layoutlmv3_max_token_labels", _i, [_i]),
     ("mhip_layoutlmv3_classify", _i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     ("mhip_layoutlmv3_hidden_host", _i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("mhip_layoutlmv3_tag", _i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("mhip_layoutlmv3_tag_host", _i, [_vp, _vp, _sz, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("mhip_token_head_host", _i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("mhip_attention_bias_host", _i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     ("mhip_max_page_size", _i, [_i, _i, _i, _i, C.c_double, C.POINTER(_i), C.POINTER(_i)]),
     ("mhip_resize_area_u8", _i, [_vp, _vp, _i, _i, _i, C.c_size_t, _vp, _i, _i]),

@@ -473,10 +473,11 @@ void mhip_attn_bias_fold(const float* w1, const float* wx, const float* wy, int 
 int mhip_relative_position_bucket(int relative_position, int num_buckets, int max_distance);
 struct Lmv3EmbedDesc {
   const int* tok = nullptr;          // [pages*max_text][8]: id, position id, x0, y0, x1, y1, h, w (clipped)
+  const int* win_page = nullptr;     // [pages]: the page image whose patch rows a window of text takes (identity: one window a page)
   const void* word = nullptr;        // [vocab][D] T
   const float *type0 = nullptr, *pos = nullptr, *xe = nullptr, *ye = nullptr, *he = nullptr, *we = nullptr;
   const float *g_text = nullptr, *b_text = nullptr;      // embeddings.LayerNorm
-  const float* patches = nullptr;    // [pages*(n_vis - 1)][D] fp32: patch projection + bias + position rows 1..
+  const float* patches = nullptr;    // [page images*(n_vis - 1)][D] fp32: patch projection + bias + position rows 1..
   const float* cls = nullptr;        // [D]: cls_token + position row 0
   const float *g_vis = nullptr, *b_vis = nullptr;        // norm (eps_vis)
   const float *g_all = nullptr, *b_all = nullptr;        // LayoutLMv3Model.LayerNorm
@@ -489,6 +490,19 @@ int mhip_launch_lmv3_embed(mhip_ctx* ctx, int precision, const Lmv3EmbedDesc& d)
 // logits[page] = out_proj(tanh(dense(h[page*npad]))), fp32 weights
 int mhip_launch_lmv3_head(mhip_ctx* ctx, const float* h, int pages, int npad, int D, const float* dw, const float* db,
                           const float* ow, const float* ob, int labels, float* logits);
+// The token-classification head and its decision: row r of `rows` is x[(r / seg) * seg_stride + r % seg] (seg text rows out of
+// every seg_stride rows); logits = W_o f(x) + b_o with f = tanh (use_tanh: x is the dense product + bias) or the identity;
+// label[r] = lowest index of the maximum, score[r] = its soft-max probability, logits[r][L] only when asked for.  All fp32.
+struct TokenHeadDesc {
+  const float* x = nullptr;          // [..][D]
+  const float *w = nullptr, *b = nullptr;      // [L][D], [L]
+  int* label = nullptr;              // [rows]
+  float* score = nullptr;            // [rows]
+  float* logits = nullptr;           // [rows][L] or nullptr
+  int rows = 0, seg = 1, seg_stride = 1, D = 0, L = 0, use_tanh = 0;
+};
+int mhip_token_head_max_labels(int D);
+int mhip_launch_token_head(mhip_ctx* ctx, const TokenHeadDesc& d);
 size_t mhip_pil_resize_fragments_scratch(const mhip_crop_desc* descs, int n, int dh, int dw, int filter);
 int mhip_pil_resize_fragments(mhip_ctx* ctx, const uint8_t* base_dev, const mhip_crop_desc* descs, int n, uint8_t* dst, int dh,
                               int dw, int filter, void* scratch, size_t scratch_bytes);

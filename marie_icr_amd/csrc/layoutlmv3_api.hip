@@ -1,11 +1,16 @@
-// layoutlmv3_api.hip — the LayoutLMv3 page classifier behind the C ABI.
+// layoutlmv3_api.hip — the LayoutLMv3 page classifier and token tagger behind the C ABI.
 //
 // Host-side counterpart of LayoutLMv3ForSequenceClassification.forward (transformers/models/layoutlmv3/modeling_layoutlmv3.py:
 // LayoutLMv3Model.forward, LayoutLMv3Encoder.forward, LayoutLMv3Layer, LayoutLMv3ClassificationHead) as
 // TransformersDocumentClassifier drives it (marie/components/document_classifier/transformers.py, task
-// "text-classification-multimodal").  One object = one weight arena + the launch sequence.
+// "text-classification-multimodal"), and of LayoutLMv3ForTokenClassification.forward as TransformersDocumentIndexer drives it
+// (marie/components/document_indexer/transformers.py:519-568).  One object = one weight arena + the launch sequence.
 //
-// Row layout: every page owns `npad` rows (seq_len rounded up to 8): max_text text rows, then cls + patches, then zeros.
+// A call runs `n` windows of text over `n_pages` page images: window w attends to the patch rows of page win_page[w].  The
+// classifier has one window a page (the identity map); the tagger cuts a long page into several windows that share the page's
+// resize, patch matrix and patch projection.
+//
+// Row layout: every window owns `npad` rows (seq_len rounded up to 8): max_text text rows, then cls + patches, then zeros.
 // Padded text rows stay in the sequence and are masked as keys, as the library does.
 // The hidden states h are fp32 (every LayerNorm writes them, and their copy in the GEMM element type); a post-LN layer is
 //   q|k = ht Wqk^T + b        V^T = Wv ht^T            (the value bias moves into the output projection: soft-max rows sum to 1)
@@ -22,6 +27,7 @@ struct mhip_layoutlmv3 {
   TensorStore store;
   Arena arena;
   bool ready = false;
+  int head = -1;      // HEAD_DENSE / HEAD_LINEAR; -1 until finalize (or, after alloc_arena, until the first call reads it back)
   size_t esz() const { return precision == MHIP_PREC_F16 ? 2 : 4; }
   int grid() const { return cfg.input_size / cfg.patch; }
   int n_vis() const { return grid() * grid() + 1; }
@@ -34,40 +40,56 @@ struct mhip_layoutlmv3 {
 namespace {
 
 constexpr float LOG2E = 1.4426950408889634f;
+// classifier.dense + classifier.out_proj (sequence classification; token classification with num_labels >= 10), or one
+// classifier.weight (token classification with num_labels < 10)
+enum { HEAD_DENSE = 0, HEAD_LINEAR = 1 };
+enum { TASK_CLASSIFY = 0, TASK_TAG = 1 };
 const char* PFX = "layoutlmv3.";
 
 std::string lyr(int i, const char* s) { return "layoutlmv3.encoder.layer." + std::to_string(i) + "." + s; }
 std::string blk(int i, const char* s) { return "l" + std::to_string(i) + "." + s; }
 
-// the buffers of one call of n pages
+// the buffers of one call of n windows over n_pages pages
 struct Lmv3Run {
   uint8_t* resized = nullptr;
   void* frag_scratch = nullptr;
   size_t frag_bytes = 0;
-  int* tok = nullptr;
+  int *tok = nullptr, *win_page = nullptr, *labels = nullptr;
   uint32_t *qcode = nullptr, *kcode = nullptr;
-  float *pe = nullptr, *h = nullptr, *y = nullptr, *logits = nullptr;
+  float *pe = nullptr, *h = nullptr, *y = nullptr, *logits = nullptr, *scores = nullptr, *dense = nullptr;
   char *ht = nullptr, *qk = nullptr, *vt = nullptr, *ao = nullptr, *hid = nullptr;
 };
 
-void lmv3_carve(const mhip_layoutlmv3* m, Carver& ws, const mhip_crop_desc* pages, int n, Lmv3Run* r) {
+// task: TASK_CLASSIFY (logits [n][labels]) or TASK_TAG (labels / scores [n][max_text]; token logits when want_logits; the
+// dense product of the text rows when the head is the dense one)
+void lmv3_carve(const mhip_layoutlmv3* m, Carver& ws, const mhip_crop_desc* pages, int n_pages, int n, int task, bool want_logits,
+                Lmv3Run* r) {
   const mhip_layoutlmv3_config& c = m->cfg;
-  const size_t es = m->esz(), D = c.hidden, R = (size_t)n * m->npad(), S = c.input_size;
-  r->resized = ws.take<uint8_t>((size_t)n * S * S * 3);
-  r->frag_bytes = mhip_pil_resize_fragments_scratch(pages, n, c.input_size, c.input_size, MHIP_PIL_BILINEAR);
+  const size_t es = m->esz(), D = c.hidden, R = (size_t)n * m->npad(), S = c.input_size, NPAT = m->n_vis() - 1, K0 = 3 * c.patch * c.patch;
+  r->resized = ws.take<uint8_t>((size_t)n_pages * S * S * 3);
+  r->frag_bytes = mhip_pil_resize_fragments_scratch(pages, n_pages, c.input_size, c.input_size, MHIP_PIL_BILINEAR);
   r->frag_scratch = ws.take(r->frag_bytes);
   r->tok = ws.take<int>((size_t)n * c.max_text * 8 * 4);
+  r->win_page = ws.take<int>((size_t)n * 4);
   r->qcode = ws.take<uint32_t>((R + 128) * 4);     // + slack: the last page's final query block / key tile reads past its rows
   r->kcode = ws.take<uint32_t>((R + 128) * 4);
-  r->pe = ws.take<float>((size_t)n * (m->n_vis() - 1) * D * 4);
+  r->pe = ws.take<float>((size_t)n_pages * NPAT * D * 4);
   r->h = ws.take<float>(R * D * 4);
   r->y = ws.take<float>(R * D * 4);
-  r->logits = ws.take<float>((size_t)n * c.num_labels * 4);
+  const size_t TR = (size_t)n * c.max_text;      // text rows
+  if (task == TASK_CLASSIFY) {
+    r->logits = ws.take<float>((size_t)n * c.num_labels * 4);
+  } else {
+    r->labels = ws.take<int>(TR * 4);
+    r->scores = ws.take<float>(TR * 4);
+    r->logits = want_logits ? ws.take<float>(TR * c.num_labels * 4) : nullptr;
+    r->dense = m->head == HEAD_DENSE ? ws.take<float>(TR * D * 4) : nullptr;
+  }
   r->ht = ws.take(R * D * es);
   r->qk = ws.take((R + 128) * 2 * D * es);
   r->vt = ws.take((D * R + 128) * es);
   r->ao = ws.take(R * D * es);
-  r->hid = ws.take(R * std::max<size_t>(c.ffn, 3 * c.patch * c.patch) * es);     // mlp hidden; also the patch matrix
+  r->hid = ws.take(R * std::max<size_t>(c.ffn, K0) * es);     // mlp hidden; also the patch matrix (n_pages <= n, fewer rows than R)
 }
 
 // token ids / boxes / mask of n pages -> the embedding kernel's gather rows and the attention codes (host)
@@ -112,8 +134,8 @@ int lmv3_prepare(mhip_layoutlmv3* m, int n, const int32_t* ids, const int32_t* b
   return MHIP_OK;
 }
 
-// pages already resized in run.resized; codes staged -> hidden states in run.h / run.ht and logits in run.logits
-int lmv3_forward(mhip_layoutlmv3* m, int n, const Lmv3Run& run) {
+// pages already resized in run.resized; codes and the window -> page map staged -> hidden states of n windows in run.h / run.ht
+int lmv3_forward(mhip_layoutlmv3* m, int n_pages, int n, const Lmv3Run& run) {
   mhip_ctx* ctx = m->ctx;
   const mhip_layoutlmv3_config& c = m->cfg;
   const int D = c.hidden, F = c.ffn, prec = m->precision, NP = m->npad(), G = m->grid(), P = c.patch, S = c.input_size;
@@ -125,16 +147,16 @@ int lmv3_forward(mhip_layoutlmv3* m, int n, const Lmv3Run& run) {
   MHIP_HIP(ctx, hipMemsetAsync(run.vt + (size_t)D * R * es, 0, 128 * es, ctx->stream));
   // (x / 255 - 0.5) / 0.5 -> 16 x 16 patches -> projection + bias + position rows 1.. (row q takes position row q % G^2)
   const int K0 = 3 * P * P, np = G * G;
-  if ((rc = mhip_launch_patchify(ctx, prec, run.resized, n, S, S, G, G, P, 0, 127.5f, 127.5f, run.hid, K0))) return rc;
+  if ((rc = mhip_launch_patchify(ctx, prec, run.resized, n_pages, S, S, G, G, P, 0, 127.5f, 127.5f, run.hid, K0))) return rc;
   {
     ConvDesc cd;
     cd.in = run.hid; cd.w = a.d("pe_w"); cd.bias = a.d<float>("pe_b"); cd.out = run.pe; cd.res = a.d<float>("pos_vis");
-    cd.B = 1; cd.H = 1; cd.W = n * np; cd.Cin = K0; cd.N = D; cd.out_f32 = 1;
+    cd.B = 1; cd.H = 1; cd.W = n_pages * np; cd.Cin = K0; cd.N = D; cd.out_f32 = 1;
     cd.row_period = np; cd.row_stride = np; cd.row_offset = 0;
     if ((rc = mhip_launch_conv_igemm(ctx, prec, cd))) return rc;
   }
   Lmv3EmbedDesc e;
-  e.tok = run.tok; e.word = a.d("word"); e.type0 = a.d<float>("type0"); e.pos = a.d<float>("pos");
+  e.tok = run.tok; e.win_page = run.win_page; e.word = a.d("word"); e.type0 = a.d<float>("type0"); e.pos = a.d<float>("pos");
   e.xe = a.d<float>("xe"); e.ye = a.d<float>("ye"); e.he = a.d<float>("he"); e.we = a.d<float>("we");
   e.g_text = a.d<float>("ln_text_g"); e.b_text = a.d<float>("ln_text_b");
   e.patches = run.pe; e.cls = a.d<float>("cls");
@@ -160,28 +182,115 @@ int lmv3_forward(mhip_layoutlmv3* m, int n, const Lmv3Run& run) {
     if ((rc = mhip_gemm(ctx, prec, run.hid, a.d(blk(i, "fc2_w")), (long long)R, D, F, nullptr, a.d<float>(blk(i, "fc2_b")), run.y, ACT_NONE, 1, run.h))) return rc;
     if ((rc = mhip_launch_layernorm2(ctx, prec, run.y, a.d<float>(blk(i, "ln2_g")), a.d<float>(blk(i, "ln2_b")), run.h, run.ht, (int)R, D, c.layer_norm_eps))) return rc;
   }
-  return mhip_launch_lmv3_head(ctx, run.h, n, NP, D, a.d<float>("cd_w"), a.d<float>("cd_b"), a.d<float>("co_w"), a.d<float>("co_b"),
-                               c.num_labels, run.logits);
-}
-
-int lmv3_check_call(mhip_layoutlmv3* m, const mhip_crop_desc* pages, int n, const int32_t* ids, const int32_t* bbox,
-                    const int32_t* mask) {
-  if (!m->ready) return mhip_fail(m->ctx, MHIP_ESTATE, "layoutlmv3: weights not finalized");
-  if (!pages || !ids || !bbox || !mask || n < 1 || n > 4096) return mhip_fail(m->ctx, MHIP_EINVAL, "layoutlmv3: bad arguments (n = %d)", n);
   return MHIP_OK;
 }
 
-// resize + stage the host tables + forward; the caller has carved `run`
-int lmv3_run(mhip_layoutlmv3* m, const uint8_t* base_dev, const mhip_crop_desc* pages, int n, const std::vector<int>& tok,
-             const std::vector<uint32_t>& qcode, const std::vector<uint32_t>& kcode, const Lmv3Run& run) {
+// the head of LayoutLMv3ForSequenceClassification on row 0 of every window -> run.logits
+int lmv3_head_rows0(mhip_layoutlmv3* m, int n, const Lmv3Run& run) {
+  const Arena& a = m->arena;
+  return mhip_launch_lmv3_head(m->ctx, run.h, n, m->npad(), m->cfg.hidden, a.d<float>("cd_w"), a.d<float>("cd_b"), a.d<float>("co_w"),
+                               a.d<float>("co_b"), m->cfg.num_labels, run.logits);
+}
+
+// the head of LayoutLMv3ForTokenClassification on the text rows of every window (sequence_output[:, :seq_length]) and the
+// decision on its logits -> run.labels / run.scores (/ run.logits)
+int lmv3_head_tokens(mhip_layoutlmv3* m, int n, const Lmv3Run& run) {
+  const mhip_layoutlmv3_config& c = m->cfg;
+  const Arena& a = m->arena;
+  const int D = c.hidden, T = c.max_text, NP = m->npad();
+  int rc;
+  TokenHeadDesc t;
+  t.w = a.d<float>("co_w"); t.b = a.d<float>("co_b"); t.label = run.labels; t.score = run.scores; t.logits = run.logits;
+  t.rows = n * T; t.seg = T; t.D = D; t.L = c.num_labels;
+  if (m->head == HEAD_DENSE) {
+    // dense on the text rows only, in the model's precision, fp32 out; tanh belongs to the head kernel
+    for (int w = 0; w < n; ++w)
+      if ((rc = mhip_gemm(m->ctx, m->precision, run.ht + (size_t)w * NP * D * m->esz(), a.d("cdt_w"), T, D, D, nullptr, a.d<float>("cd_b"),
+                          run.dense + (size_t)w * T * D, ACT_NONE, 1)))
+        return rc;
+    t.x = run.dense; t.seg_stride = T; t.use_tanh = 1;
+  } else {
+    t.x = run.h; t.seg_stride = NP; t.use_tanh = 0;
+  }
+  return mhip_launch_token_head(m->ctx, t);
+}
+
+// the head kind of a model whose arena was filled by another rank
+int lmv3_head_kind(mhip_layoutlmv3* m) {
+  if (m->head >= 0) return MHIP_OK;
   mhip_ctx* ctx = m->ctx;
-  const int S = m->cfg.input_size;
-  int rc = mhip_pil_resize_fragments(ctx, base_dev, pages, n, run.resized, S, S, MHIP_PIL_BILINEAR, run.frag_scratch, run.frag_bytes);
+  int kind = -1;
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  MHIP_HIP(ctx, hipMemcpyAsync(&kind, m->arena.d("head_kind"), 4, hipMemcpyDeviceToHost, ctx->stream));
+  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (kind != HEAD_DENSE && kind != HEAD_LINEAR) return mhip_fail(m->ctx, MHIP_ESTATE, "layoutlmv3: the arena holds no weights yet");
+  m->head = kind;
+  return MHIP_OK;
+}
+
+int lmv3_check_call(mhip_layoutlmv3* m, const mhip_crop_desc* pages, int n, const int32_t* ids, const int32_t* bbox,
+                    const int32_t* mask, int task) {
+  if (!m->ready) return mhip_fail(m->ctx, MHIP_ESTATE, "layoutlmv3: weights not finalized");
+  if (!pages || !ids || !bbox || !mask || n < 1 || n > 4096) return mhip_fail(m->ctx, MHIP_EINVAL, "layoutlmv3: bad arguments (n = %d)", n);
+  int rc = lmv3_head_kind(m);
+  if (rc) return rc;
+  if (task == TASK_CLASSIFY && m->head != HEAD_DENSE)
+    return mhip_fail(m->ctx, MHIP_ESTATE, "layoutlmv3: the weights hold the linear token head (classifier.weight): no sequence classification");
+  // the row-0 head serves any label count; only the token head has a limit, so it is checked where the task is known
+  if (task == TASK_TAG && m->cfg.num_labels > mhip_token_head_max_labels(m->cfg.hidden))
+    return mhip_fail(m->ctx, MHIP_EINVAL, "layoutlmv3: num_labels %d beyond the %d the token head covers at hidden %d", m->cfg.num_labels,
+                     mhip_token_head_max_labels(m->cfg.hidden), m->cfg.hidden);
+  return MHIP_OK;
+}
+
+int lmv3_check_pages(mhip_layoutlmv3* m, const mhip_crop_desc* pages, int n_pages, size_t pages_bytes) {
+  for (int i = 0; i < n_pages; ++i)
+    if (pages[i].h < 1 || pages[i].w < 1 || pages[i].row_stride < pages[i].w * 3 ||
+        pages[i].src_offset + (size_t)(pages[i].h - 1) * pages[i].row_stride + (size_t)pages[i].w * 3 > pages_bytes)
+      return mhip_fail(m->ctx, MHIP_EINVAL, "layoutlmv3: page %d lies outside the buffer", i);
+  return MHIP_OK;
+}
+
+// the window -> page map of a tag call: every window names one of the n_pages pages
+int lmv3_check_windows(mhip_layoutlmv3* m, const int32_t* window_page, int n_win, int n_pages, std::vector<int>& map) {
+  if (!window_page || n_pages < 1 || n_pages > n_win) return mhip_fail(m->ctx, MHIP_EINVAL, "layoutlmv3: %d pages for %d windows", n_pages, n_win);
+  map.assign(window_page, window_page + n_win);
+  for (int w = 0; w < n_win; ++w)
+    if (map[w] < 0 || map[w] >= n_pages) return mhip_fail(m->ctx, MHIP_EINVAL, "layoutlmv3: window %d names page %d of %d", w, map[w], n_pages);
+  return MHIP_OK;
+}
+
+// resize + stage the host tables + forward + the task's head; the caller has carved `run`
+int lmv3_run(mhip_layoutlmv3* m, const uint8_t* base_dev, const mhip_crop_desc* pages, int n_pages, const std::vector<int>& win_page,
+             const std::vector<int>& tok, const std::vector<uint32_t>& qcode, const std::vector<uint32_t>& kcode, int task,
+             const Lmv3Run& run) {
+  mhip_ctx* ctx = m->ctx;
+  const int S = m->cfg.input_size, n = (int)win_page.size();
+  int rc = mhip_pil_resize_fragments(ctx, base_dev, pages, n_pages, run.resized, S, S, MHIP_PIL_BILINEAR, run.frag_scratch, run.frag_bytes);
   if (rc) return rc;
   if ((rc = mhip_stage_h2d(ctx, run.tok, tok.data(), tok.size() * 4))) return rc;
+  if ((rc = mhip_stage_h2d(ctx, run.win_page, win_page.data(), win_page.size() * 4))) return rc;
   if ((rc = mhip_stage_h2d(ctx, run.qcode, qcode.data(), qcode.size() * 4))) return rc;
   if ((rc = mhip_stage_h2d(ctx, run.kcode, kcode.data(), kcode.size() * 4))) return rc;
-  return lmv3_forward(m, n, run);
+  if ((rc = lmv3_forward(m, n_pages, n, run))) return rc;
+  return task == TASK_CLASSIFY ? lmv3_head_rows0(m, n, run) : lmv3_head_tokens(m, n, run);
+}
+
+std::vector<int> lmv3_identity(int n) {
+  std::vector<int> v(n);
+  for (int i = 0; i < n; ++i) v[i] = i;
+  return v;
+}
+
+// labels / scores (/ logits) of a tag call to the host
+int lmv3_tag_out(mhip_layoutlmv3* m, int n_win, const Lmv3Run& run, int32_t* label_out, float* score_out, float* logits_out) {
+  mhip_ctx* ctx = m->ctx;
+  const size_t TR = (size_t)n_win * m->cfg.max_text;
+  MHIP_HIP(ctx, hipMemcpyAsync(label_out, run.labels, TR * 4, hipMemcpyDeviceToHost, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(score_out, run.scores, TR * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (logits_out) MHIP_HIP(ctx, hipMemcpyAsync(logits_out, run.logits, TR * m->cfg.num_labels * 4, hipMemcpyDeviceToHost, ctx->stream));
+  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return MHIP_OK;
 }
 
 }  // namespace
@@ -206,6 +315,8 @@ extern "C" int mhip_layoutlmv3_seq_len(const mhip_layoutlmv3_config* cfg) {
   const int g = cfg->input_size / cfg->patch;
   return cfg->max_text + g * g + 1;
 }
+
+extern "C" int mhip_layoutlmv3_max_token_labels(int hidden) { return mhip_token_head_max_labels(hidden); }
 
 extern "C" int mhip_layoutlmv3_bucket(int relative_position, int num_buckets, int max_distance) {
   return mhip_relative_position_bucket(relative_position, num_buckets, max_distance);
@@ -261,8 +372,12 @@ extern "C" int mhip_layoutlmv3_create(mhip_ctx* ctx, int precision, const mhip_l
     a.take(blk(i, "fc2_w"), D * F * es); a.take(blk(i, "fc2_b"), D * 4);
     a.take(blk(i, "ln2_g"), D * 4); a.take(blk(i, "ln2_b"), D * 4);
   }
+  // the head: dense (fp32 for the row-0 head, the element type for the token head's GEMM) + out_proj, or — in the out_proj
+  // entries — the linear token head; which of the two, for the ranks that receive the arena filled
   a.take("cd_w", D * D * 4); a.take("cd_b", D * 4);
   a.take("co_w", (size_t)c.num_labels * D * 4); a.take("co_b", (size_t)c.num_labels * 4);
+  a.take("cdt_w", D * D * es);
+  a.take("head_kind", 4);
   *out = m;
   return MHIP_OK;
 }
@@ -282,6 +397,7 @@ extern "C" int mhip_layoutlmv3_set_tensor(mhip_layoutlmv3* m, const char* key, c
   if (ends("position_ids") || ends("visual_bbox")) return MHIP_OK;      // buffers older checkpoints carry; rebuilt from the config
   if (k.rfind(PFX, 0) != 0 && k.rfind("classifier.", 0) != 0) return mhip_fail(m->ctx, MHIP_EINVAL, "unknown state_dict key %s", key);
   m->ready = false;
+  m->head = -1;
   return m->store.set(m->ctx, k, data, shape, ndim);
 }
 
@@ -289,6 +405,7 @@ extern "C" int mhip_layoutlmv3_alloc_arena(mhip_layoutlmv3* m) {
   if (!m) return MHIP_EINVAL;
   int rc = m->arena.alloc(m->ctx);
   if (rc) return rc;
+  m->head = -1;
   m->ready = true;
   return MHIP_OK;
 }
@@ -330,12 +447,18 @@ extern "C" int mhip_layoutlmv3_finalize(mhip_layoutlmv3* m) {
   const HostTensor* r1 = st.find(ctx, std::string(PFX) + "encoder.rel_pos_bias.weight", {c.heads, c.rel_pos_bins});
   const HostTensor* rx = st.find(ctx, std::string(PFX) + "encoder.rel_pos_x_bias.weight", {c.heads, c.rel_2d_pos_bins});
   const HostTensor* ry = st.find(ctx, std::string(PFX) + "encoder.rel_pos_y_bias.weight", {c.heads, c.rel_2d_pos_bins});
-  const HostTensor* cdw = st.find(ctx, "classifier.dense.weight", {D, D});
-  const HostTensor* cdb = st.find(ctx, "classifier.dense.bias", {D});
-  const HostTensor* cow = st.find(ctx, "classifier.out_proj.weight", {c.num_labels, D});
-  const HostTensor* cob = st.find(ctx, "classifier.out_proj.bias", {c.num_labels});
+  const bool linear = st.t.count("classifier.weight") != 0;
+  const HostTensor* cdw = linear ? nullptr : st.find(ctx, "classifier.dense.weight", {D, D});
+  const HostTensor* cdb = linear ? nullptr : st.find(ctx, "classifier.dense.bias", {D});
+  const HostTensor* cow = st.find(ctx, linear ? "classifier.weight" : "classifier.out_proj.weight", {c.num_labels, D});
+  const HostTensor* cob = st.find(ctx, linear ? "classifier.bias" : "classifier.out_proj.bias", {c.num_labels});
+  // a linear head serves token tagging only: refuse here what the token head does not cover
+  if (linear && c.num_labels > mhip_token_head_max_labels(D))
+    return mhip_fail(ctx, MHIP_EINVAL, "layoutlmv3: num_labels %d beyond the %d the token head covers at hidden %d", c.num_labels,
+                     mhip_token_head_max_labels(D), D);
+  if (linear && st.t.count("classifier.dense.weight")) return mhip_fail(ctx, MHIP_ESTATE, "layoutlmv3: the state holds both classifier.weight and classifier.dense");
   if (!word || !type || !pos || !xe || !ye || !he || !we || !ltg || !ltb || !lag || !lab || !lvg || !lvb || !pw || !pb || !cls ||
-      !pv || !r1 || !rx || !ry || !cdw || !cdb || !cow || !cob)
+      !pv || !r1 || !rx || !ry || (!linear && (!cdw || !cdb)) || !cow || !cob)
     return MHIP_ESTATE;
   Arena::put(prec, a.h("word"), word->data.data(), word->numel());
   memcpy(a.h("type0"), type->data.data(), D * 4);                  // token_type_ids are zeros on this path
@@ -394,10 +517,16 @@ extern "C" int mhip_layoutlmv3_finalize(mhip_layoutlmv3* m) {
     memcpy(a.h(blk(i, "fc2_b")), db->data.data(), D * 4);
     memcpy(a.h(blk(i, "ln2_g")), g2->data.data(), D * 4); memcpy(a.h(blk(i, "ln2_b")), b2->data.data(), D * 4);
   }
-  memcpy(a.h("cd_w"), cdw->data.data(), cdw->numel() * 4); memcpy(a.h("cd_b"), cdb->data.data(), D * 4);
+  if (!linear) {
+    memcpy(a.h("cd_w"), cdw->data.data(), cdw->numel() * 4); memcpy(a.h("cd_b"), cdb->data.data(), D * 4);
+    Arena::put(prec, a.h("cdt_w"), cdw->data.data(), cdw->numel());
+  }
+  const int kind = linear ? HEAD_LINEAR : HEAD_DENSE;
+  memcpy(a.h("head_kind"), &kind, 4);
   memcpy(a.h("co_w"), cow->data.data(), cow->numel() * 4); memcpy(a.h("co_b"), cob->data.data(), (size_t)c.num_labels * 4);
   int rc = a.upload(ctx);
   if (rc) return rc;
+  m->head = kind;
   m->ready = true;
   m->store.t.clear();
   return MHIP_OK;
@@ -408,15 +537,15 @@ extern "C" int mhip_layoutlmv3_classify(mhip_layoutlmv3* m, const uint8_t* base_
                                         const int32_t* ids, const int32_t* bbox, const int32_t* mask, float* logits_out) {
   if (!m || !base_dev || !logits_out) return MHIP_EINVAL;
   mhip_ctx* ctx = m->ctx;
-  int rc = lmv3_check_call(m, pages, n, ids, bbox, mask);
+  int rc = lmv3_check_call(m, pages, n, ids, bbox, mask, TASK_CLASSIFY);
   if (rc) return rc;
   MHIP_HIP(ctx, hipSetDevice(ctx->device));
   std::vector<int> tok;
   std::vector<uint32_t> qcode, kcode;
   if ((rc = lmv3_prepare(m, n, ids, bbox, mask, tok, qcode, kcode))) return rc;
   Lmv3Run run;
-  if ((rc = mhip_carve_workspace(ctx, [&](Carver& ws) { lmv3_carve(m, ws, pages, n, &run); }))) return rc;
-  if ((rc = lmv3_run(m, base_dev, pages, n, tok, qcode, kcode, run))) return rc;
+  if ((rc = mhip_carve_workspace(ctx, [&](Carver& ws) { lmv3_carve(m, ws, pages, n, n, TASK_CLASSIFY, false, &run); }))) return rc;
+  if ((rc = lmv3_run(m, base_dev, pages, n, lmv3_identity(n), tok, qcode, kcode, TASK_CLASSIFY, run))) return rc;
   MHIP_HIP(ctx, hipMemcpyAsync(logits_out, run.logits, (size_t)n * m->cfg.num_labels * 4, hipMemcpyDeviceToHost, ctx->stream));
   MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return MHIP_OK;
@@ -427,12 +556,9 @@ extern "C" int mhip_layoutlmv3_hidden_host(mhip_layoutlmv3* m, const uint8_t* pa
                                            const int32_t* mask, float* logits_out, float* hidden_out, uint8_t* resized_out) {
   if (!m || !pages_host || !pages_bytes) return MHIP_EINVAL;
   mhip_ctx* ctx = m->ctx;
-  int rc = lmv3_check_call(m, pages, n, ids, bbox, mask);
+  int rc = lmv3_check_call(m, pages, n, ids, bbox, mask, TASK_CLASSIFY);
   if (rc) return rc;
-  for (int i = 0; i < n; ++i)
-    if (pages[i].h < 1 || pages[i].w < 1 || pages[i].row_stride < pages[i].w * 3 ||
-        pages[i].src_offset + (size_t)(pages[i].h - 1) * pages[i].row_stride + (size_t)pages[i].w * 3 > pages_bytes)
-      return mhip_fail(ctx, MHIP_EINVAL, "layoutlmv3: page %d lies outside the buffer", i);
+  if ((rc = lmv3_check_pages(m, pages, n, pages_bytes))) return rc;
   MHIP_HIP(ctx, hipSetDevice(ctx->device));
   std::vector<int> tok;
   std::vector<uint32_t> qcode, kcode;
@@ -441,16 +567,115 @@ extern "C" int mhip_layoutlmv3_hidden_host(mhip_layoutlmv3* m, const uint8_t* pa
   uint8_t* base = nullptr;
   if ((rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
          base = ws.take<uint8_t>(pages_bytes);
-         lmv3_carve(m, ws, pages, n, &run);
+         lmv3_carve(m, ws, pages, n, n, TASK_CLASSIFY, false, &run);
        })))
     return rc;
   MHIP_HIP(ctx, hipMemcpyAsync(base, pages_host, pages_bytes, hipMemcpyHostToDevice, ctx->stream));
-  if ((rc = lmv3_run(m, base, pages, n, tok, qcode, kcode, run))) return rc;
+  if ((rc = lmv3_run(m, base, pages, n, lmv3_identity(n), tok, qcode, kcode, TASK_CLASSIFY, run))) return rc;
   const size_t D = m->cfg.hidden, S = m->cfg.input_size, seq = m->seq(), NP = m->npad();
   if (logits_out) MHIP_HIP(ctx, hipMemcpyAsync(logits_out, run.logits, (size_t)n * m->cfg.num_labels * 4, hipMemcpyDeviceToHost, ctx->stream));
   if (hidden_out)
     MHIP_HIP(ctx, hipMemcpy2DAsync(hidden_out, seq * D * 4, run.h, NP * D * 4, seq * D * 4, n, hipMemcpyDeviceToHost, ctx->stream));
   if (resized_out) MHIP_HIP(ctx, hipMemcpyAsync(resized_out, run.resized, (size_t)n * S * S * 3, hipMemcpyDeviceToHost, ctx->stream));
+  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return MHIP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------- token tagging
+extern "C" int mhip_layoutlmv3_tag(mhip_layoutlmv3* m, const uint8_t* base_dev, const mhip_crop_desc* pages, int n_pages,
+                                   const int32_t* window_page, int n_win, const int32_t* ids, const int32_t* bbox,
+                                   const int32_t* mask, int32_t* label_out, float* score_out, float* logits_out) {
+  if (!m || !base_dev || !label_out || !score_out) return MHIP_EINVAL;
+  mhip_ctx* ctx = m->ctx;
+  int rc = lmv3_check_call(m, pages, n_win, ids, bbox, mask, TASK_TAG);
+  if (rc) return rc;
+  std::vector<int> map, tok;
+  std::vector<uint32_t> qcode, kcode;
+  if ((rc = lmv3_check_windows(m, window_page, n_win, n_pages, map))) return rc;
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  if ((rc = lmv3_prepare(m, n_win, ids, bbox, mask, tok, qcode, kcode))) return rc;
+  Lmv3Run run;
+  if ((rc = mhip_carve_workspace(ctx, [&](Carver& ws) { lmv3_carve(m, ws, pages, n_pages, n_win, TASK_TAG, logits_out != nullptr, &run); })))
+    return rc;
+  if ((rc = lmv3_run(m, base_dev, pages, n_pages, map, tok, qcode, kcode, TASK_TAG, run))) return rc;
+  return lmv3_tag_out(m, n_win, run, label_out, score_out, logits_out);
+}
+
+extern "C" int mhip_layoutlmv3_tag_host(mhip_layoutlmv3* m, const uint8_t* pages_host, size_t pages_bytes,
+                                        const mhip_crop_desc* pages, int n_pages, const int32_t* window_page, int n_win,
+                                        const int32_t* ids, const int32_t* bbox, const int32_t* mask, int32_t* label_out,
+                                        float* score_out, float* logits_out) {
+  if (!m || !pages_host || !pages_bytes || !label_out || !score_out) return MHIP_EINVAL;
+  mhip_ctx* ctx = m->ctx;
+  int rc = lmv3_check_call(m, pages, n_win, ids, bbox, mask, TASK_TAG);
+  if (rc) return rc;
+  std::vector<int> map, tok;
+  std::vector<uint32_t> qcode, kcode;
+  if ((rc = lmv3_check_windows(m, window_page, n_win, n_pages, map))) return rc;
+  if ((rc = lmv3_check_pages(m, pages, n_pages, pages_bytes))) return rc;
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  if ((rc = lmv3_prepare(m, n_win, ids, bbox, mask, tok, qcode, kcode))) return rc;
+  Lmv3Run run;
+  uint8_t* base = nullptr;
+  if ((rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
+         base = ws.take<uint8_t>(pages_bytes);
+         lmv3_carve(m, ws, pages, n_pages, n_win, TASK_TAG, logits_out != nullptr, &run);
+       })))
+    return rc;
+  MHIP_HIP(ctx, hipMemcpyAsync(base, pages_host, pages_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = lmv3_run(m, base, pages, n_pages, map, tok, qcode, kcode, TASK_TAG, run))) return rc;
+  return lmv3_tag_out(m, n_win, run, label_out, score_out, logits_out);
+}
+
+// ---------------------------------------------------------------------------------------------------- the token head alone
+extern "C" int mhip_token_head_host(mhip_ctx* ctx, int precision, int rows, int D, int L, const float* hidden, const float* dense_w,
+                                    const float* dense_b, const float* out_w, const float* out_b, int32_t* label_out,
+                                    float* score_out, float* logits_out) {
+  if (!ctx || !hidden || !out_w || !out_b || !label_out || !score_out || (dense_w == nullptr) != (dense_b == nullptr)) return MHIP_EINVAL;
+  if (precision != MHIP_PREC_F16 && precision != MHIP_PREC_F32) return mhip_fail(ctx, MHIP_EINVAL, "unknown precision %d", precision);
+  if (rows < 1 || rows > (1 << 20) || D < 256 || D % 256 || D > 1024 || L < 1 || L > mhip_token_head_max_labels(D))
+    return mhip_fail(ctx, MHIP_EINVAL, "token_head: rows=%d D=%d labels=%d (D a multiple of 256 up to 1024, at most %d labels)", rows, D, L,
+                     D >= 256 ? mhip_token_head_max_labels(D) : 0);
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t es = precision == MHIP_PREC_F16 ? 2 : 4, RD = (size_t)rows * D;
+  const bool dense = dense_w != nullptr;
+  float *dx = nullptr, *dy = nullptr, *dob = nullptr, *dow = nullptr, *ddb = nullptr, *dscore = nullptr, *dlogits = nullptr;
+  char *dxt = nullptr, *ddw = nullptr;
+  int* dlabel = nullptr;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
+    dow = ws.take<float>((size_t)L * D * 4); dob = ws.take<float>((size_t)L * 4);
+    dlabel = ws.take<int>((size_t)rows * 4); dscore = ws.take<float>((size_t)rows * 4);
+    dlogits = logits_out ? ws.take<float>((size_t)rows * L * 4) : nullptr;
+    if (dense) {
+      dxt = ws.take((RD + 128 * (size_t)D) * es); ddw = ws.take((size_t)D * D * es); ddb = ws.take<float>((size_t)D * 4);
+      dy = ws.take<float>(RD * 4);
+    } else {
+      dx = ws.take<float>(RD * 4);
+    }
+  });
+  if (rc) return rc;
+  std::vector<char> xt, wt;
+  if (dense) {      // the GEMM's operands in the element type, as the model holds them
+    xt.resize(RD * es); wt.resize((size_t)D * D * es);
+    Arena::put(precision, xt.data(), hidden, RD);
+    Arena::put(precision, wt.data(), dense_w, (size_t)D * D);
+    MHIP_HIP(ctx, hipMemcpyAsync(dxt, xt.data(), xt.size(), hipMemcpyHostToDevice, ctx->stream));
+    MHIP_HIP(ctx, hipMemcpyAsync(ddw, wt.data(), wt.size(), hipMemcpyHostToDevice, ctx->stream));
+    MHIP_HIP(ctx, hipMemcpyAsync(ddb, dense_b, (size_t)D * 4, hipMemcpyHostToDevice, ctx->stream));
+  } else {
+    MHIP_HIP(ctx, hipMemcpyAsync(dx, hidden, RD * 4, hipMemcpyHostToDevice, ctx->stream));
+  }
+  MHIP_HIP(ctx, hipMemcpyAsync(dow, out_w, (size_t)L * D * 4, hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(dob, out_b, (size_t)L * 4, hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the sources are host temporaries in pageable memory
+  if (dense && (rc = mhip_gemm(ctx, precision, dxt, ddw, rows, D, D, nullptr, ddb, dy, ACT_NONE, 1))) return rc;
+  TokenHeadDesc t;
+  t.x = dense ? dy : dx; t.w = dow; t.b = dob; t.label = dlabel; t.score = dscore; t.logits = dlogits;
+  t.rows = rows; t.seg = rows; t.seg_stride = rows; t.D = D; t.L = L; t.use_tanh = dense ? 1 : 0;
+  if ((rc = mhip_launch_token_head(ctx, t))) return rc;
+  MHIP_HIP(ctx, hipMemcpyAsync(label_out, dlabel, (size_t)rows * 4, hipMemcpyDeviceToHost, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(score_out, dscore, (size_t)rows * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (logits_out) MHIP_HIP(ctx, hipMemcpyAsync(logits_out, dlogits, (size_t)rows * L * 4, hipMemcpyDeviceToHost, ctx->stream));
   MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return MHIP_OK;
 }

@@ -1,9 +1,10 @@
 // layoutlmv3_ops.hip — the pieces of LayoutLMv3 the ViT / TrOCR paths do not have: the tables of its learned relative-position
-// attention bias, the text + layout embedding gather, and the classification head.
+// attention bias, the text + layout embedding gather, the classification head and the token-classification head.
 //
 // Replaces, in transformers/models/layoutlmv3/modeling_layoutlmv3.py: LayoutLMv3Encoder._cal_1d_pos_emb / _cal_2d_pos_emb
 // (never materialised: see below), LayoutLMv3TextEmbeddings.forward, the LayerNorms of LayoutLMv3Model.forward /
-// forward_image, and LayoutLMv3ClassificationHead.forward.
+// forward_image, LayoutLMv3ClassificationHead.forward, and the head of LayoutLMv3ForTokenClassification.forward together with
+// the arg-max / soft-max the document indexer takes of its logits (marie/components/document_indexer/transformers.py:556-568).
 //
 // The bias of a score depends on (i, j) only through three integer differences, p_j - p_i, x0_j - x0_i, y1_j - y1_i, so
 // per head three difference-indexed tables replace the [heads][n][n] tensors the library builds (3 x 24 MB a page): they are
@@ -45,6 +46,7 @@ __device__ __forceinline__ void wave_layernorm(float4v v[4], int nv, int D, int 
 
 struct EmbedArgs {
   const int* tok;
+  const int* win_page;
   const void* word;
   const float *type0, *pos, *xe, *ye, *he, *we, *g_text, *b_text, *patches, *cls, *g_vis, *b_vis, *g_all, *b_all;
   float* h;
@@ -55,7 +57,8 @@ struct EmbedArgs {
 
 // one wave per row of the sequence: text rows gather word + token type + position + the six layout embeddings and take the
 // embeddings' LayerNorm, visual rows take the patch projection (or the cls row) and `norm`; both then take the model's
-// LayerNorm over the concatenated sequence.  Rows past the sequence (npad) are zeros.
+// LayerNorm over the concatenated sequence.  Rows past the sequence (npad) are zeros.  A "page" of rows is one window of text;
+// its patch rows are those of the page image win_page names (windows of one page share them).
 template <typename T>
 __global__ __launch_bounds__(256) void lmv3_embed_kernel(EmbedArgs a) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -93,7 +96,7 @@ __global__ __launch_bounds__(256) void lmv3_embed_kernel(EmbedArgs a) {
     wave_layernorm(v, nv, D, lane, a.g_text, a.b_text, a.eps);
   } else if (t < a.max_text + a.n_vis) {
     const int vi = t - a.max_text;
-    const float* src = vi == 0 ? a.cls : a.patches + ((size_t)page * (a.n_vis - 1) + vi - 1) * D;
+    const float* src = vi == 0 ? a.cls : a.patches + ((size_t)a.win_page[page] * (a.n_vis - 1) + vi - 1) * D;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       if (i < nv) v[i] = *(const float4v*)(src + (i * 64 + lane) * 4);
@@ -141,6 +144,92 @@ __global__ __launch_bounds__(256) void lmv3_head_kernel(const float* __restrict_
   }
 }
 
+// ------------------------------------------------------------------------------------------------------- token head
+// logits = W_o f(x) + b_o for every text row (f = tanh for the dense head, whose D x D product has run as a GEMM; identity for the
+// linear head), then the decision the indexer takes of them: label = lowest index of the maximum, score = 1 / sum exp(z - z_max).
+// fp32 throughout.  W_o is staged in LDS once per workgroup (rows of D + 8 floats: the eight labels a wave works on at a time
+// fall in eight different bank groups); a workgroup then takes TH_ROWS rows, a wave one row at a time: the row is read once
+// from HBM into LDS, eight lanes share a label (lane g sums k = g, g + 8, ...), eight labels a pass.
+constexpr int TH_ROWS = 32;        // rows per workgroup
+constexpr int TH_GROUP = 8;        // lanes per label
+constexpr int TH_PASSES = 8;       // passes of 64 / TH_GROUP labels: 64 labels at the most
+
+struct TokenHeadArgs {
+  const float* x;
+  const float *w, *b;
+  int* label;
+  float* score;
+  float* logits;
+  int rows, seg, seg_stride, D, L, use_tanh;
+};
+
+__global__ __launch_bounds__(256) void lmv3_token_head_kernel(TokenHeadArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float th_smem[];
+  const int D = a.D, L = a.L, ldw = D + 8;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane & (TH_GROUP - 1), jl = lane / TH_GROUP;
+  float* ws = th_smem;
+  float* xs = th_smem + (size_t)L * ldw + (size_t)wave * D;
+  for (int e = threadIdx.x * 4; e < L * D; e += 1024) {
+    const int j = e / D, k = e - j * D;
+    *(float4v*)(ws + (size_t)j * ldw + k) = *(const float4v*)(a.w + e);
+  }
+  const int row0 = blockIdx.x * TH_ROWS;
+  for (int it = 0; it < TH_ROWS / 4; ++it) {
+    const int r = row0 + it * 4 + wave;
+    const bool live = r < a.rows;
+    __syncthreads();                      // W_o staged (first turn); the previous row of this wave consumed
+    if (live) {
+      const float* x = a.x + ((size_t)(r / a.seg) * a.seg_stride + r % a.seg) * D;
+      for (int k = lane * 4; k < D; k += 256) {
+        float4v v = *(const float4v*)(x + k);
+        if (a.use_tanh) v = (float4v){tanhf(v[0]), tanhf(v[1]), tanhf(v[2]), tanhf(v[3])};
+        *(float4v*)(xs + k) = v;
+      }
+    }
+    __syncthreads();
+    if (!live) continue;                  // the barriers above are reached by every wave: TH_ROWS / 4 turns each
+    float z[TH_PASSES];
+    float best = -INFINITY;
+    int best_j = 0;
+#pragma unroll
+    for (int p = 0; p < TH_PASSES; ++p) {
+      z[p] = -INFINITY;
+      if (p * (64 / TH_GROUP) < L) {
+        const int j = p * (64 / TH_GROUP) + jl;
+        float acc = 0.f;
+        if (j < L) {
+          const float* wr = ws + (size_t)j * ldw;
+          for (int k = g; k < D; k += TH_GROUP) acc += wr[k] * xs[k];
+        }
+#pragma unroll
+        for (int o = TH_GROUP / 2; o; o >>= 1) acc += __shfl_xor(acc, o);
+        if (j < L) {
+          z[p] = acc + a.b[j];
+          if (a.logits && g == 0) a.logits[(size_t)r * L + j] = z[p];
+          if (z[p] > best) { best = z[p]; best_j = j; }
+        }
+      }
+    }
+    // the maximum over the eight label lanes, ties to the lowest index
+#pragma unroll
+    for (int o = TH_GROUP; o < 64; o <<= 1) {
+      const float ob = __shfl_xor(best, o);
+      const int oj = __shfl_xor(best_j, o);
+      if (ob > best || (ob == best && oj < best_j)) { best = ob; best_j = oj; }
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int p = 0; p < TH_PASSES; ++p)
+      if (p * (64 / TH_GROUP) + jl < L) s += expf(z[p] - best);
+#pragma unroll
+    for (int o = TH_GROUP; o < 64; o <<= 1) s += __shfl_xor(s, o);
+    if (lane == 0) {
+      a.label[r] = best_j;
+      a.score[r] = 1.f / s;
+    }
+  }
+}
+
 }  // namespace
 
 // LayoutLMv3Encoder.relative_position_bucket(bidirectional=True) of one difference.  The logarithmic half is evaluated in
@@ -179,10 +268,10 @@ void mhip_attn_bias_fold(const float* w1, const float* wx, const float* wy, int 
 
 int mhip_launch_lmv3_embed(mhip_ctx* ctx, int precision, const Lmv3EmbedDesc& d) {
   if (d.D % 256 != 0 || d.D > 1024 || d.pages <= 0 || d.coord % 4 || d.shape % 4 || 4 * d.coord + 2 * d.shape != d.D ||
-      d.npad < d.max_text + d.n_vis)
+      d.npad < d.max_text + d.n_vis || !d.win_page)
     return mhip_fail(ctx, MHIP_EINVAL, "lmv3_embed: D=%d coord=%d shape=%d", d.D, d.coord, d.shape);
   EmbedArgs a;
-  a.tok = d.tok; a.word = d.word; a.type0 = d.type0; a.pos = d.pos; a.xe = d.xe; a.ye = d.ye; a.he = d.he; a.we = d.we;
+  a.tok = d.tok; a.win_page = d.win_page; a.word = d.word; a.type0 = d.type0; a.pos = d.pos; a.xe = d.xe; a.ye = d.ye; a.he = d.he; a.we = d.we;
   a.g_text = d.g_text; a.b_text = d.b_text; a.patches = d.patches; a.cls = d.cls; a.g_vis = d.g_vis; a.b_vis = d.b_vis;
   a.g_all = d.g_all; a.b_all = d.b_all; a.h = d.h; a.ht = d.ht;
   a.rows = d.pages * d.npad; a.max_text = d.max_text; a.n_vis = d.n_vis; a.npad = d.npad; a.D = d.D; a.coord = d.coord;
@@ -199,5 +288,30 @@ int mhip_launch_lmv3_head(mhip_ctx* ctx, const float* h, int pages, int npad, in
   if (pages <= 0 || D > 1024 || labels < 1) return mhip_fail(ctx, MHIP_EINVAL, "lmv3_head: pages=%d D=%d labels=%d", pages, D, labels);
   PROF_LAUNCH(ctx, MHIP_K_VIT_OPS, hipLaunchKernelGGL(lmv3_head_kernel, dim3(pages), dim3(256), 0, ctx->stream, h, npad, D, dw, db, ow, ob, labels, logits));
   CHECK_LAUNCH(ctx, "lmv3_head");
+  return 0;
+}
+
+// labels the token head covers at width D: TH_PASSES passes of eight, and W_o (rows of D + 8 floats) beside the four rows of x in
+// the 160 KiB of LDS a workgroup may take
+int mhip_token_head_max_labels(int D) {
+  if (D < 4) return 0;
+  const long long room = (163840ll - 4ll * D * 4) / ((D + 8) * 4ll);
+  return (int)std::min<long long>(TH_PASSES * (64 / TH_GROUP), std::max<long long>(room, 0));
+}
+
+int mhip_launch_token_head(mhip_ctx* ctx, const TokenHeadDesc& d) {
+  if (d.rows <= 0 || d.D < 4 || d.D % 4 || d.L < 1 || d.L > mhip_token_head_max_labels(d.D) || d.seg < 1 || d.seg_stride < d.seg ||
+      !d.x || !d.w || !d.b || !d.label || !d.score)
+    return mhip_fail(ctx, MHIP_EINVAL, "token_head: rows=%d D=%d labels=%d (at most %d labels at this width)", d.rows, d.D, d.L,
+                     mhip_token_head_max_labels(d.D));
+  TokenHeadArgs a;
+  a.x = d.x; a.w = d.w; a.b = d.b; a.label = d.label; a.score = d.score; a.logits = d.logits;
+  a.rows = d.rows; a.seg = d.seg; a.seg_stride = d.seg_stride; a.D = d.D; a.L = d.L; a.use_tanh = d.use_tanh;
+  const size_t lds = ((size_t)d.L * (d.D + 8) + 4 * (size_t)d.D) * 4;
+  if (lds > 65536)      // per device and cheap: set on every such launch
+    MHIP_HIP(ctx, hipFuncSetAttribute((const void*)lmv3_token_head_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  dim3 grid((d.rows + TH_ROWS - 1) / TH_ROWS), block(256);
+  PROF_LAUNCH(ctx, MHIP_K_VIT_OPS, hipLaunchKernelGGL(lmv3_token_head_kernel, grid, block, lds, ctx->stream, a));
+  CHECK_LAUNCH(ctx, "token_head");
   return 0;
 }

@@ -151,6 +151,76 @@ class ByteLevelBPE:
                 self._cache[word] = ids
         return ids
 
+    def encode_word_offsets(self, word: str) -> Tuple[List[int], List[int]]:
+        """Sub-token ids of one OCR word and, per sub-token, the character offset inside the word at which it starts, as
+        ``LayoutLMv3TokenizerFast(..., return_offsets_mapping=True)`` reports it (``trim_offsets``: the leading-space marker
+        does not count, so a lone marker and the token after it both start at 0; the byte tokens of one character all start
+        at that character)."""
+        prefixed = not word.startswith(" ")
+        text = " " + word if prefixed else word
+        ids: List[int] = []
+        starts: List[int] = []
+        at = 0                                        # character index in ``text`` of the piece
+        for piece in split_gpt2(text):
+            owner: List[int] = []                     # character index of every byte of the piece
+            for ci, ch in enumerate(piece):
+                owner.extend([at + ci] * len(ch.encode("utf-8")))
+            sym = "".join(self._b2u[b] for b in piece.encode("utf-8"))
+            b = 0
+            for t in self._bpe(sym):
+                first, end = owner[b], owner[b + len(t) - 1] + 1
+                while first < end and text[first].isspace():      # trim_offsets
+                    first += 1
+                starts.append(max(first - (1 if prefixed else 0), 0))
+                ids.append(self.vocab.get(t, self.unk_id))
+                b += len(t)
+            at += len(piece)
+        return ids, starts
+
+    def encode_windows(self, words: Sequence[str], boxes: Sequence[Sequence[int]], max_length: int = MAX_LENGTH,
+                       stride: int = 128):
+        """``LayoutLMv3TokenizerFast(words, boxes=boxes, truncation=True, stride=128, padding="max_length", max_length=512,
+        return_overflowing_tokens=True, return_offsets_mapping=True)``: the sub-tokens of a page cut into windows of
+        ``max_length - 2`` that advance by ``max_length - 2 - stride``, each wrapped in ``<s>`` ... ``</s>`` and padded.
+        -> (input_ids [n][max_length], bbox [n][max_length][4], attention_mask [n][max_length] int32, first [n][max_length]
+        bool).  ``first`` is ``offset_mapping[:, 0] == 0``: what the indexer keeps as "not a sub-word" — the first sub-token(s)
+        of a word, and every special and padding token."""
+        if len(words) != len(boxes):
+            raise ValueError("words and boxes must have the same length")
+        room = max_length - 2
+        if not 0 <= stride < room:
+            raise ValueError(f"stride {stride} must lie in [0, {room})")
+        ids: List[int] = []
+        bbs: List[List[int]] = []
+        first: List[bool] = []
+        for w, b in zip(words, boxes):
+            sub, starts = self.encode_word_offsets(str(w))
+            ids.extend(sub)
+            bbs.extend([list(b)] * len(sub))
+            first.extend(st == 0 for st in starts)
+        spans, start = [], 0
+        while True:
+            end = min(start + room, len(ids))
+            spans.append((start, end))
+            if end == len(ids):
+                break
+            start += room - stride
+        n = len(spans)
+        input_ids = np.full((n, max_length), self.pad_id, np.int32)
+        bbox = np.zeros((n, max_length, 4), np.int32)
+        mask = np.zeros((n, max_length), np.int32)
+        is_first = np.ones((n, max_length), bool)
+        for k, (s0, e0) in enumerate(spans):
+            m = e0 - s0
+            input_ids[k, 0] = self.bos_id
+            input_ids[k, 1 + m] = self.eos_id
+            mask[k, :m + 2] = 1
+            if m:
+                input_ids[k, 1:1 + m] = ids[s0:e0]
+                bbox[k, 1:1 + m] = np.asarray(bbs[s0:e0], np.int64).reshape(m, 4)
+                is_first[k, 1:1 + m] = first[s0:e0]
+        return input_ids, bbox, mask, is_first
+
     def encode_page(self, words: Sequence[str], boxes: Sequence[Sequence[int]], max_length: int = MAX_LENGTH):
         """``LayoutLMv3Tokenizer(words, boxes=boxes, max_length=512, padding="max_length", truncation=True)``:
         (input_ids, bbox, attention_mask) as int32 arrays of max_length (x 4).  ``<s>``, ``</s>`` and ``<pad>`` carry

@@ -1,9 +1,11 @@
-"""LayoutLMv3 page classifier model: binding of the ``mhip_layoutlmv3_*`` entry points (include/marie_hip.h).
+"""LayoutLMv3 model (page classifier and token tagger): binding of the ``mhip_layoutlmv3_*`` entry points (include/marie_hip.h).
 
 reference: ``LayoutLMv3ForSequenceClassification`` of the transformers library as ``TransformersDocumentClassifier`` drives it
 (marie/components/document_classifier/transformers.py:159-172, :300-361).  The tokeniser and the classifier surface are in
 ``document_classifier.py``; this file is the model handle: pages + token ids + boxes + mask in, logits (and, for tests, the
-last hidden states and the resized pages) out.
+last hidden states and the resized pages) out.  For the document indexer (``LayoutLMv3ForTokenClassification`` as
+marie/components/document_indexer/transformers.py:519-568 drives it; surface in ``document_indexer.py``) the same handle tags
+windows of text: ``tag_device`` / ``tag_host`` return one label and one score per token.
 """
 from __future__ import annotations
 
@@ -122,6 +124,62 @@ class LayoutLMv3Model(ModelHandle):
         if want_resized:
             out["resized"] = resized
         return out
+
+
+    def _windows(self, n_pages: int, window_page, ids, bbox, mask):
+        wp = np.ascontiguousarray(window_page, np.int32).reshape(-1)
+        n = int(wp.size)
+        if n < 1 or wp.min() < 0 or wp.max() >= n_pages:
+            raise ValueError(f"window_page must name pages 0..{n_pages - 1} for at least one window")
+        return (wp, n) + self._inputs(n, ids, bbox, mask)
+
+    def _tag_out(self, n: int, want_logits: bool):
+        T = self.cfg.max_text
+        labels, scores = np.empty((n, T), np.int32), np.empty((n, T), np.float32)
+        logits = np.empty((n, T, self.cfg.num_labels), np.float32) if want_logits else None
+        return labels, scores, logits
+
+    def tag_device(self, base_ptr: int, descs, n_pages: int, window_page, ids, bbox, mask, want_logits: bool = False) -> dict:
+        """Windows of text over ``n_pages`` pages inside one device buffer (window w belongs to page ``window_page[w]``)
+        -> {"labels" (n_win, max_text) int32, "scores" (n_win, max_text) fp32} (+ "logits" (n_win, max_text, num_labels)),
+        one model call; the pages are resized and projected once each."""
+        wp, n, ids, bbox, mask = self._windows(n_pages, window_page, ids, bbox, mask)
+        labels, scores, logits = self._tag_out(n, want_logits)
+        check(self.ctx.h, self.lib.mhip_layoutlmv3_tag(self.h, C.c_void_p(base_ptr), descs, n_pages, _vp(wp), n, _vp(ids), _vp(bbox),
+                                                       _vp(mask), _vp(labels), _vp(scores), _vp(logits)), "mhip_layoutlmv3_tag")
+        out = {"labels": labels, "scores": scores}
+        if want_logits:
+            out["logits"] = logits
+        return out
+
+    def tag_host(self, pages: Sequence[np.ndarray], window_page, ids, bbox, mask, want_logits: bool = False) -> dict:
+        """``tag_device`` on host pages."""
+        packed, descs = pack_pages(pages)
+        wp, n, ids, bbox, mask = self._windows(len(pages), window_page, ids, bbox, mask)
+        labels, scores, logits = self._tag_out(n, want_logits)
+        check(self.ctx.h, self.lib.mhip_layoutlmv3_tag_host(self.h, _vp(packed), packed.size, descs, len(pages), _vp(wp), n, _vp(ids),
+                                                            _vp(bbox), _vp(mask), _vp(labels), _vp(scores), _vp(logits)),
+              "mhip_layoutlmv3_tag_host")
+        out = {"labels": labels, "scores": scores}
+        if want_logits:
+            out["logits"] = logits
+        return out
+
+
+def token_head_host(ctx: Context, precision: int, hidden, out_w, out_b, dense_w=None, dense_b=None, want_logits: bool = True):
+    """The token head alone (``mhip_token_head_host``): hidden (rows, D) fp32, ``out_w`` (L, D), ``out_b`` (L) and, for the
+    dense head, ``dense_w`` (D, D) + ``dense_b`` (D) -> (labels int32 (rows), scores fp32 (rows), logits fp32 (rows, L) or None)."""
+    hidden = np.ascontiguousarray(hidden, np.float32)
+    rows, D = hidden.shape
+    out_w, out_b = np.ascontiguousarray(out_w, np.float32), np.ascontiguousarray(out_b, np.float32)
+    L = out_w.shape[0]
+    if dense_w is not None:
+        dense_w, dense_b = np.ascontiguousarray(dense_w, np.float32), np.ascontiguousarray(dense_b, np.float32)
+    labels, scores = np.empty((rows,), np.int32), np.empty((rows,), np.float32)
+    logits = np.empty((rows, L), np.float32) if want_logits else None
+    check(ctx.h, ctx.lib.mhip_token_head_host(ctx.h, int(precision), rows, D, L, _vp(hidden), _vp(dense_w), _vp(dense_b), _vp(out_w),
+                                              _vp(out_b), _vp(labels), _vp(scores), _vp(logits)), "mhip_token_head_host")
+    return labels, scores, logits
 
 
 def attention_bias_host(ctx: Context, precision: int, q, k, v, pos, x, y, valid, w1, wx, wy, max_1d: int = 128,

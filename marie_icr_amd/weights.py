@@ -15,7 +15,7 @@ shipping a 34 MB file; ``state_checksum`` pins them.
 from __future__ import annotations
 
 import hashlib
-from typing import Dict
+from typing import Dict, Optional
 
 import numpy as np
 
@@ -814,3 +814,51 @@ def write_synthetic_bpe(directory: str, seed: int = 0, n_merges: int = 2500) -> 
         for a, b in merges:
             f.write(f"{a} {b}\n")
     return vocab
+
+
+def make_layoutlmv3_token_state(seed: int = 0, num_labels: int = 13, head: Optional[str] = None, head_gain: float = 24.0,
+                                **dims) -> Dict[str, np.ndarray]:
+    """Seeded LayoutLMv3ForTokenClassification weights: the encoder of ``make_layoutlmv3_state`` (``dims``: its keyword
+    arguments) under one of the two heads the library builds — ``"linear"`` (``classifier.weight`` / ``classifier.bias``, the
+    library's choice for ``num_labels < 10``) or ``"dense"`` (``classifier.dense`` + ``classifier.out_proj``, for
+    ``num_labels >= 10``); ``head=None`` follows the library's rule.  ``head_gain`` spreads the logits of a token over about that
+    many units, so that most tokens keep their label in a reduced-precision run."""
+    if head is None:
+        head = "linear" if num_labels < 10 else "dense"
+    if head not in ("linear", "dense"):
+        raise ValueError(f"head {head!r}: 'linear' or 'dense'")
+    st = make_layoutlmv3_state(seed, num_labels=num_labels, logit_gain=head_gain, **dims)
+    if head == "linear":
+        D = st["classifier.dense.bias"].shape[0]
+        rng = np.random.Generator(np.random.PCG64(seed + 49979687))
+        for k in ("classifier.dense.weight", "classifier.dense.bias", "classifier.out_proj.weight", "classifier.out_proj.bias"):
+            del st[k]
+        # hidden states are LayerNorm outputs of order one: logits spread over about head_gain
+        st["classifier.weight"] = rng.uniform(-1.0, 1.0, size=(num_labels, D)).astype(np.float32) * np.float32(head_gain * np.sqrt(3.0 / D))
+        st["classifier.bias"] = rng.uniform(-0.1, 0.1, size=(num_labels,)).astype(np.float32)
+    return st
+
+
+def make_indexer_config(seed: int = 0, n_fields: int = 3) -> dict:
+    """A seeded ``marie.json`` of the document indexer: ``n_fields`` question / answer field pairs (labels in ``B-`` / ``I-`` /
+    ``O`` form: 4 * n_fields + 5 of them), two NER-only fields whose pair makes one composite entity, ``expected_keys``,
+    ``expected_pair``, ``expected_ner``, ``possible_fields`` and ``entities_to_group``."""
+    rng = np.random.Generator(np.random.PCG64(seed + 86028121))
+    stems = ["PAN", "DOS", "CLAIM", "CHECK", "MEMBER", "PATIENT", "PAYER", "NPI"]
+    picked = [stems[int(i)] for i in rng.permutation(len(stems))[:n_fields]]
+    questions = picked
+    answers = [f"{p}_ANSWER" for p in picked]
+    ner = ["ADDRESS", "NAME"]
+    keys = [k for qa in zip(questions, answers) for k in qa] + ner
+    labels = ["O"] + [f"{p}-{k}" for k in keys for p in ("B", "I")]
+    return {
+        "labels": labels,
+        "expected_keys": keys,
+        "expected_pair": [[q, [a]] for q, a in zip(questions, answers)],
+        "expected_ner": ner + answers[:1],
+        "possible_fields": {q: [q, a] for q, a in zip(questions, answers)},
+        "entities_to_group": [{"name": "RECIPIENT", "entities": ner, "validation": {"type": "address"}}],
+        "mislabeled_token_strategy": "aggregate",
+        "debug": {"scores": False, "colors": {},
+                  "visualize": {"enabled": False, "overlay": False, "icr": False, "ner": False, "prediction": False}},
+    }
