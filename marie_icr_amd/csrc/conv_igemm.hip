@@ -54,16 +54,14 @@ struct Cfg {
   static constexpr int WN = BN / 64;             // waves along N
   static constexpr int WM = 8 / WN;              // waves along M
   static constexpr int MT = BM / WM / 16;        // 16-row MFMA tiles per wave along M (4 or 8)
-  static constexpr bool KSPLIT = false;
-  static constexpr int NSTAGE = (KSPLIT || SMALL) ? 4 : ((BN == 128) ? 3 : 2);
-  static constexpr int HROWB = KSPLIT ? 64 : ROWB;        // bytes of one staged row
-  static constexpr int A_BYTES = BM * HROWB;
-  static constexpr int B_BYTES = BN * HROWB;
+  static constexpr int NSTAGE = SMALL ? 4 : ((BN == 128) ? 3 : 2);
+  static constexpr int A_BYTES = BM * ROWB;      // a staged row is one K slice row (ROWB bytes)
+  static constexpr int B_BYTES = BN * ROWB;
   static constexpr int STAGE_BYTES = A_BYTES + B_BYTES;
-  static constexpr int RPI = 64 * 16 / HROWB / 1;         // rows covered by one wave-instruction (8 or 16)
-  static constexpr int ACHUNKS = BM * (HROWB / 16) / NTHREADS;   // A chunks staged per thread per (half-)slice
-  static constexpr int WCHUNKS = BN * (HROWB / 16) / NTHREADS;   // W chunks
-  static constexpr int GL = ACHUNKS + WCHUNKS;   // LDS-DMA instructions per wave per (half-)slice
+  static constexpr int RPI = 64 * 16 / ROWB;     // rows covered by one wave-instruction (8)
+  static constexpr int ACHUNKS = BM * (ROWB / 16) / NTHREADS;   // A chunks staged per thread per slice
+  static constexpr int WCHUNKS = BN * (ROWB / 16) / NTHREADS;   // W chunks
+  static constexpr int GL = ACHUNKS + WCHUNKS;   // LDS-DMA instructions per wave per slice (9 / 6 / 8 by BN; 4 on the 128 x 128 tile)
   static constexpr int EPW = BN < 128 ? BN : 128;         // output columns per epilogue pass
   static constexpr int EPI_BYTES = BM * (EPW * 4 + 16);   // one epilogue pass, fp32 worst case
   static constexpr int RING_BYTES = NSTAGE * STAGE_BYTES;
@@ -101,6 +99,32 @@ __device__ __forceinline__ float sum8(float v) {
   return v;
 }
 
+// ---- epilogue pieces defined once: the epilogue exists in three copies (`body`, `split_fast`, `f16_fast` in the kernel) and a
+// tile's values must not depend on which copy wrote it.  More of what they share (accumulator -> value, the row vectors) is
+// defined once inside the kernel, ahead of the copies.
+
+// eight consecutive columns of one staged fp32 row
+__device__ __forceinline__ void staged8(const char* src, float (&f)[8]) {
+  const float4v a0 = *(const float4v*)src, a1 = *(const float4v*)(src + 16);
+  f[0] = a0[0]; f[1] = a0[1]; f[2] = a0[2]; f[3] = a0[3]; f[4] = a1[0]; f[5] = a1[1]; f[6] = a1[2]; f[7] = a1[3];
+}
+
+// (The split-stream row arithmetic of EPI_SPLIT — add both residual planes, sum8, centre, sum of squares, the keep rule, hi / lo —
+// stays spelled out in `body` and `split_fast`: behind a helper <f16, 1128, EPI_SPLIT> grew from 2783 to 2786 instructions and
+// <f16, 128, EPI_SPLIT> from 4535 to 4545.)
+// (The f16 finish — gelu_erf on each value where asked for, then narrowing — stays spelled out in `body` and `f16_fast`: behind
+// a helper, by reference or by value, the narrowing reordered the GELU arithmetic of `body` in the pooled f16 kernels —
+// <f16, POOL_2x2, 128>: 155 of 7489 instructions moved.)
+
+// Output stores of the big tiles are non-temporal: the output is read next by another kernel, long after it has left the L2 (at
+// full batch the split planes are gigabytes), and kept out of it the weights stay (+3 % on the ViT GEMMs,
+// tools/ubench/gemm_bench.hip).  The few-row tile's outputs (decoder steps) are small and read back at once: those stay in the L2.
+template <bool SMALL, typename V, typename P>
+__device__ __forceinline__ void tile_store(const V& v, P dst) {
+  if (SMALL) *dst = v;
+  else __builtin_nontemporal_store(v, dst);
+}
+
 template <int POOL>
 __device__ __forceinline__ void decode_row(const IgemmArgs& p, int m, int& b, int& y, int& x) {
   if (POOL == POOL_NONE) {
@@ -134,6 +158,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_igemm_kernel(IgemmArgs p) {
   constexpr int E = Tr<T>::E;            // elements per 16-B chunk
   constexpr int BKE = ROWB / sizeof(T);  // elements per K slice
   constexpr int MT = C::MT;
+  constexpr int WROWS = MT * 16;         // output rows per wave
   constexpr int BM = C::BM;
   constexpr int A_BYTES = C::A_BYTES;
 
@@ -149,21 +174,17 @@ __global__ __launch_bounds__(NTHREADS) void conv_igemm_kernel(IgemmArgs p) {
     mt = L / p.ntiles;
   }
   const int m0 = mt * BM, n0 = nt * C::BN;
-  if (p.stagger > 0 && blockIdx.x < 256 && (blockIdx.x & 8)) {       // experiment: half of the first round starts late
-    for (int k = 0; k < p.stagger; ++k) __builtin_amdgcn_s_sleep(127);
-  }
 
   // ---- staging set-up: each thread moves BM/64 A chunks + BN/64 W chunks per slice ---------
   // a wave-instruction covers RPI rows; a thread's q-th chunk sits RPI*8 rows further down
   constexpr int RPI = C::RPI, RSTEP = RPI * 8;
-  const int srow = wave * RPI + (C::KSPLIT ? (lane >> 2) : (lane >> 3));   // row within a RSTEP-row group
-  const int lchunk = C::KSPLIT ? ((lane & 3) ^ ((srow >> 1) & 3))          // logical chunk this lane fetches
-                               : ((lane & 7) ^ ((srow >> 1) & 7));
+  const int srow = wave * RPI + (lane >> 3);             // row within a RSTEP-row group
+  const int lchunk = (lane & 7) ^ ((srow >> 1) & 7);     // logical chunk this lane fetches
   const char* a_src[C::ACHUNKS];
   int a_y[C::ACHUNKS], a_x[C::ACHUNKS];
   const char* w_src[C::WCHUNKS];
   // plain GEMM (see `stage_pure` below): pixel index = row index, no row decoding (three integer divisions per chunk)
-  const bool pure = !DUAL && !C::KSPLIT && POOL == POOL_NONE && p.KH == 1 && p.KW == 1 && p.pad == 0 && p.pad_x == 0 &&
+  const bool pure = !DUAL && POOL == POOL_NONE && p.KH == 1 && p.KW == 1 && p.pad == 0 && p.pad_x == 0 &&
                     p.sy == 1 && (size_t)p.Ktot * sizeof(T) + ROWB <= (size_t)MHIP_ZERO_BYTES;
 #pragma unroll
   for (int q = 0; q < C::ACHUNKS; ++q) {
@@ -207,46 +228,44 @@ __global__ __launch_bounds__(NTHREADS) void conv_igemm_kernel(IgemmArgs p) {
     for (int q = 0; q < C::WCHUNKS; ++q)
       if (!w_src[q]) w_src[q] = p.zeros + lchunk * 16;
   }
-  auto stage_pure = [&](int slot) {      // called once per (half-)slice, in K order
-    char* la = smem + slot * C::STAGE_BYTES + wave_s * RPI * C::HROWB;
+  auto stage_pure = [&](int slot) {      // called once per slice, in K order
+    char* la = smem + slot * C::STAGE_BYTES + wave_s * RPI * ROWB;
     char* lb = la + A_BYTES;
 #pragma unroll
     for (int q = 0; q < C::ACHUNKS; ++q) {
-      glds16(a_src[q], la + q * RSTEP * C::HROWB);
-      a_src[q] += C::HROWB;
+      glds16(a_src[q], la + q * RSTEP * ROWB);
+      a_src[q] += ROWB;
     }
 #pragma unroll
     for (int q = 0; q < C::WCHUNKS; ++q) {
-      glds16(w_src[q], lb + q * RSTEP * C::HROWB);
-      w_src[q] += C::HROWB;
+      glds16(w_src[q], lb + q * RSTEP * ROWB);
+      w_src[q] += ROWB;
     }
   };
-  // one DMA instruction of a (half-)slice: g < ACHUNKS -> A chunk g, else W chunk g - ACHUNKS.  The main loop issues them
+  // one DMA instruction of a slice: g < ACHUNKS -> A chunk g, else W chunk g - ACHUNKS.  The main loop issues them
   // BETWEEN groups of MFMAs: a wave that issues its 8 DMA instructions back to back sits in the vector-memory queue
   // behind the other waves' (64 KiB per slice drain at ~31 B/clk/CU: the second half of the waves measured ~2000 cycles
   // in `stage` before their first MFMA — profiles/r01/s_loop_phases.txt), and nothing overlaps that wait.
   auto stage_pure_chunk = [&](int slot, int g) {
-    char* la = smem + slot * C::STAGE_BYTES + wave_s * RPI * C::HROWB;
+    char* la = smem + slot * C::STAGE_BYTES + wave_s * RPI * ROWB;
     if (g < C::ACHUNKS) {
-      glds16(a_src[g], la + g * RSTEP * C::HROWB);
-      a_src[g] += C::HROWB;
+      glds16(a_src[g], la + g * RSTEP * ROWB);
+      a_src[g] += ROWB;
     } else {
       const int q = g - C::ACHUNKS;
-      glds16(w_src[q], la + A_BYTES + q * RSTEP * C::HROWB);
-      w_src[q] += C::HROWB;
+      glds16(w_src[q], la + A_BYTES + q * RSTEP * ROWB);
+      w_src[q] += ROWB;
     }
   };
-  auto stage_general = [&](int hs, int slot) {
-    const int it = C::KSPLIT ? (hs >> 1) : hs;            // K slice
-    const int hoff = C::KSPLIT ? (hs & 1) * 64 : 0;       // byte offset of the k-group half inside the slice
+  auto stage_general = [&](int it, int slot) {           // K slice `it`
     int tap = it / p.cpt, cc = it - tap * p.cpt;
     int dy = (tap / p.KW) * p.dil, dx = (tap - (tap / p.KW) * p.KW) * p.dil;
-    size_t a_off = (((size_t)dy * p.W + dx) * p.Cin + (size_t)cc * BKE) * sizeof(T) + hoff;
-    size_t w_off = (size_t)it * BKE * sizeof(T) + hoff;
-    char* la = smem + slot * C::STAGE_BYTES + wave_s * RPI * C::HROWB;
+    size_t a_off = (((size_t)dy * p.W + dx) * p.Cin + (size_t)cc * BKE) * sizeof(T);
+    size_t w_off = (size_t)it * BKE * sizeof(T);
+    char* la = smem + slot * C::STAGE_BYTES + wave_s * RPI * ROWB;
     char* lb = la + A_BYTES;
     // DUAL (KH = KW = 1, pad = 0): channel slice cc comes from `in` or from `in2`
-    const int c0 = cc * BKE + lchunk * E + hoff / (int)sizeof(T);
+    const int c0 = cc * BKE + lchunk * E;
     const bool first = c0 < p.Cin1;
     const char* dbase = first ? p.in : p.in2;
     const size_t dstride = (size_t)(first ? p.Cin1 : p.Cin - p.Cin1) * sizeof(T);
@@ -258,17 +277,17 @@ __global__ __launch_bounds__(NTHREADS) void conv_igemm_kernel(IgemmArgs p) {
       const char* src;
       if (DUAL) src = ok ? dbase + (size_t)a_src[q] * dstride + dcol : p.zeros;
       else src = ok ? a_src[q] + a_off : p.zeros;
-      glds16(src, la + q * RSTEP * C::HROWB);
+      glds16(src, la + q * RSTEP * ROWB);
     }
 #pragma unroll
     for (int q = 0; q < C::WCHUNKS; ++q) {
       const char* src = w_src[q] ? w_src[q] + w_off : p.zeros;
-      glds16(src, lb + q * RSTEP * C::HROWB);
+      glds16(src, lb + q * RSTEP * ROWB);
     }
   };
-  auto stage = [&](int hs, int slot) {
+  auto stage = [&](int it, int slot) {
     if (pure) stage_pure(slot);
-    else stage_general(hs, slot);
+    else stage_general(it, slot);
   };
 
   // ---- accumulators ---------------------------------------------------------------------
@@ -280,28 +299,28 @@ __global__ __launch_bounds__(NTHREADS) void conv_igemm_kernel(IgemmArgs p) {
 
   const int wr = wave / C::WN, wc = wave % C::WN;
   const int frow = lane & 15, fg = lane >> 4;
-  // per-lane LDS byte offsets of k-group 0 (k-group 1 = offset ^ 64; KSPLIT: the other half-slice slot)
+  // per-lane LDS byte offsets of k-group 0 (k-group 1 = offset ^ 64)
   int a_off0[MT], b_off0[4];
 #pragma unroll
   for (int t = 0; t < MT; ++t) {
-    int ra = wr * (MT * 16) + t * 16 + frow;
-    a_off0[t] = C::KSPLIT ? ra * 64 + ((fg ^ ((ra >> 1) & 3)) << 4) : ra * ROWB + ((fg ^ ((ra >> 1) & 7)) << 4);
+    int ra = wr * WROWS + t * 16 + frow;
+    a_off0[t] = ra * ROWB + ((fg ^ ((ra >> 1) & 7)) << 4);
   }
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     int rb = wc * 64 + t * 16 + frow;
-    b_off0[t] = A_BYTES + (C::KSPLIT ? rb * 64 + ((fg ^ ((rb >> 1) & 3)) << 4) : rb * ROWB + ((fg ^ ((rb >> 1) & 7)) << 4));
+    b_off0[t] = A_BYTES + rb * ROWB + ((fg ^ ((rb >> 1) & 7)) << 4);
   }
 
-  // ---- main loop: NSTAGE-slot ring, GL LDS-DMA instructions per wave per (half-)slice -------
-  constexpr int D = C::NSTAGE - 1;  // (half-)slices in flight ahead of the one being computed
-  const int nsteps = C::KSPLIT ? 2 * p.nslices : p.nslices;
+  // ---- main loop: NSTAGE-slot ring, GL LDS-DMA instructions per wave per slice -------
+  constexpr int D = C::NSTAGE - 1;  // slices in flight ahead of the one being computed
+  const int nsteps = p.nslices;
   if (nsteps > 0) stage(0, 0);
   if (D > 1 && nsteps > 1) stage(1, 1);
   if (D > 2 && nsteps > 2) stage(2, 2);
   int slot = 0, fill = D % C::NSTAGE;
   for (int it = 0; it < nsteps; ++it) {
-    const int younger = min(D - 1, nsteps - 1 - it);   // (half-)slices issued after the one needed now
+    const int younger = min(D - 1, nsteps - 1 - it);   // slices issued after the one needed now
     if (C::GL == 6) {
       if (younger >= 1) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -319,7 +338,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_igemm_kernel(IgemmArgs p) {
     if (feed && !interleave) stage(it + D, fill);
     const char* sb = smem + slot * C::STAGE_BYTES;
 #pragma unroll
-    for (int s = 0; s < (C::KSPLIT ? 1 : 2); ++s) {
+    for (int s = 0; s < 2; ++s) {     // the slice's two k-groups
       chunk_t a[MT], b[4];
 #pragma unroll
       for (int t = 0; t < 4; ++t) b[t] = *(const chunk_t*)(sb + (b_off0[t] ^ (s << 6)));
@@ -331,7 +350,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_igemm_kernel(IgemmArgs p) {
       // 1 KiB instruction per CU) and no wave sits in the queue with its MFMAs behind it; the last one is issued early
       // enough to land under the rest of the slice.  One MFMA sequence for both cases — only the DMA instructions sit
       // behind a uniform branch.
-      constexpr int NM = MT * 4, EVERY = C::KSPLIT ? (NM + C::GL - 1) / C::GL : ((MT == 8) ? 4 : (2 * NM + C::GL - 1) / C::GL / 2);
+      constexpr int NM = MT * 4, EVERY = (MT == 8) ? 4 : (2 * NM + C::GL - 1) / C::GL / 2;
 #pragma unroll
       for (int idx = 0; idx < NM; ++idx) {
         const int gidx = s * NM + idx;                     // position in the slice's MFMA sequence
@@ -340,9 +359,9 @@ __global__ __launch_bounds__(NTHREADS) void conv_igemm_kernel(IgemmArgs p) {
         }
         Tr<T>::mma(a[idx / 4], b[idx % 4], acc[idx / 4][idx % 4]);
       }
-      if (s == (C::KSPLIT ? 0 : 1) && interleave) {
+      if (s == 1 && interleave) {
 #pragma unroll
-        for (int g = ((C::KSPLIT ? 1 : 2) * NM + EVERY - 1) / EVERY; g < C::GL; ++g) stage_pure_chunk(fill, g);   // left-overs
+        for (int g = (2 * NM + EVERY - 1) / EVERY; g < C::GL; ++g) stage_pure_chunk(fill, g);   // left-overs
       }
       __builtin_amdgcn_s_setprio(0);
     }
@@ -392,10 +411,10 @@ __global__ __launch_bounds__(NTHREADS) void conv_igemm_kernel(IgemmArgs p) {
       }
     }
   }
-  // ... and the vectors indexed by the GEMM rows of this wave (MT * 16 of them): requested now, parked in a wave-private LDS
+  // ... and the vectors indexed by the GEMM rows of this wave (WROWS of them): requested now, parked in a wave-private LDS
   // strip behind the staging areas once the ring is dead, read back 16 bytes at a time per row-tile (loading them where they are
   // used put a global-load latency in front of every row-tile)
-  constexpr int WROWS = MT * 16, NRV = (WROWS + 63) / 64;
+  constexpr int NRV = (WROWS + 63) / 64;
   float rv_a[NRV], rv_b[NRV];
   if (EPI == EPI_LN_ROWS || EPI == EPI_LN_COLS) {
 #pragma unroll
@@ -419,19 +438,36 @@ __global__ __launch_bounds__(NTHREADS) void conv_igemm_kernel(IgemmArgs p) {
     __builtin_amdgcn_wave_barrier();
   }
   char* wst0 = smem + wave * (2 * 16 * SPW);   // two private staging areas per wave: tile i+1 is written while tile i drains
-  // One specialised copy of the row-tile loop per (output type, residual, GELU) combination, chosen once: the loop is
-  // unrolled over the 8 row-tiles (accumulators are registers), so every uniform test left inside it is replicated and
-  // the kernel's code outgrows the instruction cache two CUs share — which slows the neighbour's main loop as well.
   auto out_row = [&](int q) -> long long {
     return p.row_period ? (long long)(q / p.row_period) * p.row_stride + p.row_offset + q % p.row_period : (long long)q;
   };
   auto res_row = [&](int q) -> long long { return p.row_period ? (long long)(q % p.row_period) : (long long)q; };
+  // ---- what the three copies of the epilogue share (`staged8` and `tile_store` are ahead of the kernel) ----
+  // the row vectors of the four GEMM rows this lane holds of row-tile i, read back from the strip
+  //   EPI_LN_ROWS: lr_a = rstd, lr_b = mean * rstd of token m;  EPI_LN_COLS: lr_a = row sum of the folded weights, lr_b = bias
+  auto row_vectors = [&](int i, float4v& lr_a, float4v& lr_b) {
+    lr_a = lr_b = (float4v){0.f, 0.f, 0.f, 0.f};
+    if (EPI == EPI_LN_ROWS || EPI == EPI_LN_COLS) {
+      lr_a = *(const float4v*)(rvs + i * 16 + fg * 4);
+      lr_b = *(const float4v*)(rvs + WROWS + i * 16 + fg * 4);
+    }
+  };
+  // accumulator -> value in column group j of the lane; lr_a / lr_b: the row's elements of the row vectors
+  auto value = [&](float a, int j, float lr_a, float lr_b) -> float {
+    if (EPI == EPI_LN_ROWS) return __builtin_fmaf(a, lr_a, __builtin_fmaf(-lr_b, lnc_b[j], bi4[j]));
+    if (EPI == EPI_LN_COLS) return __builtin_fmaf(a, lnc_a[j], __builtin_fmaf(-lnc_b[j], lr_a, lr_b));
+    return fmaxf(__builtin_fmaf(a, sc4[j], bi4[j]), lo);
+  };
+  // EPI_SPLIT: row statistics of the passes a lane keeps (pass = 8 rows x this wave's 64 columns; lane j of an 8-lane row group
+  // keeps pass j of every set of eight), stored once after the row-tile loop.  (`body` and `split_fast` keep a store loop each: one
+  // loop for both, with the bounds tests as a parameter, shortened `body`'s by 3 instructions on <f16, 1128, EPI_SPLIT>.)
+  constexpr int NPASS = MT * 2, NSET = (NPASS + 7) / 8;
+  // One specialised copy of the row-tile loop per (output type, residual, GELU) combination, chosen once: the loop is
+  // unrolled over the 8 row-tiles (accumulators are registers), so every uniform test left inside it is replicated and
+  // the kernel's code outgrows the instruction cache two CUs share — which slows the neighbour's main loop as well.
   auto body = [&](auto OUT32_, auto RES_, auto GELU_, auto VEC_) {
     constexpr bool OUT32 = decltype(OUT32_)::value, RES = decltype(RES_)::value, GELU = decltype(GELU_)::value,
                    VEC = decltype(VEC_)::value;
-    // EPI_SPLIT: row statistics of the passes this lane keeps (pass = 8 rows x this wave's 64 columns; lane j of an 8-lane
-    // row group keeps pass j of every set of eight), stored once after the loop
-    constexpr int NPASS = MT * ((RT * 8 + 63) / 64), NSET = (NPASS + 7) / 8;
     float keep_s[NSET], keep_q[NSET];
 #pragma unroll
     for (int k = 0; k < NSET; ++k) keep_s[k] = keep_q[k] = 0.f;
@@ -445,7 +481,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_igemm_kernel(IgemmArgs p) {
     half8 rq16[RES && !OUT32 && VEC ? MT : 1][RES && !OUT32 && VEC ? NRES16 : 1];
     half8 rq16b[EPI == EPI_SPLIT ? MT : 1][EPI == EPI_SPLIT ? NRES16 : 1];
     auto load_res = [&](int i) {
-      const int qb0 = (m0 + wr * (MT * 16) + i * 16) / PF;
+      const int qb0 = (m0 + wr * WROWS + i * 16) / PF;
       if (OUT32) {
 #pragma unroll
         for (int t = 0; t < NRES32; ++t) {
@@ -484,23 +520,14 @@ __global__ __launch_bounds__(NTHREADS) void conv_igemm_kernel(IgemmArgs p) {
       float4v (&rres32)[RES && OUT32 && VEC ? NRES32 : 1] = rq32[RES && OUT32 && VEC ? i : 0];
       half8 (&rres16)[RES && !OUT32 && VEC ? NRES16 : 1] = rq16[RES && !OUT32 && VEC ? i : 0];
       half8 (&rres16b)[EPI == EPI_SPLIT ? NRES16 : 1] = rq16b[EPI == EPI_SPLIT ? i : 0];      // the low plane of a split residual
-      // LayerNorm-folded consumers: the vectors indexed by the four GEMM rows this lane holds of the row-tile
-      //   EPI_LN_ROWS: lr_a = rstd, lr_b = mean * rstd of token m;  EPI_LN_COLS: lr_a = row sum of the folded weights, lr_b = bias
-      float4v lr_a = (float4v){0.f, 0.f, 0.f, 0.f}, lr_b = (float4v){0.f, 0.f, 0.f, 0.f};
-      if (EPI == EPI_LN_ROWS || EPI == EPI_LN_COLS) {
-        lr_a = *(const float4v*)(rvs + i * 16 + fg * 4);
-        lr_b = *(const float4v*)(rvs + WROWS + i * 16 + fg * 4);
-      }
+      float4v lr_a, lr_b;
+      row_vectors(i, lr_a, lr_b);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int lc = j * 16 + frow;
         float v[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if (EPI == EPI_LN_ROWS) v[r] = __builtin_fmaf(acc[i][j][r], lr_a[r], __builtin_fmaf(-lr_b[r], lnc_b[j], bi4[j]));
-          else if (EPI == EPI_LN_COLS) v[r] = __builtin_fmaf(acc[i][j][r], lnc_a[j], __builtin_fmaf(-lnc_b[j], lr_a[r], lr_b[r]));
-          else v[r] = fmaxf(__builtin_fmaf(acc[i][j][r], sc4[j], bi4[j]), lo);
-        }
+        for (int r = 0; r < 4; ++r) v[r] = value(acc[i][j][r], j, lr_a[r], lr_b[r]);
         if (POOL == POOL_2x2) {
           lds_put<float>(wst, SPW, fg, lc, fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
         } else if (POOL == POOL_2x1) {
@@ -513,7 +540,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_igemm_kernel(IgemmArgs p) {
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
-      const int qbase = (m0 + wr * (MT * 16) + i * 16) / PF;
+      const int qbase = (m0 + wr * WROWS + i * 16) / PF;
       if (EPI == EPI_SPLIT) {
         // the residual stream as two f16 planes: x = acc * scale + bias + (res_hi + res_lo) in fp32, hi = f16(x), lo = f16(x - hi);
         // (sum, centred sum of squares) of the row over this wave's 64 columns ride along for the LayerNorm of the consumer
@@ -527,11 +554,10 @@ __global__ __launch_bounds__(NTHREADS) void conv_igemm_kernel(IgemmArgs p) {
           const int q = qbase + row, n = n0 + wc * 64 + ch * 8;
           ook[t] = row < RT && q < Mq && n < p.N;
           ooff[t] = 0;
-          float f[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+          float f[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // a chunk outside the output enters its row's statistics as zeros
           if (ook[t]) {
-            const float4v a0 = *(const float4v*)(wst + row * SPW + ch * 32), a1 = *(const float4v*)(wst + row * SPW + ch * 32 + 16);
+            staged8(wst + row * SPW + ch * 32, f);
             const half8 r8 = rres16[t], l8 = rres16b[t];
-            f[0] = a0[0]; f[1] = a0[1]; f[2] = a0[2]; f[3] = a0[3]; f[4] = a1[0]; f[5] = a1[1]; f[6] = a1[2]; f[7] = a1[3];
 #pragma unroll
             for (int k = 0; k < 8; ++k) f[k] += (float)r8[k] + (float)l8[k];
             ooff[t] = (size_t)out_row(q) * grow + (size_t)n * 2;
@@ -561,15 +587,8 @@ __global__ __launch_bounds__(NTHREADS) void conv_igemm_kernel(IgemmArgs p) {
 #pragma unroll
         for (int t = 0; t < NRES16; ++t)
           if (ook[t]) {
-            // as the other big tiles: non-temporal (at full batch the planes are gigabytes — they leave the caches before the next
-            // GEMM reads them, and written through they leave the weights in the L2); the few-row tile's stay
-            if (C::SMALL) {
-              *(__attribute__((address_space(1))) half8*)dsth[t] = hv[t];
-              *(__attribute__((address_space(1))) half8*)dstl[t] = lv[t];
-            } else {
-              __builtin_nontemporal_store(hv[t], (__attribute__((address_space(1))) half8*)dsth[t]);
-              __builtin_nontemporal_store(lv[t], (__attribute__((address_space(1))) half8*)dstl[t]);
-            }
+            tile_store<C::SMALL>(hv[t], (__attribute__((address_space(1))) half8*)dsth[t]);
+            tile_store<C::SMALL>(lv[t], (__attribute__((address_space(1))) half8*)dstl[t]);
           }
       } else if (VEC && !OUT32) {
         // f16 out: 8 columns per lane = one 16-byte store; 8 lanes cover a row's 64 columns (128 contiguous bytes).
@@ -587,8 +606,8 @@ __global__ __launch_bounds__(NTHREADS) void conv_igemm_kernel(IgemmArgs p) {
           ooff[t] = 0;
           ov[t] = (half8){0, 0, 0, 0, 0, 0, 0, 0};
           if (ook[t]) {
-            const float4v a0 = *(const float4v*)(wst + row * SPW + ch * 32), a1 = *(const float4v*)(wst + row * SPW + ch * 32 + 16);
-            float f[8] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
+            float f[8];
+            staged8(wst + row * SPW + ch * 32, f);
             if (GELU)
 #pragma unroll
               for (int k = 0; k < 8; ++k) f[k] = gelu_erf(f[k]);
@@ -613,13 +632,8 @@ __global__ __launch_bounds__(NTHREADS) void conv_igemm_kernel(IgemmArgs p) {
         }
 #pragma unroll
         for (int t = 0; t < NRES16; ++t)
-          // global, not flat: the asm hides the provenance.  Non-temporal: the output is read next by another kernel, long after
-          // it has left the L2, and kept out of it the weights stay (+3 % on the ViT GEMMs, tools/ubench/gemm_bench.hip)
-          // The few-row tile's outputs (decoder steps) are small and read back at once: those stay in the L2.
-          if (ook[t]) {
-            if (C::SMALL) *(__attribute__((address_space(1))) half8*)dst16[t] = ov[t];
-            else __builtin_nontemporal_store(ov[t], (__attribute__((address_space(1))) half8*)dst16[t]);
-          }
+          // global, not flat: the asm hides the provenance
+          if (ook[t]) tile_store<C::SMALL>(ov[t], (__attribute__((address_space(1))) half8*)dst16[t]);
       } else {
         float4v ov32[NRES32];
         size_t ooff32[NRES32];
@@ -668,10 +682,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_igemm_kernel(IgemmArgs p) {
           }
 #pragma unroll
           for (int t = 0; t < NRES32; ++t)
-            if (ook32[t]) {
-              if (C::SMALL) *(__attribute__((address_space(1))) float4v*)dst32[t] = ov32[t];
-              else __builtin_nontemporal_store(ov32[t], (__attribute__((address_space(1))) float4v*)dst32[t]);
-            }
+            if (ook32[t]) tile_store<C::SMALL>(ov32[t], (__attribute__((address_space(1))) float4v*)dst32[t]);
         }
       }
     }
@@ -684,7 +695,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_igemm_kernel(IgemmArgs p) {
           const int pass = k * 8 + j;
           if (pass < NPASS) {
             const int ii = pass / (NPASS / MT), tt = pass % (NPASS / MT);
-            const int q = m0 + wr * (MT * 16) + ii * 16 + tt * 8 + g;
+            const int q = m0 + wr * WROWS + ii * 16 + tt * 8 + g;
             if (q < Mq) {
               float* dst = p.stats + ((size_t)c64 * p.stats_ld + (size_t)out_row(q)) * 2;
               dst[0] = keep_s[k];
@@ -703,7 +714,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_igemm_kernel(IgemmArgs p) {
   auto split_fast = [&]() {
     constexpr int AH = 3;
     const int r8 = lane >> 3, c8 = lane & 7;
-    const size_t lane_off = (size_t)(m0 + wr * (MT * 16) + r8) * grow + (size_t)(n0 + wc * 64 + c8 * 8) * 2;
+    const size_t lane_off = (size_t)(m0 + wr * WROWS + r8) * grow + (size_t)(n0 + wc * 64 + c8 * 8) * 2;
     const char* rh = p.res + lane_off;
     const char* rl = p.res2 + lane_off;
     char* oh = p.out + lane_off;
@@ -719,7 +730,6 @@ __global__ __launch_bounds__(NTHREADS) void conv_igemm_kernel(IgemmArgs p) {
     };
 #pragma unroll
     for (int i = 0; i < AH && i < MT; ++i) request(i);
-    constexpr int NPASS = MT * 2, NSET = (NPASS + 7) / 8;
     float keep_s[NSET], keep_q[NSET];
 #pragma unroll
     for (int k = 0; k < NSET; ++k) keep_s[k] = keep_q[k] = 0.f;
@@ -730,15 +740,14 @@ __global__ __launch_bounds__(NTHREADS) void conv_igemm_kernel(IgemmArgs p) {
 #pragma unroll
       for (int j = 0; j < 4; ++j)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) lds_put<float>(wst, SPW, fg * 4 + r, j * 16 + frow, fmaxf(__builtin_fmaf(acc[i][j][r], sc4[j], bi4[j]), lo));
+        for (int r = 0; r < 4; ++r) lds_put<float>(wst, SPW, fg * 4 + r, j * 16 + frow, value(acc[i][j][r], j, 0.f, 0.f));
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       half8 hv[2], lv[2];
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        const int row = t * 8 + r8;
-        const float4v a0 = *(const float4v*)(wst + row * SPW + c8 * 32), a1 = *(const float4v*)(wst + row * SPW + c8 * 32 + 16);
-        float f[8] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
+        float f[8];
+        staged8(wst + (t * 8 + r8) * SPW + c8 * 32, f);
 #pragma unroll
         for (int k = 0; k < 8; ++k) f[k] += (float)qh[i][t][k] + (float)ql[i][t][k];
         float sm = sum8(((f[0] + f[1]) + (f[2] + f[3])) + ((f[4] + f[5]) + (f[6] + f[7])));
@@ -757,13 +766,8 @@ __global__ __launch_bounds__(NTHREADS) void conv_igemm_kernel(IgemmArgs p) {
       }
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        if (C::SMALL) {
-          *(half8*)(oh + (size_t)(i * 2 + t) * step8) = hv[t];
-          *(half8*)(ol + (size_t)(i * 2 + t) * step8) = lv[t];
-        } else {
-          __builtin_nontemporal_store(hv[t], (half8*)(oh + (size_t)(i * 2 + t) * step8));
-          __builtin_nontemporal_store(lv[t], (half8*)(ol + (size_t)(i * 2 + t) * step8));
-        }
+        tile_store<C::SMALL>(hv[t], (half8*)(oh + (size_t)(i * 2 + t) * step8));
+        tile_store<C::SMALL>(lv[t], (half8*)(ol + (size_t)(i * 2 + t) * step8));
       }
     }
     const int c64 = (n0 + wc * 64) >> 6;
@@ -771,7 +775,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_igemm_kernel(IgemmArgs p) {
     for (int k = 0; k < NSET; ++k) {
       const int pass = k * 8 + c8;
       if (pass < NPASS) {
-        float* dst = p.stats + ((size_t)c64 * p.stats_ld + (size_t)(m0 + wr * (MT * 16) + pass * 8 + r8)) * 2;
+        float* dst = p.stats + ((size_t)c64 * p.stats_ld + (size_t)(m0 + wr * WROWS + pass * 8 + r8)) * 2;
         dst[0] = keep_s[k];
         dst[1] = keep_q[k];
       }
@@ -783,34 +787,24 @@ __global__ __launch_bounds__(NTHREADS) void conv_igemm_kernel(IgemmArgs p) {
   auto f16_fast = [&](auto GELU_) {
     constexpr bool GELU = decltype(GELU_)::value;
     const int r8 = lane >> 3, c8 = lane & 7;
-    char* o = p.out + (size_t)(m0 + wr * (MT * 16) + r8) * grow + (size_t)(n0 + wc * 64 + c8 * 8) * 2;
+    char* o = p.out + (size_t)(m0 + wr * WROWS + r8) * grow + (size_t)(n0 + wc * 64 + c8 * 8) * 2;
     const size_t step8 = 8 * grow;
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
       char* wst = wst0 + (i & 1) * (16 * SPW);
-      float4v lr_a = (float4v){0.f, 0.f, 0.f, 0.f}, lr_b = (float4v){0.f, 0.f, 0.f, 0.f};
-      if (EPI == EPI_LN_ROWS || EPI == EPI_LN_COLS) {
-        lr_a = *(const float4v*)(rvs + i * 16 + fg * 4);
-        lr_b = *(const float4v*)(rvs + MT * 16 + i * 16 + fg * 4);
-      }
+      float4v lr_a, lr_b;
+      row_vectors(i, lr_a, lr_b);
 #pragma unroll
       for (int j = 0; j < 4; ++j)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float v;
-          if (EPI == EPI_LN_ROWS) v = __builtin_fmaf(acc[i][j][r], lr_a[r], __builtin_fmaf(-lr_b[r], lnc_b[j], bi4[j]));
-          else if (EPI == EPI_LN_COLS) v = __builtin_fmaf(acc[i][j][r], lnc_a[j], __builtin_fmaf(-lnc_b[j], lr_a[r], lr_b[r]));
-          else v = fmaxf(__builtin_fmaf(acc[i][j][r], sc4[j], bi4[j]), lo);
-          lds_put<float>(wst, SPW, fg * 4 + r, j * 16 + frow, v);
-        }
+        for (int r = 0; r < 4; ++r) lds_put<float>(wst, SPW, fg * 4 + r, j * 16 + frow, value(acc[i][j][r], j, lr_a[r], lr_b[r]));
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       half8 ov[2];
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        const int row = t * 8 + r8;
-        const float4v a0 = *(const float4v*)(wst + row * SPW + c8 * 32), a1 = *(const float4v*)(wst + row * SPW + c8 * 32 + 16);
-        float f[8] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
+        float f[8];
+        staged8(wst + (t * 8 + r8) * SPW + c8 * 32, f);
         if (GELU)
 #pragma unroll
           for (int k = 0; k < 8; ++k) f[k] = gelu_erf(f[k]);
@@ -818,10 +812,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_igemm_kernel(IgemmArgs p) {
         for (int k = 0; k < 8; ++k) ov[t][k] = (_Float16)f[k];
       }
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        if (C::SMALL) *(half8*)(o + (size_t)(i * 2 + t) * step8) = ov[t];
-        else __builtin_nontemporal_store(ov[t], (half8*)(o + (size_t)(i * 2 + t) * step8));
-      }
+      for (int t = 0; t < 2; ++t) tile_store<C::SMALL>(ov[t], (half8*)(o + (size_t)(i * 2 + t) * step8));
     }
   };
   typedef std::true_type Y;
@@ -847,27 +838,26 @@ __global__ __launch_bounds__(NTHREADS) void conv_igemm_kernel(IgemmArgs p) {
   }
 }
 
-// the LayerNorm-folded epilogues (ConvDesc::epi): plain f16 GEMMs on the 256 x 256, 256 x 128 and 128 x 128 tiles
-template <int BN_, int EPI>
-int launch_epi(mhip_ctx* ctx, const IgemmArgs& a, int kid) {
-  dim3 grid((unsigned)(a.mtiles * a.ntiles)), block(NTHREADS);
+// one launch of one instantiation: grid, LDS size (raised once per instantiation), profile slot `kid`, error text
+template <typename T, int POOL, int BN_, bool DUAL, int EPI = EPI_NONE>
+int launch(mhip_ctx* ctx, const IgemmArgs& a, int kid) {
+  const auto kernel = conv_igemm_kernel<T, POOL, BN_, DUAL, EPI>;
   const size_t lds = Cfg<BN_>::LDS_BYTES;
   static std::once_flag attr_set;
-  std::call_once(attr_set, [&] {
-    (void)hipFuncSetAttribute((const void*)conv_igemm_kernel<_Float16, POOL_NONE, BN_, false, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  });
-  PROF_LAUNCH(ctx, kid, hipLaunchKernelGGL((conv_igemm_kernel<_Float16, POOL_NONE, BN_, false, EPI>), grid, block, lds, ctx->stream, a));
+  std::call_once(attr_set, [&] { (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
+  PROF_LAUNCH(ctx, kid, hipLaunchKernelGGL(kernel, dim3((unsigned)(a.mtiles * a.ntiles)), dim3(NTHREADS), lds, ctx->stream, a));
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return mhip_fail(ctx, MHIP_EHIP, "conv_igemm launch: %s", hipGetErrorString(e));
   return 0;
 }
 
+// the LayerNorm-folded epilogues (ConvDesc::epi): plain f16 GEMMs on the 256 x 256, 256 x 128 and 128 x 128 tiles
 template <int BN_>
-int launch_epi_any(mhip_ctx* ctx, const IgemmArgs& a, int kid) {
+int launch_epi(mhip_ctx* ctx, const IgemmArgs& a, int kid) {
   switch (a.epi) {
-    case EPI_LN_ROWS: return launch_epi<BN_, EPI_LN_ROWS>(ctx, a, kid);
-    case EPI_LN_COLS: return launch_epi<BN_, EPI_LN_COLS>(ctx, a, kid);
-    case EPI_SPLIT: return launch_epi<BN_, EPI_SPLIT>(ctx, a, kid);
+    case EPI_LN_ROWS: return launch<_Float16, POOL_NONE, BN_, false, EPI_LN_ROWS>(ctx, a, kid);
+    case EPI_LN_COLS: return launch<_Float16, POOL_NONE, BN_, false, EPI_LN_COLS>(ctx, a, kid);
+    case EPI_SPLIT: return launch<_Float16, POOL_NONE, BN_, false, EPI_SPLIT>(ctx, a, kid);
     default: return mhip_fail(ctx, MHIP_EINVAL, "conv_igemm: unknown epilogue %d", a.epi);
   }
 }
@@ -876,62 +866,36 @@ template <typename T, int BN_>
 int launch_t(mhip_ctx* ctx, const IgemmArgs& a, int pool) {
   constexpr int KID = BN_ == 64 ? MHIP_K_IGEMM_T64 : (BN_ == 128 ? MHIP_K_IGEMM_T128 : MHIP_K_IGEMM_T256);
   if (a.epi != EPI_NONE) {
-    if constexpr (std::is_same<T, _Float16>::value && BN_ != 64) return launch_epi_any<BN_>(ctx, a, KID);
+    if constexpr (std::is_same<T, _Float16>::value && BN_ != 64) return launch_epi<BN_>(ctx, a, KID);
     else return mhip_fail(ctx, MHIP_EINVAL, "conv_igemm: a LayerNorm-folded epilogue needs an f16 GEMM with N > 64");
   }
-  dim3 grid((unsigned)(a.mtiles * a.ntiles)), block(NTHREADS);
-  const size_t lds = Cfg<BN_>::LDS_BYTES;
-  static std::once_flag attr_set;
-  std::call_once(attr_set, [&] {
-#define SETATTR(...) (void)hipFuncSetAttribute((const void*)__VA_ARGS__, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-    SETATTR(conv_igemm_kernel<T, POOL_NONE, BN_, false>);
-    SETATTR(conv_igemm_kernel<T, POOL_2x2, BN_, false>);
-    SETATTR(conv_igemm_kernel<T, POOL_2x1, BN_, false>);
-    SETATTR(conv_igemm_kernel<T, POOL_NONE, BN_, true>);
-#undef SETATTR
-  });
-  if (a.in2) {
-    PROF_LAUNCH(ctx, KID,
-                hipLaunchKernelGGL((conv_igemm_kernel<T, POOL_NONE, BN_, true>), grid, block, lds, ctx->stream, a));
-  } else {
-    switch (pool) {
-      case POOL_NONE:
-        PROF_LAUNCH(ctx, KID,
-                    hipLaunchKernelGGL((conv_igemm_kernel<T, POOL_NONE, BN_, false>), grid, block, lds, ctx->stream, a));
-        break;
-      case POOL_2x2:
-        PROF_LAUNCH(ctx, KID,
-                    hipLaunchKernelGGL((conv_igemm_kernel<T, POOL_2x2, BN_, false>), grid, block, lds, ctx->stream, a));
-        break;
-      default:
-        PROF_LAUNCH(ctx, KID,
-                    hipLaunchKernelGGL((conv_igemm_kernel<T, POOL_2x1, BN_, false>), grid, block, lds, ctx->stream, a));
-        break;
-    }
+  if (a.in2) return launch<T, POOL_NONE, BN_, true>(ctx, a, KID);
+  switch (pool) {
+    case POOL_NONE: return launch<T, POOL_NONE, BN_, false>(ctx, a, KID);
+    case POOL_2x2: return launch<T, POOL_2x2, BN_, false>(ctx, a, KID);
+    default: return launch<T, POOL_2x1, BN_, false>(ctx, a, KID);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return mhip_fail(ctx, MHIP_EHIP, "conv_igemm launch: %s", hipGetErrorString(e));
-  return 0;
 }
 
 // the small 128x128 tile: plain (unpooled, single-input) convs / GEMMs only
 template <typename T>
 int launch_small(mhip_ctx* ctx, const IgemmArgs& a) {
   if (a.epi != EPI_NONE) {
-    if constexpr (std::is_same<T, _Float16>::value) return launch_epi_any<1128>(ctx, a, MHIP_K_IGEMM_S128);
+    if constexpr (std::is_same<T, _Float16>::value) return launch_epi<1128>(ctx, a, MHIP_K_IGEMM_S128);
     else return mhip_fail(ctx, MHIP_EINVAL, "conv_igemm: a LayerNorm-folded epilogue needs an f16 GEMM");
   }
-  dim3 grid((unsigned)(a.mtiles * a.ntiles)), block(NTHREADS);
-  const size_t lds = Cfg<1128>::LDS_BYTES;
-  static std::once_flag attr_set;
-  std::call_once(attr_set, [&] {
-    (void)hipFuncSetAttribute((const void*)conv_igemm_kernel<T, POOL_NONE, 1128, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  });
-  PROF_LAUNCH(ctx, MHIP_K_IGEMM_S128,
-              hipLaunchKernelGGL((conv_igemm_kernel<T, POOL_NONE, 1128, false>), grid, block, lds, ctx->stream, a));
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return mhip_fail(ctx, MHIP_EHIP, "conv_igemm launch: %s", hipGetErrorString(e));
-  return 0;
+  return launch<T, POOL_NONE, 1128, false>(ctx, a, MHIP_K_IGEMM_S128);
+}
+
+// the tile shape chosen by mhip_launch_conv_igemm: 64, 128, 256, or 1128 for the small tile
+template <typename T>
+int launch_tile(mhip_ctx* ctx, const IgemmArgs& a, int pool, int tile) {
+  switch (tile) {
+    case 1128: return launch_small<T>(ctx, a);
+    case 256: return launch_t<T, 256>(ctx, a, pool);
+    case 128: return launch_t<T, 128>(ctx, a, pool);
+    default: return launch_t<T, 64>(ctx, a, pool);
+  }
 }
 
 }  // namespace
@@ -974,8 +938,6 @@ int mhip_launch_conv_igemm(mhip_ctx* ctx, int precision, const ConvDesc& d) {
     return mhip_fail(ctx, MHIP_EINVAL, "conv_igemm: bad output pitch %d", a.ldc);
   if ((a.res || a.ldc) && ((size_t)(a.ldc ? a.ldc : d.N) * (d.out_f32 ? 4 : esz)) % 16 != 0)
     return mhip_fail(ctx, MHIP_EINVAL, "conv_igemm: residual / pitched outputs need 16-byte aligned rows");
-  static const int stagger_env = getenv("MARIE_HIP_STAGGER") ? atoi(getenv("MARIE_HIP_STAGGER")) : 0;
-  a.stagger = stagger_env * (d.KH * d.KW * d.Cin / 64) / 16;      // in sixteenths of a slice count
   a.epi = d.epi;
   a.ln_a = d.ln_a; a.ln_b = d.ln_b; a.ln_cs = d.ln_cs; a.row_bias = d.row_bias;
   a.out2 = (char*)d.out2; a.res2 = (const char*)d.res2; a.stats = d.stats; a.stats_ld = d.stats_ld;
@@ -1038,22 +1000,19 @@ int mhip_launch_conv_igemm(mhip_ctx* ctx, int precision, const ConvDesc& d) {
   // too few 256 x 256 tiles to occupy the 256 CUs but enough 256 x 128 ones for one round (decoder-step GEMMs into 1024
   // columns: 7680 x 1024 = 120 / 240 tiles): the wider-than-tall tile stages 25 % fewer bytes per MFMA than 128 x 128
   static const bool mid_off = getenv("MARIE_HIP_NO_MID_TILE") != nullptr;      // A/B aid
+  int tile = bn == 256 ? 256 : (bn == 128 ? 128 : 64);
   if (!mid_off && bn == 256 && a.mtiles * a.ntiles < 192 && a.mtiles * ((a.N + 127) / 128) >= 192 && !force_bn) {
     a.ntiles = (a.N + 127) / 128;
     ctx->prof[MHIP_K_IGEMM_T128].flops += fl;
-    return precision == MHIP_PREC_F16 ? launch_t<_Float16, 128>(ctx, a, d.pool) : launch_t<float, 128>(ctx, a, d.pool);
-  }
-  // too few big tiles to occupy the 256 CUs (decoder-step GEMMs, heads on small maps): 128 x 128 tiles instead
-  if (a.mtiles * a.ntiles < 192 && (a.N > 64 || d.epi != EPI_NONE) && d.pool == POOL_NONE && !d.in2) {
+    tile = 128;
+  } else if (a.mtiles * a.ntiles < 192 && (a.N > 64 || d.epi != EPI_NONE) && d.pool == POOL_NONE && !d.in2) {
+    // too few big tiles to occupy the 256 CUs (decoder-step GEMMs, heads on small maps): 128 x 128 tiles instead
     a.mtiles = (a.M + 127) / 128;
     a.ntiles = (a.N + 127) / 128;
     ctx->prof[MHIP_K_IGEMM_S128].flops += fl;
-    return precision == MHIP_PREC_F16 ? launch_small<_Float16>(ctx, a) : launch_small<float>(ctx, a);
+    tile = 1128;
+  } else {
+    ctx->prof[bn == 64 ? MHIP_K_IGEMM_T64 : (bn == 128 ? MHIP_K_IGEMM_T128 : MHIP_K_IGEMM_T256)].flops += fl;
   }
-  ctx->prof[bn == 64 ? MHIP_K_IGEMM_T64 : (bn == 128 ? MHIP_K_IGEMM_T128 : MHIP_K_IGEMM_T256)].flops += fl;
-  if (precision == MHIP_PREC_F16)
-    return bn == 256 ? launch_t<_Float16, 256>(ctx, a, d.pool)
-                     : (bn == 128 ? launch_t<_Float16, 128>(ctx, a, d.pool) : launch_t<_Float16, 64>(ctx, a, d.pool));
-  return bn == 256 ? launch_t<float, 256>(ctx, a, d.pool)
-                   : (bn == 128 ? launch_t<float, 128>(ctx, a, d.pool) : launch_t<float, 64>(ctx, a, d.pool));
+  return precision == MHIP_PREC_F16 ? launch_tile<_Float16>(ctx, a, d.pool, tile) : launch_tile<float>(ctx, a, d.pool, tile);
 }

@@ -614,10 +614,48 @@ def test_straight_line_and_bounds_checked_columns_agree(ctx, D, Nf, Nt, tile):
         assert _same_bits(outs[0][:, :n], o[:, :n]), f"columns shared by N = {Nf} and N = {N} differ"
 
 
+PAIR_PLAIN = [
+    # N, M_full, tile: the smallest whole-tile N and M_full for which the launcher's rule picks the shape for all three M (the big
+    # tiles need 192 of them).  K = 64 is one slice.
+    (128, 128, S128), (128, 192 * 256, T128), (256, 192 * 256, T256),
+]
+_PLAIN_OPS = {}
+
+
+def _plain_operands(N, Mf):
+    """A [Mf + 4][64], W [N][64], bias [N] on the device, made once per case and left unchanged"""
+    if (N, Mf) not in _PLAIN_OPS:
+        g = _gen(7500 + N + Mf)
+        _PLAIN_OPS[(N, Mf)] = tuple(t.to(DEV) for t in (_noise(g, Mf + 4, 64).half(), _weights(g, N, 64), _noise(g, N) * 0.5))
+    return _PLAIN_OPS[(N, Mf)]
+
+
+@pytest.mark.parametrize("act", [NONE, GELU])
+@pytest.mark.parametrize("N,Mf,tile", PAIR_PLAIN)
+def test_straight_line_and_bounds_checked_plain_f16_agree(ctx, N, Mf, tile, act):
+    """the plain epilogue (EPI_NONE), f16 out, no residual, with and without GELU: `f16_fast` against `body`"""
+    K, bm = 64, TILE_BM[tile]
+    Ms = (Mf, Mf + 4, Mf - bm + 4)
+    assert Mf % bm == 0 and N % {T256: 256, T128: 128, S128: 128}[tile] == 0 and all(_rule(M, N) == tile for M in Ms)
+    A, W, bias = _plain_operands(N, Mf)
+    outs = []
+    for M in Ms:
+        out = _guarded(M, N, torch.float16, 7.0)
+        before = out[M:].clone()
+        _launch(ctx, tile, epi=0, M=M, N=N, K=K, act=act, out=out, bias=bias, **{"in": A[:M], "w": W})
+        assert _same_bits(out[M:], before), "guard rows behind the output were written"
+        assert bool(torch.isfinite(out[:M]).all()), "unwritten or non-finite output elements"
+        outs.append(out[:M])
+    for o, M in zip(outs[1:], Ms[1:]):
+        n = min(M, Mf)
+        assert _same_bits(outs[0][:n], o[:n]), f"rows shared by M = {Mf} and M = {M} differ"
+
+
 def test_every_epilogue_is_cased_on_every_tile_shape():
-    """each case asserts the tile shape that ran; this keeps the tables covering all nine (epilogue, shape) combinations"""
+    """each case asserts the tile shape that ran; this keeps the tables covering all twelve (epilogue, shape) combinations"""
     have = {("rows", c[4]) for c in ROWS_CASES} | {("cols", c[2]) for c in COLS_CASES} | {("split", c[5]) for c in SPLIT_CASES}
-    assert have == {(e, t) for e in ("rows", "cols", "split") for t in (T256, T128, S128)}
+    have |= {("plain", c[2]) for c in PAIR_PLAIN}
+    assert have == {(e, t) for e in ("rows", "cols", "split", "plain") for t in (T256, T128, S128)}
     assert {c[3] for c in PATCH_CASES} == {T256, T128, S128}
 
 
