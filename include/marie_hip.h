@@ -236,11 +236,14 @@ int mhip_craft_detect_host(mhip_craft* m, const uint8_t* page_host, int h, int w
                            double mag_ratio, float text_threshold, float link_threshold, float low_text,
                            float* boxes_host, int max_boxes, int* n_boxes, float* scores_host, double* ratio_out);
 
-/* ---- Pillow-exact 8-bit resize (antialiased BILINEAR / BICUBIC) of RGB images ------------------------------------------ */
+/* ---- Pillow-exact 8-bit resize (antialiased LANCZOS / BILINEAR / BICUBIC) of RGB images -------------------------------- */
+#define MHIP_PIL_LANCZOS 1    /* PIL.Image.LANCZOS  */
 #define MHIP_PIL_BILINEAR 2   /* PIL.Image.BILINEAR */
 #define MHIP_PIL_BICUBIC 3    /* PIL.Image.BICUBIC  */
 /* replaces: ResizeShortestEdge/ResizeTransform's PIL resize (marie/detectron/detector.py:103-105) and TrOCR's
- * im.resize((384, 384), BICUBIC) (marie/document/trocr_ocr_processor.py:116-118).  Host u8 [sh][sw][3] -> [dh][dw][3]. */
+ * im.resize((384, 384), BICUBIC) (marie/document/trocr_ocr_processor.py:116-118); LANCZOS is the document splitter's page
+ * resize (marie/components/document_splitter/transformers.py:111-113).  Host u8 [sh][sw][3] -> [dh][dw][3]; a filter other
+ * than the three above is MHIP_EINVAL. */
 int mhip_pil_resize_rgb_host(mhip_ctx* ctx, const uint8_t* src_host, int sh, int sw, uint8_t* dst_host, int dh, int dw,
                              int filter);
 
@@ -549,6 +552,9 @@ int mhip_layoutlmv3_set_tensor(mhip_layoutlmv3* m, const char* key, const float*
 int mhip_layoutlmv3_finalize(mhip_layoutlmv3* m);
 int mhip_layoutlmv3_alloc_arena(mhip_layoutlmv3* m);
 int mhip_layoutlmv3_arena(mhip_layoutlmv3* m, void** arena_dev, size_t* bytes);
+/* the Pillow filter of the page resize to input_size x input_size: MHIP_PIL_LANCZOS (the document splitter's), _BILINEAR (the
+ * default: the classifier's and the indexer's) or _BICUBIC; anything else is MHIP_EINVAL.  Holds for every later call.       */
+int mhip_layoutlmv3_set_resample(mhip_layoutlmv3* m, int filter);
 /* rows per page of the hidden states: max_text + (input_size / patch)^2 + 1 (709)                                          */
 int mhip_layoutlmv3_seq_len(const mhip_layoutlmv3_config* cfg);
 /* LayoutLMv3Encoder.relative_position_bucket (bidirectional) of one difference, evaluated in float32 as the library does.

@@ -137,6 +137,7 @@ _SIGNATURES = (
     ("mhip_layoutlmv3_finalize", _i, [_vp]),
     ("mhip_layoutlmv3_alloc_arena", _i, [_vp]),
     ("mhip_layoutlmv3_arena", _i, [_vp, C.POINTER(_vp), C.POINTER(_sz)]),
+    ("mhip_layoutlmv3_set_resample", _i, [_vp, _i]),
     ("mhip_layoutlmv3_seq_len", _i, [_vp]),
     ("mhip_layoutlmv3_bucket", _i, [_i, _i, _i]),
     ("mhip_layoutlmv3_max_token_labels", _i, [_i]),

@@ -309,6 +309,7 @@ int mhip_launch_unnest(mhip_ctx* ctx, int precision, const void* in, const void*
                        int H, int W, int C, int nest);
 
 // ------------------------------------------------------------------ Pillow-exact resize (pil_resize.hip)
+bool mhip_pil_filter_ok(int filter);      // MHIP_PIL_LANCZOS / _BILINEAR / _BICUBIC
 size_t mhip_pil_resize_scratch_bytes(int sh, int sw, int dh, int dw, int filter);
 int mhip_launch_pil_resize_rgb(mhip_ctx* ctx, const uint8_t* src, int sh, int sw, size_t src_stride, uint8_t* dst, int dh,
                                int dw, int filter, void* scratch);

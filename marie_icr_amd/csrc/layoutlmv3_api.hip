@@ -23,6 +23,7 @@
 struct mhip_layoutlmv3 {
   mhip_ctx* ctx = nullptr;
   int precision = MHIP_PREC_F16;
+  int resample = MHIP_PIL_BILINEAR;      // the Pillow filter of the page resize (mhip_layoutlmv3_set_resample)
   mhip_layoutlmv3_config cfg{};
   TensorStore store;
   Arena arena;
@@ -67,7 +68,7 @@ void lmv3_carve(const mhip_layoutlmv3* m, Carver& ws, const mhip_crop_desc* page
   const mhip_layoutlmv3_config& c = m->cfg;
   const size_t es = m->esz(), D = c.hidden, R = (size_t)n * m->npad(), S = c.input_size, NPAT = m->n_vis() - 1, K0 = 3 * c.patch * c.patch;
   r->resized = ws.take<uint8_t>((size_t)n_pages * S * S * 3);
-  r->frag_bytes = mhip_pil_resize_fragments_scratch(pages, n_pages, c.input_size, c.input_size, MHIP_PIL_BILINEAR);
+  r->frag_bytes = mhip_pil_resize_fragments_scratch(pages, n_pages, c.input_size, c.input_size, m->resample);
   r->frag_scratch = ws.take(r->frag_bytes);
   r->tok = ws.take<int>((size_t)n * c.max_text * 8 * 4);
   r->win_page = ws.take<int>((size_t)n * 4);
@@ -266,7 +267,7 @@ int lmv3_run(mhip_layoutlmv3* m, const uint8_t* base_dev, const mhip_crop_desc* 
              const Lmv3Run& run) {
   mhip_ctx* ctx = m->ctx;
   const int S = m->cfg.input_size, n = (int)win_page.size();
-  int rc = mhip_pil_resize_fragments(ctx, base_dev, pages, n_pages, run.resized, S, S, MHIP_PIL_BILINEAR, run.frag_scratch, run.frag_bytes);
+  int rc = mhip_pil_resize_fragments(ctx, base_dev, pages, n_pages, run.resized, S, S, m->resample, run.frag_scratch, run.frag_bytes);
   if (rc) return rc;
   if ((rc = mhip_stage_h2d(ctx, run.tok, tok.data(), tok.size() * 4))) return rc;
   if ((rc = mhip_stage_h2d(ctx, run.win_page, win_page.data(), win_page.size() * 4))) return rc;
@@ -387,6 +388,13 @@ extern "C" int mhip_layoutlmv3_destroy(mhip_layoutlmv3* m) {
   mhip_quiesce(m->ctx);
   m->arena.release();
   delete m;
+  return MHIP_OK;
+}
+
+extern "C" int mhip_layoutlmv3_set_resample(mhip_layoutlmv3* m, int filter) {
+  if (!m) return MHIP_EINVAL;
+  if (!mhip_pil_filter_ok(filter)) return mhip_fail(m->ctx, MHIP_EINVAL, "layoutlmv3: unknown resample filter %d (1 LANCZOS, 2 BILINEAR, 3 BICUBIC)", filter);
+  m->resample = filter;
   return MHIP_OK;
 }
 

@@ -1,13 +1,15 @@
-// pil_resize.hip — Pillow's 8-bit Image.resize (BILINEAR / BICUBIC, antialiased) for whole pages and crops, bit-exact.
+// pil_resize.hip — Pillow's 8-bit Image.resize (LANCZOS / BILINEAR / BICUBIC, antialiased) for whole pages and crops, bit-exact.
 //
 // Replaces: detectron2 ResizeShortestEdge -> ResizeTransform.apply_image's PIL bilinear resize reached from
 // OptimizedDetectronPredictor.invoke_model (marie/detectron/detector.py:103-105), and TrOCR's
-// ``im.convert("RGB").resize((384, 384), BICUBIC)`` (marie/document/trocr_ocr_processor.py:116-118).
+// ``im.convert("RGB").resize((384, 384), BICUBIC)`` (marie/document/trocr_ocr_processor.py:116-118), and the document
+// splitter's LayoutLMv3ImageProcessor(resample=Image.LANCZOS) (marie/components/document_splitter/transformers.py:111-113).
 //
 // libImaging/Resample.c: per output coordinate a window [xmin, xmin+n) of weights filter((x - center + 0.5) * ss),
 // normalised in double and rounded to 22-bit fixed point; horizontal pass rounded to uint8, then vertical pass.
 // A tiny kernel builds the two coefficient tables on the device (IEEE double, contraction off — the same arithmetic as
-// the C code); the passes are pure integer MACs, 3 interleaved channels per thread.
+// the C code); the passes are pure integer MACs, 3 interleaved channels per thread.  LANCZOS takes its sin from the device
+// library where Pillow takes it from the host libm: no rounded coefficient has been seen to move (DESIGN.md §3 pil_resize).
 #include <math.h>
 
 #include <algorithm>
@@ -20,9 +22,22 @@ namespace {
 constexpr int PRECISION_BITS = 32 - 8 - 2;
 
 #pragma clang fp contract(off)
+// the filter supports of Resample.c: lanczos 3, bilinear 1, bicubic 2
+__host__ __device__ __forceinline__ double support_of(int filter) {
+  return filter == MHIP_PIL_LANCZOS ? 3.0 : (filter == MHIP_PIL_BILINEAR ? 1.0 : 2.0);
+}
+
+// sinc_filter of Resample.c
+__device__ __forceinline__ double sinc(double x) {
+  if (x == 0.0) return 1.0;
+  x = x * M_PI;
+  return sin(x) / x;
+}
+
 __device__ __forceinline__ double filt(int filter, double x) {
   if (x < 0.0) x = -x;
   if (filter == MHIP_PIL_BILINEAR) return x < 1.0 ? 1.0 - x : 0.0;
+  if (filter == MHIP_PIL_LANCZOS) return x < 3.0 ? sinc(x) * sinc(x / 3) : 0.0;      // lanczos_filter: the truncated sinc
   const double a = -0.5;
   if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
   if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
@@ -37,7 +52,7 @@ __global__ void pil_coeffs_kernel(int in_size, int out_size, int filter, int ksi
   const double scale = (double)in_size / (double)out_size;
   double filterscale = scale;
   if (filterscale < 1.0) filterscale = 1.0;
-  const double support = (filter == MHIP_PIL_BILINEAR ? 1.0 : 2.0) * filterscale;
+  const double support = support_of(filter) * filterscale;
   const double center = ((double)xx + 0.5) * scale;
   const double ss = 1.0 / filterscale;
   int xmin = (int)(center - support + 0.5);
@@ -122,7 +137,7 @@ __global__ void pil_coeffs_batch_kernel(const FragDev* __restrict__ fr, int axis
   const double scale = (double)in_size / (double)out_size;
   double filterscale = scale;
   if (filterscale < 1.0) filterscale = 1.0;
-  const double support = (filter == MHIP_PIL_BILINEAR ? 1.0 : 2.0) * filterscale;
+  const double support = support_of(filter) * filterscale;
   const double center = ((double)xx + 0.5) * scale;
   const double ss = 1.0 / filterscale;
   int xmin = (int)(center - support + 0.5);
@@ -195,7 +210,7 @@ __global__ __launch_bounds__(256) void pil_vpass_batch_kernel(const uint8_t* __r
 int ksize_of(int in_size, int out_size, int filter) {
   double scale = (double)in_size / (double)out_size;
   if (scale < 1.0) scale = 1.0;
-  const double support = (filter == MHIP_PIL_BILINEAR ? 1.0 : 2.0) * scale;
+  const double support = support_of(filter) * scale;
   return (int)ceil(support) * 2 + 1;
 }
 
@@ -231,6 +246,8 @@ void frag_carve(Carver& c, const mhip_crop_desc* descs, int n, int dh, int dw, i
 
 }  // namespace
 
+bool mhip_pil_filter_ok(int filter) { return filter == MHIP_PIL_LANCZOS || filter == MHIP_PIL_BILINEAR || filter == MHIP_PIL_BICUBIC; }
+
 size_t mhip_pil_resize_scratch_bytes(int sh, int sw, int dh, int dw, int filter) {
   PilScratch s;
   return mhip_layout_bytes([&](Carver& c) { pil_carve(c, 1, (size_t)sh * dw * 3, dh, dw, ksize_of(sw, dw, filter), ksize_of(sh, dh, filter), &s); });
@@ -239,7 +256,7 @@ size_t mhip_pil_resize_scratch_bytes(int sh, int sw, int dh, int dw, int filter)
 // src: u8 RGB rows of `src_stride` bytes; dst [dh][dw][3]; scratch from mhip_pil_resize_scratch_bytes
 int mhip_launch_pil_resize_rgb(mhip_ctx* ctx, const uint8_t* src, int sh, int sw, size_t src_stride, uint8_t* dst, int dh,
                                int dw, int filter, void* scratch) {
-  if (sh < 1 || sw < 1 || dh < 1 || dw < 1 || (filter != MHIP_PIL_BILINEAR && filter != MHIP_PIL_BICUBIC))
+  if (sh < 1 || sw < 1 || dh < 1 || dw < 1 || !mhip_pil_filter_ok(filter))
     return mhip_fail(ctx, MHIP_EINVAL, "pil_resize: bad arguments");
   const int kx = ksize_of(sw, dw, filter), ky = ksize_of(sh, dh, filter);
   Carver c(scratch);
@@ -262,6 +279,7 @@ int mhip_launch_pil_resize_rgb(mhip_ctx* ctx, const uint8_t* src, int sh, int sw
 int mhip_pil_resize_fragments(mhip_ctx* ctx, const uint8_t* base_dev, const mhip_crop_desc* descs, int n, uint8_t* dst, int dh,
                               int dw, int filter, void* scratch, size_t scratch_bytes) {
   if (n < 1) return 0;
+  if (!mhip_pil_filter_ok(filter)) return mhip_fail(ctx, MHIP_EINVAL, "pil_resize: unknown filter %d", filter);
   std::vector<FragDev> fr(n);
   size_t tmp_off = 0;
   int hmax = 1;
@@ -299,7 +317,7 @@ size_t mhip_pil_resize_fragments_scratch(const mhip_crop_desc* descs, int n, int
   return mhip_layout_bytes([&](Carver& c) { frag_carve(c, descs, n, dh, dw, filter, &s); });
 }
 
-// replaces: Image.fromarray(rgb).resize((dw, dh), BILINEAR | BICUBIC) on host buffers (test / standalone entry)
+// replaces: Image.fromarray(rgb).resize((dw, dh), LANCZOS | BILINEAR | BICUBIC) on host buffers (test / standalone entry)
 extern "C" int mhip_pil_resize_rgb_host(mhip_ctx* ctx, const uint8_t* src_host, int sh, int sw, uint8_t* dst_host, int dh,
                                         int dw, int filter) {
   if (!ctx || !src_host || !dst_host) return MHIP_EINVAL;

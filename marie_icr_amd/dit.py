@@ -192,11 +192,15 @@ def det_final(ctx: Context, head6: np.ndarray, rois: np.ndarray, img_hw, page_hw
     return boxes[: cnt.value], scores[: cnt.value]
 
 
-def pil_resize_rgb(ctx: Context, img: np.ndarray, out_hw, bicubic: bool = False) -> np.ndarray:
+def pil_resize_rgb(ctx: Context, img: np.ndarray, out_hw, bicubic: bool = False, filter: Optional[int] = None) -> np.ndarray:
+    """``Image.fromarray(img).resize((w, h), filter)`` through ``mhip_pil_resize_rgb_host``; ``filter`` is Pillow's number
+    (1 LANCZOS, 2 BILINEAR, 3 BICUBIC) and, when given, takes the place of ``bicubic``."""
+    if filter is None:
+        filter = 3 if bicubic else 2
     img = np.ascontiguousarray(img, np.uint8)
     out = np.empty((int(out_hw[0]), int(out_hw[1]), 3), np.uint8)
     check(ctx.h, ctx.lib.mhip_pil_resize_rgb_host(ctx.h, _vp(img), img.shape[0], img.shape[1], _vp(out), out.shape[0],
-                                                  out.shape[1], 3 if bicubic else 2), "mhip_pil_resize_rgb_host")
+                                                  out.shape[1], int(filter)), "mhip_pil_resize_rgb_host")
     return out
 
 

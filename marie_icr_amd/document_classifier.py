@@ -24,6 +24,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from ._lib import PREC_F16, PREC_F32, Context, MarieHipError
+from .layoutlmv3 import PIL_BILINEAR
 
 MAX_LENGTH = 512          # predict_document_image: max_length=512, padding="max_length", truncation=True
 
@@ -271,29 +272,29 @@ def _load_state(model_dir: str) -> Dict[str, np.ndarray]:
     raise FileNotFoundError(f"no pytorch_model.bin or model.safetensors in {model_dir}")
 
 
-class TransformersDocumentClassifier:
-    """marie/components/document_classifier/transformers.py:41-361 for ``task="text-classification-multimodal"``.
+class LayoutLMv3PagePredictor:
+    """What the components that run LayoutLMv3 sequence classification page by page share (the document classifier, and
+    the document splitter of ``document_splitter.py``): the tokeniser, the weight loader, the model call and the ``predict``
+    surface.  A component names the tag its prediction goes under and the Pillow filter of its image processor.
 
     ``model_name_or_path`` is a local directory with ``config.json``, the weights (``pytorch_model.bin`` or
     ``model.safetensors``) and, unless ``tokenizer`` names another directory, ``vocab.json`` + ``merges.txt``.  ``state`` /
     ``config`` (a state dict under the Hugging Face key names, a ``config.json`` dictionary) replace the files of the same
     content."""
 
-    def __init__(self, model_name_or_path: str, tokenizer: Optional[str] = None, use_gpu: bool = True, top_k: int = 1,
-                 task: str = "text-classification-multimodal", batch_size: int = 16, id2label: Optional[dict] = None, *,
-                 state: Optional[Dict[str, np.ndarray]] = None, config: Optional[dict] = None, precision: str = "f16",
-                 ctx: Optional[Context] = None, **kwargs):
-        if task in ("text-classification", "zero-shot-classification"):
-            raise NotImplementedError(f"task {task!r}: only 'text-classification-multimodal' (LayoutLMv3) is built")
-        if task != "text-classification-multimodal":
-            raise ValueError(f"unknown task {task!r}")
+    TAG = "classification"          # documents get tags[TAG]
+    RESAMPLE = PIL_BILINEAR         # LayoutLMv3ImageProcessor(resample=...) of the component
+
+    def _setup(self, model_name_or_path: str, tokenizer: Optional[str], use_gpu: bool, batch_size: int,
+               id2label: Optional[dict], state: Optional[Dict[str, np.ndarray]], config: Optional[dict], precision: str,
+               ctx: Optional[Context]):
         if not use_gpu:
-            raise MarieHipError("TransformersDocumentClassifier runs on the GPU only: there is no CPU path in this project")
+            raise MarieHipError(f"{type(self).__name__} runs on the GPU only: there is no CPU path in this project")
         if precision not in ("f16", "f32"):
             raise ValueError(f"precision {precision!r}: 'f16' or 'f32'")
         if not os.path.isdir(model_name_or_path):
             raise FileNotFoundError(f"model directory {model_name_or_path!r} does not exist (models are local directories)")
-        self.task, self.top_k, self.batch_size = task, int(top_k), int(batch_size)
+        self.batch_size = int(batch_size)
         self.model_dir = model_name_or_path
         tok_dir = tokenizer if tokenizer is not None else model_name_or_path
         self.tokenizer = ByteLevelBPE(os.path.join(tok_dir, "vocab.json"), os.path.join(tok_dir, "merges.txt"))
@@ -321,6 +322,7 @@ class TransformersDocumentClassifier:
         if state is None:
             state = _load_state(self.model_dir)
         self.model = LayoutLMv3Model(self.ctx, state, cfg, self.precision)
+        self.model.set_resample(self.RESAMPLE)
 
     def _logits(self, pages: List[np.ndarray], ids: np.ndarray, bbox: np.ndarray, mask: np.ndarray) -> np.ndarray:
         """One model call over all pages -> (n, num_labels) fp32."""
@@ -377,7 +379,8 @@ class TransformersDocumentClassifier:
     def predict(self, documents, words: Optional[List[List[str]]] = None, boxes: Optional[List[List[List[int]]]] = None,
                 batch_size: Optional[int] = None):
         """transformers.py:174-298.  ``documents``: objects with ``.tensor`` and a ``.tags`` dict — their
-        ``tags["classification"]`` is set and they are returned — or plain frames, for which the predictions are returned."""
+        ``tags["classification"]`` (``tags[TAG]``) is set and they are returned — or plain frames, for which the predictions
+        are returned.  Page i is encoded with ``words[i]`` and ``boxes[i]``, whatever the batch size."""
         if batch_size is None:
             batch_size = self.batch_size
         if len(documents) == 0:
@@ -395,10 +398,26 @@ class TransformersDocumentClassifier:
         if plain:
             return formatted
         for document, f in zip(documents, formatted):
-            document.tags["classification"] = f
+            document.tags[self.TAG] = f
         return documents
 
     def close(self):
         m = getattr(self, "model", None)
         if m is not None and hasattr(m, "close"):
             m.close()
+
+
+class TransformersDocumentClassifier(LayoutLMv3PagePredictor):
+    """marie/components/document_classifier/transformers.py:41-361 for ``task="text-classification-multimodal"``; the
+    arguments as on :class:`LayoutLMv3PagePredictor`."""
+
+    def __init__(self, model_name_or_path: str, tokenizer: Optional[str] = None, use_gpu: bool = True, top_k: int = 1,
+                 task: str = "text-classification-multimodal", batch_size: int = 16, id2label: Optional[dict] = None, *,
+                 state: Optional[Dict[str, np.ndarray]] = None, config: Optional[dict] = None, precision: str = "f16",
+                 ctx: Optional[Context] = None, **kwargs):
+        if task in ("text-classification", "zero-shot-classification"):
+            raise NotImplementedError(f"task {task!r}: only 'text-classification-multimodal' (LayoutLMv3) is built")
+        if task != "text-classification-multimodal":
+            raise ValueError(f"unknown task {task!r}")
+        self.task, self.top_k = task, int(top_k)
+        self._setup(model_name_or_path, tokenizer, use_gpu, batch_size, id2label, state, config, precision, ctx)

@@ -16,6 +16,9 @@ import numpy as np
 
 from ._lib import PREC_F16, Context, CropDesc, LayoutLMv3Config, ModelHandle, check, load
 
+# the Pillow filters of the page resize (MHIP_PIL_* of include/marie_hip.h = PIL.Image.LANCZOS / BILINEAR / BICUBIC)
+PIL_LANCZOS, PIL_BILINEAR, PIL_BICUBIC = 1, 2, 3
+
 # config.json keys that map one to one onto mhip_layoutlmv3_config fields
 _CONFIG_KEYS = {"hidden_size": "hidden", "num_hidden_layers": "layers", "num_attention_heads": "heads",
                 "intermediate_size": "ffn", "vocab_size": "vocab", "type_vocab_size": "type_vocab",
@@ -88,6 +91,11 @@ class LayoutLMv3Model(ModelHandle):
         self.seq_len = self.lib.mhip_layoutlmv3_seq_len(C.byref(config))
         if state is not None:
             self.load_state(state)
+
+    def set_resample(self, filter: int) -> None:
+        """The Pillow filter of the page resize for every later call: ``PIL_LANCZOS`` (the document splitter's image
+        processor), ``PIL_BILINEAR`` (the default) or ``PIL_BICUBIC``; anything else raises."""
+        self._call("set_resample", int(filter))
 
     def _inputs(self, n, ids, bbox, mask):
         T = self.cfg.max_text
