@@ -235,6 +235,15 @@ int mhip_craft_detect(mhip_craft* m, const uint8_t* page_dev, int h, int w, int 
 int mhip_craft_detect_host(mhip_craft* m, const uint8_t* page_host, int h, int w, int canvas_size,
                            double mag_ratio, float text_threshold, float link_threshold, float low_text,
                            float* boxes_host, int max_boxes, int* n_boxes, float* scores_host, double* ratio_out);
+/* Stage entry: the post-processing of mhip_craft_detect alone (the same code) on a caller-supplied score map, host fp32
+ * [H][W][2] (text, link); needs no model.  boxes as above.  Optional read-backs of the labelling (each may be NULL):
+ * labels_host int32 [H*W] (0 = background, components numbered in raster order of their first pixel), flags_host uint8
+ * [H*W] (1 = text > low_text, 2 = link > link_threshold), stats_host int32 [stats_cap][6] = left, top, right, bottom,
+ * area, max text score as raw float32 bits, rows 1..n_labels-1 (row 0, the background, is zero).  n_labels counts the
+ * background; stats_cap < n_labels is MHIP_EINVAL, with n_boxes and n_labels valid and no read-back buffer written. */
+int mhip_craft_boxes_host(mhip_ctx* ctx, const float* scores_host, int H, int W, float text_threshold,
+                          float link_threshold, float low_text, float* boxes_host, int max_boxes, int* n_boxes,
+                          int32_t* labels_host, uint8_t* flags_host, int32_t* stats_host, int stats_cap, int* n_labels);
 
 /* ---- Pillow-exact 8-bit resize (antialiased LANCZOS / BILINEAR / BICUBIC) of RGB images -------------------------------- */
 #define MHIP_PIL_LANCZOS 1    /* PIL.Image.LANCZOS  */

@@ -66,6 +66,8 @@ _SIGNATURES = (
                                C.POINTER(_i), _vp, C.POINTER(C.c_double)]),
     ("mhip_craft_detect_host", _i, [_vp, _vp, _i, _i, _i, C.c_double, C.c_float, C.c_float, C.c_float, _vp, _i,
                                     C.POINTER(_i), _vp, C.POINTER(C.c_double)]),
+    ("mhip_craft_boxes_host", _i, [_vp, _vp, _i, _i, C.c_float, C.c_float, C.c_float, _vp, _i, C.POINTER(_i), _vp, _vp,
+                                   _vp, _i, C.POINTER(_i)]),
     ("mhip_crop_batch", _i, [_vp, _vp, _vp, _i, _i, _vp]),
     ("mhip_pil_resize_rgb_host", _i, [_vp, _vp, _i, _i, _vp, _i, _i, _i]),
     ("mhip_vit_create", _i, [_vp, _i, _vp, C.POINTER(_vp)]),

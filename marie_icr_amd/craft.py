@@ -91,6 +91,39 @@ class CraftModel(ModelHandle):
                 for k in range(self.lib.mhip_kernel_count())}
 
 
+def craft_boxes(ctx: Context, scores: np.ndarray, text_threshold: float, link_threshold: float, low_text: float,
+                max_boxes: int = 4096, want_labels: bool = True):
+    """The detector's post-processing alone (stage entry, no model): scores (H, W, 2) fp32 (text, link) ->
+    {"boxes": (K,4,2) fp32 in score-map coords, "n_labels": count incl. background} and, with ``want_labels``,
+    "labels" (H,W) int32, "flags" (H,W) uint8 (1 text, 2 link), "stats" (n_labels, 5) int32 = left, top, right, bottom,
+    area and "max_text" (n_labels,) fp32, rows 1.. valid (row 0 is the background)."""
+    scores = np.ascontiguousarray(scores, dtype=np.float32)
+    if scores.ndim != 3 or scores.shape[2] != 2:
+        raise ValueError(f"scores must be (H, W, 2) fp32, got {scores.shape}")
+    H, W = scores.shape[:2]
+    boxes = np.empty((max(int(max_boxes), 1), 4, 2), np.float32)
+    nb, nl = C.c_int(), C.c_int()
+    cap = H * W // 2 + 2
+    labels = np.empty((H, W), np.int32) if want_labels else None
+    flags = np.empty((H, W), np.uint8) if want_labels else None
+    raw = np.empty((cap, 6), np.int32) if want_labels else None
+
+    def ptr(a):
+        return a.ctypes.data_as(C.c_void_p) if a is not None else C.c_void_p(0)
+
+    check(ctx.h,
+          ctx.lib.mhip_craft_boxes_host(ctx.h, ptr(scores), H, W, float(text_threshold), float(link_threshold),
+                                        float(low_text), ptr(boxes), int(max_boxes), C.byref(nb), ptr(labels), ptr(flags),
+                                        ptr(raw), cap if want_labels else 0, C.byref(nl)),
+          "mhip_craft_boxes_host")
+    out = {"boxes": boxes[:nb.value].copy(), "n_labels": nl.value}
+    if want_labels:
+        raw = raw[:nl.value]
+        out.update(labels=labels, flags=flags, stats=raw[:, :5].copy(),
+                   max_text=np.ascontiguousarray(raw[:, 5]).view(np.float32))
+    return out
+
+
 def adjust_result_coordinates(polys: np.ndarray, ratio_w: float, ratio_h: float, ratio_net: int = 2) -> np.ndarray:
     """reference: adjustResultCoordinates, marie/models/craft/craft_utils.py:268-274 (in-place fp32 scaling)."""
     polys = np.array(polys, dtype=np.float32)

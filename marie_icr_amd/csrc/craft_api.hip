@@ -449,34 +449,33 @@ float norm2(float ax, float ay) {
   return sqrtf(a + b);
 }
 
+// What the post-processing read back from the labelling, for the caller that wants to look at it: views into the staging buffer.
+struct CraftLabels {
+  int n = 0;                       // labels incl. the background
+  const int* labels = nullptr;     // [H*W]
+  const uint8_t* flags = nullptr;  // [H*W]  1 text, 2 link
+  const int* stats = nullptr;      // [n][6] left, top, right, bottom, area, max text score (ordered-int encoding)
+};
+
+// host staging of one read-back: n_labels, labels, flags, statistics at their capacity
+size_t craft_stage_bytes(int npx) {
+  return 64 + (((size_t)npx * 5 + 63) / 64) * 64 + (size_t)(npx / 2 + 2) * 24;
+}
+
 }  // namespace
 
-// Full detector on carved buffers: forward + post-processing.  boxes_host receives up to max_boxes x 8 floats (4 corners x,y
-// in score-map coordinates, clockwise from the top-left-most corner) in OpenCV label order.
-static int craft_detect(mhip_craft* m, const CraftBufs& b, const CPlan& p, float* scores_dev, const uint8_t* page_dev, int h,
-                        int w, float text_threshold, float link_threshold, float low_text, float* boxes_host, int max_boxes,
-                        int* n_boxes, float* scores_host, double* ratio_out) {
-  mhip_ctx* ctx = m->ctx;
-  const int H2 = p.H / 2, W2 = p.W / 2, npx = H2 * W2;
-  int rc = craft_forward(m, b, p, page_dev, h, w, scores_dev);
-  if (rc) return rc;
-  const CclBuffers& cb = b.ccl;
-  rc = mhip_launch_ccl(ctx, scores_dev, H2, W2, low_text, link_threshold, cb);
+// Score maps (device, fp32 [H2][W2][2]) -> boxes: labelling and statistics on the GPU, read-back into `stage` (host memory
+// of craft_stage_bytes(H2 * W2), pinned or not), then the per-label box loop.  boxes_host receives up to max_boxes x 8 floats
+// (4 corners x,y in score-map coordinates, clockwise from the top-left-most corner) in OpenCV label order.
+static int craft_boxes(mhip_ctx* ctx, const CclBuffers& cb, const float* scores_dev, int H2, int W2, float text_threshold,
+                       float link_threshold, float low_text, char* stage, float* boxes_host, int max_boxes, int* n_boxes,
+                       float* scores_host, CraftLabels* seen) {
+  const int npx = H2 * W2;
+  int rc = mhip_launch_ccl(ctx, scores_dev, H2, W2, low_text, link_threshold, cb);
   if (rc) return rc;
 
-  // ---- read back: n_labels, then stats + labels + flags (+ scores on request) into pinned memory ----
-  const size_t need = 64 + (size_t)npx * 5 + (size_t)(npx / 2 + 2) * 24 + (scores_host ? (size_t)npx * 8 : 0);
-  if (need > m->hpin_bytes) {
-    if (m->hpin) (void)hipHostFree(m->hpin);
-    m->hpin = nullptr;
-    m->hpin_bytes = 0;
-    if (hipHostMalloc(&m->hpin, need + need / 4, hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      return mhip_fail(ctx, MHIP_ENOMEM, "pinned staging of %zu bytes failed", need);
-    }
-    m->hpin_bytes = need + need / 4;
-  }
-  char* hp = (char*)m->hpin;
+  // ---- read back: n_labels, then stats + labels + flags (+ scores on request) ----
+  char* hp = stage;
   int* h_n = (int*)hp;
   int* h_labels = (int*)(hp + 64);
   uint8_t* h_flags = (uint8_t*)(hp + 64 + (size_t)npx * 4);
@@ -492,7 +491,7 @@ static int craft_detect(mhip_craft* m, const CraftBufs& b, const CPlan& p, float
   if (scores_host)
     MHIP_HIP(ctx, hipMemcpyAsync(scores_host, scores_dev, (size_t)npx * 8, hipMemcpyDeviceToHost, ctx->stream));
   MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (ratio_out) *ratio_out = p.ratio;
+  if (seen) *seen = CraftLabels{nlab, h_labels, h_flags, h_stats};
 
   int nb = 0;
   std::vector<uint8_t> seg, tmp;
@@ -589,6 +588,30 @@ static int craft_detect(mhip_craft* m, const CraftBufs& b, const CPlan& p, float
   return MHIP_OK;
 }
 
+// Full detector on carved buffers: forward + post-processing, staged through the model's pinned buffer.
+static int craft_detect(mhip_craft* m, const CraftBufs& b, const CPlan& p, float* scores_dev, const uint8_t* page_dev, int h,
+                        int w, float text_threshold, float link_threshold, float low_text, float* boxes_host, int max_boxes,
+                        int* n_boxes, float* scores_host, double* ratio_out) {
+  mhip_ctx* ctx = m->ctx;
+  const int H2 = p.H / 2, W2 = p.W / 2;
+  int rc = craft_forward(m, b, p, page_dev, h, w, scores_dev);
+  if (rc) return rc;
+  const size_t need = craft_stage_bytes(H2 * W2);
+  if (need > m->hpin_bytes) {
+    if (m->hpin) (void)hipHostFree(m->hpin);
+    m->hpin = nullptr;
+    m->hpin_bytes = 0;
+    if (hipHostMalloc(&m->hpin, need + need / 4, hipHostMallocDefault) != hipSuccess) {
+      (void)hipGetLastError();
+      return mhip_fail(ctx, MHIP_ENOMEM, "pinned staging of %zu bytes failed", need);
+    }
+    m->hpin_bytes = need + need / 4;
+  }
+  if (ratio_out) *ratio_out = p.ratio;
+  return craft_boxes(ctx, b.ccl, scores_dev, H2, W2, text_threshold, link_threshold, low_text, (char*)m->hpin, boxes_host,
+                     max_boxes, n_boxes, scores_host, nullptr);
+}
+
 extern "C" int mhip_craft_detect(mhip_craft* m, const uint8_t* page_dev, int h, int w, int canvas_size,
                                  double mag_ratio, float text_threshold, float link_threshold, float low_text,
                                  float* boxes_host, int max_boxes, int* n_boxes, float* scores_host,
@@ -632,4 +655,46 @@ extern "C" int mhip_craft_detect_host(mhip_craft* m, const uint8_t* page_host, i
   MHIP_HIP(ctx, hipMemcpyAsync(page, page_host, (size_t)h * w * 3, hipMemcpyHostToDevice, ctx->stream));
   return craft_detect(m, b, p, scores, page, h, w, text_threshold, link_threshold, low_text, boxes_host, max_boxes, n_boxes,
                       scores_host, ratio_out);
+}
+
+// The post-processing alone on a caller-supplied score map (host fp32 [H][W][2], channel 0 text, 1 link): what the kernel-level
+// tests drive, and a standalone use of the stage.  No model handle, no weights.
+extern "C" int mhip_craft_boxes_host(mhip_ctx* ctx, const float* scores_host, int H, int W, float text_threshold,
+                                     float link_threshold, float low_text, float* boxes_host, int max_boxes, int* n_boxes,
+                                     int32_t* labels_host, uint8_t* flags_host, int32_t* stats_host, int stats_cap,
+                                     int* n_labels) {
+  if (!ctx || !scores_host || !n_boxes || !n_labels || (max_boxes > 0 && !boxes_host)) return MHIP_EINVAL;
+  if (H < 1 || W < 1 || (long long)H * W > 0x7fffff00LL / 4) return mhip_fail(ctx, MHIP_EINVAL, "craft: bad score map %dx%d", H, W);
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  const int npx = H * W;
+  CclBuffers cb;
+  float* scores = nullptr;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
+    mhip_ccl_carve(ws, H, W, &cb);
+    scores = ws.take<float>((size_t)npx * 8);
+  });
+  if (rc) return rc;
+  MHIP_HIP(ctx, hipMemcpyAsync(scores, scores_host, (size_t)npx * 8, hipMemcpyHostToDevice, ctx->stream));
+  std::vector<char> stage(craft_stage_bytes(npx));
+  CraftLabels seen;
+  *n_labels = 0;
+  rc = craft_boxes(ctx, cb, scores, H, W, text_threshold, link_threshold, low_text, stage.data(), boxes_host, max_boxes, n_boxes,
+                   nullptr, &seen);
+  *n_labels = seen.n;
+  if (rc) return rc;
+  if (stats_host && stats_cap < seen.n)   // before any read-back is written: the caller learns n_labels and nothing else
+    return mhip_fail(ctx, MHIP_EINVAL, "craft: %d labels exceed the caller's statistics capacity %d", seen.n, stats_cap);
+  if (labels_host) memcpy(labels_host, seen.labels, (size_t)npx * 4);
+  if (flags_host) memcpy(flags_host, seen.flags, (size_t)npx);
+  if (stats_host) {
+    for (int k = 1; k < seen.n; ++k) {
+      const int* s = seen.stats + (size_t)k * 6;
+      int32_t* o = stats_host + (size_t)k * 6;
+      memcpy(o, s, 5 * 4);
+      const float f = mhip_ordered_bits_to_float(s[5]);
+      memcpy(o + 5, &f, 4);
+    }
+    if (seen.n > 0) memset(stats_host, 0, 24);   // row 0 is the background: no statistics
+  }
+  return MHIP_OK;
 }

@@ -293,13 +293,16 @@ def dilate_rect(seg: np.ndarray, k: int) -> np.ndarray:
 
 
 def get_det_boxes(textmap: np.ndarray, linkmap: np.ndarray, text_threshold: float, link_threshold: float,
-                  low_text: float):
-    """``getDetBoxes_core`` — marie/models/craft/craft_utils.py:25-98 (minus its debug PNG writes)."""
+                  low_text: float, components=None):
+    """``getDetBoxes_core`` — marie/models/craft/craft_utils.py:25-98 (minus its debug PNG writes).
+
+    ``components``: a precomputed ``(n, labels, stats)`` of the combined mask, as ``connected_components`` returns it
+    (a caller with a faster labeller); None runs ``connected_components``."""
     img_h, img_w = textmap.shape
     text_score = (textmap > F32(low_text)).astype(F32)            # cv2.threshold(..., 1, THRESH_BINARY)
     link_score = (linkmap > F32(link_threshold)).astype(F32)
     comb = np.clip(text_score + link_score, 0, 1).astype(np.uint8)
-    n, labels, stats = connected_components(comb)
+    n, labels, stats = connected_components(comb) if components is None else components
     det, mapper = [], []
     remove = np.logical_and(link_score == 1, text_score == 0)
     for k in range(1, n):
