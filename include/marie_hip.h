@@ -621,6 +621,53 @@ int mhip_attention_bias_host(mhip_ctx* ctx, int precision, int heads, int n_tok,
                              const float* w1, const float* wx, const float* wy, int bins_1d, int max_1d, int bins_2d,
                              int max_2d, float* out);
 
+/* ---- VQ-NNF template matching (csrc/vqnnf.hip) -------------------------------------------------------------------------- */
+/* replaces: VQNNFMatcher + GaussHaarFilters + KMeans, marie/components/template_matching/vqnnf/matching/, with the colour
+ * features of PixelFeatureExtractor (num_features == 27), and the peak loop of vqnnf_template_matching.py:184-202,307.
+ * Images are uint8 [H][W][3]; a feature vector is a pixel's RGB and its eight neighbours (wrapping around the edges of its own
+ * H x W image, as torch.roll does), / 255.  Equal distances go to the lowest code.  Rectangles are x, y, w, h.              */
+#define MHIP_VQ_FEATURES 27
+#define MHIP_VQ_MAX_CODES 128
+#define MHIP_VQ_MAX_FILTERS 6
+typedef struct mhip_vq_filters {
+  int32_t n;                                  /* filters, <= MHIP_VQ_MAX_FILTERS                                             */
+  float taps[MHIP_VQ_MAX_FILTERS][16];        /* 4 x 4 integral-image taps (rows, cols), already / 16                        */
+  int32_t dil[MHIP_VQ_MAX_FILTERS][2];        /* dilation over rows, cols (>= 1): the kernel spans 3 * dil + 1               */
+  double weight[MHIP_VQ_MAX_FILTERS];         /* scale weight x filter weight                                                */
+} mhip_vq_filters;
+typedef struct mhip_vq_template mhip_vq_template;
+/* The template-side state of one template: k-means (at most 25 iterations, stop at error <= 1e-4) over the pixels of `box` of
+ * `frame` (host memory, or device memory when on_device) from the centroids at rows init_idx[n_init] of those pixels
+ * (n_init = min(128, w * h) codes).  The labels kept are those of the last assignment, the codebook the updated one.        */
+int mhip_vq_template_create(mhip_ctx* ctx, const uint8_t* frame, int on_device, int H, int W, const int32_t* box,
+                            const int32_t* init_idx, int n_init, mhip_vq_template** out);
+int mhip_vq_template_destroy(mhip_vq_template* t);
+/* codes, iterations run, labels uint8 [h*w] and codebook fp32 [K][27] (any pointer may be NULL)                               */
+int mhip_vq_template_state(mhip_vq_template* t, int* n_codes, int* iterations, uint8_t* labels_out, float* codebook_out);
+/* the filter bank and the template's responses fp32 [filters][K] (get_template_features); required before a match             */
+int mhip_vq_template_set_filters(mhip_vq_template* t, const float* responses, const mhip_vq_filters* filters);
+/* Every window (win_h x win_w at win_xy[n_win][2] = x, y of a device page with rows page_pitch bytes apart) against every
+ * template: code map, heat map and max_objects rounds of arg-max + suppression, launched over the (window, template) grid.
+ * Only the peaks reach the host: peaks_out fp32 [n_win][n_templates][max_objects][3] = row, col, value.                     */
+int mhip_vq_match(mhip_ctx* ctx, const uint8_t* page_dev, int page_h, int page_w, size_t page_pitch, const int32_t* win_xy,
+                  int n_win, int win_h, int win_w, mhip_vq_template* const* templates, int n_templates, int max_objects,
+                  float* peaks_out);
+/* The kernels alone on host arrays (parity tests).  vq_assign: codes_out uint8 [h*w] of `rect` of image [H][W][3].           */
+int mhip_vq_assign_host(mhip_ctx* ctx, const uint8_t* image, int H, int W, const int32_t* rect, const float* codebook,
+                        int n_codes, uint8_t* codes_out);
+/* one k-means iteration from centroids_in [K][27]: labels uint8 [h*w], the updated centroids (an empty cluster's is zero),
+ * members per cluster int32 [K] and error = sum (new - old)^2                                                               */
+int mhip_vq_kmeans_step_host(mhip_ctx* ctx, const uint8_t* image, int H, int W, const int32_t* rect, const float* centroids_in,
+                             int n_codes, uint8_t* labels_out, float* centroids_out, int32_t* counts_out, double* error_out);
+/* code map uint8 [H][W] -> heat fp32 [H][W] (GaussHaarFilters.get_query_map) and each filter's minimum fp64 [filters] or NULL */
+int mhip_vq_heatmap_host(mhip_ctx* ctx, const uint8_t* codes, int H, int W, int n_codes, const float* responses,
+                         const mhip_vq_filters* filters, float* heat_out, double* minima_out);
+/* n heat maps fp32 [n][H][W], updated in place; box_wh int32 [n][2] = the template box's w, h -> peaks fp32 [n][max_objects][3] */
+int mhip_vq_peaks_host(mhip_ctx* ctx, float* heat, int n, int H, int W, const int32_t* box_wh, int max_objects,
+                       float* peaks_out);
+/* cosine similarity of the colour features of n pairs of clips uint8 [n][h][w][3] -> fp32 [n]                                 */
+int mhip_clip_cosine_host(mhip_ctx* ctx, const uint8_t* a, const uint8_t* b, int n, int h, int w, float* out);
+
 /* ---- word-box / line geometry of the DiT box processor (host, pure functions; no ctx) --------------------------------- */
 /* replaces: merge_boxes, marie/utils/overlap.py:268-330 (find_overlap_horizontal(center_y_overlap=0.5) :106-183,
  * merge_bboxes_as_block :186-204).  xyxy fp32 [n][4] -> out_xyxy fp32 (capacity n rows), *n_out rows.       */

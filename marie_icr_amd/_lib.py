@@ -149,6 +149,16 @@ _SIGNATURES = (
     ("mhip_layoutlmv3_tag_host", _i, [_vp, _vp, _sz, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("mhip_token_head_host", _i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("mhip_attention_bias_host", _i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    ("mhip_vq_template_create", _i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, C.POINTER(_vp)]),
+    ("mhip_vq_template_destroy", _i, [_vp]),
+    ("mhip_vq_template_state", _i, [_vp, C.POINTER(_i), C.POINTER(_i), _vp, _vp]),
+    ("mhip_vq_template_set_filters", _i, [_vp, _vp, _vp]),
+    ("mhip_vq_match", _i, [_vp, _vp, _i, _i, _sz, _vp, _i, _i, _i, _vp, _i, _i, _vp]),
+    ("mhip_vq_assign_host", _i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp]),
+    ("mhip_vq_kmeans_step_host", _i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, C.POINTER(C.c_double)]),
+    ("mhip_vq_heatmap_host", _i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    ("mhip_vq_peaks_host", _i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp]),
+    ("mhip_clip_cosine_host", _i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     ("mhip_max_page_size", _i, [_i, _i, _i, _i, C.c_double, C.POINTER(_i), C.POINTER(_i)]),
     ("mhip_resize_area_u8", _i, [_vp, _vp, _i, _i, _i, C.c_size_t, _vp, _i, _i]),
     ("mhip_resize_area_u8_host", _i, [_vp, _vp, _i, _i, _i, _vp, _i, _i]),
@@ -231,6 +241,11 @@ class LayoutLMv3Config(C.Structure):
                 ("rel_pos_bins", C.c_int), ("max_rel_pos", C.c_int), ("rel_2d_pos_bins", C.c_int),
                 ("max_rel_2d_pos", C.c_int), ("layer_norm_eps", C.c_float), ("pad_id", C.c_int), ("num_labels", C.c_int),
                 ("max_text", C.c_int)]
+
+
+class VqFilters(C.Structure):
+    """mirror of ``mhip_vq_filters`` (include/marie_hip.h)"""
+    _fields_ = [("n", C.c_int32), ("taps", (C.c_float * 16) * 6), ("dil", (C.c_int32 * 2) * 6), ("weight", C.c_double * 6)]
 
 
 class CropDesc(C.Structure):

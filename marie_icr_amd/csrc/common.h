@@ -34,7 +34,13 @@ enum MhipKernelId {
   MHIP_K_IGEMM_PATCH = 16,  // conv3x3_patch_kernel            3x3 / pad 1 convolutions
   MHIP_K_CROSS_ATTN = 17,   // decoder encoder-attention over the encoder tokens themselves (absorbed K / V projections)
   MHIP_K_ATTN_BIAS = 18,    // the biased instances of the MHIP_K_ATTN_FLASH kernels (attn_flash.hip): relative-position bias and key mask
-  MHIP_K_COUNT = 19
+  // VQ-NNF template matching (vqnnf.hip)
+  MHIP_K_VQ_ASSIGN = 19,    // nearest code of every pixel's 27 colour features
+  MHIP_K_VQ_KMEANS = 20,    // codebook update of one k-means iteration (the assignment is counted in MHIP_K_VQ_ASSIGN)
+  MHIP_K_VQ_HEATMAP = 21,   // Gauss-Haar box filters over per-code integral images held in LDS, and the sum of the filters
+  MHIP_K_VQ_PEAKS = 22,     // arg-max and suppression per (window, template)
+  MHIP_K_CLIP_COSINE = 23,  // cosine similarity of the colour features of clip pairs
+  MHIP_K_COUNT = 24
 };
 
 constexpr int MHIP_ZERO_BYTES = 65536;

@@ -1,0 +1,658 @@
+"""Template matching on the MI355X: ``VQNNFTemplateMatcher`` (arXiv 2306.15010) behind the reference's matcher surface.
+
+Mirrors marie/components/template_matching/{model,base,vqnnf_template_matching,composite_template_maching}.py and the
+matching core under vqnnf/matching/.  The reference slices a page into windows and loops in Python over (slice, template),
+materialising 128 x H x W fp32 one-hots and integral images for each.  Here the page is uploaded once, the slices are windows
+of it, and the nearest-code assignment, the Gauss-Haar heat map and the peak rounds run over the whole (slice x template)
+grid in a handful of launches (csrc/vqnnf.hip); only the peaks come back.  Template-side state (k-means codebook, labels,
+filter responses) is built once per template and cached under the reference's key ``key_{x}_{y}_{w}_{h}``.
+
+Built: the model-free ``num_features == 27`` colour features of ``PixelFeatureExtractor`` (the paper's colour variant).
+Not built: the EfficientNet hyper-column features and ``pca_lowrank`` (``n_feature != 27`` / ``pca_dims`` raise), the CLIP
+snippet embedding (``embeddings_processor`` is any callable; with None the embedding similarity is taken equal to the
+feature similarity), ``resize_image_progressive`` (``downscale_factor != 1`` raises), ``MetaTemplateMatcher`` and
+``DeepDimTemplateMatcher``, and the reference's /tmp/dim writes, prints and visualisations.  ``slice_image`` and
+``GreedyNMMPostprocess`` restate sahi's, which is not installed here: their parity with sahi is not pinned by a golden.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import logging
+import os
+from abc import ABC, abstractmethod
+from dataclasses import dataclass
+from typing import Any, Callable, List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+
+from ._lib import Context, MarieHipError, VqFilters, check
+from .dit_box_processor import resize_image
+
+logger = logging.getLogger(__name__)
+
+N_FEATURES = 27
+N_CODE = 128
+MAX_FILTERS = 6
+CLIP_SIZE = (224, 224)
+
+
+@dataclass
+class TemplateMatchResult:
+    """marie/components/template_matching/model.py"""
+    bbox: Any
+    label: str
+    score: float
+    similarity: float
+    frame_index: Optional[int] = 0
+
+
+# ---------------------------------------------------------------------------------------------------- slicing and NMM
+def slice_image(image_height: int, image_width: int, slice_height: int, slice_width: int,
+                overlap_height_ratio: float = 0.2, overlap_width_ratio: float = 0.2) -> List[Tuple[int, int, int, int]]:
+    """The windows of sahi.slicing.slice_image(auto_slice_resolution=False) as (x, y, w, h): a step of the slice less an
+    overlap of int(ratio * size) pixels; a slice that would overrun the page is moved back inside it."""
+    y_overlap, x_overlap = int(overlap_height_ratio * slice_height), int(overlap_width_ratio * slice_width)
+    if slice_height <= y_overlap or slice_width <= x_overlap:
+        raise ValueError("the overlap must be smaller than the slice")
+    out = []
+    y_max = y_min = 0
+    while y_max < image_height:
+        x_min = x_max = 0
+        y_max = y_min + slice_height
+        while x_max < image_width:
+            x_max = x_min + slice_width
+            if y_max > image_height or x_max > image_width:
+                xm, ym = min(image_width, x_max), min(image_height, y_max)
+                x0, y0 = max(0, xm - slice_width), max(0, ym - slice_height)
+                out.append((x0, y0, xm - x0, ym - y0))
+            else:
+                out.append((x_min, y_min, slice_width, slice_height))
+            x_min = x_max - x_overlap
+        y_min = y_max - y_overlap
+    return out
+
+
+@dataclass
+class ObjectPrediction:
+    """what GreedyNMMPostprocess works on: an xyxy box, a score and a category"""
+    bbox: List[int]
+    score: float
+    category: str
+
+    def to_xywh(self):
+        return [self.bbox[0], self.bbox[1], self.bbox[2] - self.bbox[0], self.bbox[3] - self.bbox[1]]
+
+
+def box_ios(a: Sequence[float], b: Sequence[float]) -> float:
+    """intersection over the smaller area (xyxy)"""
+    iw, ih = min(a[2], b[2]) - max(a[0], b[0]), min(a[3], b[3]) - max(a[1], b[1])
+    inter = max(iw, 0) * max(ih, 0)
+    smaller = min((a[2] - a[0]) * (a[3] - a[1]), (b[2] - b[0]) * (b[3] - b[1]))
+    return inter / smaller if smaller > 0 else 0.0
+
+
+def box_iou(a: Sequence[float], b: Sequence[float]) -> float:
+    iw, ih = min(a[2], b[2]) - max(a[0], b[0]), min(a[3], b[3]) - max(a[1], b[1])
+    inter = max(iw, 0) * max(ih, 0)
+    union = (a[2] - a[0]) * (a[3] - a[1]) + (b[2] - b[0]) * (b[3] - b[1]) - inter
+    return inter / union if union > 0 else 0.0
+
+
+class GreedyNMMPostprocess:
+    """Greedy non-maximum merging: per category (unless class_agnostic), highest score first, a kept prediction absorbs
+    every remaining one whose match metric with it exceeds ``match_threshold``; a merged pair takes the union box, the
+    higher score and that one's category."""
+
+    def __init__(self, match_threshold: float = 0.5, match_metric: str = "IOS", class_agnostic: bool = False):
+        if match_metric not in ("IOS", "IOU"):
+            raise ValueError(f"match_metric should be IOS or IOU, got {match_metric}")
+        self.match_threshold, self.match_metric, self.class_agnostic = match_threshold, match_metric, class_agnostic
+
+    def _metric(self, a, b) -> float:
+        return box_ios(a, b) if self.match_metric == "IOS" else box_iou(a, b)
+
+    def __call__(self, predictions: List[ObjectPrediction]) -> List[ObjectPrediction]:
+        groups = {}
+        for i, p in enumerate(predictions):
+            groups.setdefault(None if self.class_agnostic else p.category, []).append(i)
+        out = []
+        for members in groups.values():
+            order = sorted(members, key=lambda i: predictions[i].score, reverse=True)     # stable: ties keep input order
+            while order:
+                keep, rest = order[0], order[1:]
+                matched = [i for i in rest if self._metric(predictions[keep].bbox, predictions[i].bbox) >= self.match_threshold]
+                order = [i for i in rest if i not in matched]
+                cur = predictions[keep]
+                for i in matched:
+                    other = predictions[i]
+                    if self._metric(cur.bbox, other.bbox) > self.match_threshold:
+                        best = cur if cur.score >= other.score else other
+                        cur = ObjectPrediction([min(cur.bbox[0], other.bbox[0]), min(cur.bbox[1], other.bbox[1]),
+                                                max(cur.bbox[2], other.bbox[2]), max(cur.bbox[3], other.bbox[3])],
+                                               best.score, best.category)
+                out.append(cur)
+        return out
+
+
+# ---------------------------------------------------------------------------------------------------- base
+class BaseTemplateMatcher(ABC):
+    """marie/components/template_matching/base.py"""
+
+    DEFAULT_OVERLAP_HEIGHT_RATIO = 0.2
+    DEFAULT_OVERLAP_WIDTH_RATIO = 0.2
+
+    def __init__(self, slicing_enabled: bool = True, **kwargs) -> None:
+        self.slicing_enabled = slicing_enabled
+
+    @abstractmethod
+    def predict(self, frame: np.ndarray, template_frames: List[np.ndarray], template_boxes: List[Sequence[int]],
+                template_labels: List[str], template_texts: Optional[List[str]] = None, score_threshold: float = 0.9,
+                scoring_strategy: str = "weighted", max_objects: int = 1, batch_size: int = 1, words=None, word_boxes=None,
+                word_lines=None) -> List[TemplateMatchResult]:
+        """Every location of every template in ``frame`` above the threshold, not filtered for overlap."""
+
+    def predict_windows(self, frame: np.ndarray, windows: List[Tuple[int, int, int, int]], template_frames, template_boxes,
+                        template_labels, template_texts, score_threshold, scoring_strategy, max_objects, words=None,
+                        word_boxes=None, word_lines=None) -> List[List[TemplateMatchResult]]:
+        """``predict`` on every window (x, y, w, h) of ``frame``, boxes relative to the window (base.py:238-253).  A matcher
+        that batches over the windows overrides this."""
+        return [self.predict(frame[y:y + h, x:x + w], template_frames, template_boxes, template_labels, template_texts,
+                             score_threshold, scoring_strategy, max_objects, words=words, word_boxes=word_boxes,
+                             word_lines=word_lines) for x, y, w, h in windows]
+
+    def run(self, frames: List[np.ndarray], template_frames: List[np.ndarray], template_boxes: List[Sequence[int]],
+            template_labels: List[str], template_texts: Optional[List[str]] = None, metadata=None,
+            score_threshold: float = 0.90, scoring_strategy: str = "weighted", max_overlap: float = 0.5,
+            max_objects: int = 1, window_size: Tuple[int, int] = (384, 128), regions=None, downscale_factor: float = 1.0,
+            batch_size: Optional[int] = None) -> List[TemplateMatchResult]:
+        """base.py:70-377: slice every frame into windows of ``window_size`` (h, w), match every window, shift the boxes to
+        the page, keep scores above the threshold, merge overlapping boxes per label."""
+        if not (0 <= score_threshold <= 1):
+            raise ValueError("Score threshold should be between 0 and 1")
+        if not (0 <= max_overlap <= 1):
+            raise ValueError("Max overlap should be between 0 and 1")
+        if not max_objects > 0:
+            raise ValueError("Max object should be greater than 0")
+        if downscale_factor > 1 or downscale_factor < 0:
+            raise ValueError("Downscale factor should be between 0 and 1")
+        if batch_size is not None and not batch_size > 0:
+            raise ValueError("Batch size should be either None or greater than 0")
+        if regions is None:
+            regions = [(0, 0, image.shape[1], image.shape[0]) for image in frames]
+        if len(frames) != len(regions):
+            raise ValueError("The length of the regions list should be the same as the length of the frames list.")
+        if downscale_factor != 1:
+            raise NotImplementedError("downscale_factor != 1 needs resize_image_progressive, which is not built")
+        results = []
+        postprocess = self.setup_postprocess()
+        for template_frame in template_frames:
+            if template_frame.shape[0] != window_size[0] or template_frame.shape[1] != window_size[1]:
+                raise ValueError("Template frame size does not match window size, please resize the template frames to "
+                                 "match the window size")
+        for frame_idx, frame in enumerate(frames):
+            if frame.ndim != 3:
+                raise ValueError(f"expected HxWx3 frames, got {frame.shape}")
+            if self.slicing_enabled:
+                windows = slice_image(frame.shape[0], frame.shape[1], window_size[0], window_size[1],
+                                      self.DEFAULT_OVERLAP_HEIGHT_RATIO, self.DEFAULT_OVERLAP_WIDTH_RATIO)
+            else:
+                windows = [(0, 0, frame.shape[1], frame.shape[0])]
+            per_window = self.predict_windows(frame, windows, template_frames, template_boxes, template_labels,
+                                              template_texts, score_threshold, scoring_strategy, max_objects)
+            bboxes, labels, scores, snippets = [], [], [], []
+            for (ox, oy, _, _), predictions in zip(windows, per_window):
+                for p in predictions:
+                    bboxes.append([p.bbox[0] + ox, p.bbox[1] + oy, p.bbox[2], p.bbox[3]])
+                    labels.append(p.label)
+                    scores.append(p.score)
+                    snippets.append(None)
+            bboxes, labels, scores = self.filter_scores(bboxes, labels, scores, snippets, score_threshold)
+            order = sorted(range(len(scores)), key=lambda i: scores[i], reverse=True)
+            predictions = [ObjectPrediction([bboxes[i][0], bboxes[i][1], bboxes[i][0] + bboxes[i][2],
+                                             bboxes[i][1] + bboxes[i][3]], scores[i], labels[i]) for i in order]
+            if postprocess is not None:
+                predictions = postprocess(predictions)
+            by_label = {}
+            for p in predictions:
+                by_label.setdefault(p.category, []).append(p)
+            for label, members in by_label.items():
+                for p in members:
+                    results.append(TemplateMatchResult(bbox=p.to_xywh(), label=label, score=p.score, similarity=p.score,
+                                                       frame_index=frame_idx))
+        return results
+
+    def setup_postprocess(self):
+        return GreedyNMMPostprocess(match_threshold=0.5, match_metric="IOS", class_agnostic=False)
+
+    def filter_scores(self, bboxes, labels, scores, snippets, score_threshold) -> Tuple[list, list, list]:
+        """drop what does not score strictly above the threshold"""
+        assert len(bboxes) == len(labels) == len(scores) == len(snippets)
+        keep = [i for i, s in enumerate(scores) if s > score_threshold]
+        return [bboxes[i] for i in keep], [labels[i] for i in keep], [scores[i] for i in keep]
+
+    @staticmethod
+    def extract_windows(image: np.ndarray, template_bboxes: List[Sequence[int]], window_size: Tuple[int, int],
+                        allow_padding: bool = False) -> Tuple[List[np.ndarray], List[Tuple[int, int, int, int]]]:
+        """base.py:551-615: a window of ``window_size`` (h, w) centred on every box (x, y, w, h), moved back inside the
+        image, and the box relative to its window; a smaller image is padded white when ``allow_padding``."""
+        windows, bboxes = [], []
+        img_h, img_w = image.shape[:2]
+        desired_h, desired_w = window_size
+        if img_h < desired_h or img_w < desired_w:
+            if not allow_padding:
+                raise ValueError(f"Image size should be greater than the window size, expected {window_size} but got "
+                                 f"{image.shape[:2]}")
+            padded = np.full((max(img_h, desired_h), max(img_w, desired_w), image.shape[2]), 255, image.dtype)
+            padded[:img_h, :img_w] = image
+            image = padded
+            img_h, img_w = image.shape[:2]
+        for x_, y_, w_, h_ in template_bboxes:
+            center_x, center_y = x_ + w_ // 2, y_ + h_ // 2
+            x, y = max(0, center_x - desired_w // 2), max(0, center_y - desired_h // 2)
+            if x + desired_w > img_w:
+                x = img_w - desired_w
+            if y + desired_h > img_h:
+                y = img_h - desired_h
+            window = image[y:y + desired_h, x:x + desired_w, :]
+            if window.shape[0] != desired_h or window.shape[1] != desired_w:
+                raise Exception("Template frame size does not match window size, please resize the template frames to "
+                                "match the window size")
+            windows.append(window)
+            bboxes.append((center_x - x - w_ // 2, center_y - y - h_ // 2, w_, h_))
+        return windows, bboxes
+
+
+# ---------------------------------------------------------------------------------------------------- VQ-NNF, host side
+def odd(f) -> int:
+    return int(np.ceil(f)) // 2 * 2 + 1
+
+
+def gauss_box_3x3(sigma: float = 2.0) -> np.ndarray:
+    """get_gaussian_box_filter((3, 3), sigma) of gauss_haar_filters.py:58-76: a centred impulse through a Gaussian
+    (scipy.ndimage.gaussian_filter, mode 'reflect', truncate 4.0), as fp32."""
+    radius = int(4.0 * sigma + 0.5)
+    k = np.arange(-radius, radius + 1, dtype=np.float64)
+    wts = np.exp(-0.5 / (sigma * sigma) * k ** 2)
+    wts /= wts.sum()
+    line = np.pad(np.array([0.0, 1.0, 0.0]), radius, mode="symmetric")
+    g = np.array([np.dot(wts, line[i:i + 2 * radius + 1]) for i in range(3)])
+    return np.outer(g, g).astype(np.float32)
+
+
+def integral_taps(box: np.ndarray) -> np.ndarray:
+    """convert_box_to_integral (utils.py:12-18) in fp32, over the taps' count (gauss_haar_filters.py:205-207)"""
+    mult = np.array([[1, -1], [-1, 1]], np.float32)
+    out = np.zeros((box.shape[0] + 1, box.shape[1] + 1), np.float32)
+    for i in range(box.shape[0]):
+        for j in range(box.shape[1]):
+            out[i:i + 2, j:j + 2] += np.float32(box[i, j]) * mult
+    return out / np.float32(out.size)
+
+
+def filter_bank(t_rows: int, t_cols: int, n_scales: int = 3):
+    """GaussHaarFilters(kernel_size=3, sigma=2, filters=1, n_scales=3) for a template of t_rows x t_cols: ``haar_1x`` is
+    listed twice, so two equal filters per scale -> taps (F, 4, 4) fp32, dilation (F, 2), kernel (F, 2), weight (F,)."""
+    taps1 = integral_taps(gauss_box_3x3(2.0))
+    taps, dil, ker, wgt = [], [], [], []
+    for scale in np.linspace(1, 1 / n_scales, n_scales):
+        d = (int(t_rows * scale) // 3, int(t_cols * scale) // 3)
+        if d[0] < 1 or d[1] < 1:
+            raise ValueError(f"a {t_rows} x {t_cols} template is too small: a side below 9 gives a filter dilation of 0")
+        for _ in range(2):
+            taps.append(taps1)
+            dil.append(d)
+            ker.append((3 * d[0] + 1, 3 * d[1] + 1))
+            wgt.append(float(scale))
+    return np.stack(taps), np.asarray(dil, np.int64), np.asarray(ker, np.int64), np.asarray(wgt, np.float64)
+
+
+def template_responses(labels: np.ndarray, n_codes: int, taps: np.ndarray, dil: np.ndarray, ker: np.ndarray) -> np.ndarray:
+    """GaussHaarFilters.get_template_features: the filters on the double cumulative sum of the one-hot of ``labels``
+    (t_rows, t_cols), reflect-padded where a kernel exceeds the template, at the (1, 1) centre crop -> fp32 (F, K)."""
+    onehot = (np.asarray(labels)[None, :, :] == np.arange(n_codes)[:, None, None]).astype(np.float64)
+    integral = onehot.cumsum(axis=1).cumsum(axis=2)
+    out = np.zeros((len(taps), n_codes), np.float64)
+    for f in range(len(taps)):
+        px = max(0, int(np.ceil((ker[f][0] - integral.shape[1]) / 2)))
+        py = max(0, int(np.ceil((ker[f][1] - integral.shape[2]) / 2)))
+        pad = np.pad(integral, ((0, 0), (px, px), (py, py)), mode="reflect")
+        dx, dy = int(dil[f][0]), int(dil[f][1])
+        hv, wv = pad.shape[1] - 3 * dx, pad.shape[2] - 3 * dy
+        x1, y1 = ((hv - 1) // 2 if hv > 1 else 0), ((wv - 1) // 2 if wv > 1 else 0)
+        for a in range(4):
+            for b in range(4):
+                out[f] += float(taps[f][a, b]) * pad[:, x1 + a * dx, y1 + b * dy]
+    return out.astype(np.float32)
+
+
+def peak_box(row: int, col: int, box_w: int, box_h: int) -> Tuple[int, int, int, int]:
+    """vqnnf_template_matching.py:184-202 with its swapped names folded: the box (x, y, w, h) of a heat-map peak"""
+    return (int(col + 1 - (odd(box_w) - 1) / 2), int(row + 1 - (odd(box_h) - 1) / 2), int(box_w), int(box_h))
+
+
+def make_filters(taps, dil, wgt) -> VqFilters:
+    fb = VqFilters()
+    fb.n = len(taps)
+    for f in range(len(taps)):
+        for k, v in enumerate(np.asarray(taps[f], np.float32).reshape(-1)):
+            fb.taps[f][k] = float(v)
+        fb.dil[f][0], fb.dil[f][1] = int(dil[f][0]), int(dil[f][1])
+        fb.weight[f] = float(wgt[f])
+    return fb
+
+
+def _u8(a: np.ndarray) -> np.ndarray:
+    return np.ascontiguousarray(a, np.uint8)
+
+
+def _ptr(a: np.ndarray):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+# ---- the kernels on host arrays (what tests/test_vqnnf_gpu.py drives)
+def vq_assign_host(ctx: Context, image: np.ndarray, rect: Sequence[int], codebook: np.ndarray) -> np.ndarray:
+    image, cb = _u8(image), np.ascontiguousarray(codebook, np.float32)
+    r = np.asarray(rect, np.int32)
+    out = np.empty((int(r[3]), int(r[2])), np.uint8)
+    check(ctx.h, ctx.lib.mhip_vq_assign_host(ctx.h, _ptr(image), image.shape[0], image.shape[1], _ptr(r), _ptr(cb),
+                                             cb.shape[0], _ptr(out)), "mhip_vq_assign_host")
+    return out
+
+
+def vq_kmeans_step_host(ctx: Context, image: np.ndarray, rect: Sequence[int], centroids: np.ndarray):
+    """-> (labels uint8 (h*w,), new centroids fp32 (K, 27), members int32 (K,), error)"""
+    image, cin = _u8(image), np.ascontiguousarray(centroids, np.float32)
+    r = np.asarray(rect, np.int32)
+    labels = np.empty(int(r[2]) * int(r[3]), np.uint8)
+    cout, counts, err = np.empty_like(cin), np.empty(cin.shape[0], np.int32), C.c_double()
+    check(ctx.h, ctx.lib.mhip_vq_kmeans_step_host(ctx.h, _ptr(image), image.shape[0], image.shape[1], _ptr(r), _ptr(cin),
+                                                  cin.shape[0], _ptr(labels), _ptr(cout), _ptr(counts), C.byref(err)),
+          "mhip_vq_kmeans_step_host")
+    return labels, cout, counts, err.value
+
+
+def vq_heatmap_host(ctx: Context, codes: np.ndarray, n_codes: int, responses: np.ndarray, taps, dil, wgt):
+    """-> (heat fp32 (H, W), each filter's minimum fp64 (F,))"""
+    codes, resp = _u8(codes), np.ascontiguousarray(responses, np.float32)
+    fb = make_filters(taps, dil, wgt)
+    heat, mins = np.empty(codes.shape, np.float32), np.empty(len(taps), np.float64)
+    check(ctx.h, ctx.lib.mhip_vq_heatmap_host(ctx.h, _ptr(codes), codes.shape[0], codes.shape[1], int(n_codes), _ptr(resp),
+                                              C.byref(fb), _ptr(heat), _ptr(mins)), "mhip_vq_heatmap_host")
+    return heat, mins
+
+
+def vq_peaks_host(ctx: Context, heat: np.ndarray, box_wh: Sequence[Sequence[int]], max_objects: int):
+    """heat (n, H, W) -> (peaks fp32 (n, max_objects, 3) = row, col, value; the maps after the suppressions)"""
+    heat = np.array(heat, np.float32, order="C", copy=True)
+    wh = np.ascontiguousarray(box_wh, np.int32)
+    peaks = np.empty((heat.shape[0], int(max_objects), 3), np.float32)
+    check(ctx.h, ctx.lib.mhip_vq_peaks_host(ctx.h, _ptr(heat), heat.shape[0], heat.shape[1], heat.shape[2], _ptr(wh),
+                                            int(max_objects), _ptr(peaks)), "mhip_vq_peaks_host")
+    return peaks, heat
+
+
+def clip_cosine_host(ctx: Context, a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """cosine similarity of the colour features of clip pairs, uint8 (n, h, w, 3) each -> fp32 (n,)"""
+    a, b = _u8(a), _u8(b)
+    if a.shape != b.shape or a.ndim != 4 or a.shape[3] != 3:
+        raise ValueError(f"clip pairs of one (n, h, w, 3) shape expected, got {a.shape} and {b.shape}")
+    out = np.empty(a.shape[0], np.float32)
+    check(ctx.h, ctx.lib.mhip_clip_cosine_host(ctx.h, _ptr(a), _ptr(b), a.shape[0], a.shape[1], a.shape[2], _ptr(out)),
+          "mhip_clip_cosine_host")
+    return out
+
+
+class VQTemplate:
+    """``mhip_vq_template``: codebook, labels and filter responses of one template (frame + box) on a :class:`Context`."""
+
+    def __init__(self, ctx: Context, frame, box: Sequence[int], init_idx: np.ndarray):
+        """``frame``: an HxWx3 uint8 array, or a device tensor of that shape"""
+        x, y, w, h = (int(v) for v in box)
+        self.box = (x, y, w, h)
+        taps, dil, ker, wgt = filter_bank(h, w)                    # ValueError for a side below 9, before any launch
+        self.ctx, self.lib = ctx, ctx.lib
+        on_device = hasattr(frame, "data_ptr")
+        if not on_device:
+            frame = _u8(frame)
+        fh, fw = int(frame.shape[0]), int(frame.shape[1])
+        idx = np.ascontiguousarray(init_idx, np.int32)
+        b = np.asarray(self.box, np.int32)
+        handle = C.c_void_p()
+        check(ctx.h, self.lib.mhip_vq_template_create(ctx.h, C.c_void_p(frame.data_ptr()) if on_device else _ptr(frame),
+                                                      1 if on_device else 0, fh, fw, _ptr(b), _ptr(idx), len(idx),
+                                                      C.byref(handle)), "mhip_vq_template_create")
+        self.h = handle
+        ctx.adopt(self)
+        k, it = C.c_int(), C.c_int()
+        self.lib.mhip_vq_template_state(self.h, C.byref(k), C.byref(it), None, None)
+        self.n_codes, self.iterations = k.value, it.value
+        self.labels = np.empty(w * h, np.uint8)
+        self.codebook = np.empty((self.n_codes, N_FEATURES), np.float32)
+        self.lib.mhip_vq_template_state(self.h, None, None, _ptr(self.labels), _ptr(self.codebook))
+        self.taps, self.dil, self.ker, self.wgt = taps, dil, ker, wgt
+        self.responses = template_responses(self.labels.reshape(h, w), self.n_codes, taps, dil, ker)
+        fb = make_filters(taps, dil, wgt)
+        check(ctx.h, self.lib.mhip_vq_template_set_filters(self.h, _ptr(self.responses), C.byref(fb)),
+              "mhip_vq_template_set_filters")
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h.value:
+            self.lib.mhip_vq_template_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def n_code_of(w: int, h: int, n_code: int = N_CODE) -> int:
+    """template_matching.py:46-48"""
+    return n_code if w * h > n_code else w * h
+
+
+def draw_init_indices(seed: int, box: Sequence[int]) -> np.ndarray:
+    """the rows init_methods._kpoints draws (with replacement), from a generator seeded by (seed, box)"""
+    x, y, w, h = (int(v) for v in box)
+    rng = np.random.default_rng([int(seed), x, y, w, h])
+    return rng.integers(0, w * h, size=n_code_of(w, h)).astype(np.int32)
+
+
+# ---------------------------------------------------------------------------------------------------- the matcher
+class VQNNFTemplateMatcher(BaseTemplateMatcher):
+    """Drop-in for marie/components/template_matching/vqnnf_template_matching.py on the colour features."""
+
+    def __init__(self, model_name_or_path: Union[str, os.PathLike] = "", model_version: Optional[str] = None,
+                 use_gpu: bool = True, labels: Optional[List[str]] = None, batch_size: int = 16, use_auth_token=None,
+                 devices: Optional[List[Any]] = None, show_error: Optional[Union[str, bool]] = True, *,
+                 n_feature: int = N_FEATURES, pca_dims: Optional[int] = None,
+                 embeddings_processor: Optional[Callable[[np.ndarray], np.ndarray]] = None, seed: int = 0,
+                 ctx: Optional[Context] = None, **kwargs):
+        super().__init__(True, **kwargs)
+        if not use_gpu:
+            raise MarieHipError("VQNNFTemplateMatcher here is the MI355X path; use_gpu=False has no implementation")
+        if n_feature != N_FEATURES:
+            raise NotImplementedError("n_feature != 27: the EfficientNet hyper-column features are not built")
+        if pca_dims is not None:
+            raise NotImplementedError("pca_dims: the pca_lowrank projection of the features is not built")
+        logger.info("VQNNF matcher model : %s", model_name_or_path)
+        self.show_error, self.batch_size, self.labels = show_error, batch_size, labels
+        self.n_feature, self.n_code, self.seed = n_feature, N_CODE, int(seed)
+        self.embeddings_processor = embeddings_processor
+        self.ctx = ctx or Context(self._device_id(devices))
+        self.cached_features = {}            # key_{x}_{y}_{w}_{h} -> VQTemplate
+        self.cached_embeddings_clips = {}
+        self.template_builds = 0             # k-means runs so far
+
+    @staticmethod
+    def _device_id(devices) -> int:
+        if not devices:
+            return 0
+        d = devices[0]
+        idx = getattr(d, "index", None)
+        if idx is None and isinstance(d, str) and ":" in d:
+            idx = int(d.split(":")[1])
+        return int(idx or 0)
+
+    def close(self):
+        for t in self.cached_features.values():
+            t.close()
+        self.cached_features = {}
+
+    # -- template state ----------------------------------------------------------------------------------------------
+    def template_state(self, template_frame: np.ndarray, template_box: Sequence[int]) -> VQTemplate:
+        x, y, w, h = (int(t) for t in template_box)
+        key = f"key_{x}_{y}_{w}_{h}"
+        if key not in self.cached_features:
+            box = (max(x, 0), max(y, 0), w, h)
+            self.cached_features[key] = VQTemplate(self.ctx, template_frame, box, draw_init_indices(self.seed, box))
+            self.template_builds += 1
+        return self.cached_features[key]
+
+    # -- device matching ---------------------------------------------------------------------------------------------
+    def match_windows(self, frame: np.ndarray, windows: Sequence[Sequence[int]], template_frames, template_boxes,
+                      max_objects: int) -> np.ndarray:
+        """Every window (x, y, w, h; one size) of ``frame`` against every template in one batched call ->
+        peaks fp32 (n_windows, n_templates, max_objects, 3) = row, col, value of the heat-map maxima."""
+        import torch
+
+        if frame.ndim != 3 or frame.shape[2] != 3:
+            raise ValueError(f"expected an HxWx3 frame, got {frame.shape}")
+        sizes = {(int(w[2]), int(w[3])) for w in windows}
+        if len(sizes) != 1:
+            raise ValueError(f"the windows of one call share one size, got {sorted(sizes)}")
+        win_w, win_h = sizes.pop()
+        states = [self.template_state(f, b) for f, b in zip(template_frames, template_boxes)]
+        dev_name = f"cuda:{self.ctx.device_id}"
+        self.ctx.set_stream(torch.cuda.current_stream(dev_name).cuda_stream)
+        page = torch.from_numpy(_u8(frame)).to(dev_name)
+        xy = np.ascontiguousarray([[int(w[0]), int(w[1])] for w in windows], np.int32)
+        handles = (C.c_void_p * len(states))(*[s.h.value for s in states])
+        peaks = np.empty((len(windows), len(states), int(max_objects), 3), np.float32)
+        check(self.ctx.h, self.ctx.lib.mhip_vq_match(self.ctx.h, C.c_void_p(page.data_ptr()), frame.shape[0], frame.shape[1],
+                                                     frame.shape[1] * 3, _ptr(xy), len(windows), win_h, win_w, handles,
+                                                     len(states), int(max_objects), _ptr(peaks)), "mhip_vq_match")
+        return peaks
+
+    # -- scoring -----------------------------------------------------------------------------------------------------
+    def _clip(self, snippet: np.ndarray) -> np.ndarray:
+        return _u8(resize_image(_u8(snippet), CLIP_SIZE, ctx=self.ctx)[0])
+
+    def get_embedding_feature(self, clip: np.ndarray) -> np.ndarray:
+        key = clip.tobytes()
+        if key not in self.cached_embeddings_clips:
+            if clip.shape[0] != CLIP_SIZE[0] or clip.shape[1] != CLIP_SIZE[1]:
+                raise ValueError("Image must be 224x224")
+            self.cached_embeddings_clips[key] = np.asarray(self.embeddings_processor(clip), np.float64).reshape(-1)
+        return self.cached_embeddings_clips[key]
+
+    def score_pairs(self, pairs: Sequence[Tuple[np.ndarray, np.ndarray]], scoring_strategy: str) -> List[float]:
+        """``score`` of (template snippet, query snippet) pairs with one cosine launch for all of them"""
+        if not pairs:
+            return []
+        t_clips = np.stack([self._clip(t) for t, _ in pairs])
+        q_clips = np.stack([self._clip(q) for _, q in pairs])
+        feature_sims = clip_cosine_host(self.ctx, t_clips, q_clips)
+        out = []
+        for k, feature_sim in enumerate(feature_sims):
+            feature_sim = float(feature_sim)
+            if self.embeddings_processor is None:
+                embedding_sim = feature_sim
+            else:
+                a, b = self.get_embedding_feature(t_clips[k]), self.get_embedding_feature(q_clips[k])
+                embedding_sim = float(np.dot(a, b) / (max(np.linalg.norm(a), 1e-8) * max(np.linalg.norm(b), 1e-8)))
+            if scoring_strategy == "weighted":
+                sim_val = feature_sim * 0.05 + embedding_sim * 0.95
+            elif scoring_strategy == "max":
+                sim_val = max(feature_sim, embedding_sim)
+            else:
+                sim_val = (feature_sim + embedding_sim) / 2
+            out.append(max(0, min(1, sim_val)))
+        return out
+
+    def score(self, template_snippet: np.ndarray, query_pred_snippet: np.ndarray, scoring_strategy: str) -> float:
+        """vqnnf_template_matching.py:310-362"""
+        return self.score_pairs([(template_snippet, query_pred_snippet)], scoring_strategy)[0]
+
+    # -- predictions -------------------------------------------------------------------------------------------------
+    def predict_windows(self, frame, windows, template_frames, template_boxes, template_labels, template_texts=None,
+                        score_threshold: float = 0.9, scoring_strategy: str = "weighted", max_objects: int = 1, words=None,
+                        word_boxes=None, word_lines=None) -> List[List[TemplateMatchResult]]:
+        peaks = self.match_windows(frame, windows, template_frames, template_boxes, max_objects)
+        candidates, pairs = [], []            # (window, template, k, box) of every peak with a snippet, in the loop's order
+        for wi, (wx, wy, ww, wh) in enumerate(windows):
+            patch = frame[wy:wy + wh, wx:wx + ww]
+            for ti, (tframe, tbox) in enumerate(zip(template_frames, template_boxes)):
+                tx, ty = int(max(tbox[0], 0)), int(max(tbox[1], 0))
+                tw, th = int(tbox[2]), int(tbox[3])
+                template_snippet = tframe[ty:min(ty + th, tframe.shape[0]), tx:min(tx + tw, tframe.shape[1])]
+                for k in range(max_objects):
+                    box = peak_box(int(peaks[wi, ti, k, 0]), int(peaks[wi, ti, k, 1]), tw, th)
+                    snippet = patch[box[1]:box[1] + box[3], box[0]:box[0] + box[2]]
+                    if template_snippet.shape[0] == 0 or template_snippet.shape[1] == 0:
+                        logger.warning("Template snippet is empty")
+                        continue
+                    if snippet.shape[0] == 0 or snippet.shape[1] == 0:
+                        logger.warning("Query snippet is empty")
+                        continue
+                    candidates.append((wi, ti, k, box))
+                    pairs.append((template_snippet, snippet))
+        scores = self.score_pairs(pairs, scoring_strategy)
+        out: List[List[TemplateMatchResult]] = [[] for _ in windows]
+        stopped = set()                       # the reference's break at the first candidate under the threshold
+        for (wi, ti, k, box), sim_val in zip(candidates, scores):
+            if (wi, ti) in stopped:
+                continue
+            if sim_val < score_threshold:
+                stopped.add((wi, ti))
+                continue
+            out[wi].append(TemplateMatchResult(bbox=box, label=template_labels[ti], score=sim_val, similarity=sim_val,
+                                               frame_index=-1))
+        return out
+
+    def predict(self, frame, template_frames, template_boxes, template_labels, template_texts=None,
+                score_threshold: float = 0.9, scoring_strategy: str = "weighted", max_objects: int = 1, batch_size: int = 1,
+                words=None, word_boxes=None, word_lines=None) -> List[TemplateMatchResult]:
+        """vqnnf_template_matching.py:100-308 on one frame (the whole frame is the window)"""
+        return self.predict_windows(frame, [(0, 0, frame.shape[1], frame.shape[0])], template_frames, template_boxes,
+                                    template_labels, template_texts, score_threshold, scoring_strategy, max_objects)[0]
+
+
+class CompositeTemplateMatcher(BaseTemplateMatcher):
+    """marie/components/template_matching/composite_template_maching.py: several matchers in turn, merged per page."""
+
+    def __init__(self, matchers: List[BaseTemplateMatcher], break_on_match: bool = False,
+                 show_error: Optional[Union[str, bool]] = True, **kwargs):
+        super().__init__(False, **kwargs)
+        self.show_error, self.matchers, self.break_on_match = show_error, matchers, break_on_match
+
+    def predict(self, *args, **kwargs):
+        raise NotImplementedError("This method is not implemented in CompositeTemplateMatcher")
+
+    def run(self, frames, template_frames, template_boxes, template_labels, template_texts=None, metadata=None,
+            score_threshold: float = 0.8, scoring_strategy: str = "weighted", max_overlap: float = 0.5, max_objects: int = 1,
+            window_size: Tuple[int, int] = (384, 128), regions=None, downscale_factor: float = 1.0,
+            batch_size: Optional[int] = None) -> List[TemplateMatchResult]:
+        results = []
+        postprocess = self.setup_postprocess()
+        for matcher in self.matchers:
+            result = matcher.run(frames=frames, template_frames=template_frames, template_boxes=template_boxes,
+                                 template_labels=template_labels, template_texts=template_texts, metadata=metadata,
+                                 score_threshold=score_threshold, scoring_strategy=scoring_strategy, max_overlap=max_overlap,
+                                 max_objects=max_objects, window_size=window_size, regions=regions,
+                                 downscale_factor=downscale_factor, batch_size=batch_size)
+            results.extend(result)
+            if self.break_on_match and result:
+                break
+        by_page = {}
+        for r in results:
+            by_page.setdefault(r.frame_index, []).append(r)
+        converted = []
+        for page_index, members in by_page.items():
+            predictions = [ObjectPrediction([r.bbox[0], r.bbox[1], r.bbox[0] + r.bbox[2], r.bbox[1] + r.bbox[3]], r.score,
+                                            r.label) for r in members]
+            for p in postprocess(predictions):
+                converted.append(TemplateMatchResult(bbox=p.to_xywh(), label=p.category, score=p.score, similarity=p.score,
+                                                     frame_index=page_index))
+        return converted
