@@ -668,6 +668,56 @@ int mhip_vq_peaks_host(mhip_ctx* ctx, float* heat, int n, int H, int W, const in
 /* cosine similarity of the colour features of n pairs of clips uint8 [n][h][w][3] -> fp32 [n]                                 */
 int mhip_clip_cosine_host(mhip_ctx* ctx, const uint8_t* a, const uint8_t* b, int n, int h, int w, float* out);
 
+/* ---- CLIP vision tower: image embeddings of the matcher's snippet score (csrc/clip_api.hip, clip_ops.hip) --------------- */
+/* replaces: CLIP.encode_image behind OpenAIEmbeddings.get_single_image_embedding, marie/embeddings/openai/
+ * openai_embeddings.py:146-157 (clip/model.py VisionTransformer), CLIPModel.get_image_features behind
+ * OpenAITransformerEmbeddings (openai_trans_embeddings.py:131-145), and the nn.CosineSimilarity of two embeddings in
+ * VQNNFTemplateMatcher.score, marie/components/template_matching/vqnnf_template_matching.py:335-347.
+ * "clipvis", not "clip": mhip_clip_cosine_host above is the colour-feature cosine of snippet clips.
+ * Clips are uint8 [image_size][image_size][3], already resized and cropped; normalisation (pixel / 255 - mean_c) / std_c with
+ * CLIP's constants.  Pre-LN layers with quick-GELU, class row -> post_layernorm -> projection (no bias) -> fp32 [proj_dim].   */
+typedef struct mhip_clipvis mhip_clipvis;
+typedef struct mhip_clipvis_config {
+  int dim, depth, heads;   /* 768/12/12 ViT-B; head dim must be 64, dim <= 1024.  Tokens: 1 + (image_size / patch)^2        */
+  int patch;               /* 32 (ViT-B/32), 16 (ViT-B/16): a multiple of 8 that divides image_size                       */
+  int image_size;          /* 224                                                                                         */
+  int ffn;                 /* 3072; a multiple of 64                                                                      */
+  int proj_dim;            /* 512                                                                                         */
+  float ln_eps;            /* 1e-5                                                                                        */
+} mhip_clipvis_config;
+int mhip_clipvis_create(mhip_ctx* ctx, int precision, const mhip_clipvis_config* cfg, mhip_clipvis** out);
+int mhip_clipvis_destroy(mhip_clipvis* m);
+/* keys of the OpenAI checkpoint's vision tower: visual.conv1.weight, visual.class_embedding, visual.positional_embedding,
+ * visual.ln_pre.*, visual.transformer.resblocks.N.{ln_1,attn.in_proj_weight,attn.in_proj_bias,attn.out_proj,ln_2,mlp.c_fc,
+ * mlp.c_proj}.*, visual.ln_post.*, visual.proj [dim][proj_dim]; any other key is MHIP_EINVAL                                 */
+int mhip_clipvis_set_tensor(mhip_clipvis* m, const char* key, const float* data, const int64_t* shape, int ndim);
+int mhip_clipvis_finalize(mhip_clipvis* m);
+int mhip_clipvis_alloc_arena(mhip_clipvis* m);
+int mhip_clipvis_arena(mhip_clipvis* m, void** arena_dev, size_t* bytes);
+/* bytes of context workspace one mhip_clipvis_embed_host call of B clips lays out (0: bad arguments)                         */
+size_t mhip_clipvis_workspace_bytes(mhip_clipvis* m, int B);
+/* B host clips -> emb_out fp32 [B][proj_dim].  swap_rb: the clips are stored BGR                                            */
+int mhip_clipvis_embed_host(mhip_clipvis* m, const uint8_t* clips_host, int B, int swap_rb, float* emb_out);
+/* n_clips BGR host clips through the encoder once, then cos_out[p] = x.y / max(|x| |y|, 1e-8) of the embeddings of clips
+ * pair_a[p], pair_b[p] (fp32 [n_pairs]); emb_out fp32 [n_clips][proj_dim] or NULL                                           */
+int mhip_clipvis_embed_pairs_host(mhip_clipvis* m, const uint8_t* clips_host, int n_clips, const int32_t* pair_a,
+                                  const int32_t* pair_b, int n_pairs, float* emb_out, float* cos_out);
+/* as embed_host, plus the residual stream after the embedding kernel (pre_layrnorm applied) and after every layer:
+ * taps_out fp32 [depth + 1][B][tokens][dim]; emb_out may be NULL                                                             */
+int mhip_clipvis_debug_taps_host(mhip_clipvis* m, const uint8_t* clips_host, int B, int swap_rb, float* taps_out, float* emb_out);
+/* The kernels alone on host arrays (parity tests).  quick-GELU of x fp32 [n] rounded to the precision's element type, n % 8 == 0 */
+int mhip_clipvis_quick_gelu_host(mhip_ctx* ctx, int precision, const float* x, int n, float* out);
+/* patches fp32 [B][n_tok - 1][D], cls [D], pos [n_tok][D], LayerNorm g / b [D] -> h_out fp32 [B][roundup(n_tok, 8)][D]
+ * (rows past n_tok are zeros)                                                                                               */
+int mhip_clipvis_embed_rows_host(mhip_ctx* ctx, const float* patches, const float* cls, const float* pos, const float* g,
+                                 const float* b, int B, int n_tok, int D, float eps, float* h_out);
+/* h fp32 [B][npad][D] (row 0 of every image is used), LayerNorm g / b [D], proj [D][E] -> emb_out fp32 [B][E]                */
+int mhip_clipvis_head_host(mhip_ctx* ctx, const float* h, int B, int npad, int D, const float* g, const float* b, float eps,
+                           const float* proj, int E, float* emb_out);
+/* emb fp32 [n][E], pairs of row indices -> cos_out fp32 [n_pairs]                                                             */
+int mhip_clipvis_pair_cosine_host(mhip_ctx* ctx, const float* emb, int n, int E, const int32_t* pair_a, const int32_t* pair_b,
+                                  int n_pairs, float* cos_out);
+
 /* ---- word-box / line geometry of the DiT box processor (host, pure functions; no ctx) --------------------------------- */
 /* replaces: merge_boxes, marie/utils/overlap.py:268-330 (find_overlap_horizontal(center_y_overlap=0.5) :106-183,
  * merge_bboxes_as_block :186-204).  xyxy fp32 [n][4] -> out_xyxy fp32 (capacity n rows), *n_out rows.       */

@@ -159,6 +159,20 @@ _SIGNATURES = (
     ("mhip_vq_heatmap_host", _i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     ("mhip_vq_peaks_host", _i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp]),
     ("mhip_clip_cosine_host", _i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    ("mhip_clipvis_create", _i, [_vp, _i, _vp, C.POINTER(_vp)]),
+    ("mhip_clipvis_destroy", _i, [_vp]),
+    ("mhip_clipvis_set_tensor", _i, [_vp, C.c_char_p, _vp, C.POINTER(C.c_int64), _i]),
+    ("mhip_clipvis_finalize", _i, [_vp]),
+    ("mhip_clipvis_alloc_arena", _i, [_vp]),
+    ("mhip_clipvis_arena", _i, [_vp, C.POINTER(_vp), C.POINTER(_sz)]),
+    ("mhip_clipvis_workspace_bytes", _sz, [_vp, _i]),
+    ("mhip_clipvis_embed_host", _i, [_vp, _vp, _i, _i, _vp]),
+    ("mhip_clipvis_embed_pairs_host", _i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
+    ("mhip_clipvis_debug_taps_host", _i, [_vp, _vp, _i, _i, _vp, _vp]),
+    ("mhip_clipvis_quick_gelu_host", _i, [_vp, _i, _vp, _i, _vp]),
+    ("mhip_clipvis_embed_rows_host", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_float, _vp]),
+    ("mhip_clipvis_head_host", _i, [_vp, _vp, _i, _i, _i, _vp, _vp, C.c_float, _vp, _i, _vp]),
+    ("mhip_clipvis_pair_cosine_host", _i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp]),
     ("mhip_max_page_size", _i, [_i, _i, _i, _i, C.c_double, C.POINTER(_i), C.POINTER(_i)]),
     ("mhip_resize_area_u8", _i, [_vp, _vp, _i, _i, _i, C.c_size_t, _vp, _i, _i]),
     ("mhip_resize_area_u8_host", _i, [_vp, _vp, _i, _i, _i, _vp, _i, _i]),
@@ -241,6 +255,12 @@ class LayoutLMv3Config(C.Structure):
                 ("rel_pos_bins", C.c_int), ("max_rel_pos", C.c_int), ("rel_2d_pos_bins", C.c_int),
                 ("max_rel_2d_pos", C.c_int), ("layer_norm_eps", C.c_float), ("pad_id", C.c_int), ("num_labels", C.c_int),
                 ("max_text", C.c_int)]
+
+
+class ClipVisConfig(C.Structure):
+    """mirror of mhip_clipvis_config (include/marie_hip.h)"""
+    _fields_ = [("dim", C.c_int), ("depth", C.c_int), ("heads", C.c_int), ("patch", C.c_int), ("image_size", C.c_int),
+                ("ffn", C.c_int), ("proj_dim", C.c_int), ("ln_eps", C.c_float)]
 
 
 class VqFilters(C.Structure):

@@ -40,7 +40,13 @@ enum MhipKernelId {
   MHIP_K_VQ_HEATMAP = 21,   // Gauss-Haar box filters over per-code integral images held in LDS, and the sum of the filters
   MHIP_K_VQ_PEAKS = 22,     // arg-max and suppression per (window, template)
   MHIP_K_CLIP_COSINE = 23,  // cosine similarity of the colour features of clip pairs
-  MHIP_K_COUNT = 24
+  // CLIP vision tower (clip_ops.hip)
+  MHIP_K_CLIPVIS_PATCHIFY = 24,  // u8 clips -> per-channel normalised patch rows
+  MHIP_K_CLIPVIS_EMBED = 25,     // class / patch + position rows -> pre_layrnorm -> fp32 stream; the LayerNorms of the layers
+  MHIP_K_QUICK_GELU = 26,        // x * sigmoid(1.702 x) in place
+  MHIP_K_CLIPVIS_HEAD = 27,      // post_layernorm of the class row + projection
+  MHIP_K_PAIR_COSINE = 28,       // cosine of embedding pairs by index
+  MHIP_K_COUNT = 29
 };
 
 constexpr int MHIP_ZERO_BYTES = 65536;
@@ -510,6 +516,23 @@ struct TokenHeadDesc {
 };
 int mhip_token_head_max_labels(int D);
 int mhip_launch_token_head(mhip_ctx* ctx, const TokenHeadDesc& d);
+// ------------------------------------------------------------------ CLIP vision tower ops (clip_ops.hip)
+// Row kernels: D % 64 == 0, D <= 1024.  Token rows as the ViT's: npad rows an image, row 0 the class token.
+// clips u8 [B][S][S][3] -> out [B * (S/P)^2][ld] T, column (c * P + y) * P + x = (pixel / 255 - mean[c]) / stdv[c]; P % 8 == 0
+int mhip_launch_clipvis_patchify(mhip_ctx* ctx, int precision, const uint8_t* imgs, int B, int S, int P, int swap_rb,
+                                 const float mean[3], const float stdv[3], void* out, int ld);
+// h [B*npad][D] fp32 = LN(class + pos[0]) | LN(patches [B*(n_tok-1)][D] + pos[1..]) | zeros
+int mhip_launch_clipvis_embed(mhip_ctx* ctx, const float* patches, const float* cls, const float* pos, const float* g, const float* b,
+                              float* h, int B, int npad, int n_tok, int D, float eps);
+int mhip_launch_clipvis_layernorm(mhip_ctx* ctx, int precision, const float* x, const float* g, const float* b, void* out, int rows,
+                                  int D, float eps);
+// x [n] T in place; n a multiple of 16 bytes' worth of elements
+int mhip_launch_quick_gelu(mhip_ctx* ctx, int precision, void* x, long long n);
+// emb [B][E] fp32 = LN(h[img * npad]) proj_t^T, proj_t [E][D] fp32
+int mhip_launch_clipvis_head(mhip_ctx* ctx, const float* h, int B, int npad, int D, const float* g, const float* b, float eps,
+                             const float* proj_t, int E, float* emb);
+// out[p] = cos(emb[pair_a[p]], emb[pair_b[p]]), emb [..][E] fp32; the indices are the caller's to check
+int mhip_launch_pair_cosine(mhip_ctx* ctx, const float* emb, int E, const int* pair_a, const int* pair_b, int n_pairs, float* out);
 size_t mhip_pil_resize_fragments_scratch(const mhip_crop_desc* descs, int n, int dh, int dw, int filter);
 int mhip_pil_resize_fragments(mhip_ctx* ctx, const uint8_t* base_dev, const mhip_crop_desc* descs, int n, uint8_t* dst, int dh,
                               int dw, int filter, void* scratch, size_t scratch_bytes);

@@ -1,0 +1,364 @@
+"""CLIP image embeddings on the MI355X: ``OpenAIEmbeddings`` / ``OpenAITransformerEmbeddings`` behind the reference's surface.
+
+Mirrors marie/embeddings/{embeddings_object,base}.py and marie/embeddings/openai/{openai_embeddings,openai_trans_embeddings}.py
+for what ``VQNNFTemplateMatcher.score`` takes from them: the image embedding of a 224 x 224 snippet clip, 95 % of the weighted
+score.  The vision tower (ViT + projection) runs in HIP (csrc/clip_api.hip, the ``mhip_clipvis_*`` entry points); the image
+processor — ``convert("RGB")``, Pillow BICUBIC resize of the shortest edge, centre crop — runs through the Pillow-exact resize
+the detector already has, and CLIP's normalisation is part of the patch kernel.
+
+Built: the ViT towers (ViT-B/32, ViT-B/16, any width of 64-wide heads up to 1024) from an OpenAI-scheme (``visual.*``) or a
+``transformers``-scheme (``vision_model.*`` + ``visual_projection``) state dict.  Not built: the ``ModifiedResNet`` towers
+(``RN50x4`` ...: ``NotImplementedError``), the text tower and its BPE (``image=None``: ``NotImplementedError``).  Errors raise
+``MarieHipError``; the reference's ``try/except`` returning an empty ``EmbeddingsObject`` is not restated.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import json
+import logging
+import os
+import re
+from abc import ABC, abstractmethod
+from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+
+from ._lib import PREC_F16, PREC_F32, ClipVisConfig, Context, MarieHipError, ModelHandle, check
+
+logger = logging.getLogger(__name__)
+
+
+class EmbeddingsObject:
+    """marie/embeddings/embeddings_object.py"""
+
+    def __init__(self):
+        self.embeddings = None
+        self.total_tokens = 0
+
+
+class EmbeddingsBase(ABC):
+    """marie/embeddings/base.py"""
+
+    def __init__(self, **kwargs) -> None:
+        super().__init__()
+        self.logger = logging.getLogger(self.__class__.__name__)
+
+    @abstractmethod
+    def get_embeddings(self, texts: List[str], truncation: bool = None, max_length: int = None) -> EmbeddingsObject:
+        """the embedding of ``texts`` (or, in the CLIP classes, of ``image``) and its metadata"""
+
+    def get_embeddings_raw(self, texts: List[str], truncation: bool = None, max_length: int = 256):
+        return self.get_embeddings(texts, truncation, max_length).embeddings
+
+
+# ---------------------------------------------------------------------------------------------------- checkpoint -> state
+_HF_LAYER = {"self_attn.out_proj": "attn.out_proj", "layer_norm1": "ln_1", "layer_norm2": "ln_2", "mlp.fc1": "mlp.c_fc",
+             "mlp.fc2": "mlp.c_proj"}
+_HF_TOP = {"vision_model.embeddings.class_embedding": "visual.class_embedding",
+           "vision_model.embeddings.patch_embedding.weight": "visual.conv1.weight",
+           "vision_model.embeddings.position_embedding.weight": "visual.positional_embedding",
+           "vision_model.pre_layrnorm.weight": "visual.ln_pre.weight", "vision_model.pre_layrnorm.bias": "visual.ln_pre.bias",
+           "vision_model.post_layernorm.weight": "visual.ln_post.weight",
+           "vision_model.post_layernorm.bias": "visual.ln_post.bias"}
+
+
+def _f32(t) -> np.ndarray:
+    """a checkpoint tensor (torch, any float storage — OpenAI checkpoints are fp16 — or array) as a float32 array"""
+    if hasattr(t, "detach"):
+        t = t.detach().float().cpu().numpy()
+    return np.ascontiguousarray(np.asarray(t), dtype=np.float32)
+
+
+def _from_transformers(sd: Dict[str, Any]) -> Dict[str, np.ndarray]:
+    """the ``transformers`` key scheme -> the OpenAI one: q / k / v concatenated into ``in_proj``, the projection transposed"""
+    out, qkv = {}, {}
+    for key, val in sd.items():
+        if key in _HF_TOP:
+            out[_HF_TOP[key]] = _f32(val)
+        elif key == "visual_projection.weight":
+            out["visual.proj"] = np.ascontiguousarray(_f32(val).T)
+        else:
+            m = re.match(r"vision_model\.encoder\.layers\.(\d+)\.(.+)\.(weight|bias)$", key)
+            if not m:
+                continue                                        # the text tower, logit_scale, position_ids
+            n, name, kind = int(m.group(1)), m.group(2), m.group(3)
+            if name in ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"):
+                qkv[(n, kind, name[10])] = _f32(val)
+            elif name in _HF_LAYER:
+                out[f"visual.transformer.resblocks.{n}.{_HF_LAYER[name]}.{kind}"] = _f32(val)
+    for n, kind in sorted({(n, kind) for n, kind, _ in qkv}):
+        parts = [qkv.get((n, kind, p)) for p in "qkv"]
+        if any(p is None for p in parts):
+            raise MarieHipError(f"CLIP checkpoint: layer {n} lacks one of q_proj / k_proj / v_proj ({kind})")
+        out[f"visual.transformer.resblocks.{n}.attn.in_proj_{kind}"] = np.concatenate(parts, axis=0)
+    return out
+
+
+def load_clip_vision_state(checkpoint: Dict[str, Any]) -> Tuple[Dict[str, np.ndarray], ClipVisConfig]:
+    """A ``torch.load``-ed CLIP checkpoint — ``{"model_state_dict": sd}`` or a bare state dict, OpenAI (``visual.*``) or
+    ``transformers`` (``vision_model.*``) keys — -> (the vision tower's tensors under the OpenAI keys as float32 arrays, the
+    geometry read from their shapes as ``clip.build_model`` reads it).  Text-tower keys are ignored."""
+    sd = checkpoint.get("model_state_dict", checkpoint) if isinstance(checkpoint, dict) else None
+    if not isinstance(sd, dict) or not sd:
+        raise MarieHipError("CLIP checkpoint: expected a state dict or {'model_state_dict': state dict}")
+    if any(k.startswith("visual.layer1.") or k.startswith("visual.attnpool.") for k in sd):
+        raise NotImplementedError("CLIP checkpoint holds a ModifiedResNet vision tower (RN50 / RN101 / RN50x4 ...): only the "
+                                  "ViT towers are built")
+    if any(k.startswith("vision_model.") for k in sd):
+        state = _from_transformers(sd)
+    else:
+        state = {k: _f32(v) for k, v in sd.items() if k.startswith("visual.")}
+    for need in ("visual.conv1.weight", "visual.positional_embedding", "visual.proj",
+                 "visual.transformer.resblocks.0.mlp.c_fc.weight"):
+        if need not in state:
+            raise MarieHipError(f"CLIP checkpoint: no {need} (neither key scheme matches)")
+    conv, pos = state["visual.conv1.weight"], state["visual.positional_embedding"]
+    cfg = ClipVisConfig()
+    cfg.dim, cfg.patch = int(conv.shape[0]), int(conv.shape[-1])
+    cfg.depth = len([k for k in state if k.startswith("visual.") and k.endswith(".attn.in_proj_weight")])
+    grid = int(round((pos.shape[0] - 1) ** 0.5))
+    if grid * grid + 1 != pos.shape[0]:
+        raise MarieHipError(f"CLIP checkpoint: {pos.shape[0]} position rows are no square grid plus the class token")
+    cfg.image_size = cfg.patch * grid
+    cfg.heads = cfg.dim // 64
+    cfg.ffn = int(state["visual.transformer.resblocks.0.mlp.c_fc.weight"].shape[0])
+    cfg.proj_dim = int(state["visual.proj"].shape[1])
+    cfg.ln_eps = 1e-5
+    return state, cfg
+
+
+def _vp(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None else C.c_void_p(0)
+
+
+# ---------------------------------------------------------------------------------------------------- the model handle
+class ClipVisionModel(ModelHandle):
+    """``mhip_clipvis``: the vision tower + projection on a :class:`Context`."""
+
+    def __init__(self, ctx: Context, state: Optional[Dict[str, np.ndarray]], config: ClipVisConfig, precision: int = PREC_F16):
+        self.cfg, self.precision = config, int(precision)
+        super().__init__(ctx, "clipvis", self.precision, C.byref(config))
+        self.n_tok = (config.image_size // config.patch) ** 2 + 1      # the class token + the patch grid
+        if state is not None:
+            self.load_state(state)
+
+    def _clips(self, clips) -> np.ndarray:
+        S = self.cfg.image_size
+        clips = np.ascontiguousarray(clips, np.uint8)
+        if clips.ndim == 3:
+            clips = clips[None]
+        if clips.ndim != 4 or clips.shape[1:] != (S, S, 3) or clips.shape[0] < 1:
+            raise ValueError(f"clips of shape (n, {S}, {S}, 3) expected, got {clips.shape}")
+        return clips
+
+    def workspace_bytes(self, n: int) -> int:
+        return int(self.lib.mhip_clipvis_workspace_bytes(self.h, int(n)))
+
+    def embed_host(self, clips, swap_rb: bool = False) -> np.ndarray:
+        """uint8 clips (n, S, S, 3), RGB (or BGR with ``swap_rb``) -> embeddings fp32 (n, proj_dim), one encoder call"""
+        clips = self._clips(clips)
+        out = np.empty((clips.shape[0], self.cfg.proj_dim), np.float32)
+        self._call("embed_host", _vp(clips), clips.shape[0], 1 if swap_rb else 0, _vp(out))
+        return out
+
+    def embed_pairs_host(self, clips_bgr, pairs, want_embeddings: bool = False):
+        """BGR clips through the encoder once and the cosine of every (a, b) index pair -> fp32 (n_pairs,)
+        (, embeddings (n, proj_dim))"""
+        clips = self._clips(clips_bgr)
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        pa, pb = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
+        cos = np.empty(len(pairs), np.float32)
+        emb = np.empty((clips.shape[0], self.cfg.proj_dim), np.float32) if want_embeddings else None
+        self._call("embed_pairs_host", _vp(clips), clips.shape[0], _vp(pa), _vp(pb), len(pairs), _vp(emb), _vp(cos))
+        return (cos, emb) if want_embeddings else cos
+
+    def debug_taps_host(self, clips, swap_rb: bool = False):
+        """-> (taps fp32 (depth + 1, n, tokens, dim): the residual stream after the embedding and after every layer,
+        embeddings (n, proj_dim))"""
+        clips = self._clips(clips)
+        n = clips.shape[0]
+        taps = np.empty((self.cfg.depth + 1, n, self.n_tok, self.cfg.dim), np.float32)
+        emb = np.empty((n, self.cfg.proj_dim), np.float32)
+        self._call("debug_taps_host", _vp(clips), n, 1 if swap_rb else 0, _vp(taps), _vp(emb))
+        return taps, emb
+
+
+# ---- the kernels on host arrays (what tests/test_clip_gpu.py drives)
+def quick_gelu_host(ctx: Context, precision: int, x) -> np.ndarray:
+    x = np.ascontiguousarray(x, np.float32).reshape(-1)
+    out = np.empty_like(x)
+    check(ctx.h, ctx.lib.mhip_clipvis_quick_gelu_host(ctx.h, int(precision), _vp(x), x.size, _vp(out)), "mhip_clipvis_quick_gelu_host")
+    return out
+
+
+def embed_rows_host(ctx: Context, patches, cls, pos, g, b, eps: float = 1e-5) -> np.ndarray:
+    """patches (B, n_tok - 1, D), cls (D), pos (n_tok, D), LayerNorm g / b -> h fp32 (B, roundup(n_tok, 8), D)"""
+    patches, cls, pos, g, b = (np.ascontiguousarray(a, np.float32) for a in (patches, cls, pos, g, b))
+    B, np_, D = patches.shape
+    n_tok = np_ + 1
+    out = np.empty((B, (n_tok + 7) // 8 * 8, D), np.float32)
+    check(ctx.h, ctx.lib.mhip_clipvis_embed_rows_host(ctx.h, _vp(patches), _vp(cls), _vp(pos), _vp(g), _vp(b), B, n_tok, D,
+                                                      float(eps), _vp(out)), "mhip_clipvis_embed_rows_host")
+    return out
+
+
+def head_host(ctx: Context, h, g, b, proj, eps: float = 1e-5) -> np.ndarray:
+    """h (B, npad, D) (row 0 of every image), LayerNorm g / b (D), proj (D, E) -> fp32 (B, E)"""
+    h, g, b, proj = (np.ascontiguousarray(a, np.float32) for a in (h, g, b, proj))
+    B, npad, D = h.shape
+    out = np.empty((B, proj.shape[1]), np.float32)
+    check(ctx.h, ctx.lib.mhip_clipvis_head_host(ctx.h, _vp(h), B, npad, D, _vp(g), _vp(b), float(eps), _vp(proj), proj.shape[1],
+                                                _vp(out)), "mhip_clipvis_head_host")
+    return out
+
+
+def pair_cosine_host(ctx: Context, emb, pairs) -> np.ndarray:
+    """emb (n, E) fp32, pairs (n_pairs, 2) of row indices -> fp32 (n_pairs,)"""
+    emb = np.ascontiguousarray(emb, np.float32)
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    pa, pb = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
+    out = np.empty(len(pairs), np.float32)
+    check(ctx.h, ctx.lib.mhip_clipvis_pair_cosine_host(ctx.h, _vp(emb), emb.shape[0], emb.shape[1], _vp(pa), _vp(pb), len(pairs),
+                                                       _vp(out)), "mhip_clipvis_pair_cosine_host")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------- preprocessing
+def resized_size(width: int, height: int, size: int) -> Tuple[int, int]:
+    """(w, h) after the image processor's shortest-edge resize: the short edge becomes ``size``, the long one
+    ``int(size * long / short)`` (truncated, not rounded)"""
+    short, long = (width, height) if width <= height else (height, width)
+    new_long = int(size * long / short)
+    return (size, new_long) if width <= height else (new_long, size)
+
+
+def center_crop_box(width: int, height: int, size: int) -> Tuple[int, int]:
+    """(left, top) of the ``size`` x ``size`` centre crop"""
+    return (width - size) // 2, (height - size) // 2
+
+
+# ---------------------------------------------------------------------------------------------------- the embeddings classes
+def _device_id(devices) -> int:
+    if not devices:
+        return 0
+    d = devices[0]
+    idx = getattr(d, "index", None)
+    if idx is None and isinstance(d, str) and ":" in d:
+        idx = int(d.split(":")[1])
+    return int(idx or 0)
+
+
+class ClipImageEmbeddings(EmbeddingsBase):
+    """What the two CLIP classes share: the tower, the image processor and the batched entries the matcher uses."""
+
+    def __init__(self, model_name_or_path: Union[str, os.PathLike, None] = None, model_version: Optional[str] = None,
+                 use_gpu: bool = True, batch_size: int = 16, use_auth_token: Optional[Union[str, bool]] = None,
+                 devices: Optional[List[Any]] = None, show_error: Optional[Union[str, bool]] = True, *,
+                 state: Optional[Dict[str, Any]] = None, precision: Union[str, int] = "f16", ctx: Optional[Context] = None,
+                 **kwargs):
+        """``model_name_or_path``: a model directory holding ``pytorch_model.bin`` (and, for ``OpenAIEmbeddings``,
+        ``marie.json``); ``state``: the loaded checkpoint instead (a state dict or ``{"model_state_dict": ...}``)."""
+        super().__init__(**kwargs)
+        if not use_gpu:
+            raise MarieHipError(f"{type(self).__name__} here is the MI355X path; use_gpu=False has no implementation")
+        self.show_error, self.batch_size = show_error, batch_size
+        self.model_name_or_path = model_name_or_path
+        if state is None:
+            state = self._load_checkpoint(model_name_or_path)
+        tensors, cfg = load_clip_vision_state(state)
+        if isinstance(precision, str):
+            if precision not in ("f16", "f32"):
+                raise ValueError(f"precision {precision!r}: 'f16' or 'f32'")
+            precision = PREC_F16 if precision == "f16" else PREC_F32
+        self.ctx = ctx or Context(_device_id(devices))
+        self.model = ClipVisionModel(self.ctx, tensors, cfg, precision)
+        self.image_size, self.proj_dim = cfg.image_size, cfg.proj_dim
+        self.encoder_calls = 0               # device encoder calls so far
+        self.clips_embedded = 0              # clips those calls carried
+
+    def _load_checkpoint(self, path):
+        import torch
+
+        if path is None:
+            raise MarieHipError(f"{type(self).__name__}: a model directory or a loaded state is required")
+        file = os.path.join(path, "pytorch_model.bin") if os.path.isdir(path) else path
+        if not os.path.isfile(file):
+            raise MarieHipError(f"{type(self).__name__}: no checkpoint at {file}")
+        return torch.load(file, map_location="cpu")
+
+    def close(self):
+        self.model.close()
+
+    # -- image processor ---------------------------------------------------------------------------------------------
+    def preprocess(self, image) -> np.ndarray:
+        """``convert("RGB")`` -> BICUBIC resize of the shortest edge to ``image_size`` -> centre crop: the uint8 RGB clip
+        (image_size, image_size, 3) the processor would rescale and normalise (that part is the patch kernel's)"""
+        from .dit import pil_resize_rgb
+
+        S = self.image_size
+        rgb = np.ascontiguousarray(np.asarray(image.convert("RGB")), np.uint8)
+        h, w = rgb.shape[:2]
+        if (w, h) != (S, S):
+            nw, nh = resized_size(w, h, S)
+            if (nw, nh) != (w, h):
+                rgb = pil_resize_rgb(self.ctx, rgb, (nh, nw), filter=3)
+            left, top = center_crop_box(nw, nh, S)
+            rgb = np.ascontiguousarray(rgb[top:top + S, left:left + S])
+        return rgb
+
+    # -- the reference's entry ---------------------------------------------------------------------------------------
+    def get_embeddings(self, texts: List[str], truncation: bool = None, max_length: int = None, image=None,
+                       boxes: List[List[int]] = None, **kwargs) -> EmbeddingsObject:
+        if image is None:
+            raise NotImplementedError("the CLIP text tower (get_embeddings without an image) is not built")
+        result = EmbeddingsObject()
+        result.embeddings = self._embed(self.preprocess(image)[None], swap_rb=False)
+        result.total_tokens = -1
+        return result
+
+    # -- the matcher's entries -----------------------------------------------------------------------------------------
+    def _embed(self, clips: np.ndarray, swap_rb: bool) -> np.ndarray:
+        self.encoder_calls += 1
+        self.clips_embedded += len(clips)
+        return self.model.embed_host(clips, swap_rb=swap_rb)
+
+    def embed_clips(self, clips_u8_bgr) -> np.ndarray:
+        """BGR uint8 clips (n, image_size, image_size, 3), as the matcher holds them -> fp32 (n, proj_dim), one encoder call"""
+        return self._embed(np.ascontiguousarray(clips_u8_bgr, np.uint8), swap_rb=True)
+
+    def cosine_pairs(self, clips_u8_bgr, pairs: Sequence[Tuple[int, int]], want_embeddings: bool = False):
+        """the clips through the encoder once, and the cosine of the embeddings of every (a, b) index pair -> fp32 (n_pairs,)
+        (, embeddings fp32 (n, proj_dim))"""
+        clips = np.ascontiguousarray(clips_u8_bgr, np.uint8)
+        self.encoder_calls += 1
+        self.clips_embedded += len(clips)
+        return self.model.embed_pairs_host(clips, pairs, want_embeddings=want_embeddings)
+
+
+    def pair_cosines(self, embeddings, pairs: Sequence[Tuple[int, int]]) -> np.ndarray:
+        """the cosine kernel alone on embeddings already at hand, fp32 (n, proj_dim) -> fp32 (n_pairs,)"""
+        return pair_cosine_host(self.ctx, embeddings, pairs)
+
+
+class OpenAIEmbeddings(ClipImageEmbeddings):
+    """marie/embeddings/openai/openai_embeddings.py: the architecture is named by the model directory's ``marie.json``."""
+
+    def __init__(self, model_name_or_path=None, *args, architecture: Optional[str] = None, **kwargs):
+        if architecture is None and model_name_or_path is not None and os.path.isdir(model_name_or_path):
+            config_file = os.path.join(model_name_or_path, "marie.json")
+            if not os.path.isfile(config_file):
+                raise MarieHipError(f"{model_name_or_path} does not appear to have a file named marie.json")
+            with open(config_file, "r", encoding="utf-8") as f:
+                config = json.load(f)
+            if "architecture" not in config:
+                raise ValueError(f"Model config does not contain 'architecture' key: {config}")
+            architecture = config["architecture"]
+        if architecture is not None and not str(architecture).startswith("ViT-"):
+            raise NotImplementedError(f"CLIP architecture {architecture!r}: only the ViT towers are built (ViT-B/32, ViT-B/16); "
+                                      "the ModifiedResNet / attention-pool tower is not")
+        self.architecture = architecture
+        super().__init__(model_name_or_path, *args, **kwargs)
+
+
+class OpenAITransformerEmbeddings(ClipImageEmbeddings):
+    """marie/embeddings/openai/openai_trans_embeddings.py (``transformers.CLIPModel``, openai/clip-vit-base-patch32)"""

@@ -8,10 +8,14 @@ grid in a handful of launches (csrc/vqnnf.hip); only the peaks come back.  Templ
 filter responses) is built once per template and cached under the reference's key ``key_{x}_{y}_{w}_{h}``.
 
 Built: the model-free ``num_features == 27`` colour features of ``PixelFeatureExtractor`` (the paper's colour variant).
-Not built: the EfficientNet hyper-column features and ``pca_lowrank`` (``n_feature != 27`` / ``pca_dims`` raise), the CLIP
-snippet embedding (``embeddings_processor`` is any callable; with None the embedding similarity is taken equal to the
-feature similarity), ``resize_image_progressive`` (``downscale_factor != 1`` raises), ``MetaTemplateMatcher`` and
-``DeepDimTemplateMatcher``, and the reference's /tmp/dim writes, prints and visualisations.  ``slice_image`` and
+The snippet embedding of ``score`` is CLIP's: ``embeddings_processor`` takes an ``OpenAIEmbeddings`` /
+``OpenAITransformerEmbeddings`` of ``embeddings.py`` (the ViT towers in HIP; the unique clips of a scoring batch go through the
+encoder in one call), or any callable clip -> vector; with None the embedding similarity is taken equal to the feature
+similarity.
+Not built: the EfficientNet hyper-column features and ``pca_lowrank`` (``n_feature != 27`` / ``pca_dims`` raise), CLIP's RN50x4
+tower (the reference's default snippet model: ``embeddings.py`` refuses it), ``resize_image_progressive``
+(``downscale_factor != 1`` raises), ``MetaTemplateMatcher`` and ``DeepDimTemplateMatcher``, and the reference's /tmp/dim writes,
+prints and visualisations.  ``slice_image`` and
 ``GreedyNMMPostprocess`` restate sahi's, which is not installed here: their parity with sahi is not pinned by a golden.
 """
 from __future__ import annotations
@@ -467,7 +471,7 @@ class VQNNFTemplateMatcher(BaseTemplateMatcher):
                  use_gpu: bool = True, labels: Optional[List[str]] = None, batch_size: int = 16, use_auth_token=None,
                  devices: Optional[List[Any]] = None, show_error: Optional[Union[str, bool]] = True, *,
                  n_feature: int = N_FEATURES, pca_dims: Optional[int] = None,
-                 embeddings_processor: Optional[Callable[[np.ndarray], np.ndarray]] = None, seed: int = 0,
+                 embeddings_processor: Union[Callable[[np.ndarray], np.ndarray], Any, None] = None, seed: int = 0,
                  ctx: Optional[Context] = None, **kwargs):
         super().__init__(True, **kwargs)
         if not use_gpu:
@@ -544,8 +548,39 @@ class VQNNFTemplateMatcher(BaseTemplateMatcher):
         if key not in self.cached_embeddings_clips:
             if clip.shape[0] != CLIP_SIZE[0] or clip.shape[1] != CLIP_SIZE[1]:
                 raise ValueError("Image must be 224x224")
-            self.cached_embeddings_clips[key] = np.asarray(self.embeddings_processor(clip), np.float64).reshape(-1)
+            if self._batched_embeddings():
+                self.cached_embeddings_clips[key] = self.embeddings_processor.embed_clips(clip[None])[0]
+            else:
+                self.cached_embeddings_clips[key] = np.asarray(self.embeddings_processor(clip), np.float64).reshape(-1)
         return self.cached_embeddings_clips[key]
+
+    def _batched_embeddings(self) -> bool:
+        """an embeddings object of embeddings.py (batched device entries), not a plain callable"""
+        return hasattr(self.embeddings_processor, "cosine_pairs")
+
+    def embedding_sims(self, t_clips: np.ndarray, q_clips: np.ndarray) -> np.ndarray:
+        """The embedding cosine of every (template clip, query clip) pair through an embeddings object: the unique clips of
+        the batch, keyed by their bytes as ``cached_embeddings_clips`` is, take one encoder call and the cosines one launch.
+        Clips embedded by an earlier batch (the templates of the previous page) are not embedded again."""
+        ep, cache = self.embeddings_processor, self.cached_embeddings_clips
+        index, clips = {}, []
+        for clip in list(t_clips) + list(q_clips):
+            key = clip.tobytes()
+            if key not in index:
+                if clip.shape[0] != CLIP_SIZE[0] or clip.shape[1] != CLIP_SIZE[1]:
+                    raise ValueError("Image must be 224x224")
+                index[key] = len(clips)
+                clips.append(clip)
+        pairs = [(index[t.tobytes()], index[q.tobytes()]) for t, q in zip(t_clips, q_clips)]
+        keys = list(index)
+        new = [i for i, key in enumerate(keys) if key not in cache]
+        if len(new) == len(keys):                      # nothing known yet: encoder and cosines in one call
+            sims, emb = ep.cosine_pairs(np.stack(clips), pairs, want_embeddings=True)
+            cache.update(zip(keys, emb))
+            return sims
+        if new:
+            cache.update(zip((keys[i] for i in new), ep.embed_clips(np.stack([clips[i] for i in new]))))
+        return ep.pair_cosines(np.stack([cache[key] for key in keys]), pairs)
 
     def score_pairs(self, pairs: Sequence[Tuple[np.ndarray, np.ndarray]], scoring_strategy: str) -> List[float]:
         """``score`` of (template snippet, query snippet) pairs with one cosine launch for all of them"""
@@ -554,11 +589,14 @@ class VQNNFTemplateMatcher(BaseTemplateMatcher):
         t_clips = np.stack([self._clip(t) for t, _ in pairs])
         q_clips = np.stack([self._clip(q) for _, q in pairs])
         feature_sims = clip_cosine_host(self.ctx, t_clips, q_clips)
+        batched = self.embedding_sims(t_clips, q_clips) if self._batched_embeddings() else None
         out = []
         for k, feature_sim in enumerate(feature_sims):
             feature_sim = float(feature_sim)
             if self.embeddings_processor is None:
                 embedding_sim = feature_sim
+            elif batched is not None:
+                embedding_sim = float(batched[k])
             else:
                 a, b = self.get_embedding_feature(t_clips[k]), self.get_embedding_feature(q_clips[k])
                 embedding_sim = float(np.dot(a, b) / (max(np.linalg.norm(a), 1e-8) * max(np.linalg.norm(b), 1e-8)))
@@ -623,9 +661,15 @@ class CompositeTemplateMatcher(BaseTemplateMatcher):
     """marie/components/template_matching/composite_template_maching.py: several matchers in turn, merged per page."""
 
     def __init__(self, matchers: List[BaseTemplateMatcher], break_on_match: bool = False,
-                 show_error: Optional[Union[str, bool]] = True, **kwargs):
+                 show_error: Optional[Union[str, bool]] = True, embeddings_processor: Any = None, **kwargs):
+        """``embeddings_processor``: handed to every matcher that scores with one and has none of its own"""
         super().__init__(False, **kwargs)
         self.show_error, self.matchers, self.break_on_match = show_error, matchers, break_on_match
+        self.embeddings_processor = embeddings_processor
+        if embeddings_processor is not None:
+            for matcher in matchers:
+                if hasattr(matcher, "embeddings_processor") and matcher.embeddings_processor is None:
+                    matcher.embeddings_processor = embeddings_processor
 
     def predict(self, *args, **kwargs):
         raise NotImplementedError("This method is not implemented in CompositeTemplateMatcher")
