@@ -101,6 +101,31 @@ typedef struct mhip_conv_desc {
 int mhip_conv2d_nhwc(mhip_ctx* ctx, int precision, const mhip_conv_desc* d, const void* in_dev,
                      const void* in2_dev, const void* w_dev, const float* scale_dev, const float* bias_dev,
                      void* out_dev);
+/* The same primitive with every option of the plain epilogue that the model paths use (the ResNet blocks of the attention
+ * recognizer, the overlay generator's down-sampling convs, the fp32 patch embeddings), for parity tests of each of them:
+ *   out[row(b, yp, xp)][n] = pool( relu( scale[n] * sum_{dy,dx,c} in[b][y*sy + dy*dil - pad][x + dx*dil - pad_x][c] * w[n][dy][dx][c]
+ *                                        + bias[n] + res[res_row][n] ) )
+ * sy: vertical stride (0 = 1; the horizontal stride is 1).  pad_x: horizontal padding, -1 = pad.  res_dev (may be NULL): a residual of
+ * the output's element type and row pitch, added before the ReLU (unpooled outputs; not with GELU).  row_period > 0 (unpooled):
+ * output pixel q is written to row (q / row_period) * row_stride + row_offset + q % row_period and takes residual row
+ * q % row_period; row_stride >= row_period.  The first fifteen fields are those of mhip_conv_desc, in its order.               */
+typedef struct mhip_conv_ex_desc {
+  int32_t B, H, W, Cin;
+  int32_t KH, KW, pad;
+  int32_t N;
+  int32_t pool, relu, out_f32;
+  int32_t dil;
+  int32_t Cin1;
+  int32_t ldc;
+  int32_t pad_cols_writable;
+  int32_t sy;
+  int32_t pad_x;
+  int32_t row_period, row_stride, row_offset;
+  const void* res_dev;
+} mhip_conv_ex_desc;
+int mhip_conv2d_nhwc_ex(mhip_ctx* ctx, int precision, const mhip_conv_ex_desc* d, const void* in_dev,
+                        const void* in2_dev, const void* w_dev, const float* scale_dev, const float* bias_dev,
+                        void* out_dev);
 
 /* ---- crop batcher --------------------------------------------------------------------------- */
 /* One text fragment inside a device buffer: first pixel at base + src_offset, h rows of w pixels, `channels` = 3

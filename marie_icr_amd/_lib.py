@@ -42,6 +42,7 @@ _SIGNATURES = (
     ("mhip_kernel_count", _i, []),
     ("mhip_kernel_name", C.c_char_p, [_i]),
     ("mhip_conv2d_nhwc", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("mhip_conv2d_nhwc_ex", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("mhip_icr_create", _i, [_vp, _i, _i, C.POINTER(_vp)]),
     ("mhip_icr_destroy", _i, [_vp]),
     ("mhip_icr_set_tensor", _i, [_vp, C.c_char_p, _vp, C.POINTER(C.c_int64), _i]),
@@ -206,6 +207,12 @@ class ConvDesc(C.Structure):
                                          "dil", "Cin1", "ldc", "pad_cols_writable")]
 
 
+class ConvExDesc(C.Structure):
+    """mirror of ``mhip_conv_ex_desc`` (include/marie_hip.h); res_dev is an HBM address"""
+    _fields_ = (ConvDesc._fields_ + [(n, C.c_int32) for n in ("sy", "pad_x", "row_period", "row_stride", "row_offset")] +
+                [("res_dev", C.c_void_p)])
+
+
 EPI_LN_ROWS, EPI_LN_COLS, EPI_SPLIT = 1, 2, 3
 
 
@@ -358,6 +365,14 @@ class Context:
                                                 C.c_void_p(in2_ptr or 0), C.c_void_p(w_ptr), C.c_void_p(scale_ptr or 0),
                                                 C.c_void_p(bias_ptr or 0), C.c_void_p(out_ptr)),
               "mhip_conv2d_nhwc")
+
+    def conv2d_nhwc_ex(self, precision: int, desc: "ConvExDesc", in_ptr: int, w_ptr: int, scale_ptr: int, bias_ptr: int,
+                       out_ptr: int, in2_ptr: int = 0):
+        """conv2d_nhwc with vertical stride, pad_x, residual (desc.res_dev) and the periodic output-row mapping."""
+        check(self.h, self.lib.mhip_conv2d_nhwc_ex(self.h, int(precision), C.byref(desc), C.c_void_p(in_ptr),
+                                                   C.c_void_p(in2_ptr or 0), C.c_void_p(w_ptr), C.c_void_p(scale_ptr or 0),
+                                                   C.c_void_p(bias_ptr or 0), C.c_void_p(out_ptr)),
+              "mhip_conv2d_nhwc_ex")
 
     def gemm_ln_fold(self, precision: int, desc: "GemmFoldDesc"):
         """Enqueue one LayerNorm-folded GEMM of a ViT block (EPI_SPLIT / EPI_LN_ROWS / EPI_LN_COLS) on the ctx stream."""

@@ -29,6 +29,33 @@ extern "C" int mhip_conv2d_nhwc(mhip_ctx* ctx, int precision, const mhip_conv_de
   return mhip_launch_conv_igemm(ctx, precision, c);
 }
 
+// the same primitive with every option of the plain epilogue the model paths use (icr_api.hip's `conv`, the patch embedding of
+// vit_api.hip): vertical stride, horizontal padding of its own, residual, periodic output rows
+extern "C" int mhip_conv2d_nhwc_ex(mhip_ctx* ctx, int precision, const mhip_conv_ex_desc* d, const void* in,
+                                   const void* in2, const void* w, const float* scale, const float* bias, void* out) {
+  if (!ctx || !d) return MHIP_EINVAL;
+  if (precision != MHIP_PREC_F16 && precision != MHIP_PREC_F32)
+    return mhip_fail(ctx, MHIP_EINVAL, "unknown precision %d", precision);
+  if (d->B < 1 || d->H < 1 || d->W < 1 || d->N < 1 || d->KH < 1 || d->KW < 1 || d->pad < 0 || d->pool < 0 ||
+      d->pool > 2 || d->sy < 0 || d->pad_x < -1 || d->row_period < 0 || d->row_offset < 0)
+    return mhip_fail(ctx, MHIP_EINVAL, "conv2d_ex: bad descriptor");
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  ConvDesc c;
+  c.in = in; c.w = w; c.scale = scale; c.bias = bias; c.out = out;
+  c.B = d->B; c.H = d->H; c.W = d->W; c.Cin = d->Cin;
+  c.KH = d->KH; c.KW = d->KW; c.pad = d->pad;
+  c.N = d->N; c.pool = d->pool; c.relu = d->relu; c.out_f32 = d->out_f32;
+  c.dil = d->dil > 0 ? d->dil : 1;
+  c.in2 = in2; c.Cin1 = d->Cin1;
+  c.ldc = d->ldc; c.pad_cols_writable = d->pad_cols_writable;
+  c.sy = d->sy > 0 ? d->sy : 1;
+  c.pad_x = d->pad_x;
+  c.res = d->res_dev;
+  c.row_period = d->row_period; c.row_stride = d->row_stride; c.row_offset = d->row_offset;
+  c.epi = EPI_NONE;
+  return mhip_launch_conv_igemm(ctx, precision, c);
+}
+
 // ======================================================================= CRNN model
 namespace {
 
