@@ -12,7 +12,7 @@
 //   ht = LN2(h)   hid = quick_gelu(ht W1^T + b1)              h += hid W2^T + b2
 #include <math.h>
 
-#include "vit_internal.h"
+#include "encoder_block.h"
 
 struct mhip_clipvis {
   mhip_ctx* ctx = nullptr;
@@ -29,21 +29,19 @@ struct mhip_clipvis {
 
 namespace {
 
-constexpr float LOG2E = 1.4426950408889634f;
 // the image processor's Normalize (OPENAI_CLIP_MEAN / OPENAI_CLIP_STD), RGB
 const float CLIP_MEAN[3] = {0.48145466f, 0.4578275f, 0.40821073f};
 const float CLIP_STD[3] = {0.26862954f, 0.26130258f, 0.27577711f};
 constexpr int MAX_CLIPS = 4096;
 
 std::string res(int i, const char* s) { return "visual.transformer.resblocks." + std::to_string(i) + "." + s; }
-std::string blk(int i, const char* s) { return "l" + std::to_string(i) + "." + s; }
 
 // the buffers of one call of B clips (and n_pairs cosines)
 struct ClipRun {
   uint8_t* clips = nullptr;
   int *pair_a = nullptr, *pair_b = nullptr;
   float *pe = nullptr, *h = nullptr, *emb = nullptr, *cos = nullptr;
-  char *ht = nullptr, *qk = nullptr, *vt = nullptr, *ao = nullptr, *hid = nullptr;
+  EncoderWs w;      // w.hid is also the patch matrix (B * patches rows, fewer than R)
 };
 
 void clipvis_carve(const mhip_clipvis* m, Carver& ws, int B, int n_pairs, ClipRun* r) {
@@ -56,11 +54,7 @@ void clipvis_carve(const mhip_clipvis* m, Carver& ws, int B, int n_pairs, ClipRu
   r->pe = ws.take<float>((size_t)B * NPAT * D * 4);
   r->h = ws.take<float>(R * D * 4);
   r->emb = ws.take<float>((size_t)B * c.proj_dim * 4);
-  r->ht = ws.take(R * D * es);
-  r->qk = ws.take((R + 128) * 2 * D * es);      // + slack: the last clip's final query block / key tile reads past its rows
-  r->vt = ws.take((D * R + 128) * es);
-  r->ao = ws.take(R * D * es);
-  r->hid = ws.take(R * std::max<size_t>(c.ffn, K0) * es);     // mlp hidden; also the patch matrix (B * patches rows, fewer than R)
+  encoder_ws_carve(ws, R, D, c.ffn, K0, es, &r->w);
 }
 
 // clips staged in run.clips -> embeddings in run.emb.  taps (host, or null): h after the embedding kernel and after every layer,
@@ -71,17 +65,16 @@ int clipvis_forward(mhip_clipvis* m, int B, int swap_rb, const ClipRun& run, flo
   const int D = c.dim, F = c.ffn, prec = m->precision, NP = m->npad(), NT = m->n_tok(), P = c.patch, S = c.image_size;
   const size_t es = m->esz(), R = (size_t)B * NP;
   const Arena& a = m->arena;
+  const EncoderWs& w = run.w;
   int rc;
-  // rows / columns past the last clip are read by its final tiles (and masked): keep them finite.  The fp32 attention writes
-  // the token rows only: the padding rows of ao start as zeros
-  MHIP_HIP(ctx, hipMemsetAsync(run.qk + R * 2 * D * es, 0, (size_t)128 * 2 * D * es, ctx->stream));
-  MHIP_HIP(ctx, hipMemsetAsync(run.vt + (size_t)D * R * es, 0, 128 * es, ctx->stream));
-  MHIP_HIP(ctx, hipMemsetAsync(run.ao, 0, R * D * es, ctx->stream));
+  if ((rc = encoder_ws_clear_slack(ctx, w, R, D, es))) return rc;
+  // the fp32 attention writes the token rows only: the padding rows of ao start as zeros
+  MHIP_HIP(ctx, hipMemsetAsync(w.ao, 0, R * D * es, ctx->stream));
   const int K0 = 3 * P * P, np = NT - 1;
-  if ((rc = mhip_launch_clipvis_patchify(ctx, prec, run.clips, B, S, P, swap_rb, CLIP_MEAN, CLIP_STD, run.hid, K0))) return rc;
+  if ((rc = mhip_launch_clipvis_patchify(ctx, prec, run.clips, B, S, P, swap_rb, CLIP_MEAN, CLIP_STD, w.hid, K0))) return rc;
   {
     ConvDesc cd;      // the patch convolution has no bias
-    cd.in = run.hid; cd.w = a.d("pe_w"); cd.out = run.pe;
+    cd.in = w.hid; cd.w = a.d("pe_w"); cd.out = run.pe;
     cd.B = 1; cd.H = 1; cd.W = B * np; cd.Cin = K0; cd.N = D; cd.out_f32 = 1;
     if ((rc = mhip_launch_conv_igemm(ctx, prec, cd))) return rc;
   }
@@ -95,20 +88,15 @@ int clipvis_forward(mhip_clipvis* m, int B, int swap_rb, const ClipRun& run, flo
     return MHIP_OK;
   };
   if ((rc = tap(0))) return rc;
-  AttnDesc ad;
-  ad.q = run.qk; ad.k = run.qk + (size_t)D * es; ad.vt = run.vt; ad.out = run.ao;
-  ad.ldq = ad.ldk = 2 * D; ad.ldv = (int)R; ad.ldo = D;
-  ad.images = B; ad.heads = c.heads; ad.npad_q = ad.npad_k = NP; ad.n_queries = ad.n_keys = NT;
+  const AttnDesc ad = encoder_attn_desc(w.qk, w.vt, w.ao, D, es, B, c.heads, NP, NT);
   for (int i = 0; i < c.depth; ++i) {
-    if ((rc = mhip_launch_clipvis_layernorm(ctx, prec, run.h, a.d<float>(blk(i, "ln1_g")), a.d<float>(blk(i, "ln1_b")), run.ht, (int)R, D, c.ln_eps))) return rc;
-    if ((rc = mhip_gemm(ctx, prec, run.ht, a.d(blk(i, "qk_w")), (long long)R, 2 * D, D, nullptr, a.d<float>(blk(i, "qk_b")), run.qk, ACT_NONE, 0))) return rc;
-    if ((rc = mhip_gemm(ctx, prec, a.d(blk(i, "v_w")), run.ht, D, (int)R, D, nullptr, nullptr, run.vt, ACT_NONE, 0))) return rc;   // V^T = W_v X^T
-    if ((rc = mhip_launch_attention(ctx, prec, ad))) return rc;
-    if ((rc = mhip_gemm(ctx, prec, run.ao, a.d(blk(i, "ao_w")), (long long)R, D, D, nullptr, a.d<float>(blk(i, "ao_b")), run.h, ACT_NONE, 1, run.h))) return rc;
-    if ((rc = mhip_launch_clipvis_layernorm(ctx, prec, run.h, a.d<float>(blk(i, "ln2_g")), a.d<float>(blk(i, "ln2_b")), run.ht, (int)R, D, c.ln_eps))) return rc;
-    if ((rc = mhip_gemm(ctx, prec, run.ht, a.d(blk(i, "fc1_w")), (long long)R, F, D, nullptr, a.d<float>(blk(i, "fc1_b")), run.hid, ACT_NONE, 0))) return rc;
-    if ((rc = mhip_launch_quick_gelu(ctx, prec, run.hid, (long long)R * F))) return rc;
-    if ((rc = mhip_gemm(ctx, prec, run.hid, a.d(blk(i, "fc2_w")), (long long)R, D, F, nullptr, a.d<float>(blk(i, "fc2_b")), run.h, ACT_NONE, 1, run.h))) return rc;
+    if ((rc = mhip_launch_clipvis_layernorm(ctx, prec, run.h, a.d<float>(enc_blk(i, "ln1_g")), a.d<float>(enc_blk(i, "ln1_b")), w.ht, (int)R, D, c.ln_eps))) return rc;
+    if ((rc = encoder_block_attention(ctx, prec, a, i, w, ad))) return rc;
+    if ((rc = mhip_gemm(ctx, prec, w.ao, a.d(enc_blk(i, "ao_w")), (long long)R, D, D, nullptr, a.d<float>(enc_blk(i, "ao_b")), run.h, ACT_NONE, 1, run.h))) return rc;
+    if ((rc = mhip_launch_clipvis_layernorm(ctx, prec, run.h, a.d<float>(enc_blk(i, "ln2_g")), a.d<float>(enc_blk(i, "ln2_b")), w.ht, (int)R, D, c.ln_eps))) return rc;
+    if ((rc = mhip_gemm(ctx, prec, w.ht, a.d(enc_blk(i, "fc1_w")), (long long)R, F, D, nullptr, a.d<float>(enc_blk(i, "fc1_b")), w.hid, ACT_NONE, 0))) return rc;
+    if ((rc = mhip_launch_quick_gelu(ctx, prec, w.hid, (long long)R * F))) return rc;
+    if ((rc = mhip_gemm(ctx, prec, w.hid, a.d(enc_blk(i, "fc2_w")), (long long)R, D, F, nullptr, a.d<float>(enc_blk(i, "fc2_b")), run.h, ACT_NONE, 1, run.h))) return rc;
     if ((rc = tap(i + 1))) return rc;
   }
   return mhip_launch_clipvis_head(ctx, run.h, B, NP, D, a.d<float>("ln_post_g"), a.d<float>("ln_post_b"), c.ln_eps, a.d<float>("proj_t"),
@@ -152,15 +140,7 @@ extern "C" int mhip_clipvis_create(mhip_ctx* ctx, int precision, const mhip_clip
   a.take("cls", D * 4);
   a.take("pos", (size_t)m->n_tok() * D * 4);
   a.take("ln_pre_g", D * 4); a.take("ln_pre_b", D * 4);
-  for (int i = 0; i < c.depth; ++i) {
-    a.take(blk(i, "ln1_g"), D * 4); a.take(blk(i, "ln1_b"), D * 4);
-    a.take(blk(i, "qk_w"), 2 * D * D * es); a.take(blk(i, "qk_b"), 2 * D * 4);
-    a.take(blk(i, "v_w"), D * D * es);
-    a.take(blk(i, "ao_w"), D * D * es); a.take(blk(i, "ao_b"), D * 4);
-    a.take(blk(i, "ln2_g"), D * 4); a.take(blk(i, "ln2_b"), D * 4);
-    a.take(blk(i, "fc1_w"), F * D * es); a.take(blk(i, "fc1_b"), F * 4);
-    a.take(blk(i, "fc2_w"), D * F * es); a.take(blk(i, "fc2_b"), D * 4);
-  }
+  for (int i = 0; i < c.depth; ++i) encoder_block_take(a, i, D, F, es);
   a.take("ln_post_g", D * 4); a.take("ln_post_b", D * 4);
   a.take("proj_t", (size_t)c.proj_dim * D * 4);
   *out = m;
@@ -203,7 +183,6 @@ extern "C" int mhip_clipvis_finalize(mhip_clipvis* m) {
   mhip_ctx* ctx = m->ctx;
   const mhip_clipvis_config& c = m->cfg;
   const int D = c.dim, F = c.ffn, prec = m->precision, NT = m->n_tok(), E = c.proj_dim, P = c.patch;
-  const size_t es = m->esz();
   Arena& a = m->arena;
   const TensorStore& st = m->store;
   a.begin_fill();
@@ -224,8 +203,6 @@ extern "C" int mhip_clipvis_finalize(mhip_clipvis* m) {
   float* pt = (float*)a.h("proj_t");
   for (int k = 0; k < D; ++k)
     for (int j = 0; j < E; ++j) pt[(size_t)j * D + k] = pj->data[(size_t)k * E + j];
-  // the score scale in the units the attention kernel takes: 1 / sqrt(64), base-2 exponent
-  const float qs = 0.125f * LOG2E;
   const size_t DD = (size_t)D * D;
   for (int i = 0; i < c.depth; ++i) {
     const HostTensor* iw = st.find(ctx, res(i, "attn.in_proj_weight"), {3 * D, D});
@@ -241,26 +218,13 @@ extern "C" int mhip_clipvis_finalize(mhip_clipvis* m) {
     const HostTensor* dw = st.find(ctx, res(i, "mlp.c_proj.weight"), {D, F});
     const HostTensor* db = st.find(ctx, res(i, "mlp.c_proj.bias"), {D});
     if (!iw || !ib || !ow || !ob || !g1 || !b1 || !g2 || !b2 || !fw || !fb || !dw || !db) return MHIP_ESTATE;
-    std::vector<float> wq(DD);
-    for (size_t e = 0; e < DD; ++e) wq[e] = iw->data[e] * qs;
-    Arena::put(prec, a.h(blk(i, "qk_w")), wq.data(), DD);
-    Arena::put(prec, a.h(blk(i, "qk_w")) + DD * es, iw->data.data() + DD, DD);
-    float* qkb = (float*)a.h(blk(i, "qk_b"));
-    for (int d = 0; d < D; ++d) { qkb[d] = ib->data[d] * qs; qkb[D + d] = ib->data[D + d]; }
-    Arena::put(prec, a.h(blk(i, "v_w")), iw->data.data() + 2 * DD, DD);
-    Arena::put(prec, a.h(blk(i, "ao_w")), ow->data.data(), DD);
-    float* aob = (float*)a.h(blk(i, "ao_b"));
-    for (int o = 0; o < D; ++o) {      // out_proj(ctx + b_v) = out_proj(ctx) + W_o b_v
-      double acc = ob->data[o];
-      for (int k = 0; k < D; ++k) acc += (double)ow->data[(size_t)o * D + k] * ib->data[2 * D + k];
-      aob[o] = (float)acc;
-    }
-    memcpy(a.h(blk(i, "ln1_g")), g1->data.data(), (size_t)D * 4); memcpy(a.h(blk(i, "ln1_b")), b1->data.data(), (size_t)D * 4);
-    memcpy(a.h(blk(i, "ln2_g")), g2->data.data(), (size_t)D * 4); memcpy(a.h(blk(i, "ln2_b")), b2->data.data(), (size_t)D * 4);
-    Arena::put(prec, a.h(blk(i, "fc1_w")), fw->data.data(), fw->numel());
-    memcpy(a.h(blk(i, "fc1_b")), fb->data.data(), (size_t)F * 4);
-    Arena::put(prec, a.h(blk(i, "fc2_w")), dw->data.data(), dw->numel());
-    memcpy(a.h(blk(i, "fc2_b")), db->data.data(), (size_t)D * 4);
+    EncoderBlockWeights w;      // in_proj holds q, k, v one after another
+    w.wq = iw->data.data(); w.wk = w.wq + DD; w.wv = w.wq + 2 * DD;
+    w.bq = ib->data.data(); w.bk = w.bq + D; w.bv = w.bq + 2 * D;
+    w.wo = ow->data.data(); w.bo = ob->data.data();
+    w.ln1_g = g1->data.data(); w.ln1_b = b1->data.data(); w.ln2_g = g2->data.data(); w.ln2_b = b2->data.data();
+    w.w1 = fw->data.data(); w.b1 = fb->data.data(); w.w2 = dw->data.data(); w.b2 = db->data.data();
+    encoder_block_fill(a, prec, i, D, F, w);
   }
   int rc = a.upload(ctx);
   if (rc) return rc;

@@ -209,6 +209,16 @@ struct ConvDesc {
 enum { EPI_NONE = 0, EPI_LN_ROWS = 1, EPI_LN_COLS = 2, EPI_SPLIT = 3 };
 // precision: MHIP_PREC_F16 / MHIP_PREC_F32.  Returns 0 or negative error.
 int mhip_launch_conv_igemm(mhip_ctx* ctx, int precision, const ConvDesc& d);
+// the plain GEMM of it:  out [M][N] = act(scale[n] * in [M][K] w [N][K]^T + bias[n] (+ res))
+inline int mhip_gemm(mhip_ctx* ctx, int prec, const void* in, const void* w, long long M, int N, int K, const float* scale,
+                     const float* bias, void* out, int act, int out_f32, const void* res = nullptr, int ldc = 0,
+                     int pad_cols_writable = 0) {
+  ConvDesc c;
+  c.in = in; c.w = w; c.scale = scale; c.bias = bias; c.out = out;
+  c.B = 1; c.H = 1; c.W = (int)M; c.Cin = K; c.N = N;
+  c.relu = act; c.out_f32 = out_f32; c.res = res; c.ldc = ldc; c.pad_cols_writable = pad_cols_writable;
+  return mhip_launch_conv_igemm(ctx, prec, c);
+}
 double mhip_conv_flops(const ConvDesc& d);
 
 // first layer: u8 [B][H][W] -> normalise -> conv3x3 pad1 (1->64) + bias + ReLU + maxpool 2x2 -> [B][H/2][W/2][64] T
@@ -297,6 +307,9 @@ int mhip_launch_ln_finalize(mhip_ctx* ctx, const float* stats, int chunks, int l
 int mhip_launch_split_f16(mhip_ctx* ctx, const float* in, void* hi, void* lo, long long n);
 int mhip_launch_join_f16(mhip_ctx* ctx, const void* hi, const void* lo, float* out, long long n);
 // (attn_flash.hip) softmax(Q K^T) V for `images` x `heads` independent (head_dim 64) problems; q is pre-scaled by head_dim^-0.5 * log2(e).
+// The last 128-query block / 64-key tile of an image may read up to 127 rows past it (and masks them): q and k — and the codes
+// of AttnBiasDesc — need ATTN_SLACK_ROWS finite rows past the last image, vt 64 finite elements (carved as ATTN_SLACK_ROWS)
+constexpr int ATTN_SLACK_ROWS = 128;
 struct AttnDesc {
   const void* q = nullptr;    // [images*npad_q][ldq] T, head h at column h*64
   const void* k = nullptr;    // [images*npad_k][ldk] T
@@ -304,8 +317,7 @@ struct AttnDesc {
   void* out = nullptr;        // [images*npad_q][ldo] T
   int ldq = 0, ldk = 0, ldv = 0, ldo = 0;
   int images = 0, heads = 0;
-  int npad_q = 0, npad_k = 0;  // rows per image (npad_k % 8 == 0).  The last 128-query block / 64-key tile of an image may
-                               // read up to 127 rows past it: q, k need that many finite rows of slack, vt 64 elements
+  int npad_q = 0, npad_k = 0;  // rows per image (npad_k % 8 == 0)
   int n_queries = 0, n_keys = 0;
 };
 int mhip_launch_attention(mhip_ctx* ctx, int precision, const AttnDesc& d);
@@ -473,8 +485,8 @@ int mhip_launch_beam_best(mhip_ctx* ctx, const BeamState& st, int* tokens_out, i
 constexpr float MHIP_ATTN_MASKED = -1024.f;    // log2 units: exp2 of it is 0 in fp32 beside any score a LayerNormed model produces
 struct AttnBiasDesc {
   AttnDesc a;
-  const uint32_t* qcode = nullptr;   // [images*npad_q (+ 128 of slack)]
-  const uint32_t* kcode = nullptr;   // [images*npad_k (+ 128 of slack)]
+  const uint32_t* qcode = nullptr;   // [images*npad_q + ATTN_SLACK_ROWS]
+  const uint32_t* kcode = nullptr;   // [images*npad_k + ATTN_SLACK_ROWS]
   const float* tab = nullptr;        // [heads][mhip_attn_bias_table_len(dp, dx)] fp32
   int dp = 0, dx = 0;                // largest |p_j - p_i| (<= 1023) and |x_j - x_i|, |y_j - y_i| (<= 1023)
 };

@@ -1,0 +1,112 @@
+// encoder_block.h — the transformer encoder layer the ViT (vit_api.hip), LayoutLMv3 (layoutlmv3_api.hip) and CLIP (clip_api.hip)
+// towers share, host side: its arena entries and how the checkpoint's weights are packed into them, its workspace, and the
+// attention half of a layer
+//   q|k = ht Wqk^T + b        V^T = Wv ht^T        ao = attention(q, k, V^T)
+// The LayerNorms, the residual wiring and the MLP activation differ between the towers and stay in the model files.
+#pragma once
+#include "weights_util.h"
+
+// head_dim^-0.5 (64 -> 1/8) and the exp -> exp2 change of base: attn_flash.hip takes its scores in these units, so the factor is
+// folded into W_q and b_q (and into LayoutLMv3's bias tables)
+constexpr float ATTN_SCORE_SCALE = 0.125f * 1.4426950408889634f;
+
+inline std::string enc_blk(int i, const char* s) { return "l" + std::to_string(i) + "." + s; }
+
+// the entries of block i every tower has (D: width, F: MLP width, es: bytes of a GEMM element)
+inline void encoder_block_take(Arena& a, int i, size_t D, size_t F, size_t es) {
+  a.take(enc_blk(i, "ln1_g"), D * 4); a.take(enc_blk(i, "ln1_b"), D * 4);
+  a.take(enc_blk(i, "qk_w"), 2 * D * D * es); a.take(enc_blk(i, "qk_b"), 2 * D * 4);
+  a.take(enc_blk(i, "v_w"), D * D * es);
+  a.take(enc_blk(i, "ao_w"), D * D * es); a.take(enc_blk(i, "ao_b"), D * 4);
+  a.take(enc_blk(i, "ln2_g"), D * 4); a.take(enc_blk(i, "ln2_b"), D * 4);
+  a.take(enc_blk(i, "fc1_w"), F * D * es); a.take(enc_blk(i, "fc1_b"), F * 4);
+  a.take(enc_blk(i, "fc2_w"), D * F * es); a.take(enc_blk(i, "fc2_b"), D * 4);
+}
+
+// one block's weights as the checkpoint holds them, fp32
+struct EncoderBlockWeights {
+  const float *wq = nullptr, *wk = nullptr, *wv = nullptr;      // [D][D] each
+  const float *bq = nullptr, *bk = nullptr, *bv = nullptr;      // [D] each; null = zeros
+  const float *wo = nullptr, *bo = nullptr;                     // output projection [D][D], [D]
+  const float *ln1_g = nullptr, *ln1_b = nullptr, *ln2_g = nullptr, *ln2_b = nullptr;
+  const float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr;      // [F][D], [F], [D][F], [D]
+};
+
+// fills the entries of encoder_block_take: q (scaled) | k back to back, v apart, and the value bias moved behind the soft-max —
+// its rows sum to one, so  W_o (ctx + b_v) + b_o = W_o ctx + (b_o + W_o b_v)
+inline void encoder_block_fill(Arena& a, int prec, int i, int D, int F, const EncoderBlockWeights& w) {
+  const size_t es = prec == MHIP_PREC_F16 ? 2 : 4, DD = (size_t)D * D;
+  const std::vector<float> zeros(D, 0.f);
+  const float *bq = w.bq ? w.bq : zeros.data(), *bk = w.bk ? w.bk : zeros.data(), *bv = w.bv ? w.bv : zeros.data();
+  std::vector<float> wq(DD);
+  for (size_t e = 0; e < DD; ++e) wq[e] = w.wq[e] * ATTN_SCORE_SCALE;
+  Arena::put(prec, a.h(enc_blk(i, "qk_w")), wq.data(), DD);
+  Arena::put(prec, a.h(enc_blk(i, "qk_w")) + DD * es, w.wk, DD);
+  float* qkb = (float*)a.h(enc_blk(i, "qk_b"));
+  for (int d = 0; d < D; ++d) { qkb[d] = bq[d] * ATTN_SCORE_SCALE; qkb[D + d] = bk[d]; }
+  Arena::put(prec, a.h(enc_blk(i, "v_w")), w.wv, DD);
+  Arena::put(prec, a.h(enc_blk(i, "ao_w")), w.wo, DD);
+  float* aob = (float*)a.h(enc_blk(i, "ao_b"));
+  for (int o = 0; o < D; ++o) {
+    double acc = w.bo[o];
+    for (int k = 0; k < D; ++k) acc += (double)w.wo[(size_t)o * D + k] * bv[k];
+    aob[o] = (float)acc;
+  }
+  memcpy(a.h(enc_blk(i, "ln1_g")), w.ln1_g, (size_t)D * 4); memcpy(a.h(enc_blk(i, "ln1_b")), w.ln1_b, (size_t)D * 4);
+  memcpy(a.h(enc_blk(i, "ln2_g")), w.ln2_g, (size_t)D * 4); memcpy(a.h(enc_blk(i, "ln2_b")), w.ln2_b, (size_t)D * 4);
+  Arena::put(prec, a.h(enc_blk(i, "fc1_w")), w.w1, (size_t)F * D);
+  memcpy(a.h(enc_blk(i, "fc1_b")), w.b1, (size_t)F * 4);
+  Arena::put(prec, a.h(enc_blk(i, "fc2_w")), w.w2, (size_t)D * F);
+  memcpy(a.h(enc_blk(i, "fc2_b")), w.b2, (size_t)D * 4);
+}
+
+// the buffers of the layers of one call of R = images * npad token rows, element type T
+struct EncoderWs {
+  char* ht = nullptr;    // [R][D] the layer's input rows (a LayerNorm's output)
+  char* qk = nullptr;    // [R + ATTN_SLACK_ROWS][2 D] q | k rows
+  char* vt = nullptr;    // [D][R] (+ ATTN_SLACK_ROWS elements) V^T
+  char* ao = nullptr;    // [R][D] attention output
+  char* hid = nullptr;   // [R][F] mlp hidden; also the patch matrix [<= R][K0]
+};
+
+inline void encoder_ws_carve(Carver& ws, size_t R, size_t D, size_t F, size_t K0, size_t es, EncoderWs* w) {
+  w->ht = ws.take(R * D * es);
+  w->qk = ws.take((R + ATTN_SLACK_ROWS) * 2 * D * es);
+  w->vt = ws.take((D * R + ATTN_SLACK_ROWS) * es);
+  w->ao = ws.take(R * D * es);
+  w->hid = ws.take(R * std::max(F, K0) * es);
+}
+
+// the slack of qk and vt is read by the last image's final tiles (and masked): keep it finite
+inline int encoder_ws_clear_slack(mhip_ctx* ctx, const EncoderWs& w, size_t R, size_t D, size_t es) {
+  MHIP_HIP(ctx, hipMemsetAsync(w.qk + R * 2 * D * es, 0, (size_t)ATTN_SLACK_ROWS * 2 * D * es, ctx->stream));
+  MHIP_HIP(ctx, hipMemsetAsync(w.vt + D * R * es, 0, ATTN_SLACK_ROWS * es, ctx->stream));
+  return MHIP_OK;
+}
+
+// self-attention of `images` sequences of n_tok tokens in npad rows each over q | k rows of pitch 2 D and V^T of pitch images * npad
+inline AttnDesc encoder_attn_desc(const void* qk, const void* vt, void* ao, int D, size_t es, int images, int heads, int npad, int n_tok) {
+  AttnDesc ad;
+  ad.q = qk; ad.k = (const char*)qk + (size_t)D * es; ad.vt = vt; ad.out = ao;
+  ad.ldq = ad.ldk = 2 * D; ad.ldv = images * npad; ad.ldo = D;
+  ad.images = images; ad.heads = heads; ad.npad_q = ad.npad_k = npad; ad.n_queries = ad.n_keys = n_tok;
+  return ad;
+}
+
+// q|k and V^T of block i from w.ht; ad is encoder_attn_desc of w's buffers, which carries D (ldo) and R (ldv)
+inline int encoder_block_qkv(mhip_ctx* ctx, int prec, const Arena& a, int i, const EncoderWs& w, const AttnDesc& ad) {
+  const int D = ad.ldo, R = ad.ldv;
+  int rc;
+  if ((rc = mhip_gemm(ctx, prec, w.ht, a.d(enc_blk(i, "qk_w")), R, 2 * D, D, nullptr, a.d<float>(enc_blk(i, "qk_b")), w.qk, ACT_NONE, 0))) return rc;
+  return mhip_gemm(ctx, prec, a.d(enc_blk(i, "v_w")), w.ht, D, R, D, nullptr, nullptr, w.vt, ACT_NONE, 0);   // V^T = W_v X^T
+}
+
+// the attention half of block i, w.ht -> w.ao: plain, or with LayoutLMv3's bias and key mask (bd.a the descriptor)
+inline int encoder_block_attention(mhip_ctx* ctx, int prec, const Arena& a, int i, const EncoderWs& w, const AttnDesc& ad) {
+  const int rc = encoder_block_qkv(ctx, prec, a, i, w, ad);
+  return rc ? rc : mhip_launch_attention(ctx, prec, ad);
+}
+inline int encoder_block_attention(mhip_ctx* ctx, int prec, const Arena& a, int i, const EncoderWs& w, const AttnBiasDesc& bd) {
+  const int rc = encoder_block_qkv(ctx, prec, a, i, w, bd.a);
+  return rc ? rc : mhip_launch_attention_bias(ctx, prec, bd);
+}

@@ -18,7 +18,7 @@
 //   hid = gelu(ht Wi^T + bi)           y = hid Wd^T + bd + h              h, ht = LN(y)
 #include <math.h>
 
-#include "vit_internal.h"
+#include "encoder_block.h"
 
 struct mhip_layoutlmv3 {
   mhip_ctx* ctx = nullptr;
@@ -40,7 +40,6 @@ struct mhip_layoutlmv3 {
 
 namespace {
 
-constexpr float LOG2E = 1.4426950408889634f;
 // classifier.dense + classifier.out_proj (sequence classification; token classification with num_labels >= 10), or one
 // classifier.weight (token classification with num_labels < 10)
 enum { HEAD_DENSE = 0, HEAD_LINEAR = 1 };
@@ -48,7 +47,6 @@ enum { TASK_CLASSIFY = 0, TASK_TAG = 1 };
 const char* PFX = "layoutlmv3.";
 
 std::string lyr(int i, const char* s) { return "layoutlmv3.encoder.layer." + std::to_string(i) + "." + s; }
-std::string blk(int i, const char* s) { return "l" + std::to_string(i) + "." + s; }
 
 // the buffers of one call of n windows over n_pages pages
 struct Lmv3Run {
@@ -58,7 +56,7 @@ struct Lmv3Run {
   int *tok = nullptr, *win_page = nullptr, *labels = nullptr;
   uint32_t *qcode = nullptr, *kcode = nullptr;
   float *pe = nullptr, *h = nullptr, *y = nullptr, *logits = nullptr, *scores = nullptr, *dense = nullptr;
-  char *ht = nullptr, *qk = nullptr, *vt = nullptr, *ao = nullptr, *hid = nullptr;
+  EncoderWs w;      // w.hid is also the patch matrix (n_pages <= n, fewer rows than R)
 };
 
 // task: TASK_CLASSIFY (logits [n][labels]) or TASK_TAG (labels / scores [n][max_text]; token logits when want_logits; the
@@ -72,8 +70,8 @@ void lmv3_carve(const mhip_layoutlmv3* m, Carver& ws, const mhip_crop_desc* page
   r->frag_scratch = ws.take(r->frag_bytes);
   r->tok = ws.take<int>((size_t)n * c.max_text * 8 * 4);
   r->win_page = ws.take<int>((size_t)n * 4);
-  r->qcode = ws.take<uint32_t>((R + 128) * 4);     // + slack: the last page's final query block / key tile reads past its rows
-  r->kcode = ws.take<uint32_t>((R + 128) * 4);
+  r->qcode = ws.take<uint32_t>((R + ATTN_SLACK_ROWS) * 4);
+  r->kcode = ws.take<uint32_t>((R + ATTN_SLACK_ROWS) * 4);
   r->pe = ws.take<float>((size_t)n_pages * NPAT * D * 4);
   r->h = ws.take<float>(R * D * 4);
   r->y = ws.take<float>(R * D * 4);
@@ -86,11 +84,7 @@ void lmv3_carve(const mhip_layoutlmv3* m, Carver& ws, const mhip_crop_desc* page
     r->logits = want_logits ? ws.take<float>(TR * c.num_labels * 4) : nullptr;
     r->dense = m->head == HEAD_DENSE ? ws.take<float>(TR * D * 4) : nullptr;
   }
-  r->ht = ws.take(R * D * es);
-  r->qk = ws.take((R + 128) * 2 * D * es);
-  r->vt = ws.take((D * R + 128) * es);
-  r->ao = ws.take(R * D * es);
-  r->hid = ws.take(R * std::max<size_t>(c.ffn, K0) * es);     // mlp hidden; also the patch matrix (n_pages <= n, fewer rows than R)
+  encoder_ws_carve(ws, R, D, c.ffn, K0, es, &r->w);
 }
 
 // token ids / boxes / mask of n pages -> the embedding kernel's gather rows and the attention codes (host)
@@ -100,8 +94,8 @@ int lmv3_prepare(mhip_layoutlmv3* m, int n, const int32_t* ids, const int32_t* b
   const int T = c.max_text, NP = m->npad(), G = m->grid(), NV = m->n_vis(), M2 = c.max_2d_position_embeddings;
   const uint32_t masked = (uint32_t)(2 * m->dp() + 1);
   tok.assign((size_t)n * T * 8, 0);
-  qcode.assign((size_t)n * NP + 128, 0);
-  kcode.assign((size_t)n * NP + 128, masked);
+  qcode.assign((size_t)n * NP + ATTN_SLACK_ROWS, 0);
+  kcode.assign((size_t)n * NP + ATTN_SLACK_ROWS, masked);
   for (int p = 0; p < n; ++p) {
     int seen = 0;
     for (int t = 0; t < T; ++t) {
@@ -135,23 +129,22 @@ int lmv3_prepare(mhip_layoutlmv3* m, int n, const int32_t* ids, const int32_t* b
   return MHIP_OK;
 }
 
-// pages already resized in run.resized; codes and the window -> page map staged -> hidden states of n windows in run.h / run.ht
+// pages already resized in run.resized; codes and the window -> page map staged -> hidden states of n windows in run.h / run.w.ht
 int lmv3_forward(mhip_layoutlmv3* m, int n_pages, int n, const Lmv3Run& run) {
   mhip_ctx* ctx = m->ctx;
   const mhip_layoutlmv3_config& c = m->cfg;
   const int D = c.hidden, F = c.ffn, prec = m->precision, NP = m->npad(), G = m->grid(), P = c.patch, S = c.input_size;
   const size_t es = m->esz(), R = (size_t)n * NP;
   const Arena& a = m->arena;
+  const EncoderWs& w = run.w;
   int rc;
-  // rows / columns past the last page are read by its final tiles (and masked): keep them finite
-  MHIP_HIP(ctx, hipMemsetAsync(run.qk + R * 2 * D * es, 0, (size_t)128 * 2 * D * es, ctx->stream));
-  MHIP_HIP(ctx, hipMemsetAsync(run.vt + (size_t)D * R * es, 0, 128 * es, ctx->stream));
+  if ((rc = encoder_ws_clear_slack(ctx, w, R, D, es))) return rc;
   // (x / 255 - 0.5) / 0.5 -> 16 x 16 patches -> projection + bias + position rows 1.. (row q takes position row q % G^2)
   const int K0 = 3 * P * P, np = G * G;
-  if ((rc = mhip_launch_patchify(ctx, prec, run.resized, n_pages, S, S, G, G, P, 0, 127.5f, 127.5f, run.hid, K0))) return rc;
+  if ((rc = mhip_launch_patchify(ctx, prec, run.resized, n_pages, S, S, G, G, P, 0, 127.5f, 127.5f, w.hid, K0))) return rc;
   {
     ConvDesc cd;
-    cd.in = run.hid; cd.w = a.d("pe_w"); cd.bias = a.d<float>("pe_b"); cd.out = run.pe; cd.res = a.d<float>("pos_vis");
+    cd.in = w.hid; cd.w = a.d("pe_w"); cd.bias = a.d<float>("pe_b"); cd.out = run.pe; cd.res = a.d<float>("pos_vis");
     cd.B = 1; cd.H = 1; cd.W = n_pages * np; cd.Cin = K0; cd.N = D; cd.out_f32 = 1;
     cd.row_period = np; cd.row_stride = np; cd.row_offset = 0;
     if ((rc = mhip_launch_conv_igemm(ctx, prec, cd))) return rc;
@@ -163,25 +156,21 @@ int lmv3_forward(mhip_layoutlmv3* m, int n_pages, int n, const Lmv3Run& run) {
   e.patches = run.pe; e.cls = a.d<float>("cls");
   e.g_vis = a.d<float>("ln_vis_g"); e.b_vis = a.d<float>("ln_vis_b");
   e.g_all = a.d<float>("ln_all_g"); e.b_all = a.d<float>("ln_all_b");
-  e.h = run.h; e.ht = run.ht;
+  e.h = run.h; e.ht = w.ht;
   e.pages = n; e.max_text = c.max_text; e.n_vis = m->n_vis(); e.npad = NP; e.D = D; e.coord = c.coordinate_size; e.shape = c.shape_size;
   e.eps = c.layer_norm_eps; e.eps_vis = 1e-6f;      // LayoutLMv3Model.norm = nn.LayerNorm(hidden, eps=1e-6)
   if ((rc = mhip_launch_lmv3_embed(ctx, prec, e))) return rc;
 
   AttnBiasDesc ad;
-  ad.a.q = run.qk; ad.a.k = run.qk + (size_t)D * es; ad.a.vt = run.vt; ad.a.out = run.ao;
-  ad.a.ldq = ad.a.ldk = 2 * D; ad.a.ldv = (int)R; ad.a.ldo = D;
-  ad.a.images = n; ad.a.heads = c.heads; ad.a.npad_q = ad.a.npad_k = NP; ad.a.n_queries = ad.a.n_keys = m->seq();
+  ad.a = encoder_attn_desc(w.qk, w.vt, w.ao, D, es, n, c.heads, NP, m->seq());
   ad.qcode = run.qcode; ad.kcode = run.kcode; ad.tab = a.d<float>("bias_tab"); ad.dp = m->dp(); ad.dx = m->dx();
   for (int i = 0; i < c.layers; ++i) {
-    if ((rc = mhip_gemm(ctx, prec, run.ht, a.d(blk(i, "qk_w")), (long long)R, 2 * D, D, nullptr, a.d<float>(blk(i, "qk_b")), run.qk, ACT_NONE, 0))) return rc;
-    if ((rc = mhip_gemm(ctx, prec, a.d(blk(i, "v_w")), run.ht, D, (int)R, D, nullptr, nullptr, run.vt, ACT_NONE, 0))) return rc;   // V^T = W_v X^T
-    if ((rc = mhip_launch_attention_bias(ctx, prec, ad))) return rc;
-    if ((rc = mhip_gemm(ctx, prec, run.ao, a.d(blk(i, "ao_w")), (long long)R, D, D, nullptr, a.d<float>(blk(i, "ao_b")), run.y, ACT_NONE, 1, run.h))) return rc;
-    if ((rc = mhip_launch_layernorm2(ctx, prec, run.y, a.d<float>(blk(i, "ln1_g")), a.d<float>(blk(i, "ln1_b")), run.h, run.ht, (int)R, D, c.layer_norm_eps))) return rc;
-    if ((rc = mhip_gemm(ctx, prec, run.ht, a.d(blk(i, "fc1_w")), (long long)R, F, D, nullptr, a.d<float>(blk(i, "fc1_b")), run.hid, ACT_GELU, 0))) return rc;
-    if ((rc = mhip_gemm(ctx, prec, run.hid, a.d(blk(i, "fc2_w")), (long long)R, D, F, nullptr, a.d<float>(blk(i, "fc2_b")), run.y, ACT_NONE, 1, run.h))) return rc;
-    if ((rc = mhip_launch_layernorm2(ctx, prec, run.y, a.d<float>(blk(i, "ln2_g")), a.d<float>(blk(i, "ln2_b")), run.h, run.ht, (int)R, D, c.layer_norm_eps))) return rc;
+    if ((rc = encoder_block_attention(ctx, prec, a, i, w, ad))) return rc;
+    if ((rc = mhip_gemm(ctx, prec, w.ao, a.d(enc_blk(i, "ao_w")), (long long)R, D, D, nullptr, a.d<float>(enc_blk(i, "ao_b")), run.y, ACT_NONE, 1, run.h))) return rc;
+    if ((rc = mhip_launch_layernorm2(ctx, prec, run.y, a.d<float>(enc_blk(i, "ln1_g")), a.d<float>(enc_blk(i, "ln1_b")), run.h, w.ht, (int)R, D, c.layer_norm_eps))) return rc;
+    if ((rc = mhip_gemm(ctx, prec, w.ht, a.d(enc_blk(i, "fc1_w")), (long long)R, F, D, nullptr, a.d<float>(enc_blk(i, "fc1_b")), w.hid, ACT_GELU, 0))) return rc;
+    if ((rc = mhip_gemm(ctx, prec, w.hid, a.d(enc_blk(i, "fc2_w")), (long long)R, D, F, nullptr, a.d<float>(enc_blk(i, "fc2_b")), run.y, ACT_NONE, 1, run.h))) return rc;
+    if ((rc = mhip_launch_layernorm2(ctx, prec, run.y, a.d<float>(enc_blk(i, "ln2_g")), a.d<float>(enc_blk(i, "ln2_b")), run.h, w.ht, (int)R, D, c.layer_norm_eps))) return rc;
   }
   return MHIP_OK;
 }
@@ -206,7 +195,7 @@ int lmv3_head_tokens(mhip_layoutlmv3* m, int n, const Lmv3Run& run) {
   if (m->head == HEAD_DENSE) {
     // dense on the text rows only, in the model's precision, fp32 out; tanh belongs to the head kernel
     for (int w = 0; w < n; ++w)
-      if ((rc = mhip_gemm(m->ctx, m->precision, run.ht + (size_t)w * NP * D * m->esz(), a.d("cdt_w"), T, D, D, nullptr, a.d<float>("cd_b"),
+      if ((rc = mhip_gemm(m->ctx, m->precision, run.w.ht + (size_t)w * NP * D * m->esz(), a.d("cdt_w"), T, D, D, nullptr, a.d<float>("cd_b"),
                           run.dense + (size_t)w * T * D, ACT_NONE, 1)))
         return rc;
     t.x = run.dense; t.seg_stride = T; t.use_tanh = 1;
@@ -364,15 +353,7 @@ extern "C" int mhip_layoutlmv3_create(mhip_ctx* ctx, int precision, const mhip_l
   a.take("pos_vis", (size_t)(m->n_vis() - 1) * D * 4);
   a.take("cls", D * 4);
   a.take("bias_tab", (size_t)c.heads * mhip_attn_bias_table_len(m->dp(), m->dx()) * 4);
-  for (int i = 0; i < c.layers; ++i) {
-    a.take(blk(i, "qk_w"), 2 * D * D * es); a.take(blk(i, "qk_b"), 2 * D * 4);
-    a.take(blk(i, "v_w"), D * D * es);
-    a.take(blk(i, "ao_w"), D * D * es); a.take(blk(i, "ao_b"), D * 4);
-    a.take(blk(i, "ln1_g"), D * 4); a.take(blk(i, "ln1_b"), D * 4);
-    a.take(blk(i, "fc1_w"), F * D * es); a.take(blk(i, "fc1_b"), F * 4);
-    a.take(blk(i, "fc2_w"), D * F * es); a.take(blk(i, "fc2_b"), D * 4);
-    a.take(blk(i, "ln2_g"), D * 4); a.take(blk(i, "ln2_b"), D * 4);
-  }
+  for (int i = 0; i < c.layers; ++i) encoder_block_take(a, i, D, F, es);
   // the head: dense (fp32 for the row-0 head, the element type for the token head's GEMM) + out_proj, or — in the out_proj
   // entries — the linear token head; which of the two, for the ranks that receive the arena filled
   a.take("cd_w", D * D * 4); a.take("cd_b", D * 4);
@@ -430,7 +411,6 @@ extern "C" int mhip_layoutlmv3_finalize(mhip_layoutlmv3* m) {
   mhip_ctx* ctx = m->ctx;
   const mhip_layoutlmv3_config& c = m->cfg;
   const int D = c.hidden, F = c.ffn, prec = m->precision, M2 = c.max_2d_position_embeddings, NV = m->n_vis();
-  const size_t es = m->esz();
   Arena& a = m->arena;
   const TensorStore& st = m->store;
   a.begin_fill();
@@ -483,9 +463,8 @@ extern "C" int mhip_layoutlmv3_finalize(mhip_layoutlmv3* m) {
   memcpy(a.h("pos_vis"), pv->data.data() + D, (size_t)(NV - 1) * D * 4);
   for (int d = 0; d < D; ++d) ((float*)a.h("cls"))[d] = cls->data[d] + pv->data[d];
   // the three bias matrices folded into difference-indexed tables, in the units of the scores (1 / sqrt(64), base-2 exponent)
-  const float qs = 0.125f * LOG2E;
   mhip_attn_bias_fold(r1->data.data(), rx->data.data(), ry->data.data(), c.heads, c.rel_pos_bins, c.max_rel_pos, c.rel_2d_pos_bins,
-                      c.max_rel_2d_pos, m->dp(), m->dx(), qs, (float*)a.h("bias_tab"));
+                      c.max_rel_2d_pos, m->dp(), m->dx(), ATTN_SCORE_SCALE, (float*)a.h("bias_tab"));
   for (int i = 0; i < c.layers; ++i) {
     const HostTensor* qw = st.find(ctx, lyr(i, "attention.self.query.weight"), {D, D});
     const HostTensor* qb = st.find(ctx, lyr(i, "attention.self.query.bias"), {D});
@@ -504,26 +483,13 @@ extern "C" int mhip_layoutlmv3_finalize(mhip_layoutlmv3* m) {
     const HostTensor* g2 = st.find(ctx, lyr(i, "output.LayerNorm.weight"), {D});
     const HostTensor* b2 = st.find(ctx, lyr(i, "output.LayerNorm.bias"), {D});
     if (!qw || !qb || !kw || !kb || !vw || !vb || !ow || !ob || !g1 || !b1 || !iw || !ib || !dw || !db || !g2 || !b2) return MHIP_ESTATE;
-    std::vector<float> wq((size_t)D * D);
-    for (size_t e = 0; e < wq.size(); ++e) wq[e] = qw->data[e] * qs;
-    Arena::put(prec, a.h(blk(i, "qk_w")), wq.data(), wq.size());
-    Arena::put(prec, a.h(blk(i, "qk_w")) + (size_t)D * D * es, kw->data.data(), kw->numel());
-    float* qkb = (float*)a.h(blk(i, "qk_b"));
-    for (int d = 0; d < D; ++d) { qkb[d] = qb->data[d] * qs; qkb[D + d] = kb->data[d]; }
-    Arena::put(prec, a.h(blk(i, "v_w")), vw->data.data(), vw->numel());
-    Arena::put(prec, a.h(blk(i, "ao_w")), ow->data.data(), ow->numel());
-    float* aob = (float*)a.h(blk(i, "ao_b"));
-    for (int o = 0; o < D; ++o) {      // dense(ctx + b_v) = dense(ctx) + W_o b_v
-      double acc = ob->data[o];
-      for (int k = 0; k < D; ++k) acc += (double)ow->data[(size_t)o * D + k] * vb->data[k];
-      aob[o] = (float)acc;
-    }
-    memcpy(a.h(blk(i, "ln1_g")), g1->data.data(), D * 4); memcpy(a.h(blk(i, "ln1_b")), b1->data.data(), D * 4);
-    Arena::put(prec, a.h(blk(i, "fc1_w")), iw->data.data(), iw->numel());
-    memcpy(a.h(blk(i, "fc1_b")), ib->data.data(), (size_t)F * 4);
-    Arena::put(prec, a.h(blk(i, "fc2_w")), dw->data.data(), dw->numel());
-    memcpy(a.h(blk(i, "fc2_b")), db->data.data(), D * 4);
-    memcpy(a.h(blk(i, "ln2_g")), g2->data.data(), D * 4); memcpy(a.h(blk(i, "ln2_b")), b2->data.data(), D * 4);
+    EncoderBlockWeights w;      // post-LN: ln1 follows the attention, ln2 the MLP
+    w.wq = qw->data.data(); w.wk = kw->data.data(); w.wv = vw->data.data();
+    w.bq = qb->data.data(); w.bk = kb->data.data(); w.bv = vb->data.data();
+    w.wo = ow->data.data(); w.bo = ob->data.data();
+    w.ln1_g = g1->data.data(); w.ln1_b = b1->data.data(); w.ln2_g = g2->data.data(); w.ln2_b = b2->data.data();
+    w.w1 = iw->data.data(); w.b1 = ib->data.data(); w.w2 = dw->data.data(); w.b2 = db->data.data();
+    encoder_block_fill(a, prec, i, D, F, w);
   }
   if (!linear) {
     memcpy(a.h("cd_w"), cdw->data.data(), cdw->numel() * 4); memcpy(a.h("cd_b"), cdb->data.data(), D * 4);
@@ -709,25 +675,24 @@ extern "C" int mhip_attention_bias_host(mhip_ctx* ctx, int precision, int heads,
   const size_t es = precision == MHIP_PREC_F16 ? 2 : 4, D = (size_t)heads * 64, NP = ((size_t)n_tok + 7) / 8 * 8;
   const int tl = mhip_attn_bias_table_len(dp, dx);
   // operands in the element type and with the pitches the model uses: q | k rows, V^T, zero slack
-  std::vector<char> qk((NP + 128) * 2 * D * es, 0), vt((D * NP + 128) * es, 0);
-  const float qs = 0.125f * LOG2E;
+  std::vector<char> qk((NP + ATTN_SLACK_ROWS) * 2 * D * es, 0), vt((D * NP + ATTN_SLACK_ROWS) * es, 0);
   auto put = [&](char* dst, size_t at, float val) {
     if (es == 2) ((_Float16*)dst)[at] = (_Float16)val; else ((float*)dst)[at] = val;
   };
   for (size_t t = 0; t < (size_t)n_tok; ++t)
     for (size_t d = 0; d < D; ++d) {
-      put(qk.data(), t * 2 * D + d, q[t * D + d] * qs);
+      put(qk.data(), t * 2 * D + d, q[t * D + d] * ATTN_SCORE_SCALE);
       put(qk.data(), t * 2 * D + D + d, k[t * D + d]);
       put(vt.data(), d * NP + t, v[t * D + d]);
     }
-  std::vector<uint32_t> qcode(NP + 128, 0), kcode(NP + 128, (uint32_t)(2 * dp + 1));
+  std::vector<uint32_t> qcode(NP + ATTN_SLACK_ROWS, 0), kcode(NP + ATTN_SLACK_ROWS, (uint32_t)(2 * dp + 1));
   for (int t = 0; t < n_tok; ++t) {
     const uint32_t xy = ((uint32_t)x[t] << 12) | ((uint32_t)y[t] << 22);
     qcode[t] = (uint32_t)pos[t] | xy;
     kcode[t] = (valid[t] ? (uint32_t)pos[t] : (uint32_t)(2 * dp + 1)) | xy;
   }
   std::vector<float> tab((size_t)heads * tl);
-  mhip_attn_bias_fold(w1, wx, wy, heads, bins_1d, max_1d, bins_2d, max_2d, dp, dx, qs, tab.data());
+  mhip_attn_bias_fold(w1, wx, wy, heads, bins_1d, max_1d, bins_2d, max_2d, dp, dx, ATTN_SCORE_SCALE, tab.data());
   char *dqk = nullptr, *dvt = nullptr, *dao = nullptr;
   uint32_t *dqc = nullptr, *dkc = nullptr;
   float *dtab = nullptr, *dout = nullptr;
@@ -744,9 +709,7 @@ extern "C" int mhip_attention_bias_host(mhip_ctx* ctx, int precision, int heads,
   MHIP_HIP(ctx, hipMemcpyAsync(dtab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
   MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the sources are host temporaries in pageable memory
   AttnBiasDesc ad;
-  ad.a.q = dqk; ad.a.k = dqk + D * es; ad.a.vt = dvt; ad.a.out = dao;
-  ad.a.ldq = ad.a.ldk = (int)(2 * D); ad.a.ldv = (int)NP; ad.a.ldo = (int)D;
-  ad.a.images = 1; ad.a.heads = heads; ad.a.npad_q = ad.a.npad_k = (int)NP; ad.a.n_queries = ad.a.n_keys = n_tok;
+  ad.a = encoder_attn_desc(dqk, dvt, dao, (int)D, es, 1, heads, (int)NP, n_tok);
   ad.qcode = dqc; ad.kcode = dkc; ad.tab = dtab; ad.dp = dp; ad.dx = dx;
   if ((rc = mhip_launch_attention_bias(ctx, precision, ad))) return rc;
   if ((rc = mhip_launch_convert_rows(ctx, precision, dao, dout, n_tok, (int)D))) return rc;

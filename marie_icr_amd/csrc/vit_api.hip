@@ -11,25 +11,9 @@
 
 namespace {
 
-constexpr float LOG2E = 1.4426950408889634f;
-
-int gemm(mhip_ctx* ctx, int prec, const void* in, const void* w, long long M, int N, int K, const float* scale,
-         const float* bias, void* out, int act, int out_f32, const void* res = nullptr, int ldc = 0, int pad_ok = 0) {
-  ConvDesc c;
-  c.in = in; c.w = w; c.scale = scale; c.bias = bias; c.out = out;
-  c.B = 1; c.H = 1; c.W = (int)M; c.Cin = K; c.N = N;
-  c.relu = act; c.out_f32 = out_f32; c.res = res; c.ldc = ldc; c.pad_cols_writable = pad_ok;
-  return mhip_launch_conv_igemm(ctx, prec, c);
-}
-
-std::string blk(int i, const char* s) { return "blocks." + std::to_string(i) + "." + s; }
+std::string key(int i, const char* s) { return "blocks." + std::to_string(i) + "." + s; }      // of the checkpoint
 
 }  // namespace
-
-int mhip_gemm(mhip_ctx* ctx, int prec, const void* in, const void* w, long long M, int N, int K, const float* scale,
-              const float* bias, void* out, int act, int out_f32, const void* res, int ldc, int pad_ok) {
-  return gemm(ctx, prec, in, w, M, N, K, scale, bias, out, act, out_f32, res, ldc, pad_ok);
-}
 
 // ---------------------------------------------------------------------------------------------------- lifecycle
 extern "C" int mhip_vit_create(mhip_ctx* ctx, int precision, const mhip_vit_config* cfg, mhip_vit** out) {
@@ -53,9 +37,9 @@ extern "C" int mhip_vit_create(mhip_ctx* ctx, int precision, const mhip_vit_conf
   if (m->fold) {
     a.take("cls_stats", D / 64 * 2 * 4);
     for (int i = 0; i < cfg->depth; ++i) {
-      a.take(blk(i, "qk_cs"), 2 * D * 4);
-      a.take(blk(i, "v_cs"), D * 4); a.take(blk(i, "v_rb"), D * 4);
-      a.take(blk(i, "fc1_cs"), 4 * D * 4);
+      a.take(enc_blk(i, "qk_cs"), 2 * D * 4);
+      a.take(enc_blk(i, "v_cs"), D * 4); a.take(enc_blk(i, "v_rb"), D * 4);
+      a.take(enc_blk(i, "fc1_cs"), 4 * D * 4);
     }
   }
   a.take("pe_w", D * K0 * es);
@@ -63,13 +47,8 @@ extern "C" int mhip_vit_create(mhip_ctx* ctx, int precision, const mhip_vit_conf
   a.take("pos", (size_t)cfg->pos_h * cfg->pos_w * D * 4);
   a.take("cls", D * 4);
   for (int i = 0; i < cfg->depth; ++i) {
-    a.take(blk(i, "ln1_g"), D * 4); a.take(blk(i, "ln1_b"), D * 4);
-    a.take(blk(i, "qk_w"), 2 * D * D * es); a.take(blk(i, "qk_b"), 2 * D * 4);
-    a.take(blk(i, "v_w"), D * D * es);
-    a.take(blk(i, "proj_w"), D * D * es); a.take(blk(i, "proj_s"), D * 4); a.take(blk(i, "proj_b"), D * 4);
-    a.take(blk(i, "ln2_g"), D * 4); a.take(blk(i, "ln2_b"), D * 4);
-    a.take(blk(i, "fc1_w"), 4 * D * D * es); a.take(blk(i, "fc1_b"), 4 * D * 4);
-    a.take(blk(i, "fc2_w"), 4 * D * D * es); a.take(blk(i, "fc2_s"), D * 4); a.take(blk(i, "fc2_b"), D * 4);
+    encoder_block_take(a, i, D, 4 * D, es);
+    a.take(enc_blk(i, "proj_s"), D * 4); a.take(enc_blk(i, "fc2_s"), D * 4);      // layer scale
   }
   if (cfg->final_norm) { a.take("norm_g", D * 4); a.take("norm_b", D * 4); }
   if (cfg->fpn)
@@ -163,63 +142,47 @@ extern "C" int mhip_vit_finalize(mhip_vit* m) {
       cst[c * 2] = sm; cst[c * 2 + 1] = m2;
     }
   }
-  const float qs = 0.125f * LOG2E;   // head_dim^-0.5 (64 -> 1/8) and the exp -> exp2 change of base, folded into W_q
   for (int i = 0; i < c.depth; ++i) {
-    const HostTensor* g1 = st.find(ctx, blk(i, "norm1.weight"), {D});
-    const HostTensor* b1 = st.find(ctx, blk(i, "norm1.bias"), {D});
-    const HostTensor* qkv = st.find(ctx, blk(i, "attn.qkv.weight"), {3 * D, D});
-    const HostTensor* pjw = st.find(ctx, blk(i, "attn.proj.weight"), {D, D});
-    const HostTensor* pjb = st.find(ctx, blk(i, "attn.proj.bias"), {D});
-    const HostTensor* g2 = st.find(ctx, blk(i, "norm2.weight"), {D});
-    const HostTensor* b2 = st.find(ctx, blk(i, "norm2.bias"), {D});
-    const HostTensor* f1w = st.find(ctx, blk(i, "mlp.fc1.weight"), {4 * D, D});
-    const HostTensor* f1b = st.find(ctx, blk(i, "mlp.fc1.bias"), {4 * D});
-    const HostTensor* f2w = st.find(ctx, blk(i, "mlp.fc2.weight"), {D, 4 * D});
-    const HostTensor* f2b = st.find(ctx, blk(i, "mlp.fc2.bias"), {D});
+    const HostTensor* g1 = st.find(ctx, key(i, "norm1.weight"), {D});
+    const HostTensor* b1 = st.find(ctx, key(i, "norm1.bias"), {D});
+    const HostTensor* qkv = st.find(ctx, key(i, "attn.qkv.weight"), {3 * D, D});
+    const HostTensor* pjw = st.find(ctx, key(i, "attn.proj.weight"), {D, D});
+    const HostTensor* pjb = st.find(ctx, key(i, "attn.proj.bias"), {D});
+    const HostTensor* g2 = st.find(ctx, key(i, "norm2.weight"), {D});
+    const HostTensor* b2 = st.find(ctx, key(i, "norm2.bias"), {D});
+    const HostTensor* f1w = st.find(ctx, key(i, "mlp.fc1.weight"), {4 * D, D});
+    const HostTensor* f1b = st.find(ctx, key(i, "mlp.fc1.bias"), {4 * D});
+    const HostTensor* f2w = st.find(ctx, key(i, "mlp.fc2.weight"), {D, 4 * D});
+    const HostTensor* f2b = st.find(ctx, key(i, "mlp.fc2.bias"), {D});
     if (!g1 || !b1 || !qkv || !pjw || !pjb || !g2 || !b2 || !f1w || !f1b || !f2w || !f2b) return MHIP_ESTATE;
-    std::vector<float> qb(D, 0.f), kb(D, 0.f), vb(D, 0.f);
+    const size_t DD = (size_t)D * D;
+    EncoderBlockWeights w;
+    w.wq = qkv->data.data(); w.wk = w.wq + DD; w.wv = w.wq + 2 * DD;
     if (c.qkv_bias == 1) {
-      const HostTensor* q = st.find(ctx, blk(i, "attn.q_bias"), {D});
-      const HostTensor* v = st.find(ctx, blk(i, "attn.v_bias"), {D});
+      const HostTensor* q = st.find(ctx, key(i, "attn.q_bias"), {D});
+      const HostTensor* v = st.find(ctx, key(i, "attn.v_bias"), {D});
       if (!q || !v) return MHIP_ESTATE;
-      qb = q->data; vb = v->data;
+      w.bq = q->data.data(); w.bv = v->data.data();
     } else if (c.qkv_bias == 2) {
-      const HostTensor* b = st.find(ctx, blk(i, "attn.qkv.bias"), {3 * D});
+      const HostTensor* b = st.find(ctx, key(i, "attn.qkv.bias"), {3 * D});
       if (!b) return MHIP_ESTATE;
-      qb.assign(b->data.begin(), b->data.begin() + D);
-      kb.assign(b->data.begin() + D, b->data.begin() + 2 * D);
-      vb.assign(b->data.begin() + 2 * D, b->data.end());
+      w.bq = b->data.data(); w.bk = w.bq + D; w.bv = w.bq + 2 * D;
     }
     std::vector<float> gam1(D, 1.f), gam2(D, 1.f);
     if (c.layer_scale) {
-      const HostTensor* ga = st.find(ctx, blk(i, "gamma_1"), {D});
-      const HostTensor* gb = st.find(ctx, blk(i, "gamma_2"), {D});
+      const HostTensor* ga = st.find(ctx, key(i, "gamma_1"), {D});
+      const HostTensor* gb = st.find(ctx, key(i, "gamma_2"), {D});
       if (!ga || !gb) return MHIP_ESTATE;
       gam1 = ga->data; gam2 = gb->data;
     }
-    memcpy(a.h(blk(i, "ln1_g")), g1->data.data(), D * 4);
-    memcpy(a.h(blk(i, "ln1_b")), b1->data.data(), D * 4);
-    memcpy(a.h(blk(i, "ln2_g")), g2->data.data(), D * 4);
-    memcpy(a.h(blk(i, "ln2_b")), b2->data.data(), D * 4);
-    std::vector<float> wq((size_t)D * D);
-    for (size_t e = 0; e < wq.size(); ++e) wq[e] = qkv->data[e] * qs;
-    Arena::put(prec, a.h(blk(i, "qk_w")), wq.data(), wq.size());
-    Arena::put(prec, a.h(blk(i, "qk_w")) + (size_t)D * D * es, qkv->data.data() + (size_t)D * D, (size_t)D * D);
-    float* qkb = (float*)a.h(blk(i, "qk_b"));
-    for (int d = 0; d < D; ++d) { qkb[d] = qb[d] * qs; qkb[D + d] = kb[d]; }
-    Arena::put(prec, a.h(blk(i, "v_w")), qkv->data.data() + (size_t)2 * D * D, (size_t)D * D);
-    Arena::put(prec, a.h(blk(i, "proj_w")), pjw->data.data(), pjw->numel());
-    // softmax rows sum to one, so the value bias passes through attention unchanged:  proj(o + b_v) = proj(o) + W_p b_v
-    float* ps = (float*)a.h(blk(i, "proj_s"));
-    float* pbb = (float*)a.h(blk(i, "proj_b"));
-    for (int o = 0; o < D; ++o) {
-      double acc = pjb->data[o];
-      for (int k = 0; k < D; ++k) acc += (double)pjw->data[(size_t)o * D + k] * vb[k];
-      ps[o] = gam1[o];
-      pbb[o] = (float)acc * gam1[o];
-    }
-    Arena::put(prec, a.h(blk(i, "fc1_w")), f1w->data.data(), f1w->numel());
-    memcpy(a.h(blk(i, "fc1_b")), f1b->data.data(), (size_t)4 * D * 4);
+    w.wo = pjw->data.data(); w.bo = pjb->data.data();
+    w.ln1_g = g1->data.data(); w.ln1_b = b1->data.data(); w.ln2_g = g2->data.data(); w.ln2_b = b2->data.data();
+    w.w1 = f1w->data.data(); w.b1 = f1b->data.data(); w.w2 = f2w->data.data(); w.b2 = f2b->data.data();
+    encoder_block_fill(a, prec, i, D, 4 * D, w);
+    // layer scale: the residual GEMMs' epilogue is scale * acc + bias
+    float *ps = (float*)a.h(enc_blk(i, "proj_s")), *pbb = (float*)a.h(enc_blk(i, "ao_b"));
+    float *fs = (float*)a.h(enc_blk(i, "fc2_s")), *fb = (float*)a.h(enc_blk(i, "fc2_b"));
+    for (int o = 0; o < D; ++o) { ps[o] = gam1[o]; pbb[o] = pbb[o] * gam1[o]; fs[o] = gam2[o]; fb[o] = fb[o] * gam2[o]; }
     if (m->fold) {
       // LayerNorm folded around its consumer GEMMs:  LN(x) W^T + b = rstd (x (g*W)^T - mean colsum(g*W)) + (b + W beta).
       // The column sums are those of the ROUNDED folded weights — what the matrix cores multiply — so that the mean term cancels
@@ -242,21 +205,17 @@ extern "C" int mhip_vit_finalize(mhip_vit* m) {
         Arena::put(prec, w_dst, wf.data(), wf.size());
       };
       std::vector<float> bd((size_t)4 * D);
-      float* qkcs = (float*)a.h(blk(i, "qk_cs"));
-      fold_rows(qkv->data.data(), D, g1->data, b1->data, qs, a.h(blk(i, "qk_w")), qkcs, bd.data());
+      float *qkb = (float*)a.h(enc_blk(i, "qk_b")), *qkcs = (float*)a.h(enc_blk(i, "qk_cs"));
+      fold_rows(qkv->data.data(), D, g1->data, b1->data, ATTN_SCORE_SCALE, a.h(enc_blk(i, "qk_w")), qkcs, bd.data());
       for (int d = 0; d < D; ++d) qkb[d] += bd[d];
-      fold_rows(qkv->data.data() + (size_t)D * D, D, g1->data, b1->data, 1.f, a.h(blk(i, "qk_w")) + (size_t)D * D * es, qkcs + D, bd.data());
+      fold_rows(qkv->data.data() + (size_t)D * D, D, g1->data, b1->data, 1.f, a.h(enc_blk(i, "qk_w")) + (size_t)D * D * es, qkcs + D, bd.data());
       for (int d = 0; d < D; ++d) qkb[D + d] += bd[d];
-      fold_rows(qkv->data.data() + (size_t)2 * D * D, D, g1->data, b1->data, 1.f, a.h(blk(i, "v_w")), (float*)a.h(blk(i, "v_cs")),
-                (float*)a.h(blk(i, "v_rb")));
-      fold_rows(f1w->data.data(), 4 * D, g2->data, b2->data, 1.f, a.h(blk(i, "fc1_w")), (float*)a.h(blk(i, "fc1_cs")), bd.data());
-      float* f1bb = (float*)a.h(blk(i, "fc1_b"));
+      fold_rows(qkv->data.data() + (size_t)2 * D * D, D, g1->data, b1->data, 1.f, a.h(enc_blk(i, "v_w")), (float*)a.h(enc_blk(i, "v_cs")),
+                (float*)a.h(enc_blk(i, "v_rb")));
+      fold_rows(f1w->data.data(), 4 * D, g2->data, b2->data, 1.f, a.h(enc_blk(i, "fc1_w")), (float*)a.h(enc_blk(i, "fc1_cs")), bd.data());
+      float* f1bb = (float*)a.h(enc_blk(i, "fc1_b"));
       for (int d = 0; d < 4 * D; ++d) f1bb[d] += bd[d];
     }
-    Arena::put(prec, a.h(blk(i, "fc2_w")), f2w->data.data(), f2w->numel());
-    float* fs = (float*)a.h(blk(i, "fc2_s"));
-    float* fb = (float*)a.h(blk(i, "fc2_b"));
-    for (int o = 0; o < D; ++o) { fs[o] = gam2[o]; fb[o] = f2b->data[o] * gam2[o]; }
   }
   if (c.final_norm) {
     const HostTensor* g = st.find(ctx, "norm.weight", {D});
@@ -307,11 +266,7 @@ void vit_geometry(const mhip_vit* m, int H32, int W32, VitGeom* g) {
 void vit_carve(const mhip_vit* m, Carver& ws, int B, const VitGeom& g, VitRun* run) {
   const size_t es = m->esz(), D = m->cfg.dim, R = (size_t)B * g.npad;
   run->x = ws.take(R * D * 4);                  // fp32 stream, or f16 / the two f16 planes in its bytes
-  run->ln = ws.take(R * D * es);
-  run->qk = ws.take((R + 128) * 2 * D * es);    // + slack: the last image's final query block / key tile reads past its rows
-  run->vt = ws.take((D * R + 128) * es);        // + slack, likewise
-  run->ao = ws.take(R * D * es);
-  run->hid = ws.take(R * 4 * D * es);
+  encoder_ws_carve(ws, R, D, 4 * D, 3 * m->cfg.patch * m->cfg.patch, es, &run->w);
   if (m->fold) {
     run->stats = ws.take<float>(D / 64 * R * 8);
     run->rstd = ws.take<float>(R * 4);
@@ -357,14 +312,10 @@ int vit_encode(mhip_vit* m, const uint8_t* imgs, int B, int th, int tw, int H32,
   }
   const size_t R = (size_t)B * g.npad;
   void* x = run->x;
-  char* ln = run->ln;
-  char* qk = run->qk;
-  char* vt = run->vt;
-  // rows / columns past the last image are read by its final tiles (and masked): keep them finite
-  MHIP_HIP(ctx, hipMemsetAsync(qk + R * 2 * D * es, 0, (size_t)128 * 2 * D * es, ctx->stream));
-  MHIP_HIP(ctx, hipMemsetAsync(vt + (size_t)D * R * es, 0, 128 * es, ctx->stream));
-  char* ao = run->ao;
-  char* hid = run->hid;
+  const EncoderWs& w = run->w;
+  char *ln = w.ht, *qk = w.qk, *vt = w.vt, *ao = w.ao, *hid = w.hid;
+  int rc;
+  if ((rc = encoder_ws_clear_slack(ctx, w, R, D, es))) return rc;
   const bool fold = m->fold;     // implies the f16 mode without an f16 stream (mhip_vit_create)
   const int chunks = D / 64;
   char* xlo = fold ? (char*)x + R * D * 2 : nullptr;          // the split stream: two f16 planes in the bytes of the fp32 one
@@ -372,7 +323,6 @@ int vit_encode(mhip_vit* m, const uint8_t* imgs, int B, int th, int tw, int H32,
   float* stats = run->stats;
   float* rstd = run->rstd;
   float* mur = run->mur;
-  int rc;
   // patches -> hid (as the [B*np][768] patch matrix) -> x rows 1.. with bias + resized position table
   const int K0 = 3 * P * P;
   {   // all images at once: row q of the patch matrix -> token row (q / np) * npad + 1 + q % np, + position row q % np
@@ -403,50 +353,37 @@ int vit_encode(mhip_vit* m, const uint8_t* imgs, int B, int th, int tw, int H32,
     c.epi = EPI_LN_ROWS; c.ln_a = rstd; c.ln_b = mur; c.ln_cs = cs;
     return mhip_launch_conv_igemm(ctx, prec, c);
   };
-  int tap_at = 0;
+  const AttnDesc ad = encoder_attn_desc(qk, vt, ao, D, es, B, c.heads, g.npad, g.n_tok);
   for (int i = 0; i < c.depth; ++i) {
     if (fold) {
       if ((rc = mhip_launch_ln_finalize(ctx, stats, chunks, (int)R, rstd, mur, (int)R, D, c.ln_eps))) return rc;
-      if ((rc = consume_rows(a.d(blk(i, "qk_w")), 2 * D, a.d<float>(blk(i, "qk_cs")), a.d<float>(blk(i, "qk_b")), qk, ACT_NONE))) return rc;
+      if ((rc = consume_rows(a.d(enc_blk(i, "qk_w")), 2 * D, a.d<float>(enc_blk(i, "qk_cs")), a.d<float>(enc_blk(i, "qk_b")), qk, ACT_NONE))) return rc;
       ConvDesc cv;      // V^T = W_v LN(X)^T: the tokens are the GEMM's columns
-      cv.in = a.d(blk(i, "v_w")); cv.w = x; cv.out = vt;
+      cv.in = a.d(enc_blk(i, "v_w")); cv.w = x; cv.out = vt;
       cv.B = 1; cv.H = 1; cv.W = D; cv.Cin = D; cv.N = (int)R;
-      cv.epi = EPI_LN_COLS; cv.ln_a = rstd; cv.ln_b = mur; cv.ln_cs = a.d<float>(blk(i, "v_cs")); cv.row_bias = a.d<float>(blk(i, "v_rb"));
+      cv.epi = EPI_LN_COLS; cv.ln_a = rstd; cv.ln_b = mur; cv.ln_cs = a.d<float>(enc_blk(i, "v_cs")); cv.row_bias = a.d<float>(enc_blk(i, "v_rb"));
       if ((rc = mhip_launch_conv_igemm(ctx, prec, cv))) return rc;
-    } else {
-    if ((rc = mhip_launch_layernorm(ctx, prec, x, a.d<float>(blk(i, "ln1_g")), a.d<float>(blk(i, "ln1_b")), ln, (int)R, D, c.ln_eps, x16))) return rc;
-    if ((rc = gemm(ctx, prec, ln, a.d(blk(i, "qk_w")), (long long)R, 2 * D, D, nullptr, a.d<float>(blk(i, "qk_b")), qk, ACT_NONE, 0))) return rc;
-    if ((rc = gemm(ctx, prec, a.d(blk(i, "v_w")), ln, D, (int)R, D, nullptr, nullptr, vt, ACT_NONE, 0))) return rc;   // V^T = W_v X^T
-    }
-    AttnDesc ad;
-    ad.q = qk; ad.k = qk + (size_t)D * es; ad.vt = vt; ad.out = ao;
-    ad.ldq = ad.ldk = 2 * D; ad.ldv = (int)R; ad.ldo = D;
-    ad.images = B; ad.heads = c.heads; ad.npad_q = ad.npad_k = g.npad; ad.n_queries = ad.n_keys = g.n_tok;
-    if ((rc = mhip_launch_attention(ctx, prec, ad))) return rc;
-    if (fold) {
-      if ((rc = produce(ao, a.d(blk(i, "proj_w")), D, a.d<float>(blk(i, "proj_s")), a.d<float>(blk(i, "proj_b"))))) return rc;
+      if ((rc = mhip_launch_attention(ctx, prec, ad))) return rc;
+      if ((rc = produce(ao, a.d(enc_blk(i, "ao_w")), D, a.d<float>(enc_blk(i, "proj_s")), a.d<float>(enc_blk(i, "ao_b"))))) return rc;
       if ((rc = mhip_launch_ln_finalize(ctx, stats, chunks, (int)R, rstd, mur, (int)R, D, c.ln_eps))) return rc;
-      if ((rc = consume_rows(a.d(blk(i, "fc1_w")), 4 * D, a.d<float>(blk(i, "fc1_cs")), a.d<float>(blk(i, "fc1_b")), hid, ACT_GELU))) return rc;
-      if ((rc = produce(hid, a.d(blk(i, "fc2_w")), 4 * D, a.d<float>(blk(i, "fc2_s")), a.d<float>(blk(i, "fc2_b"))))) return rc;
+      if ((rc = consume_rows(a.d(enc_blk(i, "fc1_w")), 4 * D, a.d<float>(enc_blk(i, "fc1_cs")), a.d<float>(enc_blk(i, "fc1_b")), hid, ACT_GELU))) return rc;
+      if ((rc = produce(hid, a.d(enc_blk(i, "fc2_w")), 4 * D, a.d<float>(enc_blk(i, "fc2_s")), a.d<float>(enc_blk(i, "fc2_b"))))) return rc;
     } else {
-    if ((rc = gemm(ctx, prec, ao, a.d(blk(i, "proj_w")), (long long)R, D, D, a.d<float>(blk(i, "proj_s")), a.d<float>(blk(i, "proj_b")), x, ACT_NONE, x16 ? 0 : 1, x))) return rc;
-    if ((rc = mhip_launch_layernorm(ctx, prec, x, a.d<float>(blk(i, "ln2_g")), a.d<float>(blk(i, "ln2_b")), ln, (int)R, D, c.ln_eps, x16))) return rc;
-    if ((rc = gemm(ctx, prec, ln, a.d(blk(i, "fc1_w")), (long long)R, 4 * D, D, nullptr, a.d<float>(blk(i, "fc1_b")), hid, ACT_GELU, 0))) return rc;
-    if ((rc = gemm(ctx, prec, hid, a.d(blk(i, "fc2_w")), (long long)R, D, 4 * D, a.d<float>(blk(i, "fc2_s")), a.d<float>(blk(i, "fc2_b")), x, ACT_NONE, x16 ? 0 : 1, x))) return rc;
+      if ((rc = mhip_launch_layernorm(ctx, prec, x, a.d<float>(enc_blk(i, "ln1_g")), a.d<float>(enc_blk(i, "ln1_b")), ln, (int)R, D, c.ln_eps, x16))) return rc;
+      if ((rc = encoder_block_attention(ctx, prec, a, i, w, ad))) return rc;
+      if ((rc = mhip_gemm(ctx, prec, ao, a.d(enc_blk(i, "ao_w")), (long long)R, D, D, a.d<float>(enc_blk(i, "proj_s")), a.d<float>(enc_blk(i, "ao_b")), x, ACT_NONE, x16 ? 0 : 1, x))) return rc;
+      if ((rc = mhip_launch_layernorm(ctx, prec, x, a.d<float>(enc_blk(i, "ln2_g")), a.d<float>(enc_blk(i, "ln2_b")), ln, (int)R, D, c.ln_eps, x16))) return rc;
+      if ((rc = mhip_gemm(ctx, prec, ln, a.d(enc_blk(i, "fc1_w")), (long long)R, 4 * D, D, nullptr, a.d<float>(enc_blk(i, "fc1_b")), hid, ACT_GELU, 0))) return rc;
+      if ((rc = mhip_gemm(ctx, prec, hid, a.d(enc_blk(i, "fc2_w")), (long long)R, D, 4 * D, a.d<float>(enc_blk(i, "fc2_s")), a.d<float>(enc_blk(i, "fc2_b")), x, ACT_NONE, x16 ? 0 : 1, x))) return rc;
     }
     if (c.fpn)
-      for (int j = 0; j < 4; ++j)
-        if (c.taps[j] == i) {
-          // a map in f16 of a split stream is its high plane (hi = f16(x))
-          if ((rc = mhip_launch_tokens_to_map(ctx, prec, x, run->tap[j], B, g.npad, g.np, D, x16 || fold))) return rc;
-          ++tap_at;
-        }
+      for (int j = 0; j < 4; ++j)      // a map in f16 of a split stream is its high plane (hi = f16(x))
+        if (c.taps[j] == i && (rc = mhip_launch_tokens_to_map(ctx, prec, x, run->tap[j], B, g.npad, g.np, D, x16 || fold))) return rc;
   }
   if (c.final_norm) {
     if (!run->tokens_dst) MHIP_HIP(ctx, hipMemsetAsync(run->tokens + R * D * es, 0, (size_t)64 * D * es, ctx->stream));
     if ((rc = mhip_launch_layernorm(ctx, prec, x, a.d<float>("norm_g"), a.d<float>("norm_b"), run->tokens, (int)R, D, c.ln_eps, x16 || fold, xlo))) return rc;
   }
-  (void)tap_at;
   return MHIP_OK;
 }
 
@@ -471,9 +408,9 @@ int vit_fpn(mhip_vit* m, int B, const VitRun& run, VitFpnOut* out) {
   char* o1 = out->level[0];
   char* o2 = out->level[1];
   int rc;
-  if ((rc = gemm(ctx, prec, run.tap[0], a.d("f1a_w"), M, 4 * D, D, a.d<float>("f1a_s"), a.d<float>("f1a_b"), t1, ACT_GELU, 0))) return rc;
-  if ((rc = gemm(ctx, prec, t1, a.d("f1b_w"), 4 * M, 4 * D, D, a.d<float>("f1b_s"), a.d<float>("f1b_b"), o1, ACT_NONE, 0))) return rc;
-  if ((rc = gemm(ctx, prec, run.tap[1], a.d("f2_w"), M, 4 * D, D, a.d<float>("f2_s"), a.d<float>("f2_b"), o2, ACT_NONE, 0))) return rc;
+  if ((rc = mhip_gemm(ctx, prec, run.tap[0], a.d("f1a_w"), M, 4 * D, D, a.d<float>("f1a_s"), a.d<float>("f1a_b"), t1, ACT_GELU, 0))) return rc;
+  if ((rc = mhip_gemm(ctx, prec, t1, a.d("f1b_w"), 4 * M, 4 * D, D, a.d<float>("f1b_s"), a.d<float>("f1b_b"), o1, ACT_NONE, 0))) return rc;
+  if ((rc = mhip_gemm(ctx, prec, run.tap[1], a.d("f2_w"), M, 4 * D, D, a.d<float>("f2_s"), a.d<float>("f2_b"), o2, ACT_NONE, 0))) return rc;
   out->nest[0] = 2;
   out->nest[1] = 1;
   out->level[2] = run.tap[2]; out->nest[2] = 0;
@@ -512,26 +449,24 @@ extern "C" int mhip_vit_forward_host(mhip_vit* m, const uint8_t* imgs_host, int 
   MHIP_HIP(ctx, hipMemcpyAsync(imgs, imgs_host, img_bytes, hipMemcpyHostToDevice, ctx->stream));
   if ((rc = vit_encode(m, imgs, B, th, tw, H32, W32, swap_rb, &run))) return rc;
   if (tokens_out) {
-    // final tokens (after the last norm if configured, else the residual stream), valid rows only
+    // final tokens (after the last norm if configured, else the residual stream), valid rows only; what is not fp32 already
+    // goes through the staging buffer
+    const bool x16 = m->x16 && m->precision == MHIP_PREC_F16;
     for (int b = 0; b < B; ++b) {
+      const size_t row = (size_t)b * g.npad * D;
+      const float* src = stage;
       if (m->cfg.final_norm) {
-        if ((rc = mhip_launch_convert_rows(ctx, m->precision, run.tokens + (size_t)b * g.npad * D * m->esz(), stage, g.n_tok, (int)D))) return rc;
-        MHIP_HIP(ctx, hipMemcpyAsync(tokens_out + (size_t)b * g.n_tok * D, stage, (size_t)g.n_tok * D * 4, hipMemcpyDeviceToHost, ctx->stream));
-        MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        rc = mhip_launch_convert_rows(ctx, m->precision, run.tokens + row * m->esz(), stage, g.n_tok, (int)D);
+      } else if (run.x_lo) {      // split stream: hi + lo
+        rc = mhip_launch_join_f16(ctx, (const char*)run.x + row * 2, (const char*)run.x_lo + row * 2, stage, (long long)g.n_tok * D);
+      } else if (x16) {           // f16 stream: widen
+        rc = mhip_launch_convert_rows(ctx, m->precision, (const char*)run.x + row * 2, stage, g.n_tok, (int)D);
       } else {
-        if (run.x_lo) {      // split stream: hi + lo through the staging buffer
-          const size_t o = (size_t)b * g.npad * D * 2;
-          if ((rc = mhip_launch_join_f16(ctx, (const char*)run.x + o, (const char*)run.x_lo + o, stage, (long long)g.n_tok * D))) return rc;
-          MHIP_HIP(ctx, hipMemcpyAsync(tokens_out + (size_t)b * g.n_tok * D, stage, (size_t)g.n_tok * D * 4, hipMemcpyDeviceToHost, ctx->stream));
-          MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        } else if (m->x16 && m->precision == MHIP_PREC_F16) {      // f16 stream: widen through the staging buffer
-          if ((rc = mhip_launch_convert_rows(ctx, m->precision, (const char*)run.x + (size_t)b * g.npad * D * 2, stage, g.n_tok, (int)D))) return rc;
-          MHIP_HIP(ctx, hipMemcpyAsync(tokens_out + (size_t)b * g.n_tok * D, stage, (size_t)g.n_tok * D * 4, hipMemcpyDeviceToHost, ctx->stream));
-          MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        } else {
-          MHIP_HIP(ctx, hipMemcpyAsync(tokens_out + (size_t)b * g.n_tok * D, (const float*)run.x + (size_t)b * g.npad * D, (size_t)g.n_tok * D * 4, hipMemcpyDeviceToHost, ctx->stream));
-        }
+        src = (const float*)run.x + row;
       }
+      if (rc) return rc;
+      MHIP_HIP(ctx, hipMemcpyAsync(tokens_out + (size_t)b * g.n_tok * D, src, (size_t)g.n_tok * D * 4, hipMemcpyDeviceToHost, ctx->stream));
+      if (src == stage) MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the next image takes the staging buffer
     }
   }
   if (m->cfg.fpn) {

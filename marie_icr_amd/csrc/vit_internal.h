@@ -1,6 +1,6 @@
 // vit_internal.h — the ViT encoder object as the composite models (DiT detector, TrOCR recognizer) see it.
 #pragma once
-#include "weights_util.h"
+#include "encoder_block.h"
 
 struct mhip_vit {
   mhip_ctx* ctx = nullptr;
@@ -33,11 +33,7 @@ struct VitRun {
   VitGeom g;
   void* x = nullptr;          // residual stream [B*npad][D]: fp32, or f16 when the model keeps an f16 stream, or (split) the high plane
   void* x_lo = nullptr;       // split stream: the low plane
-  char* ln = nullptr;         // LayerNorm output
-  char* qk = nullptr;         // q | k rows
-  char* vt = nullptr;         // V^T
-  char* ao = nullptr;         // attention output
-  char* hid = nullptr;        // mlp hidden; also the patch matrix
+  EncoderWs w;                // the layers' buffers; w.ht is the LayerNorm output
   float* stats = nullptr;     // split stream: row statistics per 64-column chunk, rstd, mean * rstd
   float* rstd = nullptr;
   float* mur = nullptr;
@@ -61,6 +57,3 @@ void vit_fpn_carve(const mhip_vit* m, Carver& ws, int B, const VitGeom& g, VitFp
 // imgs: B device images u8 [th][tw][3] placed on a zero canvas H32 x W32 (after normalisation); run carved by vit_carve
 int vit_encode(mhip_vit* m, const uint8_t* imgs, int B, int th, int tw, int H32, int W32, int swap_rb, VitRun* run);
 int vit_fpn(mhip_vit* m, int B, const VitRun& run, VitFpnOut* out);
-
-int mhip_gemm(mhip_ctx* ctx, int prec, const void* in, const void* w, long long M, int N, int K, const float* scale,
-              const float* bias, void* out, int act, int out_f32, const void* res = nullptr, int ldc = 0, int pad_cols_writable = 0);
