@@ -280,6 +280,11 @@ int mhip_craft_boxes_host(mhip_ctx* ctx, const float* scores_host, int H, int W,
  * than the three above is MHIP_EINVAL. */
 int mhip_pil_resize_rgb_host(mhip_ctx* ctx, const uint8_t* src_host, int sh, int sw, uint8_t* dst_host, int dh, int dw,
                              int filter);
+/* The batched form TrOCR and LayoutLMv3 run (n fragments of different sizes -> n images of one size, one launch per pass), on
+ * host buffers: fragment i is descs[i] (channels 3) inside base_host [base_bytes] -> dst_host u8 [n][dh][dw][3], each image
+ * what Image.fromarray(fragment).resize((dw, dh), filter) gives. */
+int mhip_pil_resize_fragments_host(mhip_ctx* ctx, const uint8_t* base_host, size_t base_bytes, const mhip_crop_desc* descs, int n,
+                                   int dh, int dw, int filter, uint8_t* dst_host);
 
 /* ---- ViT encoder: the DiT detector backbone (BEiT + fpn1..4) and the TrOCR image encoder ------------------------- */
 /* replaces: BEiT.forward_features, marie/boxes/dit/ditod/beit.py:706-748 (dit_base_patch16 :787-800, dit_large_patch16

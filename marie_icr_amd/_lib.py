@@ -71,6 +71,7 @@ _SIGNATURES = (
                                    _vp, _i, C.POINTER(_i)]),
     ("mhip_crop_batch", _i, [_vp, _vp, _vp, _i, _i, _vp]),
     ("mhip_pil_resize_rgb_host", _i, [_vp, _vp, _i, _i, _vp, _i, _i, _i]),
+    ("mhip_pil_resize_fragments_host", _i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, _vp]),
     ("mhip_vit_create", _i, [_vp, _i, _vp, C.POINTER(_vp)]),
     ("mhip_vit_destroy", _i, [_vp]),
     ("mhip_vit_set_tensor", _i, [_vp, C.c_char_p, _vp, C.POINTER(C.c_int64), _i]),

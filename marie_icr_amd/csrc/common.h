@@ -157,6 +157,42 @@ void mhip_prof_end(mhip_ctx* ctx, int kid, hipEvent_t e0);
     if (_e != hipSuccess) return mhip_fail((ctx), MHIP_EHIP, what " launch: %s", hipGetErrorString(_e));    \
   } while (0)
 
+// Grow-only device buffer owned by a model handle (staging that must not hipMalloc in steady state).
+struct DevBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  template <typename T = char>
+  T* as() const { return (T*)p; }
+  // at least `need` bytes: growing drains ctx->stream first (work in flight may read the old allocation); the size is recorded
+  // only once the new allocation stands
+  int ensure(mhip_ctx* ctx, size_t need) {
+    if (need <= bytes) return MHIP_OK;
+    MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    release();
+    MHIP_HIP(ctx, hipMalloc(&p, need));
+    bytes = need;
+    return MHIP_OK;
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+};
+
+// The host entries' upload: fn(dev) on a temporary device copy of `bytes` of host memory (`what` names it in the failure
+// message); ctx->stream is drained and the copy freed on every path.
+template <typename F>
+int mhip_with_upload(mhip_ctx* ctx, const void* host, size_t bytes, const char* what, F&& fn) {
+  uint8_t* dev = nullptr;
+  hipError_t e = hipMalloc((void**)&dev, bytes);
+  if (e == hipSuccess) e = hipMemcpy(dev, host, bytes, hipMemcpyHostToDevice);
+  const int rc = e == hipSuccess ? fn((const uint8_t*)dev) : mhip_fail(ctx, MHIP_EHIP, "%s upload (%zu bytes): %s", what, bytes, hipGetErrorString(e));
+  (void)hipStreamSynchronize(ctx->stream);
+  (void)hipFree(dev);
+  return rc;
+}
+
 // ------------------------------------------------------------------ conv / GEMM launcher
 // Implicit-GEMM convolution over NHWC activations:  out[m][n] = act( scale[n] * sum_k A[m][k] W[n][k] + bias[n] )
 // with A[m][k] = in[b][y+dy-pad][x+dx-pad][c], k = (dy*KW+dx)*Cin + c, and an optional max-pool
@@ -437,6 +473,9 @@ struct CrossAbsorbDesc {
   int ldo = 0;
   int crops = 0, beam = 1, heads = 0;
 };
+// finite rows E needs behind its last crop: the kernel walks a crop's keys in tiles of up to 32 rows (TK, cross_attn.hip) and reads,
+// masked, past n_keys; two tiles' worth
+constexpr int CROSS_ATTN_SLACK_ROWS = 64;
 bool mhip_cross_absorb_supported(int enc_dim, int beam, int heads);
 int mhip_launch_cross_absorbed(mhip_ctx* ctx, const CrossAbsorbDesc& d);
 struct BeamCandDesc {

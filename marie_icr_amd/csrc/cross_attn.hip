@@ -76,6 +76,7 @@ struct CrossArgs {
 #endif
 constexpr int TK = CA_TK;   // keys per tile: 32 (two 16-key row tiles, K = 32 in the second product) or 16 (one, K = 16)
 static_assert(TK == 16 || TK == 32, "cross_attn key tile");
+static_assert(TK <= CROSS_ATTN_SLACK_ROWS, "the last key tile of the last crop stays inside the slack rows of E");
 constexpr int RT = TK / 16;
 // ring slots that fit beside the score-exchange buffer (2 W waves x 2 KiB) in 160 KiB of LDS
 constexpr int cross_slots(int ed, int w) {

@@ -464,20 +464,12 @@ static int dit_detect_host(mhip_dit* m, const uint8_t* pages_host, int B, int h,
   if (!m || !pages_host || !boxes_host || !counts_host) return MHIP_EINVAL;
   mhip_ctx* ctx = m->ctx;
   MHIP_HIP(ctx, hipSetDevice(ctx->device));
-  uint8_t* dev = nullptr;
   const size_t pb = (size_t)h * w * 3;
-  MHIP_HIP(ctx, hipMalloc((void**)&dev, pb * B));
-  hipError_t e = hipMemcpyAsync(dev, pages_host, pb * B, hipMemcpyHostToDevice, ctx->stream);
-  int rc = MHIP_OK;
-  if (e != hipSuccess) rc = mhip_fail(ctx, MHIP_EHIP, "page upload: %s", hipGetErrorString(e));
-  if (!rc) {
+  return mhip_with_upload(ctx, pages_host, pb * B, "page", [&](const uint8_t* dev) {
     std::vector<const uint8_t*> ptrs(B);
     for (int b = 0; b < B; ++b) ptrs[b] = dev + pb * b;
-    rc = dit_run(m, ptrs.data(), B, h, w, boxes_host, scores_host, classes_host, counts_host, nullptr);
-  }
-  (void)hipStreamSynchronize(ctx->stream);
-  (void)hipFree(dev);
-  return rc;
+    return dit_run(m, ptrs.data(), B, h, w, boxes_host, scores_host, classes_host, counts_host, nullptr);
+  });
 }
 
 extern "C" int mhip_dit_detect_host(mhip_dit* m, const uint8_t* pages_host, int B, int h, int w, float* boxes_host,
@@ -497,21 +489,12 @@ extern "C" int mhip_dit_debug_host(mhip_dit* m, const uint8_t* page_host, int h,
   if (!m || !page_host || !boxes_host || !count_host) return MHIP_EINVAL;
   mhip_ctx* ctx = m->ctx;
   MHIP_HIP(ctx, hipSetDevice(ctx->device));
-  uint8_t* dev = nullptr;
-  const size_t pb = (size_t)h * w * 3;
-  MHIP_HIP(ctx, hipMalloc((void**)&dev, pb));
-  hipError_t e = hipMemcpy(dev, page_host, pb, hipMemcpyHostToDevice);
-  int rc = e == hipSuccess ? MHIP_OK : mhip_fail(ctx, MHIP_EHIP, "page upload: %s", hipGetErrorString(e));
-  if (!rc) {
-    DitDebug d;
-    d.fpn[0] = p2; d.fpn[1] = p3; d.fpn[2] = p4; d.fpn[3] = p5; d.fpn[4] = p6;
-    d.prop_boxes = prop_boxes; d.prop_scores = prop_scores; d.prop_count = prop_count;
-    const uint8_t* ptr = dev;
-    rc = dit_run(m, &ptr, 1, h, w, boxes_host, scores_host, nullptr, count_host, &d);
-  }
-  (void)hipStreamSynchronize(ctx->stream);
-  (void)hipFree(dev);
-  return rc;
+  DitDebug d;
+  d.fpn[0] = p2; d.fpn[1] = p3; d.fpn[2] = p4; d.fpn[3] = p5; d.fpn[4] = p6;
+  d.prop_boxes = prop_boxes; d.prop_scores = prop_scores; d.prop_count = prop_count;
+  return mhip_with_upload(ctx, page_host, (size_t)h * w * 3, "page", [&](const uint8_t* dev) {
+    return dit_run(m, &dev, 1, h, w, boxes_host, scores_host, nullptr, count_host, &d);
+  });
 }
 
 // same, plus the inputs of the two discrete stages (RPN selection, FastRCNN inference) as this run computed them: the
@@ -522,24 +505,15 @@ extern "C" int mhip_dit_debug_taps_host(mhip_dit* m, const uint8_t* page_host, i
   if (!m || !page_host || !boxes_host || !count_host) return MHIP_EINVAL;
   mhip_ctx* ctx = m->ctx;
   MHIP_HIP(ctx, hipSetDevice(ctx->device));
-  uint8_t* dev = nullptr;
-  const size_t pb = (size_t)h * w * 3;
-  MHIP_HIP(ctx, hipMalloc((void**)&dev, pb));
-  hipError_t e = hipMemcpy(dev, page_host, pb, hipMemcpyHostToDevice);
-  int rc = e == hipSuccess ? MHIP_OK : mhip_fail(ctx, MHIP_EHIP, "page upload: %s", hipGetErrorString(e));
-  if (!rc) {
-    DitDebug d;
-    for (int l = 0; l < 5; ++l) {
-      if (fpn5) d.fpn[l] = fpn5[l];
-      if (rpn_head5) d.rpn_head[l] = rpn_head5[l];
-    }
-    d.prop_boxes = prop_boxes; d.prop_scores = prop_scores; d.prop_count = prop_count; d.box_head = box_head;
-    const uint8_t* ptr = dev;
-    rc = dit_run(m, &ptr, 1, h, w, boxes_host, scores_host, nullptr, count_host, &d);
+  DitDebug d;
+  for (int l = 0; l < 5; ++l) {
+    if (fpn5) d.fpn[l] = fpn5[l];
+    if (rpn_head5) d.rpn_head[l] = rpn_head5[l];
   }
-  (void)hipStreamSynchronize(ctx->stream);
-  (void)hipFree(dev);
-  return rc;
+  d.prop_boxes = prop_boxes; d.prop_scores = prop_scores; d.prop_count = prop_count; d.box_head = box_head;
+  return mhip_with_upload(ctx, page_host, (size_t)h * w * 3, "page", [&](const uint8_t* dev) {
+    return dit_run(m, &dev, 1, h, w, boxes_host, scores_host, nullptr, count_host, &d);
+  });
 }
 
 // replaces: blackout_bboxes, marie/boxes/dit/ulim_dit_box_processor.py:161-198 — in place on a device page (BGR);

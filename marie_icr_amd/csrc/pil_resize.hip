@@ -10,83 +10,30 @@
 // A tiny kernel builds the two coefficient tables on the device (IEEE double, contraction off — the same arithmetic as
 // the C code); the passes are pure integer MACs, 3 interleaved channels per thread.  LANCZOS takes its sin from the device
 // library where Pillow takes it from the host libm: no rounded coefficient has been seen to move (DESIGN.md §3 pil_resize).
-#include <math.h>
-
 #include <algorithm>
 #include <vector>
 
-#include "common.h"
+#include "pil_resample.h"   // the arithmetic, and #pragma clang fp contract(off) for everything below
 
 namespace {
 
-constexpr int PRECISION_BITS = 32 - 8 - 2;
-
-#pragma clang fp contract(off)
-// the filter supports of Resample.c: lanczos 3, bilinear 1, bicubic 2
-__host__ __device__ __forceinline__ double support_of(int filter) {
-  return filter == MHIP_PIL_LANCZOS ? 3.0 : (filter == MHIP_PIL_BILINEAR ? 1.0 : 2.0);
+// ---- the three kernel bodies; the index type I is long long for a whole page, int for a batch of fragments ---------------
+// one row of the tables: bounds = {xmin, n}, kk[x] = fixed-point weight of tap x (0 beyond n)
+__device__ __forceinline__ void coeffs_row(int in_size, int out_size, int xx, int filter, int ksize, int* __restrict__ bounds,
+                                           int* __restrict__ kk) {
+  const PilWindow win = window(filter, in_size, out_size, xx);
+  for (int x = 0; x < ksize; ++x) kk[x] = x < win.n ? fixed_weight(filter, win, x) : 0;
+  bounds[0] = win.xmin;
+  bounds[1] = win.n;
 }
 
-// sinc_filter of Resample.c
-__device__ __forceinline__ double sinc(double x) {
-  if (x == 0.0) return 1.0;
-  x = x * M_PI;
-  return sin(x) / x;
-}
-
-__device__ __forceinline__ double filt(int filter, double x) {
-  if (x < 0.0) x = -x;
-  if (filter == MHIP_PIL_BILINEAR) return x < 1.0 ? 1.0 - x : 0.0;
-  if (filter == MHIP_PIL_LANCZOS) return x < 3.0 ? sinc(x) * sinc(x / 3) : 0.0;      // lanczos_filter: the truncated sinc
-  const double a = -0.5;
-  if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-  if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-  return 0.0;
-}
-
-// bounds[2*xx] = xmin, bounds[2*xx+1] = n ; kk[xx*ksize + x] = fixed-point weight
-__global__ void pil_coeffs_kernel(int in_size, int out_size, int filter, int ksize, int* __restrict__ bounds,
-                                  int* __restrict__ kk) {
-  const int xx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (xx >= out_size) return;
-  const double scale = (double)in_size / (double)out_size;
-  double filterscale = scale;
-  if (filterscale < 1.0) filterscale = 1.0;
-  const double support = support_of(filter) * filterscale;
-  const double center = ((double)xx + 0.5) * scale;
-  const double ss = 1.0 / filterscale;
-  int xmin = (int)(center - support + 0.5);
-  if (xmin < 0) xmin = 0;
-  int xmax = (int)(center + support + 0.5);
-  if (xmax > in_size) xmax = in_size;
-  xmax -= xmin;
-  double ww = 0.0;
-  for (int x = 0; x < xmax; ++x) ww += filt(filter, ((double)(x + xmin) - center + 0.5) * ss);
-  for (int x = 0; x < ksize; ++x) {
-    int k = 0;
-    if (x < xmax) {
-      double w = filt(filter, ((double)(x + xmin) - center + 0.5) * ss);
-      if (ww != 0.0) w /= ww;
-      k = w < 0 ? (int)(-0.5 + w * (double)(1 << PRECISION_BITS)) : (int)(0.5 + w * (double)(1 << PRECISION_BITS));
-    }
-    kk[(size_t)xx * ksize + x] = k;
-  }
-  bounds[2 * xx] = xmin;
-  bounds[2 * xx + 1] = xmax;
-}
-
-__device__ __forceinline__ uint8_t clip8(int v) {
-  v >>= PRECISION_BITS;
-  return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-}
-
-// horizontal: src [sh][src_stride bytes] RGB -> tmp [sh][dw][3]
-__global__ __launch_bounds__(256) void pil_hpass_kernel(const uint8_t* __restrict__ src, int sh, size_t src_stride, int dw,
-                                                        int ksize, const int* __restrict__ bounds,
-                                                        const int* __restrict__ kk, uint8_t* __restrict__ tmp) {
-  const long long total = (long long)sh * dw;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-    const int yy = (int)(i / dw), xx = (int)(i - (long long)yy * dw);
+// horizontal: src [sh] rows of src_stride bytes, RGB -> tmp [sh][dw][3]
+template <typename I>
+__device__ __forceinline__ void hpass_body(const uint8_t* __restrict__ src, size_t src_stride, int sh, int dw, int ksize,
+                                           const int* __restrict__ bounds, const int* __restrict__ kk, uint8_t* __restrict__ tmp) {
+  const I total = (I)sh * dw;
+  for (I i = (I)blockIdx.x * 256 + threadIdx.x; i < total; i += (I)gridDim.x * 256) {
+    const int yy = (int)(i / dw), xx = (int)(i - (I)yy * dw);
     const int xmin = bounds[2 * xx], n = bounds[2 * xx + 1];
     const int* k = kk + (size_t)xx * ksize;
     const uint8_t* p = src + (size_t)yy * src_stride + (size_t)xmin * 3;
@@ -100,13 +47,13 @@ __global__ __launch_bounds__(256) void pil_hpass_kernel(const uint8_t* __restric
   }
 }
 
-// vertical: tmp [sh][dw][3] -> dst [dh][dw][3]
-__global__ __launch_bounds__(256) void pil_vpass_kernel(const uint8_t* __restrict__ tmp, int dw, int dh, int ksize,
-                                                        const int* __restrict__ bounds, const int* __restrict__ kk,
-                                                        uint8_t* __restrict__ dst) {
-  const long long total = (long long)dh * dw;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-    const int yy = (int)(i / dw), xx = (int)(i - (long long)yy * dw);
+// vertical: tmp [..][dw][3] -> dst [dh][dw][3]
+template <typename I>
+__device__ __forceinline__ void vpass_body(const uint8_t* __restrict__ tmp, int dw, int dh, int ksize, const int* __restrict__ bounds,
+                                           const int* __restrict__ kk, uint8_t* __restrict__ dst) {
+  const I total = (I)dh * dw;
+  for (I i = (I)blockIdx.x * 256 + threadIdx.x; i < total; i += (I)gridDim.x * 256) {
+    const int yy = (int)(i / dw), xx = (int)(i - (I)yy * dw);
     const int ymin = bounds[2 * yy], n = bounds[2 * yy + 1];
     const int* k = kk + (size_t)yy * ksize;
     const uint8_t* p = tmp + ((size_t)ymin * dw + xx) * 3;
@@ -121,6 +68,27 @@ __global__ __launch_bounds__(256) void pil_vpass_kernel(const uint8_t* __restric
   }
 }
 
+// ---- one image -----------------------------------------------------------------------------------------------------------
+// bounds[2*xx] = xmin, bounds[2*xx+1] = n ; kk[xx*ksize + x] = fixed-point weight
+__global__ void pil_coeffs_kernel(int in_size, int out_size, int filter, int ksize, int* __restrict__ bounds,
+                                  int* __restrict__ kk) {
+  const int xx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (xx >= out_size) return;
+  coeffs_row(in_size, out_size, xx, filter, ksize, bounds + 2 * xx, kk + (size_t)xx * ksize);
+}
+
+__global__ __launch_bounds__(256) void pil_hpass_kernel(const uint8_t* __restrict__ src, int sh, size_t src_stride, int dw,
+                                                        int ksize, const int* __restrict__ bounds,
+                                                        const int* __restrict__ kk, uint8_t* __restrict__ tmp) {
+  hpass_body<long long>(src, src_stride, sh, dw, ksize, bounds, kk, tmp);
+}
+
+__global__ __launch_bounds__(256) void pil_vpass_kernel(const uint8_t* __restrict__ tmp, int dw, int dh, int ksize,
+                                                        const int* __restrict__ bounds, const int* __restrict__ kk,
+                                                        uint8_t* __restrict__ dst) {
+  vpass_body<long long>(tmp, dw, dh, ksize, bounds, kk, dst);
+}
+
 // ---- batched variant: n fragments of different sizes -> n images of one size, one launch per pass -------------------
 struct FragDev {
   unsigned long long src_off;   // byte offset of the fragment's first pixel
@@ -133,85 +101,24 @@ __global__ void pil_coeffs_batch_kernel(const FragDev* __restrict__ fr, int axis
                                         int* __restrict__ bounds, int* __restrict__ kk) {
   const int f = blockIdx.y, xx = blockIdx.x * blockDim.x + threadIdx.x;
   if (xx >= out_size) return;
-  const int in_size = axis ? fr[f].h : fr[f].w;
-  const double scale = (double)in_size / (double)out_size;
-  double filterscale = scale;
-  if (filterscale < 1.0) filterscale = 1.0;
-  const double support = support_of(filter) * filterscale;
-  const double center = ((double)xx + 0.5) * scale;
-  const double ss = 1.0 / filterscale;
-  int xmin = (int)(center - support + 0.5);
-  if (xmin < 0) xmin = 0;
-  int xmax = (int)(center + support + 0.5);
-  if (xmax > in_size) xmax = in_size;
-  xmax -= xmin;
-  double ww = 0.0;
-  for (int x = 0; x < xmax; ++x) ww += filt(filter, ((double)(x + xmin) - center + 0.5) * ss);
-  int* k = kk + ((size_t)f * out_size + xx) * kmax;
-  for (int x = 0; x < kmax; ++x) {
-    int v = 0;
-    if (x < xmax) {
-      double w = filt(filter, ((double)(x + xmin) - center + 0.5) * ss);
-      if (ww != 0.0) w /= ww;
-      v = w < 0 ? (int)(-0.5 + w * (double)(1 << PRECISION_BITS)) : (int)(0.5 + w * (double)(1 << PRECISION_BITS));
-    }
-    k[x] = v;
-  }
-  bounds[((size_t)f * out_size + xx) * 2] = xmin;
-  bounds[((size_t)f * out_size + xx) * 2 + 1] = xmax;
+  const size_t row = (size_t)f * out_size + xx;
+  coeffs_row(axis ? fr[f].h : fr[f].w, out_size, xx, filter, kmax, bounds + row * 2, kk + row * kmax);
 }
 
 __global__ __launch_bounds__(256) void pil_hpass_batch_kernel(const uint8_t* __restrict__ base, const FragDev* __restrict__ fr,
                                                               int dw, int kmax, const int* __restrict__ bounds,
                                                               const int* __restrict__ kk, uint8_t* __restrict__ tmp) {
   const FragDev d = fr[blockIdx.y];
-  const int total = d.h * dw;
-  const int* bb = bounds + (size_t)blockIdx.y * dw * 2;
-  const int* kf = kk + (size_t)blockIdx.y * dw * kmax;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-    const int yy = i / dw, xx = i - yy * dw;
-    const int xmin = bb[2 * xx], n = bb[2 * xx + 1];
-    const int* k = kf + (size_t)xx * kmax;
-    const uint8_t* p = base + d.src_off + (size_t)yy * d.row_stride + (size_t)xmin * 3;
-    int a0 = 1 << (PRECISION_BITS - 1), a1 = a0, a2 = a0;
-    for (int x = 0; x < n; ++x) {
-      const int w = k[x];
-      a0 += (int)p[3 * x] * w; a1 += (int)p[3 * x + 1] * w; a2 += (int)p[3 * x + 2] * w;
-    }
-    uint8_t* o = tmp + d.tmp_off + (size_t)i * 3;
-    o[0] = clip8(a0); o[1] = clip8(a1); o[2] = clip8(a2);
-  }
+  hpass_body<int>(base + d.src_off, d.row_stride, d.h, dw, kmax, bounds + (size_t)blockIdx.y * dw * 2,
+                  kk + (size_t)blockIdx.y * dw * kmax, tmp + d.tmp_off);
 }
 
 __global__ __launch_bounds__(256) void pil_vpass_batch_kernel(const uint8_t* __restrict__ tmp, const FragDev* __restrict__ fr,
                                                               int dw, int dh, int kmax, const int* __restrict__ bounds,
                                                               const int* __restrict__ kk, uint8_t* __restrict__ dst) {
   const FragDev d = fr[blockIdx.y];
-  const int total = dh * dw;
-  const int* bb = bounds + (size_t)blockIdx.y * dh * 2;
-  const int* kf = kk + (size_t)blockIdx.y * dh * kmax;
-  uint8_t* out = dst + (size_t)blockIdx.y * total * 3;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-    const int yy = i / dw, xx = i - yy * dw;
-    const int ymin = bb[2 * yy], n = bb[2 * yy + 1];
-    const int* k = kf + (size_t)yy * kmax;
-    const uint8_t* p = tmp + d.tmp_off + ((size_t)ymin * dw + xx) * 3;
-    int a0 = 1 << (PRECISION_BITS - 1), a1 = a0, a2 = a0;
-    for (int y = 0; y < n; ++y) {
-      const int w = k[y];
-      const uint8_t* q = p + (size_t)y * dw * 3;
-      a0 += (int)q[0] * w; a1 += (int)q[1] * w; a2 += (int)q[2] * w;
-    }
-    uint8_t* o = out + (size_t)i * 3;
-    o[0] = clip8(a0); o[1] = clip8(a1); o[2] = clip8(a2);
-  }
-}
-
-int ksize_of(int in_size, int out_size, int filter) {
-  double scale = (double)in_size / (double)out_size;
-  if (scale < 1.0) scale = 1.0;
-  const double support = support_of(filter) * scale;
-  return (int)ceil(support) * 2 + 1;
+  vpass_body<int>(tmp + d.tmp_off, dw, dh, kmax, bounds + (size_t)blockIdx.y * dh * 2, kk + (size_t)blockIdx.y * dh * kmax,
+                  dst + (size_t)blockIdx.y * (dh * dw) * 3);
 }
 
 // the coefficient tables and the intermediate image of n resizes (tmp_bytes of horizontal-pass output) in `c`
@@ -334,6 +241,35 @@ extern "C" int mhip_pil_resize_rgb_host(mhip_ctx* ctx, const uint8_t* src_host, 
   if (rc) return rc;
   MHIP_HIP(ctx, hipMemcpyAsync(s, src_host, sb, hipMemcpyHostToDevice, ctx->stream));
   if ((rc = mhip_launch_pil_resize_rgb(ctx, s, sh, sw, (size_t)sw * 3, d, dh, dw, filter, scratch))) return rc;
+  MHIP_HIP(ctx, hipMemcpyAsync(dst_host, d, db, hipMemcpyDeviceToHost, ctx->stream));
+  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return MHIP_OK;
+}
+
+// replaces: [Image.fromarray(f).resize((dw, dh), filter) for f in fragments] on host buffers, through the batched kernels
+// (test / standalone entry): fragments inside base_host as descs say -> dst_host [n][dh][dw][3]
+extern "C" int mhip_pil_resize_fragments_host(mhip_ctx* ctx, const uint8_t* base_host, size_t base_bytes, const mhip_crop_desc* descs,
+                                              int n, int dh, int dw, int filter, uint8_t* dst_host) {
+  if (!ctx || !base_host || !descs || !dst_host || n < 1 || dh < 1 || dw < 1) return MHIP_EINVAL;
+  for (int i = 0; i < n; ++i) {
+    const mhip_crop_desc& d = descs[i];
+    if (d.channels != 3 || d.h < 1 || d.w < 1 || d.row_stride < 3 * d.w ||
+        d.src_offset + (size_t)(d.h - 1) * d.row_stride + (size_t)3 * d.w > base_bytes)
+      return mhip_fail(ctx, MHIP_EINVAL, "pil_resize: fragment %d is not h x w x 3 inside the %zu bytes of base", i, base_bytes);
+  }
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t db = (size_t)n * dh * dw * 3, sb = mhip_pil_resize_fragments_scratch(descs, n, dh, dw, filter);
+  uint8_t* base = nullptr;
+  uint8_t* d = nullptr;
+  void* scratch = nullptr;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
+    base = ws.take<uint8_t>(base_bytes);
+    d = ws.take<uint8_t>(db);
+    scratch = ws.take(sb);
+  });
+  if (rc) return rc;
+  MHIP_HIP(ctx, hipMemcpyAsync(base, base_host, base_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = mhip_pil_resize_fragments(ctx, base, descs, n, d, dh, dw, filter, scratch, sb))) return rc;
   MHIP_HIP(ctx, hipMemcpyAsync(dst_host, d, db, hipMemcpyDeviceToHost, ctx->stream));
   MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return MHIP_OK;

@@ -25,18 +25,16 @@ struct mhip_trocr {
   Arena arena;
   bool ready = false;
   // grow-only staging of generate_fragments (resized crops + resize scratch): no hipMalloc in steady state
-  uint8_t* frag_crops = nullptr;
-  size_t frag_crops_bytes = 0;
-  void* frag_scratch = nullptr;
-  size_t frag_scratch_bytes = 0;
+  DevBuf frag_crops, frag_scratch;
   bool absorb = false;       // encoder-attention with absorbed K / V projections (f16 mode)
   mhip_gate* decode_gate = nullptr;   // signalled where the decode phase of a generate call starts in the stream
   // "crops not finished yet" after every step, copied to pinned memory; the host reads it two steps late (never drains the stream)
   int* h_remaining = nullptr;
   hipEvent_t rem_ev[2] = {nullptr, nullptr};
   // encoder tokens of the crops encoded since mhip_trocr_encode_begin (the encoder runs per batch of fragments as the page
-  // batches come out of the detector; the autoregressive decoder then runs once over all of them): [enc_cap * npad + 64][enc_dim] T
-  char* enc_store = nullptr;
+  // batches come out of the detector; the autoregressive decoder then runs once over all of them):
+  // [enc_cap * npad + CROSS_ATTN_SLACK_ROWS][enc_dim] T (enc_store_bytes)
+  DevBuf enc_store;
   int enc_cap = 0, enc_count = 0;
   size_t esz() const { return precision == MHIP_PREC_F16 ? 2 : 4; }
 };
@@ -62,6 +60,14 @@ extern "C" int mhip_trocr_default_config(int model, mhip_trocr_config* c) {
   c->embed_scale = 1.0f;       // RoBERTa arguments: no_scale_embedding
   c->img_size = 384;
   return MHIP_OK;
+}
+
+// the absorbed W_k of the encoder-attention (cross_attn.hip): out[h][d][j] = wk[h * 64 + j][d] * log2(e), f16
+static void pack_ca_kt(const float* wk, int heads, int enc_dim, _Float16* out) {
+  const float log2e = 1.4426950408889634f;
+  for (int h = 0; h < heads; ++h)
+    for (int d = 0; d < enc_dim; ++d)
+      for (int j = 0; j < 64; ++j) out[((size_t)h * enc_dim + d) * 64 + j] = (_Float16)(wk[(size_t)(h * 64 + j) * enc_dim + d] * log2e);
 }
 
 static int trocr_max_len(const mhip_trocr_config& c) { return std::min(c.max_len_b, c.max_positions - 1); }
@@ -131,9 +137,9 @@ extern "C" int mhip_trocr_destroy(mhip_trocr* m) {
     if (e) (void)hipEventDestroy(e);
   mhip_vit_destroy(m->vit);
   m->arena.release();
-  if (m->frag_crops) (void)hipFree(m->frag_crops);
-  if (m->frag_scratch) (void)hipFree(m->frag_scratch);
-  if (m->enc_store) (void)hipFree(m->enc_store);
+  m->frag_crops.release();
+  m->frag_scratch.release();
+  m->enc_store.release();
   delete m;
   return MHIP_OK;
 }
@@ -223,11 +229,7 @@ extern "C" int mhip_trocr_finalize(mhip_trocr* m) {
     if (m->absorb) {
       const HostTensor* wk = st.find(ctx, p + "encoder_attn.k_proj.weight", {D, E});
       if (!wk) return MHIP_ESTATE;
-      _Float16* kt = (_Float16*)a.h(lay(l, "ca_kt"));
-      const float log2e = 1.4426950408889634f;
-      for (int h = 0; h < c.dec_heads; ++h)
-        for (int d = 0; d < E; ++d)
-          for (int j = 0; j < 64; ++j) kt[((size_t)h * E + d) * 64 + j] = (_Float16)(wk->data[(size_t)(h * 64 + j) * E + d] * log2e);
+      pack_ca_kt(wk->data.data(), c.dec_heads, E, (_Float16*)a.h(lay(l, "ca_kt")));
     }
     const std::pair<const char*, std::string> lns[] = {{"sa_ln", p + "self_attn_layer_norm"}, {"ca_ln", p + "encoder_attn_layer_norm"},
                                                        {"fin_ln", p + "final_layer_norm"}};
@@ -361,7 +363,7 @@ static int trocr_generate(mhip_trocr* m, const uint8_t* crops_dev, int n, int sw
 }
 
 // The autoregressive part (TextRecognitionGenerator._generate, generator.py:127-362) over the encoder tokens of n crops:
-// enc_tokens T [n * vg.npad + 64 slack rows][enc_dim].
+// enc_tokens T [n * vg.npad + CROSS_ATTN_SLACK_ROWS][enc_dim].
 static int trocr_decode(mhip_trocr* m, const TrocrDecodeBufs& b, const char* enc_tokens, const VitGeom& vg, int n,
                         int32_t* tokens_out, int32_t* lengths_out, float* scores_out, float* step0_logits_host, TrocrTrace* trace) {
   mhip_ctx* ctx = m->ctx;
@@ -372,38 +374,20 @@ static int trocr_decode(mhip_trocr* m, const TrocrDecodeBufs& b, const char* enc
   const int ldv = (c.vocab + 7) / 8 * 8;
   const Arena& a = m->arena;
   int rc;
-  struct { const char* tokens; } run{enc_tokens};
   // ---- encoder keys / values of every decoder layer (static over the steps) -----------------------------------------
   const size_t cross_l = (size_t)n * vg.npad * D * es;
-  char* ck = b.ck;
-  char* cv = b.cv;
   for (int l = 0; l < L && !m->absorb; ++l) {
-    if ((rc = mhip_gemm(ctx, prec, run.tokens, a.d(lay(l, "ca_k") + "_w"), (long long)n * vg.npad, D, E, nullptr, a.d<float>(lay(l, "ca_k") + "_b"), ck + l * cross_l, ACT_NONE, 0))) return rc;
-    if ((rc = mhip_gemm(ctx, prec, run.tokens, a.d(lay(l, "ca_v") + "_w"), (long long)n * vg.npad, D, E, nullptr, a.d<float>(lay(l, "ca_v") + "_b"), cv + l * cross_l, ACT_NONE, 0))) return rc;
+    if ((rc = mhip_gemm(ctx, prec, enc_tokens, a.d(lay(l, "ca_k") + "_w"), (long long)n * vg.npad, D, E, nullptr, a.d<float>(lay(l, "ca_k") + "_b"), b.ck + l * cross_l, ACT_NONE, 0))) return rc;
+    if ((rc = mhip_gemm(ctx, prec, enc_tokens, a.d(lay(l, "ca_v") + "_w"), (long long)n * vg.npad, D, E, nullptr, a.d<float>(lay(l, "ca_v") + "_b"), b.cv + l * cross_l, ACT_NONE, 0))) return rc;
   }
   // the MFMA-bound part of the call is enqueued; what follows is HBM- and latency-bound: whoever waits on the gate (the
   // detector of the next page batch) runs underneath it
   if (m->decode_gate && (rc = mhip_gate_signal(m->decode_gate, ctx))) return rc;
   // ---- decoder state ------------------------------------------------------------------------------------------------
   const size_t hist_s = (size_t)M * 3 * D * es;              // one step of one layer: rows of q | k | v
-  char* hqkv = b.hqkv;
-  float* x = b.x;
-  char* xt = b.xt;
-  char* qb = b.qb;
-  char* ao = b.ao;
-  char* hid = b.hid;
-  char* logits = b.logits;
   const int anc_ld = ML + 2;
-  int* const* anc = b.anc;
-  float* d_cs = b.cand_scores;
-  int* d_ct = b.cand_tokens;
-  int* d_cb = b.cand_beams;
-  const BeamState& bs = b.bs;
-  // generator state (TextRecognitionGenerator._generate without batch compaction: finished crops keep their rows), all in HBM
-  int* d_out_tok = b.out_tok;
-  int* d_out_len = b.out_len;
-  float* d_out_score = b.out_score;
-  if ((rc = mhip_launch_beam_init(ctx, bs, anc[0], anc_ld))) return rc;
+  // generator state (b.bs: TextRecognitionGenerator._generate without batch compaction, finished crops keep their rows), all in HBM
+  if ((rc = mhip_launch_beam_init(ctx, b.bs, b.anc[0], anc_ld))) return rc;
   int cur = 0, tcur = 0;
   for (int step = 0; step <= ML; ++step) {
     if (step >= 2) {
@@ -413,77 +397,76 @@ static int trocr_decode(mhip_trocr* m, const TrocrDecodeBufs& b, const char* enc
       if (m->h_remaining[step - 2] == 0) break;
     }
     if (step > 0) {
-      if ((rc = mhip_launch_ancestry(ctx, anc[cur], anc[cur ^ 1], bs.parent, M, anc_ld, step - 1))) return rc;
+      if ((rc = mhip_launch_ancestry(ctx, b.anc[cur], b.anc[cur ^ 1], b.bs.parent, M, anc_ld, step - 1))) return rc;
       cur ^= 1;
     }
     // LearnedPositionalEmbedding, incremental: position = padding_idx + (step + 1)
     const float* pos_row = a.d<float>("pos") + (size_t)(c.pad + step + 1) * D;
-    if ((rc = mhip_launch_embed_step(ctx, prec, bs.last_tok, a.d("emb"), pos_row, c.embed_scale, a.d<float>("lne_g"), a.d<float>("lne_b"), x, xt, M, D, DEC_LN_EPS))) return rc;
+    if ((rc = mhip_launch_embed_step(ctx, prec, b.bs.last_tok, a.d("emb"), pos_row, c.embed_scale, a.d<float>("lne_g"), a.d<float>("lne_b"), b.x, b.xt, M, D, DEC_LN_EPS))) return rc;
     for (int l = 0; l < L; ++l) {
-      char* hl = hqkv + ((size_t)l * (ML + 1)) * hist_s;
+      char* hl = b.hqkv + ((size_t)l * (ML + 1)) * hist_s;
       // self-attention over the hypothesis' own history (post-LN residual block): q | k | v of this step in ONE GEMM (the three
       // weights are adjacent in the arena), written as one row of the history
-      if ((rc = mhip_gemm(ctx, prec, xt, a.d(lay(l, "sa_q") + "_w"), M, 3 * D, D, nullptr, a.d<float>(lay(l, "sa_q") + "_b"), hl + (size_t)step * hist_s, ACT_NONE, 0))) return rc;
+      if ((rc = mhip_gemm(ctx, prec, b.xt, a.d(lay(l, "sa_q") + "_w"), M, 3 * D, D, nullptr, a.d<float>(lay(l, "sa_q") + "_b"), hl + (size_t)step * hist_s, ACT_NONE, 0))) return rc;
       DecAttnDesc sa;
-      sa.q = hl + (size_t)step * hist_s; sa.k = hl + (size_t)D * es; sa.v = hl + (size_t)2 * D * es; sa.out = ao;
-      sa.anc = anc[cur]; sa.anc_ld = anc_ld; sa.slots = M;
+      sa.q = hl + (size_t)step * hist_s; sa.k = hl + (size_t)D * es; sa.v = hl + (size_t)2 * D * es; sa.out = b.ao;
+      sa.anc = b.anc[cur]; sa.anc_ld = anc_ld; sa.slots = M;
       sa.ldq = sa.ldk = 3 * D; sa.ldo = D; sa.heads = c.dec_heads; sa.groups = M; sa.nq = 1; sa.n_keys = step + 1;
       if ((rc = mhip_launch_decode_attention(ctx, prec, sa))) return rc;
-      if ((rc = mhip_gemm(ctx, prec, ao, a.d(lay(l, "sa_o") + "_w"), M, D, D, nullptr, a.d<float>(lay(l, "sa_o") + "_b"), x, ACT_NONE, 1, x))) return rc;
-      if ((rc = mhip_launch_layernorm2(ctx, prec, x, a.d<float>(lay(l, "sa_ln") + "_g"), a.d<float>(lay(l, "sa_ln") + "_b"), x, xt, M, D, DEC_LN_EPS))) return rc;
+      if ((rc = mhip_gemm(ctx, prec, b.ao, a.d(lay(l, "sa_o") + "_w"), M, D, D, nullptr, a.d<float>(lay(l, "sa_o") + "_b"), b.x, ACT_NONE, 1, b.x))) return rc;
+      if ((rc = mhip_launch_layernorm2(ctx, prec, b.x, a.d<float>(lay(l, "sa_ln") + "_g"), a.d<float>(lay(l, "sa_ln") + "_b"), b.x, b.xt, M, D, DEC_LN_EPS))) return rc;
       // attention over the crop's encoder tokens (keys / values shared by its beams)
-      if ((rc = mhip_gemm(ctx, prec, xt, a.d(lay(l, "ca_q") + "_w"), M, D, D, nullptr, a.d<float>(lay(l, "ca_q") + "_b"), qb, ACT_NONE, 0))) return rc;
+      if ((rc = mhip_gemm(ctx, prec, b.xt, a.d(lay(l, "ca_q") + "_w"), M, D, D, nullptr, a.d<float>(lay(l, "ca_q") + "_b"), b.qb, ACT_NONE, 0))) return rc;
       if (m->absorb) {
         CrossAbsorbDesc cd;
-        cd.q = qb; cd.ldq = D; cd.E = run.tokens; cd.kv_rows = vg.npad; cd.n_keys = vg.n_tok; cd.enc_dim = E;
+        cd.q = b.qb; cd.ldq = D; cd.E = enc_tokens; cd.kv_rows = vg.npad; cd.n_keys = vg.n_tok; cd.enc_dim = E;
         cd.wkt = a.d(lay(l, "ca_kt")); cd.wv = a.d(lay(l, "ca_v") + "_w"); cd.bv = a.d<float>(lay(l, "ca_v") + "_b");
-        cd.qt = b.qt; cd.ct = b.ct; cd.ao = ao; cd.ldo = D; cd.crops = n; cd.beam = beam; cd.heads = c.dec_heads;
+        cd.qt = b.qt; cd.ct = b.ct; cd.ao = b.ao; cd.ldo = D; cd.crops = n; cd.beam = beam; cd.heads = c.dec_heads;
         if ((rc = mhip_launch_cross_absorbed(ctx, cd))) return rc;
       } else {
         DecAttnDesc ca;
-        ca.q = qb; ca.k = ck + l * cross_l; ca.v = cv + l * cross_l; ca.out = ao; ca.kv_rows = vg.npad;
+        ca.q = b.qb; ca.k = b.ck + l * cross_l; ca.v = b.cv + l * cross_l; ca.out = b.ao; ca.kv_rows = vg.npad;
         ca.ldq = ca.ldk = ca.ldo = D; ca.heads = c.dec_heads; ca.groups = n; ca.nq = beam; ca.n_keys = vg.n_tok;
         if ((rc = mhip_launch_decode_attention(ctx, prec, ca))) return rc;
       }
-      if ((rc = mhip_gemm(ctx, prec, ao, a.d(lay(l, "ca_o") + "_w"), M, D, D, nullptr, a.d<float>(lay(l, "ca_o") + "_b"), x, ACT_NONE, 1, x))) return rc;
-      if ((rc = mhip_launch_layernorm2(ctx, prec, x, a.d<float>(lay(l, "ca_ln") + "_g"), a.d<float>(lay(l, "ca_ln") + "_b"), x, xt, M, D, DEC_LN_EPS))) return rc;
+      if ((rc = mhip_gemm(ctx, prec, b.ao, a.d(lay(l, "ca_o") + "_w"), M, D, D, nullptr, a.d<float>(lay(l, "ca_o") + "_b"), b.x, ACT_NONE, 1, b.x))) return rc;
+      if ((rc = mhip_launch_layernorm2(ctx, prec, b.x, a.d<float>(lay(l, "ca_ln") + "_g"), a.d<float>(lay(l, "ca_ln") + "_b"), b.x, b.xt, M, D, DEC_LN_EPS))) return rc;
       // feed-forward
-      if ((rc = mhip_gemm(ctx, prec, xt, a.d(lay(l, "fc1_w")), M, F, D, nullptr, a.d<float>(lay(l, "fc1_b")), hid, ACT_GELU, 0))) return rc;
-      if ((rc = mhip_gemm(ctx, prec, hid, a.d(lay(l, "fc2_w")), M, D, F, nullptr, a.d<float>(lay(l, "fc2_b")), x, ACT_NONE, 1, x))) return rc;
-      if ((rc = mhip_launch_layernorm2(ctx, prec, x, a.d<float>(lay(l, "fin_ln") + "_g"), a.d<float>(lay(l, "fin_ln") + "_b"), x, xt, M, D, DEC_LN_EPS))) return rc;
+      if ((rc = mhip_gemm(ctx, prec, b.xt, a.d(lay(l, "fc1_w")), M, F, D, nullptr, a.d<float>(lay(l, "fc1_b")), b.hid, ACT_GELU, 0))) return rc;
+      if ((rc = mhip_gemm(ctx, prec, b.hid, a.d(lay(l, "fc2_w")), M, D, F, nullptr, a.d<float>(lay(l, "fc2_b")), b.x, ACT_NONE, 1, b.x))) return rc;
+      if ((rc = mhip_launch_layernorm2(ctx, prec, b.x, a.d<float>(lay(l, "fin_ln") + "_g"), a.d<float>(lay(l, "fin_ln") + "_b"), b.x, b.xt, M, D, DEC_LN_EPS))) return rc;
     }
-    if ((rc = mhip_gemm(ctx, prec, xt, a.d("out_w"), M, c.vocab, D, nullptr, nullptr, logits, ACT_NONE, 0, nullptr, ldv, 1))) return rc;
+    if ((rc = mhip_gemm(ctx, prec, b.xt, a.d("out_w"), M, c.vocab, D, nullptr, nullptr, b.logits, ACT_NONE, 0, nullptr, ldv, 1))) return rc;
     if (step == 0 && step0_logits_host) {
-      float* stage = b.step0_stage;
       for (int i = 0; i < n; ++i) {
-        if ((rc = mhip_launch_convert_rows(ctx, prec, logits + (size_t)i * beam * ldv * es, stage, 1, c.vocab))) return rc;
-        MHIP_HIP(ctx, hipMemcpyAsync(step0_logits_host + (size_t)i * c.vocab, stage, (size_t)c.vocab * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if ((rc = mhip_launch_convert_rows(ctx, prec, b.logits + (size_t)i * beam * ldv * es, b.step0_stage, 1, c.vocab))) return rc;
+        MHIP_HIP(ctx, hipMemcpyAsync(step0_logits_host + (size_t)i * c.vocab, b.step0_stage, (size_t)c.vocab * 4, hipMemcpyDeviceToHost, ctx->stream));
         MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
       }
     }
     BeamCandDesc bc;
-    bc.logits = logits; bc.logits_f16 = prec == MHIP_PREC_F16; bc.ld = ldv; bc.vocab = c.vocab; bc.beam = beam; bc.bsz = n; bc.cum = bs.cum; bc.step = step;
+    bc.logits = b.logits; bc.logits_f16 = prec == MHIP_PREC_F16; bc.ld = ldv; bc.vocab = c.vocab; bc.beam = beam; bc.bsz = n; bc.cum = b.bs.cum; bc.step = step;
     bc.max_len = ML; bc.min_len = c.min_len; bc.pad = c.pad; bc.eos = c.eos;
-    bc.cand_scores = d_cs; bc.cand_tokens = d_ct; bc.cand_beams = d_cb;
+    bc.cand_scores = b.cand_scores; bc.cand_tokens = b.cand_tokens; bc.cand_beams = b.cand_beams;
     if ((rc = mhip_launch_beam_candidates(ctx, bc))) return rc;
     if (trace) {       // parity tests: the step's candidate list as the generator sees it (this path drains the stream)
       const size_t off = (size_t)step * n * K2;
-      MHIP_HIP(ctx, hipMemcpyAsync(trace->scores + off, d_cs, (size_t)n * K2 * 4, hipMemcpyDeviceToHost, ctx->stream));
-      MHIP_HIP(ctx, hipMemcpyAsync(trace->tokens + off, d_ct, (size_t)n * K2 * 4, hipMemcpyDeviceToHost, ctx->stream));
-      MHIP_HIP(ctx, hipMemcpyAsync(trace->beams + off, d_cb, (size_t)n * K2 * 4, hipMemcpyDeviceToHost, ctx->stream));
+      MHIP_HIP(ctx, hipMemcpyAsync(trace->scores + off, b.cand_scores, (size_t)n * K2 * 4, hipMemcpyDeviceToHost, ctx->stream));
+      MHIP_HIP(ctx, hipMemcpyAsync(trace->tokens + off, b.cand_tokens, (size_t)n * K2 * 4, hipMemcpyDeviceToHost, ctx->stream));
+      MHIP_HIP(ctx, hipMemcpyAsync(trace->beams + off, b.cand_beams, (size_t)n * K2 * 4, hipMemcpyDeviceToHost, ctx->stream));
       MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
       trace->steps = step + 1;
     }
-    if ((rc = mhip_launch_beam_select(ctx, bs, tcur, step))) return rc;
+    if ((rc = mhip_launch_beam_select(ctx, b.bs, tcur, step))) return rc;
     tcur ^= 1;
-    MHIP_HIP(ctx, hipMemcpyAsync(&m->h_remaining[step], bs.remaining, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    MHIP_HIP(ctx, hipMemcpyAsync(&m->h_remaining[step], b.bs.remaining, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     MHIP_HIP(ctx, hipEventRecord(m->rem_ev[step & 1], ctx->stream));
   }
   // best hypothesis per crop: highest score, first finalized wins ties (torch.sort(descending) on the score list)
-  if ((rc = mhip_launch_beam_best(ctx, bs, d_out_tok, d_out_len, d_out_score))) return rc;
-  MHIP_HIP(ctx, hipMemcpyAsync(tokens_out, d_out_tok, (size_t)n * (ML + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
-  MHIP_HIP(ctx, hipMemcpyAsync(lengths_out, d_out_len, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-  MHIP_HIP(ctx, hipMemcpyAsync(scores_out, d_out_score, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if ((rc = mhip_launch_beam_best(ctx, b.bs, b.out_tok, b.out_len, b.out_score))) return rc;
+  MHIP_HIP(ctx, hipMemcpyAsync(tokens_out, b.out_tok, (size_t)n * (ML + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(lengths_out, b.out_len, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(scores_out, b.out_score, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
   MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return MHIP_OK;
 }
@@ -494,21 +477,21 @@ extern "C" int mhip_trocr_generate(mhip_trocr* m, const uint8_t* crops_dev, int 
   return trocr_generate(m, crops_dev, n, swap_rb, tokens_out, lengths_out, scores_out, nullptr, nullptr);
 }
 
+// trocr_generate on host crops [n][img][img][3]
+static int trocr_generate_host(mhip_trocr* m, const uint8_t* crops_host, int n, int swap_rb, int32_t* tokens_out, int32_t* lengths_out,
+                               float* scores_out, float* enc_tokens_out, float* step0_logits_out, TrocrTrace* trace) {
+  mhip_ctx* ctx = m->ctx;
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  return mhip_with_upload(ctx, crops_host, (size_t)n * m->cfg.img_size * m->cfg.img_size * 3, "crop", [&](const uint8_t* dev) {
+    return trocr_generate(m, dev, n, swap_rb, tokens_out, lengths_out, scores_out, enc_tokens_out, step0_logits_out, trace);
+  });
+}
+
 extern "C" int mhip_trocr_generate_host(mhip_trocr* m, const uint8_t* crops_host, int n, int swap_rb, int32_t* tokens_out,
                                         int32_t* lengths_out, float* scores_out, float* enc_tokens_out,
                                         float* step0_logits_out) {
   if (!m || !crops_host || !tokens_out || !lengths_out || !scores_out || n < 1) return MHIP_EINVAL;
-  mhip_ctx* ctx = m->ctx;
-  MHIP_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t nb = (size_t)n * m->cfg.img_size * m->cfg.img_size * 3;
-  uint8_t* dev = nullptr;
-  MHIP_HIP(ctx, hipMalloc((void**)&dev, nb));
-  hipError_t e = hipMemcpy(dev, crops_host, nb, hipMemcpyHostToDevice);
-  int rc = e == hipSuccess ? MHIP_OK : mhip_fail(ctx, MHIP_EHIP, "crop upload: %s", hipGetErrorString(e));
-  if (!rc) rc = trocr_generate(m, dev, n, swap_rb, tokens_out, lengths_out, scores_out, enc_tokens_out, step0_logits_out);
-  (void)hipStreamSynchronize(ctx->stream);
-  (void)hipFree(dev);
-  return rc;
+  return trocr_generate_host(m, crops_host, n, swap_rb, tokens_out, lengths_out, scores_out, enc_tokens_out, step0_logits_out, nullptr);
 }
 
 // generate_host + the candidate list of every step as the generator saw it (parity tests: the CPU restatement walks the two
@@ -519,19 +502,26 @@ extern "C" int mhip_trocr_generate_trace_host(mhip_trocr* m, const uint8_t* crop
   if (!m || !crops_host || !tokens_out || !lengths_out || !scores_out || !trace_scores || !trace_tokens || !trace_beams ||
       !steps_out || n < 1)
     return MHIP_EINVAL;
-  mhip_ctx* ctx = m->ctx;
-  MHIP_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t nb = (size_t)n * m->cfg.img_size * m->cfg.img_size * 3;
-  uint8_t* dev = nullptr;
-  MHIP_HIP(ctx, hipMalloc((void**)&dev, nb));
-  hipError_t e = hipMemcpy(dev, crops_host, nb, hipMemcpyHostToDevice);
-  int rc = e == hipSuccess ? MHIP_OK : mhip_fail(ctx, MHIP_EHIP, "crop upload: %s", hipGetErrorString(e));
   TrocrTrace tr{trace_scores, trace_tokens, trace_beams, 0};
-  if (!rc) rc = trocr_generate(m, dev, n, swap_rb, tokens_out, lengths_out, scores_out, nullptr, nullptr, &tr);
-  (void)hipStreamSynchronize(ctx->stream);
-  (void)hipFree(dev);
+  const int rc = trocr_generate_host(m, crops_host, n, swap_rb, tokens_out, lengths_out, scores_out, nullptr, nullptr, &tr);
   *steps_out = tr.steps;
   return rc;
+}
+
+// The Pillow bicubic resize of n fragments to img x img into the handle's grow-only staging (m->frag_crops)
+static int trocr_resize_fragments(mhip_trocr* m, const uint8_t* base_dev, const mhip_crop_desc* descs_host, int n) {
+  mhip_ctx* ctx = m->ctx;
+  const int S = m->cfg.img_size;
+  int rc = m->frag_crops.ensure(ctx, (size_t)n * S * S * 3);
+  if (!rc) rc = m->frag_scratch.ensure(ctx, mhip_pil_resize_fragments_scratch(descs_host, n, S, S, MHIP_PIL_BICUBIC));
+  if (rc) return rc;
+  return mhip_pil_resize_fragments(ctx, base_dev, descs_host, n, m->frag_crops.as<uint8_t>(), S, S, MHIP_PIL_BICUBIC, m->frag_scratch.p,
+                                   m->frag_scratch.bytes);
+}
+
+// bytes of enc_store for `crops` crops
+static size_t enc_store_bytes(const mhip_trocr* m, const VitGeom& vg, int crops) {
+  return ((size_t)crops * vg.npad + CROSS_ATTN_SLACK_ROWS) * m->cfg.enc_dim * m->esz();
 }
 
 // Fragments of any size (u8, 3 channels, rows of row_stride bytes at base_dev + src_offset) -> Pillow bicubic resize to
@@ -541,26 +531,8 @@ extern "C" int mhip_trocr_generate_fragments(mhip_trocr* m, const uint8_t* base_
   if (!m || !base_dev || !descs_host || !tokens_out || !lengths_out || !scores_out || n < 1) return MHIP_EINVAL;
   mhip_ctx* ctx = m->ctx;
   MHIP_HIP(ctx, hipSetDevice(ctx->device));
-  const int S = m->cfg.img_size;
-  const size_t scratch = mhip_pil_resize_fragments_scratch(descs_host, n, S, S, MHIP_PIL_BICUBIC);
-  const size_t cb = (size_t)n * S * S * 3;
-  if (cb > m->frag_crops_bytes || scratch > m->frag_scratch_bytes) {
-    MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (cb > m->frag_crops_bytes) {
-      if (m->frag_crops) (void)hipFree(m->frag_crops);
-      m->frag_crops = nullptr; m->frag_crops_bytes = 0;
-      MHIP_HIP(ctx, hipMalloc((void**)&m->frag_crops, cb));
-      m->frag_crops_bytes = cb;
-    }
-    if (scratch > m->frag_scratch_bytes) {
-      if (m->frag_scratch) (void)hipFree(m->frag_scratch);
-      m->frag_scratch = nullptr; m->frag_scratch_bytes = 0;
-      MHIP_HIP(ctx, hipMalloc(&m->frag_scratch, scratch));
-      m->frag_scratch_bytes = scratch;
-    }
-  }
-  int rc = mhip_pil_resize_fragments(ctx, base_dev, descs_host, n, m->frag_crops, S, S, MHIP_PIL_BICUBIC, m->frag_scratch, m->frag_scratch_bytes);
-  if (!rc) rc = trocr_generate(m, m->frag_crops, n, swap_rb, tokens_out, lengths_out, scores_out, nullptr, nullptr);
+  int rc = trocr_resize_fragments(m, base_dev, descs_host, n);
+  if (!rc) rc = trocr_generate(m, m->frag_crops.as<uint8_t>(), n, swap_rb, tokens_out, lengths_out, scores_out, nullptr, nullptr);
   return rc;
 }
 
@@ -576,10 +548,9 @@ extern "C" int mhip_trocr_encode_begin(mhip_trocr* m, int max_crops) {
   if (max_crops > m->enc_cap) {
     VitGeom vg;
     vit_geometry(m->vit, m->cfg.img_size, m->cfg.img_size, &vg);
-    MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (m->enc_store) (void)hipFree(m->enc_store);
-    m->enc_store = nullptr; m->enc_cap = 0;
-    MHIP_HIP(ctx, hipMalloc((void**)&m->enc_store, ((size_t)max_crops * vg.npad + 64) * m->cfg.enc_dim * m->esz()));
+    m->enc_cap = 0;
+    const int rc = m->enc_store.ensure(ctx, enc_store_bytes(m, vg, max_crops));
+    if (rc) return rc;
     m->enc_cap = max_crops;
   }
   return MHIP_OK;
@@ -600,38 +571,21 @@ extern "C" int mhip_trocr_encode_fragments(mhip_trocr* m, const uint8_t* base_de
   vit_geometry(m->vit, S, S, &vg);
   if (m->enc_count + n > m->enc_cap) {      // grow, keeping what has been encoded
     const int cap = std::max(m->enc_count + n, 2 * m->enc_cap);
-    char* bigger = nullptr;
-    MHIP_HIP(ctx, hipMalloc((void**)&bigger, ((size_t)cap * vg.npad + 64) * c.enc_dim * es));
-    if (m->enc_count) MHIP_HIP(ctx, hipMemcpyAsync(bigger, m->enc_store, (size_t)m->enc_count * vg.npad * c.enc_dim * es, hipMemcpyDeviceToDevice, ctx->stream));
+    DevBuf bigger;
+    bigger.bytes = enc_store_bytes(m, vg, cap);
+    MHIP_HIP(ctx, hipMalloc(&bigger.p, bigger.bytes));
+    if (m->enc_count) MHIP_HIP(ctx, hipMemcpyAsync(bigger.p, m->enc_store.p, (size_t)m->enc_count * vg.npad * c.enc_dim * es, hipMemcpyDeviceToDevice, ctx->stream));
     MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (m->enc_store) (void)hipFree(m->enc_store);
+    m->enc_store.release();
     m->enc_store = bigger;
     m->enc_cap = cap;
   }
-  const size_t scratch = mhip_pil_resize_fragments_scratch(descs_host, n, S, S, MHIP_PIL_BICUBIC);
-  const size_t cb = (size_t)n * S * S * 3;
-  if (cb > m->frag_crops_bytes || scratch > m->frag_scratch_bytes) {
-    MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (cb > m->frag_crops_bytes) {
-      if (m->frag_crops) (void)hipFree(m->frag_crops);
-      m->frag_crops = nullptr; m->frag_crops_bytes = 0;
-      MHIP_HIP(ctx, hipMalloc((void**)&m->frag_crops, cb));
-      m->frag_crops_bytes = cb;
-    }
-    if (scratch > m->frag_scratch_bytes) {
-      if (m->frag_scratch) (void)hipFree(m->frag_scratch);
-      m->frag_scratch = nullptr; m->frag_scratch_bytes = 0;
-      MHIP_HIP(ctx, hipMalloc(&m->frag_scratch, scratch));
-      m->frag_scratch_bytes = scratch;
-    }
-  }
   VitRun run;
-  run.tokens_dst = m->enc_store + (size_t)m->enc_count * vg.npad * c.enc_dim * es;
+  run.tokens_dst = m->enc_store.as() + (size_t)m->enc_count * vg.npad * c.enc_dim * es;
   int rc = mhip_carve_workspace(ctx, [&](Carver& ws) { vit_carve(m->vit, ws, n, vg, &run); });
   if (rc) return rc;
-  rc = mhip_pil_resize_fragments(ctx, base_dev, descs_host, n, m->frag_crops, S, S, MHIP_PIL_BICUBIC, m->frag_scratch, m->frag_scratch_bytes);
-  if (rc) return rc;
-  if ((rc = vit_encode(m->vit, m->frag_crops, n, S, S, S, S, swap_rb, &run))) return rc;
+  if ((rc = trocr_resize_fragments(m, base_dev, descs_host, n))) return rc;
+  if ((rc = vit_encode(m->vit, m->frag_crops.as<uint8_t>(), n, S, S, S, S, swap_rb, &run))) return rc;
   m->enc_count += n;
   return MHIP_OK;
 }
@@ -647,13 +601,13 @@ extern "C" int mhip_trocr_decode(mhip_trocr* m, int32_t* tokens_out, int32_t* le
   TrocrDecodeBufs b;
   int rc = mhip_carve_workspace(ctx, [&](Carver& ws) { trocr_decode_carve(m, ws, n, vg, false, &b); });
   if (rc) return rc;
-  // the 64 rows behind the last crop are read (masked) by its final key tiles: keep them finite
-  MHIP_HIP(ctx, hipMemsetAsync(m->enc_store + (size_t)n * vg.npad * m->cfg.enc_dim * m->esz(), 0, (size_t)64 * m->cfg.enc_dim * m->esz(), ctx->stream));
-  rc = trocr_decode(m, b, m->enc_store, vg, n, tokens_out, lengths_out, scores_out, nullptr, nullptr);
+  // the slack rows behind the last crop are read (masked) by its final key tiles: keep them finite
+  const size_t row = (size_t)m->cfg.enc_dim * m->esz();
+  MHIP_HIP(ctx, hipMemsetAsync(m->enc_store.as() + (size_t)n * vg.npad * row, 0, CROSS_ATTN_SLACK_ROWS * row, ctx->stream));
+  rc = trocr_decode(m, b, m->enc_store.as(), vg, n, tokens_out, lengths_out, scores_out, nullptr, nullptr);
   m->enc_count = 0;
   return rc;
 }
-
 
 // The decoder's encoder-attention stage on caller-supplied host inputs, through the absorbed kernels (f16 operands): what the
 // parity tests compare with fairseq's MultiheadAttention (q already projected and scaled).  q [crops*beam][heads*64],
@@ -664,16 +618,13 @@ extern "C" int mhip_cross_attention_host(mhip_ctx* ctx, const float* q, const fl
   if (!mhip_cross_absorb_supported(enc_dim, beam, heads)) return mhip_fail(ctx, MHIP_EINVAL, "cross_attention: unsupported shape");
   MHIP_HIP(ctx, hipSetDevice(ctx->device));
   const int D = heads * 64, M = crops * beam, npad = (n_tok + 7) / 8 * 8;
-  const size_t rowsE = (size_t)crops * npad + 64;
+  const size_t rowsE = (size_t)crops * npad + CROSS_ATTN_SLACK_ROWS;
   std::vector<_Float16> hq((size_t)M * D), hE(rowsE * enc_dim, (_Float16)0.f), hkt((size_t)D * enc_dim), hwv((size_t)D * enc_dim);
   for (size_t i = 0; i < hq.size(); ++i) hq[i] = (_Float16)q[i];
   for (int c = 0; c < crops; ++c)
     for (int s = 0; s < n_tok; ++s)
       for (int d = 0; d < enc_dim; ++d) hE[((size_t)c * npad + s) * enc_dim + d] = (_Float16)enc[((size_t)c * n_tok + s) * enc_dim + d];
-  const float log2e = 1.4426950408889634f;
-  for (int h = 0; h < heads; ++h)
-    for (int d = 0; d < enc_dim; ++d)
-      for (int j = 0; j < 64; ++j) hkt[((size_t)h * enc_dim + d) * 64 + j] = (_Float16)(wk[(size_t)(h * 64 + j) * enc_dim + d] * log2e);
+  pack_ca_kt(wk, heads, enc_dim, hkt.data());
   for (size_t i = 0; i < hwv.size(); ++i) hwv[i] = (_Float16)wv[i];
   const size_t scr = (size_t)M * 16 * enc_dim * 2;
   char *dq = nullptr, *dE = nullptr, *dkt = nullptr, *dwv = nullptr, *qt = nullptr, *ct = nullptr, *ao = nullptr;

@@ -274,10 +274,10 @@ void vit_carve(const mhip_vit* m, Carver& ws, int B, const VitGeom& g, VitRun* r
   }
   if (m->cfg.fpn)
     for (int j = 0; j < 4; ++j) run->tap[j] = ws.take((size_t)B * g.np * D * es);
-  // + 64 finite rows: the decoder's encoder-attention walks every image's tokens in 32-row tiles and so reads (masked) rows
-  // past the last image
+  // + CROSS_ATTN_SLACK_ROWS finite rows: the decoder's encoder-attention walks every image's tokens in 32-row tiles and so reads
+  // (masked) rows past the last image
   run->tokens = nullptr;
-  if (m->cfg.final_norm) run->tokens = run->tokens_dst ? run->tokens_dst : ws.take((R + 64) * D * es);
+  if (m->cfg.final_norm) run->tokens = run->tokens_dst ? run->tokens_dst : ws.take((R + CROSS_ATTN_SLACK_ROWS) * D * es);
 }
 
 int vit_encode(mhip_vit* m, const uint8_t* imgs, int B, int th, int tw, int H32, int W32, int swap_rb, VitRun* run) {
@@ -381,7 +381,7 @@ int vit_encode(mhip_vit* m, const uint8_t* imgs, int B, int th, int tw, int H32,
         if (c.taps[j] == i && (rc = mhip_launch_tokens_to_map(ctx, prec, x, run->tap[j], B, g.npad, g.np, D, x16 || fold))) return rc;
   }
   if (c.final_norm) {
-    if (!run->tokens_dst) MHIP_HIP(ctx, hipMemsetAsync(run->tokens + R * D * es, 0, (size_t)64 * D * es, ctx->stream));
+    if (!run->tokens_dst) MHIP_HIP(ctx, hipMemsetAsync(run->tokens + R * D * es, 0, (size_t)CROSS_ATTN_SLACK_ROWS * D * es, ctx->stream));
     if ((rc = mhip_launch_layernorm(ctx, prec, x, a.d<float>("norm_g"), a.d<float>("norm_b"), run->tokens, (int)R, D, c.ln_eps, x16 || fold, xlo))) return rc;
   }
   return MHIP_OK;

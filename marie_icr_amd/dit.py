@@ -10,7 +10,7 @@ from typing import Dict, Optional, Sequence
 
 import numpy as np
 
-from ._lib import PREC_F16, Context, DitConfig, ModelHandle, check
+from ._lib import PREC_F16, Context, CropDesc, DitConfig, ModelHandle, check
 
 MAX_ROIS = 1000
 ANCHOR_SIZES = (4.0, 8.0, 16.0, 32.0, 64.0)
@@ -201,6 +201,18 @@ def pil_resize_rgb(ctx: Context, img: np.ndarray, out_hw, bicubic: bool = False,
     out = np.empty((int(out_hw[0]), int(out_hw[1]), 3), np.uint8)
     check(ctx.h, ctx.lib.mhip_pil_resize_rgb_host(ctx.h, _vp(img), img.shape[0], img.shape[1], _vp(out), out.shape[0],
                                                   out.shape[1], int(filter)), "mhip_pil_resize_rgb_host")
+    return out
+
+
+def pil_resize_fragments(ctx: Context, base: np.ndarray, frags, out_hw, filter: int) -> np.ndarray:
+    """``[Image.fromarray(f).resize((w, h), filter) for f in fragments]`` through ``mhip_pil_resize_fragments_host``, the batched
+    kernels of TrOCR and LayoutLMv3: ``base`` is one uint8 buffer, ``frags`` a list of ``(src_offset, h, w, row_stride)`` RGB
+    fragments inside it; returns uint8 (n, h, w, 3)."""
+    base = np.ascontiguousarray(base, np.uint8).reshape(-1)
+    descs = (CropDesc * len(frags))(*[CropDesc(int(o), int(h), int(w), int(rs), 3) for o, h, w, rs in frags])
+    out = np.empty((len(frags), int(out_hw[0]), int(out_hw[1]), 3), np.uint8)
+    check(ctx.h, ctx.lib.mhip_pil_resize_fragments_host(ctx.h, _vp(base), base.size, descs, len(frags), out.shape[1], out.shape[2],
+                                                        int(filter), _vp(out)), "mhip_pil_resize_fragments_host")
     return out
 
 
