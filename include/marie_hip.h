@@ -748,6 +748,56 @@ int mhip_clipvis_head_host(mhip_ctx* ctx, const float* h, int B, int npad, int D
 int mhip_clipvis_pair_cosine_host(mhip_ctx* ctx, const float* emb, int n, int E, const int32_t* pair_a, const int32_t* pair_b,
                                   int n_pairs, float* cos_out);
 
+/* ---- CLIP text tower: text embeddings (csrc/cliptext_api.hip, cliptext_ops.hip) ------------------------------------------- */
+/* replaces: CLIP.encode_text behind OpenAIEmbeddings.get_text_embedding, marie/embeddings/openai/openai_embeddings.py:122-129,
+ * 159-164 (clip/model.py: token_embedding + positional_embedding, the causal transformer, ln_final, the end-of-text row,
+ * text_projection), CLIPModel.get_text_features of transformers.  Token ids come from the caller (marie_icr_amd/
+ * clip_tokenizer.py): int32 [B][npad], npad a multiple of 8 up to the context rounded up to 8, the same for every text of a
+ * call; eot[b] is the row of text b's end-of-text token, the row that is normalised and projected.  Every row is computed under
+ * the causal mask, so what follows a text's end-of-text token (padding ids) cannot reach it, and a text's embedding does not
+ * depend on the other texts of the call or on npad, bit for bit.  Pre-LN layers with quick-GELU, fp32 [proj_dim] out.          */
+typedef struct mhip_cliptext mhip_cliptext;
+typedef struct mhip_cliptext_config {
+  int vocab;               /* 49408                                                                                       */
+  int context;             /* 77; at most 128                                                                             */
+  int dim, heads, depth;   /* 512/8/12 (ViT-B/32's text tower); head dim must be 64, dim <= 1024                           */
+  int ffn;                 /* 2048; a multiple of 64                                                                      */
+  int proj_dim;            /* 512                                                                                         */
+  float ln_eps;            /* 1e-5                                                                                        */
+} mhip_cliptext_config;
+int mhip_cliptext_create(mhip_ctx* ctx, int precision, const mhip_cliptext_config* cfg, mhip_cliptext** out);
+int mhip_cliptext_destroy(mhip_cliptext* m);
+/* keys of the OpenAI checkpoint's text tower: token_embedding.weight, positional_embedding, transformer.resblocks.N.{ln_1,
+ * attn.in_proj_weight,attn.in_proj_bias,attn.out_proj,ln_2,mlp.c_fc,mlp.c_proj}.*, ln_final.*, text_projection
+ * [dim][proj_dim]; any other key is MHIP_EINVAL                                                                              */
+int mhip_cliptext_set_tensor(mhip_cliptext* m, const char* key, const float* data, const int64_t* shape, int ndim);
+int mhip_cliptext_finalize(mhip_cliptext* m);
+int mhip_cliptext_alloc_arena(mhip_cliptext* m);
+int mhip_cliptext_arena(mhip_cliptext* m, void** arena_dev, size_t* bytes);
+/* bytes of context workspace one mhip_cliptext_embed_host call of B texts of npad rows lays out (0: bad arguments)           */
+size_t mhip_cliptext_workspace_bytes(mhip_cliptext* m, int B, int npad);
+/* B texts (1 .. 4096) -> emb_out fp32 [B][proj_dim].  MHIP_EINVAL, never a clamp: npad no multiple of 8 or above the context
+ * rounded up to 8, an id outside [0, vocab), an eot outside [1, npad)                                                         */
+int mhip_cliptext_embed_host(mhip_cliptext* m, const int32_t* ids, const int32_t* eot, int B, int npad, float* emb_out);
+/* the texts through the tower once, then cos_out[p] = x.y / max(|x| |y|, 1e-8) of the embeddings of texts pair_a[p], pair_b[p]
+ * (fp32 [n_pairs]); emb_out fp32 [B][proj_dim] or NULL                                                                        */
+int mhip_cliptext_embed_pairs_host(mhip_cliptext* m, const int32_t* ids, const int32_t* eot, int B, int npad,
+                                   const int32_t* pair_a, const int32_t* pair_b, int n_pairs, float* cos_out, float* emb_out);
+/* as embed_host, plus the residual stream after the embedding kernel and after every layer: taps_out fp32
+ * [depth + 1][B][npad][dim] (rows at positions past the context have a zero position row); emb_out may be NULL                */
+int mhip_cliptext_debug_taps_host(mhip_cliptext* m, const int32_t* ids, const int32_t* eot, int B, int npad, float* taps_out,
+                                  float* emb_out);
+/* The kernels alone on host arrays (parity tests).  table fp32 [vocab][D], pos [npad][D], ids [B][npad] -> h_out [B][npad][D]  */
+int mhip_cliptext_embed_rows_host(mhip_ctx* ctx, const float* table, const float* pos, const int32_t* ids, int B, int npad,
+                                  int vocab, int D, float* h_out);
+/* causal attention of B sequences of npad rows: q, k, v fp32 [B][npad][heads * 64], q already scaled by head_dim^-0.5 * log2(e);
+ * rounded to the precision's element type and laid out as the tower lays them out (q | k rows, V^T) -> out fp32, same shape    */
+int mhip_cliptext_attention_host(mhip_ctx* ctx, int precision, const float* q, const float* k, const float* v, int B, int heads,
+                                 int npad, float* out);
+/* h fp32 [B][npad][D], row row_of[i] of block i -> LayerNorm g / b [D] -> proj [D][E] -> emb_out fp32 [B][E]                   */
+int mhip_cliptext_head_host(mhip_ctx* ctx, const float* h, int B, int npad, int D, const float* g, const float* b, float eps,
+                            const float* proj, int E, const int32_t* row_of, float* emb_out);
+
 /* ---- word-box / line geometry of the DiT box processor (host, pure functions; no ctx) --------------------------------- */
 /* replaces: merge_boxes, marie/utils/overlap.py:268-330 (find_overlap_horizontal(center_y_overlap=0.5) :106-183,
  * merge_bboxes_as_block :186-204).  xyxy fp32 [n][4] -> out_xyxy fp32 (capacity n rows), *n_out rows.       */

@@ -175,6 +175,19 @@ _SIGNATURES = (
     ("mhip_clipvis_embed_rows_host", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_float, _vp]),
     ("mhip_clipvis_head_host", _i, [_vp, _vp, _i, _i, _i, _vp, _vp, C.c_float, _vp, _i, _vp]),
     ("mhip_clipvis_pair_cosine_host", _i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp]),
+    ("mhip_cliptext_create", _i, [_vp, _i, _vp, C.POINTER(_vp)]),
+    ("mhip_cliptext_destroy", _i, [_vp]),
+    ("mhip_cliptext_set_tensor", _i, [_vp, C.c_char_p, _vp, C.POINTER(C.c_int64), _i]),
+    ("mhip_cliptext_finalize", _i, [_vp]),
+    ("mhip_cliptext_alloc_arena", _i, [_vp]),
+    ("mhip_cliptext_arena", _i, [_vp, C.POINTER(_vp), C.POINTER(_sz)]),
+    ("mhip_cliptext_workspace_bytes", _sz, [_vp, _i, _i]),
+    ("mhip_cliptext_embed_host", _i, [_vp, _vp, _vp, _i, _i, _vp]),
+    ("mhip_cliptext_embed_pairs_host", _i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    ("mhip_cliptext_debug_taps_host", _i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    ("mhip_cliptext_embed_rows_host", _i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    ("mhip_cliptext_attention_host", _i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    ("mhip_cliptext_head_host", _i, [_vp, _vp, _i, _i, _i, _vp, _vp, C.c_float, _vp, _i, _vp, _vp]),
     ("mhip_max_page_size", _i, [_i, _i, _i, _i, C.c_double, C.POINTER(_i), C.POINTER(_i)]),
     ("mhip_resize_area_u8", _i, [_vp, _vp, _i, _i, _i, C.c_size_t, _vp, _i, _i]),
     ("mhip_resize_area_u8_host", _i, [_vp, _vp, _i, _i, _i, _vp, _i, _i]),
@@ -268,6 +281,12 @@ class LayoutLMv3Config(C.Structure):
 class ClipVisConfig(C.Structure):
     """mirror of mhip_clipvis_config (include/marie_hip.h)"""
     _fields_ = [("dim", C.c_int), ("depth", C.c_int), ("heads", C.c_int), ("patch", C.c_int), ("image_size", C.c_int),
+                ("ffn", C.c_int), ("proj_dim", C.c_int), ("ln_eps", C.c_float)]
+
+
+class ClipTextConfig(C.Structure):
+    """mirror of mhip_cliptext_config (include/marie_hip.h)"""
+    _fields_ = [("vocab", C.c_int), ("context", C.c_int), ("dim", C.c_int), ("heads", C.c_int), ("depth", C.c_int),
                 ("ffn", C.c_int), ("proj_dim", C.c_int), ("ln_eps", C.c_float)]
 
 

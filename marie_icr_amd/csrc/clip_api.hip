@@ -34,8 +34,6 @@ const float CLIP_MEAN[3] = {0.48145466f, 0.4578275f, 0.40821073f};
 const float CLIP_STD[3] = {0.26862954f, 0.26130258f, 0.27577711f};
 constexpr int MAX_CLIPS = 4096;
 
-std::string res(int i, const char* s) { return "visual.transformer.resblocks." + std::to_string(i) + "." + s; }
-
 // the buffers of one call of B clips (and n_pairs cosines)
 struct ClipRun {
   uint8_t* clips = nullptr;
@@ -89,16 +87,7 @@ int clipvis_forward(mhip_clipvis* m, int B, int swap_rb, const ClipRun& run, flo
   };
   if ((rc = tap(0))) return rc;
   const AttnDesc ad = encoder_attn_desc(w.qk, w.vt, w.ao, D, es, B, c.heads, NP, NT);
-  for (int i = 0; i < c.depth; ++i) {
-    if ((rc = mhip_launch_clipvis_layernorm(ctx, prec, run.h, a.d<float>(enc_blk(i, "ln1_g")), a.d<float>(enc_blk(i, "ln1_b")), w.ht, (int)R, D, c.ln_eps))) return rc;
-    if ((rc = encoder_block_attention(ctx, prec, a, i, w, ad))) return rc;
-    if ((rc = mhip_gemm(ctx, prec, w.ao, a.d(enc_blk(i, "ao_w")), (long long)R, D, D, nullptr, a.d<float>(enc_blk(i, "ao_b")), run.h, ACT_NONE, 1, run.h))) return rc;
-    if ((rc = mhip_launch_clipvis_layernorm(ctx, prec, run.h, a.d<float>(enc_blk(i, "ln2_g")), a.d<float>(enc_blk(i, "ln2_b")), w.ht, (int)R, D, c.ln_eps))) return rc;
-    if ((rc = mhip_gemm(ctx, prec, w.ht, a.d(enc_blk(i, "fc1_w")), (long long)R, F, D, nullptr, a.d<float>(enc_blk(i, "fc1_b")), w.hid, ACT_NONE, 0))) return rc;
-    if ((rc = mhip_launch_quick_gelu(ctx, prec, w.hid, (long long)R * F))) return rc;
-    if ((rc = mhip_gemm(ctx, prec, w.hid, a.d(enc_blk(i, "fc2_w")), (long long)R, D, F, nullptr, a.d<float>(enc_blk(i, "fc2_b")), run.h, ACT_NONE, 1, run.h))) return rc;
-    if ((rc = tap(i + 1))) return rc;
-  }
+  if ((rc = clip_encoder_layers(ctx, prec, a, c.depth, D, F, c.ln_eps, R, run.h, w, ad, tap))) return rc;
   return mhip_launch_clipvis_head(ctx, run.h, B, NP, D, a.d<float>("ln_post_g"), a.d<float>("ln_post_b"), c.ln_eps, a.d<float>("proj_t"),
                                   c.proj_dim, run.emb);
 }
@@ -203,27 +192,9 @@ extern "C" int mhip_clipvis_finalize(mhip_clipvis* m) {
   float* pt = (float*)a.h("proj_t");
   for (int k = 0; k < D; ++k)
     for (int j = 0; j < E; ++j) pt[(size_t)j * D + k] = pj->data[(size_t)k * E + j];
-  const size_t DD = (size_t)D * D;
   for (int i = 0; i < c.depth; ++i) {
-    const HostTensor* iw = st.find(ctx, res(i, "attn.in_proj_weight"), {3 * D, D});
-    const HostTensor* ib = st.find(ctx, res(i, "attn.in_proj_bias"), {3 * D});
-    const HostTensor* ow = st.find(ctx, res(i, "attn.out_proj.weight"), {D, D});
-    const HostTensor* ob = st.find(ctx, res(i, "attn.out_proj.bias"), {D});
-    const HostTensor* g1 = st.find(ctx, res(i, "ln_1.weight"), {D});
-    const HostTensor* b1 = st.find(ctx, res(i, "ln_1.bias"), {D});
-    const HostTensor* g2 = st.find(ctx, res(i, "ln_2.weight"), {D});
-    const HostTensor* b2 = st.find(ctx, res(i, "ln_2.bias"), {D});
-    const HostTensor* fw = st.find(ctx, res(i, "mlp.c_fc.weight"), {F, D});
-    const HostTensor* fb = st.find(ctx, res(i, "mlp.c_fc.bias"), {F});
-    const HostTensor* dw = st.find(ctx, res(i, "mlp.c_proj.weight"), {D, F});
-    const HostTensor* db = st.find(ctx, res(i, "mlp.c_proj.bias"), {D});
-    if (!iw || !ib || !ow || !ob || !g1 || !b1 || !g2 || !b2 || !fw || !fb || !dw || !db) return MHIP_ESTATE;
-    EncoderBlockWeights w;      // in_proj holds q, k, v one after another
-    w.wq = iw->data.data(); w.wk = w.wq + DD; w.wv = w.wq + 2 * DD;
-    w.bq = ib->data.data(); w.bk = w.bq + D; w.bv = w.bq + 2 * D;
-    w.wo = ow->data.data(); w.bo = ob->data.data();
-    w.ln1_g = g1->data.data(); w.ln1_b = b1->data.data(); w.ln2_g = g2->data.data(); w.ln2_b = b2->data.data();
-    w.w1 = fw->data.data(); w.b1 = fb->data.data(); w.w2 = dw->data.data(); w.b2 = db->data.data();
+    EncoderBlockWeights w;
+    if (!clip_resblock_weights(ctx, st, "visual.transformer.resblocks.", i, D, F, &w)) return MHIP_ESTATE;
     encoder_block_fill(a, prec, i, D, F, w);
   }
   int rc = a.upload(ctx);

@@ -152,7 +152,7 @@ __global__ __launch_bounds__(256) void quick_gelu_kernel(T* __restrict__ x, long
 }
 
 // ------------------------------------------------------------------------------------------------------- head
-// y = LN(h[img][0]) (post_layernorm), emb[img][j] = sum_k y[k] * proj_t[j][k] (no bias).  proj_t is the projection transposed,
+// y = LN(h[img][row_of ? row_of[img] : 0]) (post_layernorm / ln_final), emb[img][j] = sum_k y[k] * proj_t[j][k] (no bias).  proj_t is the projection transposed,
 // [E][D] fp32: a wave per output, lanes along k.  A workgroup takes HEAD_COLS outputs of one image and normalises the row for
 // itself (one row: cheaper than a pass that stores it); one workgroup an image left 64 of them walking the whole matrix
 // (134 us at B = 64).
@@ -160,11 +160,11 @@ constexpr int HEAD_COLS = 32;
 
 __global__ __launch_bounds__(256) void clipvis_head_kernel(const float* __restrict__ h, int npad, int D, const float* __restrict__ g,
                                                            const float* __restrict__ b, float eps, const float* __restrict__ proj_t,
-                                                           int E, float* __restrict__ emb) {
+                                                           int E, float* __restrict__ emb, const int* __restrict__ row_of) {
   __shared__ __attribute__((aligned(16))) float ys[1024];
   const int img = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (wave == 0) {
-    const float* x = h + (size_t)img * npad * D;
+    const float* x = h + ((size_t)img * npad + (row_of ? row_of[img] : 0)) * D;
     float4v v[ROW_GROUPS];
 #pragma unroll
     for (int i = 0; i < ROW_GROUPS; ++i) {
@@ -264,9 +264,9 @@ int mhip_launch_quick_gelu(mhip_ctx* ctx, int precision, void* x, long long n) {
 }
 
 int mhip_launch_clipvis_head(mhip_ctx* ctx, const float* h, int B, int npad, int D, const float* g, const float* b, float eps,
-                             const float* proj_t, int E, float* emb) {
+                             const float* proj_t, int E, float* emb, const int* row_of) {
   if (B <= 0 || npad < 1 || !row_width_ok(D) || E < 1 || E > 65535 * HEAD_COLS) return mhip_fail(ctx, MHIP_EINVAL, "clipvis_head: B=%d D=%d E=%d", B, D, E);
-  PROF_LAUNCH(ctx, MHIP_K_CLIPVIS_HEAD, hipLaunchKernelGGL(clipvis_head_kernel, dim3(B, (E + HEAD_COLS - 1) / HEAD_COLS), dim3(256), 0, ctx->stream, h, npad, D, g, b, eps, proj_t, E, emb));
+  PROF_LAUNCH(ctx, MHIP_K_CLIPVIS_HEAD, hipLaunchKernelGGL(clipvis_head_kernel, dim3(B, (E + HEAD_COLS - 1) / HEAD_COLS), dim3(256), 0, ctx->stream, h, npad, D, g, b, eps, proj_t, E, emb, row_of));
   CHECK_LAUNCH(ctx, "clipvis_head");
   return 0;
 }

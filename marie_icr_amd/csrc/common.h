@@ -46,7 +46,10 @@ enum MhipKernelId {
   MHIP_K_QUICK_GELU = 26,        // x * sigmoid(1.702 x) in place
   MHIP_K_CLIPVIS_HEAD = 27,      // post_layernorm of the class row + projection
   MHIP_K_PAIR_COSINE = 28,       // cosine of embedding pairs by index
-  MHIP_K_COUNT = 29
+  // CLIP text tower (cliptext_ops.hip)
+  MHIP_K_CLIPTEXT_EMBED = 29,    // token table gather + position rows -> fp32 stream
+  MHIP_K_ATTN_CAUSAL = 30,       // causal soft-max attention, one workgroup per (sequence, head), K / V^T held in LDS
+  MHIP_K_COUNT = 31
 };
 
 constexpr int MHIP_ZERO_BYTES = 65536;
@@ -579,11 +582,17 @@ int mhip_launch_clipvis_layernorm(mhip_ctx* ctx, int precision, const float* x, 
                                   int D, float eps);
 // x [n] T in place; n a multiple of 16 bytes' worth of elements
 int mhip_launch_quick_gelu(mhip_ctx* ctx, int precision, void* x, long long n);
-// emb [B][E] fp32 = LN(h[img * npad]) proj_t^T, proj_t [E][D] fp32
+// emb [B][E] fp32 = LN(h[img * npad + row_of[img]]) proj_t^T, proj_t [E][D] fp32; row_of (device, [B]) null: row 0 of every block
 int mhip_launch_clipvis_head(mhip_ctx* ctx, const float* h, int B, int npad, int D, const float* g, const float* b, float eps,
-                             const float* proj_t, int E, float* emb);
+                             const float* proj_t, int E, float* emb, const int* row_of = nullptr);
 // out[p] = cos(emb[pair_a[p]], emb[pair_b[p]]), emb [..][E] fp32; the indices are the caller's to check
 int mhip_launch_pair_cosine(mhip_ctx* ctx, const float* emb, int E, const int* pair_a, const int* pair_b, int n_pairs, float* out);
+// ------------------------------------------------------------------ CLIP text tower ops (cliptext_ops.hip)
+// h [B*npad][D] fp32 = table[ids[row]] + pos[row % npad]; table [vocab][D], pos [>= npad][D] fp32; the ids are the caller's to check
+int mhip_launch_cliptext_embed(mhip_ctx* ctx, const float* table, const float* pos, const int* ids, float* h, int B, int npad, int D);
+// causal softmax(Q K^T) V over AttnDesc's layout (query row t sees keys 0 .. t): npad_q == npad_k <= 128, a multiple of 8; every
+// row < npad is written, nothing past a sequence's rows is read (no slack needed)
+int mhip_launch_attention_causal(mhip_ctx* ctx, int precision, const AttnDesc& d);
 size_t mhip_pil_resize_fragments_scratch(const mhip_crop_desc* descs, int n, int dh, int dw, int filter);
 int mhip_pil_resize_fragments(mhip_ctx* ctx, const uint8_t* base_dev, const mhip_crop_desc* descs, int n, uint8_t* dst, int dh,
                               int dw, int filter, void* scratch, size_t scratch_bytes);

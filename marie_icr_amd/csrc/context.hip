@@ -22,7 +22,8 @@ static const char* kKernelNames[MHIP_K_COUNT] = {"conv_first", "conv_igemm", "ls
                                                  "conv_igemm<64>", "conv_igemm<128>", "conv_igemm<256>", "conv_igemm<1128>",
                                                  "conv3x3_patch", "cross_attn", "attn_bias",
                                                  "vq_assign", "vq_kmeans", "vq_heatmap", "vq_peaks", "clip_cosine",
-                                                 "clipvis_patchify", "clipvis_embed", "quick_gelu", "clipvis_head", "pair_cosine"};
+                                                 "clipvis_patchify", "clipvis_embed", "quick_gelu", "clipvis_head", "pair_cosine",
+                                                 "cliptext_embed", "attn_causal"};
 
 extern "C" int mhip_kernel_count(void) { return MHIP_K_COUNT; }
 extern "C" const char* mhip_kernel_name(int k) { return (k >= 0 && k < MHIP_K_COUNT) ? kKernelNames[k] : ""; }

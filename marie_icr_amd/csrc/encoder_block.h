@@ -1,8 +1,9 @@
-// encoder_block.h — the transformer encoder layer the ViT (vit_api.hip), LayoutLMv3 (layoutlmv3_api.hip) and CLIP (clip_api.hip)
-// towers share, host side: its arena entries and how the checkpoint's weights are packed into them, its workspace, and the
+// encoder_block.h — the transformer encoder layer the ViT (vit_api.hip), LayoutLMv3 (layoutlmv3_api.hip) and CLIP (clip_api.hip,
+// cliptext_api.hip) towers share, host side: its arena entries and how the checkpoint's weights are packed into them, its workspace, and the
 // attention half of a layer
 //   q|k = ht Wqk^T + b        V^T = Wv ht^T        ao = attention(q, k, V^T)
-// The LayerNorms, the residual wiring and the MLP activation differ between the towers and stay in the model files.
+// The LayerNorms, the residual wiring and the MLP activation differ between the towers and stay in the model files; the two
+// CLIP towers agree on them too (pre-LN, quick-GELU, fp32 stream) and share clip_encoder_layers below.
 #pragma once
 #include "weights_util.h"
 
@@ -60,6 +61,32 @@ inline void encoder_block_fill(Arena& a, int prec, int i, int D, int F, const En
   memcpy(a.h(enc_blk(i, "fc2_b")), w.b2, (size_t)D * 4);
 }
 
+// block i of a CLIP tower as the OpenAI checkpoints hold it, `prefix` + "N.{ln_1, attn.in_proj_*, attn.out_proj, ln_2, mlp.c_fc,
+// mlp.c_proj}": in_proj holds q, k, v one after another.  false (the error is set) when a tensor is missing or misshapen
+inline bool clip_resblock_weights(mhip_ctx* ctx, const TensorStore& st, const std::string& prefix, int i, int D, int F, EncoderBlockWeights* w) {
+  const std::string p = prefix + std::to_string(i) + ".";
+  const HostTensor* iw = st.find(ctx, p + "attn.in_proj_weight", {3 * D, D});
+  const HostTensor* ib = st.find(ctx, p + "attn.in_proj_bias", {3 * D});
+  const HostTensor* ow = st.find(ctx, p + "attn.out_proj.weight", {D, D});
+  const HostTensor* ob = st.find(ctx, p + "attn.out_proj.bias", {D});
+  const HostTensor* g1 = st.find(ctx, p + "ln_1.weight", {D});
+  const HostTensor* b1 = st.find(ctx, p + "ln_1.bias", {D});
+  const HostTensor* g2 = st.find(ctx, p + "ln_2.weight", {D});
+  const HostTensor* b2 = st.find(ctx, p + "ln_2.bias", {D});
+  const HostTensor* fw = st.find(ctx, p + "mlp.c_fc.weight", {F, D});
+  const HostTensor* fb = st.find(ctx, p + "mlp.c_fc.bias", {F});
+  const HostTensor* dw = st.find(ctx, p + "mlp.c_proj.weight", {D, F});
+  const HostTensor* db = st.find(ctx, p + "mlp.c_proj.bias", {D});
+  if (!iw || !ib || !ow || !ob || !g1 || !b1 || !g2 || !b2 || !fw || !fb || !dw || !db) return false;
+  const size_t DD = (size_t)D * D;
+  w->wq = iw->data.data(); w->wk = w->wq + DD; w->wv = w->wq + 2 * DD;
+  w->bq = ib->data.data(); w->bk = w->bq + D; w->bv = w->bq + 2 * D;
+  w->wo = ow->data.data(); w->bo = ob->data.data();
+  w->ln1_g = g1->data.data(); w->ln1_b = b1->data.data(); w->ln2_g = g2->data.data(); w->ln2_b = b2->data.data();
+  w->w1 = fw->data.data(); w->b1 = fb->data.data(); w->w2 = dw->data.data(); w->b2 = db->data.data();
+  return true;
+}
+
 // the buffers of the layers of one call of R = images * npad token rows, element type T
 struct EncoderWs {
   char* ht = nullptr;    // [R][D] the layer's input rows (a LayerNorm's output)
@@ -101,7 +128,12 @@ inline int encoder_block_qkv(mhip_ctx* ctx, int prec, const Arena& a, int i, con
   return mhip_gemm(ctx, prec, a.d(enc_blk(i, "v_w")), w.ht, D, R, D, nullptr, nullptr, w.vt, ACT_NONE, 0);   // V^T = W_v X^T
 }
 
-// the attention half of block i, w.ht -> w.ao: plain, or with LayoutLMv3's bias and key mask (bd.a the descriptor)
+// the causal attention of the CLIP text tower over the same buffers (cliptext_ops.hip)
+struct AttnCausalDesc {
+  AttnDesc a;
+};
+
+// the attention half of block i, w.ht -> w.ao: plain, with LayoutLMv3's bias and key mask (bd.a the descriptor), or causal
 inline int encoder_block_attention(mhip_ctx* ctx, int prec, const Arena& a, int i, const EncoderWs& w, const AttnDesc& ad) {
   const int rc = encoder_block_qkv(ctx, prec, a, i, w, ad);
   return rc ? rc : mhip_launch_attention(ctx, prec, ad);
@@ -109,4 +141,29 @@ inline int encoder_block_attention(mhip_ctx* ctx, int prec, const Arena& a, int 
 inline int encoder_block_attention(mhip_ctx* ctx, int prec, const Arena& a, int i, const EncoderWs& w, const AttnBiasDesc& bd) {
   const int rc = encoder_block_qkv(ctx, prec, a, i, w, bd.a);
   return rc ? rc : mhip_launch_attention_bias(ctx, prec, bd);
+}
+inline int encoder_block_attention(mhip_ctx* ctx, int prec, const Arena& a, int i, const EncoderWs& w, const AttnCausalDesc& cd) {
+  const int rc = encoder_block_qkv(ctx, prec, a, i, w, cd.a);
+  return rc ? rc : mhip_launch_attention_causal(ctx, prec, cd.a);
+}
+
+// The layers of a CLIP tower (vision: AttnDesc, text: AttnCausalDesc) on the fp32 stream h [R][D]:
+//   ht = LN1(h)   ao = attention(ht)          h += ao Wo^T + (bo + Wo bv)
+//   ht = LN2(h)   hid = quick_gelu(ht W1^T + b1)              h += hid W2^T + b2
+// tap(i + 1) runs after layer i
+template <typename AD, typename Tap>
+int clip_encoder_layers(mhip_ctx* ctx, int prec, const Arena& a, int depth, int D, int F, float ln_eps, size_t R, float* h,
+                        const EncoderWs& w, const AD& ad, Tap&& tap) {
+  int rc;
+  for (int i = 0; i < depth; ++i) {
+    if ((rc = mhip_launch_clipvis_layernorm(ctx, prec, h, a.d<float>(enc_blk(i, "ln1_g")), a.d<float>(enc_blk(i, "ln1_b")), w.ht, (int)R, D, ln_eps))) return rc;
+    if ((rc = encoder_block_attention(ctx, prec, a, i, w, ad))) return rc;
+    if ((rc = mhip_gemm(ctx, prec, w.ao, a.d(enc_blk(i, "ao_w")), (long long)R, D, D, nullptr, a.d<float>(enc_blk(i, "ao_b")), h, ACT_NONE, 1, h))) return rc;
+    if ((rc = mhip_launch_clipvis_layernorm(ctx, prec, h, a.d<float>(enc_blk(i, "ln2_g")), a.d<float>(enc_blk(i, "ln2_b")), w.ht, (int)R, D, ln_eps))) return rc;
+    if ((rc = mhip_gemm(ctx, prec, w.ht, a.d(enc_blk(i, "fc1_w")), (long long)R, F, D, nullptr, a.d<float>(enc_blk(i, "fc1_b")), w.hid, ACT_NONE, 0))) return rc;
+    if ((rc = mhip_launch_quick_gelu(ctx, prec, w.hid, (long long)R * F))) return rc;
+    if ((rc = mhip_gemm(ctx, prec, w.hid, a.d(enc_blk(i, "fc2_w")), (long long)R, D, F, nullptr, a.d<float>(enc_blk(i, "fc2_b")), h, ACT_NONE, 1, h))) return rc;
+    if ((rc = tap(i + 1))) return rc;
+  }
+  return MHIP_OK;
 }

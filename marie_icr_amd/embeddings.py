@@ -1,4 +1,5 @@
-"""CLIP image embeddings on the MI355X: ``OpenAIEmbeddings`` / ``OpenAITransformerEmbeddings`` behind the reference's surface.
+"""CLIP image and text embeddings on the MI355X: ``OpenAIEmbeddings`` / ``OpenAITransformerEmbeddings`` behind the reference's
+surface.
 
 Mirrors marie/embeddings/{embeddings_object,base}.py and marie/embeddings/openai/{openai_embeddings,openai_trans_embeddings}.py
 for what ``VQNNFTemplateMatcher.score`` takes from them: the image embedding of a 224 x 224 snippet clip, 95 % of the weighted
@@ -7,9 +8,12 @@ processor — ``convert("RGB")``, Pillow BICUBIC resize of the shortest edge, ce
 the detector already has, and CLIP's normalisation is part of the patch kernel.
 
 Built: the ViT towers (ViT-B/32, ViT-B/16, any width of 64-wide heads up to 1024) from an OpenAI-scheme (``visual.*``) or a
-``transformers``-scheme (``vision_model.*`` + ``visual_projection``) state dict.  Not built: the ``ModifiedResNet`` towers
-(``RN50x4`` ...: ``NotImplementedError``), the text tower and its BPE (``image=None``: ``NotImplementedError``).  Errors raise
-``MarieHipError``; the reference's ``try/except`` returning an empty ``EmbeddingsObject`` is not restated.
+``transformers``-scheme (``vision_model.*`` + ``visual_projection``) state dict, and the text tower of the same checkpoint
+(csrc/cliptext_api.hip, ``mhip_cliptext_*``: causal attention in HIP) with its BPE (clip_tokenizer.py) where the checkpoint holds
+one and a vocabulary is at hand: ``get_embeddings(texts, image=None)`` embeds ``" ".join(texts)``.  Not built: the
+``ModifiedResNet`` towers (``RN50x4`` ...: ``NotImplementedError``).  Without a text side ``image=None`` raises
+``NotImplementedError``.  Errors raise ``MarieHipError`` (a text longer than the context: ``ValueError``); the reference's
+``try/except`` returning an empty ``EmbeddingsObject`` is not restated.
 """
 from __future__ import annotations
 
@@ -23,7 +27,8 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from ._lib import PREC_F16, PREC_F32, ClipVisConfig, Context, MarieHipError, ModelHandle, check
+from ._lib import PREC_F16, PREC_F32, ClipTextConfig, ClipVisConfig, Context, MarieHipError, ModelHandle, check
+from .clip_tokenizer import ClipTokenizer
 
 logger = logging.getLogger(__name__)
 
@@ -69,28 +74,39 @@ def _f32(t) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(t), dtype=np.float32)
 
 
-def _from_transformers(sd: Dict[str, Any]) -> Dict[str, np.ndarray]:
-    """the ``transformers`` key scheme -> the OpenAI one: q / k / v concatenated into ``in_proj``, the projection transposed"""
+_HF_TEXT_TOP = {"text_model.embeddings.token_embedding.weight": "token_embedding.weight",
+                "text_model.embeddings.position_embedding.weight": "positional_embedding",
+                "text_model.final_layer_norm.weight": "ln_final.weight", "text_model.final_layer_norm.bias": "ln_final.bias"}
+# a tower of the ``transformers`` scheme: (top-level keys, projection key -> its OpenAI key, layer prefix -> its OpenAI prefix)
+_HF_VISION = (_HF_TOP, "visual_projection.weight", "visual.proj", "vision_model", "visual.transformer")
+_HF_TEXT = (_HF_TEXT_TOP, "text_projection.weight", "text_projection", "text_model", "transformer")
+
+
+def _from_transformers(sd: Dict[str, Any], tower=_HF_VISION) -> Dict[str, np.ndarray]:
+    """one tower of the ``transformers`` key scheme -> the OpenAI one: q / k / v concatenated into ``in_proj``, the projection
+    transposed"""
+    top, proj_in, proj_out, hf_prefix, out_prefix = tower
+    layer = re.compile(re.escape(hf_prefix) + r"\.encoder\.layers\.(\d+)\.(.+)\.(weight|bias)$")
     out, qkv = {}, {}
     for key, val in sd.items():
-        if key in _HF_TOP:
-            out[_HF_TOP[key]] = _f32(val)
-        elif key == "visual_projection.weight":
-            out["visual.proj"] = np.ascontiguousarray(_f32(val).T)
+        if key in top:
+            out[top[key]] = _f32(val)
+        elif key == proj_in:
+            out[proj_out] = np.ascontiguousarray(_f32(val).T)
         else:
-            m = re.match(r"vision_model\.encoder\.layers\.(\d+)\.(.+)\.(weight|bias)$", key)
+            m = layer.match(key)
             if not m:
-                continue                                        # the text tower, logit_scale, position_ids
+                continue                                        # the other tower, logit_scale, position_ids
             n, name, kind = int(m.group(1)), m.group(2), m.group(3)
             if name in ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"):
                 qkv[(n, kind, name[10])] = _f32(val)
             elif name in _HF_LAYER:
-                out[f"visual.transformer.resblocks.{n}.{_HF_LAYER[name]}.{kind}"] = _f32(val)
+                out[f"{out_prefix}.resblocks.{n}.{_HF_LAYER[name]}.{kind}"] = _f32(val)
     for n, kind in sorted({(n, kind) for n, kind, _ in qkv}):
         parts = [qkv.get((n, kind, p)) for p in "qkv"]
         if any(p is None for p in parts):
             raise MarieHipError(f"CLIP checkpoint: layer {n} lacks one of q_proj / k_proj / v_proj ({kind})")
-        out[f"visual.transformer.resblocks.{n}.attn.in_proj_{kind}"] = np.concatenate(parts, axis=0)
+        out[f"{out_prefix}.resblocks.{n}.attn.in_proj_{kind}"] = np.concatenate(parts, axis=0)
     return out
 
 
@@ -123,6 +139,38 @@ def load_clip_vision_state(checkpoint: Dict[str, Any]) -> Tuple[Dict[str, np.nda
     cfg.heads = cfg.dim // 64
     cfg.ffn = int(state["visual.transformer.resblocks.0.mlp.c_fc.weight"].shape[0])
     cfg.proj_dim = int(state["visual.proj"].shape[1])
+    cfg.ln_eps = 1e-5
+    return state, cfg
+
+
+_TEXT_KEYS = ("token_embedding.weight", "positional_embedding", "text_projection")
+
+
+def load_clip_text_state(checkpoint: Dict[str, Any]) -> Optional[Tuple[Dict[str, np.ndarray], ClipTextConfig]]:
+    """The text tower of a ``torch.load``-ed CLIP checkpoint (either key scheme, as :func:`load_clip_vision_state` takes it) ->
+    (its tensors under the OpenAI keys as float32 arrays, the geometry read from their shapes as ``clip.build_model`` reads
+    it), or None when the checkpoint holds no text tower."""
+    sd = checkpoint.get("model_state_dict", checkpoint) if isinstance(checkpoint, dict) else None
+    if not isinstance(sd, dict) or not sd:
+        raise MarieHipError("CLIP checkpoint: expected a state dict or {'model_state_dict': state dict}")
+    if any(k.startswith("text_model.") for k in sd):
+        state = _from_transformers(sd, _HF_TEXT)
+    elif "token_embedding.weight" in sd:
+        state = {k: _f32(v) for k, v in sd.items()
+                 if k in _TEXT_KEYS or k.startswith("transformer.resblocks.") or k.startswith("ln_final.")}
+    else:
+        return None
+    for need in _TEXT_KEYS + ("ln_final.weight", "transformer.resblocks.0.mlp.c_fc.weight"):
+        if need not in state:
+            raise MarieHipError(f"CLIP checkpoint: the text tower has no {need}")
+    tok, pos = state["token_embedding.weight"], state["positional_embedding"]
+    cfg = ClipTextConfig()
+    cfg.vocab, cfg.dim = int(tok.shape[0]), int(tok.shape[1])
+    cfg.context = int(pos.shape[0])
+    cfg.heads = cfg.dim // 64
+    cfg.depth = len([k for k in state if k.startswith("transformer.resblocks.") and k.endswith(".attn.in_proj_weight")])
+    cfg.ffn = int(state["transformer.resblocks.0.mlp.c_fc.weight"].shape[0])
+    cfg.proj_dim = int(state["text_projection"].shape[1])
     cfg.ln_eps = 1e-5
     return state, cfg
 
@@ -183,7 +231,89 @@ class ClipVisionModel(ModelHandle):
         return taps, emb
 
 
-# ---- the kernels on host arrays (what tests/test_clip_gpu.py drives)
+class ClipTextModel(ModelHandle):
+    """``mhip_cliptext``: the text tower + projection on a :class:`Context`.  Ids come from :class:`ClipTokenizer`."""
+
+    def __init__(self, ctx: Context, state: Optional[Dict[str, np.ndarray]], config: ClipTextConfig, precision: int = PREC_F16):
+        self.cfg, self.precision = config, int(precision)
+        super().__init__(ctx, "cliptext", self.precision, C.byref(config))
+        if state is not None:
+            self.load_state(state)
+
+    @staticmethod
+    def _ids(ids, eot) -> Tuple[np.ndarray, np.ndarray]:
+        ids, eot = np.ascontiguousarray(ids, np.int32), np.ascontiguousarray(eot, np.int32).reshape(-1)
+        if ids.ndim != 2 or ids.shape[0] < 1 or eot.shape[0] != ids.shape[0]:
+            raise ValueError(f"ids of shape (n, npad) and eot of shape (n,) expected, got {ids.shape} and {eot.shape}")
+        return ids, eot
+
+    def workspace_bytes(self, n: int, npad: int) -> int:
+        return int(self.lib.mhip_cliptext_workspace_bytes(self.h, int(n), int(npad)))
+
+    def embed_ids_host(self, ids, eot) -> np.ndarray:
+        """ids int32 (n, npad), eot int32 (n,) -> embeddings fp32 (n, proj_dim), one tower call"""
+        ids, eot = self._ids(ids, eot)
+        out = np.empty((ids.shape[0], self.cfg.proj_dim), np.float32)
+        self._call("embed_host", _vp(ids), _vp(eot), ids.shape[0], ids.shape[1], _vp(out))
+        return out
+
+    def embed_pairs_host(self, ids, eot, pairs, want_embeddings: bool = False):
+        """the texts through the tower once and the cosine of every (a, b) index pair -> fp32 (n_pairs,)
+        (, embeddings (n, proj_dim))"""
+        ids, eot = self._ids(ids, eot)
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        pa, pb = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
+        cos = np.empty(len(pairs), np.float32)
+        emb = np.empty((ids.shape[0], self.cfg.proj_dim), np.float32) if want_embeddings else None
+        self._call("embed_pairs_host", _vp(ids), _vp(eot), ids.shape[0], ids.shape[1], _vp(pa), _vp(pb), len(pairs), _vp(cos), _vp(emb))
+        return (cos, emb) if want_embeddings else cos
+
+    def debug_taps_host(self, ids, eot):
+        """-> (taps fp32 (depth + 1, n, npad, dim): the residual stream after the embedding and after every layer,
+        embeddings (n, proj_dim))"""
+        ids, eot = self._ids(ids, eot)
+        n, npad = ids.shape
+        taps = np.empty((self.cfg.depth + 1, n, npad, self.cfg.dim), np.float32)
+        emb = np.empty((n, self.cfg.proj_dim), np.float32)
+        self._call("debug_taps_host", _vp(ids), _vp(eot), n, npad, _vp(taps), _vp(emb))
+        return taps, emb
+
+
+# ---- the kernels on host arrays (what tests/test_clip_gpu.py and tests/test_cliptext_gpu.py drive)
+def text_embed_rows_host(ctx: Context, table, pos, ids) -> np.ndarray:
+    """table (vocab, D), pos (npad, D), ids int32 (B, npad) -> h fp32 (B, npad, D) = table[ids] + pos"""
+    table, pos = np.ascontiguousarray(table, np.float32), np.ascontiguousarray(pos, np.float32)
+    ids = np.ascontiguousarray(ids, np.int32)
+    B, npad = ids.shape
+    out = np.empty((B, npad, table.shape[1]), np.float32)
+    check(ctx.h, ctx.lib.mhip_cliptext_embed_rows_host(ctx.h, _vp(table), _vp(pos), _vp(ids), B, npad, table.shape[0], table.shape[1],
+                                                       _vp(out)), "mhip_cliptext_embed_rows_host")
+    return out
+
+
+def causal_attention_host(ctx: Context, precision: int, q, k, v, heads: int) -> np.ndarray:
+    """q, k, v fp32 (B, npad, heads * 64), q already scaled by head_dim^-0.5 * log2(e) -> fp32, same shape"""
+    q, k, v = (np.ascontiguousarray(a, np.float32) for a in (q, k, v))
+    B, npad, D = q.shape
+    if D != heads * 64 or k.shape != q.shape or v.shape != q.shape:
+        raise ValueError(f"q, k, v of shape (B, npad, {heads * 64}) expected, got {q.shape}, {k.shape}, {v.shape}")
+    out = np.empty_like(q)
+    check(ctx.h, ctx.lib.mhip_cliptext_attention_host(ctx.h, int(precision), _vp(q), _vp(k), _vp(v), B, int(heads), npad, _vp(out)),
+          "mhip_cliptext_attention_host")
+    return out
+
+
+def text_head_host(ctx: Context, h, g, b, proj, row_of, eps: float = 1e-5) -> np.ndarray:
+    """h (B, npad, D) (row row_of[i] of block i), LayerNorm g / b (D), proj (D, E) -> fp32 (B, E)"""
+    h, g, b, proj = (np.ascontiguousarray(a, np.float32) for a in (h, g, b, proj))
+    row_of = np.ascontiguousarray(row_of, np.int32)
+    B, npad, D = h.shape
+    out = np.empty((B, proj.shape[1]), np.float32)
+    check(ctx.h, ctx.lib.mhip_cliptext_head_host(ctx.h, _vp(h), B, npad, D, _vp(g), _vp(b), float(eps), _vp(proj), proj.shape[1],
+                                                 _vp(row_of), _vp(out)), "mhip_cliptext_head_host")
+    return out
+
+
 def quick_gelu_host(ctx: Context, precision: int, x) -> np.ndarray:
     x = np.ascontiguousarray(x, np.float32).reshape(-1)
     out = np.empty_like(x)
@@ -255,9 +385,12 @@ class ClipImageEmbeddings(EmbeddingsBase):
                  use_gpu: bool = True, batch_size: int = 16, use_auth_token: Optional[Union[str, bool]] = None,
                  devices: Optional[List[Any]] = None, show_error: Optional[Union[str, bool]] = True, *,
                  state: Optional[Dict[str, Any]] = None, precision: Union[str, int] = "f16", ctx: Optional[Context] = None,
-                 **kwargs):
+                 text: Optional[bool] = None, tokenizer: Optional[ClipTokenizer] = None, **kwargs):
         """``model_name_or_path``: a model directory holding ``pytorch_model.bin`` (and, for ``OpenAIEmbeddings``,
-        ``marie.json``); ``state``: the loaded checkpoint instead (a state dict or ``{"model_state_dict": ...}``)."""
+        ``marie.json``); ``state``: the loaded checkpoint instead (a state dict or ``{"model_state_dict": ...}``).
+        ``text``: None builds the text side when the checkpoint holds a text tower and a vocabulary is at hand (``tokenizer``,
+        or ``vocab.json`` + ``merges.txt`` / ``bpe_simple_vocab_16e6.txt.gz`` in the model directory); True raises when either
+        is missing; False never builds it."""
         super().__init__(**kwargs)
         if not use_gpu:
             raise MarieHipError(f"{type(self).__name__} here is the MI355X path; use_gpu=False has no implementation")
@@ -266,6 +399,7 @@ class ClipImageEmbeddings(EmbeddingsBase):
         if state is None:
             state = self._load_checkpoint(model_name_or_path)
         tensors, cfg = load_clip_vision_state(state)
+        text_side = self._text_side(state, text, tokenizer, model_name_or_path)      # before any device work
         if isinstance(precision, str):
             if precision not in ("f16", "f32"):
                 raise ValueError(f"precision {precision!r}: 'f16' or 'f32'")
@@ -275,6 +409,32 @@ class ClipImageEmbeddings(EmbeddingsBase):
         self.image_size, self.proj_dim = cfg.image_size, cfg.proj_dim
         self.encoder_calls = 0               # device encoder calls so far
         self.clips_embedded = 0              # clips those calls carried
+        self.text_model, self.tokenizer = None, None
+        if text_side is not None:
+            (text_tensors, text_cfg), self.tokenizer = text_side
+            self.text_model = ClipTextModel(self.ctx, text_tensors, text_cfg, precision)
+            self.context_length = text_cfg.context
+        self.text_encoder_calls = 0          # device text tower calls so far
+        self.texts_embedded = 0              # texts those calls carried
+
+    def _text_side(self, state, text, tokenizer, model_dir):
+        """((tensors, config), tokenizer) of the text side to build, or None"""
+        if text is False:
+            return None
+        loaded = load_clip_text_state(state)
+        if loaded is not None and tokenizer is None:
+            tokenizer = ClipTokenizer.from_dir(model_dir, loaded[1].context)
+        missing = ([] if loaded is not None else ["the checkpoint holds no text tower"]) + \
+                  ([] if tokenizer is not None else ["no vocabulary (a tokenizer argument, or vocab.json + merges.txt / "
+                                                     "bpe_simple_vocab_16e6.txt.gz in the model directory)"])
+        if missing:
+            if text:
+                raise MarieHipError(f"{type(self).__name__}(text=True): " + "; ".join(missing))
+            return None
+        if len(tokenizer.encoder) > loaded[1].vocab:
+            raise MarieHipError(f"{type(self).__name__}: the vocabulary has {len(tokenizer.encoder)} entries, the token table "
+                                f"{loaded[1].vocab} rows")
+        return loaded, tokenizer
 
     def _load_checkpoint(self, path):
         import torch
@@ -288,6 +448,8 @@ class ClipImageEmbeddings(EmbeddingsBase):
 
     def close(self):
         self.model.close()
+        if getattr(self, "text_model", None) is not None:
+            self.text_model.close()
 
     # -- image processor ---------------------------------------------------------------------------------------------
     def preprocess(self, image) -> np.ndarray:
@@ -309,9 +471,17 @@ class ClipImageEmbeddings(EmbeddingsBase):
     # -- the reference's entry ---------------------------------------------------------------------------------------
     def get_embeddings(self, texts: List[str], truncation: bool = None, max_length: int = None, image=None,
                        boxes: List[List[int]] = None, **kwargs) -> EmbeddingsObject:
-        if image is None:
-            raise NotImplementedError("the CLIP text tower (get_embeddings without an image) is not built")
+        """the embedding of ``image``; without one, of ``" ".join(texts)`` (the reference's join).  ``truncation`` cuts a text
+        longer than the model's context, as ``clip.tokenize(truncate=True)``; ``max_length`` is not used: the context length
+        is the model's"""
         result = EmbeddingsObject()
+        if image is None:
+            if getattr(self, "text_model", None) is None:
+                raise NotImplementedError("get_embeddings without an image needs the CLIP text tower, and this instance has no "
+                                          "text side: the checkpoint holds no text tower, or no vocabulary was found")
+            result.embeddings = self.embed_texts([" ".join(texts)], truncation=bool(truncation))
+            result.total_tokens = -1
+            return result
         result.embeddings = self._embed(self.preprocess(image)[None], swap_rb=False)
         result.total_tokens = -1
         return result
@@ -334,6 +504,53 @@ class ClipImageEmbeddings(EmbeddingsBase):
         self.clips_embedded += len(clips)
         return self.model.embed_pairs_host(clips, pairs, want_embeddings=want_embeddings)
 
+    # -- the text side ---------------------------------------------------------------------------------------------------
+    TEXT_CHUNK = 1024      # texts of one tower call
+
+    def _need_text(self):
+        if getattr(self, "text_model", None) is None:
+            raise MarieHipError(f"{type(self).__name__}: no text side (the checkpoint holds no text tower, or no vocabulary)")
+
+    def _encode_texts(self, texts: Sequence[str], truncation: bool):
+        return self.tokenizer.encode_batch(texts, truncation=truncation, context_length=self.context_length)
+
+    def embed_texts(self, texts: Sequence[str], truncation: bool = False, chunk: Optional[int] = None) -> np.ndarray:
+        """-> fp32 (n, proj_dim); chunks of at most ``TEXT_CHUNK`` texts, one tower call per chunk.  A text's embedding does not
+        depend on its chunk, bit for bit."""
+        self._need_text()
+        texts = list(texts)
+        chunk = min(int(chunk or self.TEXT_CHUNK), self.TEXT_CHUNK)
+        if chunk < 1:
+            raise ValueError(f"chunk of {chunk} texts")
+        out = np.empty((len(texts), self.text_model.cfg.proj_dim), np.float32)
+        for at in range(0, len(texts), chunk):
+            ids, eot = self._encode_texts(texts[at:at + chunk], truncation)
+            self.text_encoder_calls += 1
+            self.texts_embedded += len(ids)
+            out[at:at + len(ids)] = self.text_model.embed_ids_host(ids, eot)
+        return out
+
+    def text_cosine_pairs(self, texts: Sequence[str], pairs: Sequence[Tuple[int, int]], want_embeddings: bool = False,
+                          truncation: bool = False):
+        """the cosine of the embeddings of every (a, b) index pair of ``texts`` -> fp32 (n_pairs,) (, embeddings fp32
+        (n, proj_dim)).  Duplicate texts are embedded once."""
+        self._need_text()
+        texts = list(texts)
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        if len(pairs) and (pairs.min() < 0 or pairs.max() >= len(texts)):
+            raise ValueError(f"a pair names a text outside 0 .. {len(texts) - 1}")
+        first: Dict[str, int] = {}
+        slot = np.array([first.setdefault(t, len(first)) for t in texts], np.int32)
+        unique = list(first)
+        if len(unique) <= self.TEXT_CHUNK and len(pairs):
+            ids, eot = self._encode_texts(unique, truncation)
+            self.text_encoder_calls += 1
+            self.texts_embedded += len(unique)
+            cos, emb = self.text_model.embed_pairs_host(ids, eot, slot[pairs], want_embeddings=True)
+        else:
+            emb = self.embed_texts(unique, truncation)
+            cos = pair_cosine_host(self.ctx, emb, slot[pairs]) if len(pairs) else np.empty(0, np.float32)
+        return (cos, emb[slot]) if want_embeddings else cos
 
     def pair_cosines(self, embeddings, pairs: Sequence[Tuple[int, int]]) -> np.ndarray:
         """the cosine kernel alone on embeddings already at hand, fp32 (n, proj_dim) -> fp32 (n_pairs,)"""

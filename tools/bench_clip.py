@@ -9,6 +9,10 @@ clips up, normalise, forward, embeddings back.
 Per-kernel share: run one batch size under the profiler, then summarise its statistics file:
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/bench_clip.py --profile-run 64
     python tools/bench_clip.py --stats-csv OUT/.../*kernel_stats.csv
+The text tower (ViT-B/32 text geometry, f16): python tools/bench_clip.py --text [--batches 1 256 1024]
+Per batch size, three-word texts over the synthetic vocabulary of tests/cliptext_ref.py, timed as `embed_texts` runs them —
+the host tokeniser, then `ClipTextModel.embed_ids_host`: ids up, the tower, the embeddings back, ending in a stream
+synchronise — and the tower call alone; then 256 texts of the full context (77 tokens in 80 rows).
 Prints one JSON line.  Nothing is asserted on these numbers; this is not bench.py.
 """
 from __future__ import annotations
@@ -92,9 +96,44 @@ def torch_comparator(state, cfg, device):
     return run
 
 
+def bench_text(args):
+    """the text tower at ViT-B/32 text geometry: three-word texts per batch size, and 256 texts of the full context"""
+    import tempfile
+
+    import cliptext_ref as T
+    from marie_icr_amd import embeddings
+    from marie_icr_amd._lib import PREC_F16, Context
+    from marie_icr_amd.clip_tokenizer import ClipTokenizer
+
+    ctx = Context(0)
+    with tempfile.TemporaryDirectory() as d:
+        T.make_vocab(d)
+        tok = ClipTokenizer.from_dir(d)
+    tensors, c = embeddings.load_clip_text_state(T.make_state(T.VIT_B32_TEXT, seed=0))
+    model = embeddings.ClipTextModel(ctx, tensors, c, PREC_F16)
+    words = ("the", "invoice", "total")
+    three = lambda i: " ".join(words[(i // 3 ** j) % 3] for j in range(3))
+    cases = [(f"{B} three-word texts", [three(i) for i in range(B)]) for B in (args.batches or [1, 256, 1024])]
+    cases.append(("256 texts of 77 tokens", [" ".join(words[(i + j) % 3] for j in range(75)) for i in range(256)]))
+    result = {"model": "ViT-B/32 text tower", "precision": "f16", "device": ctx.device_info(), "cases": {}}
+    for name, texts in cases:
+        ids, eot = tok.encode_batch(texts)
+        whole = timed(lambda: model.embed_ids_host(*tok.encode_batch(texts)), args.warmup, args.repeats, args.window)
+        tower = timed(lambda: model.embed_ids_host(ids, eot), args.warmup, args.repeats, args.window)
+        result["cases"][name] = {"rows_per_text": int(ids.shape[1]), "ms_per_call": round(whole[0] * 1e3, 3),
+                                 "ms_min_max": [round(whole[1] * 1e3, 3), round(whole[2] * 1e3, 3)],
+                                 "tower_ms_per_call": round(tower[0] * 1e3, 3),
+                                 "tower_ms_min_max": [round(tower[1] * 1e3, 3), round(tower[2] * 1e3, 3)],
+                                 "texts_per_s": round(len(texts) / whole[0], 1), "calls_per_window": whole[3],
+                                 "workspace_mb": round(model.workspace_bytes(len(texts), ids.shape[1]) / 2**20, 1)}
+    model.close()
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--batches", type=int, nargs="+", default=[1, 16, 64, 256])
+    ap.add_argument("--text", action="store_true", help="time the text tower instead")
+    ap.add_argument("--batches", type=int, nargs="+", default=None)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--window", type=float, default=0.3, help="least seconds of one timed window")
@@ -105,6 +144,9 @@ def main():
     if args.stats_csv:
         print(json.dumps({"kernel_share": summarise_stats(args.stats_csv)}))
         return
+    if args.text:
+        return bench_text(args)
+    args.batches = args.batches or [1, 16, 64, 256]
 
     import clip_ref as R
     from marie_icr_amd import embeddings
