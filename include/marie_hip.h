@@ -200,6 +200,16 @@ size_t mhip_crnn_workspace_bytes(mhip_crnn* m, int n, int w);
  * bench.py divides by the measured kernel time for the roofline line.                    */
 double mhip_crnn_kernel_flops(mhip_crnn* m, int kernel_id, int n, int w);
 
+/* The BiLSTM recurrence alone (one layer, both directions) on host inputs, through the weight packers and the launcher of the
+ * CRNN and ICR recognizers.  replaces: the recurrent part of nn.LSTM(input, 256, bidirectional=True, batch_first=True),
+ * marie/models/icr/modules/sequence_modeling.py:8,17 (h0 = c0 = 0), everything in PyTorch's own order:
+ *   whh    fp32 [2][1024][256]     weight_hh_l0, weight_hh_l0_reverse (gate rows i, f, g, o)
+ *   xproj  fp32 [B][T][2][1024]    x_t W_ih^T + b_ih + b_hh of the forward, then the reverse direction, gate-major
+ *   out    fp32 [B + 16][T][512]   h of the forward | reverse direction (f16 widened in the f16 mode).  The device buffer carries
+ *                                  16 guard rows (one workgroup tile) behind row B, is filled with 0xff bytes before the launch and
+ *                                  comes back whole: a cell never written, or a write past row B, shows (f16 0xffff widens to NaN). */
+int mhip_lstm_rec_host(mhip_ctx* ctx, int precision, int B, int T, const float* whh, const float* xproj, float* out);
+
 /* ---- production ICR recognizer: TPS-ResNet-BiLSTM-Attn ---------------------------------------- */
 typedef struct mhip_icr mhip_icr;
 /* replaces: Model(opt) with Transformation="TPS", FeatureExtraction="ResNet", SequenceModeling="BiLSTM",

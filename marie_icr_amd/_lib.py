@@ -210,6 +210,7 @@ _SIGNATURES = (
     ("mhip_crnn_forward_host", _i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     ("mhip_crnn_workspace_bytes", _sz, [_vp, _i, _i]),
     ("mhip_crnn_kernel_flops", C.c_double, [_vp, _i, _i, _i]),
+    ("mhip_lstm_rec_host", _i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
 )
 EXPORTED_SYMBOLS = tuple(s[0] for s in _SIGNATURES)
 

@@ -366,3 +366,40 @@ int mhip_launch_lstm_rec(mhip_ctx* ctx, int precision, const float* xproj, const
   if (e != hipSuccess) return mhip_fail(ctx, MHIP_EHIP, "lstm launch: %s", hipGetErrorString(e));
   return 0;
 }
+
+// The recurrence alone on caller-supplied host inputs in PyTorch's order, through the packers and the launcher exactly as the
+// recognizers drive them: what the kernel-level tests compare with an fp64 LSTM.  See include/marie_hip.h.
+extern "C" int mhip_lstm_rec_host(mhip_ctx* ctx, int precision, int B, int T, const float* whh, const float* xproj, float* out) {
+  if (!ctx || !whh || !xproj || !out) return MHIP_EINVAL;
+  if (precision != MHIP_PREC_F16 && precision != MHIP_PREC_F32) return mhip_fail(ctx, MHIP_EINVAL, "unknown precision %d", precision);
+  if (B < 1 || T < 1) return mhip_fail(ctx, MHIP_EINVAL, "lstm_rec_host: bad shape B=%d T=%d", B, T);
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t es = precision == MHIP_PREC_F16 ? 2 : 4;
+  const size_t wbytes = mhip_lstm_wpack_bytes(precision);
+  std::vector<char> hw(wbytes);
+  mhip_lstm_pack_whh(precision, whh, whh + (size_t)1024 * HID, hw.data());
+  // xproj [B][T][2][gate*256 + unit] -> the device's gate-interleaved columns
+  const size_t rows = (size_t)B * T * 2;
+  std::vector<float> hx(rows * 1024);
+  for (size_t r = 0; r < rows; ++r)
+    for (int col = 0; col < 1024; ++col) hx[r * 1024 + col] = xproj[r * 1024 + mhip_lstm_xproj_row(col)];
+  // one whole workgroup tile of guard rows behind the B rows the launch owns
+  const size_t out_el = (size_t)(B + ROWS) * T * 512, out_bytes = out_el * es;
+  char *dw = nullptr, *dh = nullptr;
+  float* dx = nullptr;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
+    dw = ws.take(wbytes);
+    dx = ws.take<float>(hx.size() * 4);
+    dh = ws.take(out_bytes);
+  });
+  if (rc) return rc;
+  MHIP_HIP(ctx, hipMemcpyAsync(dw, hw.data(), wbytes, hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(dx, hx.data(), hx.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemsetAsync(dh, 0xff, out_bytes, ctx->stream));      // all-ones: NaN in f16 and fp32, a cell left unwritten shows
+  if ((rc = mhip_launch_lstm_rec(ctx, precision, dx, dw, dh, B, T))) return rc;
+  std::vector<char> ho(out_bytes);
+  MHIP_HIP(ctx, hipMemcpyAsync(ho.data(), dh, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (size_t i = 0; i < out_el; ++i) out[i] = es == 2 ? (float)((const _Float16*)ho.data())[i] : ((const float*)ho.data())[i];
+  return MHIP_OK;
+}
