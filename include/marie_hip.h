@@ -708,6 +708,22 @@ int mhip_vq_peaks_host(mhip_ctx* ctx, float* heat, int n, int H, int W, const in
 /* cosine similarity of the colour features of n pairs of clips uint8 [n][h][w][3] -> fp32 [n]                                 */
 int mhip_clip_cosine_host(mhip_ctx* ctx, const uint8_t* a, const uint8_t* b, int n, int h, int w, float* out);
 
+/* ---- n-gram text matching (csrc/lev_ngrams.hip) ------------------------------------------------------------------------- */
+/* replaces: the Levenshtein.distance of every (template text, page n-gram) pair that MetaTemplateMatcher.predict / score take
+ * one at a time, marie/components/template_matching/meta_template_matching.py:152-187,277-281.  Unit-cost edit distance over
+ * code points.  The page is one string S of L alphabet ids (1 .. alphabet: the code points of the template texts; 0: any other
+ * code point, equal to nothing); word i spans S[ws[i]:we[i]], fs[i] is the first non-blank position >= ws[i] of S and le[i]
+ * one past the last non-blank position < we[i], so that candidate (i, n) — words i .. i + n - 1, joined and stripped — is
+ * S[a:b], a = min(fs[i], we[i + n - 1]), b = max(le[i + n - 1], a).  line_ids int32 [N] or NULL: with them a candidate whose
+ * words do not share one id is none.  Templates: ids concatenated, template t = tmpl_ids[tmpl_off[t]:tmpl_off[t + 1]] (0 ..
+ * 1024 ids, each 1 .. alphabet), g[t] >= 1 its word count; the candidate sizes are n = g[t] - 1 + k, k = 0, 1, 2.
+ * -> dist, len int32 [T][3][N]: the distance and the candidate's length, or -1 where there is no candidate (n outside 1 .. N,
+ * i > N - n, or differing line ids).  MHIP_EINVAL for a pattern over 1024 ids or a bit table ((alphabet + 1) * ceil(m / 64)
+ * 64-bit words) over the 64 KiB of LDS budgeted for it.                                                                       */
+int mhip_lev_ngrams_host(mhip_ctx* ctx, const uint16_t* page_ids, int L, const int32_t* ws, const int32_t* we, const int32_t* fs,
+                         const int32_t* le, const int32_t* line_ids, int N, const uint16_t* tmpl_ids, const int32_t* tmpl_off,
+                         const int32_t* g, int T, int alphabet, int32_t* dist_out, int32_t* len_out);
+
 /* ---- CLIP vision tower: image embeddings of the matcher's snippet score (csrc/clip_api.hip, clip_ops.hip) --------------- */
 /* replaces: CLIP.encode_image behind OpenAIEmbeddings.get_single_image_embedding, marie/embeddings/openai/
  * openai_embeddings.py:146-157 (clip/model.py VisionTransformer), CLIPModel.get_image_features behind

@@ -161,6 +161,7 @@ _SIGNATURES = (
     ("mhip_vq_heatmap_host", _i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     ("mhip_vq_peaks_host", _i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp]),
     ("mhip_clip_cosine_host", _i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    ("mhip_lev_ngrams_host", _i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     ("mhip_clipvis_create", _i, [_vp, _i, _vp, C.POINTER(_vp)]),
     ("mhip_clipvis_destroy", _i, [_vp]),
     ("mhip_clipvis_set_tensor", _i, [_vp, C.c_char_p, _vp, C.POINTER(C.c_int64), _i]),

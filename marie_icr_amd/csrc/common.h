@@ -49,7 +49,8 @@ enum MhipKernelId {
   // CLIP text tower (cliptext_ops.hip)
   MHIP_K_CLIPTEXT_EMBED = 29,    // token table gather + position rows -> fp32 stream
   MHIP_K_ATTN_CAUSAL = 30,       // causal soft-max attention, one workgroup per (sequence, head), K / V^T held in LDS
-  MHIP_K_COUNT = 31
+  MHIP_K_LEV_NGRAMS = 31,      // edit distance of every (template text, page n-gram) pair (lev_ngrams.hip)
+  MHIP_K_COUNT = 32
 };
 
 constexpr int MHIP_ZERO_BYTES = 65536;

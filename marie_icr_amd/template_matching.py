@@ -1,7 +1,10 @@
-"""Template matching on the MI355X: ``VQNNFTemplateMatcher`` (arXiv 2306.15010) behind the reference's matcher surface.
+"""Template matching on the MI355X: ``VQNNFTemplateMatcher`` (arXiv 2306.15010) and ``MetaTemplateMatcher`` (a template's text
+among the OCR words of a page) behind the reference's matcher surface.
 
-Mirrors marie/components/template_matching/{model,base,vqnnf_template_matching,composite_template_maching}.py and the
-matching core under vqnnf/matching/.  The reference slices a page into windows and loops in Python over (slice, template),
+Mirrors marie/components/template_matching/{model,base,vqnnf_template_matching,meta_template_matching,
+composite_template_maching}.py and the matching core under vqnnf/matching/.
+
+``VQNNFTemplateMatcher``: the reference slices a page into windows and loops in Python over (slice, template),
 materialising 128 x H x W fp32 one-hots and integral images for each.  Here the page is uploaded once, the slices are windows
 of it, and the nearest-code assignment, the Gauss-Haar heat map and the peak rounds run over the whole (slice x template)
 grid in a handful of launches (csrc/vqnnf.hip); only the peaks come back.  Template-side state (k-means codebook, labels,
@@ -14,9 +17,18 @@ encoder in one call), or any callable clip -> vector; with None the embedding si
 similarity.
 Not built: the EfficientNet hyper-column features and ``pca_lowrank`` (``n_feature != 27`` / ``pca_dims`` raise), CLIP's RN50x4
 tower (the reference's default snippet model: ``embeddings.py`` refuses it), ``resize_image_progressive``
-(``downscale_factor != 1`` raises), ``MetaTemplateMatcher`` and ``DeepDimTemplateMatcher``, and the reference's /tmp/dim writes,
+(``downscale_factor != 1`` raises), ``DeepDimTemplateMatcher``, and the reference's /tmp/dim writes,
 prints and visualisations.  ``slice_image`` and
 ``GreedyNMMPostprocess`` restate sahi's, which is not installed here: their parity with sahi is not pinned by a golden.
+
+``MetaTemplateMatcher`` slides n-grams of g - 1, g and g + 1 words (g: the words of the template text) over the page's words and
+scores each by Levenshtein similarity; n-grams at 0.5 or more also take the cosine of two text embeddings and of two snippet
+embeddings, and the three are averaged.  The reference scores one pair at a time in Python; here the page is laid out once as
+one string of alphabet ids (``text_layout``), the edit distance of every (template, n-gram) pair comes from one call of
+``csrc/lev_ngrams.hip``, and what passes the 0.5 filter goes through the device resize, ``embed_clips`` / ``embed_texts`` and
+``pair_cosines`` in batches.  Text embeddings are the CLIP text tower's (or an injected callable's): the reference's
+jina-embeddings-v2-base-en is remote code and weights that are not here.  The distance is the unit-cost edit distance over
+code points, exact against the textbook DP; its parity with the ``Levenshtein`` package is not pinned.
 """
 from __future__ import annotations
 
@@ -31,6 +43,8 @@ import numpy as np
 
 from ._lib import Context, MarieHipError, VqFilters, check
 from .dit_box_processor import resize_image
+from .ocr_processor import merge_bboxes_as_block
+from .renderer import get_words_and_boxes
 
 logger = logging.getLogger(__name__)
 
@@ -201,8 +215,12 @@ class BaseTemplateMatcher(ABC):
                                       self.DEFAULT_OVERLAP_HEIGHT_RATIO, self.DEFAULT_OVERLAP_WIDTH_RATIO)
             else:
                 windows = [(0, 0, frame.shape[1], frame.shape[0])]
+            words = word_boxes = word_lines = None
+            if metadata:                                           # base.py:179-186; empty metadata counts as none
+                words, word_boxes, word_lines = get_words_and_boxes(metadata, frame_idx, include_lines=True)
             per_window = self.predict_windows(frame, windows, template_frames, template_boxes, template_labels,
-                                              template_texts, score_threshold, scoring_strategy, max_objects)
+                                              template_texts, score_threshold, scoring_strategy, max_objects, words=words,
+                                              word_boxes=word_boxes, word_lines=word_lines)
             bboxes, labels, scores, snippets = [], [], [], []
             for (ox, oy, _, _), predictions in zip(windows, per_window):
                 for p in predictions:
@@ -463,6 +481,56 @@ def draw_init_indices(seed: int, box: Sequence[int]) -> np.ndarray:
     return rng.integers(0, w * h, size=n_code_of(w, h)).astype(np.int32)
 
 
+# ---------------------------------------------------------------------------------------------------- snippet scoring
+# What VQNNFTemplateMatcher.score and MetaTemplateMatcher.score share: the embedding of 224 x 224 snippet clips, cached by the
+# clips' bytes (``cached_embeddings_clips`` of either matcher), and the cosine of (template clip, query clip) pairs.
+def is_embeddings_object(processor) -> bool:
+    """an embeddings object of embeddings.py (batched device entries), not a plain callable clip -> vector"""
+    return hasattr(processor, "cosine_pairs")
+
+
+def host_cosine(a: np.ndarray, b: np.ndarray):
+    """nn.CosineSimilarity of two vectors: each norm clamped at 1e-8"""
+    return np.dot(a, b) / (max(np.linalg.norm(a), 1e-8) * max(np.linalg.norm(b), 1e-8))
+
+
+def clip_embedding(processor, cache: dict, clip: np.ndarray) -> np.ndarray:
+    """the embedding of one clip, through ``cache``"""
+    key = clip.tobytes()
+    if key not in cache:
+        if clip.shape[0] != CLIP_SIZE[0] or clip.shape[1] != CLIP_SIZE[1]:
+            raise ValueError("Image must be 224x224")
+        if is_embeddings_object(processor):
+            cache[key] = processor.embed_clips(clip[None])[0]
+        else:
+            cache[key] = np.asarray(processor(clip), np.float64).reshape(-1)
+    return cache[key]
+
+
+def clip_embedding_sims(ep, cache: dict, t_clips: Sequence[np.ndarray], q_clips: Sequence[np.ndarray]) -> np.ndarray:
+    """The embedding cosine of every (template clip, query clip) pair through an embeddings object: the unique clips of
+    the batch, keyed by their bytes as ``cache`` is, take one encoder call and the cosines one launch.
+    Clips embedded by an earlier batch (the templates of the previous page) are not embedded again."""
+    index, clips = {}, []
+    for clip in list(t_clips) + list(q_clips):
+        key = clip.tobytes()
+        if key not in index:
+            if clip.shape[0] != CLIP_SIZE[0] or clip.shape[1] != CLIP_SIZE[1]:
+                raise ValueError("Image must be 224x224")
+            index[key] = len(clips)
+            clips.append(clip)
+    pairs = [(index[t.tobytes()], index[q.tobytes()]) for t, q in zip(t_clips, q_clips)]
+    keys = list(index)
+    new = [i for i, key in enumerate(keys) if key not in cache]
+    if len(new) == len(keys):                      # nothing known yet: encoder and cosines in one call
+        sims, emb = ep.cosine_pairs(np.stack(clips), pairs, want_embeddings=True)
+        cache.update(zip(keys, emb))
+        return sims
+    if new:
+        cache.update(zip((keys[i] for i in new), ep.embed_clips(np.stack([clips[i] for i in new]))))
+    return ep.pair_cosines(np.stack([cache[key] for key in keys]), pairs)
+
+
 # ---------------------------------------------------------------------------------------------------- the matcher
 class VQNNFTemplateMatcher(BaseTemplateMatcher):
     """Drop-in for marie/components/template_matching/vqnnf_template_matching.py on the colour features."""
@@ -544,43 +612,13 @@ class VQNNFTemplateMatcher(BaseTemplateMatcher):
         return _u8(resize_image(_u8(snippet), CLIP_SIZE, ctx=self.ctx)[0])
 
     def get_embedding_feature(self, clip: np.ndarray) -> np.ndarray:
-        key = clip.tobytes()
-        if key not in self.cached_embeddings_clips:
-            if clip.shape[0] != CLIP_SIZE[0] or clip.shape[1] != CLIP_SIZE[1]:
-                raise ValueError("Image must be 224x224")
-            if self._batched_embeddings():
-                self.cached_embeddings_clips[key] = self.embeddings_processor.embed_clips(clip[None])[0]
-            else:
-                self.cached_embeddings_clips[key] = np.asarray(self.embeddings_processor(clip), np.float64).reshape(-1)
-        return self.cached_embeddings_clips[key]
+        return clip_embedding(self.embeddings_processor, self.cached_embeddings_clips, clip)
 
     def _batched_embeddings(self) -> bool:
-        """an embeddings object of embeddings.py (batched device entries), not a plain callable"""
-        return hasattr(self.embeddings_processor, "cosine_pairs")
+        return is_embeddings_object(self.embeddings_processor)
 
     def embedding_sims(self, t_clips: np.ndarray, q_clips: np.ndarray) -> np.ndarray:
-        """The embedding cosine of every (template clip, query clip) pair through an embeddings object: the unique clips of
-        the batch, keyed by their bytes as ``cached_embeddings_clips`` is, take one encoder call and the cosines one launch.
-        Clips embedded by an earlier batch (the templates of the previous page) are not embedded again."""
-        ep, cache = self.embeddings_processor, self.cached_embeddings_clips
-        index, clips = {}, []
-        for clip in list(t_clips) + list(q_clips):
-            key = clip.tobytes()
-            if key not in index:
-                if clip.shape[0] != CLIP_SIZE[0] or clip.shape[1] != CLIP_SIZE[1]:
-                    raise ValueError("Image must be 224x224")
-                index[key] = len(clips)
-                clips.append(clip)
-        pairs = [(index[t.tobytes()], index[q.tobytes()]) for t, q in zip(t_clips, q_clips)]
-        keys = list(index)
-        new = [i for i, key in enumerate(keys) if key not in cache]
-        if len(new) == len(keys):                      # nothing known yet: encoder and cosines in one call
-            sims, emb = ep.cosine_pairs(np.stack(clips), pairs, want_embeddings=True)
-            cache.update(zip(keys, emb))
-            return sims
-        if new:
-            cache.update(zip((keys[i] for i in new), ep.embed_clips(np.stack([clips[i] for i in new]))))
-        return ep.pair_cosines(np.stack([cache[key] for key in keys]), pairs)
+        return clip_embedding_sims(self.embeddings_processor, self.cached_embeddings_clips, t_clips, q_clips)
 
     def score_pairs(self, pairs: Sequence[Tuple[np.ndarray, np.ndarray]], scoring_strategy: str) -> List[float]:
         """``score`` of (template snippet, query snippet) pairs with one cosine launch for all of them"""
@@ -598,8 +636,7 @@ class VQNNFTemplateMatcher(BaseTemplateMatcher):
             elif batched is not None:
                 embedding_sim = float(batched[k])
             else:
-                a, b = self.get_embedding_feature(t_clips[k]), self.get_embedding_feature(q_clips[k])
-                embedding_sim = float(np.dot(a, b) / (max(np.linalg.norm(a), 1e-8) * max(np.linalg.norm(b), 1e-8)))
+                embedding_sim = float(host_cosine(self.get_embedding_feature(t_clips[k]), self.get_embedding_feature(q_clips[k])))
             if scoring_strategy == "weighted":
                 sim_val = feature_sim * 0.05 + embedding_sim * 0.95
             elif scoring_strategy == "max":
@@ -655,6 +692,284 @@ class VQNNFTemplateMatcher(BaseTemplateMatcher):
         """vqnnf_template_matching.py:100-308 on one frame (the whole frame is the window)"""
         return self.predict_windows(frame, [(0, 0, frame.shape[1], frame.shape[0])], template_frames, template_boxes,
                                     template_labels, template_texts, score_threshold, scoring_strategy, max_objects)[0]
+
+
+# ---------------------------------------------------------------------------------------------------- text matching
+LEV_MAX_PATTERN = 1024             # code points of a template text (csrc/lev_ngrams.hip: LEV_MAX_M)
+LEV_LDS_BYTES = 65536              # the kernel's budget for a template's bit table (LEV_LDS_BYTES there)
+
+
+def is_overlap(bbox1, bbox2) -> bool:
+    """meta_template_matching.py:23-30, boxes as (x, y, w, h)"""
+    x1, y1, w1, h1 = bbox1
+    x2, y2, w2, h2 = bbox2
+    return bool(x1 < x2 + w2 and x1 + w1 > x2 and y1 < y2 + h2 and y1 + h1 > y2)
+
+
+def _code_points(text: str) -> np.ndarray:
+    return np.frombuffer(text.encode("utf-32-le", "surrogatepass"), np.uint32)
+
+
+@dataclass
+class TextLayout:
+    """A page's words and the template texts as the edit-distance kernel takes them (``text_layout``)."""
+    text: str                  # S: the upper-cased words joined by blanks
+    page_ids: np.ndarray       # uint16 (L,): the alphabet id of every code point of S, 0 for one outside the alphabet
+    ws: np.ndarray             # int32 (N,): word i is S[ws[i]:we[i]]
+    we: np.ndarray
+    fs: np.ndarray             # int32 (N,): first position >= ws[i] of S that is not white space (L: none)
+    le: np.ndarray             # int32 (N,): one past the last position < we[i] of S that is not white space (0: none)
+    alphabet: int              # A: ids 1 .. A are the code points of the patterns
+    pattern_ids: np.ndarray    # uint16: the patterns' ids, concatenated
+    pattern_off: np.ndarray    # int32 (T + 1,)
+
+    def span(self, i: int, n: int) -> Tuple[int, int]:
+        """(a, b): S[a:b] == " ".join(words[i:i + n]).strip().upper()"""
+        a = min(int(self.fs[i]), int(self.we[i + n - 1]))
+        return a, max(int(self.le[i + n - 1]), a)
+
+
+def text_layout(words: Sequence[str], patterns: Sequence[str], raw: bool = False) -> TextLayout:
+    """The host side of ``mhip_lev_ngrams_host``.  ``upper()`` acts per character and ``strip()`` only moves the two ends, so every
+    n-gram string of the reference is a substring of ONE string S; the strip is precomputed per word (white space as
+    ``str.isspace``, which can run through empty or blank words into their neighbours).  Distances are over code points: S is
+    handled as UTF-32, so an astral character counts once.  ``patterns``: the stripped, upper-cased template texts.
+    ``raw``: the words as they are, neither upper-cased nor stripped."""
+    upper = list(words) if raw else [w.upper() for w in words]
+    text = " ".join(upper)
+    cp = _code_points(text)
+    L, N = len(cp), len(upper)
+    lens = np.fromiter((len(u) for u in upper), np.int64, N)
+    we = np.cumsum(lens + 1) - 1
+    ws = we - lens
+    uniq, inverse = np.unique(cp, return_inverse=True)
+    space = np.fromiter((chr(u).isspace() for u in uniq), bool, len(uniq))[inverse.reshape(-1)] if L else np.zeros(0, bool)
+    ink = np.flatnonzero(~space)                                   # the positions strip() stops at
+    before = np.searchsorted(ink, ws, "left")                      # ink positions before ws[i]: the next one is fs[i]
+    fs = np.append(ink, L)[before]
+    le = np.insert(ink, 0, -1)[np.searchsorted(ink, we, "left")] + 1
+    if raw:
+        fs, le = ws, we
+    pats = [_code_points(p) for p in patterns]
+    letters = np.unique(np.concatenate(pats)) if pats and sum(len(p) for p in pats) else np.zeros(0, np.uint32)
+    if len(letters) > 65535:
+        raise ValueError(f"the template texts hold {len(letters)} distinct code points; ids are 16 bits")
+
+    def ids(points):
+        if not len(letters) or not len(points):
+            return np.zeros(len(points), np.uint16)
+        at = np.minimum(np.searchsorted(letters, points), len(letters) - 1)
+        return np.where(letters[at] == points, at + 1, 0).astype(np.uint16)
+
+    off = np.zeros(len(pats) + 1, np.int32)
+    off[1:] = np.cumsum([len(p) for p in pats])
+    pattern_ids = np.concatenate([ids(p) for p in pats]) if pats else np.zeros(0, np.uint16)
+    return TextLayout(text, ids(cp), ws.astype(np.int32), we.astype(np.int32), fs.astype(np.int32), le.astype(np.int32),
+                      len(letters), pattern_ids.astype(np.uint16), off)
+
+
+def lev_ngrams_host(ctx: Context, layout: TextLayout, g: Sequence[int], line_ids: Optional[Sequence[int]] = None):
+    """The edit distance of every pattern of ``layout`` against every n-gram of g[t] - 1, g[t] and g[t] + 1 words, one call ->
+    (dist, len) int32 (T, 3, N): the distance and the candidate's length in code points, -1 where there is no candidate.
+    ``line_ids`` (one int per word): a candidate whose words do not share one id is none."""
+    T, N = len(layout.pattern_off) - 1, len(layout.ws)
+    g = np.ascontiguousarray(g, np.int32)
+    if T < 1 or N < 1 or len(g) != T:
+        raise ValueError(f"lev_ngrams: {T} patterns with {len(g)} word counts over {N} words")
+    m = np.diff(layout.pattern_off)
+    if m.max() > LEV_MAX_PATTERN:
+        raise ValueError(f"a template text of {int(m.max())} code points: at most {LEV_MAX_PATTERN} are built")
+    table = (layout.alphabet + 1) * ((int(m.max()) + 63) // 64) * 8
+    if table > LEV_LDS_BYTES:
+        raise ValueError(f"a template text of {int(m.max())} code points over an alphabet of {layout.alphabet} needs a bit table "
+                         f"of {table} bytes; {LEV_LDS_BYTES} are budgeted")
+    lines = None
+    if line_ids is not None:
+        lines = np.ascontiguousarray(line_ids, np.int32)
+        if lines.shape != (N,):
+            raise ValueError(f"lev_ngrams: {lines.shape} line ids for {N} words")
+    page, pat, off = (np.ascontiguousarray(layout.page_ids, np.uint16), np.ascontiguousarray(layout.pattern_ids, np.uint16),
+                      np.ascontiguousarray(layout.pattern_off, np.int32))
+    arrays = [np.ascontiguousarray(a, np.int32) for a in (layout.ws, layout.we, layout.fs, layout.le)]
+    dist, length = np.empty((T, 3, N), np.int32), np.empty((T, 3, N), np.int32)
+    check(ctx.h, ctx.lib.mhip_lev_ngrams_host(ctx.h, _ptr(page), len(page), *[_ptr(a) for a in arrays],
+                                              _ptr(lines) if lines is not None else None, N, _ptr(pat), _ptr(off), _ptr(g), T,
+                                              int(layout.alphabet), _ptr(dist), _ptr(length)), "mhip_lev_ngrams_host")
+    return dist, length
+
+
+@dataclass
+class MetaCandidate:
+    """one (template, n-gram) pair of ``MetaTemplateMatcher`` with the unrounded terms of its score"""
+    template: int              # index into the template lists
+    ngram: int                 # words of the n-gram
+    start: int                 # its first word
+    words: str                 # " ".join(words[start:start + ngram]).strip().upper()
+    bbox: Any                  # merge_bboxes_as_block of the words' boxes
+    lev: float
+    cos_text: Optional[float]  # None below lev 0.5: the reference returns lev alone there
+    cos_image: Optional[float]
+    total: float
+
+
+class MetaTemplateMatcher(BaseTemplateMatcher):
+    """Drop-in for marie/components/template_matching/meta_template_matching.py: the template's text among the page's words."""
+
+    MIN_WORD_LENGTH = 3
+    MAX_TEXT_LENGTH = 1024        # get_embedding cuts a text there
+
+    def __init__(self, model_name_or_path: Union[str, os.PathLike] = "", model_version: Optional[str] = None,
+                 use_gpu: bool = True, labels: Optional[List[str]] = None, batch_size: int = 16, use_auth_token=None,
+                 devices: Optional[List[Any]] = None, show_error: Optional[Union[str, bool]] = True, *,
+                 embeddings_processor: Union[Callable[[np.ndarray], np.ndarray], Any, None] = None,
+                 text_embeddings_processor: Union[Callable[[str], np.ndarray], Any, None] = None,
+                 ctx: Optional[Context] = None, **kwargs):
+        """``embeddings_processor``: an embeddings object of ``embeddings.py`` (its vision tower scores the snippets, its text
+        tower the texts) or a callable clip -> vector.  ``text_embeddings_processor``: an embeddings object with a text side, or
+        a callable text -> vector; needed when ``embeddings_processor`` has no text side."""
+        super().__init__(False, **kwargs)
+        if not use_gpu:
+            raise MarieHipError("MetaTemplateMatcher here is the MI355X path; use_gpu=False has no implementation")
+        if embeddings_processor is None:
+            raise ValueError("MetaTemplateMatcher needs an embeddings_processor for the snippet score")
+        if text_embeddings_processor is None:
+            if getattr(embeddings_processor, "text_model", None) is None:
+                raise ValueError("MetaTemplateMatcher needs text embeddings: embeddings_processor has no text side and no "
+                                 "text_embeddings_processor is given")
+            text_embeddings_processor = embeddings_processor
+        elif hasattr(text_embeddings_processor, "embed_texts") and getattr(text_embeddings_processor, "text_model", None) is None:
+            raise ValueError("MetaTemplateMatcher: text_embeddings_processor has no text side")
+        logger.info("Document matcher : %s", model_name_or_path)
+        self.show_error, self.batch_size, self.labels = show_error, batch_size, labels
+        self.embeddings_processor = embeddings_processor
+        self.text_embeddings_processor = text_embeddings_processor
+        self.ctx = ctx or getattr(embeddings_processor, "ctx", None) or Context(VQNNFTemplateMatcher._device_id(devices))
+        self.embedding_cache = {}             # text -> embedding
+        self.cached_embeddings_clips = {}     # clip bytes -> embedding
+
+    # -- embeddings ----------------------------------------------------------------------------------------------------
+    def _clip(self, snippet: np.ndarray) -> np.ndarray:
+        if snippet.shape[0] == 0 or snippet.shape[1] == 0:
+            raise ValueError(f"an empty snippet {snippet.shape}: the box lies outside its frame")
+        return _u8(resize_image(_u8(snippet), CLIP_SIZE, ctx=self.ctx)[0])
+
+    def image_sims(self, t_clips: Sequence[np.ndarray], q_clips: Sequence[np.ndarray]) -> List[float]:
+        ep, cache = self.embeddings_processor, self.cached_embeddings_clips
+        if is_embeddings_object(ep):
+            return [float(v) for v in clip_embedding_sims(ep, cache, t_clips, q_clips)]
+        return [float(host_cosine(clip_embedding(ep, cache, t), clip_embedding(ep, cache, q))) for t, q in zip(t_clips, q_clips)]
+
+    def text_sims(self, pairs: Sequence[Tuple[str, str]]) -> List[float]:
+        """the cosine of the embeddings of (n-gram text, template text) pairs; ``embedding_cache`` is keyed by the whole text,
+        the embedding is of its first 1024 characters (meta_template_matching.py:239-247)"""
+        ep, cache = self.text_embeddings_processor, self.embedding_cache
+        new = list(dict.fromkeys(t for pair in pairs for t in pair if t not in cache))
+        if not hasattr(ep, "embed_texts"):                         # a callable text -> vector
+            for t in new:
+                cache[t] = np.asarray(ep(t[:self.MAX_TEXT_LENGTH]), np.float64).reshape(-1)
+            return [float(host_cosine(cache[a], cache[b])) for a, b in pairs]
+        if new:
+            cache.update(zip(new, ep.embed_texts([t[:self.MAX_TEXT_LENGTH] for t in new], truncation=True)))
+        index = {t: k for k, t in enumerate(dict.fromkeys(t for pair in pairs for t in pair))}
+        return [float(v) for v in ep.pair_cosines(np.stack([cache[t] for t in index]), [(index[a], index[b]) for a, b in pairs])]
+
+    # -- scoring -------------------------------------------------------------------------------------------------------
+    def _candidates(self, frame, template_frames, template_boxes, template_texts, words, word_boxes, word_lines,
+                    keep_from: float) -> List[MetaCandidate]:
+        """Every (template, n-gram) pair whose Levenshtein similarity is at least ``min(keep_from, 0.5)``, scored, in the
+        reference's order: template, n-gram size, first word."""
+        used = [k for k, text in enumerate(template_texts) if text is not None and len(text) >= self.MIN_WORD_LENGTH]
+        if not used or not len(words):
+            return []
+        patterns = [template_texts[k].strip().upper() for k in used]
+        layout = text_layout(words, patterns)
+        g = [len(template_texts[k].split(" ")) for k in used]
+        line_ids = None
+        if word_lines:
+            seen = {}
+            line_ids = [seen.setdefault(line, len(seen)) for line in word_lines]
+        dist, length = lev_ngrams_host(self.ctx, layout, g, line_ids)
+        m = np.diff(layout.pattern_off).astype(np.int64)[:, None, None]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            lev = 1 - dist / np.maximum(length, m)                   # double, as 1 - d / max(len_a, len_b) in Python
+        if np.any((dist >= 0) & (np.maximum(length, m) == 0)):
+            raise ZeroDivisionError("an empty n-gram against an empty template text")
+        out, t_clips, q_clips, texts, scored = [], [], [], [], []
+        fragments, snippets = {}, {}
+        for t, k, i in zip(*np.nonzero((dist >= 0) & (lev >= min(keep_from, 0.5)))):
+            n = g[t] - 1 + int(k)
+            a, b = layout.span(int(i), n)
+            box = merge_bboxes_as_block(word_boxes[i:i + n])
+            c = MetaCandidate(used[t], n, int(i), layout.text[a:b], box, float(lev[t, k, i]), None, None, float(lev[t, k, i]))
+            out.append(c)
+            if c.lev < 0.5:
+                continue
+            if t not in fragments:
+                tx, ty, tw, th = template_boxes[used[t]]
+                tx, ty = int(max(tx, 0)), int(max(ty, 0))
+                fragments[t] = self._clip(template_frames[used[t]][ty:ty + th, tx:tx + tw])
+            key = tuple(box)
+            if key not in snippets:
+                x, y, w, h = box
+                snippets[key] = self._clip(frame[y:y + h, x:x + w])
+            scored.append(c)
+            t_clips.append(fragments[t])
+            q_clips.append(snippets[key])
+            texts.append((c.words, patterns[t]))
+        if scored:
+            for c, cos_text, cos_image in zip(scored, self.text_sims(texts), self.image_sims(t_clips, q_clips)):
+                c.cos_text, c.cos_image = cos_text, cos_image
+                c.total = (c.lev + cos_text + cos_image) / 3
+        return out
+
+    def score_candidates(self, frame, template_frames, template_boxes, template_texts, words, word_boxes,
+                         word_lines=None) -> List[MetaCandidate]:
+        """The unrounded (lev, cos_text, cos_image, total) of every (template, n-gram) pair at a Levenshtein similarity of 0.5
+        or more: what ``score`` (meta_template_matching.py:270-311) averages."""
+        self._check(template_frames, template_boxes, template_texts, None, words, word_boxes)
+        return [c for c in self._candidates(frame, template_frames, template_boxes, template_texts, words, word_boxes,
+                                            word_lines, 0.5) if c.lev >= 0.5]
+
+    def score(self, ngram_words: str, template_text: str, query_snippet: np.ndarray, template_snippet: np.ndarray) -> float:
+        """meta_template_matching.py:270-311 for one pair"""
+        d = int(lev_ngrams_host(self.ctx, text_layout([ngram_words], [template_text], raw=True), [1])[0][0, 1, 0])
+        sim_val = 1 - d / max(len(ngram_words), len(template_text))
+        if sim_val < 0.5:
+            return sim_val
+        cos_image = self.image_sims([self._clip(template_snippet)], [self._clip(query_snippet)])[0]
+        cos_text = self.text_sims([(ngram_words, template_text)])[0]
+        return (sim_val + cos_text + cos_image) / 3
+
+    @staticmethod
+    def _check(template_frames, template_boxes, template_texts, template_labels, words, word_boxes):
+        if template_texts is None:
+            raise ValueError("MetaTemplateMatcher matches template_texts; none were given")
+        assert len(words) == len(word_boxes)
+        assert len(template_frames) == len(template_boxes)
+        assert template_labels is None or len(template_texts) == len(template_labels)
+
+    def predict(self, frame, template_frames, template_boxes, template_labels, template_texts=None,
+                score_threshold: float = 0.9, scoring_strategy: str = "weighted", max_objects: int = 1, batch_size: int = 1,
+                words=None, word_boxes=None, word_lines=None) -> List[TemplateMatchResult]:
+        """meta_template_matching.py:98-237"""
+        predictions: List[TemplateMatchResult] = []
+        if words is None or word_boxes is None:
+            logger.warning("No words or word_boxes provided. Skipping prediction.")
+            return predictions
+        self._check(template_frames, template_boxes, template_texts, template_labels, words, word_boxes)
+        scored = self._candidates(frame, template_frames, template_boxes, template_texts, words, word_boxes, word_lines,
+                                  score_threshold - 0.001)      # round(x, 3) > threshold needs x > threshold - 0.0005
+        by_template = {}
+        for c in scored:
+            sim_val = round(c.total, 3)
+            if c.words == template_texts[c.template].strip().upper() or sim_val > score_threshold:
+                by_template.setdefault(c.template, []).append((c.ngram, TemplateMatchResult(
+                    bbox=c.bbox, label=template_labels[c.template], score=sim_val, similarity=sim_val)))
+        for idx in sorted(by_template):
+            for _, candidate in sorted(by_template[idx], key=lambda e: e[0]):          # stable: by n-gram size
+                if not any(candidate.label == p.label and is_overlap(candidate.bbox, p.bbox) for p in predictions):
+                    predictions.append(candidate)
+        return predictions
 
 
 class CompositeTemplateMatcher(BaseTemplateMatcher):
