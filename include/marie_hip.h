@@ -824,6 +824,75 @@ int mhip_cliptext_attention_host(mhip_ctx* ctx, int precision, const float* q, c
 int mhip_cliptext_head_host(mhip_ctx* ctx, const float* h, int B, int npad, int D, const float* g, const float* b, float eps,
                             const float* proj, int E, const int32_t* row_of, float* emb_out);
 
+/* ---- BERT sentence encoders: text embeddings (csrc/berttext_api.hip, berttext_ops.hip) ------------------------------------ */
+/* replaces: SentenceTransformer.encode behind SentenceTransformerEmbeddings.get_embeddings (marie/embeddings/sentence_transformers/
+ * sentence_transformers_embeddings.py, all-MiniLM-L6-v2) and JinaEmbeddings.get_embeddings (marie/embeddings/jina/
+ * jina_embeddings.py, jina-embeddings-v2-base-en): BertModel without the pooler — or JinaBERT: no position table, the symmetric
+ * ALiBi bias -slope_h |i - j| on the scores, a gated GELU MLP — then masked mean (or [CLS]) pooling and, where asked for, L2
+ * normalisation.  Token ids come from the caller (marie_icr_amd/wordpiece_tokenizer.py): int32 [B][npad], npad a multiple of 8 up
+ * to 128 (the keys of a text are held in LDS), the same for every text of a call; len[b] in [1, npad] is text b's token count
+ * ([CLS] .. [SEP]), the rows after it carry the [PAD] id.  A text's embedding does not depend on the other texts of the call or on
+ * npad, bit for bit.  Post-LN layers, fp32 [dim] out.                                                                          */
+typedef struct mhip_berttext mhip_berttext;
+typedef struct mhip_berttext_config {
+  int vocab;               /* 30522                                                                                       */
+  int max_position;        /* 512: rows of the position table (position 0 only)                                           */
+  int type_vocab;          /* 2: row 0 of the token type table is added to every token                                    */
+  int dim, heads, depth;   /* 384/12/6 (all-MiniLM-L6-v2), 768/12/12 (jina-v2-base); head dim 64 or 32, dim a multiple of
+                              64 up to 1024                                                                               */
+  int ffn;                 /* 1536 / 3072; a multiple of 64                                                               */
+  float ln_eps;            /* 1e-12                                                                                       */
+  int position;            /* 0 absolute (a learned table), 1 alibi                                                       */
+  int mlp;                 /* 0 gelu (intermediate.dense + erf-GELU), 1 geglu (gated_layers: gelu(x W_a^T) * (x W_b^T))  */
+  int pool;                /* 0 mean over the len[b] tokens, 1 cls (row 0)                                               */
+  int normalize;           /* 1: divide the pooled row by max(its L2 norm, 1e-12)                                         */
+} mhip_berttext_config;
+/* MHIP_EINVAL with a message that names the field: a head dim other than 64 or 32, dim above 1024, dim or ffn no multiple of 64,
+ * an unknown position / mlp / pool / normalize value                                                                          */
+int mhip_berttext_create(mhip_ctx* ctx, int precision, const mhip_berttext_config* cfg, mhip_berttext** out);
+int mhip_berttext_destroy(mhip_berttext* m);
+/* keys of Hugging Face BERT (an optional "bert." prefix is stripped): embeddings.{word,position,token_type}_embeddings.weight,
+ * embeddings.LayerNorm.*, encoder.layer.N.attention.self.{query,key,value}.*, attention.output.{dense,LayerNorm}.*,
+ * intermediate.dense.*, output.{dense,LayerNorm}.*; with mlp = geglu the MLP is JinaBERT's encoder.layer.N.mlp.gated_layers.weight
+ * [2 ffn][dim] (no bias; first the GELU half, then the linear half), mlp.wo.*, mlp.layernorm.*, and position = alibi takes no
+ * position table.  pooler.* and embeddings.position_ids are ignored; any other key is MHIP_EINVAL.  finalize names the first
+ * missing or misshapen tensor                                                                                                 */
+int mhip_berttext_set_tensor(mhip_berttext* m, const char* key, const float* data, const int64_t* shape, int ndim);
+int mhip_berttext_finalize(mhip_berttext* m);
+int mhip_berttext_alloc_arena(mhip_berttext* m);
+int mhip_berttext_arena(mhip_berttext* m, void** arena_dev, size_t* bytes);
+/* bytes of context workspace one mhip_berttext_embed_host (or debug_taps_host) call of B texts of npad rows lays out (0: bad
+ * arguments); mhip_berttext_embed_pairs_host lays out three arrays of 4 * n_pairs bytes more, each rounded up to 256            */
+size_t mhip_berttext_workspace_bytes(mhip_berttext* m, int B, int npad);
+/* the ALiBi slopes of `heads` heads, fp32 [heads]: 2^(-8 (i + 1) / n) for n a power of two; otherwise those of the largest power
+ * of two p <= n, then the even-indexed slopes of 2 p, the first n - p of them.  Host only, no ctx                              */
+int mhip_berttext_alibi_slopes(int heads, float* slopes_out);
+/* B texts (1 .. 4096) -> emb_out fp32 [B][dim].  MHIP_EINVAL, never a clamp: npad no multiple of 8 or above 128 (or above the
+ * position table rounded up to 8), a len outside [1, npad], an id outside [0, vocab)                                          */
+int mhip_berttext_embed_host(mhip_berttext* m, const int32_t* ids, const int32_t* len, int B, int npad, float* emb_out);
+/* the texts through the encoder once, then cos_out[p] = x.y / max(|x| |y|, 1e-8) of the embeddings of texts pair_a[p], pair_b[p]
+ * (fp32 [n_pairs]); emb_out fp32 [B][dim] or NULL                                                                             */
+int mhip_berttext_embed_pairs_host(mhip_berttext* m, const int32_t* ids, const int32_t* len, int B, int npad,
+                                   const int32_t* pair_a, const int32_t* pair_b, int n_pairs, float* cos_out, float* emb_out);
+/* as embed_host, plus the residual stream after the embedding kernel and after every layer: taps_out fp32
+ * [depth + 1][B][npad][dim] (rows >= len[b] hold finite values nobody reads); emb_out may be NULL                             */
+int mhip_berttext_debug_taps_host(mhip_berttext* m, const int32_t* ids, const int32_t* len, int B, int npad, float* taps_out,
+                                  float* emb_out);
+/* The kernels alone on host arrays (parity tests).  word fp32 [vocab][D], type0 [D], pos [npad][D] or NULL, LayerNorm g / b [D],
+ * ids [B][npad] -> h_out [B][npad][D] = LN(word[id] + type0 (+ pos[t]))                                                       */
+int mhip_berttext_embed_rows_host(mhip_ctx* ctx, const float* word, const float* type0, const float* pos, const float* g,
+                                  const float* b, float eps, const int32_t* ids, int B, int npad, int vocab, int D, float* h_out);
+/* attention of B sequences of npad rows over their first len[b] keys: q, k, v fp32 [B][npad][heads * head_dim], q already scaled
+ * by head_dim^-0.5 * log2(e), slopes [heads] in the same log2 units or NULL (no bias term); rounded to the precision's element
+ * type and laid out as the encoder lays them out (q | k rows, V^T) -> out fp32, same shape                                    */
+int mhip_berttext_attention_host(mhip_ctx* ctx, int precision, const float* q, const float* k, const float* v, const int32_t* len,
+                                 const float* slopes, int B, int heads, int head_dim, int npad, float* out);
+/* x fp32 [R][2 F], rounded to the precision's element type -> out fp32 [R][F] = gelu_erf(x[:, :F]) * x[:, F:]                 */
+int mhip_berttext_geglu_host(mhip_ctx* ctx, int precision, const float* x, int R, int F, float* out);
+/* h fp32 [B][npad][D], len [B] -> emb_out fp32 [B][D]: mode 0 the mean of rows < len[b], 1 row 0; normalize 0 / 1            */
+int mhip_berttext_pool_host(mhip_ctx* ctx, const float* h, const int32_t* len, int B, int npad, int D, int mode, int normalize,
+                            float* emb_out);
+
 /* ---- word-box / line geometry of the DiT box processor (host, pure functions; no ctx) --------------------------------- */
 /* replaces: merge_boxes, marie/utils/overlap.py:268-330 (find_overlap_horizontal(center_y_overlap=0.5) :106-183,
  * merge_bboxes_as_block :186-204).  xyxy fp32 [n][4] -> out_xyxy fp32 (capacity n rows), *n_out rows.       */

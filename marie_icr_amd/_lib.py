@@ -189,6 +189,21 @@ _SIGNATURES = (
     ("mhip_cliptext_embed_rows_host", _i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     ("mhip_cliptext_attention_host", _i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
     ("mhip_cliptext_head_host", _i, [_vp, _vp, _i, _i, _i, _vp, _vp, C.c_float, _vp, _i, _vp, _vp]),
+    ("mhip_berttext_create", _i, [_vp, _i, _vp, C.POINTER(_vp)]),
+    ("mhip_berttext_destroy", _i, [_vp]),
+    ("mhip_berttext_set_tensor", _i, [_vp, C.c_char_p, _vp, C.POINTER(C.c_int64), _i]),
+    ("mhip_berttext_finalize", _i, [_vp]),
+    ("mhip_berttext_alloc_arena", _i, [_vp]),
+    ("mhip_berttext_arena", _i, [_vp, C.POINTER(_vp), C.POINTER(_sz)]),
+    ("mhip_berttext_workspace_bytes", _sz, [_vp, _i, _i]),
+    ("mhip_berttext_alibi_slopes", _i, [_i, _vp]),
+    ("mhip_berttext_embed_host", _i, [_vp, _vp, _vp, _i, _i, _vp]),
+    ("mhip_berttext_embed_pairs_host", _i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    ("mhip_berttext_debug_taps_host", _i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    ("mhip_berttext_embed_rows_host", _i, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp, _i, _i, _i, _i, _vp]),
+    ("mhip_berttext_attention_host", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    ("mhip_berttext_geglu_host", _i, [_vp, _i, _vp, _i, _i, _vp]),
+    ("mhip_berttext_pool_host", _i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     ("mhip_max_page_size", _i, [_i, _i, _i, _i, C.c_double, C.POINTER(_i), C.POINTER(_i)]),
     ("mhip_resize_area_u8", _i, [_vp, _vp, _i, _i, _i, C.c_size_t, _vp, _i, _i]),
     ("mhip_resize_area_u8_host", _i, [_vp, _vp, _i, _i, _i, _vp, _i, _i]),
@@ -290,6 +305,13 @@ class ClipTextConfig(C.Structure):
     """mirror of mhip_cliptext_config (include/marie_hip.h)"""
     _fields_ = [("vocab", C.c_int), ("context", C.c_int), ("dim", C.c_int), ("heads", C.c_int), ("depth", C.c_int),
                 ("ffn", C.c_int), ("proj_dim", C.c_int), ("ln_eps", C.c_float)]
+
+
+class BertTextConfig(C.Structure):
+    """mirror of mhip_berttext_config (include/marie_hip.h)"""
+    _fields_ = [("vocab", C.c_int), ("max_position", C.c_int), ("type_vocab", C.c_int), ("dim", C.c_int), ("heads", C.c_int),
+                ("depth", C.c_int), ("ffn", C.c_int), ("ln_eps", C.c_float), ("position", C.c_int), ("mlp", C.c_int),
+                ("pool", C.c_int), ("normalize", C.c_int)]
 
 
 class VqFilters(C.Structure):

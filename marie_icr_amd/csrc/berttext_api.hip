@@ -1,0 +1,462 @@
+// berttext_api.hip — BERT sentence encoders (the text embeddings of SentenceTransformerEmbeddings and JinaEmbeddings) behind the
+// C ABI.
+//
+// Host-side counterpart of SentenceTransformer.encode as marie/embeddings/sentence_transformers/sentence_transformers_embeddings.py
+// and marie/embeddings/jina/jina_embeddings.py drive it: BertModel.forward without the pooler (transformers/models/bert/
+// modeling_bert.py: BertEmbeddings, BertLayer under the padding mask), or JinaBERT (no position table, a symmetric ALiBi bias on
+// the scores, a gated GELU MLP), then the Pooling (mean over the attention mask, or the [CLS] row) and Normalize modules.  One
+// object = one weight arena + the launch sequence.
+//
+// Row layout: every text owns `npad` rows (a multiple of 8, the same for the whole call) of which its first len[b] are its
+// tokens; the rest carry the [PAD] id, are computed like any other row and are never a key.  The residual stream h is fp32.  The
+// layers are LayoutLMv3's (post-LN: attention, ao GEMM + residual, LayerNorm, fc1, fc2 + residual, LayerNorm) with attn_short as
+// the attention.  The word table stays fp32 in both precision modes: it is a gather of B * npad rows, not a GEMM operand.
+#include <math.h>
+
+#include "encoder_block.h"
+
+enum { BT_POS_ABSOLUTE = 0, BT_POS_ALIBI = 1, BT_MLP_GELU = 0, BT_MLP_GEGLU = 1, BT_POOL_MEAN = 0, BT_POOL_CLS = 1 };
+
+struct mhip_berttext {
+  mhip_ctx* ctx = nullptr;
+  int precision = MHIP_PREC_F16;
+  mhip_berttext_config cfg{};
+  TensorStore store;
+  Arena arena;
+  bool ready = false;
+  size_t esz() const { return precision == MHIP_PREC_F16 ? 2 : 4; }
+  int head_dim() const { return cfg.dim / cfg.heads; }
+  bool alibi() const { return cfg.position == BT_POS_ALIBI; }
+  bool geglu() const { return cfg.mlp == BT_MLP_GEGLU; }
+  // tokens of a text: the LDS-resident attention's 128, or the position table's rows when it has fewer
+  int max_tokens() const { return alibi() ? 128 : std::min(cfg.max_position, 128); }
+  int max_npad() const { return (max_tokens() + 7) / 8 * 8; }
+};
+
+namespace {
+
+constexpr int MAX_TEXTS = 4096, MAX_ROWS = 128;
+constexpr double LOG2E = 1.4426950408889634;
+
+// the buffers of one call of B texts (and n_pairs cosines)
+struct BertRun {
+  int *ids = nullptr, *len = nullptr, *pair_a = nullptr, *pair_b = nullptr;
+  float *h = nullptr, *y = nullptr, *emb = nullptr, *cos = nullptr;
+  char* gg = nullptr;      // [R][F] the gated product (geglu only)
+  EncoderWs w;
+};
+
+void berttext_carve(const mhip_berttext* m, Carver& ws, int B, int npad, int n_pairs, BertRun* r) {
+  const mhip_berttext_config& c = m->cfg;
+  const size_t D = c.dim, F = c.ffn, R = (size_t)B * npad;
+  r->ids = ws.take<int>(R * 4);
+  r->len = ws.take<int>((size_t)B * 4);
+  r->pair_a = n_pairs ? ws.take<int>((size_t)n_pairs * 4) : nullptr;
+  r->pair_b = n_pairs ? ws.take<int>((size_t)n_pairs * 4) : nullptr;
+  r->cos = n_pairs ? ws.take<float>((size_t)n_pairs * 4) : nullptr;
+  r->h = ws.take<float>(R * D * 4);
+  r->y = ws.take<float>(R * D * 4);
+  r->emb = ws.take<float>((size_t)B * D * 4);
+  r->gg = m->geglu() ? ws.take(R * F * m->esz()) : nullptr;
+  encoder_ws_carve(ws, R, D, m->geglu() ? 2 * F : F, 0, m->esz(), &r->w);
+}
+
+bool npad_ok(int npad, int max_npad) { return npad >= 8 && npad % 8 == 0 && npad <= max_npad; }
+
+// ALiBi slopes of n heads: for n a power of two 2^(-8 (i + 1) / n); otherwise those of the largest power of two p <= n, then the
+// even-indexed slopes of 2 p, the first n - p of them
+std::vector<double> alibi_slopes(int n) {
+  auto pow2 = [](int p) {
+    std::vector<double> s(p);
+    for (int i = 0; i < p; ++i) s[i] = exp2(-8.0 * (i + 1) / p);
+    return s;
+  };
+  int p = 1;
+  while (p * 2 <= n) p *= 2;
+  std::vector<double> s = pow2(p);
+  if (p < n) {
+    const std::vector<double> more = pow2(2 * p);
+    for (int i = 0; i < n - p; ++i) s.push_back(more[2 * i]);
+  }
+  return s;
+}
+
+int berttext_check_call(mhip_berttext* m, const int32_t* ids, const int32_t* len, int B, int npad) {
+  mhip_ctx* ctx = m->ctx;
+  if (!m->ready) return mhip_fail(ctx, MHIP_ESTATE, "berttext: weights not finalized");
+  if (!ids || !len || B < 1 || B > MAX_TEXTS) return mhip_fail(ctx, MHIP_EINVAL, "berttext: bad arguments (%d texts; 1 .. %d)", B, MAX_TEXTS);
+  if (!npad_ok(npad, m->max_npad()))
+    return mhip_fail(ctx, MHIP_EINVAL, "berttext: %d rows a text (a multiple of 8 up to %d)", npad, m->max_npad());
+  for (int b = 0; b < B; ++b)
+    if (len[b] < 1 || len[b] > npad || len[b] > m->max_tokens())
+      return mhip_fail(ctx, MHIP_EINVAL, "berttext: text %d has %d tokens (1 .. %d)", b, len[b], std::min(npad, m->max_tokens()));
+  for (size_t e = 0; e < (size_t)B * npad; ++e)
+    if (ids[e] < 0 || ids[e] >= m->cfg.vocab)
+      return mhip_fail(ctx, MHIP_EINVAL, "berttext: id %d at text %zu, position %zu is outside the vocabulary of %d", ids[e], e / npad, e % npad, m->cfg.vocab);
+  return MHIP_OK;
+}
+
+int berttext_upload(mhip_berttext* m, const int32_t* ids, const int32_t* len, int B, int npad, const BertRun& run) {
+  int rc = mhip_stage_h2d(m->ctx, run.ids, ids, (size_t)B * npad * 4);
+  return rc ? rc : mhip_stage_h2d(m->ctx, run.len, len, (size_t)B * 4);
+}
+
+// ids / len staged in run -> embeddings in run.emb.  taps (host, or null): h after the embedding kernel and after every layer,
+// [depth + 1][B][npad][D]
+int berttext_forward(mhip_berttext* m, int B, int npad, const BertRun& run, float* taps) {
+  mhip_ctx* ctx = m->ctx;
+  const mhip_berttext_config& c = m->cfg;
+  const int D = c.dim, F = c.ffn, prec = m->precision;
+  const size_t es = m->esz(), R = (size_t)B * npad;
+  const Arena& a = m->arena;
+  const EncoderWs& w = run.w;
+  int rc;
+  if ((rc = mhip_launch_berttext_embed(ctx, prec, a.d<float>("word"), a.d<float>("type0"), m->alibi() ? nullptr : a.d<float>("pos"),
+                                       a.d<float>("ln_emb_g"), a.d<float>("ln_emb_b"), c.ln_eps, run.ids, run.h, w.ht, B, npad, D)))
+    return rc;
+  auto tap = [&](int i) -> int {
+    if (!taps) return MHIP_OK;
+    MHIP_HIP(ctx, hipMemcpyAsync(taps + (size_t)i * R * D, run.h, R * D * 4, hipMemcpyDeviceToHost, ctx->stream));
+    return MHIP_OK;
+  };
+  if ((rc = tap(0))) return rc;
+  AttnShortDesc sd;
+  sd.a = encoder_attn_desc(w.qk, w.vt, w.ao, D, es, B, c.heads, npad, npad);
+  sd.len = run.len;
+  sd.slopes = m->alibi() ? a.d<float>("alibi") : nullptr;
+  sd.head_dim = m->head_dim();
+  for (int i = 0; i < c.depth; ++i) {
+    if ((rc = encoder_block_attention(ctx, prec, a, i, w, sd))) return rc;
+    if ((rc = mhip_gemm(ctx, prec, w.ao, a.d(enc_blk(i, "ao_w")), (long long)R, D, D, nullptr, a.d<float>(enc_blk(i, "ao_b")), run.y, ACT_NONE, 1, run.h))) return rc;
+    if ((rc = mhip_launch_berttext_layernorm(ctx, prec, run.y, a.d<float>(enc_blk(i, "ln1_g")), a.d<float>(enc_blk(i, "ln1_b")), run.h, w.ht, (int)R, D, c.ln_eps))) return rc;
+    const char* hid = w.hid;
+    if (m->geglu()) {
+      if ((rc = mhip_gemm(ctx, prec, w.ht, a.d(enc_blk(i, "fc1_w")), (long long)R, 2 * F, D, nullptr, nullptr, w.hid, ACT_NONE, 0))) return rc;
+      if ((rc = mhip_launch_geglu(ctx, prec, w.hid, run.gg, (long long)R, F))) return rc;
+      hid = run.gg;
+    } else {
+      if ((rc = mhip_gemm(ctx, prec, w.ht, a.d(enc_blk(i, "fc1_w")), (long long)R, F, D, nullptr, a.d<float>(enc_blk(i, "fc1_b")), w.hid, ACT_GELU, 0))) return rc;
+    }
+    if ((rc = mhip_gemm(ctx, prec, hid, a.d(enc_blk(i, "fc2_w")), (long long)R, D, F, nullptr, a.d<float>(enc_blk(i, "fc2_b")), run.y, ACT_NONE, 1, run.h))) return rc;
+    if ((rc = mhip_launch_berttext_layernorm(ctx, prec, run.y, a.d<float>(enc_blk(i, "ln2_g")), a.d<float>(enc_blk(i, "ln2_b")), run.h, w.ht, (int)R, D, c.ln_eps))) return rc;
+    if ((rc = tap(i + 1))) return rc;
+  }
+  return mhip_launch_berttext_pool(ctx, run.h, run.len, B, npad, D, c.pool == BT_POOL_CLS, c.normalize, run.emb);
+}
+
+// block i as Hugging Face BERT holds it, "encoder.layer.N.": attention.self.{query,key,value}, attention.output.{dense,LayerNorm},
+// then intermediate.dense / output.{dense,LayerNorm}, or (gated) JinaBERT's mlp.{gated_layers,wo,layernorm}.  false (the error
+// names the tensor) when one is missing or misshapen
+bool bert_layer_weights(mhip_ctx* ctx, const TensorStore& st, int i, int D, int F, bool gated, EncoderBlockWeights* w) {
+  const std::string p = "encoder.layer." + std::to_string(i) + ".";
+  auto mat = [&](const std::string& k, int r, int c) -> const float* {
+    const HostTensor* t = st.find(ctx, p + k, {r, c});
+    return t ? t->data.data() : nullptr;
+  };
+  auto vec = [&](const std::string& k, int n) -> const float* {
+    const HostTensor* t = st.find(ctx, p + k, {n});
+    return t ? t->data.data() : nullptr;
+  };
+  if (!(w->wq = mat("attention.self.query.weight", D, D)) || !(w->bq = vec("attention.self.query.bias", D)) ||
+      !(w->wk = mat("attention.self.key.weight", D, D)) || !(w->bk = vec("attention.self.key.bias", D)) ||
+      !(w->wv = mat("attention.self.value.weight", D, D)) || !(w->bv = vec("attention.self.value.bias", D)) ||
+      !(w->wo = mat("attention.output.dense.weight", D, D)) || !(w->bo = vec("attention.output.dense.bias", D)) ||
+      !(w->ln1_g = vec("attention.output.LayerNorm.weight", D)) || !(w->ln1_b = vec("attention.output.LayerNorm.bias", D)))
+    return false;
+  w->gated = gated;
+  if (gated)
+    return (w->w1 = mat("mlp.gated_layers.weight", 2 * F, D)) && (w->w2 = mat("mlp.wo.weight", D, F)) && (w->b2 = vec("mlp.wo.bias", D)) &&
+           (w->ln2_g = vec("mlp.layernorm.weight", D)) && (w->ln2_b = vec("mlp.layernorm.bias", D));
+  return (w->w1 = mat("intermediate.dense.weight", F, D)) && (w->b1 = vec("intermediate.dense.bias", F)) &&
+         (w->w2 = mat("output.dense.weight", D, F)) && (w->b2 = vec("output.dense.bias", D)) &&
+         (w->ln2_g = vec("output.LayerNorm.weight", D)) && (w->ln2_b = vec("output.LayerNorm.bias", D));
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------- lifecycle
+extern "C" int mhip_berttext_create(mhip_ctx* ctx, int precision, const mhip_berttext_config* cfg, mhip_berttext** out) {
+  if (!ctx || !out || !cfg) return MHIP_EINVAL;
+  *out = nullptr;
+  if (precision != MHIP_PREC_F16 && precision != MHIP_PREC_F32) return mhip_fail(ctx, MHIP_EINVAL, "unknown precision %d", precision);
+  const mhip_berttext_config& c = *cfg;
+  if (c.dim < 64 || c.dim % 64 || c.dim > 1024) return mhip_fail(ctx, MHIP_EINVAL, "berttext: dim %d (a multiple of 64 up to 1024)", c.dim);
+  if (c.heads < 1 || c.dim % c.heads || (c.dim / c.heads != 64 && c.dim / c.heads != 32))
+    return mhip_fail(ctx, MHIP_EINVAL, "berttext: heads %d at dim %d: a head dimension of %d, the attention kernel has heads of 64 or 32", c.heads, c.dim,
+                     c.heads > 0 ? c.dim / c.heads : 0);
+  if (c.ffn < 64 || c.ffn % 64) return mhip_fail(ctx, MHIP_EINVAL, "berttext: ffn %d (a multiple of 64)", c.ffn);
+  if (c.depth < 1) return mhip_fail(ctx, MHIP_EINVAL, "berttext: depth %d", c.depth);
+  if (c.vocab < 2 || c.vocab > (1 << 24)) return mhip_fail(ctx, MHIP_EINVAL, "berttext: vocab %d", c.vocab);
+  if (c.type_vocab < 1) return mhip_fail(ctx, MHIP_EINVAL, "berttext: type_vocab %d", c.type_vocab);
+  if (c.position != BT_POS_ABSOLUTE && c.position != BT_POS_ALIBI) return mhip_fail(ctx, MHIP_EINVAL, "berttext: position %d (0 absolute, 1 alibi)", c.position);
+  if (c.position == BT_POS_ABSOLUTE && c.max_position < 2) return mhip_fail(ctx, MHIP_EINVAL, "berttext: max_position %d", c.max_position);
+  if (c.mlp != BT_MLP_GELU && c.mlp != BT_MLP_GEGLU) return mhip_fail(ctx, MHIP_EINVAL, "berttext: mlp %d (0 gelu, 1 geglu)", c.mlp);
+  if (c.pool != BT_POOL_MEAN && c.pool != BT_POOL_CLS) return mhip_fail(ctx, MHIP_EINVAL, "berttext: pool %d (0 mean, 1 cls)", c.pool);
+  if (c.normalize != 0 && c.normalize != 1) return mhip_fail(ctx, MHIP_EINVAL, "berttext: normalize %d (0 or 1)", c.normalize);
+  if (!(c.ln_eps > 0.f)) return mhip_fail(ctx, MHIP_EINVAL, "berttext: ln_eps");
+  mhip_berttext* m = new mhip_berttext();
+  m->ctx = ctx;
+  m->precision = precision;
+  m->cfg = c;
+  const size_t es = m->esz(), D = c.dim;
+  Arena& a = m->arena;
+  a.take("word", (size_t)c.vocab * D * 4);
+  a.take("type0", D * 4);
+  if (m->alibi()) a.take("alibi", (size_t)c.heads * 4);
+  else a.take("pos", (size_t)m->max_npad() * D * 4);      // rows past the table (padding rows only) are zeros
+  a.take("ln_emb_g", D * 4); a.take("ln_emb_b", D * 4);
+  for (int i = 0; i < c.depth; ++i) encoder_block_take(a, i, D, c.ffn, es, m->geglu());
+  *out = m;
+  return MHIP_OK;
+}
+
+extern "C" int mhip_berttext_destroy(mhip_berttext* m) {
+  if (!m) return MHIP_OK;
+  mhip_quiesce(m->ctx);
+  m->arena.release();
+  delete m;
+  return MHIP_OK;
+}
+
+extern "C" int mhip_berttext_set_tensor(mhip_berttext* m, const char* key, const float* data, const int64_t* shape, int ndim) {
+  if (!m || !key) return MHIP_EINVAL;
+  std::string k(key);
+  if (k.rfind("bert.", 0) == 0) k = k.substr(5);
+  if (k.rfind("pooler.", 0) == 0 || k == "embeddings.position_ids") return MHIP_OK;
+  if (k.rfind("embeddings.", 0) != 0 && k.rfind("encoder.layer.", 0) != 0) return mhip_fail(m->ctx, MHIP_EINVAL, "unknown state_dict key %s", key);
+  m->ready = false;
+  return m->store.set(m->ctx, k, data, shape, ndim);
+}
+
+extern "C" int mhip_berttext_alloc_arena(mhip_berttext* m) {
+  if (!m) return MHIP_EINVAL;
+  int rc = m->arena.alloc(m->ctx);
+  if (rc) return rc;
+  m->ready = true;
+  return MHIP_OK;
+}
+
+extern "C" int mhip_berttext_arena(mhip_berttext* m, void** dev, size_t* bytes) {
+  if (!m) return MHIP_EINVAL;
+  if (dev) *dev = m->arena.dev;
+  if (bytes) *bytes = m->arena.bytes;
+  return MHIP_OK;
+}
+
+extern "C" int mhip_berttext_finalize(mhip_berttext* m) {
+  if (!m) return MHIP_EINVAL;
+  mhip_ctx* ctx = m->ctx;
+  const mhip_berttext_config& c = m->cfg;
+  const int D = c.dim, F = c.ffn, prec = m->precision;
+  Arena& a = m->arena;
+  const TensorStore& st = m->store;
+  a.begin_fill();
+  const HostTensor* word = st.find(ctx, "embeddings.word_embeddings.weight", {c.vocab, D});
+  if (!word) return MHIP_ESTATE;
+  const HostTensor* type = st.find(ctx, "embeddings.token_type_embeddings.weight", {c.type_vocab, D});
+  if (!type) return MHIP_ESTATE;
+  const HostTensor* g0 = st.find(ctx, "embeddings.LayerNorm.weight", {D});
+  if (!g0) return MHIP_ESTATE;
+  const HostTensor* b0 = st.find(ctx, "embeddings.LayerNorm.bias", {D});
+  if (!b0) return MHIP_ESTATE;
+  memcpy(a.h("word"), word->data.data(), word->numel() * 4);
+  memcpy(a.h("type0"), type->data.data(), (size_t)D * 4);
+  memcpy(a.h("ln_emb_g"), g0->data.data(), (size_t)D * 4); memcpy(a.h("ln_emb_b"), b0->data.data(), (size_t)D * 4);
+  if (m->alibi()) {
+    const std::vector<double> s = alibi_slopes(c.heads);
+    float* dst = (float*)a.h("alibi");
+    for (int h = 0; h < c.heads; ++h) dst[h] = (float)(s[h] * LOG2E);      // the scores are in log2 units
+  } else {
+    const HostTensor* pos = st.find(ctx, "embeddings.position_embeddings.weight", {c.max_position, D});
+    if (!pos) return MHIP_ESTATE;
+    memcpy(a.h("pos"), pos->data.data(), (size_t)std::min(c.max_position, m->max_npad()) * D * 4);
+  }
+  const float scale = (float)(LOG2E / sqrt((double)m->head_dim()));
+  for (int i = 0; i < c.depth; ++i) {
+    EncoderBlockWeights w;
+    if (!bert_layer_weights(ctx, st, i, D, F, m->geglu(), &w)) return MHIP_ESTATE;
+    encoder_block_fill(a, prec, i, D, F, w, scale);
+  }
+  int rc = a.upload(ctx);
+  if (rc) return rc;
+  m->ready = true;
+  m->store.t.clear();
+  return MHIP_OK;
+}
+
+extern "C" size_t mhip_berttext_workspace_bytes(mhip_berttext* m, int B, int npad) {
+  if (!m || B < 1 || B > MAX_TEXTS || !npad_ok(npad, m->max_npad())) return 0;
+  BertRun run;
+  return mhip_layout_bytes([&](Carver& ws) { berttext_carve(m, ws, B, npad, 0, &run); });
+}
+
+extern "C" int mhip_berttext_alibi_slopes(int heads, float* slopes_out) {
+  if (heads < 1 || heads > 4096 || !slopes_out) return MHIP_EINVAL;
+  const std::vector<double> s = alibi_slopes(heads);
+  for (int h = 0; h < heads; ++h) slopes_out[h] = (float)s[h];
+  return MHIP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------- forward
+// the one body of the three entries: cosines with n_pairs > 0, taps with taps_out
+static int berttext_run(mhip_berttext* m, const int32_t* ids, const int32_t* len, int B, int npad, const int32_t* pair_a,
+                        const int32_t* pair_b, int n_pairs, float* cos_out, float* taps_out, float* emb_out) {
+  mhip_ctx* ctx = m->ctx;
+  int rc = berttext_check_call(m, ids, len, B, npad);
+  if (rc) return rc;
+  if (cos_out) {
+    if (n_pairs < 1 || n_pairs > (1 << 24)) return mhip_fail(ctx, MHIP_EINVAL, "berttext: %d pairs", n_pairs);
+    for (int p = 0; p < n_pairs; ++p)
+      if (pair_a[p] < 0 || pair_a[p] >= B || pair_b[p] < 0 || pair_b[p] >= B)
+        return mhip_fail(ctx, MHIP_EINVAL, "berttext: pair %d names texts %d and %d of %d", p, pair_a[p], pair_b[p], B);
+  }
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  BertRun run;
+  if ((rc = mhip_carve_workspace(ctx, [&](Carver& ws) { berttext_carve(m, ws, B, npad, n_pairs, &run); }))) return rc;
+  if ((rc = berttext_upload(m, ids, len, B, npad, run))) return rc;
+  if (cos_out) {
+    if ((rc = mhip_stage_h2d(ctx, run.pair_a, pair_a, (size_t)n_pairs * 4))) return rc;
+    if ((rc = mhip_stage_h2d(ctx, run.pair_b, pair_b, (size_t)n_pairs * 4))) return rc;
+  }
+  if ((rc = berttext_forward(m, B, npad, run, taps_out))) return rc;
+  if (cos_out) {
+    if ((rc = mhip_launch_pair_cosine(ctx, run.emb, m->cfg.dim, run.pair_a, run.pair_b, n_pairs, run.cos))) return rc;
+    MHIP_HIP(ctx, hipMemcpyAsync(cos_out, run.cos, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (emb_out) MHIP_HIP(ctx, hipMemcpyAsync(emb_out, run.emb, (size_t)B * m->cfg.dim * 4, hipMemcpyDeviceToHost, ctx->stream));
+  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return MHIP_OK;
+}
+
+extern "C" int mhip_berttext_embed_host(mhip_berttext* m, const int32_t* ids, const int32_t* len, int B, int npad, float* emb_out) {
+  if (!m || !emb_out) return MHIP_EINVAL;
+  return berttext_run(m, ids, len, B, npad, nullptr, nullptr, 0, nullptr, nullptr, emb_out);
+}
+
+extern "C" int mhip_berttext_embed_pairs_host(mhip_berttext* m, const int32_t* ids, const int32_t* len, int B, int npad,
+                                              const int32_t* pair_a, const int32_t* pair_b, int n_pairs, float* cos_out, float* emb_out) {
+  if (!m || !pair_a || !pair_b || !cos_out) return MHIP_EINVAL;
+  return berttext_run(m, ids, len, B, npad, pair_a, pair_b, n_pairs, cos_out, nullptr, emb_out);
+}
+
+extern "C" int mhip_berttext_debug_taps_host(mhip_berttext* m, const int32_t* ids, const int32_t* len, int B, int npad, float* taps_out,
+                                             float* emb_out) {
+  if (!m || !taps_out) return MHIP_EINVAL;
+  return berttext_run(m, ids, len, B, npad, nullptr, nullptr, 0, nullptr, taps_out, emb_out);
+}
+
+// ---------------------------------------------------------------------------------------------------- the kernels alone
+extern "C" int mhip_berttext_embed_rows_host(mhip_ctx* ctx, const float* word, const float* type0, const float* pos, const float* g,
+                                             const float* b, float eps, const int32_t* ids, int B, int npad, int vocab, int D, float* h_out) {
+  if (!ctx || !word || !type0 || !g || !b || !ids || !h_out) return MHIP_EINVAL;
+  if (B < 1 || B > MAX_TEXTS || !npad_ok(npad, MAX_ROWS) || vocab < 1 || vocab > (1 << 24) || D < 64 || D % 64 || D > 1024 || !(eps > 0.f))
+    return mhip_fail(ctx, MHIP_EINVAL, "berttext_embed: B=%d npad=%d vocab=%d D=%d", B, npad, vocab, D);
+  const size_t R = (size_t)B * npad;
+  for (size_t e = 0; e < R; ++e)
+    if (ids[e] < 0 || ids[e] >= vocab) return mhip_fail(ctx, MHIP_EINVAL, "berttext_embed: id %d outside the vocabulary of %d", ids[e], vocab);
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  float *dw = nullptr, *dt = nullptr, *dp = nullptr, *dg = nullptr, *db = nullptr, *dh = nullptr;
+  int* di = nullptr;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
+    dw = ws.take<float>((size_t)vocab * D * 4); dt = ws.take<float>((size_t)D * 4); dp = ws.take<float>((size_t)npad * D * 4);
+    dg = ws.take<float>((size_t)D * 4); db = ws.take<float>((size_t)D * 4); di = ws.take<int>(R * 4); dh = ws.take<float>(R * D * 4);
+  });
+  if (rc) return rc;
+  MHIP_HIP(ctx, hipMemcpyAsync(dw, word, (size_t)vocab * D * 4, hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(dt, type0, (size_t)D * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (pos) MHIP_HIP(ctx, hipMemcpyAsync(dp, pos, (size_t)npad * D * 4, hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(dg, g, (size_t)D * 4, hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(db, b, (size_t)D * 4, hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(di, ids, R * 4, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = mhip_launch_berttext_embed(ctx, MHIP_PREC_F32, dw, dt, pos ? dp : nullptr, dg, db, eps, di, dh, nullptr, B, npad, D))) return rc;
+  MHIP_HIP(ctx, hipMemcpyAsync(h_out, dh, R * D * 4, hipMemcpyDeviceToHost, ctx->stream));
+  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return MHIP_OK;
+}
+
+extern "C" int mhip_berttext_attention_host(mhip_ctx* ctx, int precision, const float* q, const float* k, const float* v, const int32_t* len,
+                                            const float* slopes, int B, int heads, int head_dim, int npad, float* out) {
+  if (!ctx || !q || !k || !v || !len || !out) return MHIP_EINVAL;
+  if (precision != MHIP_PREC_F16 && precision != MHIP_PREC_F32) return mhip_fail(ctx, MHIP_EINVAL, "unknown precision %d", precision);
+  if (head_dim != 64 && head_dim != 32) return mhip_fail(ctx, MHIP_EINVAL, "berttext_attention: head_dim %d (64 or 32)", head_dim);
+  if (B < 1 || B > MAX_TEXTS || heads < 1 || heads > 32 || (heads * head_dim) % 64 || !npad_ok(npad, MAX_ROWS))
+    return mhip_fail(ctx, MHIP_EINVAL, "berttext_attention: B=%d heads=%d npad=%d", B, heads, npad);
+  for (int b = 0; b < B; ++b)
+    if (len[b] < 1 || len[b] > npad) return mhip_fail(ctx, MHIP_EINVAL, "berttext_attention: sequence %d has %d keys (1 .. %d)", b, len[b], npad);
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t es = precision == MHIP_PREC_F16 ? 2 : 4, D = (size_t)heads * head_dim, R = (size_t)B * npad;
+  EncoderWs w;
+  float *dout = nullptr, *dsl = nullptr;
+  int* dlen = nullptr;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
+    encoder_ws_carve(ws, R, D, 64, 0, es, &w); dout = ws.take<float>(R * D * 4); dlen = ws.take<int>((size_t)B * 4);
+    dsl = ws.take<float>((size_t)heads * 4);
+  });
+  if (rc) return rc;
+  // q | k rows of pitch 2 D and V^T [D][R], as the tower's GEMMs write them
+  std::vector<float> qk(R * 2 * D), vt(D * R);
+  for (size_t r = 0; r < R; ++r) {
+    memcpy(&qk[r * 2 * D], q + r * D, D * 4);
+    memcpy(&qk[r * 2 * D + D], k + r * D, D * 4);
+    for (size_t d = 0; d < D; ++d) vt[d * R + r] = v[r * D + d];
+  }
+  std::vector<char> qkt(qk.size() * es), vtt(vt.size() * es);
+  Arena::put(precision, qkt.data(), qk.data(), qk.size());
+  Arena::put(precision, vtt.data(), vt.data(), vt.size());
+  MHIP_HIP(ctx, hipMemcpyAsync(w.qk, qkt.data(), qkt.size(), hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(w.vt, vtt.data(), vtt.size(), hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(dlen, len, (size_t)B * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (slopes) MHIP_HIP(ctx, hipMemcpyAsync(dsl, slopes, (size_t)heads * 4, hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the sources are host temporaries in pageable memory
+  AttnShortDesc sd;
+  sd.a = encoder_attn_desc(w.qk, w.vt, w.ao, (int)D, es, B, heads, npad, npad);
+  sd.len = dlen; sd.slopes = slopes ? dsl : nullptr; sd.head_dim = head_dim;
+  if ((rc = mhip_launch_attention_short(ctx, precision, sd))) return rc;
+  if ((rc = mhip_launch_convert_rows(ctx, precision, w.ao, dout, (int)R, (int)D))) return rc;
+  MHIP_HIP(ctx, hipMemcpyAsync(out, dout, R * D * 4, hipMemcpyDeviceToHost, ctx->stream));
+  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return MHIP_OK;
+}
+
+extern "C" int mhip_berttext_geglu_host(mhip_ctx* ctx, int precision, const float* x, int R, int F, float* out) {
+  if (!ctx || !x || !out) return MHIP_EINVAL;
+  if (precision != MHIP_PREC_F16 && precision != MHIP_PREC_F32) return mhip_fail(ctx, MHIP_EINVAL, "unknown precision %d", precision);
+  if (R < 1 || R > (1 << 20) || F < 8 || F % 8 || F > (1 << 16)) return mhip_fail(ctx, MHIP_EINVAL, "geglu: R=%d F=%d (a multiple of 8)", R, F);
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t es = precision == MHIP_PREC_F16 ? 2 : 4, n = (size_t)R * F;
+  char *dx = nullptr, *dy = nullptr;
+  float* dout = nullptr;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) { dx = ws.take(2 * n * es); dy = ws.take(n * es); dout = ws.take<float>(n * 4); });
+  if (rc) return rc;
+  std::vector<char> xt(2 * n * es);
+  Arena::put(precision, xt.data(), x, 2 * n);
+  MHIP_HIP(ctx, hipMemcpyAsync(dx, xt.data(), xt.size(), hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));      // xt is a host temporary in pageable memory
+  if ((rc = mhip_launch_geglu(ctx, precision, dx, dy, R, F))) return rc;
+  if ((rc = mhip_launch_convert_rows(ctx, precision, dy, dout, R, F))) return rc;
+  MHIP_HIP(ctx, hipMemcpyAsync(out, dout, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return MHIP_OK;
+}
+
+extern "C" int mhip_berttext_pool_host(mhip_ctx* ctx, const float* h, const int32_t* len, int B, int npad, int D, int mode, int normalize,
+                                       float* emb_out) {
+  if (!ctx || !h || !len || !emb_out) return MHIP_EINVAL;
+  if (B < 1 || B > MAX_TEXTS || !npad_ok(npad, MAX_ROWS) || D < 64 || D % 64 || D > 1024 || (mode != BT_POOL_MEAN && mode != BT_POOL_CLS) ||
+      (normalize != 0 && normalize != 1))
+    return mhip_fail(ctx, MHIP_EINVAL, "berttext_pool: B=%d npad=%d D=%d mode=%d normalize=%d", B, npad, D, mode, normalize);
+  for (int b = 0; b < B; ++b)
+    if (len[b] < 1 || len[b] > npad) return mhip_fail(ctx, MHIP_EINVAL, "berttext_pool: text %d has %d tokens (1 .. %d)", b, len[b], npad);
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t HN = (size_t)B * npad * D;
+  float *dh = nullptr, *de = nullptr;
+  int* dl = nullptr;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) { dh = ws.take<float>(HN * 4); de = ws.take<float>((size_t)B * D * 4); dl = ws.take<int>((size_t)B * 4); });
+  if (rc) return rc;
+  MHIP_HIP(ctx, hipMemcpyAsync(dh, h, HN * 4, hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(dl, len, (size_t)B * 4, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = mhip_launch_berttext_pool(ctx, dh, dl, B, npad, D, mode == BT_POOL_CLS, normalize, de))) return rc;
+  MHIP_HIP(ctx, hipMemcpyAsync(emb_out, de, (size_t)B * D * 4, hipMemcpyDeviceToHost, ctx->stream));
+  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return MHIP_OK;
+}

@@ -14,42 +14,9 @@
 #include <algorithm>
 
 #include "igemm_common.h"
+#include "row_ops.h"
 
 namespace {
-
-constexpr int ROW_GROUPS = 4;      // float4 groups per lane: D <= 1024
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// LayerNorm of the row a wave holds, two-pass in registers; groups at columns >= D are not touched
-__device__ __forceinline__ void row_layernorm(float4v v[ROW_GROUPS], int D, int lane, const float* __restrict__ g,
-                                              const float* __restrict__ b, float eps) {
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < ROW_GROUPS; ++i)
-    if ((i * 64 + lane) * 4 < D) s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-  const float mean = wave_sum(s) / (float)D;
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < ROW_GROUPS; ++i)
-    if ((i * 64 + lane) * 4 < D)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { const float d = v[i][k] - mean; q += d * d; }
-  const float rstd = 1.f / sqrtf(wave_sum(q) / (float)D + eps);
-#pragma unroll
-  for (int i = 0; i < ROW_GROUPS; ++i) {
-    const int c = (i * 64 + lane) * 4;
-    if (c < D) {
-      const float4v gg = *(const float4v*)(g + c), bb = *(const float4v*)(b + c);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) v[i][k] = (v[i][k] - mean) * rstd * gg[k] + bb[k];
-    }
-  }
-}
 
 // ------------------------------------------------------------------------------------------------------- patches
 // clips u8 [B][S][S][3] (channel order as stored; `swap_rb`: stored channel 2 - c is model channel c)

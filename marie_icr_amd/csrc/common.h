@@ -50,7 +50,12 @@ enum MhipKernelId {
   MHIP_K_CLIPTEXT_EMBED = 29,    // token table gather + position rows -> fp32 stream
   MHIP_K_ATTN_CAUSAL = 30,       // causal soft-max attention, one workgroup per (sequence, head), K / V^T held in LDS
   MHIP_K_LEV_NGRAMS = 31,      // edit distance of every (template text, page n-gram) pair (lev_ngrams.hip)
-  MHIP_K_COUNT = 32
+  // BERT sentence encoders (berttext_ops.hip)
+  MHIP_K_ATTN_SHORT = 32,        // bidirectional soft-max attention over sequences of their own length (<= 128), optional ALiBi, head dim 64 / 32
+  MHIP_K_BERTTEXT_EMBED = 33,    // word + type + position rows -> LayerNorm -> fp32 stream; the post-LayerNorms of the layers
+  MHIP_K_GEGLU = 34,             // gelu(x[:, :F]) * x[:, F:]
+  MHIP_K_BERTTEXT_POOL = 35,     // masked mean / cls pooling, optional L2 normalisation
+  MHIP_K_COUNT = 36
 };
 
 constexpr int MHIP_ZERO_BYTES = 65536;
@@ -594,6 +599,29 @@ int mhip_launch_cliptext_embed(mhip_ctx* ctx, const float* table, const float* p
 // causal softmax(Q K^T) V over AttnDesc's layout (query row t sees keys 0 .. t): npad_q == npad_k <= 128, a multiple of 8; every
 // row < npad is written, nothing past a sequence's rows is read (no slack needed)
 int mhip_launch_attention_causal(mhip_ctx* ctx, int precision, const AttnDesc& d);
+// ------------------------------------------------------------------ BERT sentence encoder ops (berttext_ops.hip)
+// softmax(Q K^T [- slope |i - j|]) V over AttnDesc's layout with heads of head_dim (64 or 32) columns, sequence b attending to its
+// first len[b] keys (device, 1 .. npad; n_queries / n_keys of `a` are not used): npad_q == npad_k <= 128, a multiple of 8; every
+// row < npad is written, nothing past a sequence's rows is read (no slack needed).  slopes (device, [heads], in the log2 units of
+// q) or null: no bias term
+struct AttnShortDesc {
+  AttnDesc a;
+  const int* len = nullptr;
+  const float* slopes = nullptr;
+  int head_dim = 64;
+};
+int mhip_launch_attention_short(mhip_ctx* ctx, int precision, const AttnShortDesc& d);
+// h [B*npad][D] fp32 = LN((word[ids[row]] + type0) + pos[row % npad]), ht (null: not written) its copy in the precision's element
+// type; word [vocab][D], type0 [D], pos [>= npad][D] or null (no position table) fp32; the ids are the caller's to check
+int mhip_launch_berttext_embed(mhip_ctx* ctx, int precision, const float* word, const float* type0, const float* pos, const float* g,
+                               const float* b, float eps, const int* ids, float* h, void* ht, int B, int npad, int D);
+// h = LN(x) fp32 and ht (null: not written) its copy in the precision's element type; D % 64 == 0, D <= 1024; h may be x
+int mhip_launch_berttext_layernorm(mhip_ctx* ctx, int precision, const float* x, const float* g, const float* b, float* h, void* ht,
+                                   int rows, int D, float eps);
+// x [R][2 F] -> out [R][F] = gelu_erf(x[:, :F]) * x[:, F:], in the precision's element type; F % 8 == 0
+int mhip_launch_geglu(mhip_ctx* ctx, int precision, const void* x, void* out, long long R, int F);
+// emb [B][D] fp32: the mean of rows < len[b] of h [B][npad][D] (cls: row 0; len may be null), divided by max(norm, 1e-12) with normalize
+int mhip_launch_berttext_pool(mhip_ctx* ctx, const float* h, const int* len, int B, int npad, int D, int cls, int normalize, float* emb);
 size_t mhip_pil_resize_fragments_scratch(const mhip_crop_desc* descs, int n, int dh, int dw, int filter);
 int mhip_pil_resize_fragments(mhip_ctx* ctx, const uint8_t* base_dev, const mhip_crop_desc* descs, int n, uint8_t* dst, int dh,
                               int dw, int filter, void* scratch, size_t scratch_bytes);

@@ -23,7 +23,8 @@ static const char* kKernelNames[MHIP_K_COUNT] = {"conv_first", "conv_igemm", "ls
                                                  "conv3x3_patch", "cross_attn", "attn_bias",
                                                  "vq_assign", "vq_kmeans", "vq_heatmap", "vq_peaks", "clip_cosine",
                                                  "clipvis_patchify", "clipvis_embed", "quick_gelu", "clipvis_head", "pair_cosine",
-                                                 "cliptext_embed", "attn_causal", "lev_ngrams"};
+                                                 "cliptext_embed", "attn_causal", "lev_ngrams",
+                                                 "attn_short", "berttext_embed", "geglu", "berttext_pool"};
 
 extern "C" int mhip_kernel_count(void) { return MHIP_K_COUNT; }
 extern "C" const char* mhip_kernel_name(int k) { return (k >= 0 && k < MHIP_K_COUNT) ? kKernelNames[k] : ""; }

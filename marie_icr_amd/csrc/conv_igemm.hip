@@ -68,24 +68,6 @@ struct Cfg {
   static constexpr int LDS_BYTES = RING_BYTES > EPI_BYTES ? RING_BYTES : EPI_BYTES;
 };
 
-// erf GELU (torch.nn.functional.gelu / nn.GELU()).  erf by Abramowitz & Stegun 7.1.26 — |error| <= 1.5e-7 absolute, i.e.
-// about one fp32 ulp of (1 + erf) — branch-free: one v_rcp, one v_exp and five FMAs instead of ocml erff's two-branch
-// polynomial (the fc1 GEMM applies this to 3072 columns of every token).
-__device__ __forceinline__ float gelu_erf(float t) {
-  // every multiply-add is spelled out: the epilogue exists in several copies (bounds-checked, straight-line) and a tile's values
-  // must not depend on which copy wrote it — left to the compiler, the contraction of a * b + c may differ from copy to copy
-  const float x = t * 0.70710678118654752f, ax = fabsf(x);
-  const float u = __builtin_amdgcn_rcpf(__builtin_fmaf(0.3275911f, ax, 1.f));
-  float poly = __builtin_fmaf(1.061405429f, u, -1.453152027f);
-  poly = __builtin_fmaf(poly, u, 1.421413741f);
-  poly = __builtin_fmaf(poly, u, -0.284496736f);
-  poly = __builtin_fmaf(poly, u, 0.254829592f);
-  poly = poly * u;
-  const float e = __builtin_fmaf(-poly, __builtin_amdgcn_exp2f((-1.4426950408889634f * ax) * ax), 1.f);
-  const float h = 0.5f * t;
-  return __builtin_fmaf(h, copysignf(e, x), h);
-}
-
 // sum over the 8 lanes of an aligned lane group without leaving the VALU (HIP's __shfl_xor is a ds_bpermute: an LDS-crossbar round
 // trip per step): quad_perm [1,0,3,2], quad_perm [2,3,0,1], then row_half_mirror (lane i <-> 7 - i: the other quad's sum)
 template <int CTRL>

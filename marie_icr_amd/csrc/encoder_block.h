@@ -1,5 +1,5 @@
-// encoder_block.h — the transformer encoder layer the ViT (vit_api.hip), LayoutLMv3 (layoutlmv3_api.hip) and CLIP (clip_api.hip,
-// cliptext_api.hip) towers share, host side: its arena entries and how the checkpoint's weights are packed into them, its workspace, and the
+// encoder_block.h — the transformer encoder layer the ViT (vit_api.hip), LayoutLMv3 (layoutlmv3_api.hip), CLIP (clip_api.hip,
+// cliptext_api.hip) and BERT (berttext_api.hip) towers share, host side: its arena entries and how the checkpoint's weights are packed into them, its workspace, and the
 // attention half of a layer
 //   q|k = ht Wqk^T + b        V^T = Wv ht^T        ao = attention(q, k, V^T)
 // The LayerNorms, the residual wiring and the MLP activation differ between the towers and stay in the model files; the two
@@ -13,14 +13,16 @@ constexpr float ATTN_SCORE_SCALE = 0.125f * 1.4426950408889634f;
 
 inline std::string enc_blk(int i, const char* s) { return "l" + std::to_string(i) + "." + s; }
 
-// the entries of block i every tower has (D: width, F: MLP width, es: bytes of a GEMM element)
-inline void encoder_block_take(Arena& a, int i, size_t D, size_t F, size_t es) {
+// the entries of block i every tower has (D: width, F: MLP width, es: bytes of a GEMM element).  gated: fc1 is the doubled,
+// bias-free matrix of a gated MLP ([2 F][D]: the activated half, then the linear half) and there is no fc1_b entry
+inline void encoder_block_take(Arena& a, int i, size_t D, size_t F, size_t es, bool gated = false) {
   a.take(enc_blk(i, "ln1_g"), D * 4); a.take(enc_blk(i, "ln1_b"), D * 4);
   a.take(enc_blk(i, "qk_w"), 2 * D * D * es); a.take(enc_blk(i, "qk_b"), 2 * D * 4);
   a.take(enc_blk(i, "v_w"), D * D * es);
   a.take(enc_blk(i, "ao_w"), D * D * es); a.take(enc_blk(i, "ao_b"), D * 4);
   a.take(enc_blk(i, "ln2_g"), D * 4); a.take(enc_blk(i, "ln2_b"), D * 4);
-  a.take(enc_blk(i, "fc1_w"), F * D * es); a.take(enc_blk(i, "fc1_b"), F * 4);
+  if (gated) a.take(enc_blk(i, "fc1_w"), 2 * F * D * es);
+  else { a.take(enc_blk(i, "fc1_w"), F * D * es); a.take(enc_blk(i, "fc1_b"), F * 4); }
   a.take(enc_blk(i, "fc2_w"), D * F * es); a.take(enc_blk(i, "fc2_b"), D * 4);
 }
 
@@ -30,21 +32,22 @@ struct EncoderBlockWeights {
   const float *bq = nullptr, *bk = nullptr, *bv = nullptr;      // [D] each; null = zeros
   const float *wo = nullptr, *bo = nullptr;                     // output projection [D][D], [D]
   const float *ln1_g = nullptr, *ln1_b = nullptr, *ln2_g = nullptr, *ln2_b = nullptr;
-  const float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr;      // [F][D], [F], [D][F], [D]
+  const float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr;      // [F][D], [F], [D][F], [D]; gated: w1 [2 F][D], no b1
+  bool gated = false;
 };
 
 // fills the entries of encoder_block_take: q (scaled) | k back to back, v apart, and the value bias moved behind the soft-max —
-// its rows sum to one, so  W_o (ctx + b_v) + b_o = W_o ctx + (b_o + W_o b_v)
-inline void encoder_block_fill(Arena& a, int prec, int i, int D, int F, const EncoderBlockWeights& w) {
+// its rows sum to one, so  W_o (ctx + b_v) + b_o = W_o ctx + (b_o + W_o b_v).  score_scale: head_dim^-0.5 * log2(e) of the tower's heads
+inline void encoder_block_fill(Arena& a, int prec, int i, int D, int F, const EncoderBlockWeights& w, float score_scale = ATTN_SCORE_SCALE) {
   const size_t es = prec == MHIP_PREC_F16 ? 2 : 4, DD = (size_t)D * D;
   const std::vector<float> zeros(D, 0.f);
   const float *bq = w.bq ? w.bq : zeros.data(), *bk = w.bk ? w.bk : zeros.data(), *bv = w.bv ? w.bv : zeros.data();
   std::vector<float> wq(DD);
-  for (size_t e = 0; e < DD; ++e) wq[e] = w.wq[e] * ATTN_SCORE_SCALE;
+  for (size_t e = 0; e < DD; ++e) wq[e] = w.wq[e] * score_scale;
   Arena::put(prec, a.h(enc_blk(i, "qk_w")), wq.data(), DD);
   Arena::put(prec, a.h(enc_blk(i, "qk_w")) + DD * es, w.wk, DD);
   float* qkb = (float*)a.h(enc_blk(i, "qk_b"));
-  for (int d = 0; d < D; ++d) { qkb[d] = bq[d] * ATTN_SCORE_SCALE; qkb[D + d] = bk[d]; }
+  for (int d = 0; d < D; ++d) { qkb[d] = bq[d] * score_scale; qkb[D + d] = bk[d]; }
   Arena::put(prec, a.h(enc_blk(i, "v_w")), w.wv, DD);
   Arena::put(prec, a.h(enc_blk(i, "ao_w")), w.wo, DD);
   float* aob = (float*)a.h(enc_blk(i, "ao_b"));
@@ -55,8 +58,8 @@ inline void encoder_block_fill(Arena& a, int prec, int i, int D, int F, const En
   }
   memcpy(a.h(enc_blk(i, "ln1_g")), w.ln1_g, (size_t)D * 4); memcpy(a.h(enc_blk(i, "ln1_b")), w.ln1_b, (size_t)D * 4);
   memcpy(a.h(enc_blk(i, "ln2_g")), w.ln2_g, (size_t)D * 4); memcpy(a.h(enc_blk(i, "ln2_b")), w.ln2_b, (size_t)D * 4);
-  Arena::put(prec, a.h(enc_blk(i, "fc1_w")), w.w1, (size_t)F * D);
-  memcpy(a.h(enc_blk(i, "fc1_b")), w.b1, (size_t)F * 4);
+  Arena::put(prec, a.h(enc_blk(i, "fc1_w")), w.w1, (size_t)(w.gated ? 2 : 1) * F * D);
+  if (!w.gated) memcpy(a.h(enc_blk(i, "fc1_b")), w.b1, (size_t)F * 4);
   Arena::put(prec, a.h(enc_blk(i, "fc2_w")), w.w2, (size_t)D * F);
   memcpy(a.h(enc_blk(i, "fc2_b")), w.b2, (size_t)D * 4);
 }
@@ -133,7 +136,8 @@ struct AttnCausalDesc {
   AttnDesc a;
 };
 
-// the attention half of block i, w.ht -> w.ao: plain, with LayoutLMv3's bias and key mask (bd.a the descriptor), or causal
+// the attention half of block i, w.ht -> w.ao: plain, with LayoutLMv3's bias and key mask (bd.a the descriptor), causal, or over
+// sequences of their own length (berttext_ops.hip)
 inline int encoder_block_attention(mhip_ctx* ctx, int prec, const Arena& a, int i, const EncoderWs& w, const AttnDesc& ad) {
   const int rc = encoder_block_qkv(ctx, prec, a, i, w, ad);
   return rc ? rc : mhip_launch_attention(ctx, prec, ad);
@@ -145,6 +149,10 @@ inline int encoder_block_attention(mhip_ctx* ctx, int prec, const Arena& a, int 
 inline int encoder_block_attention(mhip_ctx* ctx, int prec, const Arena& a, int i, const EncoderWs& w, const AttnCausalDesc& cd) {
   const int rc = encoder_block_qkv(ctx, prec, a, i, w, cd.a);
   return rc ? rc : mhip_launch_attention_causal(ctx, prec, cd.a);
+}
+inline int encoder_block_attention(mhip_ctx* ctx, int prec, const Arena& a, int i, const EncoderWs& w, const AttnShortDesc& sd) {
+  const int rc = encoder_block_qkv(ctx, prec, a, i, w, sd.a);
+  return rc ? rc : mhip_launch_attention_short(ctx, prec, sd);
 }
 
 // The layers of a CLIP tower (vision: AttnDesc, text: AttnCausalDesc) on the fp32 stream h [R][D]:

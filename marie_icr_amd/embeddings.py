@@ -1,5 +1,5 @@
-"""CLIP image and text embeddings on the MI355X: ``OpenAIEmbeddings`` / ``OpenAITransformerEmbeddings`` behind the reference's
-surface.
+"""CLIP image and text embeddings and BERT sentence embeddings on the MI355X: ``OpenAIEmbeddings`` /
+``OpenAITransformerEmbeddings`` / ``SentenceTransformerEmbeddings`` / ``JinaEmbeddings`` behind the reference's surface.
 
 Mirrors marie/embeddings/{embeddings_object,base}.py and marie/embeddings/openai/{openai_embeddings,openai_trans_embeddings}.py
 for what ``VQNNFTemplateMatcher.score`` takes from them: the image embedding of a 224 x 224 snippet clip, 95 % of the weighted
@@ -14,6 +14,12 @@ one and a vocabulary is at hand: ``get_embeddings(texts, image=None)`` embeds ``
 ``ModifiedResNet`` towers (``RN50x4`` ...: ``NotImplementedError``).  Without a text side ``image=None`` raises
 ``NotImplementedError``.  Errors raise ``MarieHipError`` (a text longer than the context: ``ValueError``); the reference's
 ``try/except`` returning an empty ``EmbeddingsObject`` is not restated.
+
+The sentence encoders (marie/embeddings/sentence_transformers/sentence_transformers_embeddings.py, marie/embeddings/jina/
+jina_embeddings.py) are at the end of the file: Hugging Face BERT (all-MiniLM-L6-v2) and JinaBERT (ALiBi, GEGLU) with masked mean
+or [CLS] pooling in HIP (csrc/berttext_api.hip, ``mhip_berttext_*``), WordPiece on the host (wordpiece_tokenizer.py).  A text is
+at most 128 tokens here (the attention kernel holds a text's keys in LDS): the reference's models take 256 (MiniLM) and 8192
+(Jina).  A longer text raises ``ValueError`` unless ``truncation=True`` cuts it to ``min(model limit, 128)`` tokens.
 """
 from __future__ import annotations
 
@@ -27,8 +33,9 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from ._lib import PREC_F16, PREC_F32, ClipTextConfig, ClipVisConfig, Context, MarieHipError, ModelHandle, check
+from ._lib import PREC_F16, PREC_F32, BertTextConfig, ClipTextConfig, ClipVisConfig, Context, MarieHipError, ModelHandle, check, load
 from .clip_tokenizer import ClipTokenizer
+from .wordpiece_tokenizer import WordPieceTokenizer
 
 logger = logging.getLogger(__name__)
 
@@ -579,3 +586,416 @@ class OpenAIEmbeddings(ClipImageEmbeddings):
 
 class OpenAITransformerEmbeddings(ClipImageEmbeddings):
     """marie/embeddings/openai/openai_trans_embeddings.py (``transformers.CLIPModel``, openai/clip-vit-base-patch32)"""
+
+
+# ---------------------------------------------------------------------------------------------------- BERT sentence encoders
+BERT_MAX_TOKENS = 128      # tokens of a text, [CLS] and [SEP] included: attn_short holds a text's keys in LDS
+POS_ABSOLUTE, POS_ALIBI = 0, 1
+MLP_GELU, MLP_GEGLU = 0, 1
+POOL_MEAN, POOL_CLS = 0, 1
+
+_BERT_ATTENTION = [("attention.self.query", "dd"), ("attention.self.key", "dd"), ("attention.self.value", "dd"),
+                   ("attention.output.dense", "dd"), ("attention.output.LayerNorm", "d")]
+_BERT_MLP = {MLP_GELU: [("intermediate.dense", "fd"), ("output.dense", "df"), ("output.LayerNorm", "d")],
+             MLP_GEGLU: [("mlp.gated_layers", "2d"), ("mlp.wo", "df"), ("mlp.layernorm", "d")]}
+
+
+def alibi_slopes(heads: int) -> np.ndarray:
+    """the ALiBi slopes of ``heads`` heads as the encoder builds them, fp32 (heads,)"""
+    out = np.empty(int(heads), np.float32)
+    rc = load().mhip_berttext_alibi_slopes(int(heads), _vp(out))
+    if rc:
+        raise MarieHipError(f"mhip_berttext_alibi_slopes({heads}) failed ({rc})")
+    return out
+
+
+def bert_text_keys(cfg: BertTextConfig) -> Dict[str, Tuple[int, ...]]:
+    """every tensor the encoder of ``cfg`` takes -> its shape, in the order ``finalize`` looks them up"""
+    D, F = cfg.dim, cfg.ffn
+    dims = {"d": D, "f": F, "2": 2 * F}
+    keys = {"embeddings.word_embeddings.weight": (cfg.vocab, D),
+            "embeddings.token_type_embeddings.weight": (cfg.type_vocab, D),
+            "embeddings.LayerNorm.weight": (D,), "embeddings.LayerNorm.bias": (D,)}
+    if cfg.position == POS_ABSOLUTE:
+        keys["embeddings.position_embeddings.weight"] = (cfg.max_position, D)
+    for n in range(cfg.depth):
+        for name, shape in _BERT_ATTENTION + _BERT_MLP[cfg.mlp]:
+            if len(shape) == 2:
+                keys[f"encoder.layer.{n}.{name}.weight"] = (dims[shape[0]], dims[shape[1]])
+            else:
+                keys[f"encoder.layer.{n}.{name}.weight"] = (D,)
+            if name != "mlp.gated_layers":
+                keys[f"encoder.layer.{n}.{name}.bias"] = (dims[shape[0]],)
+    return keys
+
+
+def load_bert_text_state(checkpoint: Dict[str, Any], config_json: Dict[str, Any]) -> Tuple[Dict[str, np.ndarray], BertTextConfig]:
+    """A loaded BERT checkpoint (a state dict, an optional ``bert.`` prefix on its keys) and its ``config.json`` -> (the
+    encoder's tensors as float32 arrays, the geometry).  The scheme is read from both: ``mlp.gated_layers`` keys or
+    ``feed_forward_type: geglu`` make the MLP JinaBERT's, ``position_embedding_type: alibi`` (or no position table) drops the
+    position rows.  Pooling and normalisation are the embeddings class's to set.  A missing or misshapen tensor raises,
+    named."""
+    sd = checkpoint.get("model_state_dict", checkpoint) if isinstance(checkpoint, dict) else None
+    if not isinstance(sd, dict) or not sd:
+        raise MarieHipError("BERT checkpoint: expected a state dict or {'model_state_dict': state dict}")
+    sd = {(k[5:] if k.startswith("bert.") else k): v for k, v in sd.items()}
+    cfg = BertTextConfig()
+    try:
+        cfg.vocab, cfg.dim = int(config_json["vocab_size"]), int(config_json["hidden_size"])
+        cfg.heads, cfg.depth = int(config_json["num_attention_heads"]), int(config_json["num_hidden_layers"])
+        cfg.ffn = int(config_json["intermediate_size"])
+    except KeyError as e:
+        raise MarieHipError(f"BERT config.json: no {e.args[0]}") from None
+    cfg.max_position = int(config_json.get("max_position_embeddings", 512))
+    cfg.type_vocab = int(config_json.get("type_vocab_size", 2))
+    cfg.ln_eps = float(config_json.get("layer_norm_eps", 1e-12))
+    gated = any(k.endswith("mlp.gated_layers.weight") for k in sd)
+    ff = str(config_json.get("feed_forward_type", "geglu" if gated else "original"))
+    if ff not in ("original", "geglu"):
+        raise NotImplementedError(f"BERT config.json: feed_forward_type {ff!r} (original and geglu are built)")
+    cfg.mlp = MLP_GEGLU if ff == "geglu" else MLP_GELU
+    pe = str(config_json.get("position_embedding_type",
+                             "absolute" if "embeddings.position_embeddings.weight" in sd else "alibi"))
+    if pe not in ("absolute", "alibi"):
+        raise NotImplementedError(f"BERT config.json: position_embedding_type {pe!r} (absolute and alibi are built)")
+    cfg.position = POS_ALIBI if pe == "alibi" else POS_ABSOLUTE
+    act = str(config_json.get("hidden_act", "gelu"))
+    if act != "gelu":
+        raise NotImplementedError(f"BERT config.json: hidden_act {act!r} (the erf GELU is built)")
+    cfg.pool, cfg.normalize = POOL_MEAN, 0
+    state = {}
+    for key, shape in bert_text_keys(cfg).items():
+        if key not in sd:
+            raise MarieHipError(f"BERT checkpoint: no {key} ({'JinaBERT' if cfg.mlp == MLP_GEGLU else 'Hugging Face BERT'} keys, "
+                                f"{'no' if cfg.position == POS_ALIBI else 'a'} position table)")
+        arr = _f32(sd[key])
+        if arr.shape != shape:
+            raise MarieHipError(f"BERT checkpoint: {key} has shape {arr.shape}, the configuration asks for {shape}")
+        state[key] = arr
+    return state, cfg
+
+
+def read_sentence_model_dir(model_dir) -> Dict[str, Any]:
+    """What a sentence-transformers model directory says beyond ``config.json``: ``pooling`` ("mean" / "cls") of
+    ``1_Pooling/config.json`` (or of the Pooling module ``modules.json`` names), ``normalize`` (a Normalize module is listed),
+    ``max_seq_length`` of ``sentence_bert_config.json``.  Only the keys the directory settles are returned."""
+    out: Dict[str, Any] = {}
+
+    def read(*parts):
+        path = os.path.join(model_dir, *parts)
+        if not os.path.isfile(path):
+            return None
+        with open(path, "r", encoding="utf-8") as f:
+            return json.load(f)
+
+    pooling_dir = "1_Pooling"
+    modules = read("modules.json")
+    if modules is not None:
+        out["normalize"] = any(str(m.get("type", "")).endswith(".Normalize") for m in modules)
+        for m in modules:
+            if str(m.get("type", "")).endswith(".Pooling"):
+                pooling_dir = m.get("path", pooling_dir)
+    pooling = read(pooling_dir, "config.json")
+    if pooling is not None:
+        modes = [k[len("pooling_mode_"):] for k, v in pooling.items() if k.startswith("pooling_mode_") and v is True]
+        if modes == ["mean_tokens"]:
+            out["pooling"] = "mean"
+        elif modes == ["cls_token"]:
+            out["pooling"] = "cls"
+        else:
+            raise NotImplementedError(f"{os.path.join(model_dir, pooling_dir)}: pooling modes {modes} (mean_tokens or cls_token "
+                                      "alone are built)")
+    sbert = read("sentence_bert_config.json")
+    if sbert is not None and sbert.get("max_seq_length") is not None:
+        out["max_seq_length"] = int(sbert["max_seq_length"])
+    return out
+
+
+class BertTextModel(ModelHandle):
+    """``mhip_berttext``: a BERT sentence encoder + pooling on a :class:`Context`.  Ids come from
+    :class:`~marie_icr_amd.wordpiece_tokenizer.WordPieceTokenizer`."""
+
+    def __init__(self, ctx: Context, state: Optional[Dict[str, np.ndarray]], config: BertTextConfig, precision: int = PREC_F16):
+        self.cfg, self.precision = config, int(precision)
+        super().__init__(ctx, "berttext", self.precision, C.byref(config))
+        if state is not None:
+            self.load_state(state)
+
+    @staticmethod
+    def _ids(ids, lens) -> Tuple[np.ndarray, np.ndarray]:
+        ids, lens = np.ascontiguousarray(ids, np.int32), np.ascontiguousarray(lens, np.int32).reshape(-1)
+        if ids.ndim != 2 or ids.shape[0] < 1 or lens.shape[0] != ids.shape[0]:
+            raise ValueError(f"ids of shape (n, npad) and lengths of shape (n,) expected, got {ids.shape} and {lens.shape}")
+        return ids, lens
+
+    def workspace_bytes(self, n: int, npad: int) -> int:
+        return int(self.lib.mhip_berttext_workspace_bytes(self.h, int(n), int(npad)))
+
+    def embed_ids_host(self, ids, lens) -> np.ndarray:
+        """ids int32 (n, npad), lengths int32 (n,) -> embeddings fp32 (n, dim), one encoder call"""
+        ids, lens = self._ids(ids, lens)
+        out = np.empty((ids.shape[0], self.cfg.dim), np.float32)
+        self._call("embed_host", _vp(ids), _vp(lens), ids.shape[0], ids.shape[1], _vp(out))
+        return out
+
+    def embed_pairs_host(self, ids, lens, pairs, want_embeddings: bool = False):
+        """the texts through the encoder once and the cosine of every (a, b) index pair -> fp32 (n_pairs,)
+        (, embeddings (n, dim))"""
+        ids, lens = self._ids(ids, lens)
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        pa, pb = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
+        cos = np.empty(len(pairs), np.float32)
+        emb = np.empty((ids.shape[0], self.cfg.dim), np.float32) if want_embeddings else None
+        self._call("embed_pairs_host", _vp(ids), _vp(lens), ids.shape[0], ids.shape[1], _vp(pa), _vp(pb), len(pairs), _vp(cos), _vp(emb))
+        return (cos, emb) if want_embeddings else cos
+
+    def debug_taps_host(self, ids, lens):
+        """-> (taps fp32 (depth + 1, n, npad, dim): the residual stream after the embedding kernel and after every layer,
+        embeddings (n, dim))"""
+        ids, lens = self._ids(ids, lens)
+        n, npad = ids.shape
+        taps = np.empty((self.cfg.depth + 1, n, npad, self.cfg.dim), np.float32)
+        emb = np.empty((n, self.cfg.dim), np.float32)
+        self._call("debug_taps_host", _vp(ids), _vp(lens), n, npad, _vp(taps), _vp(emb))
+        return taps, emb
+
+
+# ---- the kernels on host arrays (what tests/test_berttext_gpu.py drives)
+def short_attention_host(ctx: Context, precision: int, q, k, v, lens, heads: int, slopes=None) -> np.ndarray:
+    """q, k, v fp32 (B, npad, heads * head_dim), q already scaled by head_dim^-0.5 * log2(e), lens int32 (B,), slopes fp32
+    (heads,) in the same log2 units or None -> fp32, same shape"""
+    q, k, v = (np.ascontiguousarray(a, np.float32) for a in (q, k, v))
+    lens = np.ascontiguousarray(lens, np.int32).reshape(-1)
+    B, npad, D = q.shape
+    if D % heads or k.shape != q.shape or v.shape != q.shape or lens.shape[0] != B:
+        raise ValueError(f"q, k, v of one shape (B, npad, heads * head_dim) and B lengths expected, got {q.shape}, {k.shape}, "
+                         f"{v.shape}, {lens.shape}")
+    if slopes is not None:
+        slopes = np.ascontiguousarray(slopes, np.float32).reshape(-1)
+        if slopes.shape[0] != heads:
+            raise ValueError(f"{heads} slopes expected, got {slopes.shape[0]}")
+    out = np.empty_like(q)
+    check(ctx.h, ctx.lib.mhip_berttext_attention_host(ctx.h, int(precision), _vp(q), _vp(k), _vp(v), _vp(lens), _vp(slopes), B,
+                                                      int(heads), D // heads, npad, _vp(out)), "mhip_berttext_attention_host")
+    return out
+
+
+def bert_embed_rows_host(ctx: Context, word, type0, pos, g, b, ids, eps: float = 1e-12) -> np.ndarray:
+    """word (vocab, D), type0 (D), pos (npad, D) or None, LayerNorm g / b (D), ids int32 (B, npad) -> h fp32 (B, npad, D)"""
+    word, type0, g, b = (np.ascontiguousarray(a, np.float32) for a in (word, type0, g, b))
+    pos = None if pos is None else np.ascontiguousarray(pos, np.float32)
+    ids = np.ascontiguousarray(ids, np.int32)
+    B, npad = ids.shape
+    if pos is not None and pos.shape != (npad, word.shape[1]):
+        raise ValueError(f"pos of shape {(npad, word.shape[1])} expected, got {pos.shape}")
+    out = np.empty((B, npad, word.shape[1]), np.float32)
+    check(ctx.h, ctx.lib.mhip_berttext_embed_rows_host(ctx.h, _vp(word), _vp(type0), _vp(pos), _vp(g), _vp(b), float(eps), _vp(ids),
+                                                       B, npad, word.shape[0], word.shape[1], _vp(out)),
+          "mhip_berttext_embed_rows_host")
+    return out
+
+
+def geglu_host(ctx: Context, precision: int, x) -> np.ndarray:
+    """x fp32 (R, 2 F) -> fp32 (R, F) = gelu(x[:, :F]) * x[:, F:]"""
+    x = np.ascontiguousarray(x, np.float32)
+    R, F2 = x.shape
+    out = np.empty((R, F2 // 2), np.float32)
+    check(ctx.h, ctx.lib.mhip_berttext_geglu_host(ctx.h, int(precision), _vp(x), R, F2 // 2, _vp(out)), "mhip_berttext_geglu_host")
+    return out
+
+
+def bert_pool_host(ctx: Context, h, lens, mode: int = POOL_MEAN, normalize: bool = False) -> np.ndarray:
+    """h fp32 (B, npad, D), lens int32 (B,) -> fp32 (B, D)"""
+    h = np.ascontiguousarray(h, np.float32)
+    lens = np.ascontiguousarray(lens, np.int32).reshape(-1)
+    B, npad, D = h.shape
+    out = np.empty((B, D), np.float32)
+    check(ctx.h, ctx.lib.mhip_berttext_pool_host(ctx.h, _vp(h), _vp(lens), B, npad, D, int(mode), 1 if normalize else 0, _vp(out)),
+          "mhip_berttext_pool_host")
+    return out
+
+
+def plan_text_groups(lengths: Sequence[int], max_group: int, rows_budget: Optional[int] = None) -> List[Tuple[int, List[int]]]:
+    """The calls of ``embed_texts``: the texts sorted by token count (ties in input order) and cut into groups of at most
+    ``max_group`` texts — and, with ``rows_budget``, of at most that many rows — that share one ``npad``, the longest of the
+    group rounded up to 8 -> [(npad, [input indices])]"""
+    order = sorted(range(len(lengths)), key=lambda i: (lengths[i], i))
+    groups: List[Tuple[int, List[int]]] = []
+    at = 0
+    while at < len(order):
+        end = min(at + max_group, len(order))
+        npad = (lengths[order[end - 1]] + 7) // 8 * 8
+        # a shorter group of the same start never needs more rows a text
+        while rows_budget is not None and end - at > 1 and (end - at) * npad > rows_budget:
+            end -= 1
+            npad = (lengths[order[end - 1]] + 7) // 8 * 8
+        groups.append((npad, order[at:end]))
+        at = end
+    return groups
+
+
+class BertTextEmbeddings(EmbeddingsBase):
+    """What the two sentence-embedding classes share: the encoder, the tokenizer, the length-bucketed batching and the
+    entries ``MetaTemplateMatcher`` uses (``text_model``, ``embed_texts``, ``pair_cosines``)."""
+
+    POOLING, NORMALIZE = "mean", False       # what a directory without modules.json / 1_Pooling gets
+    MAX_LENGTH: Optional[int] = None         # max_seq_length without a sentence_bert_config.json: the position table's
+    TEXT_CHUNK = 1024                        # texts of one encoder call
+    WORKSPACE_BUDGET = 1 << 30               # bytes of workspace one call may lay out
+
+    def __init__(self, model_name_or_path: Union[str, os.PathLike, None] = None, model_version: Optional[str] = None,
+                 use_gpu: bool = True, batch_size: int = 4, use_auth_token: Optional[Union[str, bool]] = None,
+                 devices: Optional[List[Any]] = None, show_error: Optional[Union[str, bool]] = True, *,
+                 state: Optional[Dict[str, Any]] = None, config: Optional[Dict[str, Any]] = None,
+                 tokenizer: Optional[WordPieceTokenizer] = None, precision: Union[str, int] = "f16",
+                 ctx: Optional[Context] = None, pooling: Optional[str] = None, normalize: Optional[bool] = None,
+                 max_seq_length: Optional[int] = None, **kwargs):
+        """``model_name_or_path``: a model directory holding ``config.json``, ``model.safetensors`` or ``pytorch_model.bin``,
+        ``vocab.txt`` and, optionally, ``modules.json``, ``1_Pooling/config.json`` and ``sentence_bert_config.json``.
+        ``state`` / ``config`` / ``tokenizer``: the loaded checkpoint, the ``config.json`` dict and the tokenizer instead.
+        ``pooling`` ("mean" / "cls"), ``normalize`` and ``max_seq_length`` override what the directory (or the class) says."""
+        super().__init__(**kwargs)
+        if not use_gpu:
+            raise MarieHipError(f"{type(self).__name__} here is the MI355X path; use_gpu=False has no implementation")
+        self.show_error, self.batch_size = show_error, batch_size
+        self.model_name_or_path = model_name_or_path
+        said: Dict[str, Any] = {}
+        if state is None or config is None or tokenizer is None:
+            if model_name_or_path is None or not os.path.isdir(model_name_or_path):
+                raise MarieHipError(f"{type(self).__name__}: a model directory, or state, config and tokenizer, is required")
+        if model_name_or_path is not None and os.path.isdir(model_name_or_path):
+            said = read_sentence_model_dir(model_name_or_path)
+        if config is None:
+            config = self._load_config(model_name_or_path)
+        if state is None:
+            state = self._load_checkpoint(model_name_or_path)
+        if tokenizer is None:
+            tokenizer = WordPieceTokenizer.from_dir(model_name_or_path)
+            if tokenizer is None:
+                raise MarieHipError(f"{type(self).__name__}: no vocab.txt in {model_name_or_path}")
+        tensors, cfg = load_bert_text_state(state, config)      # before any device work
+        if len(tokenizer) > cfg.vocab:
+            raise MarieHipError(f"{type(self).__name__}: the vocabulary has {len(tokenizer)} entries, the word table {cfg.vocab} rows")
+        pooling = pooling or said.get("pooling", self.POOLING)
+        if pooling not in ("mean", "cls"):
+            raise ValueError(f"pooling {pooling!r}: 'mean' or 'cls'")
+        normalize = said.get("normalize", self.NORMALIZE) if normalize is None else normalize
+        cfg.pool, cfg.normalize = (POOL_CLS if pooling == "cls" else POOL_MEAN), (1 if normalize else 0)
+        self.pooling, self.normalize = pooling, bool(normalize)
+        limit = max_seq_length or said.get("max_seq_length") or self.MAX_LENGTH
+        if cfg.position == POS_ABSOLUTE:
+            limit = min(limit or cfg.max_position, cfg.max_position)
+        self.max_seq_length = limit                                      # the model's own limit (None: none)
+        self.max_tokens = min(limit or BERT_MAX_TOKENS, BERT_MAX_TOKENS)   # this build's
+        if isinstance(precision, str):
+            if precision not in ("f16", "f32"):
+                raise ValueError(f"precision {precision!r}: 'f16' or 'f32'")
+            precision = PREC_F16 if precision == "f16" else PREC_F32
+        self.tokenizer = tokenizer
+        self.ctx = ctx or Context(_device_id(devices))
+        self.text_model = BertTextModel(self.ctx, tensors, cfg, precision)
+        self.dim = cfg.dim
+        self.text_encoder_calls = 0          # device encoder calls so far
+        self.texts_embedded = 0              # texts those calls carried
+
+    def _load_config(self, path):
+        file = os.path.join(path, "config.json")
+        if not os.path.isfile(file):
+            raise MarieHipError(f"{type(self).__name__}: no config.json in {path}")
+        with open(file, "r", encoding="utf-8") as f:
+            return json.load(f)
+
+    def _load_checkpoint(self, path):
+        file = os.path.join(path, "model.safetensors")
+        if os.path.isfile(file):
+            from safetensors.numpy import load_file
+
+            return load_file(file)
+        file = os.path.join(path, "pytorch_model.bin")
+        if os.path.isfile(file):
+            import torch
+
+            return torch.load(file, map_location="cpu")
+        raise MarieHipError(f"{type(self).__name__}: neither model.safetensors nor pytorch_model.bin in {path}")
+
+    def close(self):
+        if getattr(self, "text_model", None) is not None:
+            self.text_model.close()
+
+    # -- tokens ----------------------------------------------------------------------------------------------------------
+    def encode_texts(self, texts: Sequence[str], truncation: bool = False) -> List[List[int]]:
+        """``[CLS]`` .. ``[SEP]`` ids of every text; more than ``max_tokens`` of them raise ``ValueError`` unless ``truncation``"""
+        out = []
+        for i, text in enumerate(texts):
+            ids = self.tokenizer.encode(text, self.max_tokens if truncation else None)
+            if len(ids) > self.max_tokens:
+                raise ValueError(f"text {i} is too long: {len(ids)} tokens, at most {self.max_tokens} are built "
+                                 f"(truncation=True cuts it)")
+            out.append(ids)
+        return out
+
+    def _groups(self, lengths: Sequence[int], chunk: Optional[int]):
+        chunk = min(int(chunk or self.TEXT_CHUNK), self.TEXT_CHUNK)
+        if chunk < 1:
+            raise ValueError(f"chunk of {chunk} texts")
+        per_row = self.text_model.workspace_bytes(8, BERT_MAX_TOKENS) // (8 * BERT_MAX_TOKENS)      # the workspace grows with the rows
+        return plan_text_groups(lengths, chunk, max(self.WORKSPACE_BUDGET // max(per_row, 1), BERT_MAX_TOKENS))
+
+    # -- the matcher's entries -------------------------------------------------------------------------------------------
+    def embed_texts(self, texts: Sequence[str], truncation: bool = False, chunk: Optional[int] = None) -> np.ndarray:
+        """-> fp32 (n, dim), rows in input order.  The texts are sorted by token count and embedded in groups that share one
+        ``npad``; a text's embedding does not depend on its group, bit for bit."""
+        encoded = self.encode_texts(list(texts), truncation)
+        out = np.empty((len(encoded), self.dim), np.float32)
+        for npad, members in self._groups([len(e) for e in encoded], chunk):
+            ids, lens = self.tokenizer.pad([encoded[i] for i in members], npad)
+            self.text_encoder_calls += 1
+            self.texts_embedded += len(members)
+            out[members] = self.text_model.embed_ids_host(ids, lens)
+        return out
+
+    def text_cosine_pairs(self, texts: Sequence[str], pairs: Sequence[Tuple[int, int]], want_embeddings: bool = False,
+                          truncation: bool = False):
+        """the cosine of the embeddings of every (a, b) index pair of ``texts`` -> fp32 (n_pairs,) (, embeddings fp32
+        (n, dim)).  Duplicate texts are embedded once."""
+        texts = list(texts)
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        if len(pairs) and (pairs.min() < 0 or pairs.max() >= len(texts)):
+            raise ValueError(f"a pair names a text outside 0 .. {len(texts) - 1}")
+        first: Dict[str, int] = {}
+        slot = np.array([first.setdefault(t, len(first)) for t in texts], np.int32)
+        emb = self.embed_texts(list(first), truncation)
+        cos = pair_cosine_host(self.ctx, emb, slot[pairs]) if len(pairs) else np.empty(0, np.float32)
+        return (cos, emb[slot]) if want_embeddings else cos
+
+    def pair_cosines(self, embeddings, pairs: Sequence[Tuple[int, int]]) -> np.ndarray:
+        """the cosine kernel alone on embeddings already at hand, fp32 (n, dim) -> fp32 (n_pairs,)"""
+        return pair_cosine_host(self.ctx, embeddings, pairs)
+
+    # -- the reference's entry ---------------------------------------------------------------------------------------------
+    TOTAL_TOKENS_IS_WIDTH = False
+
+    def get_embeddings(self, texts: List[str], truncation: bool = None, max_length: int = None) -> EmbeddingsObject:
+        """one embedding per text, fp32 (n, dim), as the reference's ``encode``.  ``max_length`` is not used: the limit is
+        ``max_tokens``"""
+        result = EmbeddingsObject()
+        result.embeddings = self.embed_texts(texts, truncation=bool(truncation))
+        result.total_tokens = len(result.embeddings[0]) if self.TOTAL_TOKENS_IS_WIDTH and len(result.embeddings) else -1
+        return result
+
+
+class SentenceTransformerEmbeddings(BertTextEmbeddings):
+    """marie/embeddings/sentence_transformers/sentence_transformers_embeddings.py (``SentenceTransformer``,
+    sentence-transformers/all-MiniLM-L6-v2: mean pooling, Normalize, 256 tokens).  ``total_tokens`` is the embedding width,
+    the reference's ``len(embeddings[0])``.  ``SentenceTransformer.encode`` always truncates to ``max_seq_length``; here a text
+    past ``max_tokens`` raises unless ``truncation=True``."""
+
+    POOLING, NORMALIZE, MAX_LENGTH = "mean", True, 256
+    TOTAL_TOKENS_IS_WIDTH = True
+
+
+class JinaEmbeddings(BertTextEmbeddings):
+    """marie/embeddings/jina/jina_embeddings.py (``AutoModel(...).encode``, jinaai/jina-embeddings-v2-base-en: mean pooling, no
+    normalisation).  ``total_tokens`` is -1, as there."""
+
+    POOLING, NORMALIZE, MAX_LENGTH = "mean", False, None

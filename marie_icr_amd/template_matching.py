@@ -26,8 +26,9 @@ scores each by Levenshtein similarity; n-grams at 0.5 or more also take the cosi
 embeddings, and the three are averaged.  The reference scores one pair at a time in Python; here the page is laid out once as
 one string of alphabet ids (``text_layout``), the edit distance of every (template, n-gram) pair comes from one call of
 ``csrc/lev_ngrams.hip``, and what passes the 0.5 filter goes through the device resize, ``embed_clips`` / ``embed_texts`` and
-``pair_cosines`` in batches.  Text embeddings are the CLIP text tower's (or an injected callable's): the reference's
-jina-embeddings-v2-base-en is remote code and weights that are not here.  The distance is the unit-cost edit distance over
+``pair_cosines`` in batches.  Text embeddings are those of ``text_embeddings_processor`` — ``JinaEmbeddings`` (the reference's
+jina-embeddings-v2-base-en) or ``SentenceTransformerEmbeddings`` of embeddings.py, or a callable — or, without one, the CLIP
+text tower's.  The distance is the unit-cost edit distance over
 code points, exact against the textbook DP; its parity with the ``Levenshtein`` package is not pinned.
 """
 from __future__ import annotations
