@@ -568,6 +568,51 @@ int mhip_cross_attention_host(mhip_ctx* ctx, const float* q, const float* enc, c
 int mhip_decode_attention_host(mhip_ctx* ctx, int precision, int heads, int n_keys, int nq, int rows, int slots, int kv_rows,
                                const float* q, const float* k, const float* v, const int32_t* anc, int anc_ld,
                                int force_generic, float* out);
+/* The per-step beam search of the decoder alone, on host inputs, through the launchers trocr_decode drives.  replaces:
+ * BeamSearch.step, finalize_hypos and the row selection of TextRecognitionGenerator._generate,
+ * marie/models/unilm/trocr/generator.py:165-372.
+ *
+ * mhip_beam_candidates_host: one launch of the candidates kernel.  logits [bsz*beam][ld] in the element type the flag names
+ * (fp32, or IEEE half when logits_f16), columns vocab .. ld-1 are row padding and may hold anything; cum [bsz*beam].
+ * -> cand_scores / cand_tokens / cand_beams [bsz * 2 * beam + 16]: the device buffers carry 16 guard elements behind the lists,
+ * are filled with 0xff bytes before the launch and come back whole.  Refused without writing output: what the launcher refuses
+ * (beam outside 1 .. 4, vocab < 2 * beam, a pitch that is no multiple of 8 or shorter than the vocabulary rounded up to 8),
+ * min_len > max_len, bsz < 1, a null pointer.                                                                              */
+int mhip_beam_candidates_host(mhip_ctx* ctx, int logits_f16, const void* logits, const float* cum, int step, int max_len,
+                              int min_len, int pad, int eos, int vocab, int ld, int beam, int bsz, float* cand_scores,
+                              int32_t* cand_tokens, int32_t* cand_beams);
+/* What mhip_beam_search_host copies out.  S = max_len + 1 rows per step (the steps that ran are filled), M = bsz * beam.    */
+typedef struct mhip_beam_trace {
+  float* cand_scores;     /* [S][bsz][2*beam] the step's candidate lists as beam_select read them                          */
+  int32_t* cand_tokens;
+  int32_t* cand_beams;
+  int32_t* parent;        /* [S][M] after the step's beam_select                                                            */
+  int32_t* last_tok;      /* [S][M]                                                                                         */
+  float* cum;             /* [S][M]                                                                                         */
+  uint8_t* ignore;        /* [S][M]                                                                                         */
+  uint8_t* finished;      /* [S][bsz]                                                                                       */
+  int32_t* fin_count;     /* [S][bsz]                                                                                       */
+  int32_t* tokens;        /* [S][M][max_len + 2] the token buffer the step wrote                                            */
+  int32_t* anc;           /* [S][M][max_len + 2] the ancestry table the step's decoder would read (0xff where never written) */
+  int32_t* remaining;     /* [S]                                                                                            */
+  int32_t* fin_tokens;    /* [bsz][beam][max_len + 1], at the end; cells never written hold 0xff bytes                      */
+  int32_t* fin_len;       /* [M]                                                                                            */
+  float* fin_score;       /* [M]                                                                                            */
+  int32_t* out_tokens;    /* [bsz][max_len + 1] beam_best                                                                   */
+  int32_t* out_len;       /* [bsz]                                                                                          */
+  float* out_score;       /* [bsz]                                                                                          */
+  int32_t steps;          /* steps that ran, the extra ones included                                                        */
+} mhip_beam_trace;
+/* mhip_beam_search_host: trocr_decode's launch sequence with the decoder taken out — beam_init; per step ancestry (step > 0),
+ * the step's candidates, beam_select; beam_best at the end — on a state carved from the context workspace.  The candidates of
+ * step s come from the candidates kernel on logits[s] (logits [max_len + 1][bsz*beam][ld], element type as above), or, with
+ * logits == NULL, from the caller's lists in_scores / in_tokens / in_beams [max_len + 1][bsz][2*beam], uploaded in place of that
+ * launch.  Steps run until no crop remains or step max_len has run; then `extra_steps` (0 .. 2) more, never past step max_len.
+ * trocr_decode, which reads the counter two steps late, enqueues exactly one step past the end; 2 is a margin for a caller that
+ * reads it later still.  Refusals as above, checked before anything is written.                                            */
+int mhip_beam_search_host(mhip_ctx* ctx, int logits_f16, const void* logits, const float* in_scores, const int32_t* in_tokens,
+                          const int32_t* in_beams, int max_len, int min_len, int pad, int eos, int vocab, int ld, int beam,
+                          int bsz, int extra_steps, mhip_beam_trace* out);
 
 /* ---- LayoutLMv3 page classifier (OCR words + boxes + page image -> class logits) ------------------------------------------ */
 /* replaces: the model path of TransformersDocumentClassifier with task="text-classification-multimodal",

@@ -131,6 +131,8 @@ _SIGNATURES = (
     ("mhip_trocr_generate_trace_host", _i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i)]),
     ("mhip_cross_attention_host", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     ("mhip_decode_attention_host", _i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    ("mhip_beam_candidates_host", _i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    ("mhip_beam_search_host", _i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     ("mhip_gemm_ln_fold", _i, [_vp, _i, _vp]),
     ("mhip_ln_finalize", _i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, C.c_float]),
     ("mhip_token_init_split", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
@@ -283,6 +285,13 @@ class TrocrConfig(C.Structure):
                 ("dec_layers", C.c_int), ("dec_heads", C.c_int), ("dec_ffn", C.c_int), ("vocab", C.c_int),
                 ("max_positions", C.c_int), ("beam", C.c_int), ("max_len_b", C.c_int), ("min_len", C.c_int),
                 ("pad", C.c_int), ("eos", C.c_int), ("embed_scale", C.c_float), ("img_size", C.c_int)]
+
+
+class BeamTrace(C.Structure):
+    """mirror of mhip_beam_trace (include/marie_hip.h); the pointers are host arrays"""
+    _fields_ = ([(n, C.c_void_p) for n in ("cand_scores", "cand_tokens", "cand_beams", "parent", "last_tok", "cum", "ignore",
+                                           "finished", "fin_count", "tokens", "anc", "remaining", "fin_tokens", "fin_len",
+                                           "fin_score", "out_tokens", "out_len", "out_score")] + [("steps", C.c_int32)])
 
 
 class LayoutLMv3Config(C.Structure):

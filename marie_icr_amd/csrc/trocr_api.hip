@@ -85,6 +85,10 @@ extern "C" int mhip_trocr_create(mhip_ctx* ctx, int precision, const mhip_trocr_
   if (trocr_max_len(c) + 1 > DEC_ATTN_MAX_KEYS)
     return mhip_fail(ctx, MHIP_EINVAL, "trocr: max_len %d needs %d keys of self-attention history, decode attention runs at most %d",
                      trocr_max_len(c), trocr_max_len(c) + 1, DEC_ATTN_MAX_KEYS);
+  // the generator's own assertion (generator.py:63): with min_len above it, eos is still masked at the forced last step and every
+  // line would come back empty with score -inf
+  if (c.min_len > trocr_max_len(c))
+    return mhip_fail(ctx, MHIP_EINVAL, "trocr: min_len %d exceeds max_len %d (min of max_len_b and max_positions - 1)", c.min_len, trocr_max_len(c));
   mhip_vit_config vc{};
   vc.dim = c.enc_dim; vc.depth = c.enc_depth; vc.heads = c.enc_heads; vc.patch = 16;
   vc.pos_h = vc.pos_w = c.img_size / 16;

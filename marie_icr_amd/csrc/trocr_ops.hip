@@ -387,7 +387,15 @@ __global__ __launch_bounds__(CAND_T) void beam_candidates_kernel(CandArgs p) {
         f[e] = (c * EPC + e < p.vocab) ? (float)v[e] : -INFINITY;      // columns past the vocabulary are row padding
         cm = fmaxf(cm, f[e]);
       }
-      if (cm == -INFINITY) continue;       // a chunk of -inf logits adds nothing; (-inf) - (-inf) below would be NaN
+      if (cm == -INFINITY) {               // a chunk of -inf logits adds nothing; (-inf) - (-inf) below would be NaN
+        // ... unless a NaN hides among them (fmaxf drops it): log_softmax of a row with a NaN is NaN throughout, and m = +inf with a
+        // NaN sum carries that through every merge
+        bool nan = false;
+#pragma unroll
+        for (int e = 0; e < EPC; ++e) nan = nan || f[e] != f[e];
+        if (nan) { m = INFINITY; sum = NAN; }
+        continue;
+      }
       if (cm > m) { sum *= __builtin_amdgcn_exp2f((m - cm) * L2E); m = cm; }     // m = -inf: exp2(-inf) = 0, sum stays 0
 #pragma unroll
       for (int e = 0; e < EPC; ++e) sum += __builtin_amdgcn_exp2f((f[e] - m) * L2E);

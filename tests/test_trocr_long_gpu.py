@@ -209,3 +209,15 @@ def test_create_rejects_a_history_longer_than_decode_attention_runs(ctx):
     m = TrocrModel(ctx, None, cfg, PREC_F16)
     assert m.max_len == 639
     m.close()
+    # min_len above max_len = min(max_len_b, max_positions - 1): the generator asserts it (generator.py:63); accepted, eos would stay
+    # masked at the forced last step and every line come back empty with score -inf
+    for max_positions, max_len_b, min_len in ((512, 200, 201), (100, 200, 100)):
+        cfg = default_config(ctx.lib, "base")
+        cfg.max_positions, cfg.max_len_b, cfg.min_len = max_positions, max_len_b, min_len
+        with pytest.raises(MarieHipError, match="min_len"):
+            TrocrModel(ctx, None, cfg, PREC_F16)
+    cfg = default_config(ctx.lib, "base")                 # min_len == max_len is the forced case of this module: accepted
+    cfg.max_positions, cfg.max_len_b, cfg.min_len = 100, 200, 99
+    m = TrocrModel(ctx, None, cfg, PREC_F16)
+    assert m.max_len == 99
+    m.close()
