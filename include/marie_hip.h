@@ -938,6 +938,60 @@ int mhip_berttext_geglu_host(mhip_ctx* ctx, int precision, const float* x, int R
 int mhip_berttext_pool_host(mhip_ctx* ctx, const float* h, const int32_t* len, int B, int npad, int D, int mode, int normalize,
                             float* emb_out);
 
+/* ---- LayoutReader reading order (csrc/layoutreader_api.hip, layoutreader_ops.hip) ---------------------------------------- */
+/* replaces: LayoutlmForSeq2SeqDecoder.forward (greedy: search_beam_size 1, pos_shift off) with layoutlm_only_layout_flag behind
+ * TextLayout.forward (marie/document/layoutreader/text_layout.py; model in marie/models/unilm/layoutreader/s2s_ft/
+ * modeling_decoding.py, rows laid out by Preprocess4Seq2seqDecoder).  S = max_source source rows ([CLS] at box 0, the n <= S - 2
+ * words, [SEP] at box 1000, pads), then T = S - 2 greedy pointer steps; always all T.  A page's decisions and scores do not
+ * depend on the other pages of the call, bit for bit.                                                                        */
+typedef struct mhip_layoutreader mhip_layoutreader;
+typedef struct mhip_layoutreader_config {
+  int dim;                 /* 768; a multiple of 64 up to 1024                                                            */
+  int heads;               /* 12; dim / heads must be 64                                                                  */
+  int depth;               /* 12                                                                                          */
+  int ffn;                 /* 3072; a multiple of 64                                                                      */
+  int max_position;        /* 1024: rows of the position table, >= 2 S - 2                                                */
+  int max_2d;              /* 1024: rows of the x / y / h / w tables, > 1000                                              */
+  int max_source;          /* S = 513: source rows, and entries of cls.predictions.bias; 2 S - 1 <= 1032                  */
+  int type_vocab;          /* 2                                                                                           */
+  int source_type;         /* 0                                                                                           */
+  int target_type;         /* 1                                                                                           */
+  float ln_eps;            /* 1e-5, TF style (inside the root)                                                            */
+} mhip_layoutreader_config;
+/* MHIP_EINVAL with a message that names the field (a head dim other than 64 among them)                                     */
+int mhip_layoutreader_create(mhip_ctx* ctx, int precision, const mhip_layoutreader_config* cfg, mhip_layoutreader** out);
+int mhip_layoutreader_destroy(mhip_layoutreader* m);
+/* keys of the checkpoint (an optional "bert." prefix is stripped), LayerNorms as weight / bias: embeddings.{position,x_position,
+ * y_position,h_position,w_position,token_type}_embeddings.weight, embeddings.LayerNorm.*, encoder.layer.N.* as BERT's,
+ * cls.predictions.bias [S], cls.predictions.transform.{dense,LayerNorm}.*.  pooler.*, cls.seq_relationship.*,
+ * embeddings.word_embeddings.weight and every attention.self.key.bias are ignored (the model never reads them); any other key is
+ * MHIP_EINVAL.  finalize names the first missing or misshapen tensor                                                         */
+int mhip_layoutreader_set_tensor(mhip_layoutreader* m, const char* key, const float* data, const int64_t* shape, int ndim);
+int mhip_layoutreader_finalize(mhip_layoutreader* m);
+int mhip_layoutreader_alloc_arena(mhip_layoutreader* m);
+int mhip_layoutreader_arena(mhip_layoutreader* m, void** arena_dev, size_t* bytes);
+/* bytes of context workspace one mhip_layoutreader_order_host call of `pages` pages (1 .. 64) lays out, the key / value caches
+ * [depth][pages][S + T][dim] among them (0: bad arguments); debug_host lays out the score rows and the forced indices on top */
+size_t mhip_layoutreader_workspace_bytes(mhip_layoutreader* m, int pages);
+/* boxes int32 [pages][S - 2][4] (x0, y0, x1, y1 in 0 .. 1000; rows >= counts[page] are not read), counts int32 [pages] ->
+ * decisions int32 [pages][T]: the arg-max of every step (lowest index on ties), an index into the S source rows (the caller
+ * subtracts 1 for word indices).  MHIP_EINVAL, never a clamp: a count outside 0 .. S - 2, a coordinate outside 0 .. 1000,
+ * x1 < x0 or y1 < y0                                                                                                         */
+int mhip_layoutreader_order_host(mhip_layoutreader* m, const int32_t* boxes, const int32_t* counts, int pages, int32_t* decisions);
+/* as order_host, plus (each may be NULL) scores_out fp32 [pages][T][S]: every step's score row; emb_out fp32 [pages][S][dim]: the
+ * embedded source rows the pointer head scores against; last_out fp32 [pages][S][dim]: the last layer's output of the source pass
+ * (rows past a page's [SEP] are zeros: they are not computed).  forced int32 [pages][T] (0 .. S - 1) or NULL: step t + 1 is fed
+ * source row forced[page][t] instead of decision t; decisions and scores still report the kernel's own arg-max                */
+int mhip_layoutreader_debug_host(mhip_layoutreader* m, const int32_t* boxes, const int32_t* counts, int pages, const int32_t* forced,
+                                 int32_t* decisions, float* scores_out, float* emb_out, float* last_out);
+/* The decode attention alone on host arrays (parity tests), heads of 64: q, k, v fp32 [pages][nq][heads * 64] the nq (1 or 2)
+ * rows a step feeds per page, q already scaled by 1/8 * log2(e); kc, vc fp32 [pages][cache_rows][heads * 64] the caches; all
+ * rounded to the precision's element type.  Query row i of a page sees cache rows [0, src_len[page]), cache rows tgt_base +
+ * [0, tgt_len[page * nq + i]) and rows 0 .. i of the page's k / v: at most 1032 keys.  -> out fp32 [pages][nq][heads * 64]    */
+int mhip_layoutreader_attention_host(mhip_ctx* ctx, int precision, const float* q, const float* k, const float* v, const float* kc,
+                                     const float* vc, const int32_t* src_len, const int32_t* tgt_len, int pages, int nq, int heads,
+                                     int cache_rows, int tgt_base, float* out);
+
 /* ---- word-box / line geometry of the DiT box processor (host, pure functions; no ctx) --------------------------------- */
 /* replaces: merge_boxes, marie/utils/overlap.py:268-330 (find_overlap_horizontal(center_y_overlap=0.5) :106-183,
  * merge_bboxes_as_block :186-204).  xyxy fp32 [n][4] -> out_xyxy fp32 (capacity n rows), *n_out rows.       */

@@ -206,6 +206,16 @@ _SIGNATURES = (
     ("mhip_berttext_attention_host", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     ("mhip_berttext_geglu_host", _i, [_vp, _i, _vp, _i, _i, _vp]),
     ("mhip_berttext_pool_host", _i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    ("mhip_layoutreader_create", _i, [_vp, _i, _vp, C.POINTER(_vp)]),
+    ("mhip_layoutreader_destroy", _i, [_vp]),
+    ("mhip_layoutreader_set_tensor", _i, [_vp, C.c_char_p, _vp, C.POINTER(C.c_int64), _i]),
+    ("mhip_layoutreader_finalize", _i, [_vp]),
+    ("mhip_layoutreader_alloc_arena", _i, [_vp]),
+    ("mhip_layoutreader_arena", _i, [_vp, C.POINTER(_vp), C.POINTER(_sz)]),
+    ("mhip_layoutreader_workspace_bytes", _sz, [_vp, _i]),
+    ("mhip_layoutreader_order_host", _i, [_vp, _vp, _vp, _i, _vp]),
+    ("mhip_layoutreader_debug_host", _i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    ("mhip_layoutreader_attention_host", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     ("mhip_max_page_size", _i, [_i, _i, _i, _i, C.c_double, C.POINTER(_i), C.POINTER(_i)]),
     ("mhip_resize_area_u8", _i, [_vp, _vp, _i, _i, _i, C.c_size_t, _vp, _i, _i]),
     ("mhip_resize_area_u8_host", _i, [_vp, _vp, _i, _i, _i, _vp, _i, _i]),
@@ -321,6 +331,13 @@ class BertTextConfig(C.Structure):
     _fields_ = [("vocab", C.c_int), ("max_position", C.c_int), ("type_vocab", C.c_int), ("dim", C.c_int), ("heads", C.c_int),
                 ("depth", C.c_int), ("ffn", C.c_int), ("ln_eps", C.c_float), ("position", C.c_int), ("mlp", C.c_int),
                 ("pool", C.c_int), ("normalize", C.c_int)]
+
+
+class LayoutReaderConfig(C.Structure):
+    """mirror of mhip_layoutreader_config (include/marie_hip.h)"""
+    _fields_ = [("dim", C.c_int), ("heads", C.c_int), ("depth", C.c_int), ("ffn", C.c_int), ("max_position", C.c_int),
+                ("max_2d", C.c_int), ("max_source", C.c_int), ("type_vocab", C.c_int), ("source_type", C.c_int),
+                ("target_type", C.c_int), ("ln_eps", C.c_float)]
 
 
 class VqFilters(C.Structure):

@@ -24,7 +24,8 @@ enum MhipKernelId {
   MHIP_K_ATTN_FLASH = 8,  // ViT softmax attention: S^T = K Q^T -> online softmax -> O^T = V^T P^T on MFMA
   MHIP_K_VIT_OPS = 9,     // LayerNorm, patch extraction, token/map moves (HBM-bound)
   MHIP_K_DET_OPS = 10,    // detector heads: anchors/decode, top-k, NMS, ROIAlign
-  MHIP_K_DEC_OPS = 11,    // text decoder steps: embedding, single-query attention over caches, beam candidates
+  MHIP_K_DEC_OPS = 11,    // text decoder steps: embedding, single-query attention over caches, beam candidates; also the
+                          // LayoutReader kernels (layoutreader_ops.hip): lr_embed, lr_decode_attn, lr_pointer_scores, lr_pointer_select
   // conv_igemm by tile shape: their launches are ALSO counted in MHIP_K_CONV_IGEMM (ProfSlot::parent), so that the fraction of
   // the MFMA peak can be recomputed per variant from a profile (names as the kernels appear in a rocprofv3 trace)
   MHIP_K_IGEMM_T64 = 12,    // conv_igemm_kernel<.., 64, ..>   512 x 64 tile
@@ -53,6 +54,7 @@ enum MhipKernelId {
   // BERT sentence encoders (berttext_ops.hip)
   MHIP_K_ATTN_SHORT = 32,        // bidirectional soft-max attention over sequences of their own length (<= 128), optional ALiBi, head dim 64 / 32
   MHIP_K_BERTTEXT_EMBED = 33,    // word + type + position rows -> LayerNorm -> fp32 stream; the post-LayerNorms of the layers
+                                 // (LayoutReader's row LayerNorms go through mhip_launch_berttext_layernorm and are counted here)
   MHIP_K_GEGLU = 34,             // gelu(x[:, :F]) * x[:, F:]
   MHIP_K_BERTTEXT_POOL = 35,     // masked mean / cls pooling, optional L2 normalisation
   MHIP_K_COUNT = 36
@@ -622,6 +624,45 @@ int mhip_launch_berttext_layernorm(mhip_ctx* ctx, int precision, const float* x,
 int mhip_launch_geglu(mhip_ctx* ctx, int precision, const void* x, void* out, long long R, int F);
 // emb [B][D] fp32: the mean of rows < len[b] of h [B][npad][D] (cls: row 0; len may be null), divided by max(norm, 1e-12) with normalize
 int mhip_launch_berttext_pool(mhip_ctx* ctx, const float* h, const int* len, int B, int npad, int D, int cls, int normalize, float* emb);
+// ------------------------------------------------------------------ LayoutReader ops (layoutreader_ops.hip)
+// A row of the layout-only embedding is 8 ints in HBM: x0, y0, x1, y1, position id, type id, two spare.
+constexpr int LR_TOK_INTS = 8;
+// h [rows][D] fp32 = LN(pos[p] + x[x0] + y[y0] + x[x1] + y[y1] + h[y1 - y0] + w[x1 - x0] + type[t]), ht (null: not written) its
+// copy in the precision's element type; the tables are fp32 [..][D], an index outside its table is clamped into it
+struct LrEmbedDesc {
+  const int* tok = nullptr;          // [rows][LR_TOK_INTS], device
+  const float *pos = nullptr, *xe = nullptr, *ye = nullptr, *he = nullptr, *we = nullptr, *type = nullptr;
+  const float *g = nullptr, *b = nullptr;
+  float* h = nullptr;
+  void* ht = nullptr;
+  int rows = 0, D = 0, max_position = 0, max_2d = 0, type_vocab = 0;
+  float eps = 1e-5f;
+};
+int mhip_launch_lr_embed(mhip_ctx* ctx, int precision, const LrEmbedDesc& d);
+// Attention of the nq (1 or 2) rows a decode step feeds per page over that page's caches, head dim 64, q scaled by
+// head_dim^-0.5 * log2(e).  Query row i of a page sees cache rows [0, src_len[page]), cache rows tgt_base + [0, tgt_len[page * nq
+// + i]) and the step's own rows 0 .. i of the page (k / v below): at most LR_ATTN_MAX_KEYS keys.  keep: the own rows 0 .. nq - 2
+// are written to the cache rows tgt_base + max(tgt_len of the page) + row (the caller keeps them inside cache_rows).  Rows of the
+// caches beyond these lengths are not read.
+constexpr int LR_ATTN_MAX_KEYS = 1032;
+struct LrDecAttnDesc {
+  const void *q = nullptr, *k = nullptr, *v = nullptr;   // [pages * nq][ld] T, head h at column h * 64
+  void *kc = nullptr, *vc = nullptr;                     // [pages][cache_rows][heads * 64] T
+  void* out = nullptr;                                   // [pages * nq][ldo] T
+  const int* src_len = nullptr;                          // [pages], device
+  const int* tgt_len = nullptr;                          // [pages * nq], device
+  int ld = 0, ldo = 0, pages = 0, heads = 0, nq = 1, cache_rows = 0, tgt_base = 0, keep = 0;
+};
+int mhip_launch_lr_decode_attention(mhip_ctx* ctx, int precision, const LrDecAttnDesc& d);
+// sc[page * sc_stride + j] = LN(x[page * nq + nq - 1]) . E[page][j] + bias[j] for j < S; x [pages * nq][D], E [pages][e_rows][D] fp32
+int mhip_launch_lr_pointer_scores(mhip_ctx* ctx, const float* x, int nq, const float* g, const float* b, float eps, const float* E,
+                                  int e_rows, const float* bias, int S, int D, int pages, float* sc, long long sc_stride);
+// decisions[page][t] = arg-max of sc[page] (lowest index on ties); next_tok [pages][2][LR_TOK_INTS] = the rows of step t + 1: the box
+// of source row forced[page][t] (forced null: the decision) of src_tok [pages][e_rows][LR_TOK_INTS] at position src_len[page] + t, and
+// the mask row (box 0) at the position after it, both of type tgt_type
+int mhip_launch_lr_pointer_select(mhip_ctx* ctx, const float* sc, long long sc_stride, int S, const int* forced, int t, int T,
+                                  const int* src_tok, int e_rows, const int* src_len, int tgt_type, int pages, int* decisions,
+                                  int* next_tok);
 size_t mhip_pil_resize_fragments_scratch(const mhip_crop_desc* descs, int n, int dh, int dw, int filter);
 int mhip_pil_resize_fragments(mhip_ctx* ctx, const uint8_t* base_dev, const mhip_crop_desc* descs, int n, uint8_t* dst, int dh,
                               int dw, int filter, void* scratch, size_t scratch_bytes);
