@@ -557,6 +557,16 @@ int mhip_trocr_generate_trace_host(mhip_trocr* m, const uint8_t* crops_host, int
  * (projected, scaled), enc [crops][n_tok][enc_dim], wk / wv [heads*64][enc_dim], bv [heads*64] -> out [crops*beam][heads*64]. */
 int mhip_cross_attention_host(mhip_ctx* ctx, const float* q, const float* enc, const float* wk, const float* wv,
                               const float* bv, int crops, int beam, int heads, int n_tok, int enc_dim, float* out);
+/* The same call with each of its three kernels (absorb_q, cross_attn, absorb_v) observable, for the kernel-level tests.  enc is
+ * [crops][kv_rows][enc_dim] with kv_rows >= n_tok and kv_rows % 8 == 0: rows n_tok .. kv_rows - 1 of a crop are the caller's
+ * padding (finite values; the kernel reads them masked), the zero slack rows behind the last crop are appended by the call.
+ * The absorbed-query and context scratch and the output are filled with the f16 NaN pattern 0xffff before the launch and
+ * copied out as fp32: qt_out / ct_out [crops*beam][16][enc_dim] (either may be NULL), out [crops*beam][heads*64].  Refused
+ * without a launch: enc_dim outside {256, 512, 768, 1024}, beam outside 1 .. 4, heads outside 1 .. 16, kv_rows < n_tok,
+ * kv_rows % 8, n_tok < 1, crops < 1, a null operand.                                                                       */
+int mhip_cross_attention_stages_host(mhip_ctx* ctx, const float* q, const float* enc, const float* wk, const float* wv,
+                                     const float* bv, int crops, int beam, int heads, int n_tok, int kv_rows, int enc_dim,
+                                     float* qt_out, float* ct_out, float* out);
 /* The decoder's decode attention alone (one layer, one step) on host inputs, through the kernels trocr_decode launches: the
  * self-attention over a hypothesis' history and the encoder-attention over projected keys / values (fp32, and f16 without the
  * absorbed path).  replaces: fairseq MultiheadAttention (self_attn with incremental state / encoder_attn) as

@@ -130,6 +130,7 @@ _SIGNATURES = (
     ("mhip_trocr_decode", _i, [_vp, _vp, _vp, _vp]),
     ("mhip_trocr_generate_trace_host", _i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i)]),
     ("mhip_cross_attention_host", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    ("mhip_cross_attention_stages_host", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     ("mhip_decode_attention_host", _i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     ("mhip_beam_candidates_host", _i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     ("mhip_beam_search_host", _i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),

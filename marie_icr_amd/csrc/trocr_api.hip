@@ -616,18 +616,28 @@ extern "C" int mhip_trocr_decode(mhip_trocr* m, int32_t* tokens_out, int32_t* le
 // The decoder's encoder-attention stage on caller-supplied host inputs, through the absorbed kernels (f16 operands): what the
 // parity tests compare with fairseq's MultiheadAttention (q already projected and scaled).  q [crops*beam][heads*64],
 // enc [crops][n_tok][enc_dim], wk / wv [heads*64][enc_dim], bv [heads*64] -> out [crops*beam][heads*64], all fp32.
-extern "C" int mhip_cross_attention_host(mhip_ctx* ctx, const float* q, const float* enc, const float* wk, const float* wv,
-                                         const float* bv, int crops, int beam, int heads, int n_tok, int enc_dim, float* out) {
-  if (!ctx || !q || !enc || !wk || !wv || !bv || !out || crops < 1 || n_tok < 1) return MHIP_EINVAL;
-  if (!mhip_cross_absorb_supported(enc_dim, beam, heads)) return mhip_fail(ctx, MHIP_EINVAL, "cross_attention: unsupported shape");
+//
+// mhip_cross_attention_stages_host is the same call with the crop pitch in the caller's hands (enc [crops][kv_rows][enc_dim],
+// kv_rows >= n_tok, a multiple of 8: rows n_tok .. kv_rows - 1 of a crop are the caller's padding and must be finite) and with
+// what each of the three kernels left on the device copied out: qt_out / ct_out [crops*beam][16][enc_dim] (either may be
+// NULL).  The qt / ct scratch and the output are filled with 0xffff (an f16 NaN) before the launch, so whatever a kernel did not
+// write comes back as NaN.  The CROSS_ATTN_SLACK_ROWS zero rows behind the last crop are appended here.
+extern "C" int mhip_cross_attention_stages_host(mhip_ctx* ctx, const float* q, const float* enc, const float* wk, const float* wv,
+                                                const float* bv, int crops, int beam, int heads, int n_tok, int kv_rows,
+                                                int enc_dim, float* qt_out, float* ct_out, float* out) {
+  if (!ctx) return MHIP_EINVAL;
+  if (!q || !enc || !wk || !wv || !bv || !out) return mhip_fail(ctx, MHIP_EINVAL, "cross_attention: null operand");
+  if (crops < 1 || n_tok < 1 || kv_rows < n_tok || kv_rows % 8)
+    return mhip_fail(ctx, MHIP_EINVAL, "cross_attention: crops %d, n_tok %d, kv_rows %d (kv_rows >= n_tok >= 1, kv_rows %% 8 == 0)",
+                     crops, n_tok, kv_rows);
+  if (!mhip_cross_absorb_supported(enc_dim, beam, heads))
+    return mhip_fail(ctx, MHIP_EINVAL, "cross_attention: unsupported shape (enc_dim %d, beam %d, heads %d)", enc_dim, beam, heads);
   MHIP_HIP(ctx, hipSetDevice(ctx->device));
-  const int D = heads * 64, M = crops * beam, npad = (n_tok + 7) / 8 * 8;
-  const size_t rowsE = (size_t)crops * npad + CROSS_ATTN_SLACK_ROWS;
+  const int D = heads * 64, M = crops * beam;
+  const size_t rowsIn = (size_t)crops * kv_rows, rowsE = rowsIn + CROSS_ATTN_SLACK_ROWS;
   std::vector<_Float16> hq((size_t)M * D), hE(rowsE * enc_dim, (_Float16)0.f), hkt((size_t)D * enc_dim), hwv((size_t)D * enc_dim);
   for (size_t i = 0; i < hq.size(); ++i) hq[i] = (_Float16)q[i];
-  for (int c = 0; c < crops; ++c)
-    for (int s = 0; s < n_tok; ++s)
-      for (int d = 0; d < enc_dim; ++d) hE[((size_t)c * npad + s) * enc_dim + d] = (_Float16)enc[((size_t)c * n_tok + s) * enc_dim + d];
+  for (size_t i = 0; i < rowsIn * enc_dim; ++i) hE[i] = (_Float16)enc[i];
   pack_ca_kt(wk, heads, enc_dim, hkt.data());
   for (size_t i = 0; i < hwv.size(); ++i) hwv[i] = (_Float16)wv[i];
   const size_t scr = (size_t)M * 16 * enc_dim * 2;
@@ -644,16 +654,36 @@ extern "C" int mhip_cross_attention_host(mhip_ctx* ctx, const float* q, const fl
   MHIP_HIP(ctx, hipMemcpyAsync(dkt, hkt.data(), hkt.size() * 2, hipMemcpyHostToDevice, ctx->stream));
   MHIP_HIP(ctx, hipMemcpyAsync(dwv, hwv.data(), hwv.size() * 2, hipMemcpyHostToDevice, ctx->stream));
   MHIP_HIP(ctx, hipMemcpyAsync(dbv, bv, (size_t)D * 4, hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemsetAsync(qt, 0xff, scr, ctx->stream));
+  MHIP_HIP(ctx, hipMemsetAsync(ct, 0xff, scr, ctx->stream));
+  MHIP_HIP(ctx, hipMemsetAsync(ao, 0xff, (size_t)M * D * 2, ctx->stream));
   CrossAbsorbDesc cd;
-  cd.q = dq; cd.ldq = D; cd.E = dE; cd.kv_rows = npad; cd.n_keys = n_tok; cd.enc_dim = enc_dim;
+  cd.q = dq; cd.ldq = D; cd.E = dE; cd.kv_rows = kv_rows; cd.n_keys = n_tok; cd.enc_dim = enc_dim;
   cd.wkt = dkt; cd.wv = dwv; cd.bv = dbv; cd.qt = qt; cd.ct = ct; cd.ao = ao; cd.ldo = D;
   cd.crops = crops; cd.beam = beam; cd.heads = heads;
   if ((rc = mhip_launch_cross_absorbed(ctx, cd))) return rc;
-  std::vector<_Float16> ho((size_t)M * D);
+  std::vector<_Float16> ho((size_t)M * D), hqt(qt_out ? scr / 2 : 0), hct(ct_out ? scr / 2 : 0);
   MHIP_HIP(ctx, hipMemcpyAsync(ho.data(), ao, ho.size() * 2, hipMemcpyDeviceToHost, ctx->stream));
+  if (qt_out) MHIP_HIP(ctx, hipMemcpyAsync(hqt.data(), qt, scr, hipMemcpyDeviceToHost, ctx->stream));
+  if (ct_out) MHIP_HIP(ctx, hipMemcpyAsync(hct.data(), ct, scr, hipMemcpyDeviceToHost, ctx->stream));
   MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
   for (size_t i = 0; i < ho.size(); ++i) out[i] = (float)ho[i];
+  for (size_t i = 0; i < hqt.size(); ++i) qt_out[i] = (float)hqt[i];
+  for (size_t i = 0; i < hct.size(); ++i) ct_out[i] = (float)hct[i];
   return MHIP_OK;
+}
+
+extern "C" int mhip_cross_attention_host(mhip_ctx* ctx, const float* q, const float* enc, const float* wk, const float* wv,
+                                         const float* bv, int crops, int beam, int heads, int n_tok, int enc_dim, float* out) {
+  if (!ctx || !q || !enc || !wk || !wv || !bv || !out || crops < 1 || n_tok < 1) return MHIP_EINVAL;
+  if (!mhip_cross_absorb_supported(enc_dim, beam, heads)) return mhip_fail(ctx, MHIP_EINVAL, "cross_attention: unsupported shape");
+  // the crops at the production pitch (npad rows, zeros behind the tokens)
+  const int npad = (n_tok + 7) / 8 * 8;
+  std::vector<float> padded((size_t)crops * npad * enc_dim, 0.f);
+  for (int c = 0; c < crops; ++c)
+    std::copy(enc + (size_t)c * n_tok * enc_dim, enc + (size_t)(c + 1) * n_tok * enc_dim, padded.begin() + (size_t)c * npad * enc_dim);
+  return mhip_cross_attention_stages_host(ctx, q, padded.data(), wk, wv, bv, crops, beam, heads, n_tok, npad, enc_dim, nullptr,
+                                          nullptr, out);
 }
 
 // The decoder's decode attention on caller-supplied host inputs, through mhip_launch_decode_attention as trocr_decode drives it
