@@ -829,6 +829,62 @@ int mhip_clipvis_head_host(mhip_ctx* ctx, const float* h, int B, int npad, int D
 int mhip_clipvis_pair_cosine_host(mhip_ctx* ctx, const float* emb, int n, int E, const int32_t* pair_a, const int32_t* pair_b,
                                   int n_pairs, float* cos_out);
 
+/* ---- CLIP ModifiedResNet tower: the snippet embeddings of RN50 / RN101 / RN50x4 (csrc/cliprn_api.hip, cliprn_ops.hip) ------ */
+/* replaces: CLIP.encode_image behind OpenAIEmbeddings.get_single_image_embedding (marie/embeddings/openai/openai_embeddings.py:
+ * 146-157) for the ModifiedResNet checkpoints (clip/model.py: ModifiedResNet, Bottleneck, AttentionPool2d) — the model
+ * VQNNFTemplateMatcher and MetaTemplateMatcher build by default, marie/clip-snippet-rn50x4.
+ * Clips are uint8 [image_size][image_size][3], already resized and cropped; normalisation with CLIP's constants is part of the
+ * stem kernel.  Stem (three 3 x 3 convolutions, the first with stride 2, and a 2 x 2 average pool), four layers of Bottleneck
+ * blocks whose strides are average pools, and the attention pool: the mean token as the only query over the mean token and
+ * the map's rows, heads of 64, c_proj -> fp32 [proj_dim].  Every BatchNorm (eval mode) is folded into its convolution.
+ * Geometry as clip.build_model derives it: embed_dim = 32 width, heads = embed_dim / 64, tokens = (image_size / 32)^2 + 1.     */
+typedef struct mhip_cliprn mhip_cliprn;
+typedef struct mhip_cliprn_config {
+  int width;               /* 80 (RN50x4), 64 (RN50, RN101): even, up to 128                                               */
+  int layers[4];           /* 4, 6, 10, 6 (RN50x4); 3, 4, 6, 3 (RN50); 3, 4, 23, 3 (RN101): blocks per layer, 1 .. 64       */
+  int image_size;          /* 288 (RN50x4), 224: a multiple of 32 up to 512                                                */
+  int proj_dim;            /* 640 (RN50x4), 1024 (RN50), 512 (RN101)                                                      */
+  float bn_eps;            /* 1e-5                                                                                        */
+} mhip_cliprn_config;
+/* MHIP_EINVAL, naming it: an image_size that is no multiple of 32 or above 512, an odd width (heads not 64 wide), a width
+ * above 128, a layers entry below 1                                                                                         */
+int mhip_cliprn_create(mhip_ctx* ctx, int precision, const mhip_cliprn_config* cfg, mhip_cliprn** out);
+int mhip_cliprn_destroy(mhip_cliprn* m);
+/* keys of the OpenAI checkpoint's vision tower: visual.conv{1,2,3}.weight, visual.bn{1,2,3}.*, visual.layerL.N.{conv1,bn1,conv2,
+ * bn2,conv3,bn3,downsample.0,downsample.1}.*, visual.attnpool.{positional_embedding,q_proj,k_proj,v_proj,c_proj}.*;
+ * num_batches_tracked is dropped; a key outside visual. is MHIP_EINVAL.  finalize folds the BatchNorms, pads the channel
+ * counts conv2d_nhwc does not take with zeros, and names the first missing or misshapen tensor                                */
+int mhip_cliprn_set_tensor(mhip_cliprn* m, const char* key, const float* data, const int64_t* shape, int ndim);
+int mhip_cliprn_finalize(mhip_cliprn* m);
+int mhip_cliprn_alloc_arena(mhip_cliprn* m);
+int mhip_cliprn_arena(mhip_cliprn* m, void** arena_dev, size_t* bytes);
+/* bytes of context workspace one mhip_cliprn_embed_host call of B clips lays out (0: bad arguments)                          */
+size_t mhip_cliprn_workspace_bytes(mhip_cliprn* m, int B);
+/* B (up to 1024) host clips -> emb_out fp32 [B][proj_dim].  swap_rb: the clips are stored BGR                                */
+int mhip_cliprn_embed_host(mhip_cliprn* m, const uint8_t* clips_host, int B, int swap_rb, float* emb_out);
+/* n_clips BGR host clips through the tower once, then cos_out[p] = x.y / max(|x| |y|, 1e-8) of the embeddings of clips
+ * pair_a[p], pair_b[p] (fp32 [n_pairs]); emb_out fp32 [n_clips][proj_dim] or NULL                                           */
+int mhip_cliprn_embed_pairs_host(mhip_cliprn* m, const uint8_t* clips_host, int n_clips, const int32_t* pair_a,
+                                 const int32_t* pair_b, int n_pairs, float* emb_out, float* cos_out);
+/* shape (H, W, C) of tap i: 0 the stem after its pool, 1 .. 4 the layers, 5 the embedding (1, 1, proj_dim)                    */
+int mhip_cliprn_tap_shape(mhip_cliprn* m, int i, int32_t shape[3]);
+/* as embed_host, plus taps 0 .. 4 one after another in taps_out: fp32 [B][H][W][C] each, the checkpoint's channel counts
+ * (no padding channels); emb_out may be NULL                                                                                */
+int mhip_cliprn_debug_taps_host(mhip_cliprn* m, const uint8_t* clips_host, int B, int swap_rb, float* taps_out, float* emb_out);
+/* The kernels alone on host arrays (parity tests).  The stem's first convolution: clips u8 [B][S][S][3] (S even), w fp32
+ * [C0][3][3][3], scale / bias [C0] (the folded BatchNorm) -> out fp32 [B][S/2][S/2][C0] = relu(scale * conv(normalised clip) +
+ * bias), rounded to the precision's element type; stride 2, pad 1, zeros around the normalised clip                          */
+int mhip_cliprn_stem_host(mhip_ctx* ctx, int precision, const uint8_t* clips, int B, int S, int swap_rb, const float* w,
+                          const float* scale, const float* bias, int C0, float* out);
+/* x fp32 [B][H][W][C] (rounded to the precision's element type) -> out fp32 [B][H/k][W/k][C]: k x k means, k = 2; H and W
+ * multiples of k and C of 8 (f16) / 4 (f32), else MHIP_EINVAL                                                                */
+int mhip_avgpool_nhwc_host(mhip_ctx* ctx, int precision, const float* x, int B, int H, int W, int C, int k, float* out);
+/* the attention pool: x fp32 [B][HW][E] (the last map), pos [HW + 1][E], q / k / v projections w [E][E] + b [E], c_proj wc
+ * [P][E] + bc [P] -> emb_out fp32 [B][P]; HW up to 256, E a multiple of 64 up to 4096                                        */
+int mhip_cliprn_attnpool_host(mhip_ctx* ctx, int precision, const float* x, const float* pos, const float* wq, const float* bq,
+                              const float* wk, const float* bk, const float* wv, const float* bv, const float* wc,
+                              const float* bc, int B, int HW, int E, int P, float* emb_out);
+
 /* ---- CLIP text tower: text embeddings (csrc/cliptext_api.hip, cliptext_ops.hip) ------------------------------------------- */
 /* replaces: CLIP.encode_text behind OpenAIEmbeddings.get_text_embedding, marie/embeddings/openai/openai_embeddings.py:122-129,
  * 159-164 (clip/model.py: token_embedding + positional_embedding, the causal transformer, ln_final, the end-of-text row,

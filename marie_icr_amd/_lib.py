@@ -179,6 +179,20 @@ _SIGNATURES = (
     ("mhip_clipvis_embed_rows_host", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_float, _vp]),
     ("mhip_clipvis_head_host", _i, [_vp, _vp, _i, _i, _i, _vp, _vp, C.c_float, _vp, _i, _vp]),
     ("mhip_clipvis_pair_cosine_host", _i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp]),
+    ("mhip_cliprn_create", _i, [_vp, _i, _vp, C.POINTER(_vp)]),
+    ("mhip_cliprn_destroy", _i, [_vp]),
+    ("mhip_cliprn_set_tensor", _i, [_vp, C.c_char_p, _vp, C.POINTER(C.c_int64), _i]),
+    ("mhip_cliprn_finalize", _i, [_vp]),
+    ("mhip_cliprn_alloc_arena", _i, [_vp]),
+    ("mhip_cliprn_arena", _i, [_vp, C.POINTER(_vp), C.POINTER(_sz)]),
+    ("mhip_cliprn_workspace_bytes", _sz, [_vp, _i]),
+    ("mhip_cliprn_embed_host", _i, [_vp, _vp, _i, _i, _vp]),
+    ("mhip_cliprn_embed_pairs_host", _i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
+    ("mhip_cliprn_tap_shape", _i, [_vp, _i, _vp]),
+    ("mhip_cliprn_debug_taps_host", _i, [_vp, _vp, _i, _i, _vp, _vp]),
+    ("mhip_cliprn_stem_host", _i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    ("mhip_avgpool_nhwc_host", _i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
+    ("mhip_cliprn_attnpool_host", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     ("mhip_cliptext_create", _i, [_vp, _i, _vp, C.POINTER(_vp)]),
     ("mhip_cliptext_destroy", _i, [_vp]),
     ("mhip_cliptext_set_tensor", _i, [_vp, C.c_char_p, _vp, C.POINTER(C.c_int64), _i]),
@@ -319,6 +333,25 @@ class ClipVisConfig(C.Structure):
     """mirror of mhip_clipvis_config (include/marie_hip.h)"""
     _fields_ = [("dim", C.c_int), ("depth", C.c_int), ("heads", C.c_int), ("patch", C.c_int), ("image_size", C.c_int),
                 ("ffn", C.c_int), ("proj_dim", C.c_int), ("ln_eps", C.c_float)]
+
+
+class ClipResNetConfig(C.Structure):
+    """mirror of mhip_cliprn_config (include/marie_hip.h); ``embed_dim``, ``heads`` and ``grid`` are derived as
+    ``clip.build_model`` derives them"""
+    _fields_ = [("width", C.c_int), ("layers", C.c_int * 4), ("image_size", C.c_int), ("proj_dim", C.c_int),
+                ("bn_eps", C.c_float)]
+
+    @property
+    def embed_dim(self) -> int:
+        return 32 * self.width
+
+    @property
+    def heads(self) -> int:
+        return self.width * 32 // 64
+
+    @property
+    def grid(self) -> int:
+        return self.image_size // 32
 
 
 class ClipTextConfig(C.Structure):

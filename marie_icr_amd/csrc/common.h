@@ -13,11 +13,11 @@
 
 // ------------------------------------------------------------------ kernel ids (profiling)
 enum MhipKernelId {
-  MHIP_K_CONV_FIRST = 0,  // u8 -> normalise -> conv3x3(1->64)+ReLU+maxpool2x2
+  MHIP_K_CONV_FIRST = 0,  // u8 -> normalise -> conv3x3(1->64)+ReLU+maxpool2x2; also cliprn_stem (cliprn_ops.hip): u8 RGB -> normalise -> conv3x3 stride 2 + BN + ReLU
   MHIP_K_CONV_IGEMM = 1,  // NHWC implicit-GEMM conv / GEMM on MFMA, fused scale/bias/ReLU/pool
   MHIP_K_LSTM_REC = 2,    // BiLSTM recurrence (persistent over T, batch-sliced)
   MHIP_K_CTC_DECODE = 3,  // wave-shuffle argmax + softmax-max + collapse
-  MHIP_K_IMAGE_OPS = 4,   // resize / max-pool / bilinear up-sample (HBM-bound, 16 B per lane)
+  MHIP_K_IMAGE_OPS = 4,   // resize / max-pool / bilinear up-sample (HBM-bound, 16 B per lane); also avgpool_nhwc (cliprn_ops.hip)
   MHIP_K_CCL = 5,         // score-map binarise + connected components + per-component statistics
   MHIP_K_CROP_BATCH = 6,  // fragment -> gray -> Pillow-exact bicubic to height 32 -> replicate pad
   MHIP_K_ATTN = 7,        // attention decoder pieces (context, LSTM cell, arg-max)
@@ -25,7 +25,8 @@ enum MhipKernelId {
   MHIP_K_VIT_OPS = 9,     // LayerNorm, patch extraction, token/map moves (HBM-bound)
   MHIP_K_DET_OPS = 10,    // detector heads: anchors/decode, top-k, NMS, ROIAlign
   MHIP_K_DEC_OPS = 11,    // text decoder steps: embedding, single-query attention over caches, beam candidates; also the
-                          // LayoutReader kernels (layoutreader_ops.hip): lr_embed, lr_decode_attn, lr_pointer_scores, lr_pointer_select
+                          // LayoutReader kernels (layoutreader_ops.hip): lr_embed, lr_decode_attn, lr_pointer_scores, lr_pointer_select,
+                          // and the one-query attention of the ModifiedResNet's attention pool (cliprn_attn1q, cliprn_ops.hip)
   // conv_igemm by tile shape: their launches are ALSO counted in MHIP_K_CONV_IGEMM (ProfSlot::parent), so that the fraction of
   // the MFMA peak can be recomputed per variant from a profile (names as the kernels appear in a rocprofv3 trace)
   MHIP_K_IGEMM_T64 = 12,    // conv_igemm_kernel<.., 64, ..>   512 x 64 tile
@@ -43,9 +44,10 @@ enum MhipKernelId {
   MHIP_K_CLIP_COSINE = 23,  // cosine similarity of the colour features of clip pairs
   // CLIP vision tower (clip_ops.hip)
   MHIP_K_CLIPVIS_PATCHIFY = 24,  // u8 clips -> per-channel normalised patch rows
-  MHIP_K_CLIPVIS_EMBED = 25,     // class / patch + position rows -> pre_layrnorm -> fp32 stream; the LayerNorms of the layers
+  MHIP_K_CLIPVIS_EMBED = 25,     // class / patch + position rows -> pre_layrnorm -> fp32 stream; the LayerNorms of the layers;
+                                 // also cliprn_tokens: (mean row | map) + positions of the attention pool
   MHIP_K_QUICK_GELU = 26,        // x * sigmoid(1.702 x) in place
-  MHIP_K_CLIPVIS_HEAD = 27,      // post_layernorm of the class row + projection
+  MHIP_K_CLIPVIS_HEAD = 27,      // post_layernorm of the class row + projection; also cliprn_cproj (the attention pool's c_proj)
   MHIP_K_PAIR_COSINE = 28,       // cosine of embedding pairs by index
   // CLIP text tower (cliptext_ops.hip)
   MHIP_K_CLIPTEXT_EMBED = 29,    // token table gather + position rows -> fp32 stream
@@ -595,6 +597,22 @@ int mhip_launch_clipvis_head(mhip_ctx* ctx, const float* h, int B, int npad, int
                              const float* proj_t, int E, float* emb, const int* row_of = nullptr);
 // out[p] = cos(emb[pair_a[p]], emb[pair_b[p]]), emb [..][E] fp32; the indices are the caller's to check
 int mhip_launch_pair_cosine(mhip_ctx* ctx, const float* emb, int E, const int* pair_a, const int* pair_b, int n_pairs, float* out);
+// ------------------------------------------------------------------ CLIP ModifiedResNet tower ops (cliprn_ops.hip)
+// NHWC activations of the precision's element type.  clips u8 [B][S][S][3], S even -> out [B][S/2][S/2][Cp]: the 3 x 3, stride 2,
+// pad 1 convolution of the normalised clip (zero outside it), out = relu(scale * acc + bias); w27 fp32 [(dy*3 + dx)*3 + c][Cp],
+// Cp a multiple of 8 up to 64
+int mhip_launch_cliprn_stem(mhip_ctx* ctx, int precision, const uint8_t* imgs, int B, int S, int swap_rb, const float mean[3],
+                            const float stdv[3], const float* w27, const float* scale, const float* bias, void* out, int Cp);
+// in [B][H][W][C] -> out [B][H/k][W/k][C]: the mean of every k x k window (k = 2; H, W multiples of k; C of 16 bytes' worth)
+int mhip_launch_avgpool_nhwc(mhip_ctx* ctx, int precision, int k, const void* in, void* out, int B, int H, int W, int C);
+// the attention pool's limits: HW + 1 <= 257 keys, E a multiple of 64 up to 4096
+bool mhip_cliprn_attnpool_ok(int HW, int E, int P);
+// x [B][HW][E] -> tok [B][HW + 1][E] = (mean row | x) + pos, xq [B][E] = the mean rows; pos fp32 [HW + 1][E]
+int mhip_launch_cliprn_tokens(mhip_ctx* ctx, int precision, const void* x, const float* pos, void* tok, void* xq, int B, int HW, int E);
+// ao fp32 [B][E] = soft-max(q_h . k_h) v_h per head of 64; q fp32 [B][E] pre-scaled, kv fp32 [B * NT][2 E] (k | v)
+int mhip_launch_cliprn_attn1q(mhip_ctx* ctx, const float* q, const float* kv, float* ao, int B, int NT, int E);
+// emb fp32 [B][P] = ao w^T + bias; w fp32 [P][E]
+int mhip_launch_cliprn_cproj(mhip_ctx* ctx, const float* ao, int B, int E, const float* w, const float* bias, int P, float* emb);
 // ------------------------------------------------------------------ CLIP text tower ops (cliptext_ops.hip)
 // h [B*npad][D] fp32 = table[ids[row]] + pos[row % npad]; table [vocab][D], pos [>= npad][D] fp32; the ids are the caller's to check
 int mhip_launch_cliptext_embed(mhip_ctx* ctx, const float* table, const float* pos, const int* ids, float* h, int B, int npad, int D);

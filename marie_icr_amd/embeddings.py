@@ -10,8 +10,10 @@ the detector already has, and CLIP's normalisation is part of the patch kernel.
 Built: the ViT towers (ViT-B/32, ViT-B/16, any width of 64-wide heads up to 1024) from an OpenAI-scheme (``visual.*``) or a
 ``transformers``-scheme (``vision_model.*`` + ``visual_projection``) state dict, and the text tower of the same checkpoint
 (csrc/cliptext_api.hip, ``mhip_cliptext_*``: causal attention in HIP) with its BPE (clip_tokenizer.py) where the checkpoint holds
-one and a vocabulary is at hand: ``get_embeddings(texts, image=None)`` embeds ``" ".join(texts)``.  Not built: the
-``ModifiedResNet`` towers (``RN50x4`` ...: ``NotImplementedError``).  Without a text side ``image=None`` raises
+one and a vocabulary is at hand: ``get_embeddings(texts, image=None)`` embeds ``" ".join(texts)``.  The ``ModifiedResNet``
+towers (RN50, RN101, RN50x4 — the reference's default snippet model) have a loader and a class of their own,
+``load_clip_resnet_state`` / ``OpenAIResNetEmbeddings`` (csrc/cliprn_api.hip, ``mhip_cliprn_*``); ``OpenAIEmbeddings`` and
+``load_clip_vision_state`` refuse them with ``NotImplementedError`` and name those.  Without a text side ``image=None`` raises
 ``NotImplementedError``.  Errors raise ``MarieHipError`` (a text longer than the context: ``ValueError``); the reference's
 ``try/except`` returning an empty ``EmbeddingsObject`` is not restated.
 
@@ -33,7 +35,8 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from ._lib import PREC_F16, PREC_F32, BertTextConfig, ClipTextConfig, ClipVisConfig, Context, MarieHipError, ModelHandle, check, load
+from ._lib import (PREC_F16, PREC_F32, BertTextConfig, ClipResNetConfig, ClipTextConfig, ClipVisConfig, Context, MarieHipError,
+                   ModelHandle, check, load)
 from .clip_tokenizer import ClipTokenizer
 from .wordpiece_tokenizer import WordPieceTokenizer
 
@@ -126,7 +129,7 @@ def load_clip_vision_state(checkpoint: Dict[str, Any]) -> Tuple[Dict[str, np.nda
         raise MarieHipError("CLIP checkpoint: expected a state dict or {'model_state_dict': state dict}")
     if any(k.startswith("visual.layer1.") or k.startswith("visual.attnpool.") for k in sd):
         raise NotImplementedError("CLIP checkpoint holds a ModifiedResNet vision tower (RN50 / RN101 / RN50x4 ...): only the "
-                                  "ViT towers are built")
+                                  "ViT towers are built here; load_clip_resnet_state and OpenAIResNetEmbeddings take it")
     if any(k.startswith("vision_model.") for k in sd):
         state = _from_transformers(sd)
     else:
@@ -179,6 +182,89 @@ def load_clip_text_state(checkpoint: Dict[str, Any]) -> Optional[Tuple[Dict[str,
     cfg.ffn = int(state["transformer.resblocks.0.mlp.c_fc.weight"].shape[0])
     cfg.proj_dim = int(state["text_projection"].shape[1])
     cfg.ln_eps = 1e-5
+    return state, cfg
+
+
+# geometry of the ModifiedResNet towers ``clip`` publishes: (layers, width, image_size, proj_dim)
+CLIP_RESNETS = {"RN50": ((3, 4, 6, 3), 64, 224, 1024), "RN101": ((3, 4, 23, 3), 64, 224, 512),
+                "RN50x4": ((4, 6, 10, 6), 80, 288, 640)}
+_RN_BN = ("weight", "bias", "running_mean", "running_var")
+
+
+def clip_resnet_keys(cfg: ClipResNetConfig) -> Dict[str, Tuple[int, ...]]:
+    """every tensor the ModifiedResNet tower of ``cfg`` takes -> its shape, in the order ``finalize`` looks them up"""
+    w, E, P = cfg.width, cfg.embed_dim, cfg.proj_dim
+    keys: Dict[str, Tuple[int, ...]] = {}
+
+    def conv_bn(conv, bn, co, ci, k):
+        keys[f"visual.{conv}.weight"] = (co, ci, k, k)
+        for name in _RN_BN:
+            keys[f"visual.{bn}.{name}"] = (co,)
+
+    conv_bn("conv1", "bn1", w // 2, 3, 3)
+    conv_bn("conv2", "bn2", w // 2, w // 2, 3)
+    conv_bn("conv3", "bn3", w, w // 2, 3)
+    cin = w
+    for l in range(4):
+        planes = w << l
+        for i in range(cfg.layers[l]):
+            p = f"layer{l + 1}.{i}."
+            conv_bn(p + "conv1", p + "bn1", planes, cin, 1)
+            conv_bn(p + "conv2", p + "bn2", planes, planes, 3)
+            conv_bn(p + "conv3", p + "bn3", 4 * planes, planes, 1)
+            if (i == 0 and l > 0) or cin != 4 * planes:
+                conv_bn(p + "downsample.0", p + "downsample.1", 4 * planes, cin, 1)
+            cin = 4 * planes
+    keys["visual.attnpool.positional_embedding"] = (cfg.grid ** 2 + 1, E)
+    for name in "qkv":
+        keys[f"visual.attnpool.{name}_proj.weight"], keys[f"visual.attnpool.{name}_proj.bias"] = (E, E), (E,)
+    keys["visual.attnpool.c_proj.weight"], keys["visual.attnpool.c_proj.bias"] = (P, E), (P,)
+    return keys
+
+
+def load_clip_resnet_state(checkpoint: Dict[str, Any]) -> Tuple[Dict[str, np.ndarray], ClipResNetConfig]:
+    """A ``torch.load``-ed CLIP checkpoint with a ModifiedResNet vision tower — ``{"model_state_dict": sd}`` or a bare state
+    dict under the OpenAI keys (``visual.layerL.N.*``, ``visual.attnpool.*``), any float storage — -> (the tower's tensors as
+    float32 arrays, the geometry read from their shapes as ``clip.build_model`` reads it).  ``num_batches_tracked`` and the
+    text tower's keys are ignored; a missing or misshapen tensor raises ``MarieHipError`` naming it."""
+    sd = checkpoint.get("model_state_dict", checkpoint) if isinstance(checkpoint, dict) else None
+    if not isinstance(sd, dict) or not sd:
+        raise MarieHipError("CLIP checkpoint: expected a state dict or {'model_state_dict': state dict}")
+    if "visual.layer1.0.conv1.weight" not in sd or "visual.attnpool.positional_embedding" not in sd:
+        if "visual.proj" in sd or any(k.startswith("vision_model.") for k in sd):
+            raise MarieHipError("CLIP checkpoint holds a ViT vision tower (visual.proj / vision_model.*): load_clip_vision_state "
+                                "and OpenAIEmbeddings take it")
+        missing = [k for k in ("visual.layer1.0.conv1.weight", "visual.attnpool.positional_embedding") if k not in sd]
+        raise MarieHipError(f"CLIP checkpoint: no {missing[0]} (no ModifiedResNet vision tower under the OpenAI keys)")
+    cfg = ClipResNetConfig()
+    block = re.compile(r"visual\.layer([1-4])\.(\d+)\.")
+    counts = [set(), set(), set(), set()]
+    for k in sd:
+        m = block.match(k)
+        if m:
+            counts[int(m.group(1)) - 1].add(int(m.group(2)))
+    for l, found in enumerate(counts):
+        if not found or found != set(range(len(found))):
+            raise MarieHipError(f"CLIP checkpoint: visual.layer{l + 1} has blocks {sorted(found)}, expected 0 .. n - 1")
+        cfg.layers[l] = len(found)
+    cfg.width = int(sd["visual.layer1.0.conv1.weight"].shape[0])
+    pos_rows = int(sd["visual.attnpool.positional_embedding"].shape[0])
+    grid = int(round((pos_rows - 1) ** 0.5))
+    if grid < 1 or grid * grid + 1 != pos_rows:
+        raise MarieHipError(f"CLIP checkpoint: {pos_rows} position rows of the attention pool are no square grid plus the mean token")
+    cfg.image_size = 32 * grid
+    if "visual.attnpool.c_proj.weight" not in sd:
+        raise MarieHipError("CLIP checkpoint: no visual.attnpool.c_proj.weight")
+    cfg.proj_dim = int(sd["visual.attnpool.c_proj.weight"].shape[0])
+    cfg.bn_eps = 1e-5
+    state = {}
+    for key, shape in clip_resnet_keys(cfg).items():
+        if key not in sd:
+            raise MarieHipError(f"CLIP checkpoint: no {key} (a ModifiedResNet of width {cfg.width}, layers {tuple(cfg.layers)})")
+        arr = _f32(sd[key])
+        if arr.shape != shape:
+            raise MarieHipError(f"CLIP checkpoint: {key} has shape {arr.shape}, the geometry read from the checkpoint asks for {shape}")
+        state[key] = arr
     return state, cfg
 
 
@@ -235,6 +321,42 @@ class ClipVisionModel(ModelHandle):
         taps = np.empty((self.cfg.depth + 1, n, self.n_tok, self.cfg.dim), np.float32)
         emb = np.empty((n, self.cfg.proj_dim), np.float32)
         self._call("debug_taps_host", _vp(clips), n, 1 if swap_rb else 0, _vp(taps), _vp(emb))
+        return taps, emb
+
+
+class ClipResNetModel(ClipVisionModel):
+    """``mhip_cliprn``: CLIP's ModifiedResNet tower (stem, four layers of Bottleneck blocks, attention pool) on a
+    :class:`Context`.  The entries are :class:`ClipVisionModel`'s; the taps differ."""
+
+    def __init__(self, ctx: Context, state: Optional[Dict[str, np.ndarray]], config: ClipResNetConfig, precision: int = PREC_F16):
+        self.cfg, self.precision = config, int(precision)
+        ModelHandle.__init__(self, ctx, "cliprn", self.precision, C.byref(config))
+        self.n_tok = config.grid ** 2 + 1      # the mean token + the last map
+        if state is not None:
+            self.load_state(state)
+
+    def workspace_bytes(self, n: int) -> int:
+        return int(self.lib.mhip_cliprn_workspace_bytes(self.h, int(n)))
+
+    def tap_shape(self, i: int) -> Tuple[int, int, int]:
+        """(H, W, C) of tap ``i``: 0 the stem after its pool, 1 .. 4 the layers, 5 the embedding"""
+        shape = (C.c_int32 * 3)()
+        self._call("tap_shape", int(i), shape)
+        return tuple(shape)
+
+    def debug_taps_host(self, clips, swap_rb: bool = False):
+        """-> ([5 arrays fp32 (n, H, W, C)]: the stem after its pool and the output of every layer, the checkpoint's channel
+        counts; embeddings (n, proj_dim))"""
+        clips = self._clips(clips)
+        n = clips.shape[0]
+        shapes = [self.tap_shape(i) for i in range(5)]
+        flat = np.empty(n * sum(h * w * c for h, w, c in shapes), np.float32)
+        emb = np.empty((n, self.cfg.proj_dim), np.float32)
+        self._call("debug_taps_host", _vp(clips), n, 1 if swap_rb else 0, _vp(flat), _vp(emb))
+        taps, at = [], 0
+        for h, w, c in shapes:
+            taps.append(flat[at:at + n * h * w * c].reshape(n, h, w, c))
+            at += n * h * w * c
         return taps, emb
 
 
@@ -349,6 +471,44 @@ def head_host(ctx: Context, h, g, b, proj, eps: float = 1e-5) -> np.ndarray:
     return out
 
 
+def resnet_stem_host(ctx: Context, precision: int, clips, w, scale, bias, swap_rb: bool = False) -> np.ndarray:
+    """the ModifiedResNet's first convolution alone: uint8 clips (B, S, S, 3), w (C0, 3, 3, 3), the folded BatchNorm scale / bias
+    (C0) -> fp32 (B, S / 2, S / 2, C0) = relu(scale * conv_stride2_pad1(normalised clip) + bias)"""
+    clips = np.ascontiguousarray(clips, np.uint8)
+    w, scale, bias = (np.ascontiguousarray(a, np.float32) for a in (w, scale, bias))
+    B, S = clips.shape[:2]
+    if clips.shape != (B, S, S, 3) or w.shape[1:] != (3, 3, 3) or scale.shape != (w.shape[0],) or bias.shape != scale.shape:
+        raise ValueError(f"clips (B, S, S, 3), w (C0, 3, 3, 3), scale / bias (C0) expected, got {clips.shape}, {w.shape}, {scale.shape}")
+    out = np.empty((B, S // 2, S // 2, w.shape[0]), np.float32)
+    check(ctx.h, ctx.lib.mhip_cliprn_stem_host(ctx.h, int(precision), _vp(clips), B, S, 1 if swap_rb else 0, _vp(w), _vp(scale), _vp(bias),
+                                               w.shape[0], _vp(out)), "mhip_cliprn_stem_host")
+    return out
+
+
+def avgpool_nhwc_host(ctx: Context, precision: int, x, k: int = 2) -> np.ndarray:
+    """x fp32 (B, H, W, C) -> fp32 (B, H / k, W / k, C): the mean of every k x k window"""
+    x = np.ascontiguousarray(x, np.float32)
+    B, H, W, Cc = x.shape
+    out = np.empty((B, H // k, W // k, Cc), np.float32)
+    check(ctx.h, ctx.lib.mhip_avgpool_nhwc_host(ctx.h, int(precision), _vp(x), B, H, W, Cc, int(k), _vp(out)), "mhip_avgpool_nhwc_host")
+    return out
+
+
+def resnet_attnpool_host(ctx: Context, precision: int, x, pos, wq, bq, wk, bk, wv, bv, wc, bc) -> np.ndarray:
+    """the attention pool alone: x fp32 (B, HW, E) the last map, pos (HW + 1, E), the q / k / v projections (E, E) + (E), c_proj
+    (P, E) + (P) -> fp32 (B, P)"""
+    x, pos, wq, bq, wk, bk, wv, bv, wc, bc = (np.ascontiguousarray(a, np.float32) for a in (x, pos, wq, bq, wk, bk, wv, bv, wc, bc))
+    B, HW, E = x.shape
+    P = wc.shape[0]
+    if pos.shape != (HW + 1, E) or any(a.shape != (E, E) for a in (wq, wk, wv)) or any(a.shape != (E,) for a in (bq, bk, bv)) or \
+            wc.shape != (P, E) or bc.shape != (P,):
+        raise ValueError("attention pool: x (B, HW, E), pos (HW + 1, E), projections (E, E) + (E), c_proj (P, E) + (P) expected")
+    out = np.empty((B, P), np.float32)
+    check(ctx.h, ctx.lib.mhip_cliprn_attnpool_host(ctx.h, int(precision), _vp(x), _vp(pos), _vp(wq), _vp(bq), _vp(wk), _vp(bk), _vp(wv),
+                                                   _vp(bv), _vp(wc), _vp(bc), B, HW, E, P, _vp(out)), "mhip_cliprn_attnpool_host")
+    return out
+
+
 def pair_cosine_host(ctx: Context, emb, pairs) -> np.ndarray:
     """emb (n, E) fp32, pairs (n_pairs, 2) of row indices -> fp32 (n_pairs,)"""
     emb = np.ascontiguousarray(emb, np.float32)
@@ -405,14 +565,14 @@ class ClipImageEmbeddings(EmbeddingsBase):
         self.model_name_or_path = model_name_or_path
         if state is None:
             state = self._load_checkpoint(model_name_or_path)
-        tensors, cfg = load_clip_vision_state(state)
+        tensors, cfg = self._load_vision(state)
         text_side = self._text_side(state, text, tokenizer, model_name_or_path)      # before any device work
         if isinstance(precision, str):
             if precision not in ("f16", "f32"):
                 raise ValueError(f"precision {precision!r}: 'f16' or 'f32'")
             precision = PREC_F16 if precision == "f16" else PREC_F32
         self.ctx = ctx or Context(_device_id(devices))
-        self.model = ClipVisionModel(self.ctx, tensors, cfg, precision)
+        self.model = self._make_vision(tensors, cfg, precision)
         self.image_size, self.proj_dim = cfg.image_size, cfg.proj_dim
         self.encoder_calls = 0               # device encoder calls so far
         self.clips_embedded = 0              # clips those calls carried
@@ -423,6 +583,15 @@ class ClipImageEmbeddings(EmbeddingsBase):
             self.context_length = text_cfg.context
         self.text_encoder_calls = 0          # device text tower calls so far
         self.texts_embedded = 0              # texts those calls carried
+
+    # -- the vision tower: what a subclass with another tower overrides ---------------------------------------------------
+    def _load_vision(self, state):
+        """the loaded checkpoint -> (tensors, config) of the vision tower; no device work"""
+        return load_clip_vision_state(state)
+
+    def _make_vision(self, tensors, cfg, precision: int):
+        """the model handle on ``self.ctx``; ``cfg`` carries ``image_size`` and ``proj_dim``"""
+        return ClipVisionModel(self.ctx, tensors, cfg, precision)
 
     def _text_side(self, state, text, tokenizer, model_dir):
         """((tensors, config), tokenizer) of the text side to build, or None"""
@@ -462,10 +631,13 @@ class ClipImageEmbeddings(EmbeddingsBase):
     def preprocess(self, image) -> np.ndarray:
         """``convert("RGB")`` -> BICUBIC resize of the shortest edge to ``image_size`` -> centre crop: the uint8 RGB clip
         (image_size, image_size, 3) the processor would rescale and normalise (that part is the patch kernel's)"""
+        return self._resize_crop(np.ascontiguousarray(np.asarray(image.convert("RGB")), np.uint8))
+
+    def _resize_crop(self, rgb: np.ndarray) -> np.ndarray:
+        """uint8 (h, w, 3), either channel order -> (image_size, image_size, 3): BICUBIC shortest edge, centre crop"""
         from .dit import pil_resize_rgb
 
         S = self.image_size
-        rgb = np.ascontiguousarray(np.asarray(image.convert("RGB")), np.uint8)
         h, w = rgb.shape[:2]
         if (w, h) != (S, S):
             nw, nh = resized_size(w, h, S)
@@ -578,14 +750,92 @@ class OpenAIEmbeddings(ClipImageEmbeddings):
                 raise ValueError(f"Model config does not contain 'architecture' key: {config}")
             architecture = config["architecture"]
         if architecture is not None and not str(architecture).startswith("ViT-"):
-            raise NotImplementedError(f"CLIP architecture {architecture!r}: only the ViT towers are built (ViT-B/32, ViT-B/16); "
-                                      "the ModifiedResNet / attention-pool tower is not")
+            raise NotImplementedError(f"CLIP architecture {architecture!r}: only the ViT towers are built (ViT-B/32, ViT-B/16) "
+                                      "by this class; the ModifiedResNet / attention-pool tower is OpenAIResNetEmbeddings'")
         self.architecture = architecture
         super().__init__(model_name_or_path, *args, **kwargs)
 
 
 class OpenAITransformerEmbeddings(ClipImageEmbeddings):
     """marie/embeddings/openai/openai_trans_embeddings.py (``transformers.CLIPModel``, openai/clip-vit-base-patch32)"""
+
+
+class OpenAIResNetEmbeddings(ClipImageEmbeddings):
+    """marie/embeddings/openai/openai_embeddings.py on a ModifiedResNet checkpoint (RN50, RN101, RN50x4 — the architecture of
+    marie/clip-snippet-rn50x4, the model both template matchers build by default): the tower runs in HIP (csrc/cliprn_api.hip,
+    ``mhip_cliprn_*``).  ``OpenAIEmbeddings`` keeps refusing these architectures; hand this object to a matcher as its
+    ``embeddings_processor``.  The matchers hold 224 x 224 BGR clips: ``embed_clips`` and ``cosine_pairs`` bring clips of any one
+    size to ``image_size`` by :meth:`preprocess`'s rule (for a square clip one Pillow-exact BICUBIC resize), which is what the
+    reference's processor does to the matcher's clip in front of RN50x4."""
+
+    CLIP_CHUNK = 128       # clips of one tower call
+
+    def __init__(self, model_name_or_path=None, *args, architecture: Optional[str] = None, **kwargs):
+        """``architecture``: None reads ``marie.json`` of the model directory when there is one; a name must start with ``RN``
+        and, for RN50 / RN101 / RN50x4, agree with the geometry read from the checkpoint's shapes (``ValueError``)."""
+        if architecture is None and model_name_or_path is not None and os.path.isdir(model_name_or_path):
+            config_file = os.path.join(model_name_or_path, "marie.json")
+            if os.path.isfile(config_file):
+                with open(config_file, "r", encoding="utf-8") as f:
+                    architecture = json.load(f).get("architecture")
+        if architecture is not None and not str(architecture).startswith("RN"):
+            raise ValueError(f"CLIP architecture {architecture!r}: OpenAIResNetEmbeddings builds the ModifiedResNet towers (RN50, "
+                             "RN101, RN50x4); OpenAIEmbeddings builds the ViT ones")
+        self.architecture = architecture
+        super().__init__(model_name_or_path, *args, **kwargs)
+
+    def _load_vision(self, state):
+        tensors, cfg = load_clip_resnet_state(state)
+        known = CLIP_RESNETS.get(str(self.architecture))
+        found = (tuple(cfg.layers), cfg.width, cfg.image_size, cfg.proj_dim)
+        if known is not None and known != found:
+            raise ValueError(f"CLIP architecture {self.architecture!r} is (layers, width, image, proj_dim) = {known}; the "
+                             f"checkpoint's shapes say {found}")
+        return tensors, cfg
+
+    def _make_vision(self, tensors, cfg, precision: int):
+        return ClipResNetModel(self.ctx, tensors, cfg, precision)
+
+    def _text_side(self, state, text, tokenizer, model_dir):
+        side = super()._text_side(state, text, tokenizer, model_dir)
+        if side is not None and (side[0][1].dim % 64 or side[0][1].dim > 1024):      # what mhip_cliptext_create takes
+            if text:
+                raise MarieHipError(f"{type(self).__name__}(text=True): the text tower is {side[0][1].dim} wide; the text kernels "
+                                    "take a multiple of 64 up to 1024")
+            return None
+        return side
+
+    # -- the matcher's entries: clips of any one size ----------------------------------------------------------------------
+    def _sized(self, clips_u8_bgr) -> np.ndarray:
+        clips = np.ascontiguousarray(clips_u8_bgr, np.uint8)
+        if clips.ndim == 3:
+            clips = clips[None]
+        if clips.ndim != 4 or clips.shape[3] != 3 or clips.shape[0] < 1:
+            raise ValueError(f"clips of shape (n, h, w, 3) expected, got {clips.shape}")
+        S = self.image_size
+        if clips.shape[1:3] != (S, S):
+            clips = np.stack([self._resize_crop(c) for c in clips])
+        return clips
+
+    def _embed(self, clips: np.ndarray, swap_rb: bool) -> np.ndarray:
+        out = np.empty((len(clips), self.proj_dim), np.float32)
+        for at in range(0, len(clips), self.CLIP_CHUNK):
+            out[at:at + self.CLIP_CHUNK] = super()._embed(clips[at:at + self.CLIP_CHUNK], swap_rb)
+        return out
+
+    def embed_clips(self, clips_u8_bgr) -> np.ndarray:
+        """BGR uint8 clips (n, h, w, 3) of one size -> fp32 (n, proj_dim); one tower call per ``CLIP_CHUNK`` clips"""
+        return self._embed(self._sized(clips_u8_bgr), swap_rb=True)
+
+    def cosine_pairs(self, clips_u8_bgr, pairs: Sequence[Tuple[int, int]], want_embeddings: bool = False):
+        """the clips through the tower once (per ``CLIP_CHUNK`` clips), and the cosine of the embeddings of every (a, b) index
+        pair -> fp32 (n_pairs,) (, embeddings fp32 (n, proj_dim))"""
+        clips = self._sized(clips_u8_bgr)
+        if len(clips) <= self.CLIP_CHUNK:
+            return super().cosine_pairs(clips, pairs, want_embeddings=want_embeddings)
+        emb = self._embed(clips, swap_rb=True)
+        cos = pair_cosine_host(self.ctx, emb, pairs)
+        return (cos, emb) if want_embeddings else cos
 
 
 # ---------------------------------------------------------------------------------------------------- BERT sentence encoders

@@ -12,11 +12,11 @@ filter responses) is built once per template and cached under the reference's ke
 
 Built: the model-free ``num_features == 27`` colour features of ``PixelFeatureExtractor`` (the paper's colour variant).
 The snippet embedding of ``score`` is CLIP's: ``embeddings_processor`` takes an ``OpenAIEmbeddings`` /
-``OpenAITransformerEmbeddings`` of ``embeddings.py`` (the ViT towers in HIP; the unique clips of a scoring batch go through the
-encoder in one call), or any callable clip -> vector; with None the embedding similarity is taken equal to the feature
-similarity.
-Not built: the EfficientNet hyper-column features and ``pca_lowrank`` (``n_feature != 27`` / ``pca_dims`` raise), CLIP's RN50x4
-tower (the reference's default snippet model: ``embeddings.py`` refuses it), ``resize_image_progressive``
+``OpenAITransformerEmbeddings`` of ``embeddings.py`` (the ViT towers in HIP) or an ``OpenAIResNetEmbeddings`` (the ModifiedResNet
+towers: RN50x4, the reference's default snippet model); the unique clips of a scoring batch go through the encoder in one call.
+Or any callable clip -> vector; with None the embedding similarity is taken equal to the feature similarity.
+Not built: the EfficientNet hyper-column features and ``pca_lowrank`` (``n_feature != 27`` / ``pca_dims`` raise),
+``resize_image_progressive``
 (``downscale_factor != 1`` raises), ``DeepDimTemplateMatcher``, and the reference's /tmp/dim writes,
 prints and visualisations.  ``slice_image`` and
 ``GreedyNMMPostprocess`` restate sahi's, which is not installed here: their parity with sahi is not pinned by a golden.
