@@ -715,6 +715,31 @@ int mhip_attention_bias_host(mhip_ctx* ctx, int precision, int heads, int n_tok,
                              const float* v, const int32_t* pos, const int32_t* x, const int32_t* y, const int32_t* valid,
                              const float* w1, const float* wx, const float* wy, int bins_1d, int max_1d, int bins_2d,
                              int max_2d, float* out);
+/* One launch of the attention kernel (csrc/attn_flash.hip), plain or biased, with the whole descriptor in the caller's hands
+ * (kernel-level parity tests).  Rq = images * npad_q + MHIP_ATTN_SLACK_ROWS query rows, Rk = images * npad_k +
+ * MHIP_ATTN_SLACK_ROWS key rows, D = heads * 64.  The caller fills EVERY row, the padding rows of each image and the slack
+ * behind the last one included; the entry only narrows fp32 to the precision's element type.  q is in the kernel's units
+ * (already scaled by head_dim^-0.5 * log2 e).  Nothing is launched, and MHIP_EINVAL returned, for a shape the launcher refuses. */
+#define MHIP_ATTN_SLACK_ROWS 128
+#define MHIP_ATTN_LAYOUT_FUSED 0 /* q | k rows of pitch 2 D in one buffer, as every model lays them out: npad_q == npad_k   */
+#define MHIP_ATTN_LAYOUT_SPLIT 1 /* q and k buffers of pitch D each: npad_q and npad_k are independent                      */
+typedef struct mhip_attention_host_desc {
+  int32_t precision, layout;
+  int32_t images, heads, n_queries, n_keys, npad_q, npad_k;
+  const float* q;       /* [Rq][D]                                                                                          */
+  const float* k;       /* [Rk][D]                                                                                          */
+  const float* vt;      /* [D * images * npad_k + MHIP_ATTN_SLACK_ROWS]: V^T, row pitch images * npad_k, then the slack     */
+  /* the biased form (w1 non-NULL): per row pos, x, y (qcode [Rq][3]) and pos, x, y, valid (kcode [Rk][4]), pos in [0, dp],
+   * x and y in [0, dx]; the tables are folded from w1 [heads][bins_1d], wx / wy [heads][bins_2d] as the model folds them   */
+  const int32_t* qcode;
+  const int32_t* kcode;
+  const float *w1, *wx, *wy;
+  int32_t bins_1d, max_1d, bins_2d, max_2d, dp, dx;
+  /* [Rq][D] in the ELEMENT TYPE (f16 or fp32 bits): the device buffer is filled with the byte 0xff (a NaN in both types)
+   * before the launch and copied back whole, so that rows nobody wrote and the guard rows behind the last image show       */
+  void* out;
+} mhip_attention_host_desc;
+int mhip_attention_host(mhip_ctx* ctx, const mhip_attention_host_desc* d);
 
 /* ---- VQ-NNF template matching (csrc/vqnnf.hip) -------------------------------------------------------------------------- */
 /* replaces: VQNNFMatcher + GaussHaarFilters + KMeans, marie/components/template_matching/vqnnf/matching/, with the colour

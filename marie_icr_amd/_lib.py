@@ -154,6 +154,7 @@ _SIGNATURES = (
     ("mhip_layoutlmv3_tag_host", _i, [_vp, _vp, _sz, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("mhip_token_head_host", _i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("mhip_attention_bias_host", _i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    ("mhip_attention_host", _i, [_vp, _vp]),
     ("mhip_vq_template_create", _i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, C.POINTER(_vp)]),
     ("mhip_vq_template_destroy", _i, [_vp]),
     ("mhip_vq_template_state", _i, [_vp, C.POINTER(_i), C.POINTER(_i), _vp, _vp]),
@@ -372,6 +373,13 @@ class LayoutReaderConfig(C.Structure):
     _fields_ = [("dim", C.c_int), ("heads", C.c_int), ("depth", C.c_int), ("ffn", C.c_int), ("max_position", C.c_int),
                 ("max_2d", C.c_int), ("max_source", C.c_int), ("type_vocab", C.c_int), ("source_type", C.c_int),
                 ("target_type", C.c_int), ("ln_eps", C.c_float)]
+
+
+class AttentionHostDesc(C.Structure):
+    """mirror of ``mhip_attention_host_desc`` (include/marie_hip.h); the pointers are host arrays"""
+    _fields_ = ([(n, C.c_int32) for n in ("precision", "layout", "images", "heads", "n_queries", "n_keys", "npad_q", "npad_k")] +
+                [(n, C.c_void_p) for n in ("q", "k", "vt", "qcode", "kcode", "w1", "wx", "wy")] +
+                [(n, C.c_int32) for n in ("bins_1d", "max_1d", "bins_2d", "max_2d", "dp", "dx")] + [("out", C.c_void_p)])
 
 
 class VqFilters(C.Structure):

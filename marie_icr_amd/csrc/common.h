@@ -357,7 +357,11 @@ int mhip_launch_split_f16(mhip_ctx* ctx, const float* in, void* hi, void* lo, lo
 int mhip_launch_join_f16(mhip_ctx* ctx, const void* hi, const void* lo, float* out, long long n);
 // (attn_flash.hip) softmax(Q K^T) V for `images` x `heads` independent (head_dim 64) problems; q is pre-scaled by head_dim^-0.5 * log2(e).
 // The last 128-query block / 64-key tile of an image may read up to 127 rows past it (and masks them): q and k — and the codes
-// of AttnBiasDesc — need ATTN_SLACK_ROWS finite rows past the last image, vt 64 finite elements (carved as ATTN_SLACK_ROWS)
+// of AttnBiasDesc — need ATTN_SLACK_ROWS finite rows past the last image, vt 64 finite elements (carved as ATTN_SLACK_ROWS).
+// The same holds inside an image: its padding rows n_keys .. npad_k - 1 of k and their V^T columns are read and take a
+// probability of exactly 0, so they must be finite (0 x NaN would reach the output), whatever else they hold; a code that is
+// read — padding and slack rows included — must index inside its table (p <= 2 dp + 1, x and y <= dx).  Output rows n_queries ..
+// npad_q - 1 inside a launched 128-query block are written (with the results of the padding queries); nothing else is.
 constexpr int ATTN_SLACK_ROWS = 128;
 struct AttnDesc {
   const void* q = nullptr;    // [images*npad_q][ldq] T, head h at column h*64

@@ -654,7 +654,99 @@ extern "C" int mhip_token_head_host(mhip_ctx* ctx, int precision, int rows, int 
   return MHIP_OK;
 }
 
-// ---------------------------------------------------------------------------------------------------- the attention kernel alone
+// ---------------------------------------------------------------------------------------------------- the attention kernels alone
+static_assert(MHIP_ATTN_SLACK_ROWS == ATTN_SLACK_ROWS, "the header's slack is the kernel's");
+
+// One mhip_launch_attention / mhip_launch_attention_bias on caller-supplied host operands, every row of them the caller's (see
+// include/marie_hip.h).  The shape is judged by the launcher alone; what is checked here is what this entry's own buffers and
+// the packing of the codes need.
+extern "C" int mhip_attention_host(mhip_ctx* ctx, const mhip_attention_host_desc* hd) {
+  if (!ctx) return MHIP_EINVAL;
+  if (!hd || !hd->q || !hd->k || !hd->vt || !hd->out) return mhip_fail(ctx, MHIP_EINVAL, "attention_host: null operand");
+  const mhip_attention_host_desc& h = *hd;
+  if (h.precision != MHIP_PREC_F16 && h.precision != MHIP_PREC_F32) return mhip_fail(ctx, MHIP_EINVAL, "unknown precision %d", h.precision);
+  if (h.layout != MHIP_ATTN_LAYOUT_FUSED && h.layout != MHIP_ATTN_LAYOUT_SPLIT)
+    return mhip_fail(ctx, MHIP_EINVAL, "attention_host: unknown layout %d", h.layout);
+  if (h.layout == MHIP_ATTN_LAYOUT_FUSED && h.npad_q != h.npad_k)
+    return mhip_fail(ctx, MHIP_EINVAL, "attention_host: the fused layout has one row pitch (npad_q %d, npad_k %d)", h.npad_q, h.npad_k);
+  if (h.images < 0 || h.heads < 0 || h.heads > 64 || h.npad_q < 0 || h.npad_k < 0 || h.npad_q > 65536 || h.npad_k > 65536 || h.images > 4096)
+    return mhip_fail(ctx, MHIP_EINVAL, "attention_host: images %d, heads %d, npad %d / %d", h.images, h.heads, h.npad_q, h.npad_k);
+  const bool biased = h.w1 != nullptr;
+  const size_t es = h.precision == MHIP_PREC_F16 ? 2 : 4, D = (size_t)h.heads * 64;
+  const size_t Rq = (size_t)h.images * h.npad_q + ATTN_SLACK_ROWS, Rk = (size_t)h.images * h.npad_k + ATTN_SLACK_ROWS;
+  const size_t nvt = D * h.images * h.npad_k + ATTN_SLACK_ROWS;
+  std::vector<uint32_t> qcode, kcode;
+  std::vector<float> tab;
+  if (biased) {
+    if (!h.wx || !h.wy || !h.qcode || !h.kcode) return mhip_fail(ctx, MHIP_EINVAL, "attention_host: null bias operand");
+    if (h.bins_1d < 4 || h.bins_1d % 4 || h.bins_2d < 4 || h.bins_2d % 4 || h.max_1d <= h.bins_1d / 4 || h.max_2d <= h.bins_2d / 4 ||
+        h.dp < 0 || h.dx < 0 || h.dp > 65536 || h.dx > 65536)
+      return mhip_fail(ctx, MHIP_EINVAL, "attention_host: bad bias arguments");
+    // a code outside its table would be read outside it: pos | x << 12 | y << 22, a masked key's pos = 2 dp + 1
+    qcode.resize(Rq); kcode.resize(Rk);
+    auto pack = [&](const int32_t* c, bool valid, uint32_t* dst) {
+      if (c[0] < 0 || c[0] > h.dp || c[1] < 0 || c[1] > h.dx || c[2] < 0 || c[2] > h.dx) return false;
+      *dst = (valid ? (uint32_t)c[0] : (uint32_t)(2 * h.dp + 1)) | ((uint32_t)c[1] << 12) | ((uint32_t)c[2] << 22);
+      return true;
+    };
+    for (size_t r = 0; r < Rq; ++r)
+      if (!pack(h.qcode + 3 * r, true, &qcode[r])) return mhip_fail(ctx, MHIP_EINVAL, "attention_host: code of query row %zu outside [0, dp] / [0, dx]", r);
+    for (size_t r = 0; r < Rk; ++r)
+      if (!pack(h.kcode + 4 * r, h.kcode[4 * r + 3] != 0, &kcode[r])) return mhip_fail(ctx, MHIP_EINVAL, "attention_host: code of key row %zu outside [0, dp] / [0, dx]", r);
+    tab.resize(D / 64 * mhip_attn_bias_table_len(h.dp, h.dx));
+    mhip_attn_bias_fold(h.w1, h.wx, h.wy, h.heads, h.bins_1d, h.max_1d, h.bins_2d, h.max_2d, h.dp, h.dx, ATTN_SCORE_SCALE, tab.data());
+  }
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  // operands in the element type: q | k rows of pitch 2 D (fused) or q rows then k rows of pitch D (split); V^T as it came
+  const bool fused = h.layout == MHIP_ATTN_LAYOUT_FUSED;
+  const size_t ldq = fused ? 2 * D : D, koff = fused ? D : Rq * D;
+  std::vector<char> qk((Rq + Rk) * D * es), vt(nvt * es);
+  auto put = [&](char* dst, size_t at, float val) {
+    if (es == 2) ((_Float16*)dst)[at] = (_Float16)val; else ((float*)dst)[at] = val;
+  };
+  for (size_t r = 0; r < Rq; ++r)
+    for (size_t d = 0; d < D; ++d) put(qk.data(), r * ldq + d, h.q[r * D + d]);
+  for (size_t r = 0; r < Rk; ++r)
+    for (size_t d = 0; d < D; ++d) put(qk.data(), koff + r * ldq + d, h.k[r * D + d]);
+  for (size_t i = 0; i < nvt; ++i) put(vt.data(), i, h.vt[i]);
+  const size_t out_bytes = Rq * D * es;
+  char *dqk = nullptr, *dvt = nullptr, *dao = nullptr;
+  uint32_t *dqc = nullptr, *dkc = nullptr;
+  float* dtab = nullptr;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
+    dqk = ws.take(qk.size()); dvt = ws.take(vt.size()); dao = ws.take(out_bytes);
+    dqc = ws.take<uint32_t>(qcode.size() * 4); dkc = ws.take<uint32_t>(kcode.size() * 4);
+    dtab = ws.take<float>(tab.size() * 4);
+  });
+  if (rc) return rc;
+  MHIP_HIP(ctx, hipMemcpyAsync(dqk, qk.data(), qk.size(), hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(dvt, vt.data(), vt.size(), hipMemcpyHostToDevice, ctx->stream));
+  if (biased) {
+    MHIP_HIP(ctx, hipMemcpyAsync(dqc, qcode.data(), qcode.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    MHIP_HIP(ctx, hipMemcpyAsync(dkc, kcode.data(), kcode.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    MHIP_HIP(ctx, hipMemcpyAsync(dtab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  }
+  MHIP_HIP(ctx, hipMemsetAsync(dao, 0xff, out_bytes, ctx->stream));
+  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the sources are host temporaries in pageable memory
+  AttnBiasDesc ad;
+  if (fused) {
+    ad.a = encoder_attn_desc(dqk, dvt, dao, (int)D, es, h.images, h.heads, h.npad_k, h.n_keys);
+    ad.a.n_queries = h.n_queries;
+  } else {
+    ad.a.q = dqk; ad.a.k = dqk + koff * es; ad.a.vt = dvt; ad.a.out = dao;
+    ad.a.ldq = ad.a.ldk = ad.a.ldo = (int)D; ad.a.ldv = h.images * h.npad_k;
+    ad.a.images = h.images; ad.a.heads = h.heads; ad.a.npad_q = h.npad_q; ad.a.npad_k = h.npad_k;
+    ad.a.n_queries = h.n_queries; ad.a.n_keys = h.n_keys;
+  }
+  ad.qcode = dqc; ad.kcode = dkc; ad.tab = dtab; ad.dp = h.dp; ad.dx = h.dx;
+  if ((rc = biased ? mhip_launch_attention_bias(ctx, h.precision, ad) : mhip_launch_attention(ctx, h.precision, ad.a))) return rc;
+  MHIP_HIP(ctx, hipMemcpyAsync(h.out, dao, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return MHIP_OK;
+}
+
+// The biased kernel at the model's layout: one image of ceil8(n_tok) rows, zero padding and slack, the padding keys masked, dp / dx
+// the largest position / coordinate.  A wrapper of mhip_attention_host.
 extern "C" int mhip_attention_bias_host(mhip_ctx* ctx, int precision, int heads, int n_tok, const float* q, const float* k,
                                         const float* v, const int32_t* pos, const int32_t* x, const int32_t* y,
                                         const int32_t* valid, const float* w1, const float* wx, const float* wy, int bins_1d,
@@ -671,49 +763,31 @@ extern "C" int mhip_attention_bias_host(mhip_ctx* ctx, int precision, int heads,
     dp = std::max(dp, pos[i]);
     dx = std::max(dx, std::max(x[i], y[i]));
   }
-  MHIP_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t es = precision == MHIP_PREC_F16 ? 2 : 4, D = (size_t)heads * 64, NP = ((size_t)n_tok + 7) / 8 * 8;
-  const int tl = mhip_attn_bias_table_len(dp, dx);
-  // operands in the element type and with the pitches the model uses: q | k rows, V^T, zero slack
-  std::vector<char> qk((NP + ATTN_SLACK_ROWS) * 2 * D * es, 0), vt((D * NP + ATTN_SLACK_ROWS) * es, 0);
-  auto put = [&](char* dst, size_t at, float val) {
-    if (es == 2) ((_Float16*)dst)[at] = (_Float16)val; else ((float*)dst)[at] = val;
-  };
+  const size_t D = (size_t)heads * 64, NP = ((size_t)n_tok + 7) / 8 * 8, R = NP + ATTN_SLACK_ROWS;
+  std::vector<float> hq(R * D, 0.f), hk(R * D, 0.f), hvt(D * NP + ATTN_SLACK_ROWS, 0.f);
   for (size_t t = 0; t < (size_t)n_tok; ++t)
     for (size_t d = 0; d < D; ++d) {
-      put(qk.data(), t * 2 * D + d, q[t * D + d] * ATTN_SCORE_SCALE);
-      put(qk.data(), t * 2 * D + D + d, k[t * D + d]);
-      put(vt.data(), d * NP + t, v[t * D + d]);
+      hq[t * D + d] = q[t * D + d] * ATTN_SCORE_SCALE;
+      hk[t * D + d] = k[t * D + d];
+      hvt[d * NP + t] = v[t * D + d];
     }
-  std::vector<uint32_t> qcode(NP + ATTN_SLACK_ROWS, 0), kcode(NP + ATTN_SLACK_ROWS, (uint32_t)(2 * dp + 1));
+  std::vector<int32_t> qcode(R * 3, 0), kcode(R * 4, 0);      // rows behind the tokens: code 0, masked as keys
   for (int t = 0; t < n_tok; ++t) {
-    const uint32_t xy = ((uint32_t)x[t] << 12) | ((uint32_t)y[t] << 22);
-    qcode[t] = (uint32_t)pos[t] | xy;
-    kcode[t] = (valid[t] ? (uint32_t)pos[t] : (uint32_t)(2 * dp + 1)) | xy;
+    qcode[3 * t] = kcode[4 * t] = pos[t];
+    qcode[3 * t + 1] = kcode[4 * t + 1] = x[t];
+    qcode[3 * t + 2] = kcode[4 * t + 2] = y[t];
+    kcode[4 * t + 3] = valid[t] != 0;
   }
-  std::vector<float> tab((size_t)heads * tl);
-  mhip_attn_bias_fold(w1, wx, wy, heads, bins_1d, max_1d, bins_2d, max_2d, dp, dx, ATTN_SCORE_SCALE, tab.data());
-  char *dqk = nullptr, *dvt = nullptr, *dao = nullptr;
-  uint32_t *dqc = nullptr, *dkc = nullptr;
-  float *dtab = nullptr, *dout = nullptr;
-  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
-    dqk = ws.take(qk.size()); dvt = ws.take(vt.size()); dao = ws.take(NP * D * es);
-    dqc = ws.take<uint32_t>(qcode.size() * 4); dkc = ws.take<uint32_t>(kcode.size() * 4);
-    dtab = ws.take<float>(tab.size() * 4); dout = ws.take<float>((size_t)n_tok * D * 4);
-  });
+  const bool is16 = precision == MHIP_PREC_F16;
+  std::vector<char> raw(R * D * (is16 ? 2 : 4));
+  mhip_attention_host_desc hd{};
+  hd.precision = precision; hd.layout = MHIP_ATTN_LAYOUT_FUSED;
+  hd.images = 1; hd.heads = heads; hd.n_queries = hd.n_keys = n_tok; hd.npad_q = hd.npad_k = (int)NP;
+  hd.q = hq.data(); hd.k = hk.data(); hd.vt = hvt.data(); hd.qcode = qcode.data(); hd.kcode = kcode.data();
+  hd.w1 = w1; hd.wx = wx; hd.wy = wy; hd.bins_1d = bins_1d; hd.max_1d = max_1d; hd.bins_2d = bins_2d; hd.max_2d = max_2d;
+  hd.dp = dp; hd.dx = dx; hd.out = raw.data();
+  const int rc = mhip_attention_host(ctx, &hd);
   if (rc) return rc;
-  MHIP_HIP(ctx, hipMemcpyAsync(dqk, qk.data(), qk.size(), hipMemcpyHostToDevice, ctx->stream));
-  MHIP_HIP(ctx, hipMemcpyAsync(dvt, vt.data(), vt.size(), hipMemcpyHostToDevice, ctx->stream));
-  MHIP_HIP(ctx, hipMemcpyAsync(dqc, qcode.data(), qcode.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-  MHIP_HIP(ctx, hipMemcpyAsync(dkc, kcode.data(), kcode.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-  MHIP_HIP(ctx, hipMemcpyAsync(dtab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the sources are host temporaries in pageable memory
-  AttnBiasDesc ad;
-  ad.a = encoder_attn_desc(dqk, dvt, dao, (int)D, es, 1, heads, (int)NP, n_tok);
-  ad.qcode = dqc; ad.kcode = dkc; ad.tab = dtab; ad.dp = dp; ad.dx = dx;
-  if ((rc = mhip_launch_attention_bias(ctx, precision, ad))) return rc;
-  if ((rc = mhip_launch_convert_rows(ctx, precision, dao, dout, n_tok, (int)D))) return rc;
-  MHIP_HIP(ctx, hipMemcpyAsync(out, dout, (size_t)n_tok * D * 4, hipMemcpyDeviceToHost, ctx->stream));
-  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (size_t i = 0; i < (size_t)n_tok * D; ++i) out[i] = is16 ? (float)((const _Float16*)raw.data())[i] : ((const float*)raw.data())[i];
   return MHIP_OK;
 }

@@ -14,7 +14,7 @@ from typing import Dict, Optional, Sequence
 
 import numpy as np
 
-from ._lib import PREC_F16, Context, CropDesc, LayoutLMv3Config, ModelHandle, check, load
+from ._lib import PREC_F16, AttentionHostDesc, Context, CropDesc, LayoutLMv3Config, ModelHandle, check, load
 
 # the Pillow filters of the page resize (MHIP_PIL_* of include/marie_hip.h = PIL.Image.LANCZOS / BILINEAR / BICUBIC)
 PIL_LANCZOS, PIL_BILINEAR, PIL_BICUBIC = 1, 2, 3
@@ -203,4 +203,37 @@ def attention_bias_host(ctx: Context, precision: int, q, k, v, pos, x, y, valid,
                                                   _vp(x), _vp(y), _vp(valid), _vp(w1), _vp(wx), _vp(wy), w1.shape[1],
                                                   int(max_1d), wx.shape[1], int(max_2d), _vp(out)),
           "mhip_attention_bias_host")
+    return out
+
+
+ATTN_SLACK_ROWS = 128          # MHIP_ATTN_SLACK_ROWS
+ATTN_LAYOUT_FUSED, ATTN_LAYOUT_SPLIT = 0, 1
+
+
+def attention_host(ctx: Context, precision: int, layout: int, images: int, heads: int, n_queries: int, n_keys: int, npad_q: int,
+                   npad_k: int, q, k, vt, bias: Optional[dict] = None) -> np.ndarray:
+    """One launch of the plain or biased attention kernel with the whole descriptor in the caller's hands
+    (``mhip_attention_host``).  q (images * npad_q + 128, heads * 64), k (images * npad_k + 128, heads * 64) and vt
+    (heads * 64 * images * npad_k + 128,) fp32, every padding and slack row the caller's; ``bias``: qcode (rows, 3) and kcode
+    (rows, 4) int32, w1 / wx / wy, max_1d, max_2d, dp, dx.  -> the device's whole output (images * npad_q + 128, heads * 64) in
+    the element type (float16 / float32), pre-filled with the byte 0xff."""
+    q, k, vt = (np.ascontiguousarray(a, np.float32) for a in (q, k, vt))
+    D = max(int(heads), 0) * 64
+    rq, rk = max(int(images) * int(npad_q), 0) + ATTN_SLACK_ROWS, max(int(images) * int(npad_k), 0) + ATTN_SLACK_ROWS
+    if q.size != rq * D or k.size != rk * D or vt.size != D * (rk - ATTN_SLACK_ROWS) + ATTN_SLACK_ROWS:
+        raise ValueError("attention_host: q / k / vt do not have the rows the descriptor names")
+    out = np.zeros((rq, D), np.float16 if int(precision) == PREC_F16 else np.float32)
+    d = AttentionHostDesc(precision=int(precision), layout=int(layout), images=int(images), heads=int(heads), n_queries=int(n_queries),
+                          n_keys=int(n_keys), npad_q=int(npad_q), npad_k=int(npad_k), q=_vp(q), k=_vp(k), vt=_vp(vt), out=_vp(out))
+    keep = []
+    if bias is not None:
+        qc, kc = np.ascontiguousarray(bias["qcode"], np.int32), np.ascontiguousarray(bias["kcode"], np.int32)
+        w1, wx, wy = (np.ascontiguousarray(bias[n], np.float32) for n in ("w1", "wx", "wy"))
+        if qc.shape != (rq, 3) or kc.shape != (rk, 4) or w1.shape[0] != heads or wx.shape != wy.shape or wx.shape[0] != heads:
+            raise ValueError("attention_host: bias operands do not have the rows the descriptor names")
+        keep = [qc, kc, w1, wx, wy]
+        d.qcode, d.kcode, d.w1, d.wx, d.wy = (_vp(a) for a in keep)
+        d.bins_1d, d.bins_2d = w1.shape[1], wx.shape[1]
+        d.max_1d, d.max_2d, d.dp, d.dx = (int(bias[n]) for n in ("max_1d", "max_2d", "dp", "dx"))
+    check(ctx.h, ctx.lib.mhip_attention_host(ctx.h, C.byref(d)), "mhip_attention_host")
     return out
