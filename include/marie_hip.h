@@ -966,9 +966,11 @@ int mhip_cliptext_head_host(mhip_ctx* ctx, const float* h, int B, int npad, int 
  * jina_embeddings.py, jina-embeddings-v2-base-en): BertModel without the pooler — or JinaBERT: no position table, the symmetric
  * ALiBi bias -slope_h |i - j| on the scores, a gated GELU MLP — then masked mean (or [CLS]) pooling and, where asked for, L2
  * normalisation.  Token ids come from the caller (marie_icr_amd/wordpiece_tokenizer.py): int32 [B][npad], npad a multiple of 8 up
- * to 128 (the keys of a text are held in LDS), the same for every text of a call; len[b] in [1, npad] is text b's token count
- * ([CLS] .. [SEP]), the rows after it carry the [PAD] id.  A text's embedding does not depend on the other texts of the call or on
- * npad, bit for bit.  Post-LN layers, fp32 [dim] out.                                                                          */
+ * to 8192 (ALiBi) or to the position table's rows, whichever is less, the same for every text of a call; len[b] in [1, npad] is
+ * text b's token count ([CLS] .. [SEP]), the rows after it carry the [PAD] id.  Calls of npad <= 128 hold a text's keys in LDS
+ * (attn_short); longer ones stream them in blocks of 128 under an online soft-max (attn_long).  On each side of that boundary a
+ * text's embedding does not depend on the other texts of the call or on npad, bit for bit.  A call lays out at most
+ * 4096 * 128 = 524288 rows (B * npad).  Post-LN layers, fp32 [dim] out.                                                        */
 typedef struct mhip_berttext mhip_berttext;
 typedef struct mhip_berttext_config {
   int vocab;               /* 30522                                                                                       */
@@ -1003,8 +1005,8 @@ size_t mhip_berttext_workspace_bytes(mhip_berttext* m, int B, int npad);
 /* the ALiBi slopes of `heads` heads, fp32 [heads]: 2^(-8 (i + 1) / n) for n a power of two; otherwise those of the largest power
  * of two p <= n, then the even-indexed slopes of 2 p, the first n - p of them.  Host only, no ctx                              */
 int mhip_berttext_alibi_slopes(int heads, float* slopes_out);
-/* B texts (1 .. 4096) -> emb_out fp32 [B][dim].  MHIP_EINVAL, never a clamp: npad no multiple of 8 or above 128 (or above the
- * position table rounded up to 8), a len outside [1, npad], an id outside [0, vocab)                                          */
+/* B texts (1 .. 4096) -> emb_out fp32 [B][dim].  MHIP_EINVAL, never a clamp: npad no multiple of 8 or above 8192 (or above the
+ * position table rounded up to 8), more than 524288 rows (B * npad), a len outside [1, npad], an id outside [0, vocab)        */
 int mhip_berttext_embed_host(mhip_berttext* m, const int32_t* ids, const int32_t* len, int B, int npad, float* emb_out);
 /* the texts through the encoder once, then cos_out[p] = x.y / max(|x| |y|, 1e-8) of the embeddings of texts pair_a[p], pair_b[p]
  * (fp32 [n_pairs]); emb_out fp32 [B][dim] or NULL                                                                             */
@@ -1023,6 +1025,10 @@ int mhip_berttext_embed_rows_host(mhip_ctx* ctx, const float* word, const float*
  * type and laid out as the encoder lays them out (q | k rows, V^T) -> out fp32, same shape                                    */
 int mhip_berttext_attention_host(mhip_ctx* ctx, int precision, const float* q, const float* k, const float* v, const int32_t* len,
                                  const float* slopes, int B, int heads, int head_dim, int npad, float* out);
+/* the same through the streamed kernel (attn_long): npad a multiple of 8, 8 .. 8192 (128 and fewer rows too: one key block through
+ * the streamed code), at most 524288 rows (B * npad).  mhip_berttext_attention_host keeps its limit of 128 rows                 */
+int mhip_berttext_attention_long_host(mhip_ctx* ctx, int precision, const float* q, const float* k, const float* v,
+                                      const int32_t* len, const float* slopes, int B, int heads, int head_dim, int npad, float* out);
 /* x fp32 [R][2 F], rounded to the precision's element type -> out fp32 [R][F] = gelu_erf(x[:, :F]) * x[:, F:]                 */
 int mhip_berttext_geglu_host(mhip_ctx* ctx, int precision, const float* x, int R, int F, float* out);
 /* h fp32 [B][npad][D], len [B] -> emb_out fp32 [B][D]: mode 0 the mean of rows < len[b], 1 row 0; normalize 0 / 1            */

@@ -220,6 +220,7 @@ _SIGNATURES = (
     ("mhip_berttext_debug_taps_host", _i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     ("mhip_berttext_embed_rows_host", _i, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp, _i, _i, _i, _i, _vp]),
     ("mhip_berttext_attention_host", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    ("mhip_berttext_attention_long_host", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     ("mhip_berttext_geglu_host", _i, [_vp, _i, _vp, _i, _i, _vp]),
     ("mhip_berttext_pool_host", _i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     ("mhip_layoutreader_create", _i, [_vp, _i, _vp, C.POINTER(_vp)]),

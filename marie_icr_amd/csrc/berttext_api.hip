@@ -10,7 +10,8 @@
 // Row layout: every text owns `npad` rows (a multiple of 8, the same for the whole call) of which its first len[b] are its
 // tokens; the rest carry the [PAD] id, are computed like any other row and are never a key.  The residual stream h is fp32.  The
 // layers are LayoutLMv3's (post-LN: attention, ao GEMM + residual, LayerNorm, fc1, fc2 + residual, LayerNorm) with attn_short as
-// the attention.  The word table stays fp32 in both precision modes: it is a gather of B * npad rows, not a GEMM operand.
+// the attention of calls of npad <= 128 and attn_long, which streams the keys, past that (at most 8192 rows a text and 4096 * 128
+// rows a call).  The word table stays fp32 in both precision modes: it is a gather of B * npad rows, not a GEMM operand.
 #include <math.h>
 
 #include "encoder_block.h"
@@ -28,14 +29,16 @@ struct mhip_berttext {
   int head_dim() const { return cfg.dim / cfg.heads; }
   bool alibi() const { return cfg.position == BT_POS_ALIBI; }
   bool geglu() const { return cfg.mlp == BT_MLP_GEGLU; }
-  // tokens of a text: the LDS-resident attention's 128, or the position table's rows when it has fewer
-  int max_tokens() const { return alibi() ? 128 : std::min(cfg.max_position, 128); }
+  // tokens of a text: the streamed attention's 8192, or the position table's rows when it has fewer
+  int max_tokens() const { return alibi() ? 8192 : std::min(cfg.max_position, 8192); }
   int max_npad() const { return (max_tokens() + 7) / 8 * 8; }
 };
 
 namespace {
 
-constexpr int MAX_TEXTS = 4096, MAX_ROWS = 128;
+constexpr int MAX_TEXTS = 4096, MAX_ROWS = 128;      // MAX_ROWS: the LDS-resident attention's, the routing boundary
+constexpr int MAX_LONG_ROWS = 8192;                   // the streamed attention's
+constexpr long long MAX_CALL_ROWS = (long long)MAX_TEXTS * MAX_ROWS;      // B * npad of one call: the most this path has laid out
 constexpr double LOG2E = 1.4426950408889634;
 
 // the buffers of one call of B texts (and n_pairs cosines)
@@ -87,6 +90,8 @@ int berttext_check_call(mhip_berttext* m, const int32_t* ids, const int32_t* len
   if (!ids || !len || B < 1 || B > MAX_TEXTS) return mhip_fail(ctx, MHIP_EINVAL, "berttext: bad arguments (%d texts; 1 .. %d)", B, MAX_TEXTS);
   if (!npad_ok(npad, m->max_npad()))
     return mhip_fail(ctx, MHIP_EINVAL, "berttext: %d rows a text (a multiple of 8 up to %d)", npad, m->max_npad());
+  if ((long long)B * npad > MAX_CALL_ROWS)
+    return mhip_fail(ctx, MHIP_EINVAL, "berttext: %d texts of %d rows are %lld rows, a call lays out at most %lld", B, npad, (long long)B * npad, MAX_CALL_ROWS);
   for (int b = 0; b < B; ++b)
     if (len[b] < 1 || len[b] > npad || len[b] > m->max_tokens())
       return mhip_fail(ctx, MHIP_EINVAL, "berttext: text %d has %d tokens (1 .. %d)", b, len[b], std::min(npad, m->max_tokens()));
@@ -285,7 +290,7 @@ extern "C" int mhip_berttext_finalize(mhip_berttext* m) {
 }
 
 extern "C" size_t mhip_berttext_workspace_bytes(mhip_berttext* m, int B, int npad) {
-  if (!m || B < 1 || B > MAX_TEXTS || !npad_ok(npad, m->max_npad())) return 0;
+  if (!m || B < 1 || B > MAX_TEXTS || !npad_ok(npad, m->max_npad()) || (long long)B * npad > MAX_CALL_ROWS) return 0;
   BertRun run;
   return mhip_layout_bytes([&](Carver& ws) { berttext_carve(m, ws, B, npad, 0, &run); });
 }
@@ -374,12 +379,14 @@ extern "C" int mhip_berttext_embed_rows_host(mhip_ctx* ctx, const float* word, c
   return MHIP_OK;
 }
 
-extern "C" int mhip_berttext_attention_host(mhip_ctx* ctx, int precision, const float* q, const float* k, const float* v, const int32_t* len,
-                                            const float* slopes, int B, int heads, int head_dim, int npad, float* out) {
+// the one body of the two attention entries: attn_short (npad <= 128) or, streamed, attn_long (npad <= 8192)
+static int berttext_attention_run(mhip_ctx* ctx, int precision, const float* q, const float* k, const float* v, const int32_t* len,
+                                  const float* slopes, int B, int heads, int head_dim, int npad, float* out, bool streamed) {
   if (!ctx || !q || !k || !v || !len || !out) return MHIP_EINVAL;
   if (precision != MHIP_PREC_F16 && precision != MHIP_PREC_F32) return mhip_fail(ctx, MHIP_EINVAL, "unknown precision %d", precision);
   if (head_dim != 64 && head_dim != 32) return mhip_fail(ctx, MHIP_EINVAL, "berttext_attention: head_dim %d (64 or 32)", head_dim);
-  if (B < 1 || B > MAX_TEXTS || heads < 1 || heads > 32 || (heads * head_dim) % 64 || !npad_ok(npad, MAX_ROWS))
+  if (B < 1 || B > MAX_TEXTS || heads < 1 || heads > 32 || (heads * head_dim) % 64 || !npad_ok(npad, streamed ? MAX_LONG_ROWS : MAX_ROWS) ||
+      (long long)B * npad > MAX_CALL_ROWS)
     return mhip_fail(ctx, MHIP_EINVAL, "berttext_attention: B=%d heads=%d npad=%d", B, heads, npad);
   for (int b = 0; b < B; ++b)
     if (len[b] < 1 || len[b] > npad) return mhip_fail(ctx, MHIP_EINVAL, "berttext_attention: sequence %d has %d keys (1 .. %d)", b, len[b], npad);
@@ -411,11 +418,22 @@ extern "C" int mhip_berttext_attention_host(mhip_ctx* ctx, int precision, const 
   AttnShortDesc sd;
   sd.a = encoder_attn_desc(w.qk, w.vt, w.ao, (int)D, es, B, heads, npad, npad);
   sd.len = dlen; sd.slopes = slopes ? dsl : nullptr; sd.head_dim = head_dim;
-  if ((rc = mhip_launch_attention_short(ctx, precision, sd))) return rc;
+  if ((rc = streamed ? mhip_launch_attention_long(ctx, precision, sd) : mhip_launch_attention_short(ctx, precision, sd))) return rc;
   if ((rc = mhip_launch_convert_rows(ctx, precision, w.ao, dout, (int)R, (int)D))) return rc;
   MHIP_HIP(ctx, hipMemcpyAsync(out, dout, R * D * 4, hipMemcpyDeviceToHost, ctx->stream));
   MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return MHIP_OK;
+}
+
+extern "C" int mhip_berttext_attention_host(mhip_ctx* ctx, int precision, const float* q, const float* k, const float* v, const int32_t* len,
+                                            const float* slopes, int B, int heads, int head_dim, int npad, float* out) {
+  return berttext_attention_run(ctx, precision, q, k, v, len, slopes, B, heads, head_dim, npad, out, false);
+}
+
+extern "C" int mhip_berttext_attention_long_host(mhip_ctx* ctx, int precision, const float* q, const float* k, const float* v,
+                                                 const int32_t* len, const float* slopes, int B, int heads, int head_dim, int npad,
+                                                 float* out) {
+  return berttext_attention_run(ctx, precision, q, k, v, len, slopes, B, heads, head_dim, npad, out, true);
 }
 
 extern "C" int mhip_berttext_geglu_host(mhip_ctx* ctx, int precision, const float* x, int R, int F, float* out) {

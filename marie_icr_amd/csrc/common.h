@@ -54,7 +54,9 @@ enum MhipKernelId {
   MHIP_K_ATTN_CAUSAL = 30,       // causal soft-max attention, one workgroup per (sequence, head), K / V^T held in LDS
   MHIP_K_LEV_NGRAMS = 31,      // edit distance of every (template text, page n-gram) pair (lev_ngrams.hip)
   // BERT sentence encoders (berttext_ops.hip)
-  MHIP_K_ATTN_SHORT = 32,        // bidirectional soft-max attention over sequences of their own length (<= 128), optional ALiBi, head dim 64 / 32
+  MHIP_K_ATTN_SHORT = 32,        // bidirectional soft-max attention over sequences of their own length, optional ALiBi, head dim 64 / 32:
+                                 // attn_short (<= 128 rows, keys held in LDS) and attn_long (<= 8192 rows, keys streamed in blocks of
+                                 // 128, online soft-max) share the slot, as the post-LayerNorms share berttext_embed
   MHIP_K_BERTTEXT_EMBED = 33,    // word + type + position rows -> LayerNorm -> fp32 stream; the post-LayerNorms of the layers
                                  // (LayoutReader's row LayerNorms go through mhip_launch_berttext_layernorm and are counted here)
   MHIP_K_GEGLU = 34,             // gelu(x[:, :F]) * x[:, F:]
@@ -635,6 +637,11 @@ struct AttnShortDesc {
   int head_dim = 64;
 };
 int mhip_launch_attention_short(mhip_ctx* ctx, int precision, const AttnShortDesc& d);
+// the same attention with the keys streamed through LDS in blocks of 128 and an online soft-max: npad_q == npad_k, a multiple of 8,
+// 8 .. 8192 (128 rows and fewer are taken too: one block through the streamed code).  One workgroup per (sequence, head, 64
+// queries); a sequence's key walk is a function of len[b] alone, every row < npad is written (query blocks that start at or past
+// len[b] as zeros), nothing past a sequence's rows is read (no slack needed).  Counted in MHIP_K_ATTN_SHORT
+int mhip_launch_attention_long(mhip_ctx* ctx, int precision, const AttnShortDesc& d);
 // h [B*npad][D] fp32 = LN((word[ids[row]] + type0) + pos[row % npad]), ht (null: not written) its copy in the precision's element
 // type; word [vocab][D], type0 [D], pos [>= npad][D] or null (no position table) fp32; the ids are the caller's to check
 int mhip_launch_berttext_embed(mhip_ctx* ctx, int precision, const float* word, const float* type0, const float* pos, const float* g,

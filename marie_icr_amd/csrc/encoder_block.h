@@ -152,7 +152,9 @@ inline int encoder_block_attention(mhip_ctx* ctx, int prec, const Arena& a, int 
 }
 inline int encoder_block_attention(mhip_ctx* ctx, int prec, const Arena& a, int i, const EncoderWs& w, const AttnShortDesc& sd) {
   const int rc = encoder_block_qkv(ctx, prec, a, i, w, sd.a);
-  return rc ? rc : mhip_launch_attention_short(ctx, prec, sd);
+  if (rc) return rc;
+  // up to 128 rows a sequence the keys stay in LDS; past that they are streamed
+  return sd.a.npad_k <= 128 ? mhip_launch_attention_short(ctx, prec, sd) : mhip_launch_attention_long(ctx, prec, sd);
 }
 
 // The layers of a CLIP tower (vision: AttnDesc, text: AttnCausalDesc) on the fp32 stream h [R][D]:

@@ -19,9 +19,11 @@ towers (RN50, RN101, RN50x4 — the reference's default snippet model) have a lo
 
 The sentence encoders (marie/embeddings/sentence_transformers/sentence_transformers_embeddings.py, marie/embeddings/jina/
 jina_embeddings.py) are at the end of the file: Hugging Face BERT (all-MiniLM-L6-v2) and JinaBERT (ALiBi, GEGLU) with masked mean
-or [CLS] pooling in HIP (csrc/berttext_api.hip, ``mhip_berttext_*``), WordPiece on the host (wordpiece_tokenizer.py).  A text is
-at most 128 tokens here (the attention kernel holds a text's keys in LDS): the reference's models take 256 (MiniLM) and 8192
-(Jina).  A longer text raises ``ValueError`` unless ``truncation=True`` cuts it to ``min(model limit, 128)`` tokens.
+or [CLS] pooling in HIP (csrc/berttext_api.hip, ``mhip_berttext_*``), WordPiece on the host (wordpiece_tokenizer.py).  A text
+takes its model's own limit, as in the reference: 256 tokens (MiniLM's ``max_seq_length``), 8192 (Jina), never more than the
+position table has rows.  Texts of at most 128 tokens run through the attention kernel that holds a text's keys in LDS, longer
+ones through the one that streams them; the two never share an encoder call.  A text past the limit raises ``ValueError`` unless
+``truncation=True`` cuts it to ``max_tokens`` tokens.
 """
 from __future__ import annotations
 
@@ -839,7 +841,10 @@ class OpenAIResNetEmbeddings(ClipImageEmbeddings):
 
 
 # ---------------------------------------------------------------------------------------------------- BERT sentence encoders
-BERT_MAX_TOKENS = 128      # tokens of a text, [CLS] and [SEP] included: attn_short holds a text's keys in LDS
+BERT_MAX_TOKENS = 128      # the LDS-resident attention's limit ([CLS] and [SEP] included): the routing boundary, past which
+                           # a call streams a text's keys (attn_long)
+BERT_LONG_MAX_TOKENS = 8192      # tokens of a text: the streamed attention's limit
+BERT_MAX_CALL_ROWS = 4096 * 128  # rows (texts x npad) one encoder call lays out at most
 POS_ABSOLUTE, POS_ALIBI = 0, 1
 MLP_GELU, MLP_GEGLU = 0, 1
 POOL_MEAN, POOL_CLS = 0, 1
@@ -1011,9 +1016,7 @@ class BertTextModel(ModelHandle):
 
 
 # ---- the kernels on host arrays (what tests/test_berttext_gpu.py drives)
-def short_attention_host(ctx: Context, precision: int, q, k, v, lens, heads: int, slopes=None) -> np.ndarray:
-    """q, k, v fp32 (B, npad, heads * head_dim), q already scaled by head_dim^-0.5 * log2(e), lens int32 (B,), slopes fp32
-    (heads,) in the same log2 units or None -> fp32, same shape"""
+def _attention_host(entry: str, ctx: Context, precision: int, q, k, v, lens, heads: int, slopes) -> np.ndarray:
     q, k, v = (np.ascontiguousarray(a, np.float32) for a in (q, k, v))
     lens = np.ascontiguousarray(lens, np.int32).reshape(-1)
     B, npad, D = q.shape
@@ -1025,9 +1028,21 @@ def short_attention_host(ctx: Context, precision: int, q, k, v, lens, heads: int
         if slopes.shape[0] != heads:
             raise ValueError(f"{heads} slopes expected, got {slopes.shape[0]}")
     out = np.empty_like(q)
-    check(ctx.h, ctx.lib.mhip_berttext_attention_host(ctx.h, int(precision), _vp(q), _vp(k), _vp(v), _vp(lens), _vp(slopes), B,
-                                                      int(heads), D // heads, npad, _vp(out)), "mhip_berttext_attention_host")
+    check(ctx.h, getattr(ctx.lib, entry)(ctx.h, int(precision), _vp(q), _vp(k), _vp(v), _vp(lens), _vp(slopes), B,
+                                         int(heads), D // heads, npad, _vp(out)), entry)
     return out
+
+
+def short_attention_host(ctx: Context, precision: int, q, k, v, lens, heads: int, slopes=None) -> np.ndarray:
+    """q, k, v fp32 (B, npad, heads * head_dim), q already scaled by head_dim^-0.5 * log2(e), lens int32 (B,), slopes fp32
+    (heads,) in the same log2 units or None -> fp32, same shape.  ``attn_short``: npad is at most 128"""
+    return _attention_host("mhip_berttext_attention_host", ctx, precision, q, k, v, lens, heads, slopes)
+
+
+def long_attention_host(ctx: Context, precision: int, q, k, v, lens, heads: int, slopes=None) -> np.ndarray:
+    """the same through the streamed kernel (``attn_long``): npad a multiple of 8 up to 8192, 128 rows and fewer included; the
+    rows of 64-query blocks that start at or past a sequence's length come back as zeros"""
+    return _attention_host("mhip_berttext_attention_long_host", ctx, precision, q, k, v, lens, heads, slopes)
 
 
 def bert_embed_rows_host(ctx: Context, word, type0, pos, g, b, ids, eps: float = 1e-12) -> np.ndarray:
@@ -1065,15 +1080,20 @@ def bert_pool_host(ctx: Context, h, lens, mode: int = POOL_MEAN, normalize: bool
     return out
 
 
-def plan_text_groups(lengths: Sequence[int], max_group: int, rows_budget: Optional[int] = None) -> List[Tuple[int, List[int]]]:
+def plan_text_groups(lengths: Sequence[int], max_group: int, rows_budget: Optional[int] = None, *,
+                     boundary: Optional[int] = None) -> List[Tuple[int, List[int]]]:
     """The calls of ``embed_texts``: the texts sorted by token count (ties in input order) and cut into groups of at most
     ``max_group`` texts — and, with ``rows_budget``, of at most that many rows — that share one ``npad``, the longest of the
-    group rounded up to 8 -> [(npad, [input indices])]"""
+    group rounded up to 8 -> [(npad, [input indices])].  With ``boundary`` no group holds both a text of at most ``boundary``
+    tokens and a longer one."""
     order = sorted(range(len(lengths)), key=lambda i: (lengths[i], i))
     groups: List[Tuple[int, List[int]]] = []
     at = 0
     while at < len(order):
         end = min(at + max_group, len(order))
+        if boundary is not None and lengths[order[at]] <= boundary:
+            while lengths[order[end - 1]] > boundary:      # sorted: the group's start is on the short side, cut where that ends
+                end -= 1
         npad = (lengths[order[end - 1]] + 7) // 8 * 8
         # a shorter group of the same start never needs more rows a text
         while rows_budget is not None and end - at > 1 and (end - at) * npad > rows_budget:
@@ -1136,7 +1156,7 @@ class BertTextEmbeddings(EmbeddingsBase):
         if cfg.position == POS_ABSOLUTE:
             limit = min(limit or cfg.max_position, cfg.max_position)
         self.max_seq_length = limit                                      # the model's own limit (None: none)
-        self.max_tokens = min(limit or BERT_MAX_TOKENS, BERT_MAX_TOKENS)   # this build's
+        self.max_tokens = min(limit or BERT_LONG_MAX_TOKENS, BERT_LONG_MAX_TOKENS)   # this build's
         if isinstance(precision, str):
             if precision not in ("f16", "f32"):
                 raise ValueError(f"precision {precision!r}: 'f16' or 'f32'")
@@ -1179,7 +1199,7 @@ class BertTextEmbeddings(EmbeddingsBase):
         for i, text in enumerate(texts):
             ids = self.tokenizer.encode(text, self.max_tokens if truncation else None)
             if len(ids) > self.max_tokens:
-                raise ValueError(f"text {i} is too long: {len(ids)} tokens, at most {self.max_tokens} are built "
+                raise ValueError(f"text {i} is too long: {len(ids)} tokens, the model takes at most {self.max_tokens} "
                                  f"(truncation=True cuts it)")
             out.append(ids)
         return out
@@ -1188,8 +1208,12 @@ class BertTextEmbeddings(EmbeddingsBase):
         chunk = min(int(chunk or self.TEXT_CHUNK), self.TEXT_CHUNK)
         if chunk < 1:
             raise ValueError(f"chunk of {chunk} texts")
-        per_row = self.text_model.workspace_bytes(8, BERT_MAX_TOKENS) // (8 * BERT_MAX_TOKENS)      # the workspace grows with the rows
-        return plan_text_groups(lengths, chunk, max(self.WORKSPACE_BUDGET // max(per_row, 1), BERT_MAX_TOKENS))
+        probe = min(BERT_MAX_TOKENS, (self.max_tokens + 7) // 8 * 8)
+        per_row = self.text_model.workspace_bytes(8, probe) // (8 * probe)      # the workspace grows with the rows
+        # at least one text of max_tokens; a text of at most BERT_MAX_TOKENS tokens never shares a call with a longer one, so it
+        # always runs through attn_short and its embedding does not depend on what it is embedded with
+        rows = max(self.WORKSPACE_BUDGET // max(per_row, 1), (self.max_tokens + 7) // 8 * 8)
+        return plan_text_groups(lengths, chunk, min(rows, BERT_MAX_CALL_ROWS), boundary=BERT_MAX_TOKENS)
 
     # -- the matcher's entries -------------------------------------------------------------------------------------------
     def embed_texts(self, texts: Sequence[str], truncation: bool = False, chunk: Optional[int] = None) -> np.ndarray:

@@ -1,8 +1,12 @@
 """Times the BERT sentence encoders (f16): python tools/time_text_embeddings.py [--texts 4096] [--repeats 7] [--shapes minilm jina]
+                                                                                  [--legs short long]
 
 Seeded random weights at the all-MiniLM-L6-v2 shape (384 / 12 heads of 32 / 6 layers / ffn 1536, position table, GELU, mean +
 normalize) and the jina-embeddings-v2-base-en shape (768 / 12 heads of 64 / 12 layers / ffn 3072, ALiBi, GEGLU, mean), a synthetic
-WordPiece vocabulary of one-piece words, `--texts` texts of 4 to 24 tokens ([CLS] and [SEP] included).  Per shape:
+WordPiece vocabulary of one-piece words.  The short leg: `--texts` texts of 4 to 24 tokens ([CLS] and [SEP] included), which run
+through attn_short.  The long leg (result key "long_shapes"): 256 texts of 200 to 256 tokens at the MiniLM shape and 64 texts of 400
+to 512 tokens at the jina shape, which run through the streamed attn_long (both kernels are counted in the profiler's `attn_short`
+slot; its share of the device time is reported as "attn_share").  Per shape and leg:
 
   * `embed_texts`: what `MetaTemplateMatcher.text_sims` calls — the host tokenizer, the length-bucketed groups, per group ids up,
     the encoder, the embeddings back, ending in a stream synchronise.  The same texts are embedded again and again, so the
@@ -37,6 +41,7 @@ SHAPES = {
     "jina": dict(vocab=30528, max_position=8192, type_vocab=2, dim=768, heads=12, depth=12, ffn=3072, eps=1e-12, position="alibi",
                  mlp="geglu", cls="JinaEmbeddings"),
 }
+LONG_LEG = {"minilm": (256, 200, 256), "jina": (64, 400, 512)}      # texts, fewest and most tokens of one
 
 
 # profiler slots 12 .. 16 (MHIP_K_IGEMM_T64 .. MHIP_K_IGEMM_PATCH) are conv_igemm by tile shape: their launches are also counted in
@@ -82,6 +87,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--window", type=float, default=0.5, help="least seconds of one timed window")
+    ap.add_argument("--legs", nargs="+", default=["short", "long"], choices=["short", "long"])
     args = ap.parse_args()
 
     import bert_text_ref as R
@@ -91,12 +97,20 @@ def main():
 
     ctx = Context(0)
     result = {"precision": "f16", "device": ctx.device_info(), "clocks": clocks(), "texts": args.texts, "tokens_per_text": [4, 24],
-              "shapes": {}}
+              "shapes": {}, "long_shapes": {}}
     words = [f"w{i}" for i in range(2000)]
     tok = WordPieceTokenizer(["[PAD]", "[UNK]", "[CLS]", "[SEP]", "[MASK]"] + words)
     rng = np.random.default_rng(0)
     texts = [" ".join(words[j] for j in rng.integers(0, len(words), c)) for c in rng.integers(2, 23, args.texts)]
+    legs = []
     for name in args.shapes:
+        if "short" in args.legs:
+            legs.append((name, "shapes", texts))
+        if "long" in args.legs:
+            n, lo, hi = LONG_LEG[name]
+            lrng = np.random.default_rng(1)
+            legs.append((name, "long_shapes", [" ".join(words[j] for j in lrng.integers(0, len(words), c)) for c in lrng.integers(lo - 2, hi - 1, n)]))
+    for name, leg, texts in legs:
         cfg = SHAPES[name]
         e = getattr(embeddings, cfg["cls"])(state=R.make_state(cfg, seed=0), config=R.config_json(cfg), tokenizer=tok, precision="f16", ctx=ctx)
         encoded = e.encode_texts(texts)
@@ -118,7 +132,8 @@ def main():
         prof = {k: round(v["total_ms"], 3) for k, v in ctx.profile_read().items() if v["launches"] and v["id"] not in IGEMM_TILE_SLOTS}
         ctx.profile_enable(False)
         emb = e.embed_texts(texts[:64])
-        result["shapes"][name] = {
+        result[leg][name] = {
+            "texts": len(texts),
             "dim_heads_depth_ffn": [cfg["dim"], cfg["heads"], cfg["depth"], cfg["ffn"]], "position": cfg["position"], "mlp": cfg["mlp"],
             "tokens": [min(lengths), max(lengths)], "calls": len(groups), "rows_per_text_by_call": [int(ids.shape[1]) for ids, _ in groups],
             "token_rows": int(rows), "tokens_total": int(sum(lengths)),
@@ -130,6 +145,7 @@ def main():
                                     "ms_min_max": [round(device[1] * 1e3, 3), round(device[2] * 1e3, 3)],
                                     "gemm_tflops": round(rows * gflop_per_row(cfg) / device[0] / 1e3, 2)},
             "device_ms_by_kernel_family": prof, "device_ms_total": round(sum(prof.values()), 3),
+            "attn_share": round(prof.get("attn_short", 0.0) / max(sum(prof.values()), 1e-9), 4),
             "finite": bool(np.isfinite(emb).all()), "largest_entry": round(float(np.abs(emb).max()), 3)}
         e.close()
     print(json.dumps(result))
