@@ -210,6 +210,48 @@ double mhip_crnn_kernel_flops(mhip_crnn* m, int kernel_id, int n, int w);
  *                                  comes back whole: a cell never written, or a write past row B, shows (f16 0xffff widens to NaN). */
 int mhip_lstm_rec_host(mhip_ctx* ctx, int precision, int B, int T, const float* whh, const float* xproj, float* out);
 
+/* ---- stage entries of the recognizer's non-GEMM kernels (csrc/icr_ops.hip) ------------------------------------------------
+ * One kernel each on host buffers, through the launcher the ICR model calls (its argument checks and grid choice included);
+ * no model, no weights beyond the arguments.  Conventions of all of them, and of the detector's below:
+ *   - activations are fp32 on the host; in the f16 mode they are narrowed to f16 on the way in and widened on the way out
+ *     (f16-representable values pass exactly).  Weights, scales, biases, scores and indices stay as they are.
+ *   - every output buffer holds MHIP_STAGE_GUARD elements behind the n the launch owns.  The device copy is filled with 0xff
+ *     bytes before the launch and comes back whole: a cell never written, or a write past the end, shows (f16 0xffff widens
+ *     to the fp32 NaN 0xffffe000).  A refused call writes nothing.                                                        */
+#define MHIP_STAGE_GUARD 4096   /* elements: one workgroup's output of the widest kernel (64 pixels x 64 channels) */
+/* replaces: nn.Conv2d(1, C, 3, 1, 1, bias=False) + BatchNorm2d (folded: scale, bias) + ReLU, transformation.py:52-53,
+ * feature_extraction.py:161-163.  img u8 [B][H][W] (normalised to [-1, 1] on the fly) or fp32 [B][H][W]; w9xC fp32 [9][C]
+ * (tap dy*3+dx major); out [B*H*W*64 + guard], NHWC with 64 channels, channels >= C zero. */
+int mhip_conv_gray_first_host(mhip_ctx* ctx, int precision, int in_is_u8, const void* img, int B, int H, int W, int C,
+                              const float* w9xC, const float* scale, const float* bias, float* out);
+/* replaces: nn.MaxPool2d(kernel_size=2, stride=(2, 1), padding=(0, 1)), feature_extraction.py:180.
+ * in [B][H][W][C] -> out [B][H/2][W+1][C] + guard */
+int mhip_maxpool_s21_p01_host(mhip_ctx* ctx, int precision, const float* in, int B, int H, int W, int C, float* out);
+/* replaces: nn.AdaptiveAvgPool2d(1), transformation.py:61.  in [B][HW][C] -> out [B][C] + guard */
+int mhip_avgpool_hw_host(mhip_ctx* ctx, int precision, const float* in, int B, int HW, int C, float* out);
+/* replaces: GridGenerator.build_P_prime + F.grid_sample(padding_mode="border", align_corners=True), transformation.py:32-42,
+ * 158-167.  crops u8 [B][H][W], cprime fp32 [B][F][2], inv_delta_c fp32 [F+3][F+3], p_hat fp32 [H*W][F+3] -> out fp32
+ * [B][H][W] + guard (the rectified, normalised crop) */
+int mhip_tps_sample_host(mhip_ctx* ctx, const uint8_t* crops, const float* cprime, const float* inv_delta_c,
+                         const float* p_hat, int B, int H, int W, int F, float* out);
+/* replaces: AttentionCell's e = score(tanh(i2h(H) + h2h(h))), alpha = softmax(e, dim=1), context = alpha^T H, prediction.py:
+ * 72-79.  hproj fp32 [B][T][256] = i2h(H); hp fp32 [B][ld_hp], columns 0..255 = h2h(h) + bias (ld_hp >= 256); score_w fp32
+ * [256]; H activations [B][T][256] -> ctx_out [B][256] + guard */
+int mhip_attn_context_host(mhip_ctx* ctx, int precision, const float* hproj, const float* hp, int ld_hp,
+                           const float* score_w, const float* H, int B, int T, float* ctx_out);
+/* replaces: nn.LSTMCell(256 + num_class, 256) on [context, one_hot(char)], prediction.py:80-82.  gctx fp32 [B][1024] =
+ * W_ih[:, :256] context; ghid fp32 [B][ld_hp], columns 256..1279 = W_hh h + b_ih + b_hh (ld_hp >= 1280); w_onehot fp32
+ * [num_class][1024] = W_ih[:, 256:]^T; chars int32 [B] in [0, num_class) (checked here: the kernel does not);
+ * c fp32 [B][256] + guard, updated in place; h [B][256] + guard */
+int mhip_attn_cell_host(mhip_ctx* ctx, int precision, const float* gctx, const float* ghid, int ld_hp,
+                        const float* w_onehot, int num_class, const int32_t* chars, int B, float* c, float* h);
+/* replaces: `_, next_input = probs_step.max(1)`, prediction.py:57-59.  logits fp32 [B][ld], the first C columns of a row
+ * count -> idx int32 [B] + guard = torch.max(x, 1).indices (first maximum; first NaN if any; 0 for a row of -inf) */
+int mhip_argmax_rows_host(mhip_ctx* ctx, const float* logits, int ld, int C, int B, int32_t* idx);
+/* replaces: preds_prob = F.softmax(preds, dim=2); preds_prob.max(dim=2), craft_ocr_processor.py:259-262.  logits fp32
+ * [rows][C] -> idx int32 [rows] + guard as above, pmax fp32 [rows] + guard = softmax probability at idx */
+int mhip_rowmax_softmax_host(mhip_ctx* ctx, const float* logits, int rows, int C, int32_t* idx, float* pmax);
+
 /* ---- production ICR recognizer: TPS-ResNet-BiLSTM-Attn ---------------------------------------- */
 typedef struct mhip_icr mhip_icr;
 /* replaces: Model(opt) with Transformation="TPS", FeatureExtraction="ResNet", SequenceModeling="BiLSTM",
@@ -279,6 +321,29 @@ int mhip_craft_detect_host(mhip_craft* m, const uint8_t* page_host, int h, int w
 int mhip_craft_boxes_host(mhip_ctx* ctx, const float* scores_host, int H, int W, float text_threshold,
                           float link_threshold, float low_text, float* boxes_host, int max_boxes, int* n_boxes,
                           int32_t* labels_host, uint8_t* flags_host, int32_t* stats_host, int stats_cap, int* n_labels);
+
+/* ---- stage entries of the detector's image kernels (csrc/image_ops.hip) -----------------------------------------------------
+ * Same conventions as the recognizer's stage entries above (MHIP_STAGE_GUARD elements behind every output). */
+/* replaces: cv2.resize(img, (dw, dh), interpolation=cv2.INTER_LINEAR), imgproc.py:58; the coefficient tables are built as
+ * mhip_craft_forward builds them.  src u8 [sh][sw][3] -> dst u8 [dh][dw][3] + guard */
+int mhip_resize_linear_u8_host(mhip_ctx* ctx, const uint8_t* src, int sh, int sw, uint8_t* dst, int dh, int dw);
+/* replaces: normalizeMeanVariance + canvas padding + basenet features[0..2] (conv3x3 3 -> 64, folded BatchNorm, ReLU),
+ * imgproc.py:26-33,61-66, basenet/vgg16_bn.py:29.  img u8 [th][tw][3] top-left on an [H][W] canvas; w27x64 fp32 [27][64]
+ * (k = (dy*3+dx)*3 + c) -> out [H][W][64] + guard.  f16 mode: the MFMA kernel */
+int mhip_conv_rgb_first_host(mhip_ctx* ctx, int precision, const uint8_t* img, int th, int tw, int H, int W,
+                             const float* w27x64, const float* scale, const float* bias, float* out);
+/* replaces: nn.MaxPool2d(2, 2) (k = 2, sizes floor) and nn.MaxPool2d(3, 1, 1) (k = 3), basenet/vgg16_bn.py:27-43.
+ * in [B][H][W][C] -> out [B][Ho][Wo][C] + guard */
+int mhip_maxpool_host(mhip_ctx* ctx, int precision, int k, const float* in, int B, int H, int W, int C, float* out);
+/* replaces: F.interpolate(size=(Ho, Wo), mode='bilinear', align_corners=False), craft.py:67-75.
+ * in [B][Hi][Wi][C] -> out [B][Ho][Wo][C] + guard */
+int mhip_upsample_bilinear_host(mhip_ctx* ctx, int precision, const float* in, int B, int Hi, int Wi, int C, int Ho, int Wo,
+                                float* out);
+/* replaces: conv_cls[6..8] = ReLU(conv1x1 16 -> 16), conv1x1 16 -> 2, craft.py:46-49.  in [npix][in_stride] activations, the
+ * first 16 channels of a line count (in_stride a multiple of 8); w1 [16][16], b1 [16], w2 [2][16], b2 [2] fp32 -> scores fp32
+ * [npix][2] + guard */
+int mhip_score_head_host(mhip_ctx* ctx, int precision, const float* in, int in_stride, const float* w1, const float* b1,
+                         const float* w2, const float* b2, long long npix, float* scores);
 
 /* ---- Pillow-exact 8-bit resize (antialiased LANCZOS / BILINEAR / BICUBIC) of RGB images -------------------------------- */
 #define MHIP_PIL_LANCZOS 1    /* PIL.Image.LANCZOS  */

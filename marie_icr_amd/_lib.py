@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("MARIE_HIP_LIB") or os.path.join(_HERE, "libmarie_hip.
 
 PREC_F16 = 0
 PREC_F32 = 1
+STAGE_GUARD = 4096   # MHIP_STAGE_GUARD: elements behind every output of a stage entry
 
 # every symbol include/marie_hip.h declares: (name, restype, argtypes)
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
@@ -256,6 +257,19 @@ _SIGNATURES = (
     ("mhip_crnn_workspace_bytes", _sz, [_vp, _i, _i]),
     ("mhip_crnn_kernel_flops", C.c_double, [_vp, _i, _i, _i]),
     ("mhip_lstm_rec_host", _i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    ("mhip_conv_gray_first_host", _i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    ("mhip_maxpool_s21_p01_host", _i, [_vp, _i, _vp, _i, _i, _i, _i, _vp]),
+    ("mhip_avgpool_hw_host", _i, [_vp, _i, _vp, _i, _i, _i, _vp]),
+    ("mhip_tps_sample_host", _i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    ("mhip_attn_context_host", _i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp]),
+    ("mhip_attn_cell_host", _i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    ("mhip_argmax_rows_host", _i, [_vp, _vp, _i, _i, _i, _vp]),
+    ("mhip_rowmax_softmax_host", _i, [_vp, _vp, _i, _i, _vp, _vp]),
+    ("mhip_resize_linear_u8_host", _i, [_vp, _vp, _i, _i, _vp, _i, _i]),
+    ("mhip_conv_rgb_first_host", _i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    ("mhip_maxpool_host", _i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp]),
+    ("mhip_upsample_bilinear_host", _i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    ("mhip_score_head_host", _i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, C.c_longlong, _vp]),
 )
 EXPORTED_SYMBOLS = tuple(s[0] for s in _SIGNATURES)
 

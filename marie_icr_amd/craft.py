@@ -22,7 +22,7 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-from ._lib import PREC_F16, PREC_F32, Context, MarieHipError, ModelHandle, check
+from ._lib import PREC_F16, PREC_F32, STAGE_GUARD, Context, MarieHipError, ModelHandle, check
 from .box_processor import PSMode, find_line_number
 
 
@@ -121,6 +121,79 @@ def craft_boxes(ctx: Context, scores: np.ndarray, text_threshold: float, link_th
         raw = raw[:nl.value]
         out.update(labels=labels, flags=flags, stats=raw[:, :5].copy(),
                    max_text=np.ascontiguousarray(raw[:, 5]).view(np.float32))
+    return out
+
+
+# Stage entries of csrc/image_ops.hip (include/marie_hip.h): one kernel each on host arrays through the launcher the model
+# calls.  Activations are fp32 here (narrowed to f16 and widened again in the f16 mode).  Every returned array is FLAT and
+# STAGE_GUARD elements longer than the output proper: the tail comes back as the 0xff fill the device buffer got before the
+# launch unless the kernel wrote past its end.
+def _vp(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _f32(a):
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _guarded(n: int, dtype=np.float32) -> np.ndarray:
+    return np.zeros(int(n) + STAGE_GUARD, dtype)
+
+
+def resize_linear_u8(ctx: Context, img_u8: np.ndarray, dst_h: int, dst_w: int) -> np.ndarray:
+    """img (sh, sw, 3) uint8 -> (dst_h*dst_w*3 + guard,) uint8"""
+    img = np.ascontiguousarray(img_u8, dtype=np.uint8)
+    sh, sw = img.shape[:2]
+    if img.shape != (sh, sw, 3):
+        raise ValueError(f"img must be (h, w, 3) uint8, got {img.shape}")
+    out = _guarded(int(dst_h) * int(dst_w) * 3, np.uint8)
+    check(ctx.h, ctx.lib.mhip_resize_linear_u8_host(ctx.h, _vp(img), sh, sw, _vp(out), int(dst_h), int(dst_w)),
+          "mhip_resize_linear_u8_host")
+    return out
+
+
+def conv_rgb_first(ctx: Context, precision: int, img_u8: np.ndarray, H: int, W: int, w27x64, scale, bias) -> np.ndarray:
+    """img (th, tw, 3) uint8 on an (H, W) canvas; w27x64 (27, 64) -> (H*W*64 + guard,)"""
+    img = np.ascontiguousarray(img_u8, dtype=np.uint8)
+    th, tw = img.shape[:2]
+    w27x64, scale, bias = _f32(w27x64), _f32(scale), _f32(bias)
+    if img.shape != (th, tw, 3) or w27x64.shape != (27, 64) or scale.shape != (64,) or bias.shape != (64,):
+        raise ValueError("conv_rgb_first: shapes disagree")
+    out = _guarded(max(int(H) * int(W), 0) * 64)
+    check(ctx.h, ctx.lib.mhip_conv_rgb_first_host(ctx.h, int(precision), _vp(img), th, tw, int(H), int(W), _vp(w27x64),
+                                                  _vp(scale), _vp(bias), _vp(out)), "mhip_conv_rgb_first_host")
+    return out
+
+
+def maxpool(ctx: Context, precision: int, k: int, x: np.ndarray) -> np.ndarray:
+    """x (B, H, W, C); k = 2: 2x2 stride 2, k = 3: 3x3 stride 1 pad 1 -> (B*Ho*Wo*C + guard,)"""
+    x = _f32(x)
+    B, H, W, Cn = x.shape
+    Ho, Wo = (H // 2, W // 2) if k == 2 else (H, W)
+    out = _guarded(B * Ho * Wo * Cn)
+    check(ctx.h, ctx.lib.mhip_maxpool_host(ctx.h, int(precision), int(k), _vp(x), B, H, W, Cn, _vp(out)), "mhip_maxpool_host")
+    return out
+
+
+def upsample_bilinear(ctx: Context, precision: int, x: np.ndarray, Ho: int, Wo: int) -> np.ndarray:
+    """x (B, Hi, Wi, C) -> (B*Ho*Wo*C + guard,)"""
+    x = _f32(x)
+    B, Hi, Wi, Cn = x.shape
+    out = _guarded(B * int(Ho) * int(Wo) * Cn)
+    check(ctx.h, ctx.lib.mhip_upsample_bilinear_host(ctx.h, int(precision), _vp(x), B, Hi, Wi, Cn, int(Ho), int(Wo), _vp(out)),
+          "mhip_upsample_bilinear_host")
+    return out
+
+
+def score_head(ctx: Context, precision: int, x: np.ndarray, w1, b1, w2, b2) -> np.ndarray:
+    """x (npix, in_stride), the first 16 channels count; w1 (16, 16), b1 (16,), w2 (2, 16), b2 (2,) -> (npix*2 + guard,)"""
+    x, w1, b1, w2, b2 = _f32(x), _f32(w1), _f32(b1), _f32(w2), _f32(b2)
+    npix, stride = x.shape
+    if w1.shape != (16, 16) or b1.shape != (16,) or w2.shape != (2, 16) or b2.shape != (2,):
+        raise ValueError("score_head: shapes disagree")
+    out = _guarded(npix * 2)
+    check(ctx.h, ctx.lib.mhip_score_head_host(ctx.h, int(precision), _vp(x), stride, _vp(w1), _vp(b1), _vp(w2), _vp(b2), npix,
+                                              _vp(out)), "mhip_score_head_host")
     return out
 
 

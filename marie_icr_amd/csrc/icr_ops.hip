@@ -14,6 +14,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "stage_host.h"
 
 namespace {
 
@@ -249,15 +250,24 @@ __global__ __launch_bounds__(256) void attn_cell_kernel(const float* __restrict_
   h[(size_t)b * 256 + j] = (T)(so * tanhf(cn));
 }
 
+// torch.max(x, 1)'s order: does (v, column c) come before (best, column bi)?  A NaN beats every number, the larger number
+// beats the smaller, and among equals (two NaNs, two equal numbers, -inf against the -inf a lane starts from) the lower column
+// wins — so the index is the first NaN if there is one, else the first maximum, 0 for a row of -inf, and always in [0, C).
+__device__ __forceinline__ bool argmax_before(float v, int c, float best, int bi) {
+  const bool vn = v != v, bn = best != best;
+  if (vn || bn) return vn && (!bn || c < bi);
+  return v > best || (v == best && c < bi);
+}
+
 // first maximum of every row of logits [B][ld] (first C columns) -> idx [B]
 __global__ __launch_bounds__(64) void argmax_rows_kernel(const float* __restrict__ logits, int ld, int C,
                                                          int* __restrict__ idx) {
   const int b = blockIdx.x, lane = threadIdx.x;
   float best = -INFINITY;
-  int bi = 0x7fffffff;
+  int bi = 0x7fffffff;          // a lane without a column (C < 64) loses every comparison; lane 0 always has column 0
   for (int c = lane; c < C; c += 64) {
     const float v = logits[(size_t)b * ld + c];
-    if (v > best) {
+    if (argmax_before(v, c, best, bi)) {
       best = v;
       bi = c;
     }
@@ -266,7 +276,7 @@ __global__ __launch_bounds__(64) void argmax_rows_kernel(const float* __restrict
   for (int off = 32; off >= 1; off >>= 1) {
     const float ov = __shfl_xor(best, off);
     const int oi = __shfl_xor(bi, off);
-    if (ov > best || (ov == best && oi < bi)) {
+    if (argmax_before(ov, oi, best, bi)) {
       best = ov;
       bi = oi;
     }
@@ -274,16 +284,17 @@ __global__ __launch_bounds__(64) void argmax_rows_kernel(const float* __restrict
   if (lane == 0) idx[b] = bi;
 }
 
-// per row: first arg-max and the softmax value at the arg-max (= 1 / sum exp(x - max)); one wave per row
+// per row: first arg-max (as above) and the softmax value at the arg-max (= 1 / sum exp(x - max); NaN for a row with a NaN);
+// one wave per row
 __global__ __launch_bounds__(64) void rowmax_softmax_kernel(const float* __restrict__ logits, int rows, int C,
                                                             int* __restrict__ idx, float* __restrict__ pmax) {
   const int r = blockIdx.x, lane = threadIdx.x;
   const float* row = logits + (size_t)r * C;
   float best = -INFINITY;
-  int bi = 0x7fffffff;
+  int bi = 0x7fffffff;          // a lane without a column (C < 64) loses every comparison; lane 0 always has column 0
   for (int c = lane; c < C; c += 64) {
     const float v = row[c];
-    if (v > best) {
+    if (argmax_before(v, c, best, bi)) {
       best = v;
       bi = c;
     }
@@ -292,7 +303,7 @@ __global__ __launch_bounds__(64) void rowmax_softmax_kernel(const float* __restr
   for (int off = 32; off >= 1; off >>= 1) {
     const float ov = __shfl_xor(best, off);
     const int oi = __shfl_xor(bi, off);
-    if (ov > best || (ov == best && oi < bi)) {
+    if (argmax_before(ov, oi, best, bi)) {
       best = ov;
       bi = oi;
     }
@@ -410,3 +421,109 @@ int mhip_launch_rowmax_softmax(mhip_ctx* ctx, const float* logits, int rows, int
   CHECK_LAUNCH(ctx, "rowmax_softmax");
   return 0;
 }
+
+// ------------------------------------------------------------------ stage entries (see include/marie_hip.h)
+// One kernel each on caller-supplied host buffers through the launcher above, exactly as icr_api.hip drives it: what the
+// kernel-level tests compare with an fp64 statement of the same operation.
+#define STAGE_ARGS(ctx, cond, what)                                      \
+  do {                                                                   \
+    if (!(cond)) return mhip_fail((ctx), MHIP_EINVAL, what ": bad shape"); \
+  } while (0)
+
+extern "C" int mhip_conv_gray_first_host(mhip_ctx* ctx, int precision, int in_is_u8, const void* img, int B, int H, int W,
+                                         int C, const float* w9xC, const float* scale, const float* bias, float* out) {
+  if (!ctx || !img || !w9xC || !scale || !bias || !out) return MHIP_EINVAL;
+  if (int rc = mhip_stage_precision(ctx, precision)) return rc;
+  STAGE_ARGS(ctx, B >= 1 && H >= 1 && W >= 1 && C >= 1 && C <= 4096, "conv_gray_first_host");
+  const size_t npix = (size_t)B * H * W;
+  StageIO io(ctx, precision);
+  const int i_img = io.in_raw(img, npix, in_is_u8 ? 1 : 4), i_w = io.in_raw(w9xC, (size_t)9 * C, 4);
+  const int i_s = io.in_raw(scale, C, 4), i_b = io.in_raw(bias, C, 4), i_o = io.out_act(out, npix * 64);
+  return io.run([&] {
+    return mhip_launch_conv_gray_first(ctx, precision, in_is_u8, io.dev(i_img), B, H, W, C, io.dev<float>(i_w),
+                                       io.dev<float>(i_s), io.dev<float>(i_b), io.dev(i_o));
+  });
+}
+
+extern "C" int mhip_maxpool_s21_p01_host(mhip_ctx* ctx, int precision, const float* in, int B, int H, int W, int C,
+                                         float* out) {
+  if (!ctx || !in || !out) return MHIP_EINVAL;
+  if (int rc = mhip_stage_precision(ctx, precision)) return rc;
+  STAGE_ARGS(ctx, B >= 1 && H >= 1 && W >= 1 && C >= 1, "maxpool_s21_p01_host");
+  StageIO io(ctx, precision);
+  const int i_in = io.in_act(in, (size_t)B * H * W * C), i_o = io.out_act(out, (size_t)B * (H / 2) * (W + 1) * C);
+  return io.run([&] { return mhip_launch_maxpool_s21_p01(ctx, precision, io.dev(i_in), io.dev(i_o), B, H, W, C); });
+}
+
+extern "C" int mhip_avgpool_hw_host(mhip_ctx* ctx, int precision, const float* in, int B, int HW, int C, float* out) {
+  if (!ctx || !in || !out) return MHIP_EINVAL;
+  if (int rc = mhip_stage_precision(ctx, precision)) return rc;
+  STAGE_ARGS(ctx, B >= 1 && HW >= 1 && C >= 1, "avgpool_hw_host");
+  StageIO io(ctx, precision);
+  const int i_in = io.in_act(in, (size_t)B * HW * C), i_o = io.out_act(out, (size_t)B * C);
+  return io.run([&] { return mhip_launch_avgpool_hw(ctx, precision, io.dev(i_in), io.dev(i_o), B, HW, C); });
+}
+
+extern "C" int mhip_tps_sample_host(mhip_ctx* ctx, const uint8_t* crops, const float* cprime, const float* inv_delta_c,
+                                    const float* p_hat, int B, int H, int W, int F, float* out) {
+  if (!ctx || !crops || !cprime || !inv_delta_c || !p_hat || !out) return MHIP_EINVAL;
+  STAGE_ARGS(ctx, B >= 1 && H >= 1 && W >= 1 && F >= 1 && F <= 4096, "tps_sample_host");
+  const size_t n = (size_t)H * W, F3 = (size_t)F + 3;
+  StageIO io(ctx, MHIP_PREC_F32);
+  const int i_c = io.in_raw(crops, B * n, 1), i_cp = io.in_raw(cprime, (size_t)B * F * 2, 4);
+  const int i_d = io.in_raw(inv_delta_c, F3 * F3, 4), i_p = io.in_raw(p_hat, n * F3, 4), i_o = io.out_raw(out, B * n, 4);
+  return io.run([&] {
+    return mhip_launch_tps_sample(ctx, io.dev<uint8_t>(i_c), io.dev<float>(i_cp), io.dev<float>(i_d), io.dev<float>(i_p),
+                                  io.dev<float>(i_o), B, H, W, F);
+  });
+}
+
+extern "C" int mhip_attn_context_host(mhip_ctx* ctx, int precision, const float* hproj, const float* hp, int ld_hp,
+                                      const float* score_w, const float* H, int B, int T, float* ctx_out) {
+  if (!ctx || !hproj || !hp || !score_w || !H || !ctx_out) return MHIP_EINVAL;
+  if (int rc = mhip_stage_precision(ctx, precision)) return rc;
+  STAGE_ARGS(ctx, B >= 1 && T >= 1 && T <= 4096 && ld_hp >= 256, "attn_context_host");
+  StageIO io(ctx, precision);
+  const int i_hj = io.in_raw(hproj, (size_t)B * T * 256, 4), i_hp = io.in_raw(hp, (size_t)B * ld_hp, 4);
+  const int i_sw = io.in_raw(score_w, 256, 4), i_H = io.in_act(H, (size_t)B * T * 256), i_o = io.out_act(ctx_out, (size_t)B * 256);
+  return io.run([&] {
+    return mhip_launch_attn_context(ctx, precision, io.dev<float>(i_hj), io.dev<float>(i_hp), ld_hp, io.dev<float>(i_sw),
+                                    io.dev(i_H), io.dev(i_o), B, T);
+  });
+}
+
+extern "C" int mhip_attn_cell_host(mhip_ctx* ctx, int precision, const float* gctx, const float* ghid, int ld_hp,
+                                   const float* w_onehot, int num_class, const int32_t* chars, int B, float* c, float* h) {
+  if (!ctx || !gctx || !ghid || !w_onehot || !chars || !c || !h) return MHIP_EINVAL;
+  if (int rc = mhip_stage_precision(ctx, precision)) return rc;
+  STAGE_ARGS(ctx, B >= 1 && num_class >= 1 && ld_hp >= 1280, "attn_cell_host");
+  for (int b = 0; b < B; ++b)      // the kernel indexes w_onehot with it unchecked
+    if (chars[b] < 0 || chars[b] >= num_class) return mhip_fail(ctx, MHIP_EINVAL, "attn_cell_host: chars[%d] = %d outside [0, %d)", b, chars[b], num_class);
+  StageIO io(ctx, precision);
+  const int i_gc = io.in_raw(gctx, (size_t)B * 1024, 4), i_gh = io.in_raw(ghid, (size_t)B * ld_hp, 4);
+  const int i_wo = io.in_raw(w_onehot, (size_t)num_class * 1024, 4), i_ch = io.in_raw(chars, B, 4);
+  const int i_c = io.inout_raw(c, (size_t)B * 256, 4), i_h = io.out_act(h, (size_t)B * 256);
+  return io.run([&] {
+    return mhip_launch_attn_cell(ctx, precision, io.dev<float>(i_gc), io.dev<float>(i_gh), ld_hp, io.dev<float>(i_wo),
+                                 io.dev<int>(i_ch), io.dev<float>(i_c), io.dev(i_h), B);
+  });
+}
+
+extern "C" int mhip_argmax_rows_host(mhip_ctx* ctx, const float* logits, int ld, int C, int B, int32_t* idx) {
+  if (!ctx || !logits || !idx) return MHIP_EINVAL;
+  STAGE_ARGS(ctx, B >= 1 && ld >= 1, "argmax_rows_host");
+  StageIO io(ctx, MHIP_PREC_F32);
+  const int i_l = io.in_raw(logits, (size_t)B * ld, 4), i_o = io.out_raw(idx, B, 4);
+  return io.run([&] { return mhip_launch_argmax_rows(ctx, io.dev<float>(i_l), ld, C, io.dev<int>(i_o), B); });
+}
+
+extern "C" int mhip_rowmax_softmax_host(mhip_ctx* ctx, const float* logits, int rows, int C, int32_t* idx, float* pmax) {
+  if (!ctx || !logits || !idx || !pmax) return MHIP_EINVAL;
+  STAGE_ARGS(ctx, rows >= 1 && C >= 1, "rowmax_softmax_host");
+  StageIO io(ctx, MHIP_PREC_F32);
+  const int i_l = io.in_raw(logits, (size_t)rows * C, 4), i_i = io.out_raw(idx, rows, 4), i_p = io.out_raw(pmax, rows, 4);
+  return io.run([&] {
+    return mhip_launch_rowmax_softmax(ctx, io.dev<float>(i_l), rows, C, io.dev<int>(i_i), io.dev<float>(i_p));
+  });
+}
+#undef STAGE_ARGS

@@ -10,6 +10,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "stage_host.h"
 
 namespace {
 
@@ -438,3 +439,76 @@ int mhip_launch_score_head(mhip_ctx* ctx, int precision, const void* in, int in_
   if (e != hipSuccess) return mhip_fail(ctx, MHIP_EHIP, "score_head launch: %s", hipGetErrorString(e));
   return 0;
 }
+
+// ------------------------------------------------------------------ stage entries (see include/marie_hip.h)
+// One kernel each on caller-supplied host buffers through the launcher above, exactly as craft_api.hip drives it: what the
+// kernel-level tests compare with an fp64 statement of the same operation.
+#define STAGE_ARGS(ctx, cond, what)                                        \
+  do {                                                                     \
+    if (!(cond)) return mhip_fail((ctx), MHIP_EINVAL, what ": bad shape"); \
+  } while (0)
+
+extern "C" int mhip_resize_linear_u8_host(mhip_ctx* ctx, const uint8_t* src, int sh, int sw, uint8_t* dst, int dh, int dw) {
+  if (!ctx || !src || !dst) return MHIP_EINVAL;
+  STAGE_ARGS(ctx, sh >= 1 && sw >= 1 && dh >= 1 && dw >= 1, "resize_linear_u8_host");
+  std::vector<int> xofs, yofs;
+  std::vector<short> xa, yb;
+  mhip_resize_linear_tables(sw, dw, xofs, xa);
+  mhip_resize_linear_tables(sh, dh, yofs, yb);
+  StageIO io(ctx, MHIP_PREC_F32);
+  const int i_s = io.in_raw(src, (size_t)sh * sw * 3, 1), i_xo = io.in_raw(xofs.data(), dw, 4), i_xa = io.in_raw(xa.data(), 2 * (size_t)dw, 2);
+  const int i_yo = io.in_raw(yofs.data(), dh, 4), i_yb = io.in_raw(yb.data(), 2 * (size_t)dh, 2), i_d = io.out_raw(dst, (size_t)dh * dw * 3, 1);
+  return io.run([&] {
+    return mhip_launch_resize_linear_u8(ctx, io.dev<uint8_t>(i_s), sh, sw, io.dev<uint8_t>(i_d), dh, dw, io.dev<int>(i_xo),
+                                        io.dev<short>(i_xa), io.dev<int>(i_yo), io.dev<short>(i_yb));
+  });
+}
+
+extern "C" int mhip_conv_rgb_first_host(mhip_ctx* ctx, int precision, const uint8_t* img, int th, int tw, int H, int W,
+                                        const float* w27x64, const float* scale, const float* bias, float* out) {
+  if (!ctx || !img || !w27x64 || !scale || !bias || !out) return MHIP_EINVAL;
+  if (int rc = mhip_stage_precision(ctx, precision)) return rc;
+  STAGE_ARGS(ctx, th >= 1 && tw >= 1 && H >= 1 && W >= 1, "conv_rgb_first_host");
+  StageIO io(ctx, precision);
+  const int i_img = io.in_raw(img, (size_t)th * tw * 3, 1), i_w = io.in_raw(w27x64, 27 * 64, 4), i_s = io.in_raw(scale, 64, 4);
+  const int i_b = io.in_raw(bias, 64, 4), i_o = io.out_act(out, (size_t)H * W * 64);
+  return io.run([&] {
+    return mhip_launch_conv_rgb_first(ctx, precision, io.dev<uint8_t>(i_img), th, tw, H, W, io.dev<float>(i_w),
+                                      io.dev<float>(i_s), io.dev<float>(i_b), io.dev(i_o));
+  });
+}
+
+extern "C" int mhip_maxpool_host(mhip_ctx* ctx, int precision, int k, const float* in, int B, int H, int W, int C, float* out) {
+  if (!ctx || !in || !out) return MHIP_EINVAL;
+  if (int rc = mhip_stage_precision(ctx, precision)) return rc;
+  STAGE_ARGS(ctx, B >= 1 && H >= 1 && W >= 1 && C >= 1, "maxpool_host");
+  const int Ho = k == 2 ? H / 2 : H, Wo = k == 2 ? W / 2 : W;
+  StageIO io(ctx, precision);
+  const int i_in = io.in_act(in, (size_t)B * H * W * C), i_o = io.out_act(out, (size_t)B * Ho * Wo * C);
+  return io.run([&] { return mhip_launch_maxpool(ctx, precision, k, io.dev(i_in), io.dev(i_o), B, H, W, C); });
+}
+
+extern "C" int mhip_upsample_bilinear_host(mhip_ctx* ctx, int precision, const float* in, int B, int Hi, int Wi, int C, int Ho,
+                                           int Wo, float* out) {
+  if (!ctx || !in || !out) return MHIP_EINVAL;
+  if (int rc = mhip_stage_precision(ctx, precision)) return rc;
+  STAGE_ARGS(ctx, B >= 1 && Hi >= 1 && Wi >= 1 && C >= 1 && Ho >= 1 && Wo >= 1, "upsample_bilinear_host");
+  StageIO io(ctx, precision);
+  const int i_in = io.in_act(in, (size_t)B * Hi * Wi * C), i_o = io.out_act(out, (size_t)B * Ho * Wo * C);
+  return io.run([&] { return mhip_launch_upsample_bilinear(ctx, precision, io.dev(i_in), io.dev(i_o), B, Hi, Wi, C, Ho, Wo); });
+}
+
+extern "C" int mhip_score_head_host(mhip_ctx* ctx, int precision, const float* in, int in_stride, const float* w1,
+                                    const float* b1, const float* w2, const float* b2, long long npix, float* scores) {
+  if (!ctx || !in || !w1 || !b1 || !w2 || !b2 || !scores) return MHIP_EINVAL;
+  if (int rc = mhip_stage_precision(ctx, precision)) return rc;
+  STAGE_ARGS(ctx, npix >= 1 && in_stride >= 1 && in_stride % 8 == 0, "score_head_host");   // 16-byte reads of a pixel's line
+  StageIO io(ctx, precision);
+  const int i_in = io.in_act(in, (size_t)npix * in_stride), i_w1 = io.in_raw(w1, 256, 4), i_b1 = io.in_raw(b1, 16, 4);
+  const int i_w2 = io.in_raw(w2, 32, 4), i_b2 = io.in_raw(b2, 2, 4), i_o = io.out_raw(scores, (size_t)npix * 2, 4);
+  return io.run([&] {
+    return mhip_launch_score_head(ctx, precision, io.dev(i_in), in_stride, io.dev<float>(i_w1), io.dev<float>(i_b1),
+                                  io.dev<float>(i_w2), io.dev<float>(i_b2), io.dev<float>(i_o), npix);
+  });
+}
+#undef STAGE_ARGS

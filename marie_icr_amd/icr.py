@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-from ._lib import PREC_F16, PREC_F32, Context, MarieHipError, ModelHandle, check
+from ._lib import PREC_F16, PREC_F32, STAGE_GUARD, Context, MarieHipError, ModelHandle, check
 from .crnn import IMG_H, pack_fragments
 from .ocr_processor import OcrProcessor
 from .weights import CRNN_CHARSET, ICR_IMG_W
@@ -74,6 +74,117 @@ def attn_texts(argmax: np.ndarray, pmax: np.ndarray, charset: str):
             texts.append(pred.upper())
             confs.append(float(conf))
     return texts, confs
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Stage entries of csrc/icr_ops.hip (include/marie_hip.h): one kernel each on host arrays through the launcher the model
+# calls.  Activations are fp32 here (narrowed to f16 and widened again in the f16 mode).  Every returned array is FLAT and
+# STAGE_GUARD elements longer than the output proper: the tail comes back as the 0xff fill the device buffer got before the
+# launch unless the kernel wrote past its end.
+def _vp(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _f32(a):
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _guarded(n: int, dtype=np.float32) -> np.ndarray:
+    return np.zeros(int(n) + STAGE_GUARD, dtype)
+
+
+def conv_gray_first(ctx: Context, precision: int, img: np.ndarray, w9xC, scale, bias) -> np.ndarray:
+    """img (B, H, W) uint8 or fp32; w9xC (9, C) -> (B*H*W*64 + guard,)"""
+    img = np.ascontiguousarray(img)
+    if img.dtype != np.uint8:
+        img = _f32(img)
+    B, H, W = img.shape
+    w9xC, scale, bias = _f32(w9xC), _f32(scale), _f32(bias)
+    out = _guarded(B * H * W * 64)
+    check(ctx.h, ctx.lib.mhip_conv_gray_first_host(ctx.h, int(precision), int(img.dtype == np.uint8), _vp(img), B, H, W,
+                                                   w9xC.shape[1], _vp(w9xC), _vp(scale), _vp(bias), _vp(out)),
+          "mhip_conv_gray_first_host")
+    return out
+
+
+def maxpool_s21_p01(ctx: Context, precision: int, x: np.ndarray) -> np.ndarray:
+    """x (B, H, W, C) -> (B*(H//2)*(W+1)*C + guard,)"""
+    x = _f32(x)
+    B, H, W, Cn = x.shape
+    out = _guarded(B * (H // 2) * (W + 1) * Cn)
+    check(ctx.h, ctx.lib.mhip_maxpool_s21_p01_host(ctx.h, int(precision), _vp(x), B, H, W, Cn, _vp(out)),
+          "mhip_maxpool_s21_p01_host")
+    return out
+
+
+def avgpool_hw(ctx: Context, precision: int, x: np.ndarray) -> np.ndarray:
+    """x (B, HW, C) -> (B*C + guard,)"""
+    x = _f32(x)
+    B, HW, Cn = x.shape
+    out = _guarded(B * Cn)
+    check(ctx.h, ctx.lib.mhip_avgpool_hw_host(ctx.h, int(precision), _vp(x), B, HW, Cn, _vp(out)), "mhip_avgpool_hw_host")
+    return out
+
+
+def tps_sample(ctx: Context, crops_u8: np.ndarray, c_prime, inv_delta_c, p_hat) -> np.ndarray:
+    """crops (B, H, W) uint8, c_prime (B, F, 2), inv_delta_c (F+3, F+3), p_hat (H*W, F+3) -> (B*H*W + guard,)"""
+    crops = np.ascontiguousarray(crops_u8, dtype=np.uint8)
+    B, H, W = crops.shape
+    c_prime, inv_delta_c, p_hat = _f32(c_prime), _f32(inv_delta_c), _f32(p_hat)
+    F = c_prime.shape[1]
+    if c_prime.shape != (B, F, 2) or inv_delta_c.shape != (F + 3, F + 3) or p_hat.shape != (H * W, F + 3):
+        raise ValueError("tps_sample: shapes disagree")
+    out = _guarded(B * H * W)
+    check(ctx.h, ctx.lib.mhip_tps_sample_host(ctx.h, _vp(crops), _vp(c_prime), _vp(inv_delta_c), _vp(p_hat), B, H, W, F,
+                                              _vp(out)), "mhip_tps_sample_host")
+    return out
+
+
+def attn_context(ctx: Context, precision: int, hproj, hp, score_w, H) -> np.ndarray:
+    """hproj (B, T, 256), hp (B, ld_hp), score_w (256,), H (B, T, 256) -> (B*256 + guard,)"""
+    hproj, hp, score_w, H = _f32(hproj), _f32(hp), _f32(score_w), _f32(H)
+    B, T = H.shape[:2]
+    if hproj.shape != (B, T, 256) or H.shape != (B, T, 256) or hp.shape[0] != B or score_w.shape != (256,):
+        raise ValueError("attn_context: shapes disagree")
+    out = _guarded(B * 256)
+    check(ctx.h, ctx.lib.mhip_attn_context_host(ctx.h, int(precision), _vp(hproj), _vp(hp), hp.shape[1], _vp(score_w), _vp(H),
+                                                B, T, _vp(out)), "mhip_attn_context_host")
+    return out
+
+
+def attn_cell(ctx: Context, precision: int, gctx, ghid, w_onehot, chars, c_prev):
+    """gctx (B, 1024), ghid (B, ld_hp), w_onehot (num_class, 1024), chars (B,) int32, c_prev (B, 256) ->
+    (c (B*256 + guard,), h (B*256 + guard,))"""
+    gctx, ghid, w_onehot = _f32(gctx), _f32(ghid), _f32(w_onehot)
+    chars = np.ascontiguousarray(chars, dtype=np.int32)
+    B = gctx.shape[0]
+    if gctx.shape != (B, 1024) or ghid.shape[0] != B or w_onehot.shape[1] != 1024 or chars.shape != (B,):
+        raise ValueError("attn_cell: shapes disagree")
+    c = _guarded(B * 256)
+    c[:B * 256] = _f32(c_prev).reshape(-1)
+    h = _guarded(B * 256)
+    check(ctx.h, ctx.lib.mhip_attn_cell_host(ctx.h, int(precision), _vp(gctx), _vp(ghid), ghid.shape[1], _vp(w_onehot),
+                                             w_onehot.shape[0], _vp(chars), B, _vp(c), _vp(h)), "mhip_attn_cell_host")
+    return c, h
+
+
+def argmax_rows(ctx: Context, logits: np.ndarray, C_used: int) -> np.ndarray:
+    """logits (B, ld) fp32, the first C_used columns count -> (B + guard,) int32"""
+    logits = _f32(logits)
+    B, ld = logits.shape
+    idx = _guarded(B, np.int32)
+    check(ctx.h, ctx.lib.mhip_argmax_rows_host(ctx.h, _vp(logits), ld, int(C_used), B, _vp(idx)), "mhip_argmax_rows_host")
+    return idx
+
+
+def rowmax_softmax(ctx: Context, logits: np.ndarray):
+    """logits (rows, C) fp32 -> (idx (rows + guard,) int32, pmax (rows + guard,) fp32)"""
+    logits = _f32(logits)
+    rows, Cn = logits.shape
+    idx, pmax = _guarded(rows, np.int32), _guarded(rows)
+    check(ctx.h, ctx.lib.mhip_rowmax_softmax_host(ctx.h, _vp(logits), rows, Cn, _vp(idx), _vp(pmax)),
+          "mhip_rowmax_softmax_host")
+    return idx, pmax
 
 
 class CraftOcrProcessor(OcrProcessor):

@@ -59,13 +59,18 @@ class TorchIcrOracle:
         h = F.adaptive_avg_pool2d(h, 1).view(x.shape[0], -1)
         h = F.relu(F.linear(h, st[p + "localization_fc1.0.weight"], st[p + "localization_fc1.0.bias"]))
         c_prime = F.linear(h, st[p + "localization_fc2.weight"], st[p + "localization_fc2.bias"]).view(x.shape[0], -1, 2)
+        grid = self.tps_grid(c_prime).reshape(x.shape[0], x.shape[2], x.shape[3], 2)
+        return F.grid_sample(x, grid, padding_mode="border", align_corners=True)
+
+    @torch.no_grad()
+    def tps_grid(self, c_prime: torch.Tensor) -> torch.Tensor:
+        """GridGenerator.build_P_prime — transformation.py:158-167: (b, F, 2) -> (b, n, 2), fp32."""
+        st = self.st
         g = "Transformation.GridGenerator."
-        b = x.shape[0]
+        b = c_prime.shape[0]
         cz = torch.cat((c_prime, torch.zeros(b, 3, 2)), dim=1)
         t = torch.bmm(st[g + "inv_delta_C"].repeat(b, 1, 1), cz)
-        p_prime = torch.bmm(st[g + "P_hat"].repeat(b, 1, 1), t)
-        grid = p_prime.reshape(b, x.shape[2], x.shape[3], 2)
-        return F.grid_sample(x, grid, padding_mode="border", align_corners=True)
+        return torch.bmm(st[g + "P_hat"].repeat(b, 1, 1), t)
 
     @torch.no_grad()
     def resnet(self, x: torch.Tensor) -> torch.Tensor:

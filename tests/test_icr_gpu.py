@@ -20,9 +20,38 @@ def ctx():
     c.close()
 
 
-def _safe(ref_logits, tol):
+QUARTER = 0.25          # the largest share of (crop, step) cells a gate may set aside
+
+
+def first_unsafe_step(ref_logits, tol):
+    """per crop: its first step whose reference top-2 margin is not above 2 * tol — the step count if it has none.  The decoder
+    feeds its own arg-max back, so up to that step the device's greedy path cannot leave the reference's while its logits are
+    within tol; from it on the two may take different characters and nothing is compared."""
     s = np.sort(ref_logits, axis=2)
-    return ((s[:, :, -1] - s[:, :, -2]) > 2 * tol).all(axis=1)
+    unsafe = (s[:, :, -1] - s[:, :, -2]) <= 2 * tol
+    return np.where(unsafe.any(axis=1), unsafe.argmax(axis=1), ref_logits.shape[1])
+
+
+def step_gate(ref_logits, tol, tag):
+    """(k per crop, mask (n, steps) of the cells compared: steps 0 .. k - 1).  The share set aside depends on the reference and
+    the tolerance only; it is printed and must stay within a quarter, so the comparisons below always compare."""
+    k = first_unsafe_step(ref_logits, tol)
+    mask = np.arange(ref_logits.shape[1])[None, :] < k[:, None]
+    share = 1.0 - float(mask.mean())
+    print(f"{tag}: tolerance {tol:.4g}: {share:.3f} of the steps set aside, first unsafe steps {k.tolist()}")
+    assert share <= QUARTER, (tag, share)
+    return k, mask
+
+
+def steps_the_text_needs(ref_argmax, charset):
+    """per crop: how many leading steps decide its text and confidence under the reference's rule (attn_texts): the cut is the
+    position of "[s]" in the joined STRING, which is never before the step that emitted it"""
+    character = ["[GO]", "[s]"] + list(charset)
+    out = []
+    for row in ref_argmax.tolist():
+        eos = "".join(character[i] for i in row).find("[s]")
+        out.append(len(row) if eos < 0 else min(len(row), eos + 1))
+    return np.array(out)
 
 
 @pytest.mark.parametrize("tag", ["a", "b"])
@@ -38,19 +67,30 @@ def test_fp32_matches_reference_golden(ctx, tag):
     # the sampling grid carries ~2e-5 of fp32 accumulation-order noise (loc-net convs + the 23-term TPS sums), i.e.
     # ~1e-3 px; on these noise crops (unit gradient per pixel) that is ~1e-3 in sampled value.  Logits below hold 1e-3.
     assert np.abs(out["rectified"] - g["rectified"][:, 0]).max() <= 3e-3
-    # the decoder feeds its own arg-max back: compare step by step only while the greedy paths agree
+    # the decoder feeds its own arg-max back: compare step by step only while the greedy paths must agree
     err_first = np.abs(out["logits"][:, 0] - g["logits"][:, 0]).max()
     assert err_first <= 1e-3, err_first
-    safe = _safe(g["logits"], 2e-3)
-    err = np.abs(out["logits"][safe] - g["logits"][safe]).max() if safe.any() else 0.0
+    k, mask = step_gate(g["logits"], 2e-3, f"golden {tag}")
+    err = np.abs(out["logits"] - g["logits"]).max(axis=2)[mask].max()
+    print(f"golden {tag}: max logit error over the compared steps {err:.2e}")
     assert err <= 1e-3, err
-    np.testing.assert_array_equal(out["argmax"][safe], g["argmax"][safe])
+    np.testing.assert_array_equal(out["argmax"][mask], g["argmax"][mask])
     texts, confs = attn_texts(out["argmax"], out["pmax"], CRNN_CHARSET)
-    for ok, t, c, rt, rc in zip(safe, texts, confs, g["strings"], g["confidence"]):
+    decided = k >= steps_the_text_needs(g["argmax"], CRNN_CHARSET)
+    print(f"golden {tag}: text and confidence compared for {int(decided.sum())} of {len(k)} crops")
+    assert decided.sum() >= max(1, (k == g["logits"].shape[1]).sum())
+    for ok, t, c, rt, rc in zip(decided, texts, confs, g["strings"], g["confidence"]):
         if ok:
             assert t == str(rt)
             assert abs(c - float(rc)) <= 5e-3 * max(float(rc), 1e-30)
     m.close()
+
+
+# Crop seed 9: on the oracle alone the gate keeps within a quarter for any first-step error up to F16_ERR0_BUDGET (16 % at 0.02,
+# 24 % at 0.035; tests/test_icr_gate_cpu.py).  First MI355X figures: first-step error 0.0107 on a logit range of 8.32 (bar 0.166),
+# 7.9 % of the steps set aside, 0.032 over the compared steps (bar 0.416).
+F16_CROP_SEED = 9
+F16_ERR0_BUDGET = 0.035
 
 
 def test_f16_vs_oracle(ctx):
@@ -60,17 +100,27 @@ def test_f16_vs_oracle(ctx):
     from oracle.icr_torch import TorchIcrOracle
 
     st = make_icr_state(2)
-    crops = make_crnn_input(9, 37, 32, 100)
+    crops = make_crnn_input(F16_CROP_SEED, 37, 32, 100)
     ref = TorchIcrOracle(st).logits(crnn_numpy.normalize_u8(crops))
     m = IcrModel(ctx, st, precision=PREC_F16)
     out = m.forward_host(crops, want_logits=True)
     err0 = np.abs(out["logits"][:, 0] - ref[:, 0]).max()            # first step: no feedback yet
+    print(f"f16: first-step logit error {err0:.4f}, logit range {np.abs(ref).max():.2f}")
     assert err0 <= 0.02 * max(1.0, np.abs(ref).max()), err0
-    safe = _safe(ref, err0 * 4 + 1e-3)
-    if safe.any():
-        assert np.abs(out["logits"][safe] - ref[safe]).max() <= 0.05 * max(1.0, np.abs(ref).max())
-        np.testing.assert_array_equal(out["argmax"][safe], ref[safe].argmax(axis=2))
+    _, mask = step_gate(ref, err0 * 4 + 1e-3, "f16")
+    err = np.abs(out["logits"] - ref).max(axis=2)[mask].max()
+    print(f"f16: max logit error over the compared steps {err:.4f}")
+    assert err <= 0.05 * max(1.0, np.abs(ref).max())
+    np.testing.assert_array_equal(out["argmax"][mask], ref.argmax(axis=2)[mask])
     m.close()
+
+
+def surface_fragments():
+    """three noise fragments of different sizes.  Seed 7: the oracle's top-2 margins stay above the 2e-3 tolerance at every step
+    of all three (with seed 4, used before the per-step gate, the first fragment's margin falls under it at step 3, which sets 31 %
+    of the steps aside); tests/test_icr_gate_cpu.py checks it without a GPU."""
+    rng = np.random.default_rng(7)
+    return [rng.integers(0, 256, size=(int(h), int(w), 3)).astype(np.uint8) for h, w in [(40, 130), (25, 60), (33, 400)]]
 
 
 def test_processor_surface(ctx):
@@ -80,15 +130,17 @@ def test_processor_surface(ctx):
     from oracle.icr_torch import TorchIcrOracle, attn_decode
 
     st = make_icr_state(0)
-    rng = np.random.default_rng(4)
-    frags = [rng.integers(0, 256, size=(int(h), int(w), 3)).astype(np.uint8) for h, w in [(40, 130), (25, 60), (33, 400)]]
+    frags = surface_fragments()
     p = CraftOcrProcessor(state=st, precision="f32", ctx=ctx)
     res = p.recognize_from_fragments(frags)
     assert [r["id"] for r in res] == ["img-0", "img-1", "img-2"]
     crops = pr.align_collate_pil(frags, 100)
     ref = TorchIcrOracle(st).logits(crnn_numpy.normalize_u8(crops))
     _, texts, confs = attn_decode(ref, CRNN_CHARSET)
-    safe = _safe(ref, 2e-3)
-    for ok, r, t, c in zip(safe, res, texts, confs):
+    k, _ = step_gate(ref, 2e-3, "processor surface")
+    decided = k >= steps_the_text_needs(ref.argmax(axis=2), CRNN_CHARSET)
+    print(f"processor surface: text and confidence compared for {int(decided.sum())} of {len(k)} fragments")
+    assert decided.sum() >= max(1, (k == ref.shape[1]).sum())
+    for ok, r, t, c in zip(decided, res, texts, confs):
         if ok:
             assert r["text"] == t and abs(r["confidence"] - c) <= 5e-3 * max(c, 1e-30)
