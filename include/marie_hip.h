@@ -975,7 +975,7 @@ int mhip_cliprn_attnpool_host(mhip_ctx* ctx, int precision, const float* x, cons
                               const float* wk, const float* bk, const float* wv, const float* bv, const float* wc,
                               const float* bc, int B, int HW, int E, int P, float* emb_out);
 
-/* ---- CLIP text tower: text embeddings (csrc/cliptext_api.hip, cliptext_ops.hip) ------------------------------------------- */
+/* ---- CLIP text tower: text embeddings (csrc/cliptext_api.hip, cliptext_ops.hip, attn_seq.hip) ----------------------------- */
 /* replaces: CLIP.encode_text behind OpenAIEmbeddings.get_text_embedding, marie/embeddings/openai/openai_embeddings.py:122-129,
  * 159-164 (clip/model.py: token_embedding + positional_embedding, the causal transformer, ln_final, the end-of-text row,
  * text_projection), CLIPModel.get_text_features of transformers.  Token ids come from the caller (marie_icr_amd/
@@ -1025,7 +1025,7 @@ int mhip_cliptext_attention_host(mhip_ctx* ctx, int precision, const float* q, c
 int mhip_cliptext_head_host(mhip_ctx* ctx, const float* h, int B, int npad, int D, const float* g, const float* b, float eps,
                             const float* proj, int E, const int32_t* row_of, float* emb_out);
 
-/* ---- BERT sentence encoders: text embeddings (csrc/berttext_api.hip, berttext_ops.hip) ------------------------------------ */
+/* ---- BERT sentence encoders: text embeddings (csrc/berttext_api.hip, berttext_ops.hip, attn_seq.hip) ---------------------- */
 /* replaces: SentenceTransformer.encode behind SentenceTransformerEmbeddings.get_embeddings (marie/embeddings/sentence_transformers/
  * sentence_transformers_embeddings.py, all-MiniLM-L6-v2) and JinaEmbeddings.get_embeddings (marie/embeddings/jina/
  * jina_embeddings.py, jina-embeddings-v2-base-en): BertModel without the pooler — or JinaBERT: no position table, the symmetric

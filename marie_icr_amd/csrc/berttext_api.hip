@@ -391,38 +391,18 @@ static int berttext_attention_run(mhip_ctx* ctx, int precision, const float* q, 
   for (int b = 0; b < B; ++b)
     if (len[b] < 1 || len[b] > npad) return mhip_fail(ctx, MHIP_EINVAL, "berttext_attention: sequence %d has %d keys (1 .. %d)", b, len[b], npad);
   MHIP_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t es = precision == MHIP_PREC_F16 ? 2 : 4, D = (size_t)heads * head_dim, R = (size_t)B * npad;
-  EncoderWs w;
-  float *dout = nullptr, *dsl = nullptr;
+  float* dsl = nullptr;
   int* dlen = nullptr;
-  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
-    encoder_ws_carve(ws, R, D, 64, 0, es, &w); dout = ws.take<float>(R * D * 4); dlen = ws.take<int>((size_t)B * 4);
-    dsl = ws.take<float>((size_t)heads * 4);
-  });
-  if (rc) return rc;
-  // q | k rows of pitch 2 D and V^T [D][R], as the tower's GEMMs write them
-  std::vector<float> qk(R * 2 * D), vt(D * R);
-  for (size_t r = 0; r < R; ++r) {
-    memcpy(&qk[r * 2 * D], q + r * D, D * 4);
-    memcpy(&qk[r * 2 * D + D], k + r * D, D * 4);
-    for (size_t d = 0; d < D; ++d) vt[d * R + r] = v[r * D + d];
-  }
-  std::vector<char> qkt(qk.size() * es), vtt(vt.size() * es);
-  Arena::put(precision, qkt.data(), qk.data(), qk.size());
-  Arena::put(precision, vtt.data(), vt.data(), vt.size());
-  MHIP_HIP(ctx, hipMemcpyAsync(w.qk, qkt.data(), qkt.size(), hipMemcpyHostToDevice, ctx->stream));
-  MHIP_HIP(ctx, hipMemcpyAsync(w.vt, vtt.data(), vtt.size(), hipMemcpyHostToDevice, ctx->stream));
-  MHIP_HIP(ctx, hipMemcpyAsync(dlen, len, (size_t)B * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (slopes) MHIP_HIP(ctx, hipMemcpyAsync(dsl, slopes, (size_t)heads * 4, hipMemcpyHostToDevice, ctx->stream));
-  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the sources are host temporaries in pageable memory
-  AttnShortDesc sd;
-  sd.a = encoder_attn_desc(w.qk, w.vt, w.ao, (int)D, es, B, heads, npad, npad);
-  sd.len = dlen; sd.slopes = slopes ? dsl : nullptr; sd.head_dim = head_dim;
-  if ((rc = streamed ? mhip_launch_attention_long(ctx, precision, sd) : mhip_launch_attention_short(ctx, precision, sd))) return rc;
-  if ((rc = mhip_launch_convert_rows(ctx, precision, w.ao, dout, (int)R, (int)D))) return rc;
-  MHIP_HIP(ctx, hipMemcpyAsync(out, dout, R * D * 4, hipMemcpyDeviceToHost, ctx->stream));
-  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return MHIP_OK;
+  return encoder_attention_host(
+      ctx, precision, q, k, v, B, heads, head_dim, npad, out,
+      [&](Carver& ws) { dlen = ws.take<int>((size_t)B * 4); dsl = ws.take<float>((size_t)heads * 4); },
+      [&](const AttnDesc& ad) {      // len and slopes are the caller's: they outlive the call's last synchronisation
+        MHIP_HIP(ctx, hipMemcpyAsync(dlen, len, (size_t)B * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (slopes) MHIP_HIP(ctx, hipMemcpyAsync(dsl, slopes, (size_t)heads * 4, hipMemcpyHostToDevice, ctx->stream));
+        AttnShortDesc sd;
+        sd.a = ad; sd.len = dlen; sd.slopes = slopes ? dsl : nullptr; sd.head_dim = head_dim;
+        return streamed ? mhip_launch_attention_long(ctx, precision, sd) : mhip_launch_attention_short(ctx, precision, sd);
+      });
 }
 
 extern "C" int mhip_berttext_attention_host(mhip_ctx* ctx, int precision, const float* q, const float* k, const float* v, const int32_t* len,

@@ -179,7 +179,6 @@ __global__ __launch_bounds__(256) void pair_cosine_kernel(const float* __restric
 }
 
 inline int grid_for(long long total, int block) { return (int)std::min<long long>((total + block - 1) / block, 65535LL * 4); }
-inline bool row_width_ok(int D) { return D >= 64 && D % 64 == 0 && D <= 256 * ROW_GROUPS; }
 
 }  // namespace
 

@@ -284,31 +284,8 @@ extern "C" int mhip_cliptext_attention_host(mhip_ctx* ctx, int precision, const 
   if (B < 1 || B > MAX_TEXTS || heads < 1 || heads > 16 || !npad_ok(npad, MAX_CONTEXT))
     return mhip_fail(ctx, MHIP_EINVAL, "cliptext_attention: B=%d heads=%d npad=%d", B, heads, npad);
   MHIP_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t es = precision == MHIP_PREC_F16 ? 2 : 4, D = (size_t)heads * 64, R = (size_t)B * npad;
-  EncoderWs w;
-  float* dout = nullptr;
-  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) { encoder_ws_carve(ws, R, D, 64, 0, es, &w); dout = ws.take<float>(R * D * 4); });
-  if (rc) return rc;
-  // q | k rows of pitch 2 D and V^T [D][R], as the tower's GEMMs write them
-  std::vector<float> qk(R * 2 * D), vt(D * R);
-  for (size_t r = 0; r < R; ++r) {
-    memcpy(&qk[r * 2 * D], q + r * D, D * 4);
-    memcpy(&qk[r * 2 * D + D], k + r * D, D * 4);
-    for (size_t d = 0; d < D; ++d) vt[d * R + r] = v[r * D + d];
-  }
-  std::vector<char> qkt(qk.size() * es), vtt(vt.size() * es);
-  Arena::put(precision, qkt.data(), qk.data(), qk.size());
-  Arena::put(precision, vtt.data(), vt.data(), vt.size());
-  if ((rc = encoder_ws_clear_slack(ctx, w, R, D, es))) return rc;
-  MHIP_HIP(ctx, hipMemcpyAsync(w.qk, qkt.data(), qkt.size(), hipMemcpyHostToDevice, ctx->stream));
-  MHIP_HIP(ctx, hipMemcpyAsync(w.vt, vtt.data(), vtt.size(), hipMemcpyHostToDevice, ctx->stream));
-  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the sources are host temporaries in pageable memory
-  const AttnDesc ad = encoder_attn_desc(w.qk, w.vt, w.ao, (int)D, es, B, heads, npad, npad);
-  if ((rc = mhip_launch_attention_causal(ctx, precision, ad))) return rc;
-  if ((rc = mhip_launch_convert_rows(ctx, precision, w.ao, dout, (int)R, (int)D))) return rc;
-  MHIP_HIP(ctx, hipMemcpyAsync(out, dout, R * D * 4, hipMemcpyDeviceToHost, ctx->stream));
-  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return MHIP_OK;
+  return encoder_attention_host(ctx, precision, q, k, v, B, heads, 64, npad, out, [](Carver&) {},
+                                [&](const AttnDesc& ad) { return mhip_launch_attention_causal(ctx, precision, ad); });
 }
 
 extern "C" int mhip_cliptext_head_host(mhip_ctx* ctx, const float* h, int B, int npad, int D, const float* g, const float* b, float eps,

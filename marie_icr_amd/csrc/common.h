@@ -49,11 +49,11 @@ enum MhipKernelId {
   MHIP_K_QUICK_GELU = 26,        // x * sigmoid(1.702 x) in place
   MHIP_K_CLIPVIS_HEAD = 27,      // post_layernorm of the class row + projection; also cliprn_cproj (the attention pool's c_proj)
   MHIP_K_PAIR_COSINE = 28,       // cosine of embedding pairs by index
-  // CLIP text tower (cliptext_ops.hip)
+  // CLIP text tower (cliptext_ops.hip; the attention: attn_seq.hip)
   MHIP_K_CLIPTEXT_EMBED = 29,    // token table gather + position rows -> fp32 stream
   MHIP_K_ATTN_CAUSAL = 30,       // causal soft-max attention, one workgroup per (sequence, head), K / V^T held in LDS
   MHIP_K_LEV_NGRAMS = 31,      // edit distance of every (template text, page n-gram) pair (lev_ngrams.hip)
-  // BERT sentence encoders (berttext_ops.hip)
+  // BERT sentence encoders (berttext_ops.hip; the attention: attn_seq.hip)
   MHIP_K_ATTN_SHORT = 32,        // bidirectional soft-max attention over sequences of their own length, optional ALiBi, head dim 64 / 32:
                                  // attn_short (<= 128 rows, keys held in LDS) and attn_long (<= 8192 rows, keys streamed in blocks of
                                  // 128, online soft-max) share the slot, as the post-LayerNorms share berttext_embed
@@ -622,10 +622,10 @@ int mhip_launch_cliprn_cproj(mhip_ctx* ctx, const float* ao, int B, int E, const
 // ------------------------------------------------------------------ CLIP text tower ops (cliptext_ops.hip)
 // h [B*npad][D] fp32 = table[ids[row]] + pos[row % npad]; table [vocab][D], pos [>= npad][D] fp32; the ids are the caller's to check
 int mhip_launch_cliptext_embed(mhip_ctx* ctx, const float* table, const float* pos, const int* ids, float* h, int B, int npad, int D);
+// ------------------------------------------------------------------ per-sequence attention of the text towers (attn_seq.hip)
 // causal softmax(Q K^T) V over AttnDesc's layout (query row t sees keys 0 .. t): npad_q == npad_k <= 128, a multiple of 8; every
 // row < npad is written, nothing past a sequence's rows is read (no slack needed)
 int mhip_launch_attention_causal(mhip_ctx* ctx, int precision, const AttnDesc& d);
-// ------------------------------------------------------------------ BERT sentence encoder ops (berttext_ops.hip)
 // softmax(Q K^T [- slope |i - j|]) V over AttnDesc's layout with heads of head_dim (64 or 32) columns, sequence b attending to its
 // first len[b] keys (device, 1 .. npad; n_queries / n_keys of `a` are not used): npad_q == npad_k <= 128, a multiple of 8; every
 // row < npad is written, nothing past a sequence's rows is read (no slack needed).  slopes (device, [heads], in the log2 units of
@@ -642,6 +642,7 @@ int mhip_launch_attention_short(mhip_ctx* ctx, int precision, const AttnShortDes
 // queries); a sequence's key walk is a function of len[b] alone, every row < npad is written (query blocks that start at or past
 // len[b] as zeros), nothing past a sequence's rows is read (no slack needed).  Counted in MHIP_K_ATTN_SHORT
 int mhip_launch_attention_long(mhip_ctx* ctx, int precision, const AttnShortDesc& d);
+// ------------------------------------------------------------------ BERT sentence encoder ops (berttext_ops.hip)
 // h [B*npad][D] fp32 = LN((word[ids[row]] + type0) + pos[row % npad]), ht (null: not written) its copy in the precision's element
 // type; word [vocab][D], type0 [D], pos [>= npad][D] or null (no position table) fp32; the ids are the caller's to check
 int mhip_launch_berttext_embed(mhip_ctx* ctx, int precision, const float* word, const float* type0, const float* pos, const float* g,

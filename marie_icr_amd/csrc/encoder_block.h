@@ -131,13 +131,46 @@ inline int encoder_block_qkv(mhip_ctx* ctx, int prec, const Arena& a, int i, con
   return mhip_gemm(ctx, prec, a.d(enc_blk(i, "v_w")), w.ht, D, R, D, nullptr, nullptr, w.vt, ACT_NONE, 0);   // V^T = W_v X^T
 }
 
-// the causal attention of the CLIP text tower over the same buffers (cliptext_ops.hip)
+// The host entries that run one attention kernel alone (the kernel tests): q, k, v fp32 [R = B * npad][D = heads * head_dim] on the
+// host -> out fp32 [R][D].  Carves an EncoderWs, the fp32 output and what `more(Carver&)` takes, writes q | k rows of pitch 2 D and
+// V^T [D][R] as the tower's GEMMs write them, and runs `launch(AttnDesc)` on them
+template <typename More, typename Launch>
+int encoder_attention_host(mhip_ctx* ctx, int prec, const float* q, const float* k, const float* v, int B, int heads, int head_dim, int npad,
+                           float* out, More&& more, Launch&& launch) {
+  const size_t es = prec == MHIP_PREC_F16 ? 2 : 4, D = (size_t)heads * head_dim, R = (size_t)B * npad;
+  EncoderWs w;
+  float* dout = nullptr;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) { encoder_ws_carve(ws, R, D, 64, 0, es, &w); dout = ws.take<float>(R * D * 4); more(ws); });
+  if (rc) return rc;
+  std::vector<float> qk(R * 2 * D), vt(D * R);
+  for (size_t r = 0; r < R; ++r) {
+    memcpy(&qk[r * 2 * D], q + r * D, D * 4);
+    memcpy(&qk[r * 2 * D + D], k + r * D, D * 4);
+    for (size_t d = 0; d < D; ++d) vt[d * R + r] = v[r * D + d];
+  }
+  std::vector<char> qkt(qk.size() * es), vtt(vt.size() * es);
+  Arena::put(prec, qkt.data(), qk.data(), qk.size());
+  Arena::put(prec, vtt.data(), vt.data(), vt.size());
+  MHIP_HIP(ctx, hipMemcpyAsync(w.qk, qkt.data(), qkt.size(), hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(w.vt, vtt.data(), vtt.size(), hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the sources are host temporaries in pageable memory
+  if ((rc = launch(encoder_attn_desc(w.qk, w.vt, w.ao, (int)D, es, B, heads, npad, npad)))) {
+    (void)hipStreamSynchronize(ctx->stream);      // a refusing launch may have enqueued copies from the caller's memory: none outlives the call
+    return rc;
+  }
+  if ((rc = mhip_launch_convert_rows(ctx, prec, w.ao, dout, (int)R, (int)D))) return rc;
+  MHIP_HIP(ctx, hipMemcpyAsync(out, dout, R * D * 4, hipMemcpyDeviceToHost, ctx->stream));
+  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return MHIP_OK;
+}
+
+// the causal attention of the CLIP text tower over the same buffers (attn_seq.hip)
 struct AttnCausalDesc {
   AttnDesc a;
 };
 
 // the attention half of block i, w.ht -> w.ao: plain, with LayoutLMv3's bias and key mask (bd.a the descriptor), causal, or over
-// sequences of their own length (berttext_ops.hip)
+// sequences of their own length (attn_seq.hip)
 inline int encoder_block_attention(mhip_ctx* ctx, int prec, const Arena& a, int i, const EncoderWs& w, const AttnDesc& ad) {
   const int rc = encoder_block_qkv(ctx, prec, a, i, w, ad);
   return rc ? rc : mhip_launch_attention(ctx, prec, ad);

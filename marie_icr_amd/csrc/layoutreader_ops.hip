@@ -309,8 +309,6 @@ __global__ __launch_bounds__(LR_THREADS) void lr_pointer_select_kernel(const flo
   }
 }
 
-inline bool row_width_ok(int D) { return D >= 64 && D % 64 == 0 && D <= 256 * ROW_GROUPS; }
-
 template <typename T>
 void launch_decode(mhip_ctx* ctx, const LrDecAttnDesc& d) {
   DecArgs<T> a;

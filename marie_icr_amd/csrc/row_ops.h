@@ -1,10 +1,11 @@
-// row_ops.h — what the one-wave-per-row kernels share (clip_ops.hip, berttext_ops.hip): D % 64 == 0, D <= 1024, a lane holds the
-// float4 groups at columns (i * 64 + lane) * 4 < D.
+// row_ops.h — what the one-wave-per-row kernels share (clip_ops.hip, cliptext_ops.hip, berttext_ops.hip, layoutreader_ops.hip):
+// D % 64 == 0, D <= 1024, a lane holds the float4 groups at columns (i * 64 + lane) * 4 < D.
 #pragma once
 #include "igemm_common.h"
 
 // internal linkage: a file that includes this keeps its own helpers of the same names apart from another file's
 constexpr int ROW_GROUPS = 4;      // float4 groups per lane: D <= 1024
+static inline bool row_width_ok(int D) { return D >= 64 && D % 64 == 0 && D <= 256 * ROW_GROUPS; }
 
 static __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

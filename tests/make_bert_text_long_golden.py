@@ -1,6 +1,6 @@
 """Writes tests/golden/bert_text_long.npz: what transformers computes for the two tiny BERT models of tests/make_bert_text_golden.py
 with 512 positions on texts past 128 tokens, the third-party pin of tests/bert_text_ref.py at the lengths the streamed attention
-(attn_long, marie_icr_amd/csrc/berttext_ops.hip) serves.
+(attn_long, marie_icr_amd/csrc/attn_seq.hip) serves.
 
     python tests/make_bert_text_long_golden.py            (CPU, float64; the file regenerates byte for byte)
 

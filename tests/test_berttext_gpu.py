@@ -1,4 +1,4 @@
-"""BERT sentence encoders on the MI355X (marie_icr_amd/csrc/berttext_api.hip, berttext_ops.hip) against tests/bert_text_ref.py,
+"""BERT sentence encoders on the MI355X (marie_icr_amd/csrc/berttext_api.hip, berttext_ops.hip, attn_seq.hip) against tests/bert_text_ref.py,
 the float64 restatement that tests/test_berttext_cpu.py pins to transformers.BertModel through tests/golden/bert_text.npz.
 
 Bars:

@@ -1,4 +1,4 @@
-"""BERT sentence embeddings past 128 tokens on the MI355X: the streamed attention attn_long (marie_icr_amd/csrc/berttext_ops.hip)
+"""BERT sentence embeddings past 128 tokens on the MI355X: the streamed attention attn_long (marie_icr_amd/csrc/attn_seq.hip)
 alone, the encoders at npad 512 and the public classes, against tests/bert_text_ref.py — the float64 restatement that
 tests/test_berttext_long_cpu.py pins to transformers.BertModel at these lengths through tests/golden/bert_text_long.npz.
 
