@@ -1035,12 +1035,17 @@ int mhip_cliptext_head_host(mhip_ctx* ctx, const float* h, int B, int npad, int 
  * text b's token count ([CLS] .. [SEP]), the rows after it carry the [PAD] id.  Calls of npad <= 128 hold a text's keys in LDS
  * (attn_short); longer ones stream them in blocks of 128 under an online soft-max (attn_long).  On each side of that boundary a
  * text's embedding does not depend on the other texts of the call or on npad, bit for bit.  A call lays out at most
- * 4096 * 128 = 524288 rows (B * npad).  Post-LN layers, fp32 [dim] out.                                                        */
+ * 4096 * 128 = 524288 rows (B * npad).  Post-LN layers, fp32 [dim] out.
+ * The same encoder runs three more families once their keys are renamed onto BERT's (marie_icr_amd/embeddings.py:
+ * load_sentence_encoder_state): RoBERTa (pos_offset 2, one token type), DistilBERT (no token types) and MPNet (pos_offset 2, no
+ * token types, and MPNetEncoder's relative attention bias: one table [rel_buckets][heads] shared by the layers, added to the scores
+ * as a function of query - key clamped to +-rel_max_distance).                                                                */
 typedef struct mhip_berttext mhip_berttext;
 typedef struct mhip_berttext_config {
   int vocab;               /* 30522                                                                                       */
   int max_position;        /* 512: rows of the position table (position 0 only)                                           */
-  int type_vocab;          /* 2: row 0 of the token type table is added to every token                                    */
+  int type_vocab;          /* 2: row 0 of the token type table is added to every token; 0 (create_ex only): no token type
+                              table, no term                                                                              */
   int dim, heads, depth;   /* 384/12/6 (all-MiniLM-L6-v2), 768/12/12 (jina-v2-base); head dim 64 or 32, dim a multiple of
                               64 up to 1024                                                                               */
   int ffn;                 /* 1536 / 3072; a multiple of 64                                                               */
@@ -1050,15 +1055,31 @@ typedef struct mhip_berttext_config {
   int pool;                /* 0 mean over the len[b] tokens, 1 cls (row 0)                                               */
   int normalize;           /* 1: divide the pooled row by max(its L2 norm, 1e-12)                                         */
 } mhip_berttext_config;
+/* the same with the fields of the other families appended; zero in each is the behaviour without it.  (A struct of its own, and
+ * mhip_berttext_create_ex below: callers of mhip_berttext_create pass the twelve fields above and nothing behind them.)       */
+typedef struct mhip_berttext_config_ex {
+  mhip_berttext_config base;
+  int pos_offset;          /* the position row of token t is pos_offset + t (RoBERTa, MPNet: pad_id + 1 = 2); a text then
+                              has at most max_position - pos_offset tokens                                                */
+  int rel_buckets;         /* 0: no relative attention bias; otherwise even and >= 4 (MPNet: 32), and the tensor
+                              encoder.relative_attention_bias.weight [rel_buckets][heads] is taken.  Not with alibi       */
+  int rel_max_distance;    /* MPNet: 128.  finalize refuses (naming this field) a pair whose bucket still changes past
+                              this distance: the table is indexed by the distance clamped to it                           */
+} mhip_berttext_config_ex;
 /* MHIP_EINVAL with a message that names the field: a head dim other than 64 or 32, dim above 1024, dim or ffn no multiple of 64,
  * an unknown position / mlp / pool / normalize value                                                                          */
 int mhip_berttext_create(mhip_ctx* ctx, int precision, const mhip_berttext_config* cfg, mhip_berttext** out);
+/* as create, plus: type_vocab 0 is legal; MHIP_EINVAL naming the field for a pos_offset that leaves fewer than 2 position rows (or
+ * any with alibi), rel_buckets odd or below 4 (or any with alibi: slopes and a table together), rel_max_distance outside
+ * 1 .. 8192 with rel_buckets or non-zero without                                                                              */
+int mhip_berttext_create_ex(mhip_ctx* ctx, int precision, const mhip_berttext_config_ex* cfg, mhip_berttext** out);
 int mhip_berttext_destroy(mhip_berttext* m);
 /* keys of Hugging Face BERT (an optional "bert." prefix is stripped): embeddings.{word,position,token_type}_embeddings.weight,
  * embeddings.LayerNorm.*, encoder.layer.N.attention.self.{query,key,value}.*, attention.output.{dense,LayerNorm}.*,
  * intermediate.dense.*, output.{dense,LayerNorm}.*; with mlp = geglu the MLP is JinaBERT's encoder.layer.N.mlp.gated_layers.weight
  * [2 ffn][dim] (no bias; first the GELU half, then the linear half), mlp.wo.*, mlp.layernorm.*, and position = alibi takes no
- * position table.  pooler.* and embeddings.position_ids are ignored; any other key is MHIP_EINVAL.  finalize names the first
+ * position table; with rel_buckets encoder.relative_attention_bias.weight (finite values).  pooler.* and
+ * embeddings.position_ids are ignored; any other key is MHIP_EINVAL.  finalize names the first
  * missing or misshapen tensor                                                                                                 */
 int mhip_berttext_set_tensor(mhip_berttext* m, const char* key, const float* data, const int64_t* shape, int ndim);
 int mhip_berttext_finalize(mhip_berttext* m);
@@ -1070,6 +1091,11 @@ size_t mhip_berttext_workspace_bytes(mhip_berttext* m, int B, int npad);
 /* the ALiBi slopes of `heads` heads, fp32 [heads]: 2^(-8 (i + 1) / n) for n a power of two; otherwise those of the largest power
  * of two p <= n, then the even-indexed slopes of 2 p, the first n - p of them.  Host only, no ctx                              */
 int mhip_berttext_alibi_slopes(int heads, float* slopes_out);
+/* MPNet's relative attention bias as the encoder folds it, before the log2(e) factor: table_out fp32 [heads][2 R + 1], R =
+ * max_distance, table_out[h][d + R] = weight[bucket(-d)][h] for d = query - key in -R .. R, weight fp32 [buckets][heads], bucket
+ * MPNetEncoder.relative_position_bucket(key - query, buckets, max_distance) in float32 as the library computes it.  MHIP_EINVAL
+ * where the bucket still changes past +-R (up to 8192): clamping the distance would then differ from the model.  Host only, no ctx */
+int mhip_berttext_rel_table(int buckets, int max_distance, const float* weight, int heads, float* table_out);
 /* B texts (1 .. 4096) -> emb_out fp32 [B][dim].  MHIP_EINVAL, never a clamp: npad no multiple of 8 or above 8192 (or above the
  * position table rounded up to 8), more than 524288 rows (B * npad), a len outside [1, npad], an id outside [0, vocab)        */
 int mhip_berttext_embed_host(mhip_berttext* m, const int32_t* ids, const int32_t* len, int B, int npad, float* emb_out);
@@ -1085,6 +1111,11 @@ int mhip_berttext_debug_taps_host(mhip_berttext* m, const int32_t* ids, const in
  * ids [B][npad] -> h_out [B][npad][D] = LN(word[id] + type0 (+ pos[t]))                                                       */
 int mhip_berttext_embed_rows_host(mhip_ctx* ctx, const float* word, const float* type0, const float* pos, const float* g,
                                   const float* b, float eps, const int32_t* ids, int B, int npad, int vocab, int D, float* h_out);
+/* the same with type0 NULL (no token type term) and the position row of token t at pos_offset + t: pos fp32
+ * [pos_offset + npad][D] or NULL                                                                                              */
+int mhip_berttext_embed_rows_ex_host(mhip_ctx* ctx, const float* word, const float* type0, const float* pos, const float* g,
+                                     const float* b, float eps, const int32_t* ids, int B, int npad, int vocab, int D, int pos_offset,
+                                     float* h_out);
 /* attention of B sequences of npad rows over their first len[b] keys: q, k, v fp32 [B][npad][heads * head_dim], q already scaled
  * by head_dim^-0.5 * log2(e), slopes [heads] in the same log2 units or NULL (no bias term); rounded to the precision's element
  * type and laid out as the encoder lays them out (q | k rows, V^T) -> out fp32, same shape                                    */
@@ -1094,6 +1125,14 @@ int mhip_berttext_attention_host(mhip_ctx* ctx, int precision, const float* q, c
  * the streamed code), at most 524288 rows (B * npad).  mhip_berttext_attention_host keeps its limit of 128 rows                 */
 int mhip_berttext_attention_long_host(mhip_ctx* ctx, int precision, const float* q, const float* k, const float* v,
                                       const int32_t* len, const float* slopes, int B, int heads, int head_dim, int npad, float* out);
+/* the two attention entries with a relative-distance table in place of the slopes: the score of (query i, key j) gets
+ * table[head][clamp(i - j, -radius, radius) + radius]; table fp32 [heads][2 radius + 1] in the log2 units of q, finite (a
+ * non-finite value is MHIP_EINVAL), or NULL: then the result is that of the entry above with slopes NULL, bit for bit        */
+int mhip_berttext_attention_rel_host(mhip_ctx* ctx, int precision, const float* q, const float* k, const float* v, const int32_t* len,
+                                     const float* table, int radius, int B, int heads, int head_dim, int npad, float* out);
+int mhip_berttext_attention_rel_long_host(mhip_ctx* ctx, int precision, const float* q, const float* k, const float* v,
+                                          const int32_t* len, const float* table, int radius, int B, int heads, int head_dim, int npad,
+                                          float* out);
 /* x fp32 [R][2 F], rounded to the precision's element type -> out fp32 [R][F] = gelu_erf(x[:, :F]) * x[:, F:]                 */
 int mhip_berttext_geglu_host(mhip_ctx* ctx, int precision, const float* x, int R, int F, float* out);
 /* h fp32 [B][npad][D], len [B] -> emb_out fp32 [B][D]: mode 0 the mean of rows < len[b], 1 row 0; normalize 0 / 1            */

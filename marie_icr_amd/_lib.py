@@ -209,6 +209,7 @@ _SIGNATURES = (
     ("mhip_cliptext_attention_host", _i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
     ("mhip_cliptext_head_host", _i, [_vp, _vp, _i, _i, _i, _vp, _vp, C.c_float, _vp, _i, _vp, _vp]),
     ("mhip_berttext_create", _i, [_vp, _i, _vp, C.POINTER(_vp)]),
+    ("mhip_berttext_create_ex", _i, [_vp, _i, _vp, C.POINTER(_vp)]),
     ("mhip_berttext_destroy", _i, [_vp]),
     ("mhip_berttext_set_tensor", _i, [_vp, C.c_char_p, _vp, C.POINTER(C.c_int64), _i]),
     ("mhip_berttext_finalize", _i, [_vp]),
@@ -222,6 +223,10 @@ _SIGNATURES = (
     ("mhip_berttext_embed_rows_host", _i, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp, _i, _i, _i, _i, _vp]),
     ("mhip_berttext_attention_host", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     ("mhip_berttext_attention_long_host", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    ("mhip_berttext_rel_table", _i, [_i, _i, _vp, _i, _vp]),
+    ("mhip_berttext_embed_rows_ex_host", _i, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp, _i, _i, _i, _i, _i, _vp]),
+    ("mhip_berttext_attention_rel_host", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    ("mhip_berttext_attention_rel_long_host", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     ("mhip_berttext_geglu_host", _i, [_vp, _i, _vp, _i, _i, _vp]),
     ("mhip_berttext_pool_host", _i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     ("mhip_layoutreader_create", _i, [_vp, _i, _vp, C.POINTER(_vp)]),
@@ -381,6 +386,11 @@ class BertTextConfig(C.Structure):
     _fields_ = [("vocab", C.c_int), ("max_position", C.c_int), ("type_vocab", C.c_int), ("dim", C.c_int), ("heads", C.c_int),
                 ("depth", C.c_int), ("ffn", C.c_int), ("ln_eps", C.c_float), ("position", C.c_int), ("mlp", C.c_int),
                 ("pool", C.c_int), ("normalize", C.c_int)]
+
+
+class SentenceEncoderConfig(BertTextConfig):
+    """mirror of mhip_berttext_config_ex (include/marie_hip.h): the fields above, then those of the other families"""
+    _fields_ = [("pos_offset", C.c_int), ("rel_buckets", C.c_int), ("rel_max_distance", C.c_int)]
 
 
 class LayoutReaderConfig(C.Structure):

@@ -1,13 +1,15 @@
 // attn_seq.hip — soft-max attention of the text towers, one sequence at a time with its keys in LDS: causal over at most 128 rows
 // (attn_causal: the CLIP text tower, cliptext_api.hip), over sequences of their own length with optional ALiBi (attn_short: the
 // BERT encoders at up to 128 rows, berttext_api.hip), and the same with the keys streamed in blocks of 128 under an online
-// soft-max (attn_long: up to 8192 rows).  Every step is written once, in Seq<T, HD> below; the kernels differ in three things:
+// soft-max (attn_long: up to 8192 rows).  Every step is written once, in Seq<T, HD> below; the kernels differ in four things:
 // which key tiles a query tile walks and which scores of the last walked tile become -inf (data: `nvis`, `limit`), the ALiBi
-// term (a branch), and whether the block's result is normalised directly or folded into a running (m, l, o).
+// term (a branch), the relative-distance table's term (MPNet: a template parameter, so the instances without it are the code
+// they were), and whether the block's result is normalised directly or folded into a running (m, l, o).
 //
 // Replaces, in transformers/models/clip/modeling_clip.py: the attention of CLIPEncoderLayer under the causal mask of
 // CLIPTextTransformer (clip/model.py: the attn_mask of build_attention_mask); in transformers/models/bert/modeling_bert.py: the
-// attention of BertSelfAttention under the padding mask, and of JinaBERT the symmetric ALiBi bias.
+// attention of BertSelfAttention under the padding mask, and of JinaBERT the symmetric ALiBi bias; in transformers/models/mpnet/
+// modeling_mpnet.py: the attention of MPNetSelfAttention under MPNetEncoder.compute_position_bias.
 //
 // Whole-row kernel (attn_causal, attn_short): one workgroup = one (sequence, head).  K and V^T of that head are staged in LDS
 // once (keys past the sequence's as zeros); each wave owns the 16-query tiles wave, wave + 4.  As in attn_flash.hip the products
@@ -24,6 +26,9 @@
 //     computed like any other row: finite, and nobody reads them.
 //   * with slopes, the score of (query i, key j) gets  - slope[head] * |i - j|  (ALiBi, symmetric), in the log2 units q carries;
 //     without slopes there is no bias term.
+//   * with a table (REL instances; never with slopes, never causal), the score of (query i, key j) gets
+//     table[head][clamp(i - j, -R, R) + R], fp32 in the log2 units q carries, finite: a lane reads its four values a tile through
+//     the vector cache (257 floats a head at R = 128: the table stays resident), the index taken from `dist` and the tile.
 //   * the head dim HD is 64 or 32: at 32 the first product is one 16x16x32 f16 step and O^T has two 16-row tiles.
 //   f16: v_mfma_f32_16x16x32_f16 for both products (two key tiles make one 32-key step of the second; a tile past the last walked
 //        enters as zeros), probabilities rounded to f16 only as that operand; the row sum is of the fp32 probabilities.
@@ -73,6 +78,14 @@ struct SeqArgs {
   const float* slope;    // [heads] in log2 units, or null
   int ldq, ldk, ldv, ldo;
   int npad, heads;
+};
+// the arguments of an instance: those above and, with REL, the relative-distance table.  Without REL the struct is SeqArgs<T>
+template <typename T, bool REL>
+struct SeqRelArgs : SeqArgs<T> {};
+template <typename T>
+struct SeqRelArgs<T, true> : SeqArgs<T> {
+  const float* rel;      // [heads][2 rel_r + 1] in log2 units, finite
+  int rel_r;
 };
 
 // The steps of one query tile (lane (g, n): query column n, lane group g) over one block of at most SEQ_MAXK keys in LDS.  A
@@ -139,10 +152,11 @@ struct Seq {
   // value of the last tile's product (-inf + a finite product = -inf, and it stays -inf under the bias) and not as a select
   // on its result.  That is for a walk that is the same for every query tile (the whole-row kernel with lengths): the few
   // conditions are then kept across the tiles and nothing waits for the product.  It needs the masked keys' products finite,
-  // which holds there because keys >= len are staged as zeros; causal masks keys the caller wrote, and keeps the select
-  template <bool INIT>
-  static __device__ __forceinline__ void scores(const T* Ks, const chunk_t (&qf)[NKS], bool alibi, float slope, int query, int k0,
-                                                int nvis, int limit, int g, int n, float4v (&s)[SEQ_NT]) {
+  // which holds there because keys >= len are staged as zeros; causal masks keys the caller wrote, and keeps the select.
+  // REL: rel is the head's table [2 R + 1]; key 16 t + 4 g + r of the block is at distance dist - 16 t - r from the query
+  template <bool INIT, bool REL>
+  static __device__ __forceinline__ void scores(const T* Ks, const chunk_t (&qf)[NKS], bool alibi, float slope, const float* rel, int R,
+                                                int query, int k0, int nvis, int limit, int g, int n, float4v (&s)[SEQ_NT]) {
     // the lane's keys are 16 t + 4 g + r.  Mask and bias are written relative to one value a lane — the keys it has left in the
     // last visible tile, the distance of its first key — and not as one value a key, which would be kept across the tiles
     const int room = limit - (nvis - 1) * 16 - 4 * g, dist = query - k0 - 4 * g;
@@ -163,6 +177,12 @@ struct Seq {
         if (alibi) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) c[r] -= slope * fabsf((float)(dist - (t * 16 + r)));
+        }
+        if constexpr (REL) {
+          float4v b;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) b[r] = rel[min(max(dist - (t * 16 + r), -R), R) + R];
+          c += b;
         }
         if (!INIT && t == nvis - 1) {
 #pragma unroll
@@ -252,8 +272,9 @@ struct Seq {
   }
 };
 
-template <typename T, int HD, bool CAUSAL>
-__global__ __launch_bounds__(SEQ_THREADS) void attn_seq_rows_kernel(SeqArgs<T> p) {
+template <typename T, int HD, bool CAUSAL, bool REL>
+__global__ __launch_bounds__(SEQ_THREADS) void attn_seq_rows_kernel(SeqRelArgs<T, REL> p) {
+  static_assert(!(CAUSAL && REL), "the causal instances take no table");
   typedef Seq<T, HD> S;
   __shared__ __attribute__((aligned(16))) T Ks[S::L::KSZ];
   __shared__ __attribute__((aligned(16))) T Vs[S::L::VSZ];
@@ -270,6 +291,12 @@ __global__ __launch_bounds__(SEQ_THREADS) void attn_seq_rows_kernel(SeqArgs<T> p
 
   const bool alibi = !CAUSAL && p.slope;
   const float slope = alibi ? p.slope[head] : 0.f;
+  const float* rel = nullptr;
+  int rel_r = 0;
+  if constexpr (REL) {
+    rel_r = p.rel_r;
+    rel = p.rel + (size_t)head * (2 * rel_r + 1);
+  }
   const int ntiles = (npad + 15) >> 4;
   for (int qt = wave; qt < ntiles; qt += 4) {
     const int query = qt * 16 + n;
@@ -278,7 +305,7 @@ __global__ __launch_bounds__(SEQ_THREADS) void attn_seq_rows_kernel(SeqArgs<T> p
     typename S::chunk_t qf[S::NKS];
     S::load_q(p, head, row0, query, g, qf);
     float4v s[SEQ_NT];
-    S::template scores<!CAUSAL>(Ks, qf, alibi, slope, query, 0, nvis, limit, g, n, s);
+    S::template scores<!CAUSAL, REL>(Ks, qf, alibi, slope, rel, rel_r, query, 0, nvis, limit, g, n, s);
     const float m = S::block_max(s, nvis);
     float l = S::exp_sum(s, nvis, m);
     l += __shfl_xor(l, 16);
@@ -294,14 +321,15 @@ __global__ __launch_bounds__(SEQ_THREADS) void attn_seq_rows_kernel(SeqArgs<T> p
 // attn_long: the same attention for sequences past SEQ_MAXK keys.  One workgroup = one (sequence, head, block of 64 queries), a
 // 16-query tile a wave; the keys arrive in blocks of SEQ_MAXK, 0 .. ceil(len / SEQ_MAXK) - 1 in that order, each staged into the
 // same LDS images and walked as attn_short walks its key tiles (ALiBi from the absolute key index, the -inf select in the
-// block's last tile), then folded into the running state of the online soft-max:
+// block's last tile; the table's term from the same index, so a block farther than R away adds one value), then folded into the
+// running state of the online soft-max:
 //   m' = max(m, block max)   alpha = exp2(m - m')   l = l alpha + sum p   o = o alpha, then the block's second product
 // and o / l at the end.  The first key of every walked block is a key of the sequence, so no block maximum is -inf; alpha of the
 // first block is exp2(-inf) = 0 on o = l = 0.  The walk is a function of len alone.  A query block that starts at or past len
 // writes zeros and leaves before any barrier.  m, alpha, l and o are fp32 in both modes; l is kept as the lane's partial sum (the
 // four lane groups of a query share m and alpha) and reduced once at the end.  One buffer, two barriers a block.
-template <typename T, int HD>
-__global__ __launch_bounds__(SEQ_THREADS) void attn_seq_stream_kernel(SeqArgs<T> p) {
+template <typename T, int HD, bool REL>
+__global__ __launch_bounds__(SEQ_THREADS) void attn_seq_stream_kernel(SeqRelArgs<T, REL> p) {
   typedef Seq<T, HD> S;
   __shared__ __attribute__((aligned(16))) T Ks[S::L::KSZ];
   __shared__ __attribute__((aligned(16))) T Vs[S::L::VSZ];
@@ -325,6 +353,12 @@ __global__ __launch_bounds__(SEQ_THREADS) void attn_seq_stream_kernel(SeqArgs<T>
   S::load_q(p, head, row0, query, g, qf);
   const bool alibi = p.slope != nullptr;
   const float slope = alibi ? p.slope[head] : 0.f;
+  const float* rel = nullptr;
+  int rel_r = 0;
+  if constexpr (REL) {
+    rel_r = p.rel_r;
+    rel = p.rel + (size_t)head * (2 * rel_r + 1);
+  }
 
   const int nkb = (len + SEQ_MAXK - 1) / SEQ_MAXK;
   for (int kb = 0; kb < nkb; ++kb) {
@@ -335,7 +369,7 @@ __global__ __launch_bounds__(SEQ_THREADS) void attn_seq_stream_kernel(SeqArgs<T>
     S::template stage<true>(p, Ks, Vs, head, row0, k0, blen, S::staged(nkt));
     __syncthreads();
     float4v s[SEQ_NT];
-    S::template scores<false>(Ks, qf, alibi, slope, query, k0, nkt, blen, g, n, s);
+    S::template scores<false, REL>(Ks, qf, alibi, slope, rel, rel_r, query, k0, nkt, blen, g, n, s);
     const float mn = fmaxf(m, S::block_max(s, nkt));
     const float alpha = __builtin_amdgcn_exp2f(m - mn);
     m = mn;
@@ -365,9 +399,12 @@ int seq_check(mhip_ctx* ctx, const char* name, int max_rows, int precision, cons
   return 0;
 }
 
-template <typename T>
-SeqArgs<T> seq_args(const AttnDesc& d, const int* len, const float* slopes) {
-  SeqArgs<T> a;
+template <typename T, bool REL>
+SeqRelArgs<T, REL> seq_args(const AttnDesc& d, const int* len, const float* slopes, const float* rel, int rel_r) {
+  SeqRelArgs<T, REL> a;
+  if constexpr (REL) {
+    a.rel = rel; a.rel_r = rel_r;
+  }
   a.q = (const T*)d.q; a.k = (const T*)d.k; a.vt = (const T*)d.vt; a.out = (T*)d.out;
   a.len = len; a.slope = slopes;
   a.ldq = d.ldq; a.ldk = d.ldk; a.ldv = d.ldv; a.ldo = d.ldo;
@@ -375,25 +412,27 @@ SeqArgs<T> seq_args(const AttnDesc& d, const int* len, const float* slopes) {
   return a;
 }
 
-template <typename T, int HD>
-void seq_launch(mhip_ctx* ctx, SeqKind kind, const AttnDesc& d, const int* len, const float* slopes) {
-  const SeqArgs<T> a = seq_args<T>(d, len, slopes);
+template <typename T, int HD, bool REL>
+void seq_launch(mhip_ctx* ctx, SeqKind kind, const AttnDesc& d, const int* len, const float* slopes, const float* rel, int rel_r) {
+  const SeqRelArgs<T, REL> a = seq_args<T, REL>(d, len, slopes, rel, rel_r);
   const dim3 rows((unsigned)(d.images * d.heads)), blocks(rows.x, (unsigned)((d.npad_k + SEQ_QB - 1) / SEQ_QB)), threads(SEQ_THREADS);
-  if constexpr (HD == 64) {      // causal: head dim 64 only; its one caller dispatches with 64, so no kind is left unlaunched
-    if (kind == SEQ_CAUSAL) PROF_LAUNCH(ctx, MHIP_K_ATTN_CAUSAL, hipLaunchKernelGGL((attn_seq_rows_kernel<T, 64, true>), rows, threads, 0, ctx->stream, a));
+  if constexpr (HD == 64 && !REL) {      // causal: head dim 64 only; its one caller dispatches with 64, so no kind is left unlaunched
+    if (kind == SEQ_CAUSAL) PROF_LAUNCH(ctx, MHIP_K_ATTN_CAUSAL, hipLaunchKernelGGL((attn_seq_rows_kernel<T, 64, true, false>), rows, threads, 0, ctx->stream, a));
   }
-  if (kind == SEQ_SHORT) PROF_LAUNCH(ctx, MHIP_K_ATTN_SHORT, hipLaunchKernelGGL((attn_seq_rows_kernel<T, HD, false>), rows, threads, 0, ctx->stream, a));
+  if (kind == SEQ_SHORT) PROF_LAUNCH(ctx, MHIP_K_ATTN_SHORT, hipLaunchKernelGGL((attn_seq_rows_kernel<T, HD, false, REL>), rows, threads, 0, ctx->stream, a));
   // no slot of its own: the profiler's list is pinned, and a call runs one of the two attentions
-  if (kind == SEQ_LONG) PROF_LAUNCH(ctx, MHIP_K_ATTN_SHORT, hipLaunchKernelGGL((attn_seq_stream_kernel<T, HD>), blocks, threads, 0, ctx->stream, a));
+  if (kind == SEQ_LONG) PROF_LAUNCH(ctx, MHIP_K_ATTN_SHORT, hipLaunchKernelGGL((attn_seq_stream_kernel<T, HD, REL>), blocks, threads, 0, ctx->stream, a));
 }
 
-void seq_dispatch(mhip_ctx* ctx, int precision, int head_dim, SeqKind kind, const AttnDesc& d, const int* len, const float* slopes) {
+template <bool REL>
+void seq_dispatch(mhip_ctx* ctx, int precision, int head_dim, SeqKind kind, const AttnDesc& d, const int* len, const float* slopes,
+                  const float* rel = nullptr, int rel_r = 0) {
   if (precision == MHIP_PREC_F16) {
-    if (head_dim == 64) seq_launch<_Float16, 64>(ctx, kind, d, len, slopes);
-    else seq_launch<_Float16, 32>(ctx, kind, d, len, slopes);
+    if (head_dim == 64) seq_launch<_Float16, 64, REL>(ctx, kind, d, len, slopes, rel, rel_r);
+    else seq_launch<_Float16, 32, REL>(ctx, kind, d, len, slopes, rel, rel_r);
   } else {
-    if (head_dim == 64) seq_launch<float, 64>(ctx, kind, d, len, slopes);
-    else seq_launch<float, 32>(ctx, kind, d, len, slopes);
+    if (head_dim == 64) seq_launch<float, 64, REL>(ctx, kind, d, len, slopes, rel, rel_r);
+    else seq_launch<float, 32, REL>(ctx, kind, d, len, slopes, rel, rel_r);
   }
 }
 
@@ -402,10 +441,14 @@ int seq_lengths_entry(mhip_ctx* ctx, const char* name, int max_rows, SeqKind kin
   const AttnDesc& d = s.a;
   if (s.head_dim != 64 && s.head_dim != 32) return mhip_fail(ctx, MHIP_EINVAL, "%s: head_dim %d (64 or 32)", name, s.head_dim);
   if (!s.len) return mhip_fail(ctx, MHIP_EINVAL, "%s: len is null", name);
+  if (s.rel_table && s.slopes) return mhip_fail(ctx, MHIP_EINVAL, "%s: slopes and rel_table together (one bias term a call)", name);
+  if (s.rel_table && (s.rel_radius < 0 || s.rel_radius > SEQ_MAXROWS))
+    return mhip_fail(ctx, MHIP_EINVAL, "%s: rel_radius %d (0 .. %d)", name, s.rel_radius, SEQ_MAXROWS);
   if (const int rc = seq_check(ctx, name, max_rows, precision, d)) return rc;
   // the lengths live on the device: counted as full sequences
   if (ctx->profiling) ctx->prof[MHIP_K_ATTN_SHORT].flops += 4.0 * d.images * d.heads * (double)d.npad_k * d.npad_k * s.head_dim;
-  seq_dispatch(ctx, precision, s.head_dim, kind, d, s.len, s.slopes);
+  if (s.rel_table) seq_dispatch<true>(ctx, precision, s.head_dim, kind, d, s.len, nullptr, s.rel_table, s.rel_radius);
+  else seq_dispatch<false>(ctx, precision, s.head_dim, kind, d, s.len, s.slopes);
   return 0;
 }
 
@@ -416,7 +459,7 @@ int mhip_launch_attention_causal(mhip_ctx* ctx, int precision, const AttnDesc& d
   if (d.n_queries != d.n_keys || d.n_keys < 1 || d.n_keys > d.npad_k)
     return mhip_fail(ctx, MHIP_EINVAL, "attention_causal: %d queries, %d keys in %d rows", d.n_queries, d.n_keys, d.npad_k);
   if (ctx->profiling) ctx->prof[MHIP_K_ATTN_CAUSAL].flops += 2.0 * d.images * d.heads * (double)d.n_keys * (d.n_keys + 1) * 64;
-  seq_dispatch(ctx, precision, 64, SEQ_CAUSAL, d, nullptr, nullptr);
+  seq_dispatch<false>(ctx, precision, 64, SEQ_CAUSAL, d, nullptr, nullptr);
   CHECK_LAUNCH(ctx, "attention_causal");
   return 0;
 }

@@ -1,11 +1,13 @@
 // berttext_api.hip — BERT sentence encoders (the text embeddings of SentenceTransformerEmbeddings and JinaEmbeddings) behind the
-// C ABI.
+// C ABI, and the three families that differ from BERT in the embedding front and one score term: RoBERTa (position rows from
+// pad_id + 1), DistilBERT (no token types) and MPNet (both, and a relative attention bias shared by the layers).
 //
 // Host-side counterpart of SentenceTransformer.encode as marie/embeddings/sentence_transformers/sentence_transformers_embeddings.py
 // and marie/embeddings/jina/jina_embeddings.py drive it: BertModel.forward without the pooler (transformers/models/bert/
 // modeling_bert.py: BertEmbeddings, BertLayer under the padding mask), or JinaBERT (no position table, a symmetric ALiBi bias on
-// the scores, a gated GELU MLP), then the Pooling (mean over the attention mask, or the [CLS] row) and Normalize modules.  One
-// object = one weight arena + the launch sequence.
+// the scores, a gated GELU MLP), or MPNetModel (transformers/models/mpnet/modeling_mpnet.py: MPNetEncoder.compute_position_bias
+// folded into a table over the clamped distance query - key, `rel`), then the Pooling (mean over the attention mask, or the
+// [CLS] row) and Normalize modules.  One object = one weight arena + the launch sequence.
 //
 // Row layout: every text owns `npad` rows (a multiple of 8, the same for the whole call) of which its first len[b] are its
 // tokens; the rest carry the [PAD] id, are computed like any other row and are never a key.  The residual stream h is fp32.  The
@@ -22,15 +24,17 @@ struct mhip_berttext {
   mhip_ctx* ctx = nullptr;
   int precision = MHIP_PREC_F16;
   mhip_berttext_config cfg{};
+  int pos_offset = 0, rel_buckets = 0, rel_max_distance = 0;      // mhip_berttext_config_ex's; zero through mhip_berttext_create
   TensorStore store;
   Arena arena;
   bool ready = false;
   size_t esz() const { return precision == MHIP_PREC_F16 ? 2 : 4; }
   int head_dim() const { return cfg.dim / cfg.heads; }
   bool alibi() const { return cfg.position == BT_POS_ALIBI; }
+  bool rel() const { return rel_buckets > 0; }
   bool geglu() const { return cfg.mlp == BT_MLP_GEGLU; }
   // tokens of a text: the streamed attention's 8192, or the position table's rows when it has fewer
-  int max_tokens() const { return alibi() ? 8192 : std::min(cfg.max_position, 8192); }
+  int max_tokens() const { return alibi() ? 8192 : std::min(cfg.max_position - pos_offset, 8192); }
   int max_npad() const { return (max_tokens() + 7) / 8 * 8; }
 };
 
@@ -65,6 +69,24 @@ void berttext_carve(const mhip_berttext* m, Carver& ws, int B, int npad, int n_p
 }
 
 bool npad_ok(int npad, int max_npad) { return npad >= 8 && npad % 8 == 0 && npad <= max_npad; }
+
+// MPNet's relative attention bias as a function of d = query - key clamped to +-R (R = max_distance): out[h][d + R] =
+// weight[bucket(-d)][h] * scale, the bucket MPNetEncoder.relative_position_bucket's (the T5 rule, in float32 as the library takes
+// it: mhip_relative_position_bucket).  false where the rule is not defined (max_distance <= buckets / 4) or the bucket still
+// changes past +-R, up to the MAX_LONG_ROWS rows a text can have: the clamp would then differ from the model
+bool rel_table_fold(int buckets, int R, const float* weight, int heads, double scale, float* out) {
+  if (R <= buckets / 4) return false;
+  for (int sign = -1; sign <= 1; sign += 2) {
+    const int at_r = mhip_relative_position_bucket(sign * R, buckets, R);
+    for (int n = R + 1; n <= MAX_LONG_ROWS; ++n)
+      if (mhip_relative_position_bucket(sign * n, buckets, R) != at_r) return false;
+  }
+  for (int d = -R; d <= R; ++d) {
+    const int bucket = mhip_relative_position_bucket(-d, buckets, R);
+    for (int h = 0; h < heads; ++h) out[(size_t)h * (2 * R + 1) + d + R] = (float)((double)weight[(size_t)bucket * heads + h] * scale);
+  }
+  return true;
+}
 
 // ALiBi slopes of n heads: for n a power of two 2^(-8 (i + 1) / n); otherwise those of the largest power of two p <= n, then the
 // even-indexed slopes of 2 p, the first n - p of them
@@ -116,8 +138,9 @@ int berttext_forward(mhip_berttext* m, int B, int npad, const BertRun& run, floa
   const Arena& a = m->arena;
   const EncoderWs& w = run.w;
   int rc;
-  if ((rc = mhip_launch_berttext_embed(ctx, prec, a.d<float>("word"), a.d<float>("type0"), m->alibi() ? nullptr : a.d<float>("pos"),
-                                       a.d<float>("ln_emb_g"), a.d<float>("ln_emb_b"), c.ln_eps, run.ids, run.h, w.ht, B, npad, D)))
+  if ((rc = mhip_launch_berttext_embed(ctx, prec, a.d<float>("word"), c.type_vocab ? a.d<float>("type0") : nullptr,
+                                       m->alibi() ? nullptr : a.d<float>("pos"), a.d<float>("ln_emb_g"), a.d<float>("ln_emb_b"), c.ln_eps,
+                                       run.ids, run.h, w.ht, B, npad, D, m->pos_offset)))
     return rc;
   auto tap = [&](int i) -> int {
     if (!taps) return MHIP_OK;
@@ -130,6 +153,10 @@ int berttext_forward(mhip_berttext* m, int B, int npad, const BertRun& run, floa
   sd.len = run.len;
   sd.slopes = m->alibi() ? a.d<float>("alibi") : nullptr;
   sd.head_dim = m->head_dim();
+  if (m->rel()) {
+    sd.rel_table = a.d<float>("rel");
+    sd.rel_radius = m->rel_max_distance;
+  }
   for (int i = 0; i < c.depth; ++i) {
     if ((rc = encoder_block_attention(ctx, prec, a, i, w, sd))) return rc;
     if ((rc = mhip_gemm(ctx, prec, w.ao, a.d(enc_blk(i, "ao_w")), (long long)R, D, D, nullptr, a.d<float>(enc_blk(i, "ao_b")), run.y, ACT_NONE, 1, run.h))) return rc;
@@ -180,11 +207,12 @@ bool bert_layer_weights(mhip_ctx* ctx, const TensorStore& st, int i, int D, int 
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------- lifecycle
-extern "C" int mhip_berttext_create(mhip_ctx* ctx, int precision, const mhip_berttext_config* cfg, mhip_berttext** out) {
+extern "C" int mhip_berttext_create_ex(mhip_ctx* ctx, int precision, const mhip_berttext_config_ex* cfg, mhip_berttext** out) {
   if (!ctx || !out || !cfg) return MHIP_EINVAL;
   *out = nullptr;
   if (precision != MHIP_PREC_F16 && precision != MHIP_PREC_F32) return mhip_fail(ctx, MHIP_EINVAL, "unknown precision %d", precision);
-  const mhip_berttext_config& c = *cfg;
+  const mhip_berttext_config& c = cfg->base;
+  const mhip_berttext_config_ex& x = *cfg;
   if (c.dim < 64 || c.dim % 64 || c.dim > 1024) return mhip_fail(ctx, MHIP_EINVAL, "berttext: dim %d (a multiple of 64 up to 1024)", c.dim);
   if (c.heads < 1 || c.dim % c.heads || (c.dim / c.heads != 64 && c.dim / c.heads != 32))
     return mhip_fail(ctx, MHIP_EINVAL, "berttext: heads %d at dim %d: a head dimension of %d, the attention kernel has heads of 64 or 32", c.heads, c.dim,
@@ -192,27 +220,47 @@ extern "C" int mhip_berttext_create(mhip_ctx* ctx, int precision, const mhip_ber
   if (c.ffn < 64 || c.ffn % 64) return mhip_fail(ctx, MHIP_EINVAL, "berttext: ffn %d (a multiple of 64)", c.ffn);
   if (c.depth < 1) return mhip_fail(ctx, MHIP_EINVAL, "berttext: depth %d", c.depth);
   if (c.vocab < 2 || c.vocab > (1 << 24)) return mhip_fail(ctx, MHIP_EINVAL, "berttext: vocab %d", c.vocab);
-  if (c.type_vocab < 1) return mhip_fail(ctx, MHIP_EINVAL, "berttext: type_vocab %d", c.type_vocab);
+  if (c.type_vocab < 0) return mhip_fail(ctx, MHIP_EINVAL, "berttext: type_vocab %d", c.type_vocab);
   if (c.position != BT_POS_ABSOLUTE && c.position != BT_POS_ALIBI) return mhip_fail(ctx, MHIP_EINVAL, "berttext: position %d (0 absolute, 1 alibi)", c.position);
   if (c.position == BT_POS_ABSOLUTE && c.max_position < 2) return mhip_fail(ctx, MHIP_EINVAL, "berttext: max_position %d", c.max_position);
   if (c.mlp != BT_MLP_GELU && c.mlp != BT_MLP_GEGLU) return mhip_fail(ctx, MHIP_EINVAL, "berttext: mlp %d (0 gelu, 1 geglu)", c.mlp);
   if (c.pool != BT_POOL_MEAN && c.pool != BT_POOL_CLS) return mhip_fail(ctx, MHIP_EINVAL, "berttext: pool %d (0 mean, 1 cls)", c.pool);
   if (c.normalize != 0 && c.normalize != 1) return mhip_fail(ctx, MHIP_EINVAL, "berttext: normalize %d (0 or 1)", c.normalize);
   if (!(c.ln_eps > 0.f)) return mhip_fail(ctx, MHIP_EINVAL, "berttext: ln_eps");
+  if (x.pos_offset < 0 || (x.pos_offset && c.position != BT_POS_ABSOLUTE) || (c.position == BT_POS_ABSOLUTE && c.max_position - x.pos_offset < 2))
+    return mhip_fail(ctx, MHIP_EINVAL, "berttext: pos_offset %d (0 .. max_position - 2 = %d with a position table, 0 without)", x.pos_offset, c.max_position - 2);
+  if (x.rel_buckets < 0 || (x.rel_buckets && (x.rel_buckets < 4 || x.rel_buckets % 2 || x.rel_buckets > 4096)))
+    return mhip_fail(ctx, MHIP_EINVAL, "berttext: rel_buckets %d (0: no relative attention bias; otherwise even, 4 .. 4096)", x.rel_buckets);
+  if (x.rel_buckets && c.position == BT_POS_ALIBI)
+    return mhip_fail(ctx, MHIP_EINVAL, "berttext: rel_buckets %d with position alibi: slopes and a relative table together", x.rel_buckets);
+  if (x.rel_buckets ? (x.rel_max_distance < 1 || x.rel_max_distance > MAX_LONG_ROWS) : x.rel_max_distance != 0)
+    return mhip_fail(ctx, MHIP_EINVAL, "berttext: rel_max_distance %d (1 .. %d with rel_buckets, 0 without)", x.rel_max_distance, MAX_LONG_ROWS);
   mhip_berttext* m = new mhip_berttext();
   m->ctx = ctx;
   m->precision = precision;
   m->cfg = c;
+  m->pos_offset = x.pos_offset; m->rel_buckets = x.rel_buckets; m->rel_max_distance = x.rel_max_distance;
   const size_t es = m->esz(), D = c.dim;
   Arena& a = m->arena;
   a.take("word", (size_t)c.vocab * D * 4);
-  a.take("type0", D * 4);
+  if (c.type_vocab) a.take("type0", D * 4);
   if (m->alibi()) a.take("alibi", (size_t)c.heads * 4);
-  else a.take("pos", (size_t)m->max_npad() * D * 4);      // rows past the table (padding rows only) are zeros
+  else a.take("pos", (size_t)(m->pos_offset + m->max_npad()) * D * 4);      // rows past the table (padding rows only) are zeros
+  if (m->rel()) a.take("rel", (size_t)c.heads * (2 * m->rel_max_distance + 1) * 4);
   a.take("ln_emb_g", D * 4); a.take("ln_emb_b", D * 4);
   for (int i = 0; i < c.depth; ++i) encoder_block_take(a, i, D, c.ffn, es, m->geglu());
   *out = m;
   return MHIP_OK;
+}
+
+// the twelve fields of mhip_berttext_config alone: a token type table is required, as it always was
+extern "C" int mhip_berttext_create(mhip_ctx* ctx, int precision, const mhip_berttext_config* cfg, mhip_berttext** out) {
+  if (!ctx || !out || !cfg) return MHIP_EINVAL;
+  *out = nullptr;
+  if (cfg->type_vocab < 1) return mhip_fail(ctx, MHIP_EINVAL, "berttext: type_vocab %d", cfg->type_vocab);
+  mhip_berttext_config_ex x{};
+  x.base = *cfg;
+  return mhip_berttext_create_ex(ctx, precision, &x, out);
 }
 
 extern "C" int mhip_berttext_destroy(mhip_berttext* m) {
@@ -228,7 +276,7 @@ extern "C" int mhip_berttext_set_tensor(mhip_berttext* m, const char* key, const
   std::string k(key);
   if (k.rfind("bert.", 0) == 0) k = k.substr(5);
   if (k.rfind("pooler.", 0) == 0 || k == "embeddings.position_ids") return MHIP_OK;
-  if (k.rfind("embeddings.", 0) != 0 && k.rfind("encoder.layer.", 0) != 0) return mhip_fail(m->ctx, MHIP_EINVAL, "unknown state_dict key %s", key);
+  if (k.rfind("embeddings.", 0) != 0 && k.rfind("encoder.layer.", 0) != 0 && k != "encoder.relative_attention_bias.weight") return mhip_fail(m->ctx, MHIP_EINVAL, "unknown state_dict key %s", key);
   m->ready = false;
   return m->store.set(m->ctx, k, data, shape, ndim);
 }
@@ -258,14 +306,14 @@ extern "C" int mhip_berttext_finalize(mhip_berttext* m) {
   a.begin_fill();
   const HostTensor* word = st.find(ctx, "embeddings.word_embeddings.weight", {c.vocab, D});
   if (!word) return MHIP_ESTATE;
-  const HostTensor* type = st.find(ctx, "embeddings.token_type_embeddings.weight", {c.type_vocab, D});
-  if (!type) return MHIP_ESTATE;
+  const HostTensor* type = c.type_vocab ? st.find(ctx, "embeddings.token_type_embeddings.weight", {c.type_vocab, D}) : nullptr;
+  if (c.type_vocab && !type) return MHIP_ESTATE;
   const HostTensor* g0 = st.find(ctx, "embeddings.LayerNorm.weight", {D});
   if (!g0) return MHIP_ESTATE;
   const HostTensor* b0 = st.find(ctx, "embeddings.LayerNorm.bias", {D});
   if (!b0) return MHIP_ESTATE;
   memcpy(a.h("word"), word->data.data(), word->numel() * 4);
-  memcpy(a.h("type0"), type->data.data(), (size_t)D * 4);
+  if (type) memcpy(a.h("type0"), type->data.data(), (size_t)D * 4);
   memcpy(a.h("ln_emb_g"), g0->data.data(), (size_t)D * 4); memcpy(a.h("ln_emb_b"), b0->data.data(), (size_t)D * 4);
   if (m->alibi()) {
     const std::vector<double> s = alibi_slopes(c.heads);
@@ -274,7 +322,17 @@ extern "C" int mhip_berttext_finalize(mhip_berttext* m) {
   } else {
     const HostTensor* pos = st.find(ctx, "embeddings.position_embeddings.weight", {c.max_position, D});
     if (!pos) return MHIP_ESTATE;
-    memcpy(a.h("pos"), pos->data.data(), (size_t)std::min(c.max_position, m->max_npad()) * D * 4);
+    memcpy(a.h("pos"), pos->data.data(), (size_t)std::min(c.max_position, m->pos_offset + m->max_npad()) * D * 4);
+  }
+  if (m->rel()) {
+    const HostTensor* bias = st.find(ctx, "encoder.relative_attention_bias.weight", {m->rel_buckets, c.heads});
+    if (!bias) return MHIP_ESTATE;
+    for (float v : bias->data)
+      if (!std::isfinite(v)) return mhip_fail(ctx, MHIP_EINVAL, "berttext: encoder.relative_attention_bias.weight holds a non-finite value");
+    // the scores are in log2 units
+    if (!rel_table_fold(m->rel_buckets, m->rel_max_distance, bias->data.data(), c.heads, LOG2E, (float*)a.h("rel")))
+      return mhip_fail(ctx, MHIP_EINVAL, "berttext: rel_max_distance %d: the bucket of %d buckets still changes past that distance, the table cannot clamp there",
+                       m->rel_max_distance, m->rel_buckets);
   }
   const float scale = (float)(LOG2E / sqrt((double)m->head_dim()));
   for (int i = 0; i < c.depth; ++i) {
@@ -300,6 +358,13 @@ extern "C" int mhip_berttext_alibi_slopes(int heads, float* slopes_out) {
   const std::vector<double> s = alibi_slopes(heads);
   for (int h = 0; h < heads; ++h) slopes_out[h] = (float)s[h];
   return MHIP_OK;
+}
+
+extern "C" int mhip_berttext_rel_table(int buckets, int max_distance, const float* weight, int heads, float* table_out) {
+  if (buckets < 4 || buckets % 2 || buckets > 4096 || max_distance < 1 || max_distance > MAX_LONG_ROWS || heads < 1 || heads > 4096 || !weight ||
+      !table_out)
+    return MHIP_EINVAL;
+  return rel_table_fold(buckets, max_distance, weight, heads, 1.0, table_out) ? MHIP_OK : MHIP_EINVAL;
 }
 
 // ---------------------------------------------------------------------------------------------------- forward
@@ -351,37 +416,54 @@ extern "C" int mhip_berttext_debug_taps_host(mhip_berttext* m, const int32_t* id
 }
 
 // ---------------------------------------------------------------------------------------------------- the kernels alone
-extern "C" int mhip_berttext_embed_rows_host(mhip_ctx* ctx, const float* word, const float* type0, const float* pos, const float* g,
-                                             const float* b, float eps, const int32_t* ids, int B, int npad, int vocab, int D, float* h_out) {
-  if (!ctx || !word || !type0 || !g || !b || !ids || !h_out) return MHIP_EINVAL;
-  if (B < 1 || B > MAX_TEXTS || !npad_ok(npad, MAX_ROWS) || vocab < 1 || vocab > (1 << 24) || D < 64 || D % 64 || D > 1024 || !(eps > 0.f))
-    return mhip_fail(ctx, MHIP_EINVAL, "berttext_embed: B=%d npad=%d vocab=%d D=%d", B, npad, vocab, D);
-  const size_t R = (size_t)B * npad;
+// the one body of the two embedding entries: type0 may be null, pos holds pos_offset + npad rows
+static int berttext_embed_rows_run(mhip_ctx* ctx, const float* word, const float* type0, const float* pos, const float* g, const float* b,
+                                   float eps, const int32_t* ids, int B, int npad, int vocab, int D, int pos_offset, float* h_out) {
+  if (!ctx || !word || !g || !b || !ids || !h_out) return MHIP_EINVAL;
+  if (B < 1 || B > MAX_TEXTS || !npad_ok(npad, MAX_ROWS) || vocab < 1 || vocab > (1 << 24) || D < 64 || D % 64 || D > 1024 || !(eps > 0.f) ||
+      pos_offset < 0 || pos_offset > MAX_LONG_ROWS)
+    return mhip_fail(ctx, MHIP_EINVAL, "berttext_embed: B=%d npad=%d vocab=%d D=%d pos_offset=%d", B, npad, vocab, D, pos_offset);
+  const size_t R = (size_t)B * npad, PR = (size_t)pos_offset + npad;
   for (size_t e = 0; e < R; ++e)
     if (ids[e] < 0 || ids[e] >= vocab) return mhip_fail(ctx, MHIP_EINVAL, "berttext_embed: id %d outside the vocabulary of %d", ids[e], vocab);
   MHIP_HIP(ctx, hipSetDevice(ctx->device));
   float *dw = nullptr, *dt = nullptr, *dp = nullptr, *dg = nullptr, *db = nullptr, *dh = nullptr;
   int* di = nullptr;
   int rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
-    dw = ws.take<float>((size_t)vocab * D * 4); dt = ws.take<float>((size_t)D * 4); dp = ws.take<float>((size_t)npad * D * 4);
+    dw = ws.take<float>((size_t)vocab * D * 4); dt = ws.take<float>((size_t)D * 4); dp = ws.take<float>(PR * D * 4);
     dg = ws.take<float>((size_t)D * 4); db = ws.take<float>((size_t)D * 4); di = ws.take<int>(R * 4); dh = ws.take<float>(R * D * 4);
   });
   if (rc) return rc;
   MHIP_HIP(ctx, hipMemcpyAsync(dw, word, (size_t)vocab * D * 4, hipMemcpyHostToDevice, ctx->stream));
-  MHIP_HIP(ctx, hipMemcpyAsync(dt, type0, (size_t)D * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (pos) MHIP_HIP(ctx, hipMemcpyAsync(dp, pos, (size_t)npad * D * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (type0) MHIP_HIP(ctx, hipMemcpyAsync(dt, type0, (size_t)D * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (pos) MHIP_HIP(ctx, hipMemcpyAsync(dp, pos, PR * D * 4, hipMemcpyHostToDevice, ctx->stream));
   MHIP_HIP(ctx, hipMemcpyAsync(dg, g, (size_t)D * 4, hipMemcpyHostToDevice, ctx->stream));
   MHIP_HIP(ctx, hipMemcpyAsync(db, b, (size_t)D * 4, hipMemcpyHostToDevice, ctx->stream));
   MHIP_HIP(ctx, hipMemcpyAsync(di, ids, R * 4, hipMemcpyHostToDevice, ctx->stream));
-  if ((rc = mhip_launch_berttext_embed(ctx, MHIP_PREC_F32, dw, dt, pos ? dp : nullptr, dg, db, eps, di, dh, nullptr, B, npad, D))) return rc;
+  if ((rc = mhip_launch_berttext_embed(ctx, MHIP_PREC_F32, dw, type0 ? dt : nullptr, pos ? dp : nullptr, dg, db, eps, di, dh, nullptr, B, npad, D,
+                                       pos_offset)))
+    return rc;
   MHIP_HIP(ctx, hipMemcpyAsync(h_out, dh, R * D * 4, hipMemcpyDeviceToHost, ctx->stream));
   MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return MHIP_OK;
 }
 
+extern "C" int mhip_berttext_embed_rows_host(mhip_ctx* ctx, const float* word, const float* type0, const float* pos, const float* g,
+                                             const float* b, float eps, const int32_t* ids, int B, int npad, int vocab, int D, float* h_out) {
+  if (!type0) return MHIP_EINVAL;
+  return berttext_embed_rows_run(ctx, word, type0, pos, g, b, eps, ids, B, npad, vocab, D, 0, h_out);
+}
+
+extern "C" int mhip_berttext_embed_rows_ex_host(mhip_ctx* ctx, const float* word, const float* type0, const float* pos, const float* g,
+                                                const float* b, float eps, const int32_t* ids, int B, int npad, int vocab, int D,
+                                                int pos_offset, float* h_out) {
+  return berttext_embed_rows_run(ctx, word, type0, pos, g, b, eps, ids, B, npad, vocab, D, pos_offset, h_out);
+}
+
 // the one body of the two attention entries: attn_short (npad <= 128) or, streamed, attn_long (npad <= 8192)
 static int berttext_attention_run(mhip_ctx* ctx, int precision, const float* q, const float* k, const float* v, const int32_t* len,
-                                  const float* slopes, int B, int heads, int head_dim, int npad, float* out, bool streamed) {
+                                  const float* slopes, const float* table, int radius, int B, int heads, int head_dim, int npad, float* out,
+                                  bool streamed) {
   if (!ctx || !q || !k || !v || !len || !out) return MHIP_EINVAL;
   if (precision != MHIP_PREC_F16 && precision != MHIP_PREC_F32) return mhip_fail(ctx, MHIP_EINVAL, "unknown precision %d", precision);
   if (head_dim != 64 && head_dim != 32) return mhip_fail(ctx, MHIP_EINVAL, "berttext_attention: head_dim %d (64 or 32)", head_dim);
@@ -390,30 +472,53 @@ static int berttext_attention_run(mhip_ctx* ctx, int precision, const float* q, 
     return mhip_fail(ctx, MHIP_EINVAL, "berttext_attention: B=%d heads=%d npad=%d", B, heads, npad);
   for (int b = 0; b < B; ++b)
     if (len[b] < 1 || len[b] > npad) return mhip_fail(ctx, MHIP_EINVAL, "berttext_attention: sequence %d has %d keys (1 .. %d)", b, len[b], npad);
+  const size_t tn = table ? (size_t)heads * (2 * (size_t)radius + 1) : 0;
+  if (table) {
+    if (radius < 0 || radius > MAX_LONG_ROWS) return mhip_fail(ctx, MHIP_EINVAL, "berttext_attention: radius %d (0 .. %d)", radius, MAX_LONG_ROWS);
+    for (size_t e = 0; e < tn; ++e)      // the whole-row kernel masks by a -inf initial value: the term must not undo it
+      if (!std::isfinite(table[e])) return mhip_fail(ctx, MHIP_EINVAL, "berttext_attention: the table holds a non-finite value (head %zu)", e / (2 * (size_t)radius + 1));
+  }
   MHIP_HIP(ctx, hipSetDevice(ctx->device));
-  float* dsl = nullptr;
+  float *dsl = nullptr, *dtab = nullptr;
   int* dlen = nullptr;
   return encoder_attention_host(
       ctx, precision, q, k, v, B, heads, head_dim, npad, out,
-      [&](Carver& ws) { dlen = ws.take<int>((size_t)B * 4); dsl = ws.take<float>((size_t)heads * 4); },
-      [&](const AttnDesc& ad) {      // len and slopes are the caller's: they outlive the call's last synchronisation
+      [&](Carver& ws) {
+        dlen = ws.take<int>((size_t)B * 4); dsl = ws.take<float>((size_t)heads * 4);
+        if (tn) dtab = ws.take<float>(tn * 4);
+      },
+      [&](const AttnDesc& ad) {      // len, slopes and table are the caller's: they outlive the call's last synchronisation
         MHIP_HIP(ctx, hipMemcpyAsync(dlen, len, (size_t)B * 4, hipMemcpyHostToDevice, ctx->stream));
         if (slopes) MHIP_HIP(ctx, hipMemcpyAsync(dsl, slopes, (size_t)heads * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (tn) MHIP_HIP(ctx, hipMemcpyAsync(dtab, table, tn * 4, hipMemcpyHostToDevice, ctx->stream));
         AttnShortDesc sd;
         sd.a = ad; sd.len = dlen; sd.slopes = slopes ? dsl : nullptr; sd.head_dim = head_dim;
+        sd.rel_table = tn ? dtab : nullptr; sd.rel_radius = tn ? radius : 0;
         return streamed ? mhip_launch_attention_long(ctx, precision, sd) : mhip_launch_attention_short(ctx, precision, sd);
       });
 }
 
 extern "C" int mhip_berttext_attention_host(mhip_ctx* ctx, int precision, const float* q, const float* k, const float* v, const int32_t* len,
                                             const float* slopes, int B, int heads, int head_dim, int npad, float* out) {
-  return berttext_attention_run(ctx, precision, q, k, v, len, slopes, B, heads, head_dim, npad, out, false);
+  return berttext_attention_run(ctx, precision, q, k, v, len, slopes, nullptr, 0, B, heads, head_dim, npad, out, false);
 }
 
 extern "C" int mhip_berttext_attention_long_host(mhip_ctx* ctx, int precision, const float* q, const float* k, const float* v,
                                                  const int32_t* len, const float* slopes, int B, int heads, int head_dim, int npad,
                                                  float* out) {
-  return berttext_attention_run(ctx, precision, q, k, v, len, slopes, B, heads, head_dim, npad, out, true);
+  return berttext_attention_run(ctx, precision, q, k, v, len, slopes, nullptr, 0, B, heads, head_dim, npad, out, true);
+}
+
+extern "C" int mhip_berttext_attention_rel_host(mhip_ctx* ctx, int precision, const float* q, const float* k, const float* v,
+                                                const int32_t* len, const float* table, int radius, int B, int heads, int head_dim, int npad,
+                                                float* out) {
+  return berttext_attention_run(ctx, precision, q, k, v, len, nullptr, table, radius, B, heads, head_dim, npad, out, false);
+}
+
+extern "C" int mhip_berttext_attention_rel_long_host(mhip_ctx* ctx, int precision, const float* q, const float* k, const float* v,
+                                                     const int32_t* len, const float* table, int radius, int B, int heads, int head_dim,
+                                                     int npad, float* out) {
+  return berttext_attention_run(ctx, precision, q, k, v, len, nullptr, table, radius, B, heads, head_dim, npad, out, true);
 }
 
 extern "C" int mhip_berttext_geglu_host(mhip_ctx* ctx, int precision, const float* x, int R, int F, float* out) {

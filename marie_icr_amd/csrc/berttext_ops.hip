@@ -2,7 +2,9 @@
 // LayerNorm front, the post-LayerNorm of a layer at widths that are no multiple of 256, GEGLU and masked pooling.  (Their
 // attention over sequences of different lengths, attn_short and attn_long, is attn_seq.hip.)
 //
-// Replaces, in transformers/models/bert/modeling_bert.py: BertEmbeddings.forward, the LayerNorms of BertSelfOutput / BertOutput;
+// Replaces, in transformers/models/bert/modeling_bert.py: BertEmbeddings.forward (and the embeddings of RoBERTa and MPNet, whose
+// position rows start at pad_id + 1, and of DistilBERT and MPNet, which have no token types), the LayerNorms of BertSelfOutput /
+// BertOutput;
 // of JinaBERT the gated MLP's activation; and the Pooling (mean / cls) and Normalize modules of sentence_transformers.
 #include <algorithm>
 
@@ -31,24 +33,26 @@ __device__ __forceinline__ void store_row(const float4v v[ROW_GROUPS], float* __
   }
 }
 
-// h[seq][t] = LN((word[ids[seq][t]] + type0) + pos[t]) (pos null: no position table), one wave per row, 16 bytes a lane
+// h[seq][t] = LN((word[ids[seq][t]] + type0) + pos[pos_offset + t]) (type0 null: no token types; pos null: no position table), one
+// wave per row, 16 bytes a lane
 template <typename T>
 __global__ __launch_bounds__(256) void berttext_embed_kernel(const float* __restrict__ word, const float* __restrict__ type0,
                                                              const float* __restrict__ pos, const float* __restrict__ g,
                                                              const float* __restrict__ b, const int* __restrict__ ids,
                                                              float* __restrict__ h, T* __restrict__ ht, int rows, int npad, int D,
-                                                             float eps) {
+                                                             float eps, int pos_offset) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= rows) return;
   const float* src = word + (size_t)ids[row] * D;
-  const float* pp = pos ? pos + (size_t)(row % npad) * D : nullptr;
+  const float* pp = pos ? pos + (size_t)(pos_offset + row % npad) * D : nullptr;
   float4v v[ROW_GROUPS];
 #pragma unroll
   for (int i = 0; i < ROW_GROUPS; ++i) {
     const int c = (i * 64 + lane) * 4;
     v[i] = (float4v){0.f, 0.f, 0.f, 0.f};
     if (c < D) {
-      v[i] = *(const float4v*)(src + c) + *(const float4v*)(type0 + c);
+      v[i] = *(const float4v*)(src + c);
+      if (type0) v[i] += *(const float4v*)(type0 + c);
       if (pp) v[i] += *(const float4v*)(pp + c);
     }
   }
@@ -127,14 +131,14 @@ inline int grid_for(long long total, int block) { return (int)std::min<long long
 }  // namespace
 
 int mhip_launch_berttext_embed(mhip_ctx* ctx, int precision, const float* word, const float* type0, const float* pos, const float* g,
-                               const float* b, float eps, const int* ids, float* h, void* ht, int B, int npad, int D) {
-  if (B <= 0 || npad < 1 || !row_width_ok(D)) return mhip_fail(ctx, MHIP_EINVAL, "berttext_embed: B=%d npad=%d D=%d", B, npad, D);
+                               const float* b, float eps, const int* ids, float* h, void* ht, int B, int npad, int D, int pos_offset) {
+  if (B <= 0 || npad < 1 || !row_width_ok(D) || pos_offset < 0) return mhip_fail(ctx, MHIP_EINVAL, "berttext_embed: B=%d npad=%d D=%d", B, npad, D);
   const int rows = B * npad;
   dim3 grid((rows + 3) / 4), block(256);
   if (precision == MHIP_PREC_F16)
-    PROF_LAUNCH(ctx, MHIP_K_BERTTEXT_EMBED, hipLaunchKernelGGL(berttext_embed_kernel<_Float16>, grid, block, 0, ctx->stream, word, type0, pos, g, b, ids, h, (_Float16*)ht, rows, npad, D, eps));
+    PROF_LAUNCH(ctx, MHIP_K_BERTTEXT_EMBED, hipLaunchKernelGGL(berttext_embed_kernel<_Float16>, grid, block, 0, ctx->stream, word, type0, pos, g, b, ids, h, (_Float16*)ht, rows, npad, D, eps, pos_offset));
   else
-    PROF_LAUNCH(ctx, MHIP_K_BERTTEXT_EMBED, hipLaunchKernelGGL(berttext_embed_kernel<float>, grid, block, 0, ctx->stream, word, type0, pos, g, b, ids, h, (float*)ht, rows, npad, D, eps));
+    PROF_LAUNCH(ctx, MHIP_K_BERTTEXT_EMBED, hipLaunchKernelGGL(berttext_embed_kernel<float>, grid, block, 0, ctx->stream, word, type0, pos, g, b, ids, h, (float*)ht, rows, npad, D, eps, pos_offset));
   CHECK_LAUNCH(ctx, "berttext_embed");
   return 0;
 }

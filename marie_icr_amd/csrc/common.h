@@ -629,12 +629,16 @@ int mhip_launch_attention_causal(mhip_ctx* ctx, int precision, const AttnDesc& d
 // softmax(Q K^T [- slope |i - j|]) V over AttnDesc's layout with heads of head_dim (64 or 32) columns, sequence b attending to its
 // first len[b] keys (device, 1 .. npad; n_queries / n_keys of `a` are not used): npad_q == npad_k <= 128, a multiple of 8; every
 // row < npad is written, nothing past a sequence's rows is read (no slack needed).  slopes (device, [heads], in the log2 units of
-// q) or null: no bias term
+// q) or null: no bias term.  rel_table (device, fp32 [heads][2 rel_radius + 1] in the same log2 units, finite) or null: with it the
+// score of (query i, key j) gets rel_table[head][clamp(i - j, -rel_radius, rel_radius) + rel_radius] (MPNet's relative attention
+// bias).  Slopes and a table together are MHIP_EINVAL
 struct AttnShortDesc {
   AttnDesc a;
   const int* len = nullptr;
   const float* slopes = nullptr;
   int head_dim = 64;
+  const float* rel_table = nullptr;
+  int rel_radius = 0;
 };
 int mhip_launch_attention_short(mhip_ctx* ctx, int precision, const AttnShortDesc& d);
 // the same attention with the keys streamed through LDS in blocks of 128 and an online soft-max: npad_q == npad_k, a multiple of 8,
@@ -643,10 +647,11 @@ int mhip_launch_attention_short(mhip_ctx* ctx, int precision, const AttnShortDes
 // len[b] as zeros), nothing past a sequence's rows is read (no slack needed).  Counted in MHIP_K_ATTN_SHORT
 int mhip_launch_attention_long(mhip_ctx* ctx, int precision, const AttnShortDesc& d);
 // ------------------------------------------------------------------ BERT sentence encoder ops (berttext_ops.hip)
-// h [B*npad][D] fp32 = LN((word[ids[row]] + type0) + pos[row % npad]), ht (null: not written) its copy in the precision's element
-// type; word [vocab][D], type0 [D], pos [>= npad][D] or null (no position table) fp32; the ids are the caller's to check
+// h [B*npad][D] fp32 = LN((word[ids[row]] + type0) + pos[pos_offset + row % npad]), ht (null: not written) its copy in the
+// precision's element type; word [vocab][D], type0 [D] or null (no token types), pos [>= pos_offset + npad][D] or null (no position
+// table) fp32; the ids are the caller's to check
 int mhip_launch_berttext_embed(mhip_ctx* ctx, int precision, const float* word, const float* type0, const float* pos, const float* g,
-                               const float* b, float eps, const int* ids, float* h, void* ht, int B, int npad, int D);
+                               const float* b, float eps, const int* ids, float* h, void* ht, int B, int npad, int D, int pos_offset = 0);
 // h = LN(x) fp32 and ht (null: not written) its copy in the precision's element type; D % 64 == 0, D <= 1024; h may be x
 int mhip_launch_berttext_layernorm(mhip_ctx* ctx, int precision, const float* x, const float* g, const float* b, float* h, void* ht,
                                    int rows, int D, float eps);

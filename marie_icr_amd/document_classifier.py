@@ -116,6 +116,7 @@ class ByteLevelBPE:
         self.bos_id, self.eos_id, self.pad_id, self.unk_id = (self.vocab[t] for t in (bos, eos, pad, unk))
         self._b2u = bytes_to_unicode()
         self._cache: Dict[str, List[int]] = {}
+        self._piece_cache: Dict[str, List[int]] = {}      # text_ids: a piece of the GPT-2 split as it stands, no prefix space
 
     def _bpe(self, token: str) -> List[str]:
         word = list(token)
@@ -151,6 +152,52 @@ class ByteLevelBPE:
             if len(self._cache) < 65536:
                 self._cache[word] = ids
         return ids
+
+    # -- whole texts: the ids the sentence encoders take (``RobertaTokenizer`` on a plain string) ---------------------------
+    @classmethod
+    def from_dir(cls, model_dir) -> Optional["ByteLevelBPE"]:
+        """``vocab.json`` + ``merges.txt`` of a model directory; None where it lacks either"""
+        if model_dir is None:
+            return None
+        vocab, merges = os.path.join(model_dir, "vocab.json"), os.path.join(model_dir, "merges.txt")
+        return cls(vocab, merges) if os.path.isfile(vocab) and os.path.isfile(merges) else None
+
+    def __len__(self) -> int:
+        return len(self.vocab)
+
+    def text_ids(self, text: str) -> List[int]:
+        """the sub-token ids of a whole text: the GPT-2 split of the text as it stands (no prefix space), each piece through
+        the byte alphabet and the merges.  Special tokens written out in the text are not recognised"""
+        ids: List[int] = []
+        for piece in split_gpt2(text):
+            got = self._piece_cache.get(piece)
+            if got is None:
+                sym = "".join(self._b2u[b] for b in piece.encode("utf-8"))
+                got = [self.vocab.get(t, self.unk_id) for t in self._bpe(sym)]
+                if len(self._piece_cache) < 65536:
+                    self._piece_cache[piece] = got
+            ids.extend(got)
+        return ids
+
+    def encode(self, text: str, max_tokens: Optional[int] = None) -> List[int]:
+        """``<s>`` sub-tokens ``</s>`` as ids; with ``max_tokens`` the first ``max_tokens - 2`` sub-tokens are kept"""
+        ids = self.text_ids(text)
+        if max_tokens is not None:
+            if max_tokens < 2:
+                raise ValueError(f"max_tokens of {max_tokens}: <s> and </s> alone are two")
+            ids = ids[:max_tokens - 2]
+        return [self.bos_id] + ids + [self.eos_id]
+
+    def pad(self, encoded: Sequence[Sequence[int]], npad: int) -> Tuple[np.ndarray, np.ndarray]:
+        """id lists -> (ids int32 (n, npad) filled with ``<pad>``, lengths int32 (n,))"""
+        ids = np.full((len(encoded), npad), self.pad_id, np.int32)
+        lens = np.empty(len(encoded), np.int32)
+        for i, e in enumerate(encoded):
+            if len(e) > npad:
+                raise ValueError(f"text {i} has {len(e)} tokens, the rows hold {npad}")
+            ids[i, :len(e)] = e
+            lens[i] = len(e)
+        return ids, lens
 
     def encode_word_offsets(self, word: str) -> Tuple[List[int], List[int]]:
         """Sub-token ids of one OCR word and, per sub-token, the character offset inside the word at which it starts, as

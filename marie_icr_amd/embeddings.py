@@ -19,7 +19,9 @@ towers (RN50, RN101, RN50x4 — the reference's default snippet model) have a lo
 
 The sentence encoders (marie/embeddings/sentence_transformers/sentence_transformers_embeddings.py, marie/embeddings/jina/
 jina_embeddings.py) are at the end of the file: Hugging Face BERT (all-MiniLM-L6-v2) and JinaBERT (ALiBi, GEGLU) with masked mean
-or [CLS] pooling in HIP (csrc/berttext_api.hip, ``mhip_berttext_*``), WordPiece on the host (wordpiece_tokenizer.py).  A text
+or [CLS] pooling in HIP (csrc/berttext_api.hip, ``mhip_berttext_*``), WordPiece on the host (wordpiece_tokenizer.py); and, their
+keys renamed onto BERT's (``load_sentence_encoder_state``), MPNet, RoBERTa and DistilBERT models, the byte-level BPE of
+document_classifier.py for RoBERTa's vocabulary.  A text
 takes its model's own limit, as in the reference: 256 tokens (MiniLM's ``max_seq_length``), 8192 (Jina), never more than the
 position table has rows.  Texts of at most 128 tokens run through the attention kernel that holds a text's keys in LDS, longer
 ones through the one that streams them; the two never share an encoder call.  A text past the limit raises ``ValueError`` unless
@@ -38,8 +40,9 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from ._lib import (PREC_F16, PREC_F32, BertTextConfig, ClipResNetConfig, ClipTextConfig, ClipVisConfig, Context, MarieHipError,
-                   ModelHandle, check, load)
+                   ModelHandle, SentenceEncoderConfig, check, load)
 from .clip_tokenizer import ClipTokenizer
+from .document_classifier import ByteLevelBPE
 from .wordpiece_tokenizer import WordPieceTokenizer
 
 logger = logging.getLogger(__name__)
@@ -868,11 +871,14 @@ def bert_text_keys(cfg: BertTextConfig) -> Dict[str, Tuple[int, ...]]:
     """every tensor the encoder of ``cfg`` takes -> its shape, in the order ``finalize`` looks them up"""
     D, F = cfg.dim, cfg.ffn
     dims = {"d": D, "f": F, "2": 2 * F}
-    keys = {"embeddings.word_embeddings.weight": (cfg.vocab, D),
-            "embeddings.token_type_embeddings.weight": (cfg.type_vocab, D),
-            "embeddings.LayerNorm.weight": (D,), "embeddings.LayerNorm.bias": (D,)}
+    keys = {"embeddings.word_embeddings.weight": (cfg.vocab, D)}
+    if cfg.type_vocab:
+        keys["embeddings.token_type_embeddings.weight"] = (cfg.type_vocab, D)
+    keys.update({"embeddings.LayerNorm.weight": (D,), "embeddings.LayerNorm.bias": (D,)})
     if cfg.position == POS_ABSOLUTE:
         keys["embeddings.position_embeddings.weight"] = (cfg.max_position, D)
+    if getattr(cfg, "rel_buckets", 0):      # a SentenceEncoderConfig
+        keys["encoder.relative_attention_bias.weight"] = (cfg.rel_buckets, cfg.heads)
     for n in range(cfg.depth):
         for name, shape in _BERT_ATTENTION + _BERT_MLP[cfg.mlp]:
             if len(shape) == 2:
@@ -930,6 +936,134 @@ def load_bert_text_state(checkpoint: Dict[str, Any], config_json: Dict[str, Any]
     return state, cfg
 
 
+# ---- the other families: their keys renamed onto BERT's, the differences as configuration
+SENTENCE_FAMILIES = ("bert", "mpnet", "roberta", "distilbert")
+_MPNET_LAYER = {"attention.attn.q": "attention.self.query", "attention.attn.k": "attention.self.key",
+                "attention.attn.v": "attention.self.value", "attention.attn.o": "attention.output.dense",
+                "attention.LayerNorm": "attention.output.LayerNorm", "intermediate.dense": "intermediate.dense",
+                "output.dense": "output.dense", "output.LayerNorm": "output.LayerNorm"}
+_DISTILBERT_LAYER = {"attention.q_lin": "attention.self.query", "attention.k_lin": "attention.self.key",
+                     "attention.v_lin": "attention.self.value", "attention.out_lin": "attention.output.dense",
+                     "sa_layer_norm": "attention.output.LayerNorm", "ffn.lin1": "intermediate.dense", "ffn.lin2": "output.dense",
+                     "output_layer_norm": "output.LayerNorm"}
+
+
+def _family_names(family: str, cfg: BertTextConfig) -> Dict[str, str]:
+    """canonical (BERT) key -> the family's own key, for every tensor the encoder of ``cfg`` takes"""
+    names = {}
+    for key in bert_text_keys(cfg):
+        own = key
+        if key.startswith("encoder.layer.") and family in ("mpnet", "distilbert"):
+            _, _, n, rest = key.split(".", 3)
+            module, leaf = rest.rsplit(".", 1)
+            table = _MPNET_LAYER if family == "mpnet" else _DISTILBERT_LAYER
+            inverse = {v: k for k, v in table.items()}
+            own = f"{'encoder' if family == 'mpnet' else 'transformer'}.layer.{n}.{inverse[module]}.{leaf}"
+        names[key] = own
+    return names
+
+
+def sentence_family(sd: Dict[str, Any], config_json: Dict[str, Any]) -> str:
+    """``model_type`` of ``config.json``; without one, what the keys say"""
+    kind = config_json.get("model_type")
+    if kind is not None:
+        if kind not in SENTENCE_FAMILIES:
+            raise NotImplementedError(f"sentence encoder: model_type {kind!r} is not built ({', '.join(SENTENCE_FAMILIES)} are)")
+        return str(kind)
+    keys = [k.split(".", 1)[1] if k.split(".", 1)[0] in SENTENCE_FAMILIES and "." in k else k for k in sd]
+    if any(k.startswith("transformer.layer.") for k in keys):
+        return "distilbert"
+    if "encoder.relative_attention_bias.weight" in keys or any(".attention.attn.q." in k for k in keys):
+        return "mpnet"
+    if any(k.startswith("roberta.") for k in sd):
+        return "roberta"
+    return "bert"
+
+
+def load_sentence_encoder_state(checkpoint: Dict[str, Any], config_json: Dict[str, Any]) -> Tuple[Dict[str, np.ndarray], BertTextConfig, str]:
+    """A loaded checkpoint of one of ``SENTENCE_FAMILIES`` (an optional ``<family>.`` prefix on its keys) and its
+    ``config.json`` -> (the tensors under the BERT names the encoder takes, plus ``encoder.relative_attention_bias.weight``;
+    the geometry; the family).  ``bert`` goes through :func:`load_bert_text_state` unchanged.  RoBERTa and MPNet count
+    positions from ``pad_token_id + 1``, DistilBERT and MPNet have no token types, MPNet adds its relative attention bias.  A
+    missing or misshapen tensor raises, named by the family's own key."""
+    sd = checkpoint.get("model_state_dict", checkpoint) if isinstance(checkpoint, dict) else None
+    if not isinstance(sd, dict) or not sd:
+        raise MarieHipError("sentence encoder checkpoint: expected a state dict or {'model_state_dict': state dict}")
+    family = sentence_family(sd, config_json)
+    if family == "bert":
+        tensors, bert = load_bert_text_state(checkpoint, config_json)
+        cfg = SentenceEncoderConfig()      # the same twelve values, zeros behind them
+        for field, _ in BertTextConfig._fields_:
+            setattr(cfg, field, getattr(bert, field))
+        return tensors, cfg, family
+    sd = {(k[len(family) + 1:] if k.startswith(family + ".") else k): v for k, v in sd.items()}
+    distil = family == "distilbert"
+    fields = (dict(vocab="vocab_size", dim="dim", heads="n_heads", depth="n_layers", ffn="hidden_dim") if distil else
+              dict(vocab="vocab_size", dim="hidden_size", heads="num_attention_heads", depth="num_hidden_layers", ffn="intermediate_size"))
+    cfg = SentenceEncoderConfig()
+    try:
+        for field, name in fields.items():
+            setattr(cfg, field, int(config_json[name]))
+    except KeyError as e:
+        raise MarieHipError(f"{family} config.json: no {e.args[0]}") from None
+    # a field config.json leaves out takes the library's default (RobertaConfig, MPNetConfig, DistilBertConfig)
+    cfg.max_position = int(config_json.get("max_position_embeddings", 512))
+    cfg.ln_eps = 1e-12 if distil else float(config_json.get("layer_norm_eps", 1e-12))
+    cfg.position, cfg.mlp, cfg.pool, cfg.normalize = POS_ABSOLUTE, MLP_GELU, POOL_MEAN, 0
+    act = str(config_json.get("activation" if distil else "hidden_act", "gelu"))
+    if act != "gelu":
+        raise NotImplementedError(f"{family} config.json: activation {act!r} (the erf GELU is built)")
+    pe = str(config_json.get("position_embedding_type", "absolute"))
+    if pe != "absolute" or config_json.get("sinusoidal_pos_embds") and "embeddings.position_embeddings.weight" not in sd:
+        raise NotImplementedError(f"{family} config.json: position embeddings other than a learned table are not built")
+    cfg.pos_offset = 0 if distil else int(config_json.get("pad_token_id", 1)) + 1
+    cfg.type_vocab = int(config_json.get("type_vocab_size", 2)) if family == "roberta" else 0
+    if family == "mpnet":
+        cfg.rel_buckets, cfg.rel_max_distance = int(config_json.get("relative_attention_num_buckets", 32)), 128
+        if cfg.rel_buckets != 32:      # MPNetEncoder.compute_position_bias buckets with its default of 32, whatever the table's rows
+            raise NotImplementedError(f"mpnet config.json: relative_attention_num_buckets {cfg.rel_buckets} (the model buckets into 32)")
+    state = {}
+    names = _family_names(family, cfg)
+    for key, shape in bert_text_keys(cfg).items():
+        own = names[key]
+        if own not in sd:
+            raise MarieHipError(f"{family} checkpoint: no {own}")
+        arr = _f32(sd[own])
+        if arr.shape != shape:
+            raise MarieHipError(f"{family} checkpoint: {own} has shape {arr.shape}, the configuration asks for {shape}")
+        state[key] = arr
+    return state, cfg, family
+
+
+def sentence_tokenizer_from_dir(model_dir, family: str):
+    """the tokenizer a model directory holds: ``vocab.txt`` -> :class:`WordPieceTokenizer` (with MPNet's special tokens for that
+    family, ``do_lower_case`` of ``tokenizer_config.json``), ``vocab.json`` + ``merges.txt`` -> :class:`ByteLevelBPE`.  A
+    directory with neither raises, saying what is needed"""
+    special = dict(cls_token="<s>", sep_token="</s>", pad_token="<pad>", unk_token="[UNK]", mask_token="<mask>") if family == "mpnet" else {}
+    tokenizer = WordPieceTokenizer.from_dir(model_dir, **special) or ByteLevelBPE.from_dir(model_dir)
+    if tokenizer is None:
+        have = [f for f in ("tokenizer.json", "sentencepiece.bpe.model", "spiece.model", "tokenizer.model")
+                if os.path.isfile(os.path.join(model_dir, f))]
+        raise MarieHipError(f"no vocab.txt and no vocab.json + merges.txt in {model_dir}"
+                            f"{' (only ' + ', '.join(have) + ')' if have else ''}: the WordPiece tokenizer needs vocab.txt, the byte-level "
+                            f"BPE vocab.json and merges.txt; tokenizer.json and SentencePiece models are not read")
+    return tokenizer
+
+
+def rel_table(buckets: int, max_distance: int, weight) -> np.ndarray:
+    """MPNet's relative attention bias as the encoder folds it, before the log2(e) factor: weight fp32 (buckets, heads) -> fp32
+    (heads, 2 * max_distance + 1) over ``query - key`` in ``-max_distance .. max_distance``"""
+    weight = np.ascontiguousarray(weight, np.float32)
+    if weight.ndim != 2 or weight.shape[0] != buckets:
+        raise ValueError(f"weight of shape ({buckets}, heads) expected, got {weight.shape}")
+    out = np.empty((weight.shape[1], 2 * int(max_distance) + 1), np.float32)
+    rc = load().mhip_berttext_rel_table(int(buckets), int(max_distance), _vp(weight), weight.shape[1], _vp(out))
+    if rc:
+        raise MarieHipError(f"mhip_berttext_rel_table({buckets}, {max_distance}) failed ({rc}): the bucket must be defined and constant "
+                            f"past the distance")
+    return out
+
+
 def read_sentence_model_dir(model_dir) -> Dict[str, Any]:
     """What a sentence-transformers model directory says beyond ``config.json``: ``pooling`` ("mean" / "cls") of
     ``1_Pooling/config.json`` (or of the Pooling module ``modules.json`` names), ``normalize`` (a Normalize module is listed),
@@ -972,9 +1106,13 @@ class BertTextModel(ModelHandle):
 
     def __init__(self, ctx: Context, state: Optional[Dict[str, np.ndarray]], config: BertTextConfig, precision: int = PREC_F16):
         self.cfg, self.precision = config, int(precision)
+        self._create = "create_ex" if isinstance(config, SentenceEncoderConfig) else "create"
         super().__init__(ctx, "berttext", self.precision, C.byref(config))
         if state is not None:
             self.load_state(state)
+
+    def _fn(self, what: str):      # a SentenceEncoderConfig carries three fields more: its own create entry
+        return super()._fn(self._create if what == "create" else what)
 
     @staticmethod
     def _ids(ids, lens) -> Tuple[np.ndarray, np.ndarray]:
@@ -1016,7 +1154,7 @@ class BertTextModel(ModelHandle):
 
 
 # ---- the kernels on host arrays (what tests/test_berttext_gpu.py drives)
-def _attention_host(entry: str, ctx: Context, precision: int, q, k, v, lens, heads: int, slopes) -> np.ndarray:
+def _attention_host(entry: str, ctx: Context, precision: int, q, k, v, lens, heads: int, slopes, table=None) -> np.ndarray:
     q, k, v = (np.ascontiguousarray(a, np.float32) for a in (q, k, v))
     lens = np.ascontiguousarray(lens, np.int32).reshape(-1)
     B, npad, D = q.shape
@@ -1028,6 +1166,16 @@ def _attention_host(entry: str, ctx: Context, precision: int, q, k, v, lens, hea
         if slopes.shape[0] != heads:
             raise ValueError(f"{heads} slopes expected, got {slopes.shape[0]}")
     out = np.empty_like(q)
+    if entry.startswith("mhip_berttext_attention_rel"):
+        radius = 0
+        if table is not None:
+            table = np.ascontiguousarray(table, np.float32)
+            if table.ndim != 2 or table.shape[0] != heads or table.shape[1] % 2 != 1:
+                raise ValueError(f"a table of shape ({heads}, 2 * radius + 1) expected, got {table.shape}")
+            radius = table.shape[1] // 2
+        check(ctx.h, getattr(ctx.lib, entry)(ctx.h, int(precision), _vp(q), _vp(k), _vp(v), _vp(lens), _vp(table), radius, B,
+                                             int(heads), D // heads, npad, _vp(out)), entry)
+        return out
     check(ctx.h, getattr(ctx.lib, entry)(ctx.h, int(precision), _vp(q), _vp(k), _vp(v), _vp(lens), _vp(slopes), B,
                                          int(heads), D // heads, npad, _vp(out)), entry)
     return out
@@ -1043,6 +1191,34 @@ def long_attention_host(ctx: Context, precision: int, q, k, v, lens, heads: int,
     """the same through the streamed kernel (``attn_long``): npad a multiple of 8 up to 8192, 128 rows and fewer included; the
     rows of 64-query blocks that start at or past a sequence's length come back as zeros"""
     return _attention_host("mhip_berttext_attention_long_host", ctx, precision, q, k, v, lens, heads, slopes)
+
+
+def short_attention_rel_host(ctx: Context, precision: int, q, k, v, lens, heads: int, table=None) -> np.ndarray:
+    """``attn_short`` with a relative-distance table in place of the slopes: table fp32 (heads, 2 R + 1) in the log2 units of q,
+    the score of (query i, key j) gets ``table[h, clamp(i - j, -R, R) + R]``; None: no term"""
+    return _attention_host("mhip_berttext_attention_rel_host", ctx, precision, q, k, v, lens, heads, None, table)
+
+
+def long_attention_rel_host(ctx: Context, precision: int, q, k, v, lens, heads: int, table=None) -> np.ndarray:
+    """the same through the streamed kernel (``attn_long``)"""
+    return _attention_host("mhip_berttext_attention_rel_long_host", ctx, precision, q, k, v, lens, heads, None, table)
+
+
+def bert_embed_rows_ex_host(ctx: Context, word, type0, pos, g, b, ids, eps: float = 1e-12, pos_offset: int = 0) -> np.ndarray:
+    """as :func:`bert_embed_rows_host` with type0 (D) or None (no token types) and the position row of token t at
+    ``pos_offset + t``: pos (pos_offset + npad, D) or None"""
+    word, g, b = (np.ascontiguousarray(a, np.float32) for a in (word, g, b))
+    type0 = None if type0 is None else np.ascontiguousarray(type0, np.float32)
+    pos = None if pos is None else np.ascontiguousarray(pos, np.float32)
+    ids = np.ascontiguousarray(ids, np.int32)
+    B, npad = ids.shape
+    if pos is not None and pos.shape != (int(pos_offset) + npad, word.shape[1]):
+        raise ValueError(f"pos of shape {(int(pos_offset) + npad, word.shape[1])} expected, got {pos.shape}")
+    out = np.empty((B, npad, word.shape[1]), np.float32)
+    check(ctx.h, ctx.lib.mhip_berttext_embed_rows_ex_host(ctx.h, _vp(word), _vp(type0), _vp(pos), _vp(g), _vp(b), float(eps), _vp(ids),
+                                                          B, npad, word.shape[0], word.shape[1], int(pos_offset), _vp(out)),
+          "mhip_berttext_embed_rows_ex_host")
+    return out
 
 
 def bert_embed_rows_host(ctx: Context, word, type0, pos, g, b, ids, eps: float = 1e-12) -> np.ndarray:
@@ -1117,11 +1293,12 @@ class BertTextEmbeddings(EmbeddingsBase):
                  use_gpu: bool = True, batch_size: int = 4, use_auth_token: Optional[Union[str, bool]] = None,
                  devices: Optional[List[Any]] = None, show_error: Optional[Union[str, bool]] = True, *,
                  state: Optional[Dict[str, Any]] = None, config: Optional[Dict[str, Any]] = None,
-                 tokenizer: Optional[WordPieceTokenizer] = None, precision: Union[str, int] = "f16",
+                 tokenizer: Union[WordPieceTokenizer, ByteLevelBPE, None] = None, precision: Union[str, int] = "f16",
                  ctx: Optional[Context] = None, pooling: Optional[str] = None, normalize: Optional[bool] = None,
                  max_seq_length: Optional[int] = None, **kwargs):
-        """``model_name_or_path``: a model directory holding ``config.json``, ``model.safetensors`` or ``pytorch_model.bin``,
-        ``vocab.txt`` and, optionally, ``modules.json``, ``1_Pooling/config.json`` and ``sentence_bert_config.json``.
+        """``model_name_or_path``: a model directory of a BERT, MPNet, RoBERTa or DistilBERT sentence encoder holding
+        ``config.json``, ``model.safetensors`` or ``pytorch_model.bin``, ``vocab.txt`` (WordPiece) or ``vocab.json`` + ``merges.txt``
+        (byte-level BPE) and, optionally, ``modules.json``, ``1_Pooling/config.json`` and ``sentence_bert_config.json``.
         ``state`` / ``config`` / ``tokenizer``: the loaded checkpoint, the ``config.json`` dict and the tokenizer instead.
         ``pooling`` ("mean" / "cls"), ``normalize`` and ``max_seq_length`` override what the directory (or the class) says."""
         super().__init__(**kwargs)
@@ -1139,11 +1316,15 @@ class BertTextEmbeddings(EmbeddingsBase):
             config = self._load_config(model_name_or_path)
         if state is None:
             state = self._load_checkpoint(model_name_or_path)
+        tensors, cfg, family = load_sentence_encoder_state(state, config)      # before any device work
         if tokenizer is None:
-            tokenizer = WordPieceTokenizer.from_dir(model_name_or_path)
-            if tokenizer is None:
-                raise MarieHipError(f"{type(self).__name__}: no vocab.txt in {model_name_or_path}")
-        tensors, cfg = load_bert_text_state(state, config)      # before any device work
+            if family == "bert":
+                tokenizer = WordPieceTokenizer.from_dir(model_name_or_path)
+                if tokenizer is None:
+                    raise MarieHipError(f"{type(self).__name__}: no vocab.txt in {model_name_or_path}")
+            else:
+                tokenizer = sentence_tokenizer_from_dir(model_name_or_path, family)
+        self.family = family
         if len(tokenizer) > cfg.vocab:
             raise MarieHipError(f"{type(self).__name__}: the vocabulary has {len(tokenizer)} entries, the word table {cfg.vocab} rows")
         pooling = pooling or said.get("pooling", self.POOLING)
@@ -1154,7 +1335,7 @@ class BertTextEmbeddings(EmbeddingsBase):
         self.pooling, self.normalize = pooling, bool(normalize)
         limit = max_seq_length or said.get("max_seq_length") or self.MAX_LENGTH
         if cfg.position == POS_ABSOLUTE:
-            limit = min(limit or cfg.max_position, cfg.max_position)
+            limit = min(limit or cfg.max_position - cfg.pos_offset, cfg.max_position - cfg.pos_offset)
         self.max_seq_length = limit                                      # the model's own limit (None: none)
         self.max_tokens = min(limit or BERT_LONG_MAX_TOKENS, BERT_LONG_MAX_TOKENS)   # this build's
         if isinstance(precision, str):

@@ -16,7 +16,6 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-SPECIAL_TOKENS = ("[UNK]", "[SEP]", "[PAD]", "[CLS]", "[MASK]")
 MAX_CHARS_PER_WORD = 100
 WORD_CACHE_ENTRIES = 1 << 16      # blank-separated words whose ids are remembered
 
@@ -43,7 +42,7 @@ def _is_cjk(cp: int) -> bool:
 
 class WordPieceTokenizer:
     def __init__(self, vocab: Sequence[str], do_lower_case: bool = True, unk_token: str = "[UNK]", cls_token: str = "[CLS]",
-                 sep_token: str = "[SEP]", pad_token: str = "[PAD]"):
+                 sep_token: str = "[SEP]", pad_token: str = "[PAD]", mask_token: str = "[MASK]"):
         self.vocab: Dict[str, int] = {tok: i for i, tok in enumerate(vocab)}
         self.do_lower_case = bool(do_lower_case)
         for tok in (unk_token, cls_token, sep_token, pad_token):
@@ -52,14 +51,15 @@ class WordPieceTokenizer:
         self.unk_token = unk_token
         self.unk_id, self.cls_id = self.vocab[unk_token], self.vocab[cls_token]
         self.sep_id, self.pad_id = self.vocab[sep_token], self.vocab[pad_token]
-        self.never_split = frozenset(t for t in SPECIAL_TOKENS if t in self.vocab)
+        # BERT's names, and the family's own where they differ (MPNet: <s>, </s>, <pad>, [UNK], <mask>)
+        self.never_split = frozenset(t for t in (unk_token, sep_token, pad_token, cls_token, mask_token) if t in self.vocab)
         self._word_ids: Dict[str, List[int]] = {}
         self._specials = re.compile("(" + "|".join(re.escape(t) for t in sorted(self.never_split, key=len, reverse=True)) + ")")
 
     @classmethod
-    def from_dir(cls, model_dir) -> Optional["WordPieceTokenizer"]:
+    def from_dir(cls, model_dir, **special_tokens) -> Optional["WordPieceTokenizer"]:
         """``vocab.txt`` (one piece a line) and ``do_lower_case`` of ``tokenizer_config.json`` (default true); None where the
-        directory holds no ``vocab.txt``"""
+        directory holds no ``vocab.txt``.  ``special_tokens``: ``unk_token`` .. ``mask_token`` where they are not BERT's"""
         if model_dir is None or not os.path.isfile(os.path.join(model_dir, "vocab.txt")):
             return None
         with open(os.path.join(model_dir, "vocab.txt"), "r", encoding="utf-8") as f:
@@ -71,7 +71,7 @@ class WordPieceTokenizer:
         if os.path.isfile(config):
             with open(config, "r", encoding="utf-8") as f:
                 lower = bool(json.load(f).get("do_lower_case", True))
-        return cls(vocab, do_lower_case=lower)
+        return cls(vocab, do_lower_case=lower, **special_tokens)
 
     def __len__(self) -> int:
         return len(self.vocab)

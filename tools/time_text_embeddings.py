@@ -1,9 +1,14 @@
 """Times the BERT sentence encoders (f16): python tools/time_text_embeddings.py [--texts 4096] [--repeats 7] [--shapes minilm jina]
                                                                                   [--legs short long]
+(more shapes: mpnet bertbase distilroberta, short leg only)
 
 Seeded random weights at the all-MiniLM-L6-v2 shape (384 / 12 heads of 32 / 6 layers / ffn 1536, position table, GELU, mean +
 normalize) and the jina-embeddings-v2-base-en shape (768 / 12 heads of 64 / 12 layers / ffn 3072, ALiBi, GEGLU, mean), a synthetic
-WordPiece vocabulary of one-piece words.  The short leg: `--texts` texts of 4 to 24 tokens ([CLS] and [SEP] included), which run
+WordPiece vocabulary of one-piece words.  Also the all-mpnet-base-v2 shape (`mpnet`: 768 / 12 heads of 64 / 12 layers / ffn 3072,
+514 position rows from row 2, no token types, the relative attention bias), a BERT-base-shaped model of the same geometry
+(`bertbase`: what `mpnet` costs without the table term) and the all-distilroberta-v1 shape (`distilroberta`: the same with 6
+layers, one token type, no bias); all three over the same WordPiece words (a tokenizer handed to the class), since the encoder is
+what is timed.  The short leg: `--texts` texts of 4 to 24 tokens ([CLS] and [SEP] included), which run
 through attn_short.  The long leg (result key "long_shapes"): 256 texts of 200 to 256 tokens at the MiniLM shape and 64 texts of 400
 to 512 tokens at the jina shape, which run through the streamed attn_long (both kernels are counted in the profiler's `attn_short`
 slot; its share of the device time is reported as "attn_share").  Per shape and leg:
@@ -40,6 +45,13 @@ SHAPES = {
                    mlp="gelu", cls="SentenceTransformerEmbeddings"),
     "jina": dict(vocab=30528, max_position=8192, type_vocab=2, dim=768, heads=12, depth=12, ffn=3072, eps=1e-12, position="alibi",
                  mlp="geglu", cls="JinaEmbeddings"),
+    "bertbase": dict(vocab=30527, max_position=514, type_vocab=2, dim=768, heads=12, depth=12, ffn=3072, eps=1e-12, position="absolute",
+                     mlp="gelu", cls="SentenceTransformerEmbeddings"),
+    # the other families: weights and config.json from tests/sentence_families_ref.py
+    "mpnet": dict(family="mpnet", vocab=30527, max_position=514, type_vocab=0, dim=768, heads=12, depth=12, ffn=3072, eps=1e-5, pos_offset=2,
+                  position="absolute", mlp="gelu", cls="SentenceTransformerEmbeddings"),
+    "distilroberta": dict(family="roberta", vocab=50265, max_position=514, type_vocab=1, dim=768, heads=12, depth=6, ffn=3072, eps=1e-5,
+                          pos_offset=2, position="absolute", mlp="gelu", cls="SentenceTransformerEmbeddings"),
 }
 LONG_LEG = {"minilm": (256, 200, 256), "jina": (64, 400, 512)}      # texts, fewest and most tokens of one
 
@@ -91,6 +103,7 @@ def main():
     args = ap.parse_args()
 
     import bert_text_ref as R
+    import sentence_families_ref as S
     from marie_icr_amd import embeddings
     from marie_icr_amd._lib import Context
     from marie_icr_amd.wordpiece_tokenizer import WordPieceTokenizer
@@ -106,13 +119,17 @@ def main():
     for name in args.shapes:
         if "short" in args.legs:
             legs.append((name, "shapes", texts))
-        if "long" in args.legs:
+        if "long" in args.legs and name in LONG_LEG:
             n, lo, hi = LONG_LEG[name]
             lrng = np.random.default_rng(1)
             legs.append((name, "long_shapes", [" ".join(words[j] for j in lrng.integers(0, len(words), c)) for c in lrng.integers(lo - 2, hi - 1, n)]))
     for name, leg, texts in legs:
         cfg = SHAPES[name]
-        e = getattr(embeddings, cfg["cls"])(state=R.make_state(cfg, seed=0), config=R.config_json(cfg), tokenizer=tok, precision="f16", ctx=ctx)
+        if "family" in cfg:
+            state, conf = S.make_state(cfg, 0), S.config_json(cfg)
+        else:
+            state, conf = R.make_state(cfg, seed=0), R.config_json(cfg)
+        e = getattr(embeddings, cfg["cls"])(state=state, config=conf, tokenizer=tok, precision="f16", ctx=ctx)
         encoded = e.encode_texts(texts)
         lengths = [len(x) for x in encoded]
         groups = [tok.pad([encoded[i] for i in members], npad) for npad, members in e._groups(lengths, None)]
