@@ -345,6 +345,14 @@ int mhip_upsample_bilinear_host(mhip_ctx* ctx, int precision, const float* in, i
 int mhip_score_head_host(mhip_ctx* ctx, int precision, const float* in, int in_stride, const float* w1, const float* b1,
                          const float* w2, const float* b2, long long npix, float* scores);
 
+/* ---- stage entry of the row LayerNorm every tower shares (csrc/row_ops.hip) -------------------------------------------------
+ * Test surface only, same conventions as the stage entries above.  replaces: nn.LayerNorm(D, eps) over rows.  x fp32 [rows][D];
+ * with x_f16 (f16 mode only) it is narrowed to an f16 stream, and x_lo (or NULL) is its low plane, x = hi + lo.  g, b fp32 [D];
+ * D a multiple of 64 up to 1024.  h fp32 [rows][D] + guard (NULL: not written); ht [rows][D] + guard in the mode's element type,
+ * widened (NULL: not written); one of the two at least.  in_place: h and x are one device buffer (needs h, no x_f16). */
+int mhip_row_layernorm_host(mhip_ctx* ctx, int precision, const float* x, int x_f16, const float* x_lo, const float* g,
+                            const float* b, int rows, int D, float eps, int in_place, float* h, float* ht);
+
 /* ---- Pillow-exact 8-bit resize (antialiased LANCZOS / BILINEAR / BICUBIC) of RGB images -------------------------------- */
 #define MHIP_PIL_LANCZOS 1    /* PIL.Image.LANCZOS  */
 #define MHIP_PIL_BILINEAR 2   /* PIL.Image.BILINEAR */

@@ -270,6 +270,7 @@ _SIGNATURES = (
     ("mhip_attn_cell_host", _i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp]),
     ("mhip_argmax_rows_host", _i, [_vp, _vp, _i, _i, _i, _vp]),
     ("mhip_rowmax_softmax_host", _i, [_vp, _vp, _i, _i, _vp, _vp]),
+    ("mhip_row_layernorm_host", _i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, C.c_float, _i, _vp, _vp]),
     ("mhip_resize_linear_u8_host", _i, [_vp, _vp, _i, _i, _vp, _i, _i]),
     ("mhip_conv_rgb_first_host", _i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     ("mhip_maxpool_host", _i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp]),

@@ -160,7 +160,7 @@ int berttext_forward(mhip_berttext* m, int B, int npad, const BertRun& run, floa
   for (int i = 0; i < c.depth; ++i) {
     if ((rc = encoder_block_attention(ctx, prec, a, i, w, sd))) return rc;
     if ((rc = mhip_gemm(ctx, prec, w.ao, a.d(enc_blk(i, "ao_w")), (long long)R, D, D, nullptr, a.d<float>(enc_blk(i, "ao_b")), run.y, ACT_NONE, 1, run.h))) return rc;
-    if ((rc = mhip_launch_berttext_layernorm(ctx, prec, run.y, a.d<float>(enc_blk(i, "ln1_g")), a.d<float>(enc_blk(i, "ln1_b")), run.h, w.ht, (int)R, D, c.ln_eps))) return rc;
+    if ((rc = mhip_launch_row_layernorm(ctx, MHIP_K_BERTTEXT_EMBED, prec, run.y, 0, nullptr, a.d<float>(enc_blk(i, "ln1_g")), a.d<float>(enc_blk(i, "ln1_b")), run.h, w.ht, (int)R, D, c.ln_eps))) return rc;
     const char* hid = w.hid;
     if (m->geglu()) {
       if ((rc = mhip_gemm(ctx, prec, w.ht, a.d(enc_blk(i, "fc1_w")), (long long)R, 2 * F, D, nullptr, nullptr, w.hid, ACT_NONE, 0))) return rc;
@@ -170,7 +170,7 @@ int berttext_forward(mhip_berttext* m, int B, int npad, const BertRun& run, floa
       if ((rc = mhip_gemm(ctx, prec, w.ht, a.d(enc_blk(i, "fc1_w")), (long long)R, F, D, nullptr, a.d<float>(enc_blk(i, "fc1_b")), w.hid, ACT_GELU, 0))) return rc;
     }
     if ((rc = mhip_gemm(ctx, prec, hid, a.d(enc_blk(i, "fc2_w")), (long long)R, D, F, nullptr, a.d<float>(enc_blk(i, "fc2_b")), run.y, ACT_NONE, 1, run.h))) return rc;
-    if ((rc = mhip_launch_berttext_layernorm(ctx, prec, run.y, a.d<float>(enc_blk(i, "ln2_g")), a.d<float>(enc_blk(i, "ln2_b")), run.h, w.ht, (int)R, D, c.ln_eps))) return rc;
+    if ((rc = mhip_launch_row_layernorm(ctx, MHIP_K_BERTTEXT_EMBED, prec, run.y, 0, nullptr, a.d<float>(enc_blk(i, "ln2_g")), a.d<float>(enc_blk(i, "ln2_b")), run.h, w.ht, (int)R, D, c.ln_eps))) return rc;
     if ((rc = tap(i + 1))) return rc;
   }
   return mhip_launch_berttext_pool(ctx, run.h, run.len, B, npad, D, c.pool == BT_POOL_CLS, c.normalize, run.emb);

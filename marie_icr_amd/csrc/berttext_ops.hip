@@ -1,13 +1,12 @@
 // berttext_ops.hip — the kernels of the BERT sentence encoders (berttext_api.hip) the other towers do not have: the embedding +
-// LayerNorm front, the post-LayerNorm of a layer at widths that are no multiple of 256, GEGLU and masked pooling.  (Their
-// attention over sequences of different lengths, attn_short and attn_long, is attn_seq.hip.)
+// LayerNorm front (its row load, LayerNorm and store are row_ops.h's), GEGLU and masked pooling.  (Their attention over sequences
+// of different lengths, attn_short and attn_long, is attn_seq.hip; the post-LayerNorms of the layers are row_ops.hip's kernel,
+// counted in berttext_embed.)
 //
 // Replaces, in transformers/models/bert/modeling_bert.py: BertEmbeddings.forward (and the embeddings of RoBERTa and MPNet, whose
 // position rows start at pad_id + 1, and of DistilBERT and MPNet, which have no token types), the LayerNorms of BertSelfOutput /
 // BertOutput;
 // of JinaBERT the gated MLP's activation; and the Pooling (mean / cls) and Normalize modules of sentence_transformers.
-#include <algorithm>
-
 #include "igemm_common.h"
 #include "row_ops.h"
 
@@ -16,23 +15,6 @@ using namespace igemm;
 namespace {
 
 // ------------------------------------------------------------------------------------------------------- rows
-// a lane's float4 groups of the row -> the fp32 stream and the operand of the next GEMM
-template <typename T>
-__device__ __forceinline__ void store_row(const float4v v[ROW_GROUPS], float* __restrict__ h, T* __restrict__ ht, size_t row, int D, int lane) {
-#pragma unroll
-  for (int i = 0; i < ROW_GROUPS; ++i) {
-    const int c = (i * 64 + lane) * 4;
-    if (c < D) {
-      *(float4v*)(h + row * D + c) = v[i];
-      if (ht) {
-        T o4[4] = {(T)v[i][0], (T)v[i][1], (T)v[i][2], (T)v[i][3]};
-        if (sizeof(T) == 2) *(uint64_t*)(ht + row * D + c) = *(uint64_t*)o4;
-        else *(float4v*)(ht + row * D + c) = *(float4v*)o4;
-      }
-    }
-  }
-}
-
 // h[seq][t] = LN((word[ids[seq][t]] + type0) + pos[pos_offset + t]) (type0 null: no token types; pos null: no position table), one
 // wave per row, 16 bytes a lane
 template <typename T>
@@ -46,36 +28,11 @@ __global__ __launch_bounds__(256) void berttext_embed_kernel(const float* __rest
   const float* src = word + (size_t)ids[row] * D;
   const float* pp = pos ? pos + (size_t)(pos_offset + row % npad) * D : nullptr;
   float4v v[ROW_GROUPS];
-#pragma unroll
-  for (int i = 0; i < ROW_GROUPS; ++i) {
-    const int c = (i * 64 + lane) * 4;
-    v[i] = (float4v){0.f, 0.f, 0.f, 0.f};
-    if (c < D) {
-      v[i] = *(const float4v*)(src + c);
-      if (type0) v[i] += *(const float4v*)(type0 + c);
-      if (pp) v[i] += *(const float4v*)(pp + c);
-    }
-  }
+  row_load(v, src, D, lane);
+  if (type0) row_add(v, type0, D, lane);
+  if (pp) row_add(v, pp, D, lane);
   row_layernorm(v, D, lane, g, b, eps);
-  store_row<T>(v, h, ht, (size_t)row, D, lane);
-}
-
-// the post-LayerNorm of a layer: h = LN(x), ht its copy in the GEMM element type
-template <typename T>
-__global__ __launch_bounds__(256) void berttext_layernorm_kernel(const float* __restrict__ x, const float* __restrict__ g,
-                                                                 const float* __restrict__ b, float* __restrict__ h,
-                                                                 T* __restrict__ ht, int rows, int D, float eps) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= rows) return;
-  float4v v[ROW_GROUPS];
-#pragma unroll
-  for (int i = 0; i < ROW_GROUPS; ++i) {
-    const int c = (i * 64 + lane) * 4;
-    v[i] = (float4v){0.f, 0.f, 0.f, 0.f};
-    if (c < D) v[i] = *(const float4v*)(x + (size_t)row * D + c);
-  }
-  row_layernorm(v, D, lane, g, b, eps);
-  store_row<T>(v, h, ht, (size_t)row, D, lane);
+  row_store<T>(v, h + (size_t)row * D, ht ? ht + (size_t)row * D : nullptr, D, lane);
 }
 
 // ------------------------------------------------------------------------------------------------------- GEGLU
@@ -126,8 +83,6 @@ __global__ __launch_bounds__(256) void berttext_pool_kernel(const float* __restr
   if (c < D) *(float4v*)(emb + (size_t)b * D + c) = acc;
 }
 
-inline int grid_for(long long total, int block) { return (int)std::min<long long>((total + block - 1) / block, 65535LL * 4); }
-
 }  // namespace
 
 int mhip_launch_berttext_embed(mhip_ctx* ctx, int precision, const float* word, const float* type0, const float* pos, const float* g,
@@ -140,18 +95,6 @@ int mhip_launch_berttext_embed(mhip_ctx* ctx, int precision, const float* word, 
   else
     PROF_LAUNCH(ctx, MHIP_K_BERTTEXT_EMBED, hipLaunchKernelGGL(berttext_embed_kernel<float>, grid, block, 0, ctx->stream, word, type0, pos, g, b, ids, h, (float*)ht, rows, npad, D, eps, pos_offset));
   CHECK_LAUNCH(ctx, "berttext_embed");
-  return 0;
-}
-
-int mhip_launch_berttext_layernorm(mhip_ctx* ctx, int precision, const float* x, const float* g, const float* b, float* h, void* ht,
-                                   int rows, int D, float eps) {
-  if (rows <= 0 || !row_width_ok(D)) return mhip_fail(ctx, MHIP_EINVAL, "berttext_layernorm: D=%d rows=%d", D, rows);
-  dim3 grid((rows + 3) / 4), block(256);
-  if (precision == MHIP_PREC_F16)
-    PROF_LAUNCH(ctx, MHIP_K_BERTTEXT_EMBED, hipLaunchKernelGGL(berttext_layernorm_kernel<_Float16>, grid, block, 0, ctx->stream, x, g, b, h, (_Float16*)ht, rows, D, eps));
-  else
-    PROF_LAUNCH(ctx, MHIP_K_BERTTEXT_EMBED, hipLaunchKernelGGL(berttext_layernorm_kernel<float>, grid, block, 0, ctx->stream, x, g, b, h, (float*)ht, rows, D, eps));
-  CHECK_LAUNCH(ctx, "berttext_layernorm");
   return 0;
 }
 

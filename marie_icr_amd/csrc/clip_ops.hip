@@ -1,6 +1,6 @@
 // clip_ops.hip — the pieces of the CLIP vision tower the other ViT paths do not have: patch extraction with CLIP's per-channel
-// normalisation, the token embedding fused with pre_layrnorm, a LayerNorm for widths that are no multiple of 256, quick-GELU,
-// the post_layernorm + projection head, and the cosine of embedding pairs.
+// normalisation, the token embedding fused with pre_layrnorm, quick-GELU, the post_layernorm + projection head, and the cosine
+// of embedding pairs.  (The LayerNorms of the layers are row_ops.hip's kernel, counted in clipvis_embed.)
 //
 // Replaces, in transformers/models/clip/modeling_clip.py: CLIPVisionEmbeddings.forward + CLIPVisionTransformer.pre_layrnorm,
 // the two LayerNorms of CLIPEncoderLayer, QuickGELUActivation, post_layernorm + CLIPVisionModelWithProjection.visual_projection
@@ -9,8 +9,7 @@
 // (GEMMs are conv_igemm.hip; the softmax attention is attn_flash.hip.)
 //
 // Token layout as in vit_ops.hip: every image owns `npad` rows (npad % 8 == 0): row 0 = class token, rows 1..n_tok-1 = patches,
-// the rest zeros.  The residual stream h is fp32.  All row kernels: one wave per row, D % 64 == 0, D <= 1024, a lane holds the
-// float4 groups at columns (i * 64 + lane) * 4 < D.
+// the rest zeros.  The residual stream h is fp32.  All row kernels: one wave per row, loaded, normalised and stored by row_ops.h.
 #include <algorithm>
 
 #include "igemm_common.h"
@@ -57,49 +56,13 @@ __global__ __launch_bounds__(256) void clipvis_embed_kernel(const float* __restr
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= rows) return;
   const int img = row / npad, t = row % npad;
-  float4v v[ROW_GROUPS];
-#pragma unroll
-  for (int i = 0; i < ROW_GROUPS; ++i) {
-    const int c = (i * 64 + lane) * 4;
-    v[i] = (float4v){0.f, 0.f, 0.f, 0.f};
-    if (c < D && t < n_tok) {
-      const float* src = t == 0 ? cls : patches + ((size_t)img * (n_tok - 1) + t - 1) * D;
-      v[i] = *(const float4v*)(src + c) + *(const float4v*)(pos + (size_t)t * D + c);
-    }
+  float4v v[ROW_GROUPS] = {};
+  if (t < n_tok) {
+    row_load(v, t == 0 ? cls : patches + ((size_t)img * (n_tok - 1) + t - 1) * D, D, lane);
+    row_add(v, pos + (size_t)t * D, D, lane);
+    row_layernorm(v, D, lane, g, b, eps);
   }
-  if (t < n_tok) row_layernorm(v, D, lane, g, b, eps);
-#pragma unroll
-  for (int i = 0; i < ROW_GROUPS; ++i) {
-    const int c = (i * 64 + lane) * 4;
-    if (c < D) *(float4v*)(h + (size_t)row * D + c) = v[i];
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------- LayerNorm
-// fp32 rows -> T rows (the operand of the next GEMM)
-template <typename T>
-__global__ __launch_bounds__(256) void clipvis_layernorm_kernel(const float* __restrict__ x, const float* __restrict__ g,
-                                                                const float* __restrict__ b, T* __restrict__ out, int rows,
-                                                                int D, float eps) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= rows) return;
-  float4v v[ROW_GROUPS];
-#pragma unroll
-  for (int i = 0; i < ROW_GROUPS; ++i) {
-    const int c = (i * 64 + lane) * 4;
-    v[i] = (float4v){0.f, 0.f, 0.f, 0.f};
-    if (c < D) v[i] = *(const float4v*)(x + (size_t)row * D + c);
-  }
-  row_layernorm(v, D, lane, g, b, eps);
-#pragma unroll
-  for (int i = 0; i < ROW_GROUPS; ++i) {
-    const int c = (i * 64 + lane) * 4;
-    if (c < D) {
-      T o4[4] = {(T)v[i][0], (T)v[i][1], (T)v[i][2], (T)v[i][3]};
-      if (sizeof(T) == 2) *(uint64_t*)(out + (size_t)row * D + c) = *(uint64_t*)o4;
-      else *(float4v*)(out + (size_t)row * D + c) = *(float4v*)o4;
-    }
-  }
+  row_store<float>(v, h + (size_t)row * D, nullptr, D, lane);
 }
 
 // ------------------------------------------------------------------------------------------------------- quick-GELU
@@ -131,20 +94,10 @@ __global__ __launch_bounds__(256) void clipvis_head_kernel(const float* __restri
   __shared__ __attribute__((aligned(16))) float ys[1024];
   const int img = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (wave == 0) {
-    const float* x = h + ((size_t)img * npad + (row_of ? row_of[img] : 0)) * D;
     float4v v[ROW_GROUPS];
-#pragma unroll
-    for (int i = 0; i < ROW_GROUPS; ++i) {
-      const int c = (i * 64 + lane) * 4;
-      v[i] = (float4v){0.f, 0.f, 0.f, 0.f};
-      if (c < D) v[i] = *(const float4v*)(x + c);
-    }
+    row_load(v, h + ((size_t)img * npad + (row_of ? row_of[img] : 0)) * D, D, lane);
     row_layernorm(v, D, lane, g, b, eps);
-#pragma unroll
-    for (int i = 0; i < ROW_GROUPS; ++i) {
-      const int c = (i * 64 + lane) * 4;
-      if (c < D) *(float4v*)(ys + c) = v[i];
-    }
+    row_store<float>(v, ys, nullptr, D, lane);
   }
   __syncthreads();
   const int j0 = blockIdx.y * HEAD_COLS, j1 = min(j0 + HEAD_COLS, E);
@@ -178,8 +131,6 @@ __global__ __launch_bounds__(256) void pair_cosine_kernel(const float* __restric
   if (lane == 0) out[p] = xy / fmaxf(sqrtf(xx * yy), 1e-8f);
 }
 
-inline int grid_for(long long total, int block) { return (int)std::min<long long>((total + block - 1) / block, 65535LL * 4); }
-
 }  // namespace
 
 int mhip_launch_clipvis_patchify(mhip_ctx* ctx, int precision, const uint8_t* imgs, int B, int S, int P, int swap_rb,
@@ -204,18 +155,6 @@ int mhip_launch_clipvis_embed(mhip_ctx* ctx, const float* patches, const float* 
   const int rows = B * npad;
   PROF_LAUNCH(ctx, MHIP_K_CLIPVIS_EMBED, hipLaunchKernelGGL(clipvis_embed_kernel, dim3((rows + 3) / 4), dim3(256), 0, ctx->stream, patches, cls, pos, g, b, h, rows, npad, n_tok, D, eps));
   CHECK_LAUNCH(ctx, "clipvis_embed");
-  return 0;
-}
-
-int mhip_launch_clipvis_layernorm(mhip_ctx* ctx, int precision, const float* x, const float* g, const float* b, void* out, int rows,
-                                  int D, float eps) {
-  if (rows <= 0 || !row_width_ok(D)) return mhip_fail(ctx, MHIP_EINVAL, "clipvis_layernorm: D=%d rows=%d", D, rows);
-  dim3 grid((rows + 3) / 4), block(256);
-  if (precision == MHIP_PREC_F16)
-    PROF_LAUNCH(ctx, MHIP_K_CLIPVIS_EMBED, hipLaunchKernelGGL(clipvis_layernorm_kernel<_Float16>, grid, block, 0, ctx->stream, x, g, b, (_Float16*)out, rows, D, eps));
-  else
-    PROF_LAUNCH(ctx, MHIP_K_CLIPVIS_EMBED, hipLaunchKernelGGL(clipvis_layernorm_kernel<float>, grid, block, 0, ctx->stream, x, g, b, (float*)out, rows, D, eps));
-  CHECK_LAUNCH(ctx, "clipvis_layernorm");
   return 0;
 }
 

@@ -10,14 +10,10 @@
 //
 // Profile slots (the kernel table is not extended): the stem counts under conv_first, the pool under image_ops, the token
 // build under clipvis_embed, the one-query attention under dec_ops, c_proj under clipvis_head.
-#include <algorithm>
-
 #include "igemm_common.h"
 #include "row_ops.h"
 
 namespace {
-
-inline int grid_for(long long total, int block) { return (int)std::min<long long>((total + block - 1) / block, 65535LL * 4); }
 
 template <typename T>
 __device__ __forceinline__ void store8(T* dst, const float f[8]) {

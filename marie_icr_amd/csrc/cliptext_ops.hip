@@ -1,5 +1,5 @@
 // cliptext_ops.hip — the row kernel the CLIP text tower has that the vision tower (clip_ops.hip) does not: the token + position
-// embedding.  (Its causal attention is attn_seq.hip.)
+// embedding (a row_ops.h load, add and store).  (Its causal attention is attn_seq.hip.)
 //
 // Replaces, in transformers/models/clip/modeling_clip.py: CLIPTextEmbeddings.forward (the same arithmetic as clip/model.py:
 // CLIP.encode_text's token_embedding + positional_embedding).
@@ -15,13 +15,10 @@ __global__ __launch_bounds__(256) void cliptext_embed_kernel(const float* __rest
                                                              int npad, int D) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= rows) return;
-  const float* src = table + (size_t)ids[row] * D;
-  const float* pp = pos + (size_t)(row % npad) * D;
-#pragma unroll
-  for (int i = 0; i < ROW_GROUPS; ++i) {
-    const int c = (i * 64 + lane) * 4;
-    if (c < D) *(float4v*)(h + (size_t)row * D + c) = *(const float4v*)(src + c) + *(const float4v*)(pp + c);
-  }
+  float4v v[ROW_GROUPS];
+  row_load(v, table + (size_t)ids[row] * D, D, lane);
+  row_add(v, pos + (size_t)(row % npad) * D, D, lane);
+  row_store<float>(v, h + (size_t)row * D, nullptr, D, lane);
 }
 
 }  // namespace

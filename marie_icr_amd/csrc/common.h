@@ -58,7 +58,7 @@ enum MhipKernelId {
                                  // attn_short (<= 128 rows, keys held in LDS) and attn_long (<= 8192 rows, keys streamed in blocks of
                                  // 128, online soft-max) share the slot, as the post-LayerNorms share berttext_embed
   MHIP_K_BERTTEXT_EMBED = 33,    // word + type + position rows -> LayerNorm -> fp32 stream; the post-LayerNorms of the layers
-                                 // (LayoutReader's row LayerNorms go through mhip_launch_berttext_layernorm and are counted here)
+                                 // (LayoutReader's row LayerNorms are counted here too)
   MHIP_K_GEGLU = 34,             // gelu(x[:, :F]) * x[:, F:]
   MHIP_K_BERTTEXT_POOL = 35,     // masked mean / cls pooling, optional L2 normalisation
   MHIP_K_COUNT = 36
@@ -208,6 +208,26 @@ int mhip_with_upload(mhip_ctx* ctx, const void* host, size_t bytes, const char* 
   return rc;
 }
 
+// workgroups of `block` threads a grid-stride kernel over `total` items is launched with
+inline int grid_for(long long total, int block) {
+  const long long g = (total + block - 1) / block;
+  return (int)(g < 65535LL * 4 ? g : 65535LL * 4);
+}
+// the grid of the image kernels of the recognizer and the detector (icr_ops.hip, image_ops.hip): blocks of 256, 1 .. 8192 of
+// them (its own name: another clamp than grid_for's)
+inline unsigned image_grid_for(long long total) {
+  const long long g = (total + 255) / 256;
+  return (unsigned)(g < 1 ? 1 : (g > 256 * 32 ? 256 * 32 : g));
+}
+
+// ------------------------------------------------------------------ row LayerNorm (row_ops.hip; the arithmetic: row_ops.h)
+// h fp32 (null: not written) = LN(x), ht (null: not written) its copy in the precision's element type; one of the two at least.
+// x: the residual stream, fp32 — or f16 (x_f16, f16 mode only), x_lo then being the low plane when the stream is kept as two f16
+// planes (x = hi + lo; ConvDesc::epi) or null.  D % 64 == 0, D <= 1024.  h may be x (a wave holds its row in registers before it
+// writes).  slot: the MhipKernelId the launch is counted in (the caller's tower's)
+int mhip_launch_row_layernorm(mhip_ctx* ctx, int slot, int precision, const void* x, int x_f16, const void* x_lo, const float* g,
+                              const float* b, float* h, void* ht, int rows, int D, float eps);
+
 // ------------------------------------------------------------------ conv / GEMM launcher
 // Implicit-GEMM convolution over NHWC activations:  out[m][n] = act( scale[n] * sum_k A[m][k] W[n][k] + bias[n] )
 // with A[m][k] = in[b][y+dy-pad][x+dx-pad][c], k = (dy*KW+dx)*Cin + c, and an optional max-pool
@@ -347,10 +367,6 @@ int mhip_launch_argmax_rows(mhip_ctx* ctx, const float* logits, int ld, int C, i
 int mhip_launch_rowmax_softmax(mhip_ctx* ctx, const float* logits, int rows, int C, int* idx, float* pmax);
 
 // ------------------------------------------------------------------ ViT encoder ops (vit_ops.hip)
-// x: the residual stream, fp32 — or f16 (x_f16, f16 mode only)
-// x_lo: the low plane when the stream is kept as two f16 planes (x = hi + lo; ConvDesc::epi), x then being the high plane
-int mhip_launch_layernorm(mhip_ctx* ctx, int precision, const void* x, const float* g, const float* b, void* out,
-                          int rows, int D, float eps, int x_f16 = 0, const void* x_lo = nullptr);
 // the split stream (two f16 planes + row statistics per 64-column chunk, stats[(chunk * stats_ld + row) * 2]):
 int mhip_launch_token_init_split(mhip_ctx* ctx, void* hi, void* lo, const float* cls_row, const float* cls_stats, float* stats,
                                  int stats_ld, int B, int npad, int n_tok, int D);
@@ -458,6 +474,9 @@ int mhip_launch_blackout(mhip_ctx* ctx, uint8_t* page, int H, int W, const int* 
 int mhip_launch_subsample2(mhip_ctx* ctx, int precision, const void* in, void* out, int B, int H, int W, int C);
 
 // ------------------------------------------------------------------ TrOCR decoder steps (trocr_ops.hip)
+// y_f32 (may be x) = LN(x), y_t its copy in the precision's element type; D % 256 == 0.  The post-LayerNorm of the TrOCR decoder and
+// of the LayoutLMv3 layers: not mhip_launch_row_layernorm, whose variance rounds differently in a row's first group (DESIGN.md §3,
+// "The row kernels of the towers")
 int mhip_launch_layernorm2(mhip_ctx* ctx, int precision, const float* x, const float* g, const float* b, float* y_f32,
                            void* y_t, int rows, int D, float eps);
 int mhip_launch_embed_step(mhip_ctx* ctx, int precision, const int* tokens, const void* emb, const float* pos_row, float scale,
@@ -594,8 +613,6 @@ int mhip_launch_clipvis_patchify(mhip_ctx* ctx, int precision, const uint8_t* im
 // h [B*npad][D] fp32 = LN(class + pos[0]) | LN(patches [B*(n_tok-1)][D] + pos[1..]) | zeros
 int mhip_launch_clipvis_embed(mhip_ctx* ctx, const float* patches, const float* cls, const float* pos, const float* g, const float* b,
                               float* h, int B, int npad, int n_tok, int D, float eps);
-int mhip_launch_clipvis_layernorm(mhip_ctx* ctx, int precision, const float* x, const float* g, const float* b, void* out, int rows,
-                                  int D, float eps);
 // x [n] T in place; n a multiple of 16 bytes' worth of elements
 int mhip_launch_quick_gelu(mhip_ctx* ctx, int precision, void* x, long long n);
 // emb [B][E] fp32 = LN(h[img * npad + row_of[img]]) proj_t^T, proj_t [E][D] fp32; row_of (device, [B]) null: row 0 of every block
@@ -652,9 +669,6 @@ int mhip_launch_attention_long(mhip_ctx* ctx, int precision, const AttnShortDesc
 // table) fp32; the ids are the caller's to check
 int mhip_launch_berttext_embed(mhip_ctx* ctx, int precision, const float* word, const float* type0, const float* pos, const float* g,
                                const float* b, float eps, const int* ids, float* h, void* ht, int B, int npad, int D, int pos_offset = 0);
-// h = LN(x) fp32 and ht (null: not written) its copy in the precision's element type; D % 64 == 0, D <= 1024; h may be x
-int mhip_launch_berttext_layernorm(mhip_ctx* ctx, int precision, const float* x, const float* g, const float* b, float* h, void* ht,
-                                   int rows, int D, float eps);
 // x [R][2 F] -> out [R][F] = gelu_erf(x[:, :F]) * x[:, F:], in the precision's element type; F % 8 == 0
 int mhip_launch_geglu(mhip_ctx* ctx, int precision, const void* x, void* out, long long R, int F);
 // emb [B][D] fp32: the mean of rows < len[b] of h [B][npad][D] (cls: row 0; len may be null), divided by max(norm, 1e-12) with normalize

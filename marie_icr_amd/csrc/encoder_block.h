@@ -199,10 +199,10 @@ int clip_encoder_layers(mhip_ctx* ctx, int prec, const Arena& a, int depth, int 
                         const EncoderWs& w, const AD& ad, Tap&& tap) {
   int rc;
   for (int i = 0; i < depth; ++i) {
-    if ((rc = mhip_launch_clipvis_layernorm(ctx, prec, h, a.d<float>(enc_blk(i, "ln1_g")), a.d<float>(enc_blk(i, "ln1_b")), w.ht, (int)R, D, ln_eps))) return rc;
+    if ((rc = mhip_launch_row_layernorm(ctx, MHIP_K_CLIPVIS_EMBED, prec, h, 0, nullptr, a.d<float>(enc_blk(i, "ln1_g")), a.d<float>(enc_blk(i, "ln1_b")), nullptr, w.ht, (int)R, D, ln_eps))) return rc;
     if ((rc = encoder_block_attention(ctx, prec, a, i, w, ad))) return rc;
     if ((rc = mhip_gemm(ctx, prec, w.ao, a.d(enc_blk(i, "ao_w")), (long long)R, D, D, nullptr, a.d<float>(enc_blk(i, "ao_b")), h, ACT_NONE, 1, h))) return rc;
-    if ((rc = mhip_launch_clipvis_layernorm(ctx, prec, h, a.d<float>(enc_blk(i, "ln2_g")), a.d<float>(enc_blk(i, "ln2_b")), w.ht, (int)R, D, ln_eps))) return rc;
+    if ((rc = mhip_launch_row_layernorm(ctx, MHIP_K_CLIPVIS_EMBED, prec, h, 0, nullptr, a.d<float>(enc_blk(i, "ln2_g")), a.d<float>(enc_blk(i, "ln2_b")), nullptr, w.ht, (int)R, D, ln_eps))) return rc;
     if ((rc = mhip_gemm(ctx, prec, w.ht, a.d(enc_blk(i, "fc1_w")), (long long)R, F, D, nullptr, a.d<float>(enc_blk(i, "fc1_b")), w.hid, ACT_NONE, 0))) return rc;
     if ((rc = mhip_launch_quick_gelu(ctx, prec, w.hid, (long long)R * F))) return rc;
     if ((rc = mhip_gemm(ctx, prec, w.hid, a.d(enc_blk(i, "fc2_w")), (long long)R, D, F, nullptr, a.d<float>(enc_blk(i, "fc2_b")), h, ACT_NONE, 1, h))) return rc;

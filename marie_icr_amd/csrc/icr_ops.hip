@@ -318,11 +318,6 @@ __global__ __launch_bounds__(64) void rowmax_softmax_kernel(const float* __restr
   }
 }
 
-unsigned grid_for(long long total) {
-  long long g = (total + 255) / 256;
-  return (unsigned)(g < 1 ? 1 : (g > 256 * 32 ? 256 * 32 : g));
-}
-
 }  // namespace
 
 int mhip_launch_conv_gray_first(mhip_ctx* ctx, int precision, int in_is_u8, const void* img, int B, int H, int W,
@@ -346,7 +341,7 @@ int mhip_launch_conv_gray_first(mhip_ctx* ctx, int precision, int in_is_u8, cons
 int mhip_launch_maxpool_s21_p01(mhip_ctx* ctx, int precision, const void* in, void* out, int B, int H, int W, int C) {
   const int vn = precision == MHIP_PREC_F16 ? 8 : 4;
   if (B < 1 || H < 2 || W < 1 || C % vn) return mhip_fail(ctx, MHIP_EINVAL, "maxpool_s21: bad shape");
-  const unsigned grid = grid_for((long long)B * (H / 2) * (W + 1) * (C / vn));
+  const unsigned grid = image_grid_for((long long)B * (H / 2) * (W + 1) * (C / vn));
   if (precision == MHIP_PREC_F16)
     PROF_LAUNCH(ctx, MHIP_K_IMAGE_OPS, hipLaunchKernelGGL((maxpool_s21_p01_kernel<_Float16>), dim3(grid), dim3(256), 0,
                                                           ctx->stream, (const _Float16*)in, (_Float16*)out, B, H, W, C));
@@ -359,7 +354,7 @@ int mhip_launch_maxpool_s21_p01(mhip_ctx* ctx, int precision, const void* in, vo
 
 int mhip_launch_avgpool_hw(mhip_ctx* ctx, int precision, const void* in, void* out, int B, int HW, int C) {
   if (B < 1 || HW < 1 || C < 1) return mhip_fail(ctx, MHIP_EINVAL, "avgpool: bad shape");
-  const unsigned grid = grid_for((long long)B * C);
+  const unsigned grid = image_grid_for((long long)B * C);
   if (precision == MHIP_PREC_F16)
     PROF_LAUNCH(ctx, MHIP_K_IMAGE_OPS, hipLaunchKernelGGL((avgpool_hw_kernel<_Float16>), dim3(grid), dim3(256), 0,
                                                           ctx->stream, (const _Float16*)in, (_Float16*)out, B, HW, C));

@@ -316,11 +316,6 @@ __global__ __launch_bounds__(256) void upsample_bilinear_kernel(const T* __restr
   }
 }
 
-unsigned grid_for(long long total) {
-  long long g = (total + 255) / 256;
-  return (unsigned)(g < 1 ? 1 : (g > 256 * 32 ? 256 * 32 : g));
-}
-
 }  // namespace
 
 // Host side of cv2.resize's coefficient tables (same float arithmetic as OpenCV's resize.cpp).
@@ -384,7 +379,7 @@ int mhip_launch_maxpool(mhip_ctx* ctx, int precision, int k, const void* in, voi
   if ((k != 2 && k != 3) || B < 1 || H < 1 || W < 1 || C % vn) return mhip_fail(ctx, MHIP_EINVAL, "maxpool: bad args");
   const int Ho = k == 2 ? H / 2 : H, Wo = k == 2 ? W / 2 : W;
   if (Ho < 1 || Wo < 1) return mhip_fail(ctx, MHIP_EINVAL, "maxpool: empty output");
-  const unsigned grid = grid_for((long long)B * Ho * Wo * (C / vn));
+  const unsigned grid = image_grid_for((long long)B * Ho * Wo * (C / vn));
 #define MP(T, K)                                                                                               \
   PROF_LAUNCH(ctx, MHIP_K_IMAGE_OPS,                                                                           \
               hipLaunchKernelGGL((maxpool_kernel<T, K>), dim3(grid), dim3(256), 0, ctx->stream, (const T*)in, \
@@ -407,7 +402,7 @@ int mhip_launch_upsample_bilinear(mhip_ctx* ctx, int precision, const void* in, 
     return mhip_fail(ctx, MHIP_EINVAL, "upsample: bad args");
   // area_pixel_compute_scale(align_corners = false, no explicit scale_factor): in / out, in fp32
   const float sh = (float)Hi / (float)Ho, sw = (float)Wi / (float)Wo;
-  const unsigned grid = grid_for((long long)B * Ho * Wo * (C / vn));
+  const unsigned grid = image_grid_for((long long)B * Ho * Wo * (C / vn));
   if (precision == MHIP_PREC_F16) {
     PROF_LAUNCH(ctx, MHIP_K_IMAGE_OPS,
                 hipLaunchKernelGGL((upsample_bilinear_kernel<_Float16>), dim3(grid), dim3(256), 0, ctx->stream,
@@ -425,7 +420,7 @@ int mhip_launch_upsample_bilinear(mhip_ctx* ctx, int precision, const void* in, 
 int mhip_launch_score_head(mhip_ctx* ctx, int precision, const void* in, int in_stride, const float* w1,
                            const float* b1, const float* w2, const float* b2, float* scores, long long npix) {
   if (npix < 1 || in_stride < 16) return mhip_fail(ctx, MHIP_EINVAL, "score_head: bad shape");
-  const unsigned grid = grid_for(npix);
+  const unsigned grid = image_grid_for(npix);
   if (precision == MHIP_PREC_F16) {
     PROF_LAUNCH(ctx, MHIP_K_IMAGE_OPS,
                 hipLaunchKernelGGL((score_head_kernel<_Float16>), dim3(grid), dim3(256), 0, ctx->stream,

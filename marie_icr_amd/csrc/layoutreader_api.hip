@@ -148,10 +148,10 @@ int lr_block_tail(mhip_layoutreader* m, int i, long long rows, const char* ao, f
   const float eps = m->cfg.ln_eps;
   int rc;
   if ((rc = mhip_gemm(ctx, prec, ao, a.d(enc_blk(i, "ao_w")), rows, D, D, nullptr, a.d<float>(enc_blk(i, "ao_b")), y, ACT_NONE, 1, h))) return rc;
-  if ((rc = mhip_launch_berttext_layernorm(ctx, prec, y, a.d<float>(enc_blk(i, "ln1_g")), a.d<float>(enc_blk(i, "ln1_b")), h, ht, (int)rows, D, eps))) return rc;
+  if ((rc = mhip_launch_row_layernorm(ctx, MHIP_K_BERTTEXT_EMBED, prec, y, 0, nullptr, a.d<float>(enc_blk(i, "ln1_g")), a.d<float>(enc_blk(i, "ln1_b")), h, ht, (int)rows, D, eps))) return rc;
   if ((rc = mhip_gemm(ctx, prec, ht, a.d(enc_blk(i, "fc1_w")), rows, F, D, nullptr, a.d<float>(enc_blk(i, "fc1_b")), hid, ACT_GELU, 0))) return rc;
   if ((rc = mhip_gemm(ctx, prec, hid, a.d(enc_blk(i, "fc2_w")), rows, D, F, nullptr, a.d<float>(enc_blk(i, "fc2_b")), y, ACT_NONE, 1, h))) return rc;
-  return mhip_launch_berttext_layernorm(ctx, prec, y, a.d<float>(enc_blk(i, "ln2_g")), a.d<float>(enc_blk(i, "ln2_b")), h, ht, (int)rows, D, eps);
+  return mhip_launch_row_layernorm(ctx, MHIP_K_BERTTEXT_EMBED, prec, y, 0, nullptr, a.d<float>(enc_blk(i, "ln2_g")), a.d<float>(enc_blk(i, "ln2_b")), h, ht, (int)rows, D, eps);
 }
 
 // the source rows of every page: embeddings (run.E / run.Et), then page by page the encoder over the n + 2 real rows, filling

@@ -7,7 +7,8 @@
 // cached), BertPredictionHeadTransform's LayerNorm with the einsum against the source embedding of LayoutlmSPLMPredictionHead,
 // and the torch.max / torch.gather that turn the scores into the next step's token.
 //
-// lr_embed: one wave per row, 16 bytes a lane.  A row is described by 8 ints in HBM (x0, y0, x1, y1, position id, type id, two
+// lr_embed: one wave per row, 16 bytes a lane (the row's load, LayerNorm and store, here and in lr_pointer_scores: row_ops.h; the
+//   row LayerNorms of the layers: row_ops.hip's kernel, counted in berttext_embed).  A row is described by 8 ints in HBM (x0, y0, x1, y1, position id, type id, two
 //   spare): the source rows' come from the host, a step's rows are written by lr_pointer_select of the step before, so the 511
 //   steps are enqueued back to back and no decision travels to the host in between.
 // lr_decode_attn: one workgroup per (page, head), NQ = 1 or 2 query rows, head dim 64.  The keys of query row i are
@@ -32,23 +33,6 @@ namespace {
 constexpr int LR_THREADS = 256;
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
-// a lane's float4 groups of the row -> the fp32 stream and the operand of the next GEMM
-template <typename T>
-__device__ __forceinline__ void lr_store_row(const float4v v[ROW_GROUPS], float* __restrict__ h, T* __restrict__ ht, size_t row, int D, int lane) {
-#pragma unroll
-  for (int i = 0; i < ROW_GROUPS; ++i) {
-    const int c = (i * 64 + lane) * 4;
-    if (c < D) {
-      *(float4v*)(h + row * D + c) = v[i];
-      if (ht) {
-        T o4[4] = {(T)v[i][0], (T)v[i][1], (T)v[i][2], (T)v[i][3]};
-        if (sizeof(T) == 2) *(uint64_t*)(ht + row * D + c) = *(uint64_t*)o4;
-        else *(float4v*)(ht + row * D + c) = *(float4v*)o4;
-      }
-    }
-  }
-}
 
 struct EmbedArgs {
   const int* tok;
@@ -76,18 +60,11 @@ __global__ __launch_bounds__(LR_THREADS) void lr_embed_kernel(EmbedArgs a, T* __
                          a.we + (size_t)clampi(x1 - x0, 0, m2) * D,
                          a.type + (size_t)clampi(t[5], 0, a.type_vocab - 1) * D};
   float4v v[ROW_GROUPS];
+  row_load(v, src[0], D, lane);
 #pragma unroll
-  for (int i = 0; i < ROW_GROUPS; ++i) {
-    const int c = (i * 64 + lane) * 4;
-    v[i] = (float4v){0.f, 0.f, 0.f, 0.f};
-    if (c < D) {
-      v[i] = *(const float4v*)(src[0] + c);
-#pragma unroll
-      for (int s = 1; s < 8; ++s) v[i] += *(const float4v*)(src[s] + c);
-    }
-  }
+  for (int s = 1; s < 8; ++s) row_add(v, src[s], D, lane);
   row_layernorm(v, D, lane, a.g, a.b, a.eps);
-  lr_store_row<T>(v, a.h, ht, (size_t)row, D, lane);
+  row_store<T>(v, a.h + (size_t)row * D, ht ? ht + (size_t)row * D : nullptr, D, lane);
 }
 
 // ------------------------------------------------------------------------------------------------------- decode attention
@@ -243,14 +220,8 @@ __global__ __launch_bounds__(LR_THREADS) void lr_pointer_scores_kernel(const flo
                                                                        const float* __restrict__ bias, int S, int D,
                                                                        float* __restrict__ sc, long long sc_stride) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, page = blockIdx.y;
-  const float* xr = x + ((size_t)page * nq + nq - 1) * D;
   float4v v[ROW_GROUPS];
-#pragma unroll
-  for (int i = 0; i < ROW_GROUPS; ++i) {
-    const int c = (i * 64 + lane) * 4;
-    v[i] = (float4v){0.f, 0.f, 0.f, 0.f};
-    if (c < D) v[i] = *(const float4v*)(xr + c);
-  }
+  row_load(v, x + ((size_t)page * nq + nq - 1) * D, D, lane);
   row_layernorm(v, D, lane, g, b, eps);
   for (int r = 0; r < PS_ROWS / 4; ++r) {
     const int j = blockIdx.x * PS_ROWS + wave * (PS_ROWS / 4) + r;

@@ -369,10 +369,10 @@ int vit_encode(mhip_vit* m, const uint8_t* imgs, int B, int th, int tw, int H32,
       if ((rc = consume_rows(a.d(enc_blk(i, "fc1_w")), 4 * D, a.d<float>(enc_blk(i, "fc1_cs")), a.d<float>(enc_blk(i, "fc1_b")), hid, ACT_GELU))) return rc;
       if ((rc = produce(hid, a.d(enc_blk(i, "fc2_w")), 4 * D, a.d<float>(enc_blk(i, "fc2_s")), a.d<float>(enc_blk(i, "fc2_b"))))) return rc;
     } else {
-      if ((rc = mhip_launch_layernorm(ctx, prec, x, a.d<float>(enc_blk(i, "ln1_g")), a.d<float>(enc_blk(i, "ln1_b")), ln, (int)R, D, c.ln_eps, x16))) return rc;
+      if ((rc = mhip_launch_row_layernorm(ctx, MHIP_K_VIT_OPS, prec, x, x16, nullptr, a.d<float>(enc_blk(i, "ln1_g")), a.d<float>(enc_blk(i, "ln1_b")), nullptr, ln, (int)R, D, c.ln_eps))) return rc;
       if ((rc = encoder_block_attention(ctx, prec, a, i, w, ad))) return rc;
       if ((rc = mhip_gemm(ctx, prec, ao, a.d(enc_blk(i, "ao_w")), (long long)R, D, D, a.d<float>(enc_blk(i, "proj_s")), a.d<float>(enc_blk(i, "ao_b")), x, ACT_NONE, x16 ? 0 : 1, x))) return rc;
-      if ((rc = mhip_launch_layernorm(ctx, prec, x, a.d<float>(enc_blk(i, "ln2_g")), a.d<float>(enc_blk(i, "ln2_b")), ln, (int)R, D, c.ln_eps, x16))) return rc;
+      if ((rc = mhip_launch_row_layernorm(ctx, MHIP_K_VIT_OPS, prec, x, x16, nullptr, a.d<float>(enc_blk(i, "ln2_g")), a.d<float>(enc_blk(i, "ln2_b")), nullptr, ln, (int)R, D, c.ln_eps))) return rc;
       if ((rc = mhip_gemm(ctx, prec, ln, a.d(enc_blk(i, "fc1_w")), (long long)R, 4 * D, D, nullptr, a.d<float>(enc_blk(i, "fc1_b")), hid, ACT_GELU, 0))) return rc;
       if ((rc = mhip_gemm(ctx, prec, hid, a.d(enc_blk(i, "fc2_w")), (long long)R, D, 4 * D, a.d<float>(enc_blk(i, "fc2_s")), a.d<float>(enc_blk(i, "fc2_b")), x, ACT_NONE, x16 ? 0 : 1, x))) return rc;
     }
@@ -382,7 +382,7 @@ int vit_encode(mhip_vit* m, const uint8_t* imgs, int B, int th, int tw, int H32,
   }
   if (c.final_norm) {
     if (!run->tokens_dst) MHIP_HIP(ctx, hipMemsetAsync(run->tokens + R * D * es, 0, (size_t)CROSS_ATTN_SLACK_ROWS * D * es, ctx->stream));
-    if ((rc = mhip_launch_layernorm(ctx, prec, x, a.d<float>("norm_g"), a.d<float>("norm_b"), run->tokens, (int)R, D, c.ln_eps, x16 || fold, xlo))) return rc;
+    if ((rc = mhip_launch_row_layernorm(ctx, MHIP_K_VIT_OPS, prec, x, x16 || fold, xlo, a.d<float>("norm_g"), a.d<float>("norm_b"), nullptr, run->tokens, (int)R, D, c.ln_eps))) return rc;
   }
   return MHIP_OK;
 }

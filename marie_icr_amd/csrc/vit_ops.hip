@@ -1,9 +1,9 @@
 // vit_ops.hip — the non-GEMM pieces of the ViT encoder stack shared by the DiT detector backbone and the TrOCR encoder:
-// LayerNorm, patch extraction, token <-> feature-map moves, bicubic position-embedding resize.
+// patch extraction, token <-> feature-map moves, bicubic position-embedding resize.
 //
-// Replaces, in marie/boxes/dit/ditod/beit.py: Block's nn.LayerNorm (:293,305), PatchEmbed's patch gather + bicubic
-// pos-emb resize (:362-376), and the token -> NCHW tap reshape of forward_features (:730-732).  (GEMMs — qkv, proj, fc1,
-// fc2, patch projection — are conv_igemm.hip; the softmax attention is attn_flash.hip.)
+// Replaces, in marie/boxes/dit/ditod/beit.py: PatchEmbed's patch gather + bicubic pos-emb resize (:362-376), and the token ->
+// NCHW tap reshape of forward_features (:730-732).  (GEMMs — qkv, proj, fc1, fc2, patch projection — are conv_igemm.hip; the
+// softmax attention is attn_flash.hip; Block's nn.LayerNorm is row_ops.hip's kernel, counted in vit_ops.)
 //
 // Token layout: every image owns `npad` consecutive rows (npad % 8 == 0): row 0 = cls, rows 1..n_tok-1 = patches,
 // the rest padding (finite values, masked as keys).  The residual stream is fp32; GEMM operands are T (f16 / fp32).
@@ -14,60 +14,6 @@
 using namespace igemm;
 
 namespace {
-
-// ------------------------------------------------------------------------------------------------------- LayerNorm
-// one wave per row; D % 256 == 0, D <= 1024.  Two-pass (mean, then centred variance) in registers, fp32.  XT: element type of the
-// residual stream that is normalised (fp32, or f16 when the model keeps an f16 stream as the reference's .half() path does).
-// xlo: the low plane of a split stream (x = hi + lo, two f16 planes), or null.
-template <typename T, typename XT>
-__global__ __launch_bounds__(256) void layernorm_kernel(const XT* __restrict__ x, const float* __restrict__ g,
-                                                        const float* __restrict__ b, T* __restrict__ out, int rows,
-                                                        int D, float eps, const _Float16* __restrict__ xlo = nullptr) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= rows) return;
-  const int nv = D >> 8;   // 4-element groups per lane
-  float4v v[4];
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    if (i < nv) {
-      if (sizeof(XT) == 4) {
-        v[i] = *(const float4v*)((const float*)x + (size_t)row * D + (i * 64 + lane) * 4);
-      } else {
-        typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-        const half4 h = *(const half4*)((const _Float16*)x + (size_t)row * D + (i * 64 + lane) * 4);
-        v[i] = (float4v){(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
-        if (xlo) {
-          const half4 l = *(const half4*)(xlo + (size_t)row * D + (i * 64 + lane) * 4);
-          v[i] += (float4v){(float)l[0], (float)l[1], (float)l[2], (float)l[3]};
-        }
-      }
-      s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-    }
-#pragma unroll
-  for (int o = 32; o; o >>= 1) s += __shfl_xor(s, o);
-  const float mean = s / (float)D;
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    if (i < nv)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { float d = v[i][k] - mean; q += d * d; }
-#pragma unroll
-  for (int o = 32; o; o >>= 1) q += __shfl_xor(q, o);
-  const float rstd = 1.f / sqrtf(q / (float)D + eps);
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    if (i < nv) {
-      const int c = (i * 64 + lane) * 4;
-      const float4v gg = *(const float4v*)(g + c), bb = *(const float4v*)(b + c);
-      T o4[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) o4[k] = (T)((v[i][k] - mean) * rstd * gg[k] + bb[k]);
-      if (sizeof(T) == 2) *(uint64_t*)(out + (size_t)row * D + c) = *(uint64_t*)o4;
-      else *(float4v*)(out + (size_t)row * D + c) = *(float4v*)o4;
-    }
-}
 
 // ------------------------------------------------------------------------------------------------------- patches
 // resized page u8 [th][tw][3] (channel order as stored; `swap_rb` selects which stored channel is model channel 0)
@@ -270,25 +216,7 @@ __global__ void unnest_kernel(const T* __restrict__ in, const T* __restrict__ co
   }
 }
 
-inline int grid_for(long long total, int block) { return (int)std::min<long long>((total + block - 1) / block, 65535LL * 4); }
-
 }  // namespace
-
-int mhip_launch_layernorm(mhip_ctx* ctx, int precision, const void* x, const float* g, const float* b, void* out,
-                          int rows, int D, float eps, int x_f16, const void* x_lo) {
-  if (D % 256 != 0 || D > 1024 || rows <= 0) return mhip_fail(ctx, MHIP_EINVAL, "layernorm: D=%d rows=%d", D, rows);
-  if (x_f16 && precision != MHIP_PREC_F16) return mhip_fail(ctx, MHIP_EINVAL, "layernorm: an f16 stream needs the f16 mode");
-  if (x_lo && !x_f16) return mhip_fail(ctx, MHIP_EINVAL, "layernorm: a low plane belongs to an f16 high plane");
-  dim3 grid((rows + 3) / 4), block(256);
-  if (precision == MHIP_PREC_F16 && x_f16)
-    PROF_LAUNCH(ctx, MHIP_K_VIT_OPS, hipLaunchKernelGGL((layernorm_kernel<_Float16, _Float16>), grid, block, 0, ctx->stream, (const _Float16*)x, g, b, (_Float16*)out, rows, D, eps, (const _Float16*)x_lo));
-  else if (precision == MHIP_PREC_F16)
-    PROF_LAUNCH(ctx, MHIP_K_VIT_OPS, hipLaunchKernelGGL((layernorm_kernel<_Float16, float>), grid, block, 0, ctx->stream, (const float*)x, g, b, (_Float16*)out, rows, D, eps));
-  else
-    PROF_LAUNCH(ctx, MHIP_K_VIT_OPS, hipLaunchKernelGGL((layernorm_kernel<float, float>), grid, block, 0, ctx->stream, (const float*)x, g, b, (float*)out, rows, D, eps));
-  CHECK_LAUNCH(ctx, "layernorm");
-  return 0;
-}
 
 int mhip_launch_patchify(mhip_ctx* ctx, int precision, const uint8_t* img, int B, int th, int tw, int hp, int wp, int P,
                          int swap_rb, float mean, float stdv, void* out, int ld) {

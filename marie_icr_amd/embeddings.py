@@ -39,8 +39,8 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from ._lib import (PREC_F16, PREC_F32, BertTextConfig, ClipResNetConfig, ClipTextConfig, ClipVisConfig, Context, MarieHipError,
-                   ModelHandle, SentenceEncoderConfig, check, load)
+from ._lib import (PREC_F16, PREC_F32, STAGE_GUARD, BertTextConfig, ClipResNetConfig, ClipTextConfig, ClipVisConfig, Context,
+                   MarieHipError, ModelHandle, SentenceEncoderConfig, check, load)
 from .clip_tokenizer import ClipTokenizer
 from .document_classifier import ByteLevelBPE
 from .wordpiece_tokenizer import WordPieceTokenizer
@@ -1234,6 +1234,22 @@ def bert_embed_rows_host(ctx: Context, word, type0, pos, g, b, ids, eps: float =
                                                        B, npad, word.shape[0], word.shape[1], _vp(out)),
           "mhip_berttext_embed_rows_host")
     return out
+
+
+def row_layernorm_host(ctx: Context, precision: int, x, g, b, eps: float, want_h: bool = True, want_ht: bool = True,
+                       in_place: bool = False, x_f16: bool = False, x_lo=None):
+    """The row LayerNorm every tower shares (csrc/row_ops.hip): x fp32 (rows, D), g / b (D) -> (h, ht), each None unless asked
+    for: h the fp32 rows, ht their copy in the precision's element type (widened).  Both are FLAT and STAGE_GUARD elements longer
+    than rows * D: the tail comes back as the 0xff fill unless the kernel wrote past its end.  in_place: h and x share one
+    device buffer.  x_f16: x is narrowed to an f16 stream (f16 mode only), x_lo its low plane or None"""
+    x, g, b = (np.ascontiguousarray(a, np.float32) for a in (x, g, b))
+    x_lo = None if x_lo is None else np.ascontiguousarray(x_lo, np.float32)
+    rows, D = x.shape
+    h = np.zeros(rows * D + STAGE_GUARD, np.float32) if want_h else None
+    ht = np.zeros(rows * D + STAGE_GUARD, np.float32) if want_ht else None
+    check(ctx.h, ctx.lib.mhip_row_layernorm_host(ctx.h, int(precision), _vp(x), int(x_f16), _vp(x_lo), _vp(g), _vp(b), rows, D,
+                                                 float(eps), int(in_place), _vp(h), _vp(ht)), "mhip_row_layernorm_host")
+    return h, ht
 
 
 def geglu_host(ctx: Context, precision: int, x) -> np.ndarray:
