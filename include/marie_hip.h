@@ -1081,6 +1081,22 @@ int mhip_berttext_create(mhip_ctx* ctx, int precision, const mhip_berttext_confi
  * any with alibi), rel_buckets odd or below 4 (or any with alibi: slopes and a table together), rel_max_distance outside
  * 1 .. 8192 with rel_buckets or non-zero without                                                                              */
 int mhip_berttext_create_ex(mhip_ctx* ctx, int precision, const mhip_berttext_config_ex* cfg, mhip_berttext** out);
+/* the same with Longformer's windowed attention and a sequence-classification head appended (LongformerForSequenceClassification
+ * as pipeline("text-classification") runs it: global attention on <s> alone).  In layer l a token i >= 1 attends to token 0 and to
+ * the tokens max(1, i - w_l) .. min(len - 1, i + w_l), w_l = attention_window[l] / 2 (attn_window); token 0 attends to all of them
+ * through query_global / key_global / value_global (attn_global_row); logits = out_proj(tanh(dense(row 0))) (cls_head).            */
+typedef struct mhip_berttext_config_cls {
+  mhip_berttext_config_ex ex;      /* RoBERTa's front: pos_offset 2, type_vocab 1; position absolute, no rel_buckets; heads of 64  */
+  const int* attention_window;     /* [depth] the two-sided window of every layer as config.json holds it: even, 2 .. 1024         */
+  int num_labels;                  /* 1 .. 1024                                                                                  */
+  int head_function;               /* scores of classify_host: 0 the logits, 1 their soft-max, 2 their sigmoid                   */
+} mhip_berttext_config_cls;
+/* as create_ex, plus MHIP_EINVAL naming the field: attention_window NULL, odd or not positive, a one-sided window above 512;
+ * num_labels outside 1 .. 1024; an unknown head_function; a head dimension other than 64; alibi or rel_buckets.  set_tensor then
+ * takes, in addition, encoder.layer.N.attention.self.{query,key,value}_global.* and classifier.{dense,out_proj}.* (a "longformer."
+ * prefix is stripped as "bert." is), and finalize names the first of them that is missing.  embed_host and debug_taps_host work
+ * on such a handle: they pool, and tap, the windowed encoder's rows                                                           */
+int mhip_berttext_create_cls(mhip_ctx* ctx, int precision, const mhip_berttext_config_cls* cfg, mhip_berttext** out);
 int mhip_berttext_destroy(mhip_berttext* m);
 /* keys of Hugging Face BERT (an optional "bert." prefix is stripped): embeddings.{word,position,token_type}_embeddings.weight,
  * embeddings.LayerNorm.*, encoder.layer.N.attention.self.{query,key,value}.*, attention.output.{dense,LayerNorm}.*,
@@ -1093,7 +1109,7 @@ int mhip_berttext_set_tensor(mhip_berttext* m, const char* key, const float* dat
 int mhip_berttext_finalize(mhip_berttext* m);
 int mhip_berttext_alloc_arena(mhip_berttext* m);
 int mhip_berttext_arena(mhip_berttext* m, void** arena_dev, size_t* bytes);
-/* bytes of context workspace one mhip_berttext_embed_host (or debug_taps_host) call of B texts of npad rows lays out (0: bad
+/* bytes of context workspace one mhip_berttext_embed_host (or debug_taps_host, classify_host) call of B texts of npad rows lays out (0: bad
  * arguments); mhip_berttext_embed_pairs_host lays out three arrays of 4 * n_pairs bytes more, each rounded up to 256            */
 size_t mhip_berttext_workspace_bytes(mhip_berttext* m, int B, int npad);
 /* the ALiBi slopes of `heads` heads, fp32 [heads]: 2^(-8 (i + 1) / n) for n a power of two; otherwise those of the largest power
@@ -1107,6 +1123,11 @@ int mhip_berttext_rel_table(int buckets, int max_distance, const float* weight, 
 /* B texts (1 .. 4096) -> emb_out fp32 [B][dim].  MHIP_EINVAL, never a clamp: npad no multiple of 8 or above 8192 (or above the
  * position table rounded up to 8), more than 524288 rows (B * npad), a len outside [1, npad], an id outside [0, vocab)        */
 int mhip_berttext_embed_host(mhip_berttext* m, const int32_t* ids, const int32_t* len, int B, int npad, float* emb_out);
+/* B texts through the encoder and the classification head: logits_out, scores_out fp32 [B][num_labels] (scores: head_function of
+ * the logits).  The arguments and refusals of embed_host; MHIP_ESTATE on a handle without a head (not from create_cls).  A text's
+ * logits do not depend on the other texts of the call or on npad, bit for bit                                                  */
+int mhip_berttext_classify_host(mhip_berttext* m, const int32_t* ids, const int32_t* len, int B, int npad, float* logits_out,
+                                float* scores_out);
 /* the texts through the encoder once, then cos_out[p] = x.y / max(|x| |y|, 1e-8) of the embeddings of texts pair_a[p], pair_b[p]
  * (fp32 [n_pairs]); emb_out fp32 [B][dim] or NULL                                                                             */
 int mhip_berttext_embed_pairs_host(mhip_berttext* m, const int32_t* ids, const int32_t* len, int B, int npad,
@@ -1141,6 +1162,19 @@ int mhip_berttext_attention_rel_host(mhip_ctx* ctx, int precision, const float* 
 int mhip_berttext_attention_rel_long_host(mhip_ctx* ctx, int precision, const float* q, const float* k, const float* v,
                                           const int32_t* len, const float* table, int radius, int B, int heads, int head_dim, int npad,
                                           float* out);
+/* attn_window alone, on the layout of the entries above (head_dim 64): query i of sequence b over key 0 and the keys
+ * max(1, i - w) .. min(len[b] - 1, i + w), w one-sided in 1 .. 512; npad a multiple of 8 up to 8192.  Row 0 and the rows >= len[b]
+ * come back finite and mean nothing                                                                                            */
+int mhip_berttext_attention_window_host(mhip_ctx* ctx, int precision, const float* q, const float* k, const float* v,
+                                        const int32_t* len, int w, int B, int heads, int head_dim, int npad, float* out);
+/* attn_global_row alone: qg fp32 [B][heads * 64] (scaled like q above, kept fp32), kg, vg fp32 [B][npad][heads * 64] rounded to the
+ * precision's element type -> out fp32 [B][heads * 64] = softmax(qg . kg[j], j < len[b]) vg per head                            */
+int mhip_berttext_attention_global_host(mhip_ctx* ctx, int precision, const float* qg, const float* kg, const float* vg,
+                                        const int32_t* len, int B, int heads, int npad, float* out);
+/* cls_head alone, fp32: h0 [B][D], dense_w [D][D], dense_b [D], out_w [L][D], out_b [L] -> logits_out, scores_out [B][L];
+ * function 0 / 1 / 2 as head_function.  D a multiple of 64 up to 1024, L up to 1024                                             */
+int mhip_berttext_cls_head_host(mhip_ctx* ctx, const float* h0, const float* dense_w, const float* dense_b, const float* out_w,
+                                const float* out_b, int B, int D, int L, int function, float* logits_out, float* scores_out);
 /* x fp32 [R][2 F], rounded to the precision's element type -> out fp32 [R][F] = gelu_erf(x[:, :F]) * x[:, F:]                 */
 int mhip_berttext_geglu_host(mhip_ctx* ctx, int precision, const float* x, int R, int F, float* out);
 /* h fp32 [B][npad][D], len [B] -> emb_out fp32 [B][D]: mode 0 the mean of rows < len[b], 1 row 0; normalize 0 / 1            */

@@ -229,6 +229,11 @@ _SIGNATURES = (
     ("mhip_berttext_attention_rel_long_host", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     ("mhip_berttext_geglu_host", _i, [_vp, _i, _vp, _i, _i, _vp]),
     ("mhip_berttext_pool_host", _i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    ("mhip_berttext_create_cls", _i, [_vp, _i, _vp, C.POINTER(_vp)]),
+    ("mhip_berttext_classify_host", _i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    ("mhip_berttext_attention_window_host", _i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    ("mhip_berttext_attention_global_host", _i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    ("mhip_berttext_cls_head_host", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     ("mhip_layoutreader_create", _i, [_vp, _i, _vp, C.POINTER(_vp)]),
     ("mhip_layoutreader_destroy", _i, [_vp]),
     ("mhip_layoutreader_set_tensor", _i, [_vp, C.c_char_p, _vp, C.POINTER(C.c_int64), _i]),
@@ -392,6 +397,13 @@ class BertTextConfig(C.Structure):
 class SentenceEncoderConfig(BertTextConfig):
     """mirror of mhip_berttext_config_ex (include/marie_hip.h): the fields above, then those of the other families"""
     _fields_ = [("pos_offset", C.c_int), ("rel_buckets", C.c_int), ("rel_max_distance", C.c_int)]
+
+
+class TextClassifierConfig(C.Structure):
+    """mirror of mhip_berttext_config_cls (include/marie_hip.h).  ``attention_window`` points at an int array the owner keeps
+    alive for the duration of the create call"""
+    _fields_ = [("ex", SentenceEncoderConfig), ("attention_window", C.POINTER(C.c_int)), ("num_labels", C.c_int),
+                ("head_function", C.c_int)]
 
 
 class LayoutReaderConfig(C.Structure):

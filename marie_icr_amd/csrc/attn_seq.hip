@@ -4,7 +4,9 @@
 // soft-max (attn_long: up to 8192 rows).  Every step is written once, in Seq<T, HD> below; the kernels differ in four things:
 // which key tiles a query tile walks and which scores of the last walked tile become -inf (data: `nvis`, `limit`), the ALiBi
 // term (a branch), the relative-distance table's term (MPNet: a template parameter, so the instances without it are the code
-// they were), and whether the block's result is normalised directly or folded into a running (m, l, o).
+// they were), and whether the block's result is normalised directly or folded into a running (m, l, o).  Longformer's attention
+// (berttext_api.hip with windows) is two more kernels, described where they stand: attn_window, the streamed kernel over a band
+// of keys plus key 0 (the *_band steps of Seq), and attn_global_row, the global token's single query over all keys.
 //
 // Replaces, in transformers/models/clip/modeling_clip.py: the attention of CLIPEncoderLayer under the causal mask of
 // CLIPTextTransformer (clip/model.py: the attn_mask of build_attention_mask); in transformers/models/bert/modeling_bert.py: the
@@ -34,6 +36,7 @@
 //        enters as zeros), probabilities rounded to f16 only as that operand; the row sum is of the fp32 probabilities.
 //   f32: v_mfma_f32_16x16x4_f32, an fp32 fma chain: no f16 value anywhere.
 #include <algorithm>
+#include <type_traits>
 
 #include "igemm_common.h"
 
@@ -254,6 +257,92 @@ struct Seq {
     }
   }
 
+  // ---- the same steps over the tiles tlo <= t < thi of the block (uniform across the wave), for a band of keys (attn_window)
+  // S^T of those tiles; the others are zeros and are not computed.  Key 16 t + 4 g + r of the block is the lane's to see when
+  // lo <= it <= hi (the query's band, counted from the block's first key); a tile inside [ilo, ihi], the band every query of
+  // the wave shares, needs no mask.  A masked score is a select on the product: the keys below the band are rows of the text
+  static __device__ __forceinline__ void scores_band(const T* Ks, const chunk_t (&qf)[NKS], int tlo, int thi, int lo, int hi, int ilo,
+                                                     int ihi, int g, int n, float4v (&s)[SEQ_NT]) {
+    const int lo4 = lo - 4 * g, hi4 = hi - 4 * g;
+#pragma unroll
+    for (int t = 0; t < SEQ_NT; ++t) {
+      float4v c = {0.f, 0.f, 0.f, 0.f};
+      if (t >= tlo && t < thi) {
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) {
+          const chunk_t a = *(const chunk_t*)&Ks[L::k(t * 16 + n, ks * 4 * E + g * E)];
+          X::mma(a, qf[ks], c);
+        }
+        if (t * 16 < ilo || t * 16 + 15 > ihi) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            if (t * 16 + r < lo4 || t * 16 + r > hi4) c[r] = -INFINITY;
+        }
+      }
+      s[t] = c;
+    }
+  }
+
+  // the maximum of the walked scores: -inf for a query that sees none of them
+  static __device__ __forceinline__ float block_max_band(const float4v (&s)[SEQ_NT], int tlo, int thi) {
+    float m = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < SEQ_NT; ++t)
+      if (t >= tlo && t < thi) m = fmaxf(fmaxf(fmaxf(s[t][0], s[t][1]), fmaxf(s[t][2], s[t][3])), m);
+    m = fmaxf(m, __shfl_xor(m, 16));
+    return fmaxf(m, __shfl_xor(m, 32));
+  }
+
+  // s -> exp2(s - m) on the walked tiles (m finite); the others stay zeros
+  static __device__ __forceinline__ float exp_sum_band(float4v (&s)[SEQ_NT], int tlo, int thi, float m) {
+    float l = 0.f;
+#pragma unroll
+    for (int t = 0; t < SEQ_NT; ++t) {
+      float4v e = s[t];
+      if (t >= tlo && t < thi) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) e[r] = __builtin_amdgcn_exp2f(e[r] - m);
+        l += (e[0] + e[1]) + (e[2] + e[3]);
+      }
+      s[t] = e;
+    }
+    return l;
+  }
+
+  // O^T += V^T P^T over the walked tiles; f16: a 32-key step with one walked tile takes the other's probabilities as the zeros
+  // they are (both tiles are staged: staged() rounds up to the step)
+  static __device__ __forceinline__ void pv_band(const T* Vs, const float4v (&s)[SEQ_NT], int tlo, int thi, int g, int n, float4v (&o)[NDT]) {
+    if constexpr (sizeof(T) == 2) {
+#pragma unroll
+      for (int t0 = 0; t0 < SEQ_NT; t0 += 2)
+        if (t0 + 1 >= tlo && t0 < thi) {
+          half8 b;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            b[r] = (_Float16)s[t0][r];
+            b[4 + r] = (_Float16)s[t0 + 1][r];
+          }
+#pragma unroll
+          for (int dt = 0; dt < NDT; ++dt) {
+            const half4 lo = *(const half4*)&Vs[L::v(dt * 16 + n, t0 * 16 + 4 * g)];
+            const half4 hi = *(const half4*)&Vs[L::v(dt * 16 + n, t0 * 16 + 16 + 4 * g)];
+            const half8 a = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+            X::mma(a, b, o[dt]);
+          }
+        }
+    } else {
+#pragma unroll
+      for (int t = 0; t < SEQ_NT; ++t)
+        if (t >= tlo && t < thi) {
+#pragma unroll
+          for (int dt = 0; dt < NDT; ++dt) {
+            const float4v a = *(const float4v*)&Vs[L::v(dt * 16 + n, t * 16 + 4 * g)];
+            X::mma(a, s[t], o[dt]);
+          }
+        }
+    }
+  }
+
   // out[query][head] = o * inv, for the queries that are rows of the sequence
   static __device__ __forceinline__ void store(const SeqArgs<T>& p, int head, size_t row0, int query, int g, const float4v (&o)[NDT], float inv) {
     if (query >= p.npad) return;
@@ -383,6 +472,179 @@ __global__ __launch_bounds__(SEQ_THREADS) void attn_seq_stream_kernel(SeqRelArgs
   S::store(p, head, row0, query, g, o, 1.f / l);
 }
 
+// attn_window: Longformer's attention of the local queries.  Query i of a text of len rows sees key 0 (the one global token, with
+// the local k_0, v_0, counted once) and the keys max(1, i - w) .. min(len - 1, i + w).  The workgroup and the steps are attn_long's;
+// what differs is data: the walk of a block of 64 queries at q0 starts at max(1, q0 - w) rounded down to 16 (the V^T chunks stay
+// 16-byte aligned) and ends at min(len, q0 + 64 + w); a wave skips the key tiles outside the union of its 16 bands, and masks, per
+// lane, from below and from above, the tiles that are not inside all of them.  Key 0 is the state the walk starts from:
+// m = q_i . k_0, l = 1, o = v_0 — a one-key block without a product — so m is finite for every row and a query that sees no key of
+// a block folds it in with alpha = 1 and probabilities exp2(-inf) = 0.  The walk is a function of (q0, w, len) alone: a text's
+// rows do not depend on npad or on the batch.  Rows >= len and row 0 are computed like the others, finite; nobody reads them (row 0
+// is attn_global_row's).  Head dim 64.
+template <typename T>
+struct SeqWinArgs : SeqArgs<T> {
+  int w;      // one-sided window, 1 .. 512
+};
+
+template <typename T, int HD>
+__global__ __launch_bounds__(SEQ_THREADS) void attn_seq_window_kernel(SeqWinArgs<T> p) {
+  typedef Seq<T, HD> S;
+  constexpr int E = S::E;
+  __shared__ __attribute__((aligned(16))) T Ks[S::L::KSZ];
+  __shared__ __attribute__((aligned(16))) T Vs[S::L::VSZ];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int g = lane >> 4, n = lane & 15;
+  const int head = blockIdx.x % p.heads, seq = blockIdx.x / p.heads;
+  const int npad = p.npad, w = p.w;
+  const size_t row0 = (size_t)seq * npad;
+  const int len = min(max(p.len[seq], 1), npad);
+  const int q0 = blockIdx.y * SEQ_QB;
+  const int qa = q0 + wave * 16, query = qa + n;
+  float4v o[S::NDT];
+#pragma unroll
+  for (int dt = 0; dt < S::NDT; ++dt) o[dt] = (float4v){0.f, 0.f, 0.f, 0.f};
+  if (q0 >= len) {      // uniform over the workgroup: nobody reads these rows, they are written as zeros
+    S::store(p, head, row0, query, g, o, 1.f);
+    return;
+  }
+  typename S::chunk_t qf[S::NKS];
+  S::load_q(p, head, row0, query, g, qf);
+
+  // key 0: the lane group's quarter of q . k_0, summed over the four groups in an order that gives each the same bits
+  float m = 0.f;
+#pragma unroll
+  for (int ks = 0; ks < S::NKS; ++ks) {
+    const typename S::chunk_t kc = *(const typename S::chunk_t*)(p.k + row0 * p.ldk + head * HD + ks * 4 * E + g * E);
+#pragma unroll
+    for (int j = 0; j < E; ++j) m += (float)qf[ks][j] * (float)kc[j];
+  }
+  m += __shfl_xor(m, 16);
+  m += __shfl_xor(m, 32);
+  float l = g == 0 ? 1.f : 0.f;      // the lane's partial sum, as in attn_long
+#pragma unroll
+  for (int dt = 0; dt < S::NDT; ++dt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) o[dt][r] = (float)p.vt[((size_t)head * HD + dt * 16 + 4 * g + r) * p.ldv + row0];
+
+  const int kend = min(len, q0 + SEQ_QB + w);            // one past the last key of the walk
+  const int a0 = max(1, q0 - w) & ~15;
+  const int lo = max(1, query - w), hi = min(len - 1, query + w);      // the lane's band
+  // the wave's: the union of its bands (empty for a tile past the text) and what they share
+  const int ulo = max(1, qa - w), uhi = qa < len ? min(len - 1, qa + 15 + w) : -1;
+  const int ilo = max(1, qa + 15 - w), ihi = min(len - 1, qa + w);
+  for (int k0 = a0; k0 < kend; k0 += SEQ_MAXK) {
+    const int blen = min(kend - k0, SEQ_MAXK);      // keys of this block, >= 1, all rows of the text
+    const int nkt = (blen + 15) >> 4;
+    if (k0 != a0) __syncthreads();      // the block before has been read
+    S::template stage<true>(p, Ks, Vs, head, row0, k0, blen, S::staged(nkt));
+    __syncthreads();
+    const int tlo = max(ulo - k0, 0) >> 4, thi = min(((uhi - k0) >> 4) + 1, nkt);
+    if (tlo < thi) {
+      float4v s[SEQ_NT];
+      S::scores_band(Ks, qf, tlo, thi, lo - k0, hi - k0, ilo - k0, ihi - k0, g, n, s);
+      const float mn = fmaxf(m, S::block_max_band(s, tlo, thi));
+      const float alpha = __builtin_amdgcn_exp2f(m - mn);
+      m = mn;
+      l = l * alpha + S::exp_sum_band(s, tlo, thi, mn);
+#pragma unroll
+      for (int dt = 0; dt < S::NDT; ++dt) o[dt] = o[dt] * alpha;
+      S::pv_band(Vs, s, tlo, thi, g, n, o);
+    }
+  }
+  l += __shfl_xor(l, 16);
+  l += __shfl_xor(l, 32);
+  S::store(p, head, row0, query, g, o, 1.f / l);
+}
+
+// attn_global_row: Longformer's attention of the global token, query 0 of every text, over all len keys with the global
+// projections.  One workgroup = one (text, head); q_g fp32 [64] in the log2 units of the other kernels, k_g | v_g rows of the
+// element type.  The keys go by in chunks of 1024 under an online soft-max whose state (m, l, the 64 outputs) is fp32: a thread
+// scores a key (its row is 64 contiguous elements), the chunk's maximum and sum are reduced over the workgroup, then thread
+// (key group kg, output d) adds p_j v_j[d] over the keys j = kg mod 4.  The order is a function of len alone.  `bias` (fp32, or
+// null) is added to the normalised row: b_vg less the b_v that the output projection's folded bias adds to every row
+constexpr int GROW_CHUNK = 1024;
+
+template <typename T>
+struct GlobalRowArgs {
+  const float* qg;       // [seqs][ldq], head h at column h * 64
+  const T* k;            // [seqs * npad][ldk]
+  const T* v;            // [seqs * npad][ldv]
+  const float* bias;     // [heads * 64] or null
+  T* out;                // row seq * out_rows of [..][ldo]
+  const int* len;
+  int ldq, ldk, ldv, ldo, npad, heads;
+  long long out_rows;    // rows between two texts' outputs
+};
+
+// the workgroup's maximum / sum of v; every thread gets the same bits.  red: [4]
+template <bool MAX>
+__device__ __forceinline__ float grow_reduce(float v, float* red, int lane, int wave) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) {
+    const float u = __shfl_xor(v, o);
+    v = MAX ? fmaxf(v, u) : v + u;
+  }
+  __syncthreads();      // red of the reduction before has been read
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  return MAX ? fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) : (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void attn_global_row_kernel(GlobalRowArgs<T> p) {
+  typedef Tr<T> X;
+  typedef typename X::chunk_t chunk_t;
+  constexpr int E = X::E, HD = 64;
+  __shared__ float qs[HD];
+  __shared__ float sc[GROW_CHUNK];
+  __shared__ float red[4];
+  __shared__ float part[4][HD];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int head = blockIdx.x % p.heads, seq = blockIdx.x / p.heads;
+  const size_t row0 = (size_t)seq * p.npad;
+  const int len = min(max(p.len[seq], 1), p.npad);
+  if (tid < HD) qs[tid] = p.qg[(size_t)seq * p.ldq + head * HD + tid];
+  __syncthreads();
+  const int kg = wave, d = lane;
+  float m = -INFINITY, l = 0.f, acc = 0.f;
+  for (int c0 = 0; c0 < len; c0 += GROW_CHUNK) {
+    const int cn = min(len - c0, GROW_CHUNK);
+    float lm = -INFINITY;
+    for (int j = tid; j < cn; j += 256) {
+      const T* kr = p.k + (row0 + c0 + j) * p.ldk + head * HD;
+      float s = 0.f;
+#pragma unroll
+      for (int c = 0; c < HD / E; ++c) {
+        const chunk_t kc = *(const chunk_t*)(kr + c * E);
+#pragma unroll
+        for (int e = 0; e < E; ++e) s += qs[c * E + e] * (float)kc[e];
+      }
+      sc[j] = s;
+      lm = fmaxf(lm, s);
+    }
+    const float mn = fmaxf(m, grow_reduce<true>(lm, red, lane, wave));      // finite: the chunk has a key
+    const float alpha = __builtin_amdgcn_exp2f(m - mn);
+    m = mn;
+    float ls = 0.f;
+    for (int j = tid; j < cn; j += 256) {      // the thread's own scores
+      const float e = __builtin_amdgcn_exp2f(sc[j] - mn);
+      sc[j] = e;
+      ls += e;
+    }
+    l = l * alpha + grow_reduce<false>(ls, red, lane, wave);      // its barriers publish sc
+    acc *= alpha;
+    for (int j = kg; j < cn; j += 4) acc += sc[j] * (float)p.v[(row0 + c0 + j) * p.ldv + head * HD + d];
+    __syncthreads();      // sc is read before the next chunk's scores
+  }
+  part[kg][d] = acc;
+  __syncthreads();
+  if (tid < HD) {
+    float r = ((part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid])) / l;
+    if (p.bias) r += p.bias[head * HD + tid];
+    p.out[(size_t)seq * p.out_rows * p.ldo + head * HD + tid] = (T)r;
+  }
+}
+
 enum SeqKind { SEQ_CAUSAL, SEQ_SHORT, SEQ_LONG };
 
 // what the three entries require of an AttnDesc: counts, rows per sequence (a multiple of 8, 8 .. max_rows, the same for queries
@@ -473,5 +735,54 @@ int mhip_launch_attention_short(mhip_ctx* ctx, int precision, const AttnShortDes
 int mhip_launch_attention_long(mhip_ctx* ctx, int precision, const AttnShortDesc& s) {
   if (const int rc = seq_lengths_entry(ctx, "attention_long", SEQ_MAXROWS, SEQ_LONG, precision, s)) return rc;
   CHECK_LAUNCH(ctx, "attention_long");
+  return 0;
+}
+
+int mhip_launch_attention_window(mhip_ctx* ctx, int precision, const AttnShortDesc& s, int w) {
+  const AttnDesc& d = s.a;
+  if (s.head_dim != 64) return mhip_fail(ctx, MHIP_EINVAL, "attention_window: head_dim %d (64)", s.head_dim);
+  if (!s.len) return mhip_fail(ctx, MHIP_EINVAL, "attention_window: len is null");
+  if (s.slopes || s.rel_table) return mhip_fail(ctx, MHIP_EINVAL, "attention_window: no bias term (slopes, rel_table)");
+  if (w < 1 || w > ATTN_WINDOW_MAX) return mhip_fail(ctx, MHIP_EINVAL, "attention_window: w %d (one-sided, 1 .. %d)", w, ATTN_WINDOW_MAX);
+  if (const int rc = seq_check(ctx, "attention_window", SEQ_MAXROWS, precision, d)) return rc;
+  // the lengths live on the device: counted as full bands of full sequences
+  if (ctx->profiling) ctx->prof[MHIP_K_ATTN_SHORT].flops += 4.0 * d.images * d.heads * (double)d.npad_k * std::min(2 * w + 2, d.npad_k) * 64;
+  const dim3 blocks((unsigned)(d.images * d.heads), (unsigned)((d.npad_k + SEQ_QB - 1) / SEQ_QB)), threads(SEQ_THREADS);
+  // counted with the other per-sequence attentions: the profiler's list is pinned, and a call runs one of them
+  if (precision == MHIP_PREC_F16) {
+    SeqWinArgs<_Float16> a;
+    (SeqArgs<_Float16>&)a = seq_args<_Float16, false>(d, s.len, nullptr, nullptr, 0);
+    a.w = w;
+    PROF_LAUNCH(ctx, MHIP_K_ATTN_SHORT, hipLaunchKernelGGL((attn_seq_window_kernel<_Float16, 64>), blocks, threads, 0, ctx->stream, a));
+  } else {
+    SeqWinArgs<float> a;
+    (SeqArgs<float>&)a = seq_args<float, false>(d, s.len, nullptr, nullptr, 0);
+    a.w = w;
+    PROF_LAUNCH(ctx, MHIP_K_ATTN_SHORT, hipLaunchKernelGGL((attn_seq_window_kernel<float, 64>), blocks, threads, 0, ctx->stream, a));
+  }
+  CHECK_LAUNCH(ctx, "attention_window");
+  return 0;
+}
+
+int mhip_launch_attention_global_row(mhip_ctx* ctx, int precision, const AttnGlobalRowDesc& d) {
+  if (!d.qg || !d.k || !d.v || !d.out || !d.len) return mhip_fail(ctx, MHIP_EINVAL, "attention_global_row: null operand");
+  if (d.seqs <= 0 || d.heads <= 0 || (long long)d.seqs * d.heads > 0x7fffffffLL || d.npad < 8 || d.npad % 8 || d.npad > SEQ_MAXROWS || d.out_rows < 1)
+    return mhip_fail(ctx, MHIP_EINVAL, "attention_global_row: bad shape (%d sequences, %d heads, %d rows: a multiple of 8, 8 .. %d)", d.seqs, d.heads,
+                     d.npad, SEQ_MAXROWS);
+  const int esz = precision == MHIP_PREC_F16 ? 2 : 4;
+  if ((d.ldk * esz) % 16 || ((uintptr_t)d.k & 15) || d.ldk < d.heads * 64 || d.ldv < d.heads * 64 || d.ldq < d.heads * 64 || d.ldo < d.heads * 64)
+    return mhip_fail(ctx, MHIP_EINVAL, "attention_global_row: key rows must keep 16-byte alignment, every pitch hold heads * 64 columns");
+  if (ctx->profiling) ctx->prof[MHIP_K_ATTN_SHORT].flops += 4.0 * d.seqs * d.heads * (double)d.npad * 64;
+  const dim3 blocks((unsigned)(d.seqs * d.heads)), threads(256);
+  auto args = [&](auto* t) {
+    typedef std::remove_pointer_t<decltype(t)> T;
+    GlobalRowArgs<T> a;
+    a.qg = d.qg; a.k = (const T*)d.k; a.v = (const T*)d.v; a.bias = d.bias; a.out = (T*)d.out; a.len = d.len;
+    a.ldq = d.ldq; a.ldk = d.ldk; a.ldv = d.ldv; a.ldo = d.ldo; a.npad = d.npad; a.heads = d.heads; a.out_rows = d.out_rows;
+    return a;
+  };
+  if (precision == MHIP_PREC_F16) PROF_LAUNCH(ctx, MHIP_K_ATTN_SHORT, hipLaunchKernelGGL(attn_global_row_kernel<_Float16>, blocks, threads, 0, ctx->stream, args((_Float16*)nullptr)));
+  else PROF_LAUNCH(ctx, MHIP_K_ATTN_SHORT, hipLaunchKernelGGL(attn_global_row_kernel<float>, blocks, threads, 0, ctx->stream, args((float*)nullptr)));
+  CHECK_LAUNCH(ctx, "attention_global_row");
   return 0;
 }

@@ -14,6 +14,12 @@
 // layers are LayoutLMv3's (post-LN: attention, ao GEMM + residual, LayerNorm, fc1, fc2 + residual, LayerNorm) with attn_short as
 // the attention of calls of npad <= 128 and attn_long, which streams the keys, past that (at most 8192 rows a text and 4096 * 128
 // rows a call).  The word table stays fp32 in both precision modes: it is a gather of B * npad rows, not a GEMM operand.
+//
+// The same handle runs LongformerForSequenceClassification behind pipeline("text-classification") (transformers/models/longformer/
+// modeling_longformer.py: LongformerSelfAttention with global attention on <s> alone, LongformerClassificationHead), created
+// through mhip_berttext_create_cls: RoBERTa's embedding front, and in every layer attn_window for the local queries (the band of
+// that layer's window plus key 0), attn_global_row for query 0 (query_global / key_global / value_global over all the rows: k_g | v_g
+// from one GEMM into the MLP's hidden buffer, which is free during the attention), then the block as above; cls_head on row 0.
 #include <math.h>
 
 #include "encoder_block.h"
@@ -25,6 +31,8 @@ struct mhip_berttext {
   int precision = MHIP_PREC_F16;
   mhip_berttext_config cfg{};
   int pos_offset = 0, rel_buckets = 0, rel_max_distance = 0;      // mhip_berttext_config_ex's; zero through mhip_berttext_create
+  std::vector<int> window;                                        // mhip_berttext_config_cls's: the one-sided window of every layer
+  int num_labels = 0, head_function = 0;                          // (empty: full attention); 0 labels: no classification head
   TensorStore store;
   Arena arena;
   bool ready = false;
@@ -33,6 +41,8 @@ struct mhip_berttext {
   bool alibi() const { return cfg.position == BT_POS_ALIBI; }
   bool rel() const { return rel_buckets > 0; }
   bool geglu() const { return cfg.mlp == BT_MLP_GEGLU; }
+  bool windowed() const { return !window.empty(); }
+  bool has_head() const { return num_labels > 0; }
   // tokens of a text: the streamed attention's 8192, or the position table's rows when it has fewer
   int max_tokens() const { return alibi() ? 8192 : std::min(cfg.max_position - pos_offset, 8192); }
   int max_npad() const { return (max_tokens() + 7) / 8 * 8; }
@@ -49,6 +59,7 @@ constexpr double LOG2E = 1.4426950408889634;
 struct BertRun {
   int *ids = nullptr, *len = nullptr, *pair_a = nullptr, *pair_b = nullptr;
   float *h = nullptr, *y = nullptr, *emb = nullptr, *cos = nullptr;
+  float *qg = nullptr, *logits = nullptr, *scores = nullptr;      // [B][D] the global queries (windowed); [B][L] each (head)
   char* gg = nullptr;      // [R][F] the gated product (geglu only)
   EncoderWs w;
 };
@@ -65,7 +76,11 @@ void berttext_carve(const mhip_berttext* m, Carver& ws, int B, int npad, int n_p
   r->y = ws.take<float>(R * D * 4);
   r->emb = ws.take<float>((size_t)B * D * 4);
   r->gg = m->geglu() ? ws.take(R * F * m->esz()) : nullptr;
-  encoder_ws_carve(ws, R, D, m->geglu() ? 2 * F : F, 0, m->esz(), &r->w);
+  r->qg = m->windowed() ? ws.take<float>((size_t)B * D * 4) : nullptr;
+  r->logits = m->has_head() ? ws.take<float>((size_t)B * m->num_labels * 4) : nullptr;
+  r->scores = m->has_head() ? ws.take<float>((size_t)B * m->num_labels * 4) : nullptr;
+  // windowed: the hidden buffer also holds k_g | v_g [R][2 D] during the attention
+  encoder_ws_carve(ws, R, D, std::max(m->geglu() ? 2 * F : F, m->windowed() ? 2 * D : (size_t)0), 0, m->esz(), &r->w);
 }
 
 bool npad_ok(int npad, int max_npad) { return npad >= 8 && npad % 8 == 0 && npad <= max_npad; }
@@ -128,9 +143,9 @@ int berttext_upload(mhip_berttext* m, const int32_t* ids, const int32_t* len, in
   return rc ? rc : mhip_stage_h2d(m->ctx, run.len, len, (size_t)B * 4);
 }
 
-// ids / len staged in run -> embeddings in run.emb.  taps (host, or null): h after the embedding kernel and after every layer,
+// ids / len staged in run -> embeddings in run.emb (want_emb), logits and scores in run.logits / run.scores (want_head).  taps (host, or null): h after the embedding kernel and after every layer,
 // [depth + 1][B][npad][D]
-int berttext_forward(mhip_berttext* m, int B, int npad, const BertRun& run, float* taps) {
+int berttext_forward(mhip_berttext* m, int B, int npad, const BertRun& run, float* taps, bool want_emb, bool want_head) {
   mhip_ctx* ctx = m->ctx;
   const mhip_berttext_config& c = m->cfg;
   const int D = c.dim, F = c.ffn, prec = m->precision;
@@ -157,8 +172,20 @@ int berttext_forward(mhip_berttext* m, int B, int npad, const BertRun& run, floa
     sd.rel_table = a.d<float>("rel");
     sd.rel_radius = m->rel_max_distance;
   }
+  AttnGlobalRowDesc gd;
+  if (m->windowed()) {      // k_g | v_g rows in w.hid
+    gd.qg = run.qg; gd.k = w.hid; gd.v = w.hid + (size_t)D * es; gd.out = w.ao; gd.len = run.len;
+    gd.ldq = D; gd.ldk = gd.ldv = 2 * D; gd.ldo = D; gd.npad = npad; gd.heads = c.heads; gd.seqs = B; gd.out_rows = npad;
+  }
   for (int i = 0; i < c.depth; ++i) {
-    if ((rc = encoder_block_attention(ctx, prec, a, i, w, sd))) return rc;
+    if (m->windowed()) {
+      if ((rc = encoder_block_qkv(ctx, prec, a, i, w, sd.a))) return rc;
+      if ((rc = mhip_gemm(ctx, prec, w.ht, a.d(enc_blk(i, "kvg_w")), (long long)R, 2 * D, D, nullptr, a.d<float>(enc_blk(i, "kvg_b")), w.hid, ACT_NONE, 0))) return rc;
+      if ((rc = mhip_launch_first_row_linear(ctx, prec, w.ht, npad, a.d(enc_blk(i, "qg_w")), a.d<float>(enc_blk(i, "qg_b")), run.qg, B, D, D))) return rc;
+      if ((rc = mhip_launch_attention_window(ctx, prec, sd, m->window[i]))) return rc;
+      gd.bias = a.d<float>(enc_blk(i, "vg_b"));
+      if ((rc = mhip_launch_attention_global_row(ctx, prec, gd))) return rc;      // row 0 of every text, over the window kernel's
+    } else if ((rc = encoder_block_attention(ctx, prec, a, i, w, sd))) return rc;
     if ((rc = mhip_gemm(ctx, prec, w.ao, a.d(enc_blk(i, "ao_w")), (long long)R, D, D, nullptr, a.d<float>(enc_blk(i, "ao_b")), run.y, ACT_NONE, 1, run.h))) return rc;
     if ((rc = mhip_launch_row_layernorm(ctx, MHIP_K_BERTTEXT_EMBED, prec, run.y, 0, nullptr, a.d<float>(enc_blk(i, "ln1_g")), a.d<float>(enc_blk(i, "ln1_b")), run.h, w.ht, (int)R, D, c.ln_eps))) return rc;
     const char* hid = w.hid;
@@ -173,7 +200,11 @@ int berttext_forward(mhip_berttext* m, int B, int npad, const BertRun& run, floa
     if ((rc = mhip_launch_row_layernorm(ctx, MHIP_K_BERTTEXT_EMBED, prec, run.y, 0, nullptr, a.d<float>(enc_blk(i, "ln2_g")), a.d<float>(enc_blk(i, "ln2_b")), run.h, w.ht, (int)R, D, c.ln_eps))) return rc;
     if ((rc = tap(i + 1))) return rc;
   }
-  return mhip_launch_berttext_pool(ctx, run.h, run.len, B, npad, D, c.pool == BT_POOL_CLS, c.normalize, run.emb);
+  // the pooled rows and the head's outputs only where the call hands them on
+  if (want_emb && (rc = mhip_launch_berttext_pool(ctx, run.h, run.len, B, npad, D, c.pool == BT_POOL_CLS, c.normalize, run.emb))) return rc;
+  if (!want_head) return MHIP_OK;
+  return mhip_launch_cls_head(ctx, run.h, npad, a.d<float>("cls_dense_w"), a.d<float>("cls_dense_b"), a.d<float>("cls_out_w"),
+                              a.d<float>("cls_out_b"), B, D, m->num_labels, m->head_function, run.logits, run.scores);
 }
 
 // block i as Hugging Face BERT holds it, "encoder.layer.N.": attention.self.{query,key,value}, attention.output.{dense,LayerNorm},
@@ -207,7 +238,9 @@ bool bert_layer_weights(mhip_ctx* ctx, const TensorStore& st, int i, int D, int 
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------- lifecycle
-extern "C" int mhip_berttext_create_ex(mhip_ctx* ctx, int precision, const mhip_berttext_config_ex* cfg, mhip_berttext** out) {
+// the one body of the create entries.  cls (or null): the windows and the head of mhip_berttext_config_cls
+static int berttext_create_impl(mhip_ctx* ctx, int precision, const mhip_berttext_config_ex* cfg, const mhip_berttext_config_cls* cls,
+                                mhip_berttext** out) {
   if (!ctx || !out || !cfg) return MHIP_EINVAL;
   *out = nullptr;
   if (precision != MHIP_PREC_F16 && precision != MHIP_PREC_F32) return mhip_fail(ctx, MHIP_EINVAL, "unknown precision %d", precision);
@@ -235,11 +268,32 @@ extern "C" int mhip_berttext_create_ex(mhip_ctx* ctx, int precision, const mhip_
     return mhip_fail(ctx, MHIP_EINVAL, "berttext: rel_buckets %d with position alibi: slopes and a relative table together", x.rel_buckets);
   if (x.rel_buckets ? (x.rel_max_distance < 1 || x.rel_max_distance > MAX_LONG_ROWS) : x.rel_max_distance != 0)
     return mhip_fail(ctx, MHIP_EINVAL, "berttext: rel_max_distance %d (1 .. %d with rel_buckets, 0 without)", x.rel_max_distance, MAX_LONG_ROWS);
+  if (cls) {
+    if (!cls->attention_window) return mhip_fail(ctx, MHIP_EINVAL, "berttext: attention_window is null");
+    for (int i = 0; i < c.depth; ++i) {
+      const int aw = cls->attention_window[i];
+      if (aw < 2 || aw % 2) return mhip_fail(ctx, MHIP_EINVAL, "berttext: attention_window %d of layer %d (even and positive)", aw, i);
+      if (aw / 2 > ATTN_WINDOW_MAX)
+        return mhip_fail(ctx, MHIP_EINVAL, "berttext: attention_window %d of layer %d: a one-sided window of %d (at most %d)", aw, i, aw / 2, ATTN_WINDOW_MAX);
+    }
+    if (cls->num_labels < 1 || cls->num_labels > CLS_HEAD_MAX_LABELS)
+      return mhip_fail(ctx, MHIP_EINVAL, "berttext: num_labels %d (1 .. %d)", cls->num_labels, CLS_HEAD_MAX_LABELS);
+    if (cls->head_function < 0 || cls->head_function > 2)
+      return mhip_fail(ctx, MHIP_EINVAL, "berttext: head_function %d (0 none, 1 softmax, 2 sigmoid)", cls->head_function);
+    if (c.dim / c.heads != 64)
+      return mhip_fail(ctx, MHIP_EINVAL, "berttext: heads %d at dim %d: a head dimension of %d, the windowed attention has heads of 64", c.heads, c.dim, c.dim / c.heads);
+    if (c.position != BT_POS_ABSOLUTE || x.rel_buckets)
+      return mhip_fail(ctx, MHIP_EINVAL, "berttext: attention_window with position alibi or rel_buckets: the windowed attention has no bias term");
+  }
   mhip_berttext* m = new mhip_berttext();
   m->ctx = ctx;
   m->precision = precision;
   m->cfg = c;
   m->pos_offset = x.pos_offset; m->rel_buckets = x.rel_buckets; m->rel_max_distance = x.rel_max_distance;
+  if (cls) {
+    for (int i = 0; i < c.depth; ++i) m->window.push_back(cls->attention_window[i] / 2);
+    m->num_labels = cls->num_labels; m->head_function = cls->head_function;
+  }
   const size_t es = m->esz(), D = c.dim;
   Arena& a = m->arena;
   a.take("word", (size_t)c.vocab * D * 4);
@@ -248,9 +302,29 @@ extern "C" int mhip_berttext_create_ex(mhip_ctx* ctx, int precision, const mhip_
   else a.take("pos", (size_t)(m->pos_offset + m->max_npad()) * D * 4);      // rows past the table (padding rows only) are zeros
   if (m->rel()) a.take("rel", (size_t)c.heads * (2 * m->rel_max_distance + 1) * 4);
   a.take("ln_emb_g", D * 4); a.take("ln_emb_b", D * 4);
-  for (int i = 0; i < c.depth; ++i) encoder_block_take(a, i, D, c.ffn, es, m->geglu());
+  for (int i = 0; i < c.depth; ++i) {
+    encoder_block_take(a, i, D, c.ffn, es, m->geglu());
+    if (m->windowed()) {      // key_global | value_global, query_global (scaled), b_vg - b_v
+      a.take(enc_blk(i, "kvg_w"), 2 * D * D * es); a.take(enc_blk(i, "kvg_b"), 2 * D * 4);
+      a.take(enc_blk(i, "qg_w"), D * D * es); a.take(enc_blk(i, "qg_b"), D * 4);
+      a.take(enc_blk(i, "vg_b"), D * 4);
+    }
+  }
+  if (m->has_head()) {      // fp32 in both modes: B rows, not a GEMM
+    a.take("cls_dense_w", D * D * 4); a.take("cls_dense_b", D * 4);
+    a.take("cls_out_w", (size_t)m->num_labels * D * 4); a.take("cls_out_b", (size_t)m->num_labels * 4);
+  }
   *out = m;
   return MHIP_OK;
+}
+
+extern "C" int mhip_berttext_create_ex(mhip_ctx* ctx, int precision, const mhip_berttext_config_ex* cfg, mhip_berttext** out) {
+  return berttext_create_impl(ctx, precision, cfg, nullptr, out);
+}
+
+extern "C" int mhip_berttext_create_cls(mhip_ctx* ctx, int precision, const mhip_berttext_config_cls* cfg, mhip_berttext** out) {
+  if (!ctx || !out || !cfg) return MHIP_EINVAL;
+  return berttext_create_impl(ctx, precision, &cfg->ex, cfg, out);
 }
 
 // the twelve fields of mhip_berttext_config alone: a token type table is required, as it always was
@@ -275,8 +349,11 @@ extern "C" int mhip_berttext_set_tensor(mhip_berttext* m, const char* key, const
   if (!m || !key) return MHIP_EINVAL;
   std::string k(key);
   if (k.rfind("bert.", 0) == 0) k = k.substr(5);
+  else if (k.rfind("longformer.", 0) == 0) k = k.substr(11);
   if (k.rfind("pooler.", 0) == 0 || k == "embeddings.position_ids") return MHIP_OK;
-  if (k.rfind("embeddings.", 0) != 0 && k.rfind("encoder.layer.", 0) != 0 && k != "encoder.relative_attention_bias.weight") return mhip_fail(m->ctx, MHIP_EINVAL, "unknown state_dict key %s", key);
+  if (k.rfind("embeddings.", 0) != 0 && k.rfind("encoder.layer.", 0) != 0 && k != "encoder.relative_attention_bias.weight" &&
+      !(m->has_head() && k.rfind("classifier.", 0) == 0))
+    return mhip_fail(m->ctx, MHIP_EINVAL, "unknown state_dict key %s", key);
   m->ready = false;
   return m->store.set(m->ctx, k, data, shape, ndim);
 }
@@ -339,6 +416,34 @@ extern "C" int mhip_berttext_finalize(mhip_berttext* m) {
     EncoderBlockWeights w;
     if (!bert_layer_weights(ctx, st, i, D, F, m->geglu(), &w)) return MHIP_ESTATE;
     encoder_block_fill(a, prec, i, D, F, w, scale);
+    if (m->windowed()) {
+      const std::string p = "encoder.layer." + std::to_string(i) + ".attention.self.";
+      const HostTensor *wq = st.find(ctx, p + "query_global.weight", {D, D}), *bq = wq ? st.find(ctx, p + "query_global.bias", {D}) : nullptr;
+      const HostTensor *wk = bq ? st.find(ctx, p + "key_global.weight", {D, D}) : nullptr, *bk = wk ? st.find(ctx, p + "key_global.bias", {D}) : nullptr;
+      const HostTensor *wv = bk ? st.find(ctx, p + "value_global.weight", {D, D}) : nullptr, *bv = wv ? st.find(ctx, p + "value_global.bias", {D}) : nullptr;
+      if (!bv) return MHIP_ESTATE;
+      const size_t es = m->esz(), DD = (size_t)D * D;
+      std::vector<float> sq(DD);
+      for (size_t e = 0; e < DD; ++e) sq[e] = wq->data[e] * scale;
+      Arena::put(prec, a.h(enc_blk(i, "qg_w")), sq.data(), DD);
+      Arena::put(prec, a.h(enc_blk(i, "kvg_w")), wk->data.data(), DD);
+      Arena::put(prec, a.h(enc_blk(i, "kvg_w")) + DD * es, wv->data.data(), DD);
+      float *qb = (float*)a.h(enc_blk(i, "qg_b")), *kvb = (float*)a.h(enc_blk(i, "kvg_b")), *vb = (float*)a.h(enc_blk(i, "vg_b"));
+      for (int d = 0; d < D; ++d) {
+        qb[d] = bq->data[d] * scale;
+        kvb[d] = bk->data[d];
+        kvb[D + d] = 0.f;
+        vb[d] = bv->data[d] - (w.bv ? w.bv[d] : 0.f);      // the output projection's folded bias adds W_o b_v to every row
+      }
+    }
+  }
+  if (m->has_head()) {
+    const HostTensor *dw = st.find(ctx, "classifier.dense.weight", {D, D}), *db = dw ? st.find(ctx, "classifier.dense.bias", {D}) : nullptr;
+    const HostTensor *ow = db ? st.find(ctx, "classifier.out_proj.weight", {m->num_labels, D}) : nullptr;
+    const HostTensor* ob = ow ? st.find(ctx, "classifier.out_proj.bias", {m->num_labels}) : nullptr;
+    if (!ob) return MHIP_ESTATE;
+    memcpy(a.h("cls_dense_w"), dw->data.data(), dw->numel() * 4); memcpy(a.h("cls_dense_b"), db->data.data(), (size_t)D * 4);
+    memcpy(a.h("cls_out_w"), ow->data.data(), ow->numel() * 4); memcpy(a.h("cls_out_b"), ob->data.data(), (size_t)m->num_labels * 4);
   }
   int rc = a.upload(ctx);
   if (rc) return rc;
@@ -370,8 +475,10 @@ extern "C" int mhip_berttext_rel_table(int buckets, int max_distance, const floa
 // ---------------------------------------------------------------------------------------------------- forward
 // the one body of the three entries: cosines with n_pairs > 0, taps with taps_out
 static int berttext_run(mhip_berttext* m, const int32_t* ids, const int32_t* len, int B, int npad, const int32_t* pair_a,
-                        const int32_t* pair_b, int n_pairs, float* cos_out, float* taps_out, float* emb_out) {
+                        const int32_t* pair_b, int n_pairs, float* cos_out, float* taps_out, float* emb_out, float* logits_out = nullptr,
+                        float* scores_out = nullptr) {
   mhip_ctx* ctx = m->ctx;
+  if ((logits_out || scores_out) && !m->has_head()) return mhip_fail(ctx, MHIP_ESTATE, "berttext: the handle has no classification head");
   int rc = berttext_check_call(m, ids, len, B, npad);
   if (rc) return rc;
   if (cos_out) {
@@ -388,12 +495,14 @@ static int berttext_run(mhip_berttext* m, const int32_t* ids, const int32_t* len
     if ((rc = mhip_stage_h2d(ctx, run.pair_a, pair_a, (size_t)n_pairs * 4))) return rc;
     if ((rc = mhip_stage_h2d(ctx, run.pair_b, pair_b, (size_t)n_pairs * 4))) return rc;
   }
-  if ((rc = berttext_forward(m, B, npad, run, taps_out))) return rc;
+  if ((rc = berttext_forward(m, B, npad, run, taps_out, emb_out || cos_out, logits_out || scores_out))) return rc;
   if (cos_out) {
     if ((rc = mhip_launch_pair_cosine(ctx, run.emb, m->cfg.dim, run.pair_a, run.pair_b, n_pairs, run.cos))) return rc;
     MHIP_HIP(ctx, hipMemcpyAsync(cos_out, run.cos, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, ctx->stream));
   }
   if (emb_out) MHIP_HIP(ctx, hipMemcpyAsync(emb_out, run.emb, (size_t)B * m->cfg.dim * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (logits_out) MHIP_HIP(ctx, hipMemcpyAsync(logits_out, run.logits, (size_t)B * m->num_labels * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (scores_out) MHIP_HIP(ctx, hipMemcpyAsync(scores_out, run.scores, (size_t)B * m->num_labels * 4, hipMemcpyDeviceToHost, ctx->stream));
   MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return MHIP_OK;
 }
@@ -413,6 +522,12 @@ extern "C" int mhip_berttext_debug_taps_host(mhip_berttext* m, const int32_t* id
                                              float* emb_out) {
   if (!m || !taps_out) return MHIP_EINVAL;
   return berttext_run(m, ids, len, B, npad, nullptr, nullptr, 0, nullptr, taps_out, emb_out);
+}
+
+extern "C" int mhip_berttext_classify_host(mhip_berttext* m, const int32_t* ids, const int32_t* len, int B, int npad, float* logits_out,
+                                           float* scores_out) {
+  if (!m || !logits_out || !scores_out) return MHIP_EINVAL;
+  return berttext_run(m, ids, len, B, npad, nullptr, nullptr, 0, nullptr, nullptr, nullptr, logits_out, scores_out);
 }
 
 // ---------------------------------------------------------------------------------------------------- the kernels alone
@@ -460,10 +575,11 @@ extern "C" int mhip_berttext_embed_rows_ex_host(mhip_ctx* ctx, const float* word
   return berttext_embed_rows_run(ctx, word, type0, pos, g, b, eps, ids, B, npad, vocab, D, pos_offset, h_out);
 }
 
-// the one body of the two attention entries: attn_short (npad <= 128) or, streamed, attn_long (npad <= 8192)
+// the one body of the attention entries: attn_short (npad <= 128), streamed, attn_long (npad <= 8192), or with a one-sided
+// window w > 0, attn_window (head_dim 64, no bias term)
 static int berttext_attention_run(mhip_ctx* ctx, int precision, const float* q, const float* k, const float* v, const int32_t* len,
                                   const float* slopes, const float* table, int radius, int B, int heads, int head_dim, int npad, float* out,
-                                  bool streamed) {
+                                  bool streamed, int w = 0) {
   if (!ctx || !q || !k || !v || !len || !out) return MHIP_EINVAL;
   if (precision != MHIP_PREC_F16 && precision != MHIP_PREC_F32) return mhip_fail(ctx, MHIP_EINVAL, "unknown precision %d", precision);
   if (head_dim != 64 && head_dim != 32) return mhip_fail(ctx, MHIP_EINVAL, "berttext_attention: head_dim %d (64 or 32)", head_dim);
@@ -494,6 +610,7 @@ static int berttext_attention_run(mhip_ctx* ctx, int precision, const float* q, 
         AttnShortDesc sd;
         sd.a = ad; sd.len = dlen; sd.slopes = slopes ? dsl : nullptr; sd.head_dim = head_dim;
         sd.rel_table = tn ? dtab : nullptr; sd.rel_radius = tn ? radius : 0;
+        if (w) return mhip_launch_attention_window(ctx, precision, sd, w);
         return streamed ? mhip_launch_attention_long(ctx, precision, sd) : mhip_launch_attention_short(ctx, precision, sd);
       });
 }
@@ -519,6 +636,78 @@ extern "C" int mhip_berttext_attention_rel_long_host(mhip_ctx* ctx, int precisio
                                                      const int32_t* len, const float* table, int radius, int B, int heads, int head_dim,
                                                      int npad, float* out) {
   return berttext_attention_run(ctx, precision, q, k, v, len, nullptr, table, radius, B, heads, head_dim, npad, out, true);
+}
+
+extern "C" int mhip_berttext_attention_window_host(mhip_ctx* ctx, int precision, const float* q, const float* k, const float* v,
+                                                   const int32_t* len, int w, int B, int heads, int head_dim, int npad, float* out) {
+  if (!ctx) return MHIP_EINVAL;
+  if (head_dim != 64) return mhip_fail(ctx, MHIP_EINVAL, "berttext_attention_window: head_dim %d (64)", head_dim);
+  if (w < 1 || w > ATTN_WINDOW_MAX) return mhip_fail(ctx, MHIP_EINVAL, "berttext_attention_window: w %d (one-sided, 1 .. %d)", w, ATTN_WINDOW_MAX);
+  return berttext_attention_run(ctx, precision, q, k, v, len, nullptr, nullptr, 0, B, heads, head_dim, npad, out, true, w);
+}
+
+extern "C" int mhip_berttext_attention_global_host(mhip_ctx* ctx, int precision, const float* qg, const float* kg, const float* vg,
+                                                   const int32_t* len, int B, int heads, int npad, float* out) {
+  if (!ctx || !qg || !kg || !vg || !len || !out) return MHIP_EINVAL;
+  if (precision != MHIP_PREC_F16 && precision != MHIP_PREC_F32) return mhip_fail(ctx, MHIP_EINVAL, "unknown precision %d", precision);
+  if (B < 1 || B > MAX_TEXTS || heads < 1 || heads > 32 || !npad_ok(npad, MAX_LONG_ROWS) || (long long)B * npad > MAX_CALL_ROWS)
+    return mhip_fail(ctx, MHIP_EINVAL, "berttext_attention_global: B=%d heads=%d npad=%d", B, heads, npad);
+  for (int b = 0; b < B; ++b)
+    if (len[b] < 1 || len[b] > npad) return mhip_fail(ctx, MHIP_EINVAL, "berttext_attention_global: sequence %d has %d keys (1 .. %d)", b, len[b], npad);
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t es = precision == MHIP_PREC_F16 ? 2 : 4, D = (size_t)heads * 64, R = (size_t)B * npad;
+  char *dk = nullptr, *dv = nullptr, *dr = nullptr;
+  float *dq = nullptr, *dout = nullptr;
+  int* dlen = nullptr;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
+    dk = ws.take(R * D * es); dv = ws.take(R * D * es); dr = ws.take((size_t)B * D * es); dq = ws.take<float>((size_t)B * D * 4);
+    dout = ws.take<float>((size_t)B * D * 4); dlen = ws.take<int>((size_t)B * 4);
+  });
+  if (rc) return rc;
+  std::vector<char> kt(R * D * es), vt(R * D * es);
+  Arena::put(precision, kt.data(), kg, R * D);
+  Arena::put(precision, vt.data(), vg, R * D);
+  MHIP_HIP(ctx, hipMemcpyAsync(dk, kt.data(), kt.size(), hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(dv, vt.data(), vt.size(), hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(dq, qg, (size_t)B * D * 4, hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(dlen, len, (size_t)B * 4, hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));      // kt, vt are host temporaries in pageable memory
+  AttnGlobalRowDesc gd;
+  gd.qg = dq; gd.k = dk; gd.v = dv; gd.out = dr; gd.len = dlen;
+  gd.ldq = gd.ldk = gd.ldv = gd.ldo = (int)D; gd.npad = npad; gd.heads = heads; gd.seqs = B; gd.out_rows = 1;
+  if ((rc = mhip_launch_attention_global_row(ctx, precision, gd))) return rc;
+  if ((rc = mhip_launch_convert_rows(ctx, precision, dr, dout, B, (int)D))) return rc;
+  MHIP_HIP(ctx, hipMemcpyAsync(out, dout, (size_t)B * D * 4, hipMemcpyDeviceToHost, ctx->stream));
+  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return MHIP_OK;
+}
+
+extern "C" int mhip_berttext_cls_head_host(mhip_ctx* ctx, const float* h0, const float* dense_w, const float* dense_b, const float* out_w,
+                                           const float* out_b, int B, int D, int L, int function, float* logits_out, float* scores_out) {
+  if (!ctx || !h0 || !dense_w || !dense_b || !out_w || !out_b || !logits_out || !scores_out) return MHIP_EINVAL;
+  if (B < 1 || B > MAX_TEXTS || D < 64 || D % 64 || D > 1024 || L < 1 || L > CLS_HEAD_MAX_LABELS || function < 0 || function > 2)
+    return mhip_fail(ctx, MHIP_EINVAL, "berttext_cls_head: B=%d D=%d L=%d function=%d", B, D, L, function);
+  MHIP_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t uD = D, uL = L;
+  float *dh = nullptr, *dw = nullptr, *db = nullptr, *ow = nullptr, *ob = nullptr, *dl = nullptr, *ds = nullptr;
+  int rc = mhip_carve_workspace(ctx, [&](Carver& ws) {
+    dh = ws.take<float>(B * uD * 4); dw = ws.take<float>(uD * uD * 4); db = ws.take<float>(uD * 4); ow = ws.take<float>(uL * uD * 4);
+    ob = ws.take<float>(uL * 4); dl = ws.take<float>(B * uL * 4); ds = ws.take<float>(B * uL * 4);
+  });
+  if (rc) return rc;
+  MHIP_HIP(ctx, hipMemcpyAsync(dh, h0, B * uD * 4, hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(dw, dense_w, uD * uD * 4, hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(db, dense_b, uD * 4, hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(ow, out_w, uL * uD * 4, hipMemcpyHostToDevice, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(ob, out_b, uL * 4, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = mhip_launch_cls_head(ctx, dh, 1, dw, db, ow, ob, B, D, L, function, dl, ds))) {
+    (void)hipStreamSynchronize(ctx->stream);      // the copies from the caller's memory do not outlive the call
+    return rc;
+  }
+  MHIP_HIP(ctx, hipMemcpyAsync(logits_out, dl, B * uL * 4, hipMemcpyDeviceToHost, ctx->stream));
+  MHIP_HIP(ctx, hipMemcpyAsync(scores_out, ds, B * uL * 4, hipMemcpyDeviceToHost, ctx->stream));
+  MHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return MHIP_OK;
 }
 
 extern "C" int mhip_berttext_geglu_host(mhip_ctx* ctx, int precision, const float* x, int R, int F, float* out) {

@@ -83,7 +83,105 @@ __global__ __launch_bounds__(256) void berttext_pool_kernel(const float* __restr
   if (c < D) *(float4v*)(emb + (size_t)b * D + c) = acc;
 }
 
+// ------------------------------------------------------------------------------------------------------- the global token's query
+// out[b][o] = bias[o] + sum_k x[b * x_rows][k] w[o][k]: a wave per output, 16 bytes a lane and step, fp32 sums
+template <typename T>
+__global__ __launch_bounds__(256) void first_row_linear_kernel(const T* __restrict__ x, long long x_rows, const T* __restrict__ w,
+                                                               const float* __restrict__ bias, float* __restrict__ out, int N, int K) {
+  constexpr int V = 16 / sizeof(T);
+  const int b = blockIdx.y, o = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (o >= N) return;
+  const T* xr = x + (size_t)b * x_rows * K;
+  const T* wr = w + (size_t)o * K;
+  float acc = 0.f;
+  for (int k = lane * V; k < K; k += 64 * V) {
+    const uint4v rx = *(const uint4v*)(xr + k), rw = *(const uint4v*)(wr + k);
+    const T* xv = (const T*)&rx;
+    const T* wv = (const T*)&rw;
+#pragma unroll
+    for (int j = 0; j < V; ++j) acc += (float)xv[j] * (float)wv[j];
+  }
+  acc = wave_sum(acc);
+  if (lane == 0) out[(size_t)b * N + o] = acc + (bias ? bias[o] : 0.f);
+}
+
+// ------------------------------------------------------------------------------------------------------- classification head
+// One workgroup a text: x = h[b * h_rows] -> y = tanh(dense_w x + dense_b) -> logits = out_w y + out_b -> scores.  A wave per
+// output, a float4 a lane and step; the soft-max's maximum and sum are taken by every thread over the L logits in LDS, in order
+__global__ __launch_bounds__(256) void cls_head_kernel(const float* __restrict__ h, long long h_rows, const float* __restrict__ dense_w,
+                                                       const float* __restrict__ dense_b, const float* __restrict__ out_w,
+                                                       const float* __restrict__ out_b, int D, int L, int function,
+                                                       float* __restrict__ logits, float* __restrict__ scores) {
+  __shared__ __attribute__((aligned(16))) float xs[1024];
+  __shared__ __attribute__((aligned(16))) float ys[1024];
+  __shared__ float ls[CLS_HEAD_MAX_LABELS];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* x = h + (size_t)b * h_rows * D;
+  for (int c = tid; c < D; c += 256) xs[c] = x[c];
+  __syncthreads();
+  for (int o = wave; o < D; o += 4) {
+    const float* wr = dense_w + (size_t)o * D;
+    float acc = 0.f;
+    for (int k = lane * 4; k < D; k += 256) {
+      const float4v a = *(const float4v*)(wr + k), v = *(const float4v*)(xs + k);
+      acc += (a[0] * v[0] + a[1] * v[1]) + (a[2] * v[2] + a[3] * v[3]);
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) ys[o] = tanhf(acc + dense_b[o]);
+  }
+  __syncthreads();
+  for (int o = wave; o < L; o += 4) {
+    const float* wr = out_w + (size_t)o * D;
+    float acc = 0.f;
+    for (int k = lane * 4; k < D; k += 256) {
+      const float4v a = *(const float4v*)(wr + k), v = *(const float4v*)(ys + k);
+      acc += (a[0] * v[0] + a[1] * v[1]) + (a[2] * v[2] + a[3] * v[3]);
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) ls[o] = acc + out_b[o];
+  }
+  __syncthreads();
+  float mx = 0.f, inv = 1.f;
+  if (function == 1) {
+    mx = -INFINITY;
+    for (int o = 0; o < L; ++o) mx = fmaxf(mx, ls[o]);
+    float sum = 0.f;
+    for (int o = 0; o < L; ++o) sum += expf(ls[o] - mx);
+    inv = 1.f / sum;
+  }
+  for (int o = tid; o < L; o += 256) {
+    const float z = ls[o];
+    logits[(size_t)b * L + o] = z;
+    scores[(size_t)b * L + o] = function == 1 ? expf(z - mx) * inv : function == 2 ? 1.f / (1.f + expf(-z)) : z;
+  }
+}
+
 }  // namespace
+
+int mhip_launch_first_row_linear(mhip_ctx* ctx, int precision, const void* x, long long x_rows, const void* w, const float* bias, float* out,
+                                 int B, int N, int K) {
+  if (!x || !w || !out || B <= 0 || B > 65535 || N <= 0 || K < 8 || K % 8 || x_rows < 1 || ((uintptr_t)x & 15) || ((uintptr_t)w & 15))
+    return mhip_fail(ctx, MHIP_EINVAL, "first_row_linear: B=%d N=%d K=%d (K a multiple of 8, 16-byte rows)", B, N, K);
+  dim3 grid((N + 3) / 4, B), block(256);
+  if (precision == MHIP_PREC_F16)
+    PROF_LAUNCH(ctx, MHIP_K_BERTTEXT_POOL, hipLaunchKernelGGL(first_row_linear_kernel<_Float16>, grid, block, 0, ctx->stream, (const _Float16*)x, x_rows, (const _Float16*)w, bias, out, N, K));
+  else
+    PROF_LAUNCH(ctx, MHIP_K_BERTTEXT_POOL, hipLaunchKernelGGL(first_row_linear_kernel<float>, grid, block, 0, ctx->stream, (const float*)x, x_rows, (const float*)w, bias, out, N, K));
+  CHECK_LAUNCH(ctx, "first_row_linear");
+  return 0;
+}
+
+int mhip_launch_cls_head(mhip_ctx* ctx, const float* h, long long h_rows, const float* dense_w, const float* dense_b, const float* out_w,
+                         const float* out_b, int B, int D, int L, int function, float* logits, float* scores) {
+  if (!h || !dense_w || !dense_b || !out_w || !out_b || !logits || !scores || B <= 0 || D < 4 || D % 4 || D > 1024 || L < 1 ||
+      L > CLS_HEAD_MAX_LABELS || h_rows < 1 || function < 0 || function > 2)
+    return mhip_fail(ctx, MHIP_EINVAL, "cls_head: B=%d D=%d L=%d function=%d (D a multiple of 4 up to 1024, L up to %d, function 0 .. 2)", B, D, L,
+                     function, CLS_HEAD_MAX_LABELS);
+  // counted with the pooling: the profiler's list is pinned, and both are the call's last kernel over B rows
+  PROF_LAUNCH(ctx, MHIP_K_BERTTEXT_POOL, hipLaunchKernelGGL(cls_head_kernel, dim3(B), dim3(256), 0, ctx->stream, h, h_rows, dense_w, dense_b, out_w, out_b, D, L, function, logits, scores));
+  CHECK_LAUNCH(ctx, "cls_head");
+  return 0;
+}
 
 int mhip_launch_berttext_embed(mhip_ctx* ctx, int precision, const float* word, const float* type0, const float* pos, const float* g,
                                const float* b, float eps, const int* ids, float* h, void* ht, int B, int npad, int D, int pos_offset) {

@@ -663,6 +663,26 @@ int mhip_launch_attention_short(mhip_ctx* ctx, int precision, const AttnShortDes
 // queries); a sequence's key walk is a function of len[b] alone, every row < npad is written (query blocks that start at or past
 // len[b] as zeros), nothing past a sequence's rows is read (no slack needed).  Counted in MHIP_K_ATTN_SHORT
 int mhip_launch_attention_long(mhip_ctx* ctx, int precision, const AttnShortDesc& d);
+// Longformer's attention of the local queries over the same layout (head_dim 64, no bias term): query i of sequence b sees key 0
+// (the global token, once) and the keys max(1, i - w) .. min(len[b] - 1, i + w), w the one-sided window, 1 .. ATTN_WINDOW_MAX.  One
+// workgroup per (sequence, head, 64 queries) that stages only the keys of its band; every row < npad is written (row 0 and the
+// rows >= len[b] finite values nobody reads), nothing past a sequence's rows is read.  Counted in MHIP_K_ATTN_SHORT
+constexpr int ATTN_WINDOW_MAX = 512;
+int mhip_launch_attention_window(mhip_ctx* ctx, int precision, const AttnShortDesc& d, int w);
+// Longformer's attention of the global token: out row b * out_rows = softmax(q_g[b] . k_g[b][j], j < len[b]) v_g[b] + bias, per head
+// of 64 columns.  q_g fp32 in the log2 units of the other entries, k / v rows of the precision's element type (k: 16-byte rows),
+// bias fp32 [heads * 64] or null.  One workgroup per (sequence, head), online soft-max in fp32.  Counted in MHIP_K_ATTN_SHORT
+struct AttnGlobalRowDesc {
+  const float* qg = nullptr;      // [seqs][ldq]
+  const void* k = nullptr;        // [seqs * npad][ldk]
+  const void* v = nullptr;        // [seqs * npad][ldv]
+  const float* bias = nullptr;
+  void* out = nullptr;            // [..][ldo]
+  const int* len = nullptr;       // device, 1 .. npad
+  int ldq = 0, ldk = 0, ldv = 0, ldo = 0, npad = 0, heads = 0, seqs = 0;
+  long long out_rows = 1;
+};
+int mhip_launch_attention_global_row(mhip_ctx* ctx, int precision, const AttnGlobalRowDesc& d);
 // ------------------------------------------------------------------ BERT sentence encoder ops (berttext_ops.hip)
 // h [B*npad][D] fp32 = LN((word[ids[row]] + type0) + pos[pos_offset + row % npad]), ht (null: not written) its copy in the
 // precision's element type; word [vocab][D], type0 [D] or null (no token types), pos [>= pos_offset + npad][D] or null (no position
@@ -673,6 +693,16 @@ int mhip_launch_berttext_embed(mhip_ctx* ctx, int precision, const float* word, 
 int mhip_launch_geglu(mhip_ctx* ctx, int precision, const void* x, void* out, long long R, int F);
 // emb [B][D] fp32: the mean of rows < len[b] of h [B][npad][D] (cls: row 0; len may be null), divided by max(norm, 1e-12) with normalize
 int mhip_launch_berttext_pool(mhip_ctx* ctx, const float* h, const int* len, int B, int npad, int D, int cls, int normalize, float* emb);
+// out [B][N] fp32 = bias + x W^T over row b * x_rows of x [..][K] (the precision's element type), W [N][K] of the same type: the
+// global token's query projection, a wave per output.  K % 8 == 0, 16-byte rows
+int mhip_launch_first_row_linear(mhip_ctx* ctx, int precision, const void* x, long long x_rows, const void* w, const float* bias, float* out,
+                                 int B, int N, int K);
+// the classification head on row b * h_rows of the fp32 stream h [..][D]: logits [B][L] = out_w tanh(dense_w h + dense_b) + out_b,
+// scores [B][L] = the logits (function 0), their soft-max (1) or their sigmoid (2).  fp32 weights and arithmetic, one launch, one
+// workgroup a text.  D % 4 == 0, D <= 1024, L <= CLS_HEAD_MAX_LABELS
+constexpr int CLS_HEAD_MAX_LABELS = 1024;
+int mhip_launch_cls_head(mhip_ctx* ctx, const float* h, long long h_rows, const float* dense_w, const float* dense_b, const float* out_w,
+                         const float* out_b, int B, int D, int L, int function, float* logits, float* scores);
 // ------------------------------------------------------------------ LayoutReader ops (layoutreader_ops.hip)
 // A row of the layout-only embedding is 8 ints in HBM: x0, y0, x1, y1, position id, type id, two spare.
 constexpr int LR_TOK_INTS = 8;

@@ -10,8 +10,8 @@ the host, here, without the transformers library: RoBERTa byte-level BPE from ``
 ``boxes`` are what ``get_words_and_boxes`` (renderer.py) returns for a page.
 
 Unlike the reference, whose "batch" loops page by page, the pages of a batch go through one model call.  There is no CPU path:
-``use_gpu=False`` raises.  The ``text-classification`` and ``zero-shot-classification`` tasks (text-only pipelines of other
-model families) are not part of this project.
+``use_gpu=False`` raises.  ``task="text-classification"`` runs a Longformer over the page's words alone (``text_classifier.py``);
+other model families under that task, and ``zero-shot-classification``, are not part of this project.
 """
 from __future__ import annotations
 
@@ -455,16 +455,85 @@ class LayoutLMv3PagePredictor:
 
 
 class TransformersDocumentClassifier(LayoutLMv3PagePredictor):
-    """marie/components/document_classifier/transformers.py:41-361 for ``task="text-classification-multimodal"``; the
-    arguments as on :class:`LayoutLMv3PagePredictor`."""
+    """marie/components/document_classifier/transformers.py:41-361 for ``task="text-classification-multimodal"`` (LayoutLMv3 over
+    the page image, words and boxes) and ``task="text-classification"`` (a Longformer over ``" ".join(words)``:
+    ``text_classifier.py``); the arguments as on :class:`LayoutLMv3PagePredictor`.  With the text task ``id2label`` renames the
+    model's labels as the reference does (``LABEL_n`` -> ``id2label[n]``; labels of another form by their index), and ``boxes`` and
+    the page images are accepted and unused."""
 
     def __init__(self, model_name_or_path: str, tokenizer: Optional[str] = None, use_gpu: bool = True, top_k: int = 1,
                  task: str = "text-classification-multimodal", batch_size: int = 16, id2label: Optional[dict] = None, *,
                  state: Optional[Dict[str, np.ndarray]] = None, config: Optional[dict] = None, precision: str = "f16",
                  ctx: Optional[Context] = None, **kwargs):
-        if task in ("text-classification", "zero-shot-classification"):
-            raise NotImplementedError(f"task {task!r}: only 'text-classification-multimodal' (LayoutLMv3) is built")
-        if task != "text-classification-multimodal":
+        if task == "zero-shot-classification":
+            raise NotImplementedError(f"task {task!r}: the reference's own predict raises for it; not built")
+        if task not in ("text-classification-multimodal", "text-classification"):
             raise ValueError(f"unknown task {task!r}")
         self.task, self.top_k = task, int(top_k)
-        self._setup(model_name_or_path, tokenizer, use_gpu, batch_size, id2label, state, config, precision, ctx)
+        if task == "text-classification":
+            self._setup_text(model_name_or_path, tokenizer, use_gpu, batch_size, id2label, state, config, precision, ctx)
+        else:
+            self._setup(model_name_or_path, tokenizer, use_gpu, batch_size, id2label, state, config, precision, ctx)
+
+    # ---- task="text-classification" ---------------------------------------------------------------------------
+    def _setup_text(self, model_name_or_path, tokenizer, use_gpu, batch_size, id2label, state, config, precision, ctx):
+        if not use_gpu:
+            raise MarieHipError(f"{type(self).__name__} runs on the GPU only: there is no CPU path in this project")
+        if not os.path.isdir(model_name_or_path):
+            raise FileNotFoundError(f"model directory {model_name_or_path!r} does not exist (models are local directories)")
+        if config is None:
+            with open(os.path.join(model_name_or_path, "config.json"), encoding="utf-8") as f:
+                config = json.load(f)
+        model_type = config.get("model_type")
+        if model_type != "longformer":
+            raise NotImplementedError(f"task 'text-classification' with model_type {model_type!r}: only 'longformer' is built")
+        self.batch_size = int(batch_size)
+        self.model_dir = model_name_or_path
+        self.hf_config = dict(config)
+        self.text_model = self._open_text_model(model_name_or_path, tokenizer, state, self.hf_config, precision, ctx)
+        self.tokenizer, self.ctx = self.text_model.tokenizer, getattr(self.text_model, "ctx", None)
+        self.given_id2label = None if id2label is None else {int(k): v for k, v in id2label.items()}
+        self.id2label = self.given_id2label if self.given_id2label is not None else dict(self.text_model.id2label)
+
+    def _open_text_model(self, model_dir, tokenizer, state, config, precision, ctx):
+        from .text_classifier import LongformerTextClassifier
+
+        return LongformerTextClassifier(model_dir, tokenizer, state=state, config=config, precision=precision, ctx=ctx)
+
+    def _label(self, label: str) -> str:
+        """transformers.py:247-250: ``id2label[int(label.split("_")[1])]``; a label of another form goes by its index"""
+        if self.given_id2label is None:
+            return label
+        parts = label.split("_")
+        if len(parts) == 2 and parts[0] == "LABEL" and parts[1].isdigit():
+            return self.given_id2label[int(parts[1])]
+        index = {v: k for k, v in self.text_model.id2label.items()}
+        return self.given_id2label[index[label]]
+
+    def predict_texts(self, texts: Sequence[str], batch_size: Optional[int] = None) -> List[List[Dict[str, Any]]]:
+        """per text its own ``top_k`` entries, whatever the batch size (the reference concatenates the entries of a batch)"""
+        results = self.text_model(list(texts), top_k=self.top_k, truncation=True, batch_size=batch_size or self.batch_size)
+        return [[{"label": self._label(el["label"]), "score": el["score"]} for el in page] for page in results]
+
+    def predict(self, documents, words: Optional[List[List[str]]] = None, boxes: Optional[List[List[List[int]]]] = None,
+                batch_size: Optional[int] = None):
+        if self.task != "text-classification":
+            return super().predict(documents, words, boxes, batch_size)
+        if len(documents) == 0:
+            return documents
+        assert words is not None, "words must be provided for text classification"
+        assert len(documents) == len(words), "documents and words must have the same length"
+        predictions = self.predict_texts([" ".join(str(w) for w in page) for page in words], batch_size)
+        formatted = [{"label": p[0]["label"], "score": p[0]["score"], "details": {el["label"]: el["score"] for el in p}}
+                     for p in predictions]
+        if not hasattr(documents[0], "tags"):
+            return formatted
+        for document, f in zip(documents, formatted):
+            document.tags[self.TAG] = f
+        return documents
+
+    def close(self):
+        t = getattr(self, "text_model", None)
+        if t is not None:
+            t.close()
+        super().close()
